@@ -21,10 +21,20 @@ streamed pixels.
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --slide 40000 --steps 200         # the north-star slide (31 684 tiles; ranks walk disjoint shards)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy files
+    python bench.py --full                            # + roofline, stage pass, side lines and CPU baseline
 
-Besides the headline the line carries ``roofline`` (dominant kernel + per-stage table; the post-processing stage is timed
-repetition by repetition with device AND host clocks), ``cpu_baseline`` (oracle worker processes sized by the cores / cgroup CPU quota the host grants) and, at N = 1, ``side_lines``: the same pipeline with ``--precision fp32`` and with the network's own
-(random-weight) fields driving the dynamics instead of the injected ones (SURVEY 8d asks for both modes).
+A plain run sets up, warms up, times the steps and prints the headline line (tiles/s, ms_per_step, cells/s).  With
+``--full`` the line also carries ``roofline`` (dominant kernel timed inside the timed steps + per-stage table; the
+post-processing stage is timed repetition by repetition with device AND host clocks), ``cpu_baseline`` (oracle worker
+processes sized by the cores / cgroup CPU quota the host grants) and, at N = 1, ``side_lines``: the same pipeline with
+``--precision fp32`` and with the network's own (random-weight) fields driving the dynamics instead of the injected ones
+(SURVEY 8d asks for both modes); the ``--no-*`` options switch single parts of that off.
+
+``--dump-outputs DIR`` writes what the timed path returned for its LAST timed step (rank 0) after the clock stops, as
+float32 / float64 ``DIR/<name>.npy``: ``masks``, ``class_masks``, ``nlabels``, ``dP``, ``cellprob``, ``logits`` (the
+``TileOutputs`` fields) and ``records`` (the per-cell records, one row per cell sorted by (tile, label), columns in
+``RECORD_FIELDS`` order).  Inputs are seeded, so two runs with the same arguments see identical inputs.
 """
 from __future__ import annotations
 
@@ -58,6 +68,8 @@ FLOPS = {"fc1": lambda M: 2.0 * M * 4096 * 1024, "fc2": lambda M: 2.0 * M * 4096
          "qkv": lambda M: 2.0 * M * 3072 * 1024, "proj": lambda M: 2.0 * M * 1024 * 1024,
          "attention": lambda M: (M / 1024) * (4.0 * 1024 * 1024 * 64 * 16 + 4.0 * 16 * 1024 * 32 * 64)}
 POST_BYTES_PER_TILE = 524288 + 262144 + NCLS * 262144 + 131072 + 65536      # dP + cellprob + logits in, ids + classes out
+DUMP_BYTES_MAX = 64 * 10**6                                   # --dump-outputs writes at most this much (the batch's first tiles that fit)
+RECORD_FIELDS = ("tile", "label", "cls", "area", "y0", "x0", "y1", "x1", "sum_y", "sum_x")      # columns of records.npy
 
 
 class CachedSlide:
@@ -247,6 +259,30 @@ def spawn_ranks(n: int) -> int:
     return subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
 
 
+def dump_outputs(d: str, eng, out, n: int) -> list[str]:
+    """--dump-outputs: what ``Engine.result`` handed back for one batch of n tiles, as float32 / float64 .npy files under d.
+    Every array is per tile; when the n tiles do not fit DUMP_BYTES_MAX only its first tiles that do are written (the same
+    ones in every run).  Ids, classes and counts are integers below 2**24 (float32 holds them exactly), record columns go to
+    float64 (the int64 coordinate sums stay below 2**53)."""
+    from classpose_amd import ops
+    recs = eng.fetch_records(n, out)
+    recs = recs[np.lexsort((recs["label"], recs["tile"]))]
+    per_tile = {"masks": out.masks, "class_masks": out.class_masks, "nlabels": out.nlabels, "dP": out.dP, "cellprob": out.cellprob}
+    if out.logits is not None:
+        per_tile["logits"] = out.logits
+    tile_bytes = sum(t[0].numel() for t in per_tile.values()) * 4
+    k = n
+    while k > 1 and k * tile_bytes + int((recs["tile"] < k).sum()) * len(RECORD_FIELDS) * 8 > DUMP_BYTES_MAX:
+        k -= 1
+    arrays = {name: (ops.masks_to_numpy(t[:k]) if name == "masks" else t[:k].cpu().numpy()).astype(np.float32) for name, t in per_tile.items()}
+    recs = recs[recs["tile"] < k]
+    arrays["records"] = np.stack([recs[f].astype(np.float64) for f in RECORD_FIELDS], 1).reshape(-1, len(RECORD_FIELDS))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def _mmm(v):
     v = sorted(v)
     return {"min": round(v[0], 4), "median": round(v[len(v) // 2], 4), "max": round(v[-1], 4)}
@@ -260,10 +296,13 @@ def main():
     ap.add_argument("--batch-tiles", type=int, default=8)
     ap.add_argument("--depth", type=int, default=24)
     ap.add_argument("--slide", type=int, default=10000, help="side of the synthetic slide in pixels (10000 = configs[1]; 40000 = the north-star slide)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stages", action="store_true")
-    ap.add_argument("--no-side-lines", action="store_true")
-    ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes (roofline.traffic then comes from the committed profile)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the roofline (launch profile of the timed steps, live "
+                    "rocprofv3 --pmc traffic passes), the stage pass, the side lines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-stages", action="store_true", help="with --full: skip the stage pass")
+    ap.add_argument("--no-side-lines", action="store_true", help="with --full: skip the side lines")
+    ap.add_argument("--no-live-traffic", action="store_true", help="with --full: skip the two rocprofv3 --pmc child passes (roofline.traffic then comes from the committed profile)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -313,6 +352,7 @@ def main():
     pinned = torch.empty((bt, max_cells, rec_bytes), dtype=torch.uint8).pin_memory()
     pinned_cnt = torch.empty(bt, dtype=torch.int32).pin_memory()
     rec_keep = []
+    last_out = []                             # TileOutputs of the timed run's last step (its slot is not reused before --dump-outputs reads it)
 
     def collect(e, sid, cells_acc, keep=False):
         out = e.result(sid)                                            # current stream waits for the post stream
@@ -322,6 +362,7 @@ def main():
         cells_acc.add_(out.nlabels.sum())
         if keep:
             rec_keep.append(recs.clone())
+            last_out[:] = [out]
         # ... and the host waits for them, as the CLI's tile loop does (run_rank's collect() reads the batch's label counts back before it
         # takes the next batch): one batch runs on the device while the previous one is collected, the host is never more than one
         # step ahead.  Until round 5 this loop only QUEUED the read-backs, so the host ran ~12 steps (2 500 launches, 12 fresh tile
@@ -406,53 +447,59 @@ def main():
             decode_ahead = ts.ahead
         return dt, float(cells_acc.item()), allrec
 
+    # a plain run times the steps with no event pair of its own; with --full
     # the dominant GEMM is timed on every 4th layer, the sampled layers rotating by one per step so that all 24 are
     # covered equally (BENCH_PROF_STRIDE): each event pair costs the stream ~6 us of idle time on either side of the
     # launch (tools/r02_gaps.sh: 0.28 ms per step with every launch timed = 1.1 % of the headline; stride 4: +0.3-0.5 %
     # tiles/s at the same measured launch duration; stride 8 reads ~3 % longer launches on the same box -- with fewer
     # idle gaps the chip sustains a lower clock -- DESIGN 5)
-    prof = C.c_void_p()
-    _lib.check(L.cpx_prof_create(2 * steps * args.depth + 8, int(os.environ.get("BENCH_PROF_STRIDE", "4")), 1,
-                                 C.byref(prof)), "prof_create")
+    prof = None
+    if args.full:
+        prof = C.c_void_p()
+        _lib.check(L.cpx_prof_create(2 * steps * args.depth + 8, int(os.environ.get("BENCH_PROF_STRIDE", "4")), 1,
+                                     C.byref(prof)), "prof_create")
     dt, cells, allrec = timed_run(eng, steps, args.warmup, inject=True, prof=prof, collective=True)
     dt = parallel.allreduce_max(dt, dev)
     cells = parallel.allreduce_sum(cells, dev)
-    NK = len(_lib.PROF_KINDS)
-    ms_k, cnt_k = (C.c_double * NK)(), (C.c_int * NK)()
-    _lib.check(L.cpx_prof_collect(prof, ms_k, cnt_k), "prof_collect")
-    L.cpx_prof_destroy(prof)
-    fc1_launches = int(cnt_k[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, last_out[0], bt)       # before anything else submits to the engine's slots
 
     n_tiles = steps * bt * world
     M = bt * eng.n_sub * 1024
     # mlp.lin1 / mlp.lin2 run in row parts of 16 384 tokens (cpx_net_mlp_parts): one of THEIR launches covers M / parts rows
     mlp_parts = int(L.cpx_net_mlp_parts(bt * eng.n_sub, _lib.DTYPE_CODE["bf16"]))
     M_of = lambda name: M // mlp_parts if name in ("fc1", "fc2") else M
-    avg_ms = ms_k[0] / max(cnt_k[0], 1)
-    achieved = FLOPS["fc1"](M_of("fc1")) / (avg_ms * 1e-3) / 1e12 if fc1_launches else 0.0
     flop_per_tile = 727.3e9 * eng.n_sub
-    # HBM-side bytes per launch of the dominant kernel: PMC counters cannot be read from inside this process, so rank 0 of
-    # a 1-GPU run collects them NOW through two rocprofv3 --pmc child passes over that kernel alone (measure_traffic_live);
-    # otherwise (N > 1, --no-live-traffic, rocprofv3 unavailable) the figure of the same passes over the whole bench command
-    # committed under profiles/ is reported, named with its source
-    traffic, traffic_src, traffic_detail = None, None, None
-    fallback_reason = ("not attempted: --no-live-traffic" if args.no_live_traffic else
-                       "not attempted: the live passes run on rank 0 of a 1-GPU run only" if (rank != 0 or world != 1) else None)
-    if fallback_reason is None:
-        traffic_detail, fallback_reason = measure_traffic_live()
-        if traffic_detail is not None:
-            traffic, traffic_src = traffic_detail["traffic"], "measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child passes over tools/pmc_fc1.py"
-    if traffic is None:
-        traffic_detail = {"fallback_reason": fallback_reason}
-        for name in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
-            try:
-                with open(os.path.join(ROOT, "profiles", name)) as f:
-                    traffic = json.load(f)["traffic_bytes_per_launch"]
-                traffic_src = "profiles/%s (separate rocprofv3 --pmc passes over this command)" % name
-                traffic_detail["source"] = "profiles/" + name
-                break
-            except Exception:
-                pass
+    if args.full:
+        NK = len(_lib.PROF_KINDS)
+        ms_k, cnt_k = (C.c_double * NK)(), (C.c_int * NK)()
+        _lib.check(L.cpx_prof_collect(prof, ms_k, cnt_k), "prof_collect")
+        L.cpx_prof_destroy(prof)
+        fc1_launches = int(cnt_k[0])
+        avg_ms = ms_k[0] / max(cnt_k[0], 1)
+        achieved = FLOPS["fc1"](M_of("fc1")) / (avg_ms * 1e-3) / 1e12 if fc1_launches else 0.0
+        # HBM-side bytes per launch of the dominant kernel: PMC counters cannot be read from inside this process, so rank 0 of
+        # a 1-GPU run collects them NOW through two rocprofv3 --pmc child passes over that kernel alone (measure_traffic_live);
+        # otherwise (N > 1, --no-live-traffic, rocprofv3 unavailable) the figure of the same passes over the whole bench command
+        # committed under profiles/ is reported, named with its source
+        traffic, traffic_src, traffic_detail = None, None, None
+        fallback_reason = ("not attempted: --no-live-traffic" if args.no_live_traffic else
+                           "not attempted: the live passes run on rank 0 of a 1-GPU run only" if (rank != 0 or world != 1) else None)
+        if fallback_reason is None:
+            traffic_detail, fallback_reason = measure_traffic_live()
+            if traffic_detail is not None:
+                traffic, traffic_src = traffic_detail["traffic"], "measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child passes over tools/pmc_fc1.py"
+        if traffic is None:
+            traffic_detail = {"fallback_reason": fallback_reason}
+            for name in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
+                try:
+                    with open(os.path.join(ROOT, "profiles", name)) as f:
+                        traffic = json.load(f)["traffic_bytes_per_launch"]
+                    traffic_src = "profiles/%s (separate rocprofv3 --pmc passes over this command)" % name
+                    traffic_detail["source"] = "profiles/" + name
+                    break
+                except Exception:
+                    pass
 
     # ---- per-stage roofline (after the timed region, so the extra event pairs do not touch the headline).
     # Rounds 2 and 3 reported one bogus stage each in the driver's run (post-processing 5.03 ms, proj 0.518 ms): this pass
@@ -462,7 +509,7 @@ def main():
     # the MEDIAN, min / max beside it and an `outlier` flag when max > 3 x median.
     stages = None
     kernel_time_sum = None
-    if rank == 0 and not args.no_stages:
+    if rank == 0 and args.full and not args.no_stages:
         stages = {}
         n6 = min(6, n_distinct)
         # per layer: qkv, attention, proj + one mlp.lin1 and one mlp.lin2 launch per row part (cpx_net_mlp_parts: 2 at 8 tiles per step,
@@ -513,7 +560,7 @@ def main():
 
     # ---- side lines (N = 1): --precision fp32, and the network's own fields instead of the injected ones
     side = None
-    if rank == 0 and world == 1 and not args.no_side_lines:
+    if rank == 0 and world == 1 and args.full and not args.no_side_lines:
         side = {}
         ns = min(12, n_distinct)
         dts, cs, _ = timed_run(eng, ns, 2, inject=False)
@@ -579,15 +626,16 @@ def main():
                    # (of `steps`) may already sit decoded in pinned host memory when the clock starts, as at any moment of the steady
                    # state.  Rounds 1-3 also timed their decoding (worth ~1.3 % at 20 steps, nothing over the whole slide)
                    "decode_ahead_batches_at_t0": decode_ahead, "device_resident_batches_at_t0": RESIDENT_AT_T0},
-        "roofline": {"bound": "mfma", "kernel": "%s (mlp.lin1 %dx4096x1024%s)" % (
-                         _lib.FC1_KERNEL_NAME, M_of("fc1"), "" if mlp_parts == 1 else "; the %d token rows of a step in %d launches per layer" % (M, mlp_parts)),
-                     "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic,
-                     "traffic_unit": "bytes/launch = FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE; %s" % traffic_src,
-                     "traffic_detail": traffic_detail,
-                     "algorithmic_bytes": 2.0 * (M_of("fc1") * 1024 + 4096 * 1024 + M_of("fc1") * 4096),
-                     "launches_timed": fc1_launches, "avg_launch_ms": avg_ms},
     }
+    if args.full:
+        line["roofline"] = {"bound": "mfma", "kernel": "%s (mlp.lin1 %dx4096x1024%s)" % (
+                                _lib.FC1_KERNEL_NAME, M_of("fc1"), "" if mlp_parts == 1 else "; the %d token rows of a step in %d launches per layer" % (M, mlp_parts)),
+                            "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                            "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic,
+                            "traffic_unit": "bytes/launch = FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE; %s" % traffic_src,
+                            "traffic_detail": traffic_detail,
+                            "algorithmic_bytes": 2.0 * (M_of("fc1") * 1024 + 4096 * 1024 + M_of("fc1") * 4096),
+                            "launches_timed": fc1_launches, "avg_launch_ms": avg_ms}
     if stages is not None:
         line["roofline"]["stages"] = stages
         # the five per-layer kernels at their median launch time x depth: the part of ms_per_step the network stream spends
@@ -606,7 +654,7 @@ def main():
     if side is not None:
         line["side_lines"] = side
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(S, args.depth)
         print(json.dumps(line), flush=True)
     if torch.distributed.is_initialized():

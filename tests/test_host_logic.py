@@ -324,6 +324,49 @@ def test_bench_gpus_n_without_gpus_exits_nonzero():
     assert "--gpus 2" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_writes_what_the_engine_returned(tmp_path, monkeypatch):
+    """--dump-outputs: every TileOutputs array of the batch as float32, the per-cell records as float64 rows sorted by (tile, label),
+    values unchanged; over the byte budget only the batch's first tiles are written."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    nT, H, W, ncls, max_rec = 3, 8, 8, 7, 4
+
+    class FakeEngine:
+        fetch_records = engine.Engine.fetch_records
+        _checked_counts = engine.Engine._checked_counts
+
+    eng = FakeEngine()
+    eng.nT, eng.max_rec = nT, max_rec
+    rng = np.random.default_rng(0)
+    counts = np.array([2, 0, 3], np.int32)
+    rec = np.zeros((nT, max_rec), engine.RECORD_DTYPE)
+    for t in range(nT):
+        for j in range(counts[t]):
+            rec[t, j] = (t, counts[t] - j, j % ncls, 10 + j, 0, 1, 2, 3, 2**40 + j, -j)      # labels in descending order
+    masks = rng.integers(0, 65536, (nT, H, W)).astype(np.uint16)
+    out = engine.TileOutputs(torch.from_numpy(masks.view(np.int16)), torch.from_numpy(rng.integers(0, ncls, (nT, H, W)).astype(np.uint8)),
+                             torch.from_numpy(counts.copy()), torch.randn(nT, 2, H, W), torch.randn(nT, H, W), torch.randn(nT, ncls, H, W),
+                             torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()), torch.from_numpy(counts.copy()))
+    names = bench.dump_outputs(str(tmp_path / "all"), eng, out, nT)
+    assert names == ["cellprob", "class_masks", "dP", "logits", "masks", "nlabels", "records"]
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in names}
+    assert all(a.dtype == (np.float64 if n == "records" else np.float32) for n, a in got.items())
+    assert np.array_equal(got["masks"], masks.astype(np.float32))
+    assert np.array_equal(got["dP"], out.dP.numpy()) and np.array_equal(got["logits"], out.logits.numpy())
+    assert np.array_equal(got["nlabels"], counts.astype(np.float32))
+    want = np.concatenate([np.sort(rec[t, :counts[t]], order="label") for t in range(nT)])
+    assert got["records"].shape == (5, len(bench.RECORD_FIELDS))
+    for c, f in enumerate(bench.RECORD_FIELDS):
+        assert np.array_equal(got["records"][:, c], want[f].astype(np.float64)), f
+    # a budget of two tiles: tiles 0 and 1 (and only their records) are written
+    per_tile = ((1 + 1 + 2 + 1 + ncls) * H * W + 1) * 4                # masks, classes, dP, cellprob, logits + one label count
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2 * per_tile + 2 * len(bench.RECORD_FIELDS) * 8)
+    bench.dump_outputs(str(tmp_path / "two"), eng, out, nT)
+    assert np.load(tmp_path / "two" / "dP.npy").shape == (2, 2, H, W)
+    assert np.array_equal(np.load(tmp_path / "two" / "records.npy"), got["records"][:2])
+
+
 def test_classpose_model_engine_pool_is_bounded(monkeypatch):
     """ClassposeModel hands engines out of a bounded pool per (shape, options): at most max_engines exist however many threads call, a lease
     returns its engine on exit (also when the body raises), and a failed construction gives its reservation back."""

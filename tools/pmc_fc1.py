@@ -1,6 +1,6 @@
 """The dominant kernel alone -- an mlp.lin1 launch of one 8-tile batch: (32768 / cpx_net_mlp_parts) x 4096 x 1024 (the engine runs the MLP of 32
 sub-tiles in two row parts of 16 384 tokens), folded LayerNorm + erf-GELU epilogue, random bf16 operands -- for rocprofv3 --pmc passes
-(bench.py starts it twice as a child: FETCH_SIZE, WRITE_SIZE)."""
+(bench.py --full starts it twice as a child: FETCH_SIZE, WRITE_SIZE)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,4 +1,4 @@
-"""Print the headline and the stage table of a bench.py JSON line (file argument or stdin)."""
+"""Print the headline and the stage table of a `bench.py --full` JSON line (file argument or stdin)."""
 import json, sys
 src = open(sys.argv[1]) if len(sys.argv) > 1 else sys.stdin
 d = json.loads([l for l in src if l.startswith('{"metric"')][-1])
