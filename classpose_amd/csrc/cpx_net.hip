@@ -670,7 +670,8 @@ __global__ void __launch_bounds__(A8_THREADS, 2) k_attention8(const unsigned sho
 
 
 // ---------------------------------------------------------------------------
-// flash attention, 4 waves per workgroup, LDS-DMA ring + software-pipelined S (variant 2)
+// flash attention, 4 waves per workgroup, LDS-DMA ring + software-pipelined S (variant 7; the production kernel of rounds
+// 2-5, replaced by k_attention2w of cpx_attn2w.hip)
 // ---------------------------------------------------------------------------
 // Same decomposition as k_attention (one wave = one image row of 32 queries, key tiles = image rows, rel-pos bias
 // as MFMA C operand + one scalar per lane, P^T fed to the P.V MFMA from the accumulator registers).  What differs:
@@ -999,8 +1000,9 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
 }
 
 CPX_SWITCH(g_att_xcd, 1);          // XCD-aware workgroup order
-CPX_SWITCH(g_att_v8, 2);           // 2: 4-wave kernel with the LDS-DMA ring and software-pipelined S (production); 0: the first 4-wave kernel
-                                   // (register ring); 1: the 8-wave ping-pong experiment
+CPX_SWITCH(g_att_v8, 2);           // 2: two query rows per wave, two workgroups per CU (k_attention2w, production); 7: 4-wave kernel with the
+                                   // LDS-DMA ring and software-pipelined S (k_attention4p, rounds 2-5); 0: the first 4-wave kernel
+                                   // (register ring); 1: the 8-wave ping-pong experiment; 3-6: k_attention2q (cpx_attn2q.hip)
 // experiment switch (default off): V read from the qkv rows through ds_read_b64_tr_b16, no V^T buffer and a plain
 // qkv epilogue.  Bitwise identical outputs; the whole engine step measured 24.57 vs 24.44 ms (one-process A/B,
 // tools/ab_switch.py cpx_attention_set_trv): the 8 transposed reads per tile cost more than the epilogue saves.
@@ -1082,7 +1084,7 @@ int cpx_attention_half(int dtype, const void *qkv, const void *rel_h, const void
         CPX_CHECK_LAUNCH();
         return CPX_OK;
     }
-    if (g_att_v8 != 2 || g_att_trv) {
+    if (g_att_v8 < 2 || g_att_v8 > 7 || g_att_trv) {        // (variants 3-6 and 7 are dispatched below)
         dim3 grid(8, 16, n_subtiles);
 #define ATT_LAUNCH(F16_, TRV_)                                                                              \
     hipLaunchKernelGGL((k_attention<F16_, false, TRV_>), grid, dim3(ATT_THREADS), 0, s, (const unsigned short *)qkv, \
@@ -1098,13 +1100,19 @@ int cpx_attention_half(int dtype, const void *qkv, const void *rel_h, const void
 #ifdef CPX_DEBUG
     if (g_att_v8 >= 3 && g_att_v8 <= 6) return cpx_attention2q_launch(dtype, qkv, vT_ws, rel_h, rel_w, n_subtiles, out, g_att_v8 - 3, s);   // round-4 experiments
 #endif
+    // production: two query rows per wave, two workgroups per CU (cpx_attn2w.hip).  The debug library keeps the round-2/3 kernel
+    // k_attention4p as variant 7, with its round-5 experiment switches (cpx_attention_set_lsum 1..5, which select it too)
+#ifdef CPX_DEBUG
+    if (g_att_v8 == 2 && !g_att_lsum)
+#endif
+        return cpx_attention2w_launch(dtype, qkv, vT_ws, rel_h, rel_w, n_subtiles, out, g_att_xcd, s);
+#ifdef CPX_DEBUG
     const dim3 grid4(8, 16, n_subtiles);
     static CpxOncePerDevice once4;
     once4([] {
         (void)hipFuncSetAttribute((const void *)k_attention4p<true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
         (void)hipFuncSetAttribute((const void *)k_attention4p<false>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
     });
-#ifdef CPX_DEBUG
     if (g_att_lsum == 3 && dtype != CPX_DT_F16) {           // round-5 experiment: no overflow vote (k_attention4p<.., NV>), bf16
         static CpxOncePerDevice once4n;
         once4n([] { (void)hipFuncSetAttribute((const void *)k_attention4p<false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES); });
@@ -1159,7 +1167,6 @@ int cpx_attention_half(int dtype, const void *qkv, const void *rel_h, const void
         CPX_CHECK_LAUNCH();
         return CPX_OK;
     }
-#endif
     if (dtype == CPX_DT_F16)
         hipLaunchKernelGGL((k_attention4p<true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
                            (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
@@ -1168,6 +1175,7 @@ int cpx_attention_half(int dtype, const void *qkv, const void *rel_h, const void
                            (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
     CPX_CHECK_LAUNCH();
     return CPX_OK;
+#endif
 }
 
 // ---------------------------------------------------------------------------
