@@ -175,6 +175,8 @@ _PRIVATE = {
     "cpx_gemm_pingpong_occupancy": (_i, []),
     "cpx_gemm_pingpong_stamps": (_i, [_p, _sz]),
     "cpx_gemm_set_pingpong_opts": (None, [_i, _i]),
+    "cpx_gemm_ln_dt": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "cpx_row_stats_dt": (_i, [_i, _p, _i, _p, _p]),
 }
 
 _lib = None

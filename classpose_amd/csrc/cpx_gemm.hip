@@ -320,6 +320,10 @@ __global__ void __launch_bounds__(GEMM_THREADS, 2) k_gemm(GemmArgs g) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
             } else if constexpr (EPI == CPX_EPI_RESID_BF16) {
+                // the reference's double rounding, as in the 256^2 kernels: the layer output is rounded to the half type first,
+                // then added to the residual and rounded again (attn.proj / mlp.lin2 of batches under 16 sub-tiles run here)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = from_half<F16>(to_half<F16>(v[r]));
                 const uint2 rr = *reinterpret_cast<const uint2 *>((const unsigned short *)g.aux + (size_t)m * g.ld_out + n);
                 v[0] += from_half<F16>(rr.x & 0xFFFF); v[1] += from_half<F16>(rr.x >> 16);
                 v[2] += from_half<F16>(rr.y & 0xFFFF); v[3] += from_half<F16>(rr.y >> 16);
@@ -1844,9 +1848,11 @@ static bool launch_gemm256(const GemmArgs &a0, hipStream_t s) {
 #endif
             // direct-store epilogue (G2F_DIRECT): production for the GELU epilogue (mlp.lin1 -3.5 %, bitwise equal); the lighter epilogues
             // measured equal or slower with it (qkv +1.2 %) and keep the staged rows -- cpx_gemm_set_direct(2) in the debug build forces it
+            // on the plain and ReLU epilogues.  Not on qkv: forced onto the balanced q|k / V^T tile list it wrote scattered wrong q|k elements
+            // (2119 of 33.5 M at M = 16384, integer operands, tests/test_gpu_gemm_exact.py), cause not found -- that variant is retired
             constexpr bool DIRECT_OK = EPI == CPX_EPI_GELU_BF16
 #ifdef CPX_DEBUG
-                                       || EPI != CPX_EPI_RESID_BF16
+                                       || (EPI != CPX_EPI_RESID_BF16 && EPI != CPX_EPI_QKV_BF16)
 #endif
                 ;
             // balanced fragment-read schedule (G2F_BAL): ONLY the bf16 residual epilogue with row statistics (proj / mlp.lin2 of the engine: 0.98 of the
@@ -2005,6 +2011,21 @@ extern "C" int cpx_gemm_ln(const void *A, const void *Wt, int M, int N, int K, i
                            const float *ln_stats, const float *ln_colsum, float *stats_out, void *stream) {
     return cpx_gemm_half(CPX_DT_BF16, A, Wt, M, N, K, epilogue, bias, aux, out, ld_out, ln_stats, ln_colsum, stats_out, stream);
 }
+#ifdef CPX_DEBUG
+// cpx_gemm_ln in either half type (the product's cpx_gemm_ln is bf16 only; the fp16 folded-LayerNorm, residual + statistics and
+// mlp.lin1 instantiations are otherwise reachable only through cpx_net_forward): kernel-level tests of the fp16 network
+extern "C" int cpx_gemm_ln_dt(int dtype, const void *A, const void *Wt, int M, int N, int K, int epilogue,
+                              const float *bias, const void *aux, void *out, int ld_out,
+                              const float *ln_stats, const float *ln_colsum, float *stats_out, void *stream) {
+    return cpx_gemm_half(dtype, A, Wt, M, N, K, epilogue, bias, aux, out, ld_out, ln_stats, ln_colsum, stats_out, stream);
+}
+#endif
+#ifdef CPX_DEBUG
+// cpx_row_stats in either half type (the product entry is bf16 only; the network launches the fp16 instantiation itself)
+extern "C" int cpx_row_stats_dt(int dtype, const void *x, int rows, float *stats, void *stream) {
+    return cpx_row_stats_half(dtype, x, rows, stats, stream);
+}
+#endif
 extern "C" int cpx_gemm_bf16(const void *A, const void *Wt, int M, int N, int K, int epilogue,
                              const float *bias, const void *aux, void *out, int ld_out, void *stream) {
     return cpx_gemm_half(CPX_DT_BF16, A, Wt, M, N, K, epilogue, bias, aux, out, ld_out, nullptr, nullptr, nullptr, stream);

@@ -277,20 +277,33 @@ def attention(qkv: torch.Tensor, rel_h: torch.Tensor, rel_w: torch.Tensor):
 
 
 def row_stats(x: torch.Tensor) -> torch.Tensor:
+    """(sum, sum of squares) of each 1024-wide row into slot 0 of [rows][4][2].  bf16 through the product library; fp16 under
+    ``_lib.use_debug_library()`` (cpx_row_stats_dt)."""
+    if x.dim() != 2 or x.shape[1] != 1024 or not x.is_contiguous():
+        raise ValueError(f"row_stats takes contiguous [rows][1024] rows, not {tuple(x.shape)}")
     st = torch.empty((x.shape[0], 4, 2), dtype=torch.float32, device=x.device)
-    check(_lib.lib().cpx_row_stats(ptr(x), x.shape[0], ptr(st), _stream(x.device)), "row_stats")
+    L = _lib.lib()
+    if x.dtype != torch.bfloat16:             # debug library only: the product has no such symbol (AttributeError)
+        check(L.cpx_row_stats_dt(_DT[x.dtype], ptr(x), x.shape[0], ptr(st), _stream(x.device)), "row_stats")
+    else:
+        check(L.cpx_row_stats(ptr(x), x.shape[0], ptr(st), _stream(x.device)), "row_stats")
     return st
 
 
 def gemm_ln(A, Wt, epilogue="bf16", bias=None, aux=None, ln_stats=None, ln_colsum=None, want_stats=False):
-    """GEMM with a LayerNorm over the input row folded in / output row statistics emitted."""
+    """GEMM with a LayerNorm over the input row folded in / output row statistics emitted.  bf16 through the product
+    library; under ``_lib.use_debug_library()`` the half type follows ``A.dtype`` (bf16 or fp16, cpx_gemm_ln_dt)."""
     M, K = A.shape
     N = Wt.shape[0]
     dev = A.device
     out = torch.empty((M, N), dtype=torch.float32 if epilogue == "f32" else A.dtype, device=dev)
     st = torch.zeros((M, 4, 2), dtype=torch.float32, device=dev) if want_stats else None
-    check(_lib.lib().cpx_gemm_ln(ptr(A), ptr(Wt), M, N, K, EPI[epilogue], ptr(bias), ptr(aux), ptr(out), N,
-                                 ptr(ln_stats), ptr(ln_colsum), ptr(st), _stream(dev)), "gemm_ln")
+    L = _lib.lib()
+    args = (ptr(A), ptr(Wt), M, N, K, EPI[epilogue], ptr(bias), ptr(aux), ptr(out), N, ptr(ln_stats), ptr(ln_colsum), ptr(st), _stream(dev))
+    if A.dtype != torch.bfloat16:             # debug library only: the product has no such symbol (AttributeError)
+        check(L.cpx_gemm_ln_dt(_DT[A.dtype], *args), "gemm_ln")
+    else:
+        check(L.cpx_gemm_ln(*args), "gemm_ln")
     return (out, st) if want_stats else out
 
 

@@ -23,7 +23,7 @@ void cpx_gemm_set_pingpong_opts(int persistent, int delay);   /* (1, 2) default:
 int cpx_gemm_pingpong_stamps(unsigned long long *host_out, size_t n_words);   /* cycle stamps written under cpx_gemm_set_dbg(32) */
 int cpx_gemm_pingpong_occupancy(void);      /* workgroups of the ping-pong kernel admitted per CU (design point: 2) */
 void cpx_gemm_set_reverse(int on);          /* 0 (default): mlp.lin2 walks M backwards when 1            */
-void cpx_gemm_set_direct(int mode);         /* 1 (default): direct-store epilogue of the persistent 256^2 kernel (accumulators -> v_permlane16_swap -> 16-byte buffer stores, no LDS staging) for the GELU epilogue; 2: for every non-residual epilogue; 0: staged rows */
+void cpx_gemm_set_direct(int mode);         /* 1 (default): direct-store epilogue of the persistent 256^2 kernel (accumulators -> v_permlane16_swap -> 16-byte buffer stores, no LDS staging) for the GELU epilogue; 2: also for the plain and ReLU epilogues (qkv keeps the staged rows); 0: staged rows */
 void cpx_gemm_set_balanced(int on);         /* 1 (default): balanced fragment-read schedule of the persistent 256^2 main loop for the bf16 residual + row-statistics epilogue (proj, mlp.lin2); 0: plain schedule */
 int cpx_gemm4w(const void *A, const void *W, int M, int N, int K, const float *bias, void *out, int ld_out, void *stream);   /* the 256^2 GEMM tile with ONE wave per SIMD (4 waves x 128 x 128, AGPR accumulators), persistent, bias epilogue, bf16 (csrc/cpx_gemm4w.hip) */
 void cpx_gemm_set_4w(int mask);             /* 1 (default): mlp.lin1 (bf16, folded LayerNorm + GELU) on the one-wave-per-SIMD kernel; +2: attn.proj / mlp.lin2 (residual + statistics) too (slower, not shipped); 0: everything on the 8-wave persistent kernel (same bits) */
@@ -39,6 +39,12 @@ void cpx_postproc_set_fused(int on);        /* 1 (default): the 23-launch fused 
 void cpx_gemm_set_nt(int on);               /* bits 0 / 1 / 2: non-temporal stores for the q / k / V^T thirds of the qkv projection's output (7 = default); 0: ordinary stores */
 void cpx_follow_set_early_exit(int on);     /* 1 (default): Euler loop leaves when its orbit closes      */
 void cpx_follow_set_lds_window(int on);     /* 1 (default): 32 x 32-cell foreground segments, the Euler loop's taps from an LDS copy of the segment's neighbourhood; 0: round 4 */
+/* the product's bf16-only cpx_row_stats, with the half type as its first argument: CPX_DT_BF16 or CPX_DT_F16 */
+int cpx_row_stats_dt(int dtype, const void *x, int rows, float *stats, void *stream);
+/* the product's bf16-only cpx_gemm_ln, with the half type as its first argument: CPX_DT_BF16 or CPX_DT_F16 */
+int cpx_gemm_ln_dt(int dtype, const void *A, const void *Wt, int M, int N, int K, int epilogue,
+                   const float *bias, const void *aux, void *out, int ld_out,
+                   const float *ln_stats, const float *ln_colsum, float *stats_out, void *stream);
 /* per-wave cycle stamps of the attention loop segments: dbg [n_subtiles*16*8][4][9] */
 int cpx_attention_debug(const void *qkv, const void *rel_h, const void *rel_w, int n_subtiles,
                         void *vT_ws, void *out, unsigned *dbg, void *stream);
