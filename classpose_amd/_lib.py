@@ -177,6 +177,8 @@ _PRIVATE = {
     "cpx_gemm_set_pingpong_opts": (None, [_i, _i]),
     "cpx_gemm_ln_dt": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),
     "cpx_row_stats_dt": (_i, [_i, _p, _i, _p, _p]),
+    "cpx_im2col3_f32_debug": (_i, [_p, _i, _p, _p]),
+    "cpx_unet_head_layout": (_i, [C.POINTER(CpxConvOp), _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
 }
 
 _lib = None

@@ -1438,26 +1438,62 @@ __global__ void __launch_bounds__(256) k_depth2space(const char *__restrict__ in
 static inline int up128(long long x) { return (int)((x + 127) / 128 * 128); }
 static inline int up64(int x) { return (x + 63) / 64 * 64; }
 
-// workspace: tensors [rows_pad][ld], one per op, + the largest im2col / GEMM staging buffers
-size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS) {
+// workspace layout: [im2col staging][convT GEMM staging][one tensor [rows_pad][ld] per op] + 1024 bytes of slack.  The
+// LAST op (a convT into the head) gets a slot too but never writes it: its GEMM output stays in the convT staging buffer
+// and k_depth2space widens it straight into the head.  One helper for the size, the run and the debug layout entry.
+struct UnetLayout {
+    size_t col_off, g_off, total;
+    size_t off[64];                      // op i's output tensor
+    int ld[64];                          // its row stride in elements
+};
+static void unet_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, UnetLayout &L) {
     const size_t es = dtype == CPX_DT_F32 ? 4 : 2;
-    size_t tot = 0, col_max = 0, g_max = 0;
-    for (int i = 0; i < n_ops; ++i) {
+    size_t col_max = 0, g_max = 0;
+    for (int i = 0; i < n_ops; ++i) {     // sizes of the shared staging buffers first
         const cpx_conv_op &o = ops[i];
         const int ho = o.kind == 0 ? o.h : (o.kind == 1 ? o.h / 2 : o.h * 2), wo = o.kind == 0 ? o.w : (o.kind == 1 ? o.w / 2 : o.w * 2);
-        const size_t rows_out = (size_t)nS * ho * wo;
-        tot += cpx_align_up((size_t)up128(rows_out) * up128(o.cout) * es, 256);
-        if (o.kind != 2) col_max = std::max(col_max, (size_t)up128(rows_out) * up64((o.kind == 0 ? 9 : 4) * (o.cin_a + o.cin_b)) * es);
+        if (o.kind != 2) col_max = std::max(col_max, (size_t)up128((size_t)nS * ho * wo) * up64((o.kind == 0 ? 9 : 4) * (o.cin_a + o.cin_b)) * es);
         else {
             g_max = std::max(g_max, (size_t)up128((size_t)nS * o.h * o.w) * up128(4 * o.cout) * es);
             col_max = std::max(col_max, (size_t)up128((size_t)nS * o.h * o.w) * up64(o.cin_a) * es);
         }
     }
-    return tot + cpx_align_up(col_max, 256) + cpx_align_up(g_max, 256) + 1024;
+    L.col_off = 0;
+    L.g_off = cpx_align_up(col_max, 256);
+    size_t off = L.g_off + cpx_align_up(g_max, 256);
+    for (int i = 0; i < n_ops && i < 64; ++i) {
+        const cpx_conv_op &o = ops[i];
+        const int ho = o.kind == 0 ? o.h : (o.kind == 1 ? o.h / 2 : o.h * 2), wo = o.kind == 0 ? o.w : (o.kind == 1 ? o.w / 2 : o.w * 2);
+        L.off[i] = off;
+        L.ld[i] = up128(o.cout);
+        off += cpx_align_up((size_t)up128((size_t)nS * ho * wo) * up128(o.cout) * es, 256);
+    }
+    L.total = off + 1024;
+}
+
+size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS) {
+    if (!ops || n_ops <= 0 || n_ops > 64 || nS <= 0) return 0;
+    UnetLayout L;
+    unet_layout(dtype, ops, n_ops, nS, L);
+    return L.total;
 }
 extern "C" size_t cpx_unet_workspace_bytes(const cpx_conv_op *ops, int n_ops, int nS, int dtype) {
     return cpx_unet_ws_bytes(dtype, ops, n_ops, nS);
 }
+#ifdef CPX_DEBUG
+// where cpx_unet_head_run leaves each op's output in its workspace: byte offset and row stride (elements).  Op i < n_ops - 1:
+// its output tensor [rows_pad][ld], channels 0 .. cout - 1 valid.  The last op (the convT into the head): its GEMM output
+// before depth-to-space, [rows_in_pad][ld = up128(4 cout)] with column tap * cout + co, in the convT staging buffer.
+extern "C" int cpx_unet_head_layout(const cpx_conv_op *ops, int n_ops, int nS, int dtype, size_t *dst_off, int *ld) {
+    CPX_REQUIRE(ops && n_ops > 0 && n_ops <= 64 && nS > 0 && dst_off && ld && ops[n_ops - 1].kind == 2);
+    UnetLayout L;
+    unet_layout(dtype, ops, n_ops, nS, L);
+    for (int i = 0; i < n_ops; ++i) { dst_off[i] = L.off[i]; ld[i] = L.ld[i]; }
+    dst_off[n_ops - 1] = L.g_off;
+    ld[n_ops - 1] = up128(4 * ops[n_ops - 1].cout);
+    return CPX_OK;
+}
+#endif
 
 // feat: neck output [nS*1024][256] (tensor id 0).  The LAST op must be a convT producing
 // ncls*64 channels at 32x32: it is written as float32 into head[:, col0 : col0 + cout].
@@ -1470,18 +1506,9 @@ int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *
     struct T { const char *p; int ld, c, h, w; } tens[66];
     tens[0] = {(const char *)feat, 256, 256, 32, 32};
     char *ws = (char *)workspace;
-    size_t off = 0, col_max = 0, g_max = 0;
-    for (int i = 0; i < n_ops; ++i) {     // sizes of the shared staging buffers first
-        const cpx_conv_op &o = ops[i];
-        const int ho = o.kind == 0 ? o.h : (o.kind == 1 ? o.h / 2 : o.h * 2), wo = o.kind == 0 ? o.w : (o.kind == 1 ? o.w / 2 : o.w * 2);
-        if (o.kind != 2) col_max = std::max(col_max, (size_t)up128((size_t)nS * ho * wo) * up64((o.kind == 0 ? 9 : 4) * (o.cin_a + o.cin_b)) * es);
-        else {
-            g_max = std::max(g_max, (size_t)up128((size_t)nS * o.h * o.w) * up128(4 * o.cout) * es);
-            col_max = std::max(col_max, (size_t)up128((size_t)nS * o.h * o.w) * up64(o.cin_a) * es);
-        }
-    }
-    char *colbuf = ws; off = cpx_align_up(col_max, 256);
-    char *gbuf = ws + off; off += cpx_align_up(g_max, 256);
+    UnetLayout lay;
+    unet_layout(dtype, ops, n_ops, nS, lay);
+    char *colbuf = ws + lay.col_off, *gbuf = ws + lay.g_off;
     auto gather = [&](const T &A, int ca, const T &B, int cb, int kind, int h, int w, size_t rows, int Kp) {
         const size_t n_chunks = rows * (Kp / (16 / es));
         const dim3 grid((unsigned)((n_chunks + 255) / 256));
@@ -1506,8 +1533,7 @@ int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *
             const size_t rows = (size_t)nS * ho * wo;
             const int Mp = up128(rows), Kp = up64((o.kind == 0 ? 9 : 4) * (o.cin_a + o.cin_b)), Np = up128(o.cout);
             gather(A, o.cin_a, B, o.cin_b, o.kind, o.h, o.w, rows, Kp);
-            char *dst = ws + off;
-            off += cpx_align_up((size_t)Mp * Np * es, 256);
+            char *dst = ws + lay.off[i];
             rc = gemm(colbuf, o.weight, Mp, Np, Kp, o.relu ? CPX_EPI_RELU_BF16 : CPX_EPI_BF16, o.bias, dst);
             if (rc) return rc;
             tens[o.dst] = {dst, Np, o.cout, ho, wo};
@@ -1519,9 +1545,8 @@ int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *
             rc = gemm(colbuf, o.weight, Mp, Np, Kp, CPX_EPI_BF16, o.bias, gbuf);
             if (rc) return rc;
             const bool last = i == n_ops - 1;
-            char *dst = ws + off;
-            const int ldo = up128(o.cout);
-            if (!last) off += cpx_align_up((size_t)up128(rows * 4) * ldo * es, 256);
+            char *dst = ws + lay.off[i];
+            const int ldo = lay.ld[i];
             const size_t n_thr = rows * 4 * (o.cout / (16 / es));
             const dim3 grid((unsigned)((n_thr + 255) / 256));
 #define D2S(DT_) hipLaunchKernelGGL(k_depth2space<DT_>, grid, dim3(256), 0, s, gbuf, Np, o.cout, o.h, o.w, rows, dst, ldo, last ? head : nullptr, ld_head, col0)

@@ -341,6 +341,16 @@ __global__ void __launch_bounds__(256) k_im2col3_f32(const float *__restrict__ x
         v = *reinterpret_cast<const float4 *>(x + ((row & ~(size_t)1023) + yy * 32 + xx) * 256 + c4 * 4);
     *reinterpret_cast<float4 *>(out + row * 2304 + tap * 256 + c4 * 4) = v;
 }
+#ifdef CPX_DEBUG
+// the neck's im2col on its own: x [n_subtiles*1024][256] -> out [n_subtiles*1024][2304]
+extern "C" int cpx_im2col3_f32_debug(const float *x, int n_subtiles, float *out, void *stream) {
+    CPX_REQUIRE(x && out && n_subtiles > 0);
+    const size_t n_chunks = (size_t)n_subtiles * 1024 * 576;
+    hipLaunchKernelGGL(k_im2col3_f32, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n_chunks, out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+#endif
 
 // ---------------------------------------------------------------------------
 // forward driver (ClassTransformer.forward, vit_sam.py:148-197)

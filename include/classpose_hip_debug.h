@@ -45,6 +45,13 @@ int cpx_row_stats_dt(int dtype, const void *x, int rows, float *stats, void *str
 int cpx_gemm_ln_dt(int dtype, const void *A, const void *Wt, int M, int N, int K, int epilogue,
                    const float *bias, const void *aux, void *out, int ld_out,
                    const float *ln_stats, const float *ln_colsum, float *stats_out, void *stream);
+/* the fp32 neck's im2col (k_im2col3_f32) on its own: x [n_subtiles*1024][256] -> out [n_subtiles*1024][9*256], k = tap*256 + c */
+int cpx_im2col3_f32_debug(const float *x, int n_subtiles, float *out, void *stream);
+/* where cpx_unet_head_forward leaves each op's output in its workspace (the layout helper the run itself uses): byte offset
+ * and row stride in elements.  Ops 0 .. n_ops-2: the output tensor [rows_pad][ld].  The last op (the convT into the head): its
+ * GEMM output before depth-to-space, [rows_in_pad][ld] with column tap*cout + co.                                            */
+struct cpx_conv_op;
+int cpx_unet_head_layout(const struct cpx_conv_op *ops, int n_ops, int n_subtiles, int dtype, size_t *dst_off, int *ld);
 /* per-wave cycle stamps of the attention loop segments: dbg [n_subtiles*16*8][4][9] */
 int cpx_attention_debug(const void *qkv, const void *rel_h, const void *rel_w, int n_subtiles,
                         void *vT_ws, void *out, unsigned *dbg, void *stream);

@@ -1,8 +1,8 @@
-"""Per-element numerics checker for the half-precision kernels -- TEST INFRASTRUCTURE ONLY.
+"""Per-element numerics checker for the bf16 / fp16 / fp32 kernels -- TEST INFRASTRUCTURE ONLY.
 
-``round_half`` rounds float64 values to bf16 / fp16 by round-to-nearest-even in ONE step (torch's own ``.to()`` from
-float64 goes through float32 first for bf16, a double rounding), with fp16 gradual underflow and overflow to +-inf.
-``ulp`` is the spacing of the half type at a value.  ``check`` asserts an elementwise bound and a per-block / per-row
+``round_half`` rounds float64 values to bf16, fp16 or float32 by round-to-nearest-even in ONE step (torch's own ``.to()``
+from float64 goes through float32 first for bf16, a double rounding), with gradual underflow and overflow to +-inf; for
+float32 it equals ``.float()``.  ``ulp`` is the spacing of the type at a value.  ``check`` asserts an elementwise bound and a per-block / per-row
 RMS gate and, on failure, names where the error sits: the worst element, 16 x 16 block, row and column.
 
 Everything is torch on whatever device the tensors live on (float64), so a test can build its reference on the GPU.
@@ -15,6 +15,7 @@ import torch
 _FMT = {
     torch.bfloat16: (8, -126, (2.0 - 2.0 ** -7) * 2.0 ** 127),
     torch.float16: (11, -14, 65504.0),
+    torch.float32: (24, -126, (2.0 - 2.0 ** -23) * 2.0 ** 127),
 }
 
 # RMS gate: a correctly rounded result has |err| <= 0.5 ulp everywhere, and for values spread over the binade
@@ -26,7 +27,7 @@ RMS_LIMIT = 0.40
 
 def _fmt(dtype):
     if dtype not in _FMT:
-        raise ValueError(f"not a half type: {dtype}")
+        raise ValueError(f"not bf16, fp16 or float32: {dtype}")
     return _FMT[dtype]
 
 
@@ -69,7 +70,7 @@ def check(got: torch.Tensor, ref64: torch.Tensor, bound, block=(16, 16), dtype=N
     got: the kernel's output (any dtype; compared as float64).  ref64: the float64 reference of the SAME operation
     (exact, or correctly rounded when the bound is 0).  bound, atol: scalars or tensors broadcastable to got, absolute;
     atol is the part of the bound that is not rounding (the RMS gate discounts it).
-    dtype: the half type that sets ulp (default got.dtype).  Non-finite values must match exactly (same inf sign / NaN).
+    dtype: the type that sets ulp (bf16, fp16 or float32; default got.dtype).  Non-finite values must match exactly (same inf sign / NaN).
     On failure the AssertionError names the worst element (index, ulps, got, ref), the worst block, row and column.
     Returns a few summary numbers (max ulps, worst block RMS) for the caller's report."""
     dtype = dtype or got.dtype

@@ -145,3 +145,42 @@ def test_checker_flags_fp16_overflow_stored_as_max():
     with pytest.raises(AssertionError) as e:
         nm.check_exact(bad, ref, what="saturation")
     assert _loc(str(e.value)) == (9, 17)
+
+
+def test_round_half_float32_equals_torch_float():
+    """float32 in the same table: round_half(x64, float32) == x64.float() (torch's one RNE step from float64) on random
+    values over the whole exponent range, exact ties, subnormals (spacing 2^-149, ties at odd multiples of 2^-150) and values
+    past FLT_MAX (from FLT_MAX + ulp/2 = 2^128 - 2^103 on: inf)"""
+    f32 = torch.float32
+    g = torch.Generator().manual_seed(3)
+    n = 8192
+    sgn = torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0).double()
+    # exact ties: (m + 1/2) ulp with a 24-bit significand m, and just above / below them (float64 has 29 more bits)
+    e = torch.randint(-120, 120, (n,), generator=g).double()
+    m = torch.randint(2 ** 23, 2 ** 24, (n,), generator=g).double()
+    ties = (m + 0.5) * torch.exp2(e - 23) * sgn
+    near = torch.cat([ties * (1 + 2.0 ** -40), ties * (1 - 2.0 ** -40)])
+    rnd = torch.randn(n, generator=g).double() * torch.exp2(torch.randint(-140, 128, (n,), generator=g).double())
+    k = torch.arange(-4096, 4096).double()
+    sub = torch.cat([k * 2.0 ** -150, k * 2.0 ** -149 * 0.3, k * 2.0 ** -140 + 2.0 ** -150])     # ties, inexact, subnormal
+    fmax = (2.0 - 2.0 ** -23) * 2.0 ** 127
+    big = torch.tensor([fmax, fmax + 2.0 ** 102, fmax + 2.0 ** 103 - 2.0 ** 80, fmax + 2.0 ** 103, 2.0 ** 128, 1e300, 1e39])
+    big = torch.cat([big, -big])
+    x = torch.cat([ties, near, rnd, sub, big, torch.tensor([0.0, -0.0, 2.0 ** -151, 3 * 2.0 ** -151])])
+    got = nm.round_half(x, f32)
+    exp = x.float().double()
+    assert torch.equal(got, exp), (x[got != exp][:8], got[got != exp][:8], exp[got != exp][:8])
+    assert nm.round_half(torch.tensor([fmax + 2.0 ** 103], dtype=torch.float64), f32).item() == float("inf")
+    assert nm.round_half(torch.tensor([fmax + 2.0 ** 103 - 2.0 ** 80], dtype=torch.float64), f32).item() == fmax
+    assert nm.round_half(torch.tensor([2.0 ** -150], dtype=torch.float64), f32).item() == 0.0          # tie to the even zero
+    assert nm.round_half(torch.tensor([3 * 2.0 ** -150], dtype=torch.float64), f32).item() == 2.0 ** -148
+    assert nm.ulp(torch.tensor([1.0]), f32).item() == 2.0 ** -23 and nm.ulp(torch.tensor([0.0]), f32).item() == 2.0 ** -149
+    # the checker on float32 outputs: exact where exact, one float32 ulp flagged and located
+    ref = torch.randn(64, 96, generator=g).double()
+    got32 = ref.float()
+    nm.check_exact(got32, ref, what="f32")
+    bad = got32.clone()
+    bad[10, 20] = torch.nextafter(bad[10, 20], torch.tensor(float("inf")))
+    with pytest.raises(AssertionError) as ei:
+        nm.check_exact(bad, ref, what="f32 1 ulp")
+    assert _loc(str(ei.value)) == (10, 20)
