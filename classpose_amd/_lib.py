@@ -144,8 +144,6 @@ SIGNATURES = {
 # include/classpose_hip_debug.h: process-global A/B and ablation switches -- exported by libclasspose_hip_debug.so only
 _PRIVATE = {
     "cpx_gemm_set_variant": (None, [_i]),
-    "cpx_attention_set_trv": (None, [_i]),
-    "cpx_attention_set_lsum": (None, [_i]),
     "cpx_attention_set_variant": (None, [_i]),
     "cpx_gemm_set_nt": (None, [_i]),
     "cpx_follow_set_early_exit": (None, [_i]),
@@ -155,13 +153,7 @@ _PRIVATE = {
     "cpx_gemm_set_big": (None, [_i]),
     "cpx_gemm_set_persistent": (None, [_i]),
     "cpx_gemm_set_persistent_qkv": (None, [_i]),
-    "cpx_attention_debug": (_i, [_p, _p, _p, _i, _p, _p, _p, _p]),
-    "cpx_attention8_debug": (_i, [_p, _p, _p, _i, _p, _p, _p, _p]),
-    "cpx_attention4_debug": (_i, [_p, _p, _p, _i, _p, _p, _p, _p]),
-    "cpx_attention2q_debug": (_i, [_p, _p, _p, _p, _i, _p, _p, _p]),
-    "cpx_attention2q_set_ablation": (None, [_i]),
     "cpx_postproc_set_fused": (None, [_i]),
-    "cpx_gemm_set_split": (None, [_i]),
     "cpx_gemm_set_direct": (None, [_i]),
     "cpx_gemm4w": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _p]),
     "cpx_gemm4w_set_variant": (None, [_i]),
@@ -170,11 +162,6 @@ _PRIVATE = {
     "cpx_gemm_set_balanced": (None, [_i]),
     "cpx_gemm_set_dbg": (None, [_i]),
     "cpx_gemm_set_l2_block": (None, [_i]),
-    "cpx_gemm_set_pingpong": (None, [_i]),
-    "cpx_gemm_set_epi4": (None, [_i]),
-    "cpx_gemm_pingpong_occupancy": (_i, []),
-    "cpx_gemm_pingpong_stamps": (_i, [_p, _sz]),
-    "cpx_gemm_set_pingpong_opts": (None, [_i, _i]),
     "cpx_gemm_ln_dt": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),
     "cpx_row_stats_dt": (_i, [_i, _p, _i, _p, _p]),
     "cpx_im2col3_f32_debug": (_i, [_p, _i, _p, _p]),

@@ -3,8 +3,8 @@
 //
 // The round-2/3 kernel (k_attention4p, cpx_net.hip; debug variant 7) runs one strictly serial chain per wave
 // (K reads -> QK^T -> softmax -> V reads -> P.V -> barrier) and hides it behind three co-resident workgroups per CU; the
-// round-4 one (k_attention2q, cpx_attn2q.hip) interleaves two chains per wave but runs one wave per SIMD, with nothing to
-// hide its skeleton (ring, waits, barrier, seams) behind.  This kernel is the combination: each wave owns image rows
+// round-4 one (k_attention2q, retired: git show f07d44d:classpose_amd/csrc/cpx_attn2q.hip) interleaves two chains per wave
+// but runs one wave per SIMD, with nothing to hide its skeleton (ring, waits, barrier, seams) behind.  This kernel is the combination: each wave owns image rows
 // 2 w and 2 w + 1 of its workgroup's 8 (chains 0 and 1) and alternates them in half steps --
 //   half step A:  matrix pipe  S1 = K(t) Q1^T + Gw1,  O1 += V(t - 1) P1(t - 1)  |  vector pipe  P0(t) = softmax(S0)
 //   half step B:  matrix pipe  S0 = K(t + 1) Q0^T + Gw0,  O0 += V(t) P0(t)     |  vector pipe  P1(t) = softmax(S1)

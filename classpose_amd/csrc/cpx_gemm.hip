@@ -76,8 +76,6 @@ struct GemmArgs {
     // implicit 3x3 convolution (128^2 kernel, CONV instantiation): A is the [S*1024][conv_c] token-major activation of
     // 32 x 32-token images, K = 9 * conv_c with k = tap * conv_c + c (tap = 3 (dy + 1) + (dx + 1)); 0 = plain GEMM
     int conv_c;
-    int epi4;               // persistent 256^2 kernel: 1 = quarter-tile epilogue (conversion of quarter q beside the stores of q - 1)
-    int pp_delay;           // ping-pong kernel: x ~8k cycles the second workgroup of a CU waits at launch (0 = no offset)
 };
 #define LN_SLOTS 4
 __device__ __forceinline__ void ln_row_params(const float *st, int m, float inv_k, float &mean, float &rstd) {
@@ -417,29 +415,6 @@ __device__ __forceinline__ void g2_mma(f32x4 (&acc)[4][2], const u32x4 (&fx)[4][
                 acc[mb][nb] = mfma16v<F16>(fw[nb][ks], fx[mb][ks], (FIRST && ks == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[mb][nb]);
     __builtin_amdgcn_s_setprio(0);
 }
-// SPLIT (experiment, round 4): fragment reads ordered k-substep 0 first, so that the first eight MFMAs of a phase can start
-// behind a COUNTED lgkmcnt while the k-substep-1 fragments are still landing
-template <int HM>
-__device__ __forceinline__ void g2_read_x_ks(u32x4 (&fx)[4][2], unsigned b0, unsigned b1) {
-    fx[0][0] = lds_read128<HM * G2_HALF + 0 * 2048>(b0); fx[1][0] = lds_read128<HM * G2_HALF + 1 * 2048>(b0);
-    fx[2][0] = lds_read128<HM * G2_HALF + 2 * 2048>(b0); fx[3][0] = lds_read128<HM * G2_HALF + 3 * 2048>(b0);
-    fx[0][1] = lds_read128<HM * G2_HALF + 0 * 2048>(b1); fx[1][1] = lds_read128<HM * G2_HALF + 1 * 2048>(b1);
-    fx[2][1] = lds_read128<HM * G2_HALF + 2 * 2048>(b1); fx[3][1] = lds_read128<HM * G2_HALF + 3 * 2048>(b1);
-}
-template <int HN>
-__device__ __forceinline__ void g2_read_w_ks(u32x4 (&fw)[2][2], unsigned b0, unsigned b1) {
-    fw[0][0] = lds_read128<(2 + HN) * G2_HALF + 0 * 2048>(b0); fw[1][0] = lds_read128<(2 + HN) * G2_HALF + 1 * 2048>(b0);
-    fw[0][1] = lds_read128<(2 + HN) * G2_HALF + 0 * 2048>(b1); fw[1][1] = lds_read128<(2 + HN) * G2_HALF + 1 * 2048>(b1);
-}
-template <bool F16, bool FIRST, int KS>
-__device__ __forceinline__ void g2_mma_ks(f32x4 (&acc)[4][2], const u32x4 (&fx)[4][2], const u32x4 (&fw)[2][2]) {
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-            acc[mb][nb] = mfma16v<F16>(fw[nb][KS], fx[mb][KS], (FIRST && KS == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[mb][nb]);
-}
-#define G2_LGKM(N) do { asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define G2_BAR() __builtin_amdgcn_s_barrier()
 #define G2_LGKM0() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
@@ -449,8 +424,6 @@ __device__ __forceinline__ void g2_mma_ks(f32x4 (&acc)[4][2], const u32x4 (&fx)[
 #define G2F_LN 1
 #define G2F_STATS 2
 #define G2F_DBG 4
-#define G2F_Q4 8          // persistent kernel: quarter-tile epilogue (experiment, debug build)
-#define G2F_SPLIT 16      // persistent kernel: counted LDS waits inside a phase (experiment, round 4)
 #define G2F_BAL 64        // persistent kernel: balanced fragment-read schedule (W0 of the next K tile pre-read in phase 4, no W0 re-read, every operand item 6 phases ahead)
 #define G2F_DIRECT 32     // persistent kernel: epilogue stores straight from the accumulator registers (v_permlane16_swap -> 16-byte rows), no LDS staging
 template <int EPI, bool F16, int FLAGS>
@@ -946,56 +919,6 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
         g2_mma<F16, FIRST>(acc[1][0], fx, fw);                                                     \
         __builtin_amdgcn_sched_barrier(0); G2_BARX();                                        \
     }
-#define G2_TILE_SPLIT(T, B, FIRST)                                                                 \
-    {                                                                                       \
-        const int t_ = (T);                                                                 \
-        /* p1: W0 + X0 -> (0,0): ks 0 operands = the first 6 of the 12 reads */             \
-        fw[0][0] = lds_read128<2 * G2_HALF>(wb[B][0]); fw[1][0] = lds_read128<2 * G2_HALF + 2048>(wb[B][0]); \
-        fx[0][0] = lds_read128<0>(xb[B][0]); fx[1][0] = lds_read128<2048>(xb[B][0]);        \
-        fx[2][0] = lds_read128<4096>(xb[B][0]); fx[3][0] = lds_read128<6144>(xb[B][0]);     \
-        fw[0][1] = lds_read128<2 * G2_HALF>(wb[B][1]); fw[1][1] = lds_read128<2 * G2_HALF + 2048>(wb[B][1]); \
-        fx[0][1] = lds_read128<0>(xb[B][1]); fx[1][1] = lds_read128<2048>(xb[B][1]);        \
-        fx[2][1] = lds_read128<4096>(xb[B][1]); fx[3][1] = lds_read128<6144>(xb[B][1]);     \
-        if (t_ + 1 < nk) stage(1, t_ + 1);                                                  \
-        G2_BAR(); G2_LGKM(6);                                                               \
-        __builtin_amdgcn_s_setprio(1);                                                      \
-        g2_mma_ks<F16, FIRST, 0>(acc[0][0], fx, fw);                                        \
-        G2_LGKM(0);                                                                         \
-        g2_mma_ks<F16, FIRST, 1>(acc[0][0], fx, fw);                                        \
-        __builtin_amdgcn_s_setprio(0);                                                      \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        /* p2: W1 -> (0,1) */                                                               \
-        g2_read_w_ks<1>(fw, wb[B][0], wb[B][1]);                                            \
-        if (t_ + 1 < nk) stage(2, t_ + 1);                                                  \
-        G2_BAR(); G2_LGKM(2);                                                               \
-        __builtin_amdgcn_s_setprio(1);                                                      \
-        g2_mma_ks<F16, FIRST, 0>(acc[0][1], fx, fw);                                        \
-        G2_LGKM(0);                                                                         \
-        g2_mma_ks<F16, FIRST, 1>(acc[0][1], fx, fw);                                        \
-        __builtin_amdgcn_s_setprio(0);                                                      \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        /* p3: X1 -> (1,1) */                                                               \
-        g2_read_x_ks<1>(fx, xb[B][0], xb[B][1]);                                            \
-        if (t_ + 2 < nk) stage(0, t_ + 2);                                                  \
-        G2_BAR(); G2_LGKM(4);                                                               \
-        __builtin_amdgcn_s_setprio(1);                                                      \
-        g2_mma_ks<F16, FIRST, 0>(acc[1][1], fx, fw);                                        \
-        G2_LGKM(0);                                                                         \
-        g2_mma_ks<F16, FIRST, 1>(acc[1][1], fx, fw);                                        \
-        __builtin_amdgcn_s_setprio(0);                                                      \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        /* p4: W0 -> (1,0) */                                                               \
-        g2_read_w_ks<0>(fw, wb[B][0], wb[B][1]);                                            \
-        if (t_ + 2 < nk) { stage(3, t_ + 2); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); } \
-        else if (t_ + 1 < nk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              \
-        G2_BAR(); G2_LGKM(2);                                                               \
-        __builtin_amdgcn_s_setprio(1);                                                      \
-        g2_mma_ks<F16, FIRST, 0>(acc[1][0], fx, fw);                                        \
-        G2_LGKM(0);                                                                         \
-        g2_mma_ks<F16, FIRST, 1>(acc[1][0], fx, fw);                                        \
-        __builtin_amdgcn_s_setprio(0);                                                      \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-    }
 // ---- balanced schedule (G2F_BAL).  The plain schedule reads 12 fragments in phase 1 (W0 + X0: 48 KB per wave row against a 256-cycle
 // MFMA slot of the partner row), re-reads W0 in phase 4 (28 reads per K tile) and requests W-lo only 3 phases before its first read.
 // Here the two W fragment sets swap roles every K tile: W0 of tile t sits in FA, phase 2 reads W1 into FB, phase 4 (which multiplies with
@@ -1048,21 +971,18 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
             G2_TILE_BAL(nk - 2, 0, false, 3, fw, fw2)
             G2_TILE_BAL(nk - 1, 1, false, 4, fw2, fw)
         } else {
-#define G2_TILE(T, B, FIRST, KIND) { if constexpr ((FLAGS & G2F_SPLIT) != 0) G2_TILE_SPLIT(T, B, FIRST) else G2_TILE_PLAIN(T, B, FIRST, KIND) }
         // (peeling the last two K tiles here as well -- KIND 2 / 3 / 4 -- measured no gain for this schedule: 1.000 of the run-time form)
-        G2_TILE(0, 0, true, -1)
-        G2_TILE(1, 1, false, -1)
+        G2_TILE_PLAIN(0, 0, true, -1)
+        G2_TILE_PLAIN(1, 1, false, -1)
         for (int t = 2; t < nk; t += 2) {
-            G2_TILE(t, 0, false, -1)
-            G2_TILE(t + 1, 1, false, -1)
+            G2_TILE_PLAIN(t, 0, false, -1)
+            G2_TILE_PLAIN(t + 1, 1, false, -1)
         }
-#undef G2_TILE
         }
 #undef G2_TILE_BAL
 #undef G2_VM
 #undef G2_BARX
 #undef G2_TILE_PLAIN
-#undef G2_TILE_SPLIT
         if (wm == 0) G2_BAR();                       // re-balance the barrier count of the two wave rows
         __builtin_amdgcn_sched_barrier(0);
 
@@ -1126,80 +1046,6 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             G2_BAR();
-        } else if constexpr (EPI != CPX_EPI_RESID_BF16 && (FLAGS & G2F_Q4) != 0) {
-            // ---- quarter-tile epilogue: the tile leaves in four 128-row x 128-column quarters through TWO 34 KB staging
-            // buffers; in stage q a wave first requests its 16-byte chunks of quarter q - 1 from LDS, then converts quarter q
-            // (the VALU stream: LayerNorm fold, bias, GELU, pack) into the other buffer, then stores quarter q - 1 -- the LDS
-            // round trip and the store issue of one quarter run beside the vector work of the next instead of behind it.
-            // Five barriers per tile instead of four; outputs bit for bit those of the two-half epilogue.
-            if (has_next) prefetch_next();
-            char *stg = smem + G2P_STG_OFF;
-            const int srow = tid >> 4, sc16 = tid & 15;          // store side: 32 rows x 16 chunks of 16 bytes per pass
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                uint4 h0 = make_uint4(0u, 0u, 0u, 0u), h1 = h0, h2 = h0, h3 = h0;      // (named registers: an array here goes to scratch)
-                const int hm = (q >> 1) & 1, hn = q & 1;
-                const int phm = ((q - 1) >> 1) & 1, phn = (q - 1) & 1;
-                char *buf = stg + (q & 1) * 34816, *pbuf = stg + ((q - 1) & 1) * 34816;
-                if (q > 0) {
-                    const char *src = pbuf + srow * 272 + sc16 * 16;
-                    h0 = *reinterpret_cast<const uint4 *>(src);
-                    h1 = *reinterpret_cast<const uint4 *>(src + 32 * 272);
-                    h2 = *reinterpret_cast<const uint4 *>(src + 64 * 272);
-                    h3 = *reinterpret_cast<const uint4 *>(src + 96 * 272);
-                }
-                if (q < 4) {
-                    float ln_rs[4], ln_nm[4];
-                    if constexpr (LN_IN) {
-#pragma unroll
-                        for (int mb = 0; mb < 4; ++mb) {
-                            const float2 pr = *reinterpret_cast<const float2 *>(smem + G2P_TAIL + (hm * 128 + wm * 64 + mb * 16 + fr) * 8);
-                            ln_rs[mb] = pr.x; ln_nm[mb] = pr.y;
-                        }
-                    }
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) {
-                        const int nq = wn * 32 + nb * 16 + fq * 4;                  // column inside the quarter
-                        const int nl = hn * 128 + nq;
-                        const float4 b = *reinterpret_cast<const float4 *>(smem + G2P_TAIL + 2048 + nl * 4);
-                        float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if constexpr (LN_IN) cs = *reinterpret_cast<const float4 *>(smem + G2P_TAIL + 3072 + nl * 4);
-#pragma unroll
-                        for (int mb = 0; mb < 4; ++mb) {
-                            const int mlh = wm * 64 + mb * 16 + fr;
-                            f32x4 vv = acc[hm][hn][mb][nb];
-                            if constexpr (LN_IN) {
-                                const float nm = ln_nm[mb], rs = ln_rs[mb];
-                                vv[0] = fmaf(vv[0], rs, fmaf(nm, cs.x, b.x)); vv[1] = fmaf(vv[1], rs, fmaf(nm, cs.y, b.y));
-                                vv[2] = fmaf(vv[2], rs, fmaf(nm, cs.z, b.z)); vv[3] = fmaf(vv[3], rs, fmaf(nm, cs.w, b.w));
-                            } else {
-                                vv[0] += b.x; vv[1] += b.y; vv[2] += b.z; vv[3] += b.w;
-                            }
-                            if constexpr (EPI == CPX_EPI_GELU_BF16) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) vv[r] = gelu_erf(vv[r]);
-                            } else if constexpr (EPI == CPX_EPI_RELU_BF16) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) vv[r] = fmaxf(vv[r], 0.f);
-                            }
-                            uint2 o;
-                            o.x = pack2<F16>(vv[0], vv[1]);
-                            o.y = pack2<F16>(vv[2], vv[3]);
-                            *reinterpret_cast<uint2 *>(buf + mlh * 272 + nq * 2) = o;
-                        }
-                    }
-                }
-                if (q > 0) {
-                    unsigned short *dst = (unsigned short *)g.out + (size_t)(m0 + phm * 128 + srow) * g.ld_out + n0 + phn * 128 + sc16 * 8;
-                    const size_t r32 = (size_t)32 * g.ld_out;
-                    *reinterpret_cast<uint4 *>(dst) = h0;
-                    *reinterpret_cast<uint4 *>(dst + r32) = h1;
-                    *reinterpret_cast<uint4 *>(dst + 2 * r32) = h2;
-                    *reinterpret_cast<uint4 *>(dst + 3 * r32) = h3;
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                G2_BAR();
-            }
         } else if constexpr (EPI != CPX_EPI_RESID_BF16 && (FLAGS & G2F_DIRECT) != 0) {
             // ---- direct epilogue: no LDS staging, no barriers between the halves.  After packing, a lane holds 4 consecutive channels
             // (8 bytes) of token row fr for each of the wave's two 16-channel blocks nb; v_permlane16_swap (vdst = block 0, src = block 1:
@@ -1370,296 +1216,6 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
     }
 }
 
-#ifdef CPX_DEBUG
-// ===========================================================================
-// EXPERIMENT (debug build only, cpx_gemm_set_pingpong): "ping-pong" form, 256 (M) x 128 (N) x 64 tile, 256 threads = 4 waves,
-// TWO workgroups per CU.  Bitwise identical to the 256^2 kernel, race-screened, and 5-8 % SLOWER on every layer shape
-// (profiles/r03_gemm_pingpong_ab.txt) -- kept as the measured record of why:
-//   * the two workgroups of a CU do fall into complementary phases by themselves (89 % of every epilogue runs beside the
-//     partner's main loop, tools/pp_stamps.py), a forced start offset changes nothing;
-//   * but a wave's OWN timeline is the limit: per K tile 64 MFMAs (1 088 cycles) + 12 LDS-DMA instructions at ~60-100 issue
-//     cycles each + two LDS round trips + two barriers = ~2 700 cycles, so the main loop of a 256 x 128 tile takes 43 k cycles
-//     where the MFMAs alone need 17 k: half the tile size means 1.5x the operand bytes -- and DMA instructions -- per MFMA
-//     (0.19 against 0.125 KB), and ~35 B/clk/CU is at the rate one CU can pull from its L2 (~70 GB/s);
-//   * beside another wave's saturating MFMA stream a wave issues one VALU instruction per ~8.5 cycles, not one per 3.3
-//     (tools/micro/coexec.hip), so an overlapped epilogue is also a slower epilogue.
-// ===========================================================================
-// The 256^2 kernel holds a CU with one 8-wave workgroup: while its waves run the VALU-bound epilogue (LayerNorm
-// fold, bias, erf-GELU, conversion, staging, stores: ~40 % of a mlp.lin1 tile) the CU's matrix cores idle, and while
-// they wait at the phase barriers of the main loop nothing else can issue.  Here a workgroup is half as large
-// (4 waves, one per SIMD, <= 256 registers, 80 KB of LDS) so that two of them, working on DIFFERENT tiles and
-// drifting freely against each other, share every SIMD: one workgroup's epilogue VALU stream issues beside the other's
-// MFMA stream (a v_mfma_f32_16x16x32 holds the SIMD's vector issue for 8 of its 16 cycles, tools/micro/coexec.hip), and
-// one's barrier / LDS-latency bubbles are the other's issue slots.
-// Per-wave output = 2 quadrants (hm) of 64 tokens x 64 channels: tokens 128 hm + 64 wm + [0,64), channels 64 wn + [0,64)
-// -> in a phase ALL waves read the same operand items.  Operand items of 16 KB (128 rows x 64 k, lane-linear LDS-DMA
-// image, 16-byte chunk c of row r at position c ^ (r & 7)): per K tile t  W(t), X0(t), X1(t) = items 3t, 3t+1, 3t+2, item
-// j in slot j % 5 of a 5-slot ring.  Two phases per K tile, ONE raw barrier each, behind a counted vmcnt:
-//   A(t): reads W(t), X0(t) -> 32 MFMAs into quadrant 0;  issues item 3t+4 = X0(t+1)   (slot of X1(t-1), read in B(t-1))
-//   B(t): reads X1(t)       -> 32 MFMAs into quadrant 1;  issues items 3t+5, 3t+6 = X1(t+1), W(t+2)  (slots of W(t), X0(t))
-// A slot is re-filled only after the barrier that follows its last reading phase; every item is requested >= 2 phases
-// before the phase that reads it; waits never drain the queue in the steady state (vmcnt(8)).
-#define PP_THREADS 256
-#define PP_SLOT 16384
-#define PP_NSLOT 5
-#define PP_EPI_LD 272                                   // staging row: 128 channels x 2 B + 16
-#define PP_PAR_OFF (256 * PP_EPI_LD)                    // 69632: 256 x (rstd, -mean rstd) behind the staging rows
-#define PP_LDS_BYTES (PP_NSLOT * PP_SLOT)               // 81920 >= PP_PAR_OFF + 2048
-__device__ __forceinline__ u32x4 pp_read128(unsigned addr) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-// Which of a CU's two resident workgroups arrived second?  (arrival counters per CU, monotonically increasing: two
-// consecutive arrivals on a CU always get different parities, so no reset is needed and nothing depends on it but timing)
-__device__ unsigned g_pp_arrival[8 * 256];
-#ifdef CPX_DEBUG
-// diagnostic (g.dbg & 32): s_memtime at tile start / main-loop end / tile end of every workgroup's tiles + its CU key and
-// arrival number: [workgroup < 1024][2 + 3 * 32] 64-bit words, fetched by cpx_gemm_pingpong_stamps
-__device__ unsigned long long g_pp_stamps[1024 * 98];
-#define PP_STAMP(slot_)                                                                                   \
-    do {                                                                                                  \
-        if ((g.dbg & 32) && tid == 0 && blockIdx.x < 1024 && it_ < 32) {                                  \
-            unsigned long long t_;                                                                        \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                    \
-            g_pp_stamps[blockIdx.x * 98 + 2 + 3 * it_ + (slot_)] = t_;                                    \
-        }                                                                                                 \
-    } while (0)
-#else
-#define PP_STAMP(slot_) do { } while (0)
-#endif
-template <int EPI, bool F16, int FLAGS>
-__global__ void __launch_bounds__(PP_THREADS, 2) k_gemm_pp(GemmArgs g) {
-    constexpr bool LN_IN = (FLAGS & G2F_LN) != 0;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int K = g.K, nk = K / 64;
-    // ---- phase offset between the two workgroups of a CU: identical tiles take identical time, so two workgroups that
-    // start together stay in lockstep (both in the main loop, then both in the epilogue) and never complement each other.
-    // The second arrival on a CU therefore waits g.pp_delay x ~8k cycles once; from then on one workgroup's epilogue runs
-    // beside the other's main loop for the whole launch.
-    if (g.pp_delay > 0 || (g.dbg & 32)) {
-        if (tid == 0) {
-            const unsigned hw = __builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4);      // HW_REG_HW_ID bits 15:8 = SE, SH, CU
-            const unsigned xcc = __builtin_amdgcn_s_getreg((2 << 11) | (0 << 6) | 20);    // HW_REG_XCC_ID bits 2:0
-            *reinterpret_cast<unsigned *>(smem) = atomicAdd(&g_pp_arrival[((xcc & 7) << 8) | (hw & 255)], 1u);
-        }
-        __syncthreads();
-        const unsigned arrival = *reinterpret_cast<volatile unsigned *>(smem);
-        __syncthreads();
-#ifdef CPX_DEBUG
-        if ((g.dbg & 32) && tid == 0 && blockIdx.x < 1024) {
-            const unsigned hw = __builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4), xcc = __builtin_amdgcn_s_getreg((2 << 11) | (0 << 6) | 20);
-            g_pp_stamps[blockIdx.x * 98] = ((xcc & 7) << 8) | (hw & 255);
-            g_pp_stamps[blockIdx.x * 98 + 1] = arrival;
-        }
-#endif
-        if (arrival & 1)
-            for (int i = 0; i < g.pp_delay; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-    const int tiles_m = g.n_blocks / g.tiles_n;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
-  int it_ = 0;
-  for (int v = blockIdx.x; v < g.n_blocks; v += gridDim.x, ++it_) {
-    PP_STAMP(0);
-    // workgroup -> tile: ids that share an XCD (id % 8) get a contiguous range; the 64 workgroups an XCD runs at a time
-    // (2 per CU) cover an 8 (M) x 8 (N) super-tile = 8 activation panels + 8 weight panels
-    int tile_m, tile_n;
-    {
-        const int nxcd = 8, q = g.n_blocks / nxcd, r = g.n_blocks % nxcd, x = v % nxcd;
-        const int bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + v / nxcd;
-        if ((tiles_m & 7) == 0 && (g.tiles_n & 7) == 0) {
-            const int grp = bid >> 6, w_ = bid & 63, cgn = g.tiles_n >> 3;
-            const int rg = grp / cgn, cg = grp - rg * cgn;
-            tile_m = rg * 8 + (w_ >> 3);
-            tile_n = cg * 8 + (w_ & 7);
-        } else {
-            tile_m = bid / g.tiles_n;
-            tile_n = bid - tile_m * g.tiles_n;
-        }
-    }
-    const int m0 = tile_m * 256, n0 = tile_n * 128;
-
-    // folded LayerNorm: this thread's token row (m0 + tid) -> (rstd, -mean rstd), parked in LDS after the main loop
-    float ln_rs = 0.f, ln_nm = 0.f;
-    if constexpr (LN_IN) {
-        const float4 a = *reinterpret_cast<const float4 *>(g.ln_stats + (size_t)(m0 + tid) * 8);
-        const float4 b = *reinterpret_cast<const float4 *>(g.ln_stats + (size_t)(m0 + tid) * 8 + 4);
-        const float inv_k = 1.0f / K;
-        const float sum = (a.x + a.z) + (b.x + b.z), sq = (a.y + a.w) + (b.y + b.w);
-        const float mean = sum * inv_k;
-        ln_rs = rsqrtf(fmaxf(sq * inv_k - mean * mean, 0.f) + 1e-6f);
-        ln_nm = -mean * ln_rs;
-    }
-
-    // staging: one item = 128 rows x 64 k = 4 DMA instructions per wave; thread -> (row = 32 q + tid>>3, position tid&7)
-    const int srow = tid >> 3, kc = (tid & 7) ^ (srow & 7);
-    const unsigned short *pX = g.A + (size_t)(m0 + srow) * K + kc * 8;
-    const unsigned short *pW = g.W + (size_t)(n0 + srow) * K + kc * 8;
-    const size_t k32 = (size_t)32 * K, k128 = (size_t)128 * K;
-    char *sdst = smem + wave * 1024;
-    auto issue = [&](const unsigned short *p, int slot) {
-        char *d = sdst + slot * PP_SLOT;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(p + q * k32),
-                                             (__attribute__((address_space(3))) void *)(d + q * 4096), 16, 0, 0);
-    };
-    auto issue_w = [&](int t, int slot) { issue(pW + (size_t)t * 64, slot); };
-    auto issue_x = [&](int hm, int t, int slot) { issue(pX + hm * k128 + (size_t)t * 64, slot); };
-
-    unsigned xa[2], wa[2];                       // per-lane fragment bases (slot offset added per phase)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const unsigned sw = (unsigned)(((ks * 4 + fq) ^ (fr & 7)) << 4);
-        xa[ks] = lds0 + (wm * 64 + fr) * 128 + sw;
-        wa[ks] = lds0 + (wn * 64 + fr) * 128 + sw;
-    }
-
-    f32x4 acc[2][4][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[a][b][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u32x4 fx[4][2], fw[4][2];
-
-    // prologue: items 0..4 = W(0), X0(0), X1(0), W(1), X0(1)
-    issue_w(0, 0); issue_x(0, 0, 1); issue_x(1, 0, 2);
-    if (nk > 1) { issue_w(1, 3); issue_x(0, 1, 4); }
-    int sl = 0;                                  // slot of item 3t = W(t)
-    auto nxt = [](int s_, int d) { int r = s_ + d; return r >= PP_NSLOT ? r - PP_NSLOT : r; };
-    for (int t = 0; t < nk; ++t) {
-        const int s_w = sl, s_x0 = nxt(sl, 1), s_x1 = nxt(sl, 2);
-        // ---- phase A(t)
-        if (t == 0) { if (nk > 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-        else if (t < nk - 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (t >= 1 && t + 1 < nk) issue_x(0, t + 1, nxt(sl, 4));          // item 3t+4 -> slot of item 3t-1
-        {
-            const unsigned ow = (unsigned)s_w * PP_SLOT, ox = (unsigned)s_x0 * PP_SLOT;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { fw[i][0] = pp_read128(wa[0] + ow + i * 2048); fw[i][1] = pp_read128(wa[1] + ow + i * 2048); }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { fx[i][0] = pp_read128(xa[0] + ox + i * 2048); fx[i][1] = pp_read128(xa[1] + ox + i * 2048); }
-        }
-        G2_LGKM0();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb) acc[0][mb][nb] = mfma16v<F16>(fw[nb][ks], fx[mb][ks], acc[0][mb][nb]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- phase B(t)
-        if (t < nk - 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (t + 1 < nk) {
-            issue_x(1, t + 1, nxt(sl, 0));                                 // item 3t+5 -> slot of W(t)
-            if (t + 2 < nk) issue_w(t + 2, nxt(sl, 1));                    // item 3t+6 -> slot of X0(t)
-        }
-        {
-            const unsigned ox = (unsigned)s_x1 * PP_SLOT;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { fx[i][0] = pp_read128(xa[0] + ox + i * 2048); fx[i][1] = pp_read128(xa[1] + ox + i * 2048); }
-        }
-        G2_LGKM0();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb) acc[1][mb][nb] = mfma16v<F16>(fw[nb][ks], fx[mb][ks], acc[1][mb][nb]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        sl = nxt(sl, 3);
-    }
-    // (the vmcnt at the tail depends on how many items were actually issued after the awaited one: see the counts above;
-    // with t + 2 >= nk the B phase issues one item, with t + 1 >= nk none)
-    __builtin_amdgcn_s_barrier();                // every wave is done reading the ring: it becomes the staging area
-    PP_STAMP(1);
-    if constexpr (LN_IN) {
-        *reinterpret_cast<float2 *>(smem + PP_PAR_OFF + tid * 8) = make_float2(ln_rs, ln_nm);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    }
-
-    // ---- epilogue: f32 -> (LayerNorm fold, bias, activation) -> half rows in LDS -> whole 256-byte rows to HBM
-    float4 colb[4], colc[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-        const int nl = wn * 64 + nb * 16 + fq * 4;
-        colb[nb] = g.bias ? *reinterpret_cast<const float4 *>(g.bias + n0 + nl) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (LN_IN) colc[nb] = *reinterpret_cast<const float4 *>(g.ln_colsum + n0 + nl);
-    }
-    // this lane's 8 token rows: LayerNorm parameters to registers BEFORE the staging stores (the stores alias every LDS
-    // pointer for the compiler: read inside the loop, each parameter read would wait for the stores in front of it)
-    float prs[2][4], pnm[2][4];
-#pragma unroll
-    for (int hm = 0; hm < 2; ++hm)
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            prs[hm][mb] = 1.f; pnm[hm][mb] = 0.f;
-            if constexpr (LN_IN) {
-                const float2 pr = *reinterpret_cast<const float2 *>(smem + PP_PAR_OFF + (hm * 128 + wm * 64 + mb * 16 + fr) * 8);
-                prs[hm][mb] = pr.x; pnm[hm][mb] = pr.y;
-            }
-        }
-#pragma unroll
-    for (int hm = 0; hm < 2; ++hm)
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            const int ml = hm * 128 + wm * 64 + mb * 16 + fr;
-            const float rs = prs[hm][mb], nm = pnm[hm][mb];
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) {
-                const int nl = wn * 64 + nb * 16 + fq * 4;
-                f32x4 vv = acc[hm][mb][nb];
-                const float4 b = colb[nb];
-                if constexpr (LN_IN) {
-                    const float4 cs = colc[nb];
-                    vv[0] = fmaf(vv[0], rs, fmaf(nm, cs.x, b.x)); vv[1] = fmaf(vv[1], rs, fmaf(nm, cs.y, b.y));
-                    vv[2] = fmaf(vv[2], rs, fmaf(nm, cs.z, b.z)); vv[3] = fmaf(vv[3], rs, fmaf(nm, cs.w, b.w));
-                } else {
-                    vv[0] += b.x; vv[1] += b.y; vv[2] += b.z; vv[3] += b.w;
-                }
-                if constexpr (EPI == CPX_EPI_GELU_BF16) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) vv[r] = gelu_erf(vv[r]);
-                } else if constexpr (EPI == CPX_EPI_RELU_BF16) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) vv[r] = fmaxf(vv[r], 0.f);
-                }
-                uint2 o;
-                o.x = pack2<F16>(vv[0], vv[1]);
-                o.y = pack2<F16>(vv[2], vv[3]);
-                *reinterpret_cast<uint2 *>(smem + ml * PP_EPI_LD + nl * 2) = o;
-            }
-        }
-    __syncthreads();
-    const int c16 = tid & 15;                    // 16-byte chunk of a 256-byte row
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-        const int ml = it * 16 + (tid >> 4);
-        const uint4 vv = *reinterpret_cast<const uint4 *>(smem + ml * PP_EPI_LD + c16 * 16);
-        *reinterpret_cast<uint4 *>((unsigned short *)g.out + (size_t)(m0 + ml) * g.ld_out + n0 + c16 * 8) = vv;
-    }
-    __syncthreads();                             // staging rows read: the ring may be re-filled for the next tile
-    PP_STAMP(2);
-  }
-}
-
-#endif  // CPX_DEBUG (ping-pong experiment)
-
 CPX_SWITCH(g_gemm_persist, 1);      // 1 = persistent 256^2 kernel (k_gemm256p), 0 = one workgroup per tile (k_gemm256)
 CPX_SWITCH(g_gemm_variant, 1);      // 1 = LDS-DMA staging, 0 = register staging (debug / A-B)
 CPX_SWITCH(g_gemm_dbg, 0);          // timing-only ablations of the 256^2 epilogue
@@ -1671,17 +1227,10 @@ CPX_SWITCH(g_gemm_persist_qkv, 1);  // balanced persistent tile list for the qkv
 CPX_SWITCH(g_gemm_rev, 0);
 CPX_SWITCH(g_gemm_big, 1);          // 1 = use the 256^2 kernel when the shape allows
 CPX_SWITCH(g_gemm_bal, 1);          // 1 = balanced fragment-read schedule of the persistent main loop (G2F_BAL; K >= 256) for the bf16 residual + statistics epilogue, 0 = plain
-CPX_SWITCH(g_gemm_split, 0);        // 1 = counted LDS waits inside the main-loop phases (k_gemm256p<.., G2F_SPLIT>; experiment)
 CPX_SWITCH(g_gemm_direct, 1);       // 1 = direct-store epilogue (G2F_DIRECT) for the GELU epilogue, 2 (debug build) = for every non-residual epilogue, 0 = staged rows
-CPX_SWITCH(g_gemm_epi4, 0);         // 1 = quarter-tile epilogue of the persistent 256^2 kernel (conversion beside the previous quarter's stores)
 CPX_SWITCH(g_gemm_nt, 15);          // bits 0 / 1 / 2: the q / k / V^T thirds of the qkv projection's output leave by non-temporal stores; bit 3 (round 6): the residual epilogues (attn.proj, mlp.lin2) store at agent scope (sc1, written through: proj 73.9 -> 72.4 us, lin2 105.2 -> 103.2 in situ); 15 = production, 0 = ordinary stores (A/B)
-CPX_SWITCH(g_gemm_4w, 1);           // bit 0 (production): mlp.lin1 (bf16, folded LayerNorm + GELU) on the one-wave-per-SIMD kernel (cpx_gemm4w.hip), 0.98 of k_gemm256p;
-                                    // bit 1 (debug build, measured and NOT shipped): attn.proj / mlp.lin2 (residual + row statistics) on it as well -- 1.06 / 1.03 of
-                                    // k_gemm256p (profiles/r05_ab_gemm4w_resid.txt): that epilogue is unpacked integer / f32 vector work, which a lone wave issues at
-                                    // 4 cycles per instruction against 2.9 for two waves of a SIMD.  Same bits either way.
-CPX_SWITCH(g_gemm_pp, 0);           // 1 = ping-pong kernel (256 x 128 tiles, two 4-wave workgroups per CU) for the epilogues it covers
-CPX_SWITCH(g_gemm_pp_persist, 1);   // ping-pong kernel: 1 = two persistent workgroups per CU walk the tiles, 0 = one workgroup per tile
-CPX_SWITCH(g_gemm_pp_delay, 2);     // ping-pong kernel: start offset of a CU's second workgroup, x s_sleep 127 (~8k cycles)
+CPX_SWITCH(g_gemm_4w, 1);           // 1 (production): mlp.lin1 (bf16, folded LayerNorm + GELU) on the one-wave-per-SIMD kernel (cpx_gemm4w.hip), 0.98 of
+                                    // k_gemm256p; 0: on k_gemm256p (same bits)
 #ifdef CPX_DEBUG
 extern "C" void cpx_gemm_set_persistent(int on) { g_gemm_persist = on; }
 extern "C" void cpx_gemm_set_variant(int glds) { g_gemm_variant = glds; }
@@ -1690,28 +1239,10 @@ extern "C" void cpx_gemm_set_persistent_qkv(int on) { g_gemm_persist_qkv = on; }
 extern "C" void cpx_gemm_set_l2_block(int on) { g_gemm_l2 = on; }
 extern "C" void cpx_gemm_set_reverse(int on) { g_gemm_rev = on; }
 extern "C" void cpx_gemm_set_big(int on) { g_gemm_big = on; }
-extern "C" void cpx_gemm_set_epi4(int on) { g_gemm_epi4 = on; }
-extern "C" void cpx_gemm_set_split(int on) { g_gemm_split = on; }
 extern "C" void cpx_gemm_set_direct(int on) { g_gemm_direct = on; }
 extern "C" void cpx_gemm_set_balanced(int on) { g_gemm_bal = on; }
-extern "C" void cpx_gemm_set_pingpong(int on) { g_gemm_pp = on; }
 extern "C" void cpx_gemm_set_4w(int on) { g_gemm_4w = on; }
 extern "C" void cpx_gemm_set_nt(int on) { g_gemm_nt = on; }
-extern "C" void cpx_gemm_set_pingpong_opts(int persistent, int delay) { g_gemm_pp_persist = persistent; g_gemm_pp_delay = delay; }
-#endif
-
-#ifdef CPX_DEBUG
-// workgroups of the ping-pong kernel the runtime admits per CU (2 is the design point: 2 x 80 KB of LDS = all 160 KB)
-extern "C" int cpx_gemm_pingpong_stamps(unsigned long long *host_out, size_t n_words) {
-    if (n_words > 1024 * 98) n_words = 1024 * 98;
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_pp_stamps), n_words * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-extern "C" int cpx_gemm_pingpong_occupancy(void) {
-    int n = -1;
-    (void)hipFuncSetAttribute((const void *)k_gemm_pp<CPX_EPI_GELU_BF16, false, G2F_LN>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_gemm_pp<CPX_EPI_GELU_BF16, false, G2F_LN>, PP_THREADS, PP_LDS_BYTES) != hipSuccess) return -1;
-    return n;
-}
 #endif
 
 template <int EPI, bool F16, int FLAGS>
@@ -1757,31 +1288,6 @@ static bool launch_gemm256(const GemmArgs &a0, hipStream_t s) {
         if (!g_gemm_big || a0.M % 256 || a0.N % 256 || a0.K < 128) return false;
         if ((a0.K / 64) % 2 && EPI != CPX_EPI_POS_BF16) return false;
         if ((a0.M / 256) * (a0.N / 256) < 256) return false;          // not enough tiles for 256 CUs
-#ifdef CPX_DEBUG
-        if constexpr (EPI == CPX_EPI_BF16 || EPI == CPX_EPI_GELU_BF16 || EPI == CPX_EPI_RELU_BF16) {
-            if (g_gemm_pp) {
-                GemmArgs p = a0;
-                p.tiles_n = p.N / 128; p.n_blocks = (p.M / 256) * (p.N / 128);
-                static CpxOncePerDevice once_pp;
-                once_pp([] {
-                    (void)hipFuncSetAttribute((const void *)k_gemm_pp<EPI, F16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES);
-                    (void)hipFuncSetAttribute((const void *)k_gemm_pp<EPI, F16, G2F_LN>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES);
-                });
-                static int n_cu_pp = 0;
-                if (!n_cu_pp) {
-                    int dev = 0, cus = 256;
-                    (void)hipGetDevice(&dev);
-                    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                    n_cu_pp = cus > 0 ? cus : 256;
-                }
-                const int grid = g_gemm_pp_persist ? (p.n_blocks < 2 * n_cu_pp ? p.n_blocks : 2 * n_cu_pp) : p.n_blocks;
-                p.pp_delay = g_gemm_pp_delay;
-                if (p.ln_stats) hipLaunchKernelGGL((k_gemm_pp<EPI, F16, G2F_LN>), dim3(grid), dim3(PP_THREADS), PP_LDS_BYTES, s, p);
-                else hipLaunchKernelGGL((k_gemm_pp<EPI, F16, 0>), dim3(grid), dim3(PP_THREADS), PP_LDS_BYTES, s, p);
-                return true;
-            }
-        }
-#endif
         GemmArgs a = a0;
         a.tiles_n = a.N / 256; a.n_blocks = (a.M / 256) * (a.N / 256);
         // one instantiation per (LayerNorm consumer | statistics producer) x (timing ablations, bf16 only)
@@ -1814,38 +1320,13 @@ static bool launch_gemm256(const GemmArgs &a0, hipStream_t s) {
                 }
             }
 #endif
-#ifdef CPX_DEBUG
-            if (g_gemm_split) {
-                if (f1) launch_gemm256_flags<EPI, F16, F1 | G2F_SPLIT>(a, s);
-                else launch_gemm256_flags<EPI, F16, G2F_SPLIT>(a, s);
-                return true;
-            }
-#endif
-#ifdef CPX_DEBUG
-            if constexpr (EPI != CPX_EPI_RESID_BF16) {
-                if (g_gemm_epi4) {
-                    if (f1) launch_gemm256_flags<EPI, F16, F1 | G2F_Q4>(a, s);
-                    else launch_gemm256_flags<EPI, F16, G2F_Q4>(a, s);
-                    return true;
-                }
-            }
-#endif
             // mlp.lin1 of the bf16 network (folded LayerNorm + bias + erf-GELU) on the one-wave-per-SIMD kernel: bitwise equal to the
             // k_gemm256p instantiation below, its main loop and its epilogue both faster (profiles/r05_ab_gemm4w_*.txt)
             if constexpr (EPI == CPX_EPI_GELU_BF16) {
-                if ((g_gemm_4w & 1) && f1 && a.bias && a.K >= 256 && (a.K / 64) % 2 == 0 &&
+                if (g_gemm_4w && f1 && a.bias && a.K >= 256 && (a.K / 64) % 2 == 0 &&
                     cpx_gemm4w_gelu_ln(F16 ? 1 : 0, a.A, a.W, a.M, a.N, a.K, a.bias, a.ln_stats, a.ln_colsum, a.out, a.ld_out, s))
                     return true;
             }
-#ifdef CPX_DEBUG
-            // attn.proj / mlp.lin2 of the bf16 network (residual + row statistics, N = 1024) on that kernel: bitwise equal to k_gemm256p<.., F1 | G2F_BAL>
-            // and 3 - 6 % SLOWER, so only the debug build's cpx_gemm_set_4w(3) takes this branch (g_gemm_4w is the constant 1 in the product)
-            if constexpr (EPI == CPX_EPI_RESID_BF16 && !F16) {
-                if ((g_gemm_4w & 2) && f1 && a.bias && a.aux && a.N == 1024 && a.K >= 256 && (a.K / 64) % 2 == 0 &&
-                    cpx_gemm4w_resid_stats(a.A, a.W, a.M, a.N, a.K, a.bias, a.aux, a.out, a.ld_out, a.stats_out, s))
-                    return true;
-            }
-#endif
             // direct-store epilogue (G2F_DIRECT): production for the GELU epilogue (mlp.lin1 -3.5 %, bitwise equal); the lighter epilogues
             // measured equal or slower with it (qkv +1.2 %) and keep the staged rows -- cpx_gemm_set_direct(2) in the debug build forces it
             // on the plain and ReLU epilogues.  Not on qkv: forced onto the balanced q|k / V^T tile list it wrote scattered wrong q|k elements
@@ -1955,7 +1436,7 @@ int cpx_gemm_half(int dtype, const void *A, const void *Wt, int M, int N, int K,
     a.tiles_n = N / BN; a.n_blocks = (M / BM) * (N / BN);
     a.ln_stats = ln_stats; a.ln_colsum = ln_colsum; a.stats_out = stats_out; a.l2_block = g_gemm_l2; a.dbg = g_gemm_dbg; a.nt_out = g_gemm_nt;
     a.rev_m = (g_gemm_rev && K >= 4096) ? 1 : 0;
-    a.conv_c = 0; a.pp_delay = 0; a.epi4 = g_gemm_epi4;
+    a.conv_c = 0;
     hipStream_t s = (hipStream_t)stream;
     switch (epilogue) {
         case CPX_EPI_BF16: launch_gemm<CPX_EPI_BF16>(a, s, f16); break;
@@ -1985,7 +1466,7 @@ int cpx_conv3_half(int dtype, const void *x, const void *Wt, int M, int N, int C
     a.M = M; a.N = N; a.K = 9 * C; a.bias = bias; a.aux = nullptr; a.out = out; a.ld_out = ld_out;
     a.tiles_n = N / BN; a.n_blocks = (M / BM) * (N / BN);
     a.ln_stats = nullptr; a.ln_colsum = nullptr; a.stats_out = nullptr; a.l2_block = 0; a.dbg = 0; a.rev_m = 0; a.nt_out = 0;
-    a.conv_c = C; a.pp_delay = 0; a.epi4 = 0;
+    a.conv_c = C;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(a.n_blocks), block(GEMM_THREADS);
     const size_t lds = 2 * STAGE_BYTES;

@@ -59,17 +59,10 @@ int cpx_gemm_half_uses_big_tile(int M, int N, int K, int epilogue);
 // one-wave-per-SIMD 256^2 kernel (cpx_gemm4w.hip), bf16 / fp16: gelu(folded-LayerNorm(A) W^T + bias); 1 = launched, 0 = not this kernel's shape
 int cpx_gemm4w_gelu_ln(int f16, const void *A, const void *W, int M, int N, int K, const float *bias, const float *ln_stats, const float *ln_colsum,
                        void *out, int ld_out, hipStream_t s);
-// ... and bf16(bf16(A W^T + bias) + resid) with the partial row statistics of the output (N = 1024); resid may be out
-int cpx_gemm4w_resid_stats(const void *A, const void *W, int M, int N, int K, const float *bias, const void *resid, void *out, int ld_out,
-                           float *stats_out, hipStream_t s);
 int cpx_layernorm_half(int dtype, const void *x, const float *w, const float *b, int rows, int C, float eps,
                        void *out, void *stream);
 int cpx_attention_half(int dtype, const void *qkv, const void *rel_h, const void *rel_w, int n_subtiles, void *vT_ws,
                        void *out, void *stream, bool transpose_v);
-int cpx_attention_trv_enabled(void);
-// round-4 attention kernel (cpx_attn2q.hip): one wave per SIMD, two query rows per wave; vT holds V^T already
-int cpx_attention2q_launch(int dtype, const void *qkv, const void *vT, const void *rel_h, const void *rel_w,
-                           int n_subtiles, void *out, int gl, hipStream_t s);
 // production attention kernel (cpx_attn2w.hip): two query rows per wave, two workgroups per CU; vT holds V^T already
 int cpx_attention2w_launch(int dtype, const void *qkv, const void *vT, const void *rel_h, const void *rel_w,
                            int n_subtiles, void *out, int xcd_order, hipStream_t s);

@@ -170,514 +170,18 @@ __global__ void __launch_bounds__(256) k_v_transpose(const unsigned short *__res
 // flash attention with decomposed rel-pos bias
 // ---------------------------------------------------------------------------
 #define ATT_THREADS 256
-#define GS_LD 65                       // padded row of the per-wave G scratch (floats)
 __device__ __forceinline__ int pi_perm(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
-#ifdef CPX_DEBUG   // ---- non-production attention kernels (variant 0: register ring; variant 1: 8-wave ping-pong) + stamps
-// DBG = true: diagnostic build with s_memtime stamps per loop segment (never used in production;
-// stamp values only go to `dbg`, no output depends on them)
-#define ATT_STAMP(i)                                                                           \
-    do {                                                                                       \
-        if constexpr (DBG) {                                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-            unsigned long long t_;                                                             \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");         \
-            seg[i] += (unsigned)(t_ - tprev);                                                  \
-            tprev = t_;                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-        }                                                                                      \
-    } while (0)
-#define ATT_FORCE(x)                                                                           \
-    do {                                                                                       \
-        if constexpr (DBG) { float d_; asm volatile("v_mov_b32 %0, %1" : "=v"(d_) : "v"(x)); asm volatile("" ::"v"(d_)); } \
-    } while (0)
-// TRV: V is read in its natural [token][d] layout straight from the qkv rows and transposed by the LDS read
-// (ds_read_b64_tr_b16) instead of coming pre-transposed from a V^T buffer written by the qkv GEMM
-template <bool F16, bool DBG = false, bool TRV = false>
-__global__ void __launch_bounds__(ATT_THREADS, 3) k_attention(const unsigned short *__restrict__ qkv,
-                                                           const unsigned short *__restrict__ vT,
-                                                           const unsigned short *__restrict__ relh,
-                                                           const unsigned short *__restrict__ relw,
-                                                           unsigned short *__restrict__ out,
-                                                           unsigned *__restrict__ dbg = nullptr,
-                                                           int g_att_xcd_order = 1) {
-    unsigned seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = 0, tstart = 0;
-    if constexpr (DBG) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tstart)::"memory"); tprev = tstart; }
-    __shared__ __attribute__((aligned(16))) unsigned short sK[2][32 * 64];
-    __shared__ __attribute__((aligned(16))) unsigned short sV[2][64 * 32];
-    __shared__ float sG[4][32 * GS_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h2 = lane >> 5;
-    const unsigned lds_v = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned short *)&sV[0][0];
-    // XCD-aware block order: workgroups go round-robin to the 8 XCDs by linear id, and the 8 row groups of
-    // one (sub-tile, head) stream the same 256 KB of K / V^T -- keep them on ONE XCD's L2 (per-XCD order:
-    // 8 consecutive workgroups = one pair) instead of fetching that pair once per XCD (fabric reads / 8)
-    const int lin = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    int rg = blockIdx.x, head = blockIdx.y, s = blockIdx.z;
-    if (g_att_xcd_order) {
-        const int j = lin >> 3, pair = (j >> 3) * 8 + (lin & 7);
-        rg = j & 7; head = pair & 15; s = pair >> 4;
-    }
-    const int qh = rg * 4 + wave;                         // image row of this wave's queries
-    const size_t tok0 = (size_t)s * 1024;
-    const unsigned short *qrow = qkv + (tok0 + qh * 32 + r) * 3072 + head * 64;
-
-    // Q fragments (MFMA B operand): d = 16*ks + 8*h2 + j
-    uint4 qf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const uint4 *>(qrow + 16 * ks + 8 * h2);
-
-    // G = Q . table^T  (tables hold rel_pos / scale, row 63 = 0) -> LDS scratch [q][j]
-    float *G = sG[wave];
-    float gw[16];
-    auto compute_G = [&](const unsigned short *table) {
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                uint4 tf = *reinterpret_cast<const uint4 *>(table + (jb * 32 + r) * 64 + 16 * ks + 8 * h2);
-                acc = mfma32<F16>(tf, qf[ks], acc);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                int j = jb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h2;
-                G[r * GS_LD + j] = acc[i];
-            }
-        }
-    };
-    compute_G(relw);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        int kw = pi_perm((i & 3) + 8 * (i >> 2) + 4 * h2);
-        gw[i] = G[r * GS_LD + (r - kw + 31)];
-    }
-    compute_G(relh);                                       // G now holds Gh for the key loop
-
-    // staging maps
-    const int k_key = tid >> 3, k_c = tid & 7;            // K tile: 32 keys x 8 chunks
-    const int v_d = tid >> 2, v_c = tid & 3;              // V^T tile: 64 d x 4 chunks
-    const unsigned short *kbase = qkv + (tok0 + k_key) * 3072 + 1024 + head * 64 + k_c * 8;
-    const unsigned short *vbase = TRV ? qkv + (tok0 + k_key) * 3072 + 2048 + head * 64 + k_c * 8
-                                      : vT + (((size_t)s * 16 + head) * 64 + v_d) * 1024 + v_c * 8;
-    const size_t v_tile_step = TRV ? (size_t)32 * 3072 : 32;            // elements from one key tile to the next
-    const int k_dst = k_key * 64 + ((k_c ^ (k_key & 7)) * 8);
-    // TRV image: [32 keys][64 d], 16-byte chunk c of key row k at position c ^ 4*((k>>1)&1): the four rows a
-    // transposed read touches per half-wave then fall on disjoint banks
-    const int v_dst = TRV ? k_key * 64 + ((k_c ^ (((k_key >> 1) & 1) * 4)) * 8)
-                          : v_d * 32 + ((v_c ^ ((v_d >> 2) & 3)) * 8);
-    // K / V^T tiles reach LDS through a 4-deep REGISTER ring: the global loads for key tile t+3 are
-    // issued in iteration t and written to LDS at the end of iteration t+2, so each load has two
-    // full iterations to land (one iteration did not cover the L2/HBM latency: a lone workgroup
-    // spent ~1800 cycles per 32-key tile waiting for it).
-    uint4 kr0, kr1, kr2, kr3, vr0, vr1, vr2, vr3;      // named (statically indexed) so they stay in VGPRs
-    kr0 = *reinterpret_cast<const uint4 *>(kbase);
-    vr0 = *reinterpret_cast<const uint4 *>(vbase);
-    kr1 = *reinterpret_cast<const uint4 *>(kbase + (size_t)1 * 32 * 3072);
-    vr1 = *reinterpret_cast<const uint4 *>(vbase + 1 * v_tile_step);
-    kr2 = *reinterpret_cast<const uint4 *>(kbase + (size_t)2 * 32 * 3072);
-    vr2 = *reinterpret_cast<const uint4 *>(vbase + 2 * v_tile_step);
-    kr3 = kr0; vr3 = vr0;
-    *reinterpret_cast<uint4 *>(&sK[0][k_dst]) = kr0;
-    *reinterpret_cast<uint4 *>(&sV[0][v_dst]) = vr0;
-    __syncthreads();
-
-    f32x16 O[2], GW, Lacc;                                   // Lacc row 0 = running softmax denominator
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { O[0][i] = 0.f; O[1][i] = 0.f; GW[i] = gw[i]; Lacc[i] = 0.f; }
-    // A operand whose row 0 is all ones: (ones . P^T)[0][q] = sum_k P[k][q], summed over both
-    // half-waves by the MFMA itself -> no VALU adds and no cross-lane reduction for the row sums
-    const unsigned one2 = F16 ? 0x3C003C00u : 0x3F803F80u;
-    const uint4 ones_f = r == 0 ? make_uint4(one2, one2, one2, one2) : make_uint4(0, 0, 0, 0);
-    float m_run = -1e30f;
-    const float cexp = 0.125f * 1.44269504088896340736f;   // softmax scale (64^-0.5) * log2(e)
-    // P is kept HEADROOM octaves below 1 (a uniform factor that cancels in O / l): bf16 has f32's exponent range,
-    // fp16 starts losing mantissa bits below 2^-14, so its headroom is smaller
-    constexpr float HEADROOM = F16 ? 3.0f : 6.0f;
-    const int krow = pi_perm(r);                            // key row this lane feeds to the K operand
-
-    ATT_STAMP(7);                                      // prologue (Q load, G products, first tiles)
-    auto tile = [&](const int kh, const int buf, uint4 &k_ld, uint4 &v_ld, const uint4 &k_st, const uint4 &v_st) {
-        if (kh + 3 < 32) {
-            k_ld = *reinterpret_cast<const uint4 *>(kbase + (size_t)(kh + 3) * 32 * 3072);
-            v_ld = *reinterpret_cast<const uint4 *>(vbase + (kh + 3) * v_tile_step);
-        }
-        // S' = K . Q^T + Gw   (Gw rides in as the MFMA C operand; Gh is one scalar per lane and
-        // is folded into the exponent offset, so the bias costs no per-element VALU work)
-        const float gh = G[r * GS_LD + (qh - kh + 31)];
-        f32x16 S;
-        {
-            uint4 kf = *reinterpret_cast<const uint4 *>(&sK[buf][krow * 64 + (((0 + h2) ^ (krow & 7)) * 8)]);
-            S = mfma32<F16>(kf, qf[0], GW);
-        }
-#pragma unroll
-        for (int ks = 1; ks < 4; ++ks) {
-            uint4 kf = *reinterpret_cast<const uint4 *>(&sK[buf][krow * 64 + (((2 * ks + h2) ^ (krow & 7)) * 8)]);
-            S = mfma32<F16>(kf, qf[ks], S);
-        }
-        ATT_FORCE(S[15]); ATT_STAMP(0);                 // gh + K fragment reads + 4 QK MFMAs
-        // online softmax (per lane = per query; the two half-waves hold different keys) without a per-tile max
-        // chain: P is formed against the running reference first and the PACKED words are OR-ed; bit 14 / 30 of
-        // the OR is set iff some p >= 2 (exponent MSB of a non-negative half) or the reference is still -inf.
-        // Only then the exact maximum / rescale runs (wave-uniform branch); it puts the reference HEADROOM
-        // octaves above the true maximum, so it is taken for the first tile and for genuine outliers only.
-        float p[16];
-        unsigned pk[8];
-        {
-            // scale + offset as 16 single fmas with the scale as a literal (v_fmamk_f32, a VOP2 encoding): measured on
-            // gfx950 (tools/micro/valu_issue.hip) a v_pk_fma_f32 costs ~9.7 issue cycles per wave with three waves
-            // on the SIMD against ~3.7 for v_fma_f32, i.e. the packed form is slower per element
-            const float off = (gh - m_run) * cexp;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) p[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(S[i], cexp, off));
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pk[j] = pack2<F16>(p[2 * j], p[2 * j + 1]);
-        }
-        ATT_FORCE(__uint_as_float(pk[7])); ATT_STAMP(1);   // fma + exp + pack
-        if (__builtin_expect(__any(((pk[0] | pk[1] | pk[2]) | (pk[3] | pk[4] | pk[5]) | (pk[6] | pk[7])) & 0x40004000u), 0)) {
-            float mx = __builtin_fmaxf(__builtin_fmaxf(S[0], S[1]), S[2]);
-#pragma unroll
-            for (int i = 3; i < 15; i += 2) mx = __builtin_fmaxf(__builtin_fmaxf(mx, S[i]), S[i + 1]);
-            mx = __builtin_fmaxf(mx, S[15]);
-            mx = __builtin_fmaxf(mx, __shfl_xor(mx, 32)) + gh + HEADROOM / cexp;
-            const float m_new = __builtin_fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cexp);
-            Lacc[0] *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { O[0][i] *= alpha; O[1][i] *= alpha; }
-            m_run = m_new;
-            const float off = (gh - m_run) * cexp;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) p[i] = __builtin_amdgcn_exp2f(S[i] * cexp + off);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pk[j] = pack2<F16>(p[2 * j], p[2 * j + 1]);
-        }
-        // P^T (accumulator layout) -> B operand of the P.V product, natural key order
-        uint4 pf[2];
-        pf[0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-        pf[1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-        ATT_FORCE(__uint_as_float(pf[1].w)); ATT_STAMP(2);   // fma + exp + pack
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-            const int d = db * 32 + r;
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                uint4 vf;
-                if constexpr (TRV) {
-                    // lane 16g + 4q + p supplies the address of key row k0 + q, d columns 4p..4p+3 of its group's
-                    // 16-column block and receives d column (lane & 15) of the 4 rows: two reads = 8 keys
-                    const int p_ = lane & 3, q_ = (lane >> 2) & 3, g1 = (lane >> 4) & 1;
-                    const int c = db * 4 + g1 * 2 + (p_ >> 1);
-                    unsigned long long lo, hi;
-                    {
-                        const int row = st * 16 + h2 * 8 + q_;
-                        const unsigned a = lds_v + (unsigned)(buf * 64 * 32 + row * 64 + ((c ^ (((row >> 1) & 1) * 4)) * 8) + (p_ & 1) * 4) * 2;
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(a));
-                    }
-                    {
-                        const int row = st * 16 + h2 * 8 + 4 + q_;
-                        const unsigned a = lds_v + (unsigned)(buf * 64 * 32 + row * 64 + ((c ^ (((row >> 1) & 1) * 4)) * 8) + (p_ & 1) * 4) * 2;
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(a));
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    vf = make_uint4((unsigned)lo, (unsigned)(lo >> 32), (unsigned)hi, (unsigned)(hi >> 32));
-                } else {
-                    vf = *reinterpret_cast<const uint4 *>(&sV[buf][d * 32 + (((2 * st + h2) ^ ((d >> 2) & 3)) * 8)]);
-                }
-                O[db] = mfma32<F16>(vf, pf[st], O[db]);
-            }
-        }
-        Lacc = mfma32<F16>(ones_f, pf[0], Lacc);
-        Lacc = mfma32<F16>(ones_f, pf[1], Lacc);
-        ATT_FORCE(O[1][15]); ATT_FORCE(Lacc[15]); ATT_STAMP(3);   // V fragment reads + 6 PV / ones MFMAs
-        if (kh + 1 < 32) {
-            *reinterpret_cast<uint4 *>(&sK[buf ^ 1][k_dst]) = k_st;
-            *reinterpret_cast<uint4 *>(&sV[buf ^ 1][v_dst]) = v_st;
-        }
-        ATT_STAMP(4);                                   // wait for the prefetched tile + LDS writes
-        __syncthreads();
-        ATT_STAMP(5);                                   // barrier
-    };
-    for (int kh0 = 0; kh0 < 32; kh0 += 4) {          // ring slot of tile t is t & 3
-        tile(kh0 + 0, 0, kr3, vr3, kr1, vr1);
-        tile(kh0 + 1, 1, kr0, vr0, kr2, vr2);
-        tile(kh0 + 2, 0, kr1, vr1, kr3, vr3);
-        tile(kh0 + 3, 1, kr2, vr2, kr0, vr0);
-    }
-    if constexpr (DBG) {
-        unsigned long long tend;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tend)::"memory");
-        if (lane == 0) {
-            unsigned *d = dbg + (size_t)lin * 4 * 9 + wave * 9;
-            for (int i = 0; i < 8; ++i) d[i] = seg[i];
-            d[8] = (unsigned)(tend - tstart);
-        }
-    }
-    // row 0 of Lacc sits in register 0 of the lower half-wave (row = (reg&3)+8*(reg>>2)+4*h2)
-    const float l_tot = __shfl(Lacc[0], r);
-    const float inv = 1.0f / l_tot;
-    unsigned short *orow = out + (tok0 + qh * 32 + r) * 1024 + head * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int d = db * 32 + 8 * g4 + 4 * h2;
-            uint2 o;
-            o.x = (unsigned)h_from_f32<F16>(O[db][4 * g4 + 0] * inv) | ((unsigned)h_from_f32<F16>(O[db][4 * g4 + 1] * inv) << 16);
-            o.y = (unsigned)h_from_f32<F16>(O[db][4 * g4 + 2] * inv) | ((unsigned)h_from_f32<F16>(O[db][4 * g4 + 3] * inv) << 16);
-            *reinterpret_cast<uint2 *>(orow + d) = o;
-        }
-}
-
-
 // ---------------------------------------------------------------------------
-// flash attention, 8-wave ping-pong layout (the production kernel)
+// flash attention, 4 waves per workgroup, LDS-DMA ring + software-pipelined S (debug build: variant 7, the bitwise
+// reference of tests/test_gpu_attn2w.py; the production kernel of rounds 2-5, replaced by k_attention2w of cpx_attn2w.hip)
 // ---------------------------------------------------------------------------
-// One workgroup = 512 threads = 8 waves = 8 image rows of queries of one (sub-tile, head); two waves
-// per SIMD.  Every wave runs the same software-pipelined loop over the 32 key tiles (image rows)
-//     V-phase(t):  softmax of tile t from S (VALU: scale+offset, exp2, row sum, pack)      | barrier
-//     MM-phase(t): O += V_t^T P_t ; S = K_{t+1} Q^T + Gw (8 MFMAs) + K/V ring traffic       | barrier
-// and waves 4-7 run ONE barrier interval behind waves 0-3, so that on every SIMD one wave is in
-// its matrix phase while its partner is in its vector phase (MI355X_MICROARCH "Two waves per
-// SIMD": the matrix pipe and the VALU issue of a SIMD are shared by its two waves; complementary
-// segments are what nets).  K / V^T tiles go through a 4-slot LDS ring: each thread loads 16 bytes
-// of tile t+4 in MM(t) and writes the 16 bytes of tile t+2 it loaded two iterations earlier (a slot is
-// rewritten >= 2 barriers after its last read, and read >= 1 barrier after its last write).
-// Softmax without a per-tile max chain: P is formed against the running reference maximum and the
-// PACKED half-precision words are OR-ed together; bit 14 / 30 of the OR is set iff some p >= 2 (or
-// the reference is still -inf), and only then the exact maximum / rescale path runs (wave-uniform
-// branch); that path puts the reference HEADROOM octaves above the true maximum, so it is taken for
-// the first tile and for genuine outliers only.  Row sums are f32 VALU adds in the vector phase (the matrix phase is the longer one here).
-#define A8_THREADS 512
-#define A8_SLOT_BYTES 8192              // K tile (32 keys x 64 d) + V^T tile (64 d x 32 keys), halves
-#define A8_STAMP(i)                                                                            \
-    do {                                                                                       \
-        if constexpr (DBG) {                                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-            unsigned long long t_;                                                             \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");         \
-            seg[i] += (unsigned)(t_ - tprev);                                                  \
-            tprev = t_;                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-        }                                                                                      \
-    } while (0)
-template <bool F16, bool DBG = false>
-__global__ void __launch_bounds__(A8_THREADS, 2) k_attention8(const unsigned short *__restrict__ qkv,
-                                                              const unsigned short *__restrict__ vT,
-                                                              const unsigned short *__restrict__ relh,
-                                                              const unsigned short *__restrict__ relw,
-                                                              unsigned short *__restrict__ out, int xcd_order,
-                                                              unsigned *__restrict__ dbg = nullptr) {
-    unsigned seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = 0, tstart = 0;
-    if constexpr (DBG) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tstart)::"memory"); tprev = tstart; }
-    __shared__ __attribute__((aligned(16))) unsigned short sKV[4 * A8_SLOT_BYTES / 2];
-    __shared__ float sG[8][32 * GS_LD];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h2 = lane >> 5;
-    // the 4 workgroups of one (sub-tile, head) pair stream the same 256 KB of K / V^T: same XCD (lin % 8)
-    const int lin = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    int rg = blockIdx.x, head = blockIdx.y, s = blockIdx.z;
-    if (xcd_order) {
-        const int j = lin >> 3, pair = (j >> 2) * 8 + (lin & 7);
-        rg = j & 3; head = pair & 15; s = pair >> 4;
-    }
-    const int qh = rg * 8 + wave;
-    const size_t tok0 = (size_t)s * 1024;
-    const unsigned short *qrow = qkv + (tok0 + qh * 32 + r) * 3072 + head * 64;
-    uint4 qf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const uint4 *>(qrow + 16 * ks + 8 * h2);
-
-    // K / V^T ring staging: threads 0..255 move K chunks (key = tid>>3, chunk = tid&7), 256..511 V^T chunks
-    const bool is_k = tid < 256;
-    const int t2 = tid & 255;
-    const int k_key = t2 >> 3, k_c = t2 & 7, v_d = t2 >> 2, v_c = t2 & 3;
-    const unsigned short *gsrc = is_k ? qkv + (tok0 + k_key) * 3072 + 1024 + head * 64 + k_c * 8
-                                      : vT + (((size_t)s * 16 + head) * 64 + v_d) * 1024 + v_c * 8;
-    const size_t gstep = is_k ? (size_t)32 * 3072 : 32;
-    const int sdst = is_k ? k_key * 64 + ((k_c ^ (k_key & 7)) * 8) : 2048 + v_d * 32 + ((v_c ^ ((v_d >> 2) & 3)) * 8);
-    const uint4 st0 = *reinterpret_cast<const uint4 *>(gsrc);
-    const uint4 st1 = *reinterpret_cast<const uint4 *>(gsrc + gstep);
-    // staged registers: at the top of iteration kh, st_a / st_b (kh even / odd) holds tile kh + 2, loaded two iterations ago
-    uint4 st_a = *reinterpret_cast<const uint4 *>(gsrc + 2 * gstep);
-    uint4 st_b = *reinterpret_cast<const uint4 *>(gsrc + 3 * gstep);
-
-    // G = Q . table^T (tables hold rel_pos / scale, row 63 = 0) -> this wave's LDS scratch [q][j]
-    float *G = sG[wave];
-    auto compute_G = [&](const unsigned short *table) {
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                uint4 tf = *reinterpret_cast<const uint4 *>(table + (jb * 32 + r) * 64 + 16 * ks + 8 * h2);
-                acc = mfma32<F16>(tf, qf[ks], acc);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) G[r * GS_LD + jb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h2] = acc[i];
-        }
-    };
-    compute_G(relw);
-    f32x16 GW;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) GW[i] = G[r * GS_LD + (r - pi_perm((i & 3) + 8 * (i >> 2) + 4 * h2) + 31)];
-    compute_G(relh);
-
-    *reinterpret_cast<uint4 *>(&sKV[0 * (A8_SLOT_BYTES / 2) + sdst]) = st0;
-    *reinterpret_cast<uint4 *>(&sKV[1 * (A8_SLOT_BYTES / 2) + sdst]) = st1;
-    __syncthreads();
-
-    const int krow = pi_perm(r);
-    auto qk = [&](const int slot) {          // S'^T = K . Q^T + Gw for the tile in ring slot `slot`
-        const unsigned short *kb = &sKV[slot * (A8_SLOT_BYTES / 2) + krow * 64];
-        f32x16 S = mfma32<F16>(*reinterpret_cast<const uint4 *>(kb + ((h2 ^ (krow & 7)) * 8)), qf[0], GW);
-#pragma unroll
-        for (int ks = 1; ks < 4; ++ks)
-            S = mfma32<F16>(*reinterpret_cast<const uint4 *>(kb + (((2 * ks + h2) ^ (krow & 7)) * 8)), qf[ks], S);
-        return S;
-    };
-    f32x16 S = qk(0);
-    f32x16 O0, O1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { O0[i] = 0.f; O1[i] = 0.f; }
-    float m_run = -1e30f, l_run = 0.f;
-    const float cexp = 0.125f * 1.44269504088896340736f;   // softmax scale (64^-0.5) * log2(e)
-    const f32x2_t c2 = {cexp, cexp};
-    // P is kept a few octaves below 1 (a uniform factor that cancels in O / l): bf16 has f32's exponent range,
-    // fp16 starts losing mantissa bits below 2^-14, so its headroom is smaller
-    constexpr float HEADROOM = F16 ? 3.0f : 6.0f;
-
-    A8_STAMP(7);                                            // prologue
-    if (wave >= 4) __builtin_amdgcn_s_barrier();            // waves 4-7 run one barrier interval behind
-    A8_STAMP(6);
-
-    // one key tile: kh = tile index, SLOT = kh & 3 (static)
-    auto tile = [&](const int kh, auto slot_tag, uint4 &st) {
-        constexpr int SLOT = decltype(slot_tag)::value;
-        // ---- vector phase: softmax of tile kh
-        const float gh = G[r * GS_LD + (qh - kh + 31)];
-        unsigned pk[8];
-        float p[16];
-        {
-            const float off = (gh - m_run) * cexp;
-            const f32x2_t off2 = {off, off};
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                const f32x2_t sv = {S[i], S[i + 1]};
-                const f32x2_t a = sv * c2 + off2;
-                p[i] = __builtin_amdgcn_exp2f(a[0]);
-                p[i + 1] = __builtin_amdgcn_exp2f(a[1]);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pk[j] = pack2<F16>(p[2 * j], p[2 * j + 1]);
-        }
-        // some p >= 2 (bit 14 of a half = exponent MSB; p is never negative) or the reference is still -inf?
-        const unsigned big = F16 ? 0x40004000u : 0x40004000u;
-        if (__builtin_expect(__any(((pk[0] | pk[1] | pk[2]) | (pk[3] | pk[4] | pk[5]) | (pk[6] | pk[7])) & big), 0)) {
-            float mx = __builtin_fmaxf(__builtin_fmaxf(S[0], S[1]), S[2]);
-#pragma unroll
-            for (int i = 3; i < 15; i += 2) mx = __builtin_fmaxf(__builtin_fmaxf(mx, S[i]), S[i + 1]);
-            mx = __builtin_fmaxf(mx, S[15]);
-            // new reference = (true maximum so far) + HEADROOM octaves: P stays <= 2^-HEADROOM until a score beats
-            // the old maximum by more than HEADROOM + 1 octaves, so this branch is rare (first tile, true outliers)
-            mx = __builtin_fmaxf(mx, __shfl_xor(mx, 32)) + gh + HEADROOM / cexp;
-            const float m_new = __builtin_fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cexp);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { O0[i] *= alpha; O1[i] *= alpha; }
-            const float off = (gh - m_run) * cexp;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) p[i] = __builtin_amdgcn_exp2f(S[i] * cexp + off);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pk[j] = pack2<F16>(p[2 * j], p[2 * j + 1]);
-        }
-        {
-            float a0 = (p[0] + p[1]) + (p[2] + p[3]), a1 = (p[4] + p[5]) + (p[6] + p[7]);
-            float a2 = (p[8] + p[9]) + (p[10] + p[11]), a3 = (p[12] + p[13]) + (p[14] + p[15]);
-            l_run += (a0 + a1) + (a2 + a3);
-        }
-        const uint4 pf0 = make_uint4(pk[0], pk[1], pk[2], pk[3]), pf1 = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-        if constexpr (DBG) { asm volatile("" ::"v"(pf0.x), "v"(pf1.w), "v"(l_run)); }
-        A8_STAMP(0);                                        // vector phase
-        __builtin_amdgcn_s_barrier();
-        A8_STAMP(1);                                        // wait at the first barrier
-        // ---- matrix phase: ring traffic, O += V_kh^T P, S = K_{kh+1} Q^T + Gw
-        if (kh + 2 < 32) *reinterpret_cast<uint4 *>(&sKV[((SLOT + 2) & 3) * (A8_SLOT_BYTES / 2) + sdst]) = st;     // tile kh + 2
-        if (kh + 4 < 32) st = *reinterpret_cast<const uint4 *>(gsrc + (size_t)(kh + 4) * gstep);                   // two iterations to land
-        {
-            const unsigned short *vb = &sKV[SLOT * (A8_SLOT_BYTES / 2) + 2048];
-            const int d0 = r, d1 = 32 + r;
-            const uint4 v00 = *reinterpret_cast<const uint4 *>(vb + d0 * 32 + (((0 + h2) ^ ((d0 >> 2) & 3)) * 8));
-            const uint4 v01 = *reinterpret_cast<const uint4 *>(vb + d0 * 32 + (((2 + h2) ^ ((d0 >> 2) & 3)) * 8));
-            const uint4 v10 = *reinterpret_cast<const uint4 *>(vb + d1 * 32 + (((0 + h2) ^ ((d1 >> 2) & 3)) * 8));
-            const uint4 v11 = *reinterpret_cast<const uint4 *>(vb + d1 * 32 + (((2 + h2) ^ ((d1 >> 2) & 3)) * 8));
-            O0 = mfma32<F16>(v00, pf0, O0);
-            O1 = mfma32<F16>(v10, pf0, O1);
-            O0 = mfma32<F16>(v01, pf1, O0);
-            O1 = mfma32<F16>(v11, pf1, O1);
-        }
-        if (kh + 1 < 32) S = qk((SLOT + 1) & 3);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // this thread's ring write has landed
-        if constexpr (DBG) { asm volatile("" ::"v"(S[15]), "v"(O0[15]), "v"(O1[15])); }
-        A8_STAMP(2);                                        // matrix phase
-        __builtin_amdgcn_s_barrier();
-        A8_STAMP(3);                                        // wait at the second barrier
-    };
-    using std::integral_constant;
-    for (int kh0 = 0; kh0 < 32; kh0 += 4) {
-        tile(kh0 + 0, integral_constant<int, 0>{}, st_a);
-        tile(kh0 + 1, integral_constant<int, 1>{}, st_b);
-        tile(kh0 + 2, integral_constant<int, 2>{}, st_a);
-        tile(kh0 + 3, integral_constant<int, 3>{}, st_b);
-    }
-    if (wave < 4) __builtin_amdgcn_s_barrier();             // re-balance the barrier count of the two wave groups
-    if constexpr (DBG) {
-        unsigned long long tend;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tend)::"memory");
-        if (lane == 0) {
-            unsigned *d = dbg + ((size_t)lin * 8 + wave) * 9;
-            for (int i = 0; i < 8; ++i) d[i] = seg[i];
-            d[8] = (unsigned)(tend - tstart);
-        }
-    }
-
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
-    const float inv = 1.0f / l_tot;
-    unsigned short *orow = out + (tok0 + qh * 32 + r) * 1024 + head * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int d = db * 32 + 8 * g4 + 4 * h2;
-            const f32x16 &O = db ? O1 : O0;
-            uint2 o;
-            o.x = pack2<F16>(O[4 * g4 + 0] * inv, O[4 * g4 + 1] * inv);
-            o.y = pack2<F16>(O[4 * g4 + 2] * inv, O[4 * g4 + 3] * inv);
-            *reinterpret_cast<uint2 *>(orow + d) = o;
-        }
-}
-#endif  // CPX_DEBUG
-
-
-// ---------------------------------------------------------------------------
-// flash attention, 4 waves per workgroup, LDS-DMA ring + software-pipelined S (variant 7; the production kernel of rounds
-// 2-5, replaced by k_attention2w of cpx_attn2w.hip)
-// ---------------------------------------------------------------------------
-// Same decomposition as k_attention (one wave = one image row of 32 queries, key tiles = image rows, rel-pos bias
-// as MFMA C operand + one scalar per lane, P^T fed to the P.V MFMA from the accumulator registers).  What differs:
+// Same decomposition as the round-1 kernel k_attention (register ring, retired: git show f07d44d:classpose_amd/csrc/cpx_net.hip):
+// one wave = one image row of 32 queries, key tiles = image rows, rel-pos bias as MFMA C operand + one scalar per lane, P^T fed
+// to the P.V MFMA from the accumulator registers.  What differs:
 //   * K / V^T tiles reach LDS by LDS-DMA (global_load_lds_dwordx4, swizzle on the SOURCE address, lane-linear
 //     image) into a 4-slot ring, requested three tiles ahead: no staging registers (the register ring of
-//     k_attention holds 32 VGPRs), no ds_write, one raw s_barrier per tile behind a counted vmcnt;
+//     k_attention held 32 VGPRs), no ds_write, one raw s_barrier per tile behind a counted vmcnt;
 //   * the freed registers hold a second score tile: S = K_{t+1} Q^T + Gw is issued BEFORE the softmax of tile t,
 //     so the dependent QK^T chain (~330 cycles for a lone wave, profiles/r02_attn4_stamps.txt) runs under the
 //     softmax's VALU work instead of in front of it;
@@ -694,48 +198,13 @@ __device__ __forceinline__ uint4 a4_read128(unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
     return v;
 }
-// DBG (debug build only): s_memtime stamps per loop segment -> dbg [workgroup][4 waves][6]: 0 vmcnt wait + barrier,
-// 1 DMA requests + gh + K fragment reads + their wait + the 4 QK^T MFMAs of the NEXT tile (issue), 2 the softmax's vector
-// stream, 3 V fragment reads + wait + the 4 P.V MFMAs (issue), 4 prologue, 5 whole kernel.  The stamps pin the
-// instruction order at the segment borders (no QK^T / softmax interleave across them): a diagnostic of where an in-order
-// wave spends its time, not a timing of the production schedule.
-#define A4_STAMP(i)                                                                            \
-    do {                                                                                       \
-        if constexpr (DBG) {                                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-            unsigned long long t_;                                                             \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");         \
-            seg[i] += (unsigned)(t_ - tprev);                                                  \
-            tprev = t_;                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-        }                                                                                      \
-    } while (0)
-// LSUM: the softmax denominators come out of the matrix pipe -- two more MFMAs per tile with an all-ones A operand
-// (every row of the product is the column sum of P^T, i.e. the sum over the tile's 32 keys of the ROUNDED probabilities, the
-// same values P.V multiplies) instead of a 15-add tree per lane: 16 fewer vector instructions per tile and wave (of 67), no
-// cross-lane step at the end (both lane halves hold the full sum), 20 more registers.
-// ERD ("early reads"): the K fragments of tile kh + 1 AND the V fragments of tile kh are requested right behind the barrier and
-// the softmax's vector stream runs under their LDS latency (gh is waited for with a counted lgkmcnt(8)); the eight MFMAs
-// follow in one block.  Without it the wave sits in lgkmcnt(0) twice per tile (in front of QK^T and in front of P.V).
-// NV ("no vote", round-5 experiment, bf16 only): the reference of the softmax is fixed by the FIRST key tile (its exact maximum + the headroom); later
-// tiles neither OR their packed probabilities nor vote nor branch.  bf16 has float32's exponent range, so a probability above 2 is as accurate as one
-// below (the rescale of the production kernel only matters for fp16's range); what is lost is the guard against float32 overflow when a later score
-// exceeds the first tile's maximum by > ~80 octaves -- a production form would have to test the row sums for finiteness and re-run such an item.
-// NTL (round-5 experiment, debug build): the query rows are loaded with the non-temporal hint (an earlier form put the hint on the K / V^T ring
-// requests: 184 -> 199 us, the eight query blocks of a head lose their L2 sharing)
-// PRIO (round-5 experiment, debug build): wave priority by phase -- s_setprio 3 around a tile's matrix instructions and 0 around its softmax stream
-// measured 189.2 -> 193.8 us, the inverse (this form: 0 around the MFMAs, 2 otherwise) 186.4 -> 189.2: the three waves of a SIMD arbitrate better unaided
-template <bool F16, bool DBG = false, bool LSUM = false, bool ERD = false, bool NV = false, bool NTL = false, bool PRIO = false>
+template <bool F16>
 __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned short *__restrict__ qkv,
                                                                 const unsigned short *__restrict__ vT,
                                                                 const unsigned short *__restrict__ relh,
                                                                 const unsigned short *__restrict__ relw,
-                                                                unsigned short *__restrict__ out, int xcd_order,
-                                                                unsigned *__restrict__ dbg = nullptr) {
+                                                                unsigned short *__restrict__ out, int xcd_order) {
     extern __shared__ __attribute__((aligned(16))) char a4_smem[];
-    unsigned seg[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = 0, tstart = 0;
-    if constexpr (DBG) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory"); tstart = tprev; }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h2 = lane >> 5;
@@ -751,7 +220,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
     const int kkey = tid >> 3, vd = tid >> 2;
     // K image: 16-byte chunk c of key row k sits at position c ^ ((k >> 1) & 7): the 16 rows one ds_read_b128 lane group
     // touches ({0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} after the key permutation) then fall on 16 distinct
-    // 16-byte slots of the 256-byte bank row (the (k & 7) swizzle of k_attention is 2-way conflicted: rows k and k + 8)
+    // 16-byte slots of the 256-byte bank row (the (k & 7) swizzle of k_attention was 2-way conflicted: rows k and k + 8)
     const unsigned short *ksrc = qkv + (tok0 + kkey) * 3072 + 1024 + head * 64 + (((tid & 7) ^ ((kkey >> 1) & 7)) * 8);
     const unsigned short *vsrc = vT + (((size_t)s * 16 + head) * 64 + vd) * 1024 + (((tid & 3) ^ ((vd >> 2) & 3)) * 8);
     char *dma_dst = a4_smem + wave * 1024;
@@ -767,13 +236,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
     const unsigned short *qrow = qkv + (tok0 + qh * 32 + r) * 3072 + head * 64;
     uint4 qf[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        if constexpr (NTL) {              // (experiment) the query rows are read once, by this workgroup only: non-temporal
-            typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-            const u32x4_t q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(qrow + 16 * ks + 8 * h2));
-            qf[ks] = make_uint4(q[0], q[1], q[2], q[3]);
-        } else qf[ks] = *reinterpret_cast<const uint4 *>(qrow + 16 * ks + 8 * h2);
-    }
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const uint4 *>(qrow + 16 * ks + 8 * h2);
     // G = Q . table^T -> this wave's fp16 scratch [q][j] (values are bias / scale, |G| < ~60: fp16 keeps 2^-11 relative)
     _Float16 *G = reinterpret_cast<_Float16 *>(a4_smem + 4 * A4_SLOT) + wave * 32 * A4_G_LD;
     auto compute_G = [&](const unsigned short *table) {
@@ -820,12 +283,10 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
         const uint4 k2 = a4_read128<SL * A4_SLOT>(ka[2]), k3 = a4_read128<SL * A4_SLOT>(ka[3]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
         f32x16 S = mfma32<F16>(k0, qf[0], GW);
         S = mfma32<F16>(k1, qf[1], S);
         S = mfma32<F16>(k2, qf[2], S);
         S = mfma32<F16>(k3, qf[3], S);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(2);
         return S;
     };
     using std::integral_constant;
@@ -836,51 +297,27 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
     float m_run = -1e30f, l_run = 0.f;
     const float cexp = 0.125f * 1.44269504088896340736f;
     constexpr float HEADROOM = F16 ? 3.0f : 6.0f;
-    f32x16 Lacc;
-    uint4 ones;
-    if constexpr (LSUM) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) Lacc[i] = 0.f;
-        const unsigned one2 = F16 ? 0x3C003C00u : 0x3F803F80u;
-        ones = make_uint4(one2, one2, one2, one2);
-    }
 
-    A4_STAMP(4);
     // TAIL (compile time): 0 = any key tile up to 28 (every end-of-sequence condition below holds), 1 / 2 / 3 = tiles 29 / 30 / 31 -- the last four
     // tiles are peeled so that the steady-state body carries no scalar branch for them (round 4)
     auto tile = [&](const int kh, auto slot_tag, auto next_tag, auto tail_tag) {
-        constexpr int SL = decltype(slot_tag)::value, SN = decltype(next_tag)::value, TAILV = decltype(tail_tag)::value;
-        constexpr bool FIRST_TILE = TAILV == 4;                  // (NV: tag 4 = the very first key tile, otherwise a steady-state tile)
-        constexpr int TAIL = FIRST_TILE ? 0 : TAILV;
+        constexpr int SL = decltype(slot_tag)::value, SN = decltype(next_tag)::value, TAIL = decltype(tail_tag)::value;
         // tile kh + 1 (this thread's part) has landed; after the barrier every part has, and every wave is done with
         // slot (kh - 1) & 3, which the next request overwrites
         if constexpr (TAIL < 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        A4_STAMP(0);
         if constexpr (TAIL == 0) issue(kh + 3);
         unsigned gh_bits;
         asm volatile("ds_read_u16 %0, %1" : "=v"(gh_bits) : "v"(gaddr - 2u * (unsigned)kh));
         f32x16 Sn = S;
-        uint4 ek0, ek1, ek2, ek3, ev00, ev01, ev10, ev11;
-        if constexpr (ERD) {
-            // 8 fragment reads in flight behind gh (for the last tile the K reads repeat slot SN's stale rows: never used)
-            ek0 = a4_read128<SN * A4_SLOT>(ka[0]); ek1 = a4_read128<SN * A4_SLOT>(ka[1]);
-            ek2 = a4_read128<SN * A4_SLOT>(ka[2]); ek3 = a4_read128<SN * A4_SLOT>(ka[3]);
-            ev00 = a4_read128<SL * A4_SLOT>(va[0]); ev01 = a4_read128<SL * A4_SLOT>(va[1]);
-            ev10 = a4_read128<SL * A4_SLOT>(va[2]); ev11 = a4_read128<SL * A4_SLOT>(va[3]);
-            asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");             // gh only
+        if constexpr (TAIL < 3) Sn = qk(integral_constant<int, SN>{});          // waits lgkmcnt(0): gh is there too
+        else {
+            // (gh_bits is an inline-asm LDS read: the wait must carry it as an operand, or the compiler is free to schedule its consumer in
+            // front of the wait -- it did, in the peeled last tile, and every output was wrong by a few per cent)
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(gh_bits)::"memory");
             __builtin_amdgcn_sched_barrier(0);
-        } else {
-            if constexpr (TAIL < 3) Sn = qk(integral_constant<int, SN>{});          // waits lgkmcnt(0): gh is there too
-            else {
-                // (gh_bits is an inline-asm LDS read: the wait must carry it as an operand, or the compiler is free to schedule its consumer in
-                // front of the wait -- it did, in the peeled last tile, and every output was wrong by a few per cent)
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(gh_bits)::"memory");
-                __builtin_amdgcn_sched_barrier(0);
-            }
         }
-        A4_STAMP(1);
         const float gh = (float)__builtin_bit_cast(_Float16, (unsigned short)gh_bits);
         float p[16];
         unsigned pk[8];
@@ -891,9 +328,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
 #pragma unroll
             for (int j = 0; j < 8; ++j) pk[j] = pack2<F16>(p[2 * j], p[2 * j + 1]);
         }
-        bool resc;
-        if constexpr (NV) resc = FIRST_TILE;
-        else resc = __builtin_expect(__any(((pk[0] | pk[1] | pk[2]) | (pk[3] | pk[4] | pk[5]) | (pk[6] | pk[7])) & 0x40004000u), 0);
+        const bool resc = __builtin_expect(__any(((pk[0] | pk[1] | pk[2]) | (pk[3] | pk[4] | pk[5]) | (pk[6] | pk[7])) & 0x40004000u), 0);
         if (resc) {
             float mx = __builtin_fmaxf(__builtin_fmaxf(S[0], S[1]), S[2]);
 #pragma unroll
@@ -903,8 +338,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
             const float m_new = __builtin_fmaxf(m_run, mx);
             const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cexp);
             m_run = m_new;
-            if constexpr (LSUM) Lacc[0] *= alpha;        // only row 0 of the (all equal) rows is ever read
-            else l_run *= alpha;
+            l_run *= alpha;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { O0[i] *= alpha; O1[i] *= alpha; }
             const float off = (gh - m_run) * cexp;
@@ -913,52 +347,22 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
 #pragma unroll
             for (int j = 0; j < 8; ++j) pk[j] = pack2<F16>(p[2 * j], p[2 * j + 1]);
         }
-        if constexpr (!LSUM) {
-            const float a0 = (p[0] + p[1]) + (p[2] + p[3]), a1 = (p[4] + p[5]) + (p[6] + p[7]);
-            const float a2 = (p[8] + p[9]) + (p[10] + p[11]), a3 = (p[12] + p[13]) + (p[14] + p[15]);
-            l_run += (a0 + a1) + (a2 + a3);
-        }
+        const float a0 = (p[0] + p[1]) + (p[2] + p[3]), a1 = (p[4] + p[5]) + (p[6] + p[7]);
+        const float a2 = (p[8] + p[9]) + (p[10] + p[11]), a3 = (p[12] + p[13]) + (p[14] + p[15]);
+        l_run += (a0 + a1) + (a2 + a3);
         const uint4 pf0 = make_uint4(pk[0], pk[1], pk[2], pk[3]), pf1 = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-        if constexpr (DBG) { asm volatile("" ::"v"(pk[0]), "v"(pk[3]), "v"(pk[7]), "v"(l_run)); }
-        A4_STAMP(2);
-        if constexpr (ERD) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // long since landed: the vector stream ran meanwhile
-            __builtin_amdgcn_sched_barrier(0);
-            O0 = mfma32<F16>(ev00, pf0, O0);
-            O1 = mfma32<F16>(ev10, pf0, O1);
-            if constexpr (TAIL < 3) Sn = mfma32<F16>(ek0, qf[0], GW);
-            O0 = mfma32<F16>(ev01, pf1, O0);
-            O1 = mfma32<F16>(ev11, pf1, O1);
-            if constexpr (TAIL < 3) {
-                Sn = mfma32<F16>(ek1, qf[1], Sn);
-                Sn = mfma32<F16>(ek2, qf[2], Sn);
-                Sn = mfma32<F16>(ek3, qf[3], Sn);
-            }
-            if constexpr (LSUM) { Lacc = mfma32<F16>(ones, pf0, Lacc); Lacc = mfma32<F16>(ones, pf1, Lacc); }
-        } else {
-            const uint4 v00 = a4_read128<SL * A4_SLOT>(va[0]), v01 = a4_read128<SL * A4_SLOT>(va[1]);
-            const uint4 v10 = a4_read128<SL * A4_SLOT>(va[2]), v11 = a4_read128<SL * A4_SLOT>(va[3]);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-            O0 = mfma32<F16>(v00, pf0, O0);
-            O1 = mfma32<F16>(v10, pf0, O1);
-            O0 = mfma32<F16>(v01, pf1, O0);
-            O1 = mfma32<F16>(v11, pf1, O1);
-            if constexpr (LSUM) { Lacc = mfma32<F16>(ones, pf0, Lacc); Lacc = mfma32<F16>(ones, pf1, Lacc); }
-            if constexpr (PRIO) __builtin_amdgcn_s_setprio(2);
-        }
-        A4_STAMP(3);
+        const uint4 v00 = a4_read128<SL * A4_SLOT>(va[0]), v01 = a4_read128<SL * A4_SLOT>(va[1]);
+        const uint4 v10 = a4_read128<SL * A4_SLOT>(va[2]), v11 = a4_read128<SL * A4_SLOT>(va[3]);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        O0 = mfma32<F16>(v00, pf0, O0);
+        O1 = mfma32<F16>(v10, pf0, O1);
+        O0 = mfma32<F16>(v01, pf1, O0);
+        O1 = mfma32<F16>(v11, pf1, O1);
         S = Sn;
     };
     using T0 = integral_constant<int, 0>;
-    if constexpr (NV) {                                          // the first round peeled: its first tile fixes the reference
-        tile(0, integral_constant<int, 0>{}, integral_constant<int, 1>{}, integral_constant<int, 4>{});
-        tile(1, integral_constant<int, 1>{}, integral_constant<int, 2>{}, T0{});
-        tile(2, integral_constant<int, 2>{}, integral_constant<int, 3>{}, T0{});
-        tile(3, integral_constant<int, 3>{}, integral_constant<int, 0>{}, T0{});
-    }
-    for (int kh0 = NV ? 4 : 0; kh0 < 28; kh0 += 4) {
+    for (int kh0 = 0; kh0 < 28; kh0 += 4) {
         tile(kh0 + 0, integral_constant<int, 0>{}, integral_constant<int, 1>{}, T0{});
         tile(kh0 + 1, integral_constant<int, 1>{}, integral_constant<int, 2>{}, T0{});
         tile(kh0 + 2, integral_constant<int, 2>{}, integral_constant<int, 3>{}, T0{});
@@ -968,10 +372,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
     tile(29, integral_constant<int, 1>{}, integral_constant<int, 2>{}, integral_constant<int, 1>{});
     tile(30, integral_constant<int, 2>{}, integral_constant<int, 3>{}, integral_constant<int, 2>{});
     tile(31, integral_constant<int, 3>{}, integral_constant<int, 0>{}, integral_constant<int, 3>{});
-    float l_tot;
-    if constexpr (LSUM) l_tot = Lacc[0];
-    else l_tot = l_run + __shfl_xor(l_run, 32);
-    const float inv = 1.0f / l_tot;
+    const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
     unsigned short *orow = out + (tok0 + qh * 32 + r) * 1024 + head * 64;
     // a lane holds 4 consecutive channels (8 bytes) per group g4, its partner lane + 32 the next 4: one v_permlane32_swap per dword and
     // group pair (vdst = group g4, src = group g4 + 1) leaves the lower half-wave with channels 8 g4 .. + 7 and the upper one with
@@ -987,71 +388,14 @@ __global__ void __launch_bounds__(ATT_THREADS, 3) k_attention4p(const unsigned s
             const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
             *reinterpret_cast<uint4 *>(orow + db * 32 + 8 * g4 + 8 * h2) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
         }
-    if constexpr (DBG) {
-        unsigned long long t_;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");
-        seg[5] = (unsigned)(t_ - tstart);
-        if (lane == 0 && dbg) {
-            unsigned *d = dbg + ((size_t)lin * 4 + wave) * 6;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) d[i] = seg[i];
-        }
-    }
 }
 
 CPX_SWITCH(g_att_xcd, 1);          // XCD-aware workgroup order
 CPX_SWITCH(g_att_v8, 2);           // 2: two query rows per wave, two workgroups per CU (k_attention2w, production); 7: 4-wave kernel with the
-                                   // LDS-DMA ring and software-pipelined S (k_attention4p, rounds 2-5); 0: the first 4-wave kernel
-                                   // (register ring); 1: the 8-wave ping-pong experiment; 3-6: k_attention2q (cpx_attn2q.hip)
-// experiment switch (default off): V read from the qkv rows through ds_read_b64_tr_b16, no V^T buffer and a plain
-// qkv epilogue.  Bitwise identical outputs; the whole engine step measured 24.57 vs 24.44 ms (one-process A/B,
-// tools/ab_switch.py cpx_attention_set_trv): the 8 transposed reads per tile cost more than the epilogue saves.
-CPX_SWITCH(g_att_trv, 0);
-CPX_SWITCH(g_att_lsum, 0);         // 1: softmax denominators by an all-ones MFMA instead of the vector add tree (k_attention4p<.., LSUM>)
-int cpx_attention_trv_enabled(void) { return g_att_trv; }
+                                   // LDS-DMA ring and software-pipelined S (k_attention4p, rounds 2-5)
 #ifdef CPX_DEBUG
 extern "C" void cpx_attention_set_variant(int v8) { g_att_v8 = v8; }
 extern "C" void cpx_attention_set_xcd_order(int v) { g_att_xcd = v; }
-extern "C" void cpx_attention_set_trv(int v) { g_att_trv = v; }
-extern "C" void cpx_attention_set_lsum(int v) { g_att_lsum = v; }
-// diagnostic: per-wave cycle counts of the loop segments -> dbg [n_subtiles*16*8 blocks][4 waves][9]
-extern "C" int cpx_attention_debug(const void *qkv, const void *rel_h, const void *rel_w, int n_subtiles,
-                                   void *vT_ws, void *out, unsigned *dbg, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_v_transpose, dim3(16, 16, n_subtiles), dim3(256), 0, s,
-                       (const unsigned short *)qkv, (unsigned short *)vT_ws);
-    hipLaunchKernelGGL((k_attention<false, true>), dim3(8, 16, n_subtiles), dim3(ATT_THREADS), 0, s,
-                       (const unsigned short *)qkv, (const unsigned short *)vT_ws, (const unsigned short *)rel_h,
-                       (const unsigned short *)rel_w, (unsigned short *)out, dbg, g_att_xcd);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
-}
-// the same for the PRODUCTION kernel (k_attention4p): dbg [n_subtiles*16*8 blocks][4 waves][6], vT_ws holds V^T already or is
-// filled by the transpose kernel here
-extern "C" int cpx_attention4_debug(const void *qkv, const void *rel_h, const void *rel_w, int n_subtiles,
-                                    void *vT_ws, void *out, unsigned *dbg, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_v_transpose, dim3(16, 16, n_subtiles), dim3(256), 0, s,
-                       (const unsigned short *)qkv, (unsigned short *)vT_ws);
-    (void)hipFuncSetAttribute((const void *)k_attention4p<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
-    hipLaunchKernelGGL((k_attention4p<false, true>), dim3(8, 16, n_subtiles), dim3(ATT_THREADS), A4_LDS_BYTES, s,
-                       (const unsigned short *)qkv, (const unsigned short *)vT_ws, (const unsigned short *)rel_h,
-                       (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd, dbg);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
-}
-// diagnostic build of the 8-wave kernel: dbg [n_subtiles*16*4 blocks][8 waves][9] cycle sums
-extern "C" int cpx_attention8_debug(const void *qkv, const void *rel_h, const void *rel_w, int n_subtiles,
-                                    void *vT_ws, void *out, unsigned *dbg, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_v_transpose, dim3(16, 16, n_subtiles), dim3(256), 0, s,
-                       (const unsigned short *)qkv, (unsigned short *)vT_ws);
-    hipLaunchKernelGGL((k_attention8<false, true>), dim3(4, 16, n_subtiles), dim3(A8_THREADS), 0, s,
-                       (const unsigned short *)qkv, (const unsigned short *)vT_ws, (const unsigned short *)rel_h,
-                       (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd, dbg);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
-}
 #endif
 extern "C" int cpx_attention_relpos(const void *qkv, const void *rel_h, const void *rel_w,
                                     int n_subtiles, void *vT_ws, void *out, void *stream) {
@@ -1068,114 +412,34 @@ int cpx_attention_half(int dtype, const void *qkv, const void *rel_h, const void
                        void *vT_ws, void *out, void *stream, bool transpose_v) {
     CPX_REQUIRE(qkv && rel_h && rel_w && vT_ws && out && n_subtiles > 0);
     CPX_REQUIRE(dtype == CPX_DT_BF16 || dtype == CPX_DT_F16);
+#ifdef CPX_DEBUG
+    CPX_REQUIRE(g_att_v8 == 2 || g_att_v8 == 7);
+#endif
     hipStream_t s = (hipStream_t)stream;
-    if (transpose_v && !g_att_trv)
+    if (transpose_v)
         hipLaunchKernelGGL(k_v_transpose, dim3(16, 16, n_subtiles), dim3(256), 0, s,
                            (const unsigned short *)qkv, (unsigned short *)vT_ws);
-#ifdef CPX_DEBUG
-    if (g_att_v8 == 1 && !g_att_trv) {
-        const dim3 grid8(4, 16, n_subtiles);
-        if (dtype == CPX_DT_F16)
-            hipLaunchKernelGGL((k_attention8<true, false>), grid8, dim3(A8_THREADS), 0, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                               (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-        else
-            hipLaunchKernelGGL((k_attention8<false, false>), grid8, dim3(A8_THREADS), 0, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                               (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd, (unsigned *)nullptr);
-        CPX_CHECK_LAUNCH();
-        return CPX_OK;
-    }
-    if (g_att_v8 < 2 || g_att_v8 > 7 || g_att_trv) {        // (variants 3-6 and 7 are dispatched below)
-        dim3 grid(8, 16, n_subtiles);
-#define ATT_LAUNCH(F16_, TRV_)                                                                              \
-    hipLaunchKernelGGL((k_attention<F16_, false, TRV_>), grid, dim3(ATT_THREADS), 0, s, (const unsigned short *)qkv, \
-                       (const unsigned short *)vT_ws, (const unsigned short *)rel_h, (const unsigned short *)rel_w, \
-                       (unsigned short *)out, (unsigned *)nullptr, g_att_xcd)
-        if (dtype == CPX_DT_F16) { if (g_att_trv) ATT_LAUNCH(true, true); else ATT_LAUNCH(true, false); }
-        else { if (g_att_trv) ATT_LAUNCH(false, true); else ATT_LAUNCH(false, false); }
-#undef ATT_LAUNCH
-        CPX_CHECK_LAUNCH();
-        return CPX_OK;
-    }
-#endif
-#ifdef CPX_DEBUG
-    if (g_att_v8 >= 3 && g_att_v8 <= 6) return cpx_attention2q_launch(dtype, qkv, vT_ws, rel_h, rel_w, n_subtiles, out, g_att_v8 - 3, s);   // round-4 experiments
-#endif
     // production: two query rows per wave, two workgroups per CU (cpx_attn2w.hip).  The debug library keeps the round-2/3 kernel
-    // k_attention4p as variant 7, with its round-5 experiment switches (cpx_attention_set_lsum 1..5, which select it too)
+    // k_attention4p as variant 7, the bitwise reference of tests/test_gpu_attn2w.py
 #ifdef CPX_DEBUG
-    if (g_att_v8 == 2 && !g_att_lsum)
-#endif
-        return cpx_attention2w_launch(dtype, qkv, vT_ws, rel_h, rel_w, n_subtiles, out, g_att_xcd, s);
-#ifdef CPX_DEBUG
-    const dim3 grid4(8, 16, n_subtiles);
-    static CpxOncePerDevice once4;
-    once4([] {
-        (void)hipFuncSetAttribute((const void *)k_attention4p<true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)k_attention4p<false>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
-    });
-    if (g_att_lsum == 3 && dtype != CPX_DT_F16) {           // round-5 experiment: no overflow vote (k_attention4p<.., NV>), bf16
-        static CpxOncePerDevice once4n;
-        once4n([] { (void)hipFuncSetAttribute((const void *)k_attention4p<false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES); });
-        hipLaunchKernelGGL((k_attention4p<false, false, false, false, true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                           (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-        CPX_CHECK_LAUNCH();
-        return CPX_OK;
-    }
-    if (g_att_lsum == 4 && dtype != CPX_DT_F16) {           // round-5 experiment: non-temporal K / V^T requests (k_attention4p<.., NTL>), bf16
-        static CpxOncePerDevice once4t;
-        once4t([] { (void)hipFuncSetAttribute((const void *)k_attention4p<false, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES); });
-        hipLaunchKernelGGL((k_attention4p<false, false, false, false, false, true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                           (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-        CPX_CHECK_LAUNCH();
-        return CPX_OK;
-    }
-    if (g_att_lsum == 5 && dtype != CPX_DT_F16) {           // round-5 experiment: wave priority around the matrix instructions (k_attention4p<.., PRIO>), bf16
-        static CpxOncePerDevice once4q;
-        once4q([] { (void)hipFuncSetAttribute((const void *)k_attention4p<false, false, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES); });
-        hipLaunchKernelGGL((k_attention4p<false, false, false, false, false, false, true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                           (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-        CPX_CHECK_LAUNCH();
-        return CPX_OK;
-    }
-    if (g_att_lsum == 2) {           // experiment: early fragment reads (k_attention4p<.., ERD>)
-        static CpxOncePerDevice once4e;
-        once4e([] {
-            (void)hipFuncSetAttribute((const void *)k_attention4p<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
-            (void)hipFuncSetAttribute((const void *)k_attention4p<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
+    if (g_att_v8 == 7) {
+        const dim3 grid4(8, 16, n_subtiles);
+        static CpxOncePerDevice once4;
+        once4([] {
+            (void)hipFuncSetAttribute((const void *)k_attention4p<true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
+            (void)hipFuncSetAttribute((const void *)k_attention4p<false>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
         });
         if (dtype == CPX_DT_F16)
-            hipLaunchKernelGGL((k_attention4p<true, false, false, true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
+            hipLaunchKernelGGL((k_attention4p<true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
                                (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
         else
-            hipLaunchKernelGGL((k_attention4p<false, false, false, true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
+            hipLaunchKernelGGL((k_attention4p<false>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
                                (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
         CPX_CHECK_LAUNCH();
         return CPX_OK;
     }
-    if (g_att_lsum) {
-        static CpxOncePerDevice once4l;
-        once4l([] {
-            (void)hipFuncSetAttribute((const void *)k_attention4p<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
-            (void)hipFuncSetAttribute((const void *)k_attention4p<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
-        });
-        if (dtype == CPX_DT_F16)
-            hipLaunchKernelGGL((k_attention4p<true, false, true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                               (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-        else
-            hipLaunchKernelGGL((k_attention4p<false, false, true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                               (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-        CPX_CHECK_LAUNCH();
-        return CPX_OK;
-    }
-    if (dtype == CPX_DT_F16)
-        hipLaunchKernelGGL((k_attention4p<true>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                           (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-    else
-        hipLaunchKernelGGL((k_attention4p<false>), grid4, dim3(ATT_THREADS), A4_LDS_BYTES, s, (const unsigned short *)qkv, (const unsigned short *)vT_ws,
-                           (const unsigned short *)rel_h, (const unsigned short *)rel_w, (unsigned short *)out, g_att_xcd);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
 #endif
+    return cpx_attention2w_launch(dtype, qkv, vT_ws, rel_h, rel_w, n_subtiles, out, g_att_xcd, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1297,7 +561,6 @@ extern "C" int cpx_net_forward(const cpx_net_weights *w, const void *patches, in
     CpxProf *prof = (CpxProf *)w->prof;
     if (prof) prof->phase = (prof->phase + 1) % prof->stride;
     hipStream_t hs = (hipStream_t)stream;
-    const int trv = cpx_attention_trv_enabled();
     int rc;
 #define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
 #define GEMM(A_, W_, N_, K_, EPI_, B_, AUX_, OUT_, LD_) \
@@ -1315,11 +578,10 @@ extern "C" int cpx_net_forward(const cpx_net_weights *w, const void *patches, in
     TIMED(CPX_PROF_PE, 0, cpx_gemm_half(dt, patches, w->pe_w, M, 1024, 192, CPX_EPI_POS_BF16, w->pe_b, w->pos, x, 1024, nullptr, nullptr,
                                         pe_stats ? st : nullptr, stream));
     if (fuse && !pe_stats) RUN(cpx_row_stats_half(dt, x, M, st, stream));
-    const int qkv_epi = trv ? CPX_EPI_BF16 : CPX_EPI_QKV_BF16;
     for (int i = 0; i < w->depth; ++i) {
         const cpx_block_weights &b = w->blocks[i];
         if (fuse) {
-            TIMED(CPX_PROF_QKV, i, cpx_gemm_half(dt, x, b.qkv_w, M, 3072, 1024, qkv_epi, b.qkv_b, trv ? nullptr : vt, qkv, 3072, st, b.qkv_colsum, nullptr, stream));
+            TIMED(CPX_PROF_QKV, i, cpx_gemm_half(dt, x, b.qkv_w, M, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072, st, b.qkv_colsum, nullptr, stream));
             TIMED(CPX_PROF_ATTN, i, cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
             TIMED(CPX_PROF_PROJ, i, cpx_gemm_half(dt, ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, x, x, 1024, nullptr, nullptr, big_stats ? st : nullptr, stream));
             if (!big_stats) RUN(cpx_row_stats_half(dt, x, M, st, stream));
@@ -1340,7 +602,7 @@ extern "C" int cpx_net_forward(const cpx_net_weights *w, const void *patches, in
             continue;
         }
         RUN(cpx_layernorm_half(dt, x, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, xn, stream));
-        TIMED(CPX_PROF_QKV, i, GEMM(xn, b.qkv_w, 3072, 1024, qkv_epi, b.qkv_b, trv ? nullptr : vt, qkv, 3072));
+        TIMED(CPX_PROF_QKV, i, GEMM(xn, b.qkv_w, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072));
         TIMED(CPX_PROF_ATTN, i, cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
         TIMED(CPX_PROF_PROJ, i, GEMM(ao, b.proj_w, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, x, x, 1024));
         RUN(cpx_layernorm_half(dt, x, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, xn, stream));

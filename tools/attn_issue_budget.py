@@ -7,7 +7,7 @@ the occupancy it allows, i.e. why no 4-waves-per-SIMD form exists.
     python tools/attn_issue_budget.py [library.so] [kernel symbol regex] [wave-tiles per loop iteration]        (CPU only)
 
 Defaults: the product library, the production kernel k_attention2w (bf16), 8 wave-tiles per iteration (four key tiles x two query rows
-per wave).  The round-2/3 kernel: classpose_amd/libclasspose_hip_debug.so '^_Z\d+k_attention4pILb0ELb0ELb0ELb0ELb0ELb0ELb0E' 4"""
+per wave).  The round-2/3 kernel: classpose_amd/libclasspose_hip_debug.so '^_Z\d+k_attention4pILb0EE' 4"""
 import os
 import re
 import subprocess

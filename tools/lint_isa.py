@@ -66,10 +66,6 @@ def _regs(text: str) -> list[tuple[str, int, int]]:
             for m in RE_REG.finditer(text)]
 
 
-# timing-only ablation instantiations whose loads go to dead registers by design (results are garbage, the debug build says so)
-ALLOW = re.compile(r"k_attention2qILb[01]ELb1ELi[1-9]")
-# debug-build experiments measured once and not shipped (the no-vote attention variant of round 5 spills two registers): rule 3 is about what ships
-EXPERIMENT = re.compile(r"k_attention4pILb0ELb0ELb0ELb0ELb1E")
 NO_SPILL = re.compile(r"^_Z\d+(k_gemm256pI|k_attention4pI|k_attention2wI|k_gemm4wI)")
 
 
@@ -106,8 +102,8 @@ VMEM_ASM_LOADS = re.compile(r"^_Z\d+k_gemm4wI")          # kernels that load reg
 
 def vmem_findings(sym: str, body: list[str], lib: str) -> list[str]:
     """Rule 4 (kernels of VMEM_ASM_LOADS): no instruction reads -- or overwrites -- the destination of a vector-memory load to REGISTERS before
-    an `s_waitcnt vmcnt(N)` that covers it.  The one-wave-per-SIMD GEMM requests its residual rows with inline-asm buffer loads (an ordinary
-    load makes hipcc drain the LDS-DMA queue) and waits with a counted vmcnt that carries the registers as "+v" operands; what the operands
+    an `s_waitcnt vmcnt(N)` that covers it.  The one-wave-per-SIMD GEMM's round-5 residual epilogue (retired) requested its residual rows with
+    inline-asm buffer loads (an ordinary load makes hipcc drain the LDS-DMA queue) and waited with a counted vmcnt that carried the registers as "+v" operands; what the operands
     cannot forbid is a register COPY the allocator inserts between the load and the wait (seen in round 4's hoist experiment).  Model: every
     vector-memory instruction (loads, stores, LDS-DMA) enters an in-order queue; vmcnt(N) retires all but the N youngest."""
     res, queue = [], []
@@ -136,15 +132,13 @@ def vmem_findings(sym: str, body: list[str], lib: str) -> list[str]:
 def findings(so_path: str) -> list[str]:
     res = []
     for sym, body in disassemble(so_path):
-        if ALLOW.search(sym):
-            continue
         res += permlane_findings(sym, body, os.path.basename(so_path))
         if VMEM_ASM_LOADS.search(sym):
             res += vmem_findings(sym, body, os.path.basename(so_path))
         # Rule 3: the persistent GEMM and the production attention kernel pace their LDS-DMA with counted vmcnt waits and live at the edge of
         # the register file; a spill there is legal (extra vector-memory operations only make a counted wait stricter) but costs a drained
         # queue per reload, and the one combination that ever returned wrong numbers (round 4) was one that spilled -- keep them spill-free
-        if NO_SPILL.search(sym) and not EXPERIMENT.search(sym):
+        if NO_SPILL.search(sym):
             n = sum(1 for ins in body if ins.startswith("scratch_"))
             if n:
                 res.append(f"{os.path.basename(so_path)}: {sym[:70]}: {n} scratch instruction(s) (register spill) in a kernel that must not spill")
