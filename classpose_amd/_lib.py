@@ -78,6 +78,14 @@ class CpxRecord(C.Structure):
                 ("sum_y", C.c_int64), ("sum_x", C.c_int64)]
 
 
+class CpxPqPair(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("image", "cls", "first_true", "first_pred", "inter", "area_true", "area_pred", "reserved")]
+
+
+class CpxPqInst(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("image", "side", "cls", "first", "area", "reserved")]
+
+
 class CpxCell(C.Structure):
     _fields_ = [("area", C.c_double), ("perimeter", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("n_pts", C.c_int32), ("offset", C.c_int32), ("valid", C.c_int32), ("cls", C.c_int32)]
@@ -133,6 +141,8 @@ SIGNATURES = {
     "cpx_compute_masks": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _d, _i, _i, _d, _p, _p, _p, _p, _p]),
     "cpx_instance_records": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "cpx_compute_masks_records": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _d, _i, _i, _d, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "cpx_pq_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "cpx_pq_stats": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _sz, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),

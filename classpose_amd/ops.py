@@ -336,3 +336,141 @@ def dedup_pairs(centers: np.ndarray, max_dist: float = 15 / 2, device=None) -> n
     check(L.cpx_dedup_pairs(ptr(c), n, x0, y0, cell, gw, gh, float(max_dist), ptr(pairs), P, ptr(tot), ptr(ws), nbytes, st),
           "dedup_pairs(write)")
     return pairs.cpu().numpy()
+
+
+# ---- a16b -------------------------------------------------------------------
+PQ_WS_LIMIT = 1 << 30          # bytes of table workspace per call: larger batches run in chunks of images
+
+
+def _pq_ids(x: torch.Tensor):
+    """(contiguous tensor, bytes per id): int32, or the uint16 ids ``compute_masks`` / ``Engine`` keep in an int16 tensor."""
+    if x.dtype == torch.int32:
+        return x.contiguous(), 4
+    if x.dtype == torch.int16 or x.dtype == getattr(torch, "uint16", None):
+        return x.contiguous(), 2
+    raise ValueError(f"instance ids must be int32 or uint16-in-int16, not {x.dtype}")
+
+
+def pq_full_table_cap(H: int, W: int) -> int:
+    """Slots per table with which ``cpx_pq_stats`` cannot overflow: a power of two >= 2 * H * W."""
+    return max(16, 1 << (2 * H * W - 1).bit_length())
+
+
+def pq_stats(true_ids: torch.Tensor, pred_ids: torch.Tensor, true_cls: torch.Tensor | None = None,
+             pred_cls: torch.Tensor | None = None, nr_classes: int = 1, match_iou: float = 0.5,
+             filter_unlabelled: bool | None = None, no_border_instances: bool = False, return_lists: bool = False,
+             table_cap: int | None = None) -> dict:
+    """Per-(image, class) panoptic-quality statistics of device-resident maps (``cpx_pq_stats``): what
+    ``get_multi_pq_info`` (stats_utils.py:8-61) returns per image after ``filter_out_unlabelled_cells`` and
+    ``remove_border_instances``, or ``get_pq``'s counts per image in binary mode (``true_cls is None``).
+
+    true_ids / pred_ids (n, H, W) int32 or the engine's uint16-in-int16 ids; true_cls / pred_cls (n, H, W) uint8.  The inputs are
+    not modified.  Returns host arrays ``tp, fp, fn`` int32 (n, nr_classes) and ``iou_sum`` float64; with ``return_lists`` also
+    ``pairs`` / ``insts`` (structured, see cpx_pq_pair / cpx_pq_inst) and ``nobg`` (n, 2).  Tables start at H * W / 16 slots per
+    image; an image that fills them is repeated with tables that cannot fill (2 * H * W slots)."""
+    binary = true_cls is None
+    if (pred_cls is None) != binary:
+        raise ValueError("give both class maps or neither")
+    if filter_unlabelled is None:
+        filter_unlabelled = not binary
+    if binary and (nr_classes != 1 or filter_unlabelled):
+        raise ValueError("binary mode has one pseudo-class and no unlabelled-cell filter")
+    if not 1 <= nr_classes <= 255:
+        raise ValueError(f"nr_classes must be in 1..255, not {nr_classes}")
+    true_ids, _ = _batched(true_ids, 2)
+    pred_ids, _ = _batched(pred_ids, 2)
+    t_ids, idb = _pq_ids(true_ids)
+    p_ids, idb2 = _pq_ids(pred_ids)
+    if idb != idb2 or t_ids.shape != p_ids.shape:
+        raise ValueError("true and predicted ids differ in type or shape")
+    nI, H, W = t_ids.shape
+    dev = t_ids.device
+    if not binary:
+        true_cls, _ = _batched(true_cls, 2)
+        pred_cls, _ = _batched(pred_cls, 2)
+        if true_cls.dtype != torch.uint8 or pred_cls.dtype != torch.uint8 or true_cls.shape != t_ids.shape or pred_cls.shape != t_ids.shape:
+            raise ValueError("class maps must be uint8 of the ids' shape")
+        true_cls, pred_cls = true_cls.contiguous(), pred_cls.contiguous()
+    L = _lib.lib()
+    full_cap = pq_full_table_cap(H, W)
+    cap0 = min(full_cap, max(1024, 1 << max(H * W // 16 - 1, 1).bit_length())) if table_cap is None else int(table_cap)
+    out = dict(tp=np.zeros((nI, nr_classes), np.int32), fp=np.zeros((nI, nr_classes), np.int32),
+               fn=np.zeros((nI, nr_classes), np.int32), iou_sum=np.zeros((nI, nr_classes), np.float64))
+    pairs_all, insts_all, nobg_all = [], [], np.zeros((nI, 2), np.int32)
+
+    def run(idx: torch.Tensor | None, lo: int, hi: int, cap: int):
+        """images lo:hi (idx None) or the listed ones, with tables of `cap` slots -> (status, stats, lists)"""
+        sel = (lambda x: x[lo:hi]) if idx is None else (lambda x: x.index_select(0, idx))
+        ti, pi = sel(t_ids), sel(p_ids)
+        tc, pc = (None, None) if binary else (sel(true_cls), sel(pred_cls))
+        n = ti.shape[0]
+        nbytes = L.cpx_pq_workspace_bytes(n, H, W, nr_classes, cap)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        cnt = torch.empty((3, n, nr_classes), dtype=torch.int32, device=dev)
+        ious = torch.empty((n, nr_classes), dtype=torch.float64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        nobg = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        pairs = insts = lc = None
+        mx = 0
+        if return_lists:
+            mx = min(n * cap, 1 << 26)
+            pairs = torch.empty((mx, 8), dtype=torch.int32, device=dev)
+            insts = torch.empty((mx, 6), dtype=torch.int32, device=dev)
+            lc = torch.empty(2, dtype=torch.int32, device=dev)
+        check(L.cpx_pq_stats(ptr(ti), ptr(pi), idb, ptr(tc), ptr(pc), n, H, W, nr_classes, float(match_iou),
+                             int(bool(filter_unlabelled)), int(bool(no_border_instances)), cap, ptr(cnt[0]), ptr(cnt[1]),
+                             ptr(cnt[2]), ptr(ious), ptr(status), ptr(nobg), ptr(pairs), mx, ptr(insts), mx, ptr(lc),
+                             ptr(ws), nbytes, _stream(dev)), "pq_stats")
+        lists = None
+        if return_lists:
+            npair, ninst = (int(v) for v in lc.cpu())
+            if npair > mx or ninst > mx:
+                raise _lib.CpxError(f"pq_stats: {npair} pairs / {ninst} instances exceed the list limit of {mx} entries per call")
+            lists = (pairs[:npair].cpu().numpy(), insts[:ninst].cpu().numpy(), nobg.cpu().numpy())
+        return status.cpu().numpy(), cnt.cpu().numpy(), ious.cpu().numpy(), lists
+
+    def store(where, res, which=None):
+        _st, cnt, ious, lists = res
+        rows = slice(None) if which is None else which
+        out["tp"][where], out["fp"][where], out["fn"][where] = cnt[0][rows], cnt[1][rows], cnt[2][rows]
+        out["iou_sum"][where] = ious[rows]
+        if lists is not None:
+            pr, ins, nb = lists
+            local = np.arange(len(nb)) if which is None else which
+            glob = np.arange(where.start, where.stop) if isinstance(where, slice) else np.asarray(where)
+            lut = np.full(len(nb), -1, np.int64)
+            lut[local] = glob
+            pr, ins = pr[lut[pr[:, 0]] >= 0].copy(), ins[lut[ins[:, 0]] >= 0].copy()
+            pr[:, 0], ins[:, 0] = lut[pr[:, 0]], lut[ins[:, 0]]
+            pairs_all.append(pr); insts_all.append(ins)
+            nobg_all[glob] = nb[local]
+
+    def chunk_of(cap: int) -> int:
+        per = L.cpx_pq_workspace_bytes(1, H, W, nr_classes, cap)
+        return max(1, min(65535, PQ_WS_LIMIT // per))
+
+    step = chunk_of(cap0)
+    redo: list[int] = []
+    for lo in range(0, nI, step):
+        hi = min(nI, lo + step)
+        res = run(None, lo, hi, cap0)
+        ok = np.flatnonzero(res[0] == 0)
+        store(lo + ok, res, ok)
+        redo += [lo + int(i) for i in np.flatnonzero(res[0] != 0)]
+    if redo:
+        if cap0 >= full_cap and table_cap is None:
+            raise _lib.CpxError(f"pq_stats: tables of {cap0} slots (2 * H * W) filled up")
+        if table_cap is not None:
+            raise _lib.CpxError(f"pq_stats: table_cap = {cap0} slots is too small for image(s) {redo[:8]} (limit without overflow: {full_cap})")
+        step = chunk_of(full_cap)
+        for k in range(0, len(redo), step):
+            part = redo[k:k + step]
+            res = run(torch.tensor(part, dtype=torch.long, device=dev), 0, 0, full_cap)
+            if res[0].any():
+                raise _lib.CpxError(f"pq_stats: tables of {full_cap} slots (2 * H * W) filled up")
+            store(np.asarray(part), res, None)
+    if return_lists:
+        out["pairs"] = np.concatenate(pairs_all) if pairs_all else np.zeros((0, 8), np.int32)
+        out["insts"] = np.concatenate(insts_all) if insts_all else np.zeros((0, 6), np.int32)
+        out["nobg"] = nobg_all
+    return out

@@ -45,7 +45,8 @@ extern "C" {
  * Version history: 2 = no process-global compute state (round 2); round 4 ADDED cpx_build_id, cpx_compute_masks_records and
  * cpx_prof_collect_launches without a bump (additive); 3 (round 5) = cpx_prof_collect fills CPX_PROF_N_KINDS = 7 entries (was 5) and
  * the post-processing workspace of cpx_postproc_workspace_bytes holds six table sets per tile -- callers compiled against version 2
- * must be rebuilt, and classpose_amd/_lib.py refuses a library whose version differs.                                          */
+ * must be rebuilt, and classpose_amd/_lib.py refuses a library whose version differs.  cpx_pq_workspace_bytes and cpx_pq_stats (the
+ * panoptic-quality statistics) were ADDED later without a bump, like the round-4 additions.                                    */
 int cpx_abi_version(void);
 /* Last HIP error string recorded by a failing call on this thread (host ptr). */
 const char *cpx_last_error(void);
@@ -407,6 +408,49 @@ int cpx_compute_masks_records(const float *dP, const float *cellprob, const floa
                               double max_size_fraction, uint16_t *masks_u16,
                               uint8_t *class_masks, int32_t *nlabels, int max_rec, cpx_record *records,
                               int32_t *rec_counts, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------
+ * a16b  panoptic-quality statistics (offline evaluation against an annotated set)
+ * replaces, per image pair, filter_out_unlabelled_cells (/root/reference/src/classpose/metrics/utils.py:162-252),
+ * remove_border_instances (metrics/pq.py:65-92), get_multi_pq_info (metrics/stats_utils.py:8-61) and the pairing of
+ * get_pq (stats_utils.py:64-178) as driven by compute_multiclass_pq_metrics / compute_binary_pq_metrics
+ * (metrics/pq.py:95-290)
+ * ---------------------------------------------------------------------- */
+/* true_ids / pred_ids [nI][H][W] instance ids >= 0, 0 = background: int32 (id_bytes 4) or uint16 (id_bytes 2, what cpx_compute_masks
+ * writes); true_cls / pred_cls [nI][H][W] uint8, or both NULL = binary mode (one pseudo-class, nr_classes 1, no filter).  Inputs are
+ * not modified (the reference edits its arrays in place).  Stages, all on the device:
+ *   filter_unlabelled    a true instance without a class > 0 pixel leaves, with every predicted instance whose class-agnostic IoU
+ *                        with it is > 0.5 (utils.py:203-244; the reference's early exits remove nothing either);
+ *   no_border_instances  then ids with a pixel on the first / last row / column leave, each map on its own (pq.py:56-58);
+ *   per class c = 1..nr_classes over the one-class maps inst * (cls == c): iou = inter / (area_true + area_pred - inter) as one
+ *                        float64 division of exactly converted integers; a pair counts when iou > match_iou.
+ * Outputs [nI][nr_classes]: tp = pairs, fp / fn = predicted / true instances of the class in no pair (int32), iou_sum = the sum of
+ * the pairs' iou (float64): accumulated exactly in integer fixed point and rounded once, so it does not depend on the order of
+ * arrival and two runs give the same bits.  Reference quirk kept: a one-class map WITHOUT a zero pixel loses its first-appearing
+ * instance from the id list (`true_id_list[1:]`, stats_utils.py:108,161-162): a true one is neither paired nor fn, a predicted
+ * one is never fp.  nobg (nullable) [nI][2] receives that class per (image, side: 0 true, 1 predicted), else 0.
+ * The tables are hash tables of table_cap slots (a power of two >= 16) per image and kind; status [nI] is set to 1 for an image
+ * whose tables filled up -- its outputs are then void and the call is to be repeated with a larger table_cap; 2 * H * W slots
+ * (rounded up to a power of two) always suffice.
+ * Optional lists for the match_iou == 0 branch (scipy's linear_sum_assignment needs the dense matrix, stats_utils.py:144-158; host
+ * side): every overlapping same-class pair and every (side, class, instance), in no particular order, an instance identified by the
+ * index of its first raster pixel in the one-class map (their order is the reference's row / column order); list_counts [2] = the
+ * number of pairs and instances found (may exceed max_pairs / max_insts: then the lists are truncated and the caller enlarges them). */
+typedef struct cpx_pq_pair {
+    int32_t image, cls;
+    int32_t first_true, first_pred;      /* first raster pixel (y * W + x) of the two instances in their one-class maps */
+    int32_t inter, area_true, area_pred, reserved;
+} cpx_pq_pair;
+typedef struct cpx_pq_inst {
+    int32_t image, side, cls;            /* side 0 = true, 1 = predicted */
+    int32_t first, area, reserved;
+} cpx_pq_inst;
+size_t cpx_pq_workspace_bytes(int nI, int H, int W, int nr_classes, int table_cap);
+int cpx_pq_stats(const void *true_ids, const void *pred_ids, int id_bytes, const uint8_t *true_cls, const uint8_t *pred_cls,
+                 int nI, int H, int W, int nr_classes, double match_iou, int filter_unlabelled, int no_border_instances,
+                 int table_cap, int32_t *tp, int32_t *fp, int32_t *fn, double *iou_sum, int32_t *status, int32_t *nobg,
+                 cpx_pq_pair *pairs, int max_pairs, cpx_pq_inst *insts, int max_insts, int32_t *list_counts,
+                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
