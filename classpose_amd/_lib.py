@@ -143,6 +143,14 @@ SIGNATURES = {
     "cpx_compute_masks_records": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _d, _i, _i, _d, _p, _p, _p, _i, _p, _p, _p, _p]),
     "cpx_pq_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "cpx_pq_stats": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _sz, _p]),
+    "cpx_net_neck_offset": (_sz, [_i, _i]),
+    "cpx_patchify_f32": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "cpx_class_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "cpx_class_loss": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _p, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "cpx_head_wgrad_slab_rows": (_i, []),
+    "cpx_head_wgrad_workspace_bytes": (_sz, [_i, _i]),
+    "cpx_head_wgrad": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "cpx_adamw_step": (_i, [_p, _p, _p, _p, C.c_longlong, _d, _d, _d, _d, _d, _d, _d, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),

@@ -75,6 +75,7 @@ int cpx_layernorm_f32(const float *x, const float *w, const float *b, int rows, 
 int cpx_attention_f32(const float *qkv, const float *rel_h, const float *rel_w, int n_subtiles, float *out,
                       void *stream);
 size_t cpx_net_f32_workspace_bytes(int n_subtiles);
+size_t cpx_net_f32_neck_offset(int n_subtiles);        // byte offset of the neck output (head GEMM operand) in that workspace
 int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
                         size_t workspace_bytes, void *stream);
 

@@ -468,6 +468,13 @@ extern "C" size_t cpx_net_workspace_bytes(int n_subtiles, int dtype) {
     return dtype == CPX_DT_F32 ? cpx_net_f32_workspace_bytes(n_subtiles) : net_ws(n_subtiles).total;
 }
 
+// where cpx_net_forward leaves the neck output [n_subtiles * 1024][256] (element type = network dtype; the operand of the head GEMM) in its
+// workspace: the features a frozen-backbone training step starts from (cpx_train.hip).  0 for an invalid argument (the offset is never 0).
+extern "C" size_t cpx_net_neck_offset(int n_subtiles, int dtype) {
+    if (n_subtiles <= 0 || dtype < CPX_DT_BF16 || dtype > CPX_DT_F32) return 0;
+    return dtype == CPX_DT_F32 ? cpx_net_f32_neck_offset(n_subtiles) : net_ws(n_subtiles).off_neck2;
+}
+
 // ---------------------------------------------------------------------------
 // optional per-launch timing (bench.py's roofline lines): HIP events recorded on the launch
 // stream around the selected kernels of a forward.  The handle is created by the caller (never

@@ -366,6 +366,7 @@ static NetWsF32 net_ws_f32(int nS) {
     return w;
 }
 size_t cpx_net_f32_workspace_bytes(int n_subtiles) { return n_subtiles > 0 ? net_ws_f32(n_subtiles).total : 0; }
+size_t cpx_net_f32_neck_offset(int n_subtiles) { return n_subtiles > 0 ? net_ws_f32(n_subtiles).off_neck2 : 0; }
 
 int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
                         size_t workspace_bytes, void *stream) {

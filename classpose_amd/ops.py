@@ -474,3 +474,117 @@ def pq_stats(true_ids: torch.Tensor, pred_ids: torch.Tensor, true_cls: torch.Ten
         out["insts"] = np.concatenate(insts_all) if insts_all else np.zeros((0, 6), np.int32)
         out["nobg"] = nobg_all
     return out
+
+
+# ---- t1: training the 1x1 class head (csrc/cpx_train.hip) -------------------------------------------------------
+def neck_features(net_ws: torch.Tensor, n_subtiles: int, dtype: torch.dtype) -> torch.Tensor:
+    """View of the neck output [n_subtiles * 1024, 256] that ``cpx_net_forward`` left in its workspace ``net_ws`` (uint8):
+    valid until the next forward on that workspace -- clone it to keep it."""
+    off = _lib.lib().cpx_net_neck_offset(n_subtiles, _DT[dtype])
+    if off == 0:
+        raise ValueError("neck_features: invalid n_subtiles / dtype")
+    n = n_subtiles * 1024 * 256 * torch.empty(0, dtype=dtype).element_size()
+    return net_ws[off:off + n].view(dtype).view(n_subtiles * 1024, 256)
+
+
+def patchify_f32(x: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """float32 NCHW crops (n, 3, H, W), already normalised -> patch rows (n * H/8 * W/8, 192) rounded as ``x.to(dtype)``."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 8 or x.shape[3] % 8:
+        raise ValueError("patchify_f32: expected float32 (n, 3, H, W) with H, W multiples of 8")
+    x = x.contiguous()
+    n, _c, H, W = x.shape
+    out = torch.empty((n * (H // 8) * (W // 8), 192), dtype=dtype, device=x.device)
+    check(_lib.lib().cpx_patchify_f32(ptr(x), n, H, W, _DT[dtype], ptr(out), _stream(x.device)), "patchify_f32")
+    return out
+
+
+class ClassLossOut:
+    """Device results of ``class_loss`` (nothing is copied to the host until ``check_status`` / ``.item()``)."""
+    __slots__ = ("ce", "tversky", "tp", "fp", "fn", "n_annot", "dlogits", "status")
+
+    def check_status(self):
+        flags, first = (int(v) for v in self.status.tolist())
+        if flags & 2:
+            raise ValueError(f"class_loss: image {first} has a label outside [0, nclasses) other than -100")
+        if flags & 1:
+            raise ValueError(f"class_loss: image {first} has no annotated pixel (every label is -100); the reference's "
+                             "Tversky loss is NaN for such a batch -- drop the image")
+
+
+def class_loss(head: torch.Tensor, labels: torch.Tensor, ncls: int, col0: int = 192, class_weights: torch.Tensor | None = None,
+               alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, w_ce: float = 1.0, w_tv: float = 1.0,
+               dlogits: torch.Tensor | None = None, check_status: bool = True) -> ClassLossOut:
+    """Cross-entropy (ignore_index = -100) + focal Tversky loss of the reference's head training and their gradient.
+    head (n * H/8 * W/8, ld_head) float32 token-major (class columns from ``col0``), labels (n, H, W) int16."""
+    if head.dtype != torch.float32 or head.dim() != 2 or not head.is_contiguous():
+        raise ValueError("class_loss: head must be a contiguous float32 (rows, ld_head) tensor")
+    if labels.dtype != torch.int16 or labels.dim() != 3:
+        raise ValueError("class_loss: labels must be int16 (n, H, W)")
+    labels = labels.contiguous()
+    nI, H, W = labels.shape
+    rows, ld = head.shape
+    if H % 8 or W % 8 or rows != nI * (H // 8) * (W // 8) or not 2 <= ncls <= 64 or ld < col0 + ncls * 64:
+        raise ValueError(f"class_loss: head {tuple(head.shape)} does not fit labels {tuple(labels.shape)} with {ncls} classes")
+    dev = head.device
+    L = _lib.lib()
+    o = ClassLossOut()
+    o.ce = torch.empty(1, dtype=torch.float32, device=dev)
+    o.tversky = torch.empty(1, dtype=torch.float32, device=dev)
+    o.tp, o.fp, o.fn = (torch.empty((nI, ncls), dtype=torch.float32, device=dev) for _ in range(3))
+    o.n_annot = torch.empty(nI, dtype=torch.int32, device=dev)
+    o.status = torch.empty(2, dtype=torch.int32, device=dev)
+    o.dlogits = dlogits if dlogits is not None else torch.empty((rows, ncls * 64), dtype=torch.float32, device=dev)
+    if o.dlogits.shape != (rows, ncls * 64) or o.dlogits.dtype != torch.float32 or not o.dlogits.is_contiguous():
+        raise ValueError("class_loss: dlogits must be contiguous float32 (rows, ncls * 64)")
+    if class_weights is not None:
+        class_weights = class_weights.to(device=dev, dtype=torch.float32).contiguous()
+        if class_weights.numel() != ncls:
+            raise ValueError("class_loss: one class weight per class")
+    key = ("closs", nI, H, W, ncls, str(dev))
+    if key not in _ws_cache:
+        _ws_cache[key] = torch.empty(L.cpx_class_loss_workspace_bytes(nI, H, W, ncls), dtype=torch.uint8, device=dev)
+    ws = _ws_cache[key]
+    check(L.cpx_class_loss(ptr(head), ld, col0, ptr(labels), nI, H, W, ncls, ptr(class_weights), alpha, gamma, eps, w_ce, w_tv,
+                           ptr(o.ce), ptr(o.tversky), ptr(o.tp), ptr(o.fp), ptr(o.fn), ptr(o.n_annot), ptr(o.dlogits),
+                           ptr(o.status), ptr(ws), ws.numel(), _stream(dev)), "class_loss")
+    if check_status:
+        o.check_status()
+    return o
+
+
+def head_wgrad(dlogits: torch.Tensor, feat: torch.Tensor):
+    """(dW (n_cols, 256), db (n_cols,)) float32 of the 1x1 head: dW = dlogits^T feat, db = column sums; dlogits (rows, n_cols)
+    float32, feat (rows, 256) in the network dtype."""
+    if dlogits.dtype != torch.float32 or dlogits.dim() != 2 or feat.dim() != 2 or feat.shape != (dlogits.shape[0], 256) \
+            or feat.dtype not in _DT or dlogits.shape[1] % 32 or not dlogits.is_contiguous() or not feat.is_contiguous():
+        raise ValueError("head_wgrad: expected contiguous dlogits (rows, n_cols % 32 == 0) float32 and feat (rows, 256)")
+    rows, N = dlogits.shape
+    dev = dlogits.device
+    L = _lib.lib()
+    dW = torch.empty((N, 256), dtype=torch.float32, device=dev)
+    db = torch.empty(N, dtype=torch.float32, device=dev)
+    key = ("wgrad", rows, N, str(dev))
+    if key not in _ws_cache:
+        _ws_cache[key] = torch.empty(L.cpx_head_wgrad_workspace_bytes(rows, N), dtype=torch.uint8, device=dev)
+    ws = _ws_cache[key]
+    check(L.cpx_head_wgrad(ptr(dlogits), ptr(feat), _DT[feat.dtype], rows, N, ptr(dW), ptr(db), ptr(ws), ws.numel(),
+                           _stream(dev)), "head_wgrad")
+    return dW, db
+
+
+def adamw_step(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int, lr: float,
+               betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.1) -> None:
+    """One torch.optim.AdamW step in place on float32 device tensors; ``step`` counts from 1 (bias corrections in double here)."""
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != param.numel() or t.device != param.device:
+            raise ValueError("adamw_step: four contiguous float32 tensors of one size on one device")
+    if step < 1:
+        raise ValueError("adamw_step: step counts from 1")
+    check(_lib.lib().cpx_adamw_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr), betas[0], betas[1],
+                                    eps, weight_decay, 1.0 - betas[0] ** step, 1.0 - betas[1] ** step, _stream(param.device)),
+          "adamw_step")
+
+
+def round_weights(src: torch.Tensor, dst_ptr: int, dtype_code: int, keep_f32: bool) -> None:
+    """``cpx_round_weights`` from a float32 device tensor into device memory at ``dst_ptr`` (16-byte aligned)."""
+    check(_lib.lib().cpx_round_weights(ptr(src), dst_ptr, src.numel(), dtype_code, int(keep_f32), _stream(src.device)), "round_weights")

@@ -1,0 +1,330 @@
+"""Fine-tuning the 1x1 semantic class head on the device with the backbone, the neck and the flow head frozen.
+
+The reference's cheapest adaptation mode, ``--freeze backbone segmentation_head neck`` (paper_experiments/run_training.py:92-98,
+354-358; vit_sam.py:199-249): ``train_class_seg`` (train.py:356-655) then has two active losses with weight 1 each, the pixel
+cross-entropy with ``ignore_index=-100`` and the focal Tversky loss, optimised by AdamW under the schedule of train.py:460-469.
+Here the forward is the inference network (``cpx_net_forward``), and the loss, its gradient, the weight gradient and the AdamW
+update are the HIP kernels of csrc/cpx_train.hip.  Because the frozen backbone is deterministic, the neck features of a fixed
+training set are computed once and kept on the device (512 KB per 256 x 256 crop in bf16); an epoch then costs only the head.
+
+Deliberately different from the reference:
+  * the backbone runs as in inference.  The reference calls ``net.train()`` every epoch (train.py:609), which re-enables the
+    stochastic layer drop of ``ClassTransformer.forward`` (vit_sam.py:165-173) even in a frozen backbone;
+  * an image without a single annotated pixel raises ``ValueError`` (the reference's Tversky loss is NaN for such a batch);
+  * no augmentation stack, HDF5 datasets, oversampling, learned loss weighting, multi-GPU exchange or optimiser-state resume.
+
+A trainer owns its ``engine.NetWeights`` and updates the head operands in place: sharing them with an ``Engine`` that is running on
+another stream is the caller's risk.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import _lib, engine, ops
+from ._lib import check, ptr
+from .log import get_logger
+
+train_logger = get_logger(__name__)
+
+CROP = 256          # the network's sub-tile size: training crops are exactly one sub-tile
+TOKENS = 1024
+
+
+def lr_schedule(learning_rate: float, n_epochs: int) -> np.ndarray:
+    """Per-epoch learning rates of train.py:460-469: ten warm-up epochs from 0 (entry 0 is 0.0; fewer than 10 epochs still yield
+    10 entries), then constant; above 99 epochs the last 50 are replaced by ten halvings of 5 epochs each, above 300 the last 100
+    by ten halvings of 10."""
+    LR = np.linspace(0, learning_rate, 10)
+    LR = np.append(LR, learning_rate * np.ones(max(0, n_epochs - 10)))
+    if n_epochs > 300:
+        LR = LR[:-100]
+        for _ in range(10):
+            LR = np.append(LR, LR[-1] / 2 * np.ones(10))
+    elif n_epochs > 99:
+        LR = LR[:-50]
+        for _ in range(10):
+            LR = np.append(LR, LR[-1] / 2 * np.ones(5))
+    return LR
+
+
+def prepare_state_dict(pretrained_model, nclasses: int | None = None, head_seed: int = 0) -> tuple[dict, int]:
+    """(state dict with a 1x1 ``out_class`` head in the reference's key layout, class count).  A checkpoint without a semantic head
+    (a plain Cellpose-SAM backbone) gets a freshly initialised one -- nn.Conv2d's default initialisation, seeded -- when ``nclasses``
+    is given, the reference's starting point (README.md:197).  Host only."""
+    sd = pretrained_model if isinstance(pretrained_model, dict) else \
+        torch.load(os.fspath(pretrained_model), map_location="cpu", weights_only=True)
+    sd = {k.removeprefix("module."): v for k, v in sd.items()}
+    if any(k.startswith("out_class.encoder_blocks.") for k in sd):
+        raise NotImplementedError("the checkpoint has a UNet semantic head: only the 1x1 out_class head is trainable here")
+    if "out_class.weight" not in sd:
+        if nclasses is None or nclasses < 2:
+            raise ValueError("the checkpoint has no semantic head: pass nclasses >= 2 to initialise one")
+        g = torch.Generator().manual_seed(head_seed)
+        bound = 1.0 / np.sqrt(256.0)            # kaiming_uniform_(a = sqrt(5)) of a 1x1 conv with fan_in 256, and its bias bound
+        oc = nclasses * 64
+        sd["out_class.weight"] = (torch.rand(oc, 256, 1, 1, generator=g) * 2 - 1) * bound
+        sd["out_class.bias"] = (torch.rand(oc, generator=g) * 2 - 1) * bound
+        sd["W3"] = torch.eye(oc).reshape(oc, nclasses, 8, 8)
+    ncls = sd["out_class.weight"].shape[0] // 64
+    if "W3" not in sd:
+        sd["W3"] = torch.eye(ncls * 64).reshape(ncls * 64, ncls, 8, 8)
+    if sd["W3"].shape[1] != ncls or tuple(sd["out_class.weight"].shape[1:]) != (256, 1, 1):
+        raise ValueError("out_class / W3 of the checkpoint do not describe a 1x1 head over 256 channels")
+    if nclasses is not None and nclasses != ncls:
+        raise ValueError(f"nclasses={nclasses} but the checkpoint's head has {ncls} classes")
+    return sd, ncls
+
+
+def _labels_i16(labels, dev) -> torch.Tensor:
+    t = torch.as_tensor(np.asarray(labels) if not isinstance(labels, torch.Tensor) else labels)
+    if t.dim() != 3 or t.shape[1:] != (CROP, CROP) or t.dtype.is_floating_point:
+        raise ValueError(f"labels: expected integer class maps (n, {CROP}, {CROP}), got {tuple(t.shape)} {t.dtype}")
+    return t.to(device=dev, dtype=torch.int16).contiguous()
+
+
+class HeadTrainer:
+    """Trains ``out_class`` (nn.Conv2d(256, nclasses * 64, 1)) of a checkpoint; everything else stays as loaded.
+
+    The forward numerics are the inference engine's: GEMM operands rounded to the network dtype, a float32 master copy of the head kept
+    here and re-rounded into the operands after every update, so a saved head run by ``predict_wsi`` computes the logits it was
+    trained on.  ``feature_batch`` is the fixed number of crops per backbone launch (short batches are padded): kernel selection
+    depends on the row count, so a fixed one keeps a crop's features bitwise independent of how the crops are batched."""
+
+    def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
+                 weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
+                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
+        self.sd, self.nclasses = prepare_state_dict(pretrained_model, nclasses, head_seed)
+        self.precision = precision
+        self.weights = engine.NetWeights.from_state_dict(self.sd, precision, self.device)
+        self.dtype = engine.NET_DTYPES[precision]
+        self.weight_decay, self.alpha, self.gamma, self.eps = weight_decay, alpha, gamma, eps
+        self.betas, self.adam_eps = betas, adam_eps
+        self.w_ce, self.w_tv = 1.0, 1.0                  # LossAggregator(optimise=False): both multipliers exp(-0) = 1
+        ncols = self.nclasses * 64
+        dev = self.device
+        if class_weights is not None:
+            class_weights = torch.as_tensor(np.float32(class_weights)).to(dev)          # train.py:444-448
+            if class_weights.numel() != self.nclasses:
+                raise ValueError("class_weights: one weight per class")
+        self.class_weights = class_weights
+        self.w = self.sd["out_class.weight"].detach().float().reshape(ncols, 256).contiguous().to(dev)      # master copies
+        self.b = self.sd["out_class.bias"].detach().float().contiguous().to(dev)
+        self.m_w, self.v_w, self.m_b, self.v_b = (torch.zeros_like(t) for t in (self.w, self.w, self.b, self.b))
+        self.n_steps = 0
+        self.feature_batch = int(feature_batch)
+        c = self.weights.c
+        self._L = _lib.lib()
+        nS = self.feature_batch
+        self._net_ws = torch.empty(self._L.cpx_net_workspace_bytes(nS, c.dtype), dtype=torch.uint8, device=dev)
+        self._head_fb = torch.empty((nS * TOKENS, c.ld_head), dtype=torch.float32, device=dev)
+        self._es = torch.empty(0, dtype=self.dtype).element_size()
+        self._buf: dict = {}
+
+    # -- forward pieces ----------------------------------------------------------------------------------------
+    def _patches(self, X) -> torch.Tensor:
+        dev = self.device
+        if isinstance(X, np.ndarray):
+            X = torch.from_numpy(np.ascontiguousarray(X))
+        if X.dtype == torch.uint8:
+            if X.dim() != 4 or X.shape[1:] != (CROP, CROP, 3):
+                raise ValueError(f"uint8 crops must be (n, {CROP}, {CROP}, 3), got {tuple(X.shape)}")
+            x = ops.normalize_img(X.to(dev)).permute(0, 3, 1, 2).contiguous()          # cellpose normalize_img, then NCHW
+        elif X.dtype == torch.float32:
+            if X.dim() != 4 or X.shape[1:] != (3, CROP, CROP):
+                raise ValueError(f"float32 crops must be (n, 3, {CROP}, {CROP}) (already normalised), got {tuple(X.shape)}")
+            x = X.to(dev)
+        else:
+            raise ValueError("crops must be uint8 (n, 256, 256, 3) or float32 (n, 3, 256, 256)")
+        return ops.patchify_f32(x, self.dtype)
+
+    def features(self, X) -> torch.Tensor:
+        """Neck features (n * 1024, 256) in the network dtype of n crops: the input of the class head."""
+        patches = self._patches(X)
+        n = patches.shape[0] // TOKENS
+        FB, c, dev = self.feature_batch, self.weights.c, self.device
+        out = torch.empty((n * TOKENS, 256), dtype=self.dtype, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for s in range(0, n, FB):
+            k = min(FB, n - s)
+            chunk = patches[s * TOKENS:(s + k) * TOKENS]
+            if k < FB:
+                chunk = torch.cat([chunk, torch.zeros(((FB - k) * TOKENS, 192), dtype=self.dtype, device=dev)])
+            check(self._L.cpx_net_forward(C.byref(c), ptr(chunk), FB, ptr(self._head_fb), ptr(self._net_ws), self._net_ws.numel(), st),
+                  "net_forward")
+            out[s * TOKENS:(s + k) * TOKENS] = ops.neck_features(self._net_ws, FB, self.dtype)[:k * TOKENS]
+        return out
+
+    def _as_features(self, X) -> torch.Tensor:
+        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == 256 and X.dtype == self.dtype and X.is_cuda:
+            if X.shape[0] % TOKENS:
+                raise ValueError("features: 1024 rows per crop")
+            return X.contiguous()
+        return self.features(X)
+
+    def head(self, feat: torch.Tensor) -> torch.Tensor:
+        """The head launch of ``cpx_net_forward`` on ``feat``: float32 (rows, ld_head), flow columns 0..191, class columns from 192."""
+        c = self.weights.c
+        rows = feat.shape[0]
+        key = ("head", rows)
+        if key not in self._buf:
+            self._buf[key] = torch.empty((rows, c.ld_head), dtype=torch.float32, device=self.device)
+        out = self._buf[key]
+        check(self._L.cpx_gemm(c.dtype, ptr(feat), c.head_w, rows, c.ld_head, 256, ops.EPI["f32"], c.head_b, None, ptr(out), c.ld_head,
+                               torch.cuda.current_stream(self.device).cuda_stream), "head gemm")
+        return out
+
+    def _loss(self, X, labels):
+        feat = self._as_features(X)
+        lab = _labels_i16(labels, self.device)
+        if lab.shape[0] * TOKENS != feat.shape[0]:
+            raise ValueError(f"{feat.shape[0] // TOKENS} crops but {lab.shape[0]} label maps")
+        head = self.head(feat)
+        key = ("dl", feat.shape[0])
+        if key not in self._buf:
+            self._buf[key] = torch.empty((feat.shape[0], self.nclasses * 64), dtype=torch.float32, device=self.device)
+        o = ops.class_loss(head, lab, self.nclasses, 192, self.class_weights, self.alpha, self.gamma, self.eps, self.w_ce, self.w_tv,
+                           dlogits=self._buf[key], check_status=True)
+        return feat, head, o
+
+    def _result(self, o, n) -> dict:
+        ce, tv = float(o.ce.item()), float(o.tversky.item())
+        return {"ce": ce, "tversky": tv, "loss": self.w_ce * ce + self.w_tv * tv, "n": n}
+
+    # -- public ------------------------------------------------------------------------------------------------
+    def evaluate(self, X, labels, return_head: bool = False) -> dict:
+        """Losses of a batch without an update.  ``return_head`` adds the float32 head buffer (a view that the next call overwrites)."""
+        feat, head, o = self._loss(X, labels)
+        r = self._result(o, feat.shape[0] // TOKENS)
+        if return_head:
+            r["head"] = head
+        return r
+
+    def step(self, X, labels, lr: float) -> dict:
+        """One optimisation step on a batch of crops (or of cached ``features``) at learning rate ``lr``; returns the losses of the
+        batch BEFORE the update, like the reference's loop."""
+        feat, _head, o = self._loss(X, labels)            # raises before anything is updated
+        dW, db = ops.head_wgrad(o.dlogits, feat)
+        self.n_steps += 1
+        kw = dict(betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay)     # net.parameters(): decay on the bias too
+        ops.adamw_step(self.w, dW, self.m_w, self.v_w, self.n_steps, lr, **kw)
+        ops.adamw_step(self.b, db, self.m_b, self.v_b, self.n_steps, lr, **kw)
+        self._refresh_operands()
+        return self._result(o, feat.shape[0] // TOKENS)
+
+    def _refresh_operands(self) -> None:
+        """Master weights -> the head operands of ``self.weights`` in place (rows 192... of head_w and head_b), rounded as at load."""
+        c = self.weights.c
+        half = c.dtype != _lib.DT_F32
+        ops.round_weights(self.w, c.head_w + 192 * 256 * self._es, c.dtype, keep_f32=not half)
+        ops.round_weights(self.b, c.head_b + 192 * 4, c.dtype, keep_f32=True)
+
+    def state_dict(self) -> dict:
+        """The checkpoint in the reference's key layout (vit_sam.py:269-285): ``out_class.weight`` [ncls * 64, 256, 1, 1],
+        ``out_class.bias``, ``W3``; every other entry as loaded."""
+        sd = dict(self.sd)
+        sd["out_class.weight"] = self.w.detach().cpu().reshape(self.nclasses * 64, 256, 1, 1).clone()
+        sd["out_class.bias"] = self.b.detach().cpu().clone()
+        return sd
+
+    def save(self, path, save_only_trainable_params: bool = False) -> None:
+        sd = self.state_dict()
+        if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
+            sd = {k: sd[k] for k in ("out_class.weight", "out_class.bias")}
+        torch.save(sd, os.fspath(path))
+
+
+def _check_dataset(images, labels, what: str):
+    images, labels = np.asarray(images), np.asarray(labels)
+    ok_u8 = images.dtype == np.uint8 and images.ndim == 4 and images.shape[1:] == (CROP, CROP, 3)
+    ok_f32 = images.dtype == np.float32 and images.ndim == 4 and images.shape[1:] == (3, CROP, CROP)
+    if not (ok_u8 or ok_f32):
+        raise ValueError(f"{what} images: expected (N, 256, 256, 3) uint8 or (N, 3, 256, 256) float32, got {images.shape} {images.dtype}")
+    if labels.shape != (len(images), CROP, CROP) or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"{what} labels: expected integer class maps {(len(images), CROP, CROP)}, got {labels.shape} {labels.dtype}")
+    empty = np.nonzero((labels == -100).reshape(len(labels), -1).all(1))[0]
+    if len(empty):
+        raise ValueError(f"{what} image {int(empty[0])} has no annotated pixel (every label is -100): drop it")
+    return images, labels
+
+
+def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, test_labels=None, batch_size: int = 8,
+                     n_epochs: int = 100, learning_rate: float = 5e-5, nimg_per_epoch: int | None = None, cache_features: bool = True,
+                     save_path=None, model_name: str | None = None, random_seed: int = 42, transform=None):
+    """The epoch loop of train.py:606-655 for the frozen-backbone mode: per-epoch learning rate from ``lr_schedule``, seeded sampling
+    without replacement (with, when ``nimg_per_epoch`` exceeds the set), sample-weighted running means of CE / Tversky / total,
+    validation once per epoch, ``checkpoint_last.pt`` and ``checkpoint_best.pt`` (lowest validation loss; training loss without a
+    validation set) next to the final model.  ``cache_features`` runs the backbone once per image; ``transform(X, labels, rng) ->
+    (X, labels)``, a host callback per batch for callers who augment, forces the uncached path.
+    Returns ``(path of the final model, train_losses, test_losses)``."""
+    images, labels = _check_dataset(images, labels, "training")
+    has_test = test_images is not None
+    if has_test:
+        test_images, test_labels = _check_dataset(test_images, test_labels, "validation")
+    nimg = len(images)
+    nimg_per_epoch = nimg if nimg_per_epoch is None else int(nimg_per_epoch)
+    LR = lr_schedule(learning_rate, n_epochs)
+    model_name = "classpose_head" if model_name is None else model_name
+    model_dir = (Path.cwd() if save_path is None else Path(save_path)) / model_name
+    model_dir.mkdir(parents=True, exist_ok=True)
+    filename = model_dir / model_name
+    cached = cache_features and transform is None
+    dev = trainer.device
+    lab_dev = test_lab_dev = feats = test_feats = None
+    if cached:
+        train_logger.info(">>> caching neck features of %d training crops", nimg)
+        feats = trainer.features(images).view(nimg, TOKENS, 256)
+        lab_dev = _labels_i16(labels, dev)
+        if has_test:
+            test_feats = trainer.features(test_images).view(len(test_images), TOKENS, 256)
+            test_lab_dev = _labels_i16(test_labels, dev)
+    train_logger.info(">>> n_epochs=%d, n_train=%d, n_test=%s, AdamW, learning_rate=%0.5f, weight_decay=%0.5f, cached features: %s",
+                      n_epochs, nimg, len(test_images) if has_test else None, learning_rate, trainer.weight_decay, cached)
+    train_losses, test_losses = np.zeros(n_epochs), np.zeros(n_epochs)
+    best = np.inf
+    for iepoch in range(n_epochs):
+        rng = np.random.default_rng([random_seed, iepoch])
+        order = rng.permutation(nimg)[:nimg_per_epoch] if nimg_per_epoch <= nimg else rng.choice(nimg, nimg_per_epoch)
+        sums, count = np.zeros(3), 0
+        for s in range(0, len(order), batch_size):
+            idx = order[s:s + batch_size]
+            if cached:
+                ti = torch.from_numpy(idx).to(dev)
+                x, y = feats[ti].reshape(-1, 256), lab_dev[ti]
+            else:
+                x, y = images[idx], labels[idx]
+                if transform is not None:
+                    x, y = transform(x, y, rng)
+            r = trainer.step(x, y, float(LR[iepoch]))
+            sums += np.array([r["ce"], r["tversky"], r["loss"]]) * len(idx)
+            count += len(idx)
+        train_losses[iepoch] = sums[2] / count
+        msg = f"{iepoch}, train_loss={sums[2] / count:.4f} (ce={sums[0] / count:.4f}, tversky={sums[1] / count:.4f}), LR={LR[iepoch]:.6f}"
+        if has_test:
+            tsum, tcount = 0.0, 0
+            for s in range(0, len(test_images), batch_size):
+                if cached:
+                    x, y = test_feats[s:s + batch_size].reshape(-1, 256), test_lab_dev[s:s + batch_size]
+                else:
+                    x, y = test_images[s:s + batch_size], test_labels[s:s + batch_size]
+                r = trainer.evaluate(x, y)
+                tsum += r["loss"] * r["n"]
+                tcount += r["n"]
+            test_losses[iepoch] = tsum / tcount
+            msg += f", test_loss={test_losses[iepoch]:.4f}"
+        train_logger.info(msg)
+        trainer.save(model_dir / "checkpoint_last.pt")
+        score = test_losses[iepoch] if has_test else train_losses[iepoch]
+        if score < best:
+            best = score
+            trainer.save(model_dir / "checkpoint_best.pt")
+    trainer.save(filename)
+    train_logger.info(">>> saved model to %s", filename)
+    return filename, train_losses, test_losses

@@ -46,7 +46,7 @@ extern "C" {
  * cpx_prof_collect_launches without a bump (additive); 3 (round 5) = cpx_prof_collect fills CPX_PROF_N_KINDS = 7 entries (was 5) and
  * the post-processing workspace of cpx_postproc_workspace_bytes holds six table sets per tile -- callers compiled against version 2
  * must be rebuilt, and classpose_amd/_lib.py refuses a library whose version differs.  cpx_pq_workspace_bytes and cpx_pq_stats (the
- * panoptic-quality statistics) were ADDED later without a bump, like the round-4 additions.                                    */
+ * panoptic-quality statistics) and the head-training entry points of section t1 were ADDED later without a bump, like the round-4 additions. */
 int cpx_abi_version(void);
 /* Last HIP error string recorded by a failing call on this thread (host ptr). */
 const char *cpx_last_error(void);
@@ -451,6 +451,64 @@ int cpx_pq_stats(const void *true_ids, const void *pred_ids, int id_bytes, const
                  int table_cap, int32_t *tp, int32_t *fp, int32_t *fn, double *iou_sum, int32_t *status, int32_t *nobg,
                  cpx_pq_pair *pairs, int max_pairs, cpx_pq_inst *insts, int max_insts, int32_t *list_counts,
                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
+ * t1  training the 1x1 semantic class head with the backbone frozen (csrc/cpx_train.hip; additive, no ABI bump)
+ * replaces, for `--freeze backbone segmentation_head neck` (paper_experiments/run_training.py:92-98,354-358,
+ * classpose/vit_sam.py:199-249), one step of train_class_seg (classpose/train.py:606-655):
+ * net(X) is cpx_net_forward; the rest is below.  Every entry point takes a stream and allocates nothing; no floating-point atomics:
+ * every result is bitwise reproducible run to run.
+ *
+ * cpx_net_neck_offset: byte offset, inside the workspace of cpx_net_forward for the same (n_subtiles, dtype), of the neck output
+ *   [n_subtiles * 1024][256] (element type = network dtype) -- the operand of the head GEMM, i.e. the input of out / out_class
+ *   (vit_sam.py:233-249).  It is valid after cpx_net_forward has run on the stream and until the next forward on that workspace.
+ *   0 = invalid argument.
+ * cpx_patchify_f32: float32 NCHW crops x [nS][3][H][W], already normalised (what the reference's loader hands to net(X),
+ *   train.py:617-620) -> patch rows [nS * (H/8) * (W/8)][192], k = c*64 + i*8 + j, rounded to `dtype` as X.to(dtype) rounds
+ *   (core.py:61-63).  H, W multiples of 8 (the network takes 256).                                                              */
+size_t cpx_net_neck_offset(int n_subtiles, int dtype);
+int cpx_patchify_f32(const float *x, int nS, int H, int W, int dtype, void *patches, void *stream);
+
+/* cpx_class_loss: _loss_fn_class (train.py:156-181: nn.CrossEntropyLoss(reduction="mean", weight, ignore_index=-100)) and
+ *   _loss_fn_tversky (train.py:108-153), their weighted sum as LossAggregator(optimise=False) forms it (train.py:41-84,482-493,642; both
+ *   multipliers 1 there) and d(w_ce * CE + w_tv * Tversky) / d logits (what loss.backward(), train.py:645, leaves at out_class's output).
+ *   head [nI * (H/8) * (W/8)][ld_head] float32 token-major: column col0 + c*64 + i*8 + j of token (ph, pw) is the class-c logit of
+ *   pixel (8 ph + i, 8 pw + j) -- the layout cpx_blend_subtiles reads, col0 = 192 for the head buffer of cpx_net_forward.
+ *   labels [nI][H][W] int16, -100 = not annotated; class_weights [ncls] or NULL; 2 <= ncls <= 64.
+ *     CE      = sum w[y] * (-log softmax(z)[y]) / sum w[y]                      over the annotated pixels of the batch
+ *     Tversky = mean over (image b, class c) of clip(1 - tp / (tp + alpha fp + (1 - alpha) fn), eps, 1 - eps)^(1/gamma) * w[c],
+ *               tp = sum p[c] [y = c], fp = sum p[c] [y != c], fn = sum (1 - p[c]) [y = c] over the annotated pixels of image b;
+ *               the clip passes no gradient outside [eps, 1 - eps]: a class absent from an image (raw loss exactly 1) contributes
+ *               (1 - eps)^(1/gamma) * w[c] and a zero gradient.
+ *   Out: ce [1], tversky [1], tp / fp / fn [nI][ncls] float32, n_annot [nI] annotated pixels per image, dlogits
+ *   [rows][ncls * 64] float32 in the same column order (rows of pixels that are not annotated are exactly zero), status [2]:
+ *   status[0] = CPX_LOSS_* flags, status[1] = the first image they apply to (or -1).  An image without annotated pixels makes the
+ *   reference return NaN; here it is flagged (the outputs are then undefined) and the Python layer raises.
+ *   Two passes over the logits with a one-workgroup kernel between them; sums are float64, added in a fixed order.                 */
+#define CPX_LOSS_EMPTY_IMAGE 1    /* an image has no annotated pixel                    */
+#define CPX_LOSS_BAD_LABEL 2      /* a label other than -100 lies outside [0, ncls)     */
+size_t cpx_class_loss_workspace_bytes(int nI, int H, int W, int ncls);
+int cpx_class_loss(const float *head, int ld_head, int col0, const int16_t *labels, int nI, int H, int W, int ncls,
+                   const float *class_weights, float alpha, float gamma, float eps, float w_ce, float w_tv,
+                   float *ce, float *tversky, float *tp, float *fp, float *fn, int32_t *n_annot, float *dlogits,
+                   int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* cpx_head_wgrad: the backward of out_class = nn.Conv2d(256, ncls * 64, 1) (vit_sam.py:199-249) for its own parameters:
+ *   dW [n_cols][256] = dlogits^T feat, db [n_cols] = column sums of dlogits; dlogits [rows][n_cols] float32, feat [rows][256] of
+ *   `dtype` (widened exactly), n_cols % 32 == 0, float32 out.  v_mfma_f32_32x32x2_f32 (exact float32) over slabs of
+ *   cpx_head_wgrad_slab_rows rows; the per-slab partials are added in slab order in float64 and rounded once.                    */
+int cpx_head_wgrad_slab_rows(void);
+size_t cpx_head_wgrad_workspace_bytes(int rows, int n_cols);
+int cpx_head_wgrad(const float *dlogits, const void *feat, int dtype, int rows, int n_cols, float *dW, float *db,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
+/* cpx_adamw_step: torch.optim.AdamW (train.py:478-480,648; amsgrad off) on float32 parameters with float32 moments, in place:
+ *   p *= 1 - lr * weight_decay;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
+ *   p -= lr / bias_correction1 * m / (sqrt(v) / sqrt(bias_correction2) + eps),  bias_correction_i = 1 - beta_i^step from the host.
+ *   lr = 0 (the first epoch of the schedule, train.py:460) leaves the parameters bitwise unchanged.                               */
+int cpx_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long long n, double lr,
+                   double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
+                   double bias_correction2, void *stream);
 
 /* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
