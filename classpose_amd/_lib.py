@@ -151,6 +151,11 @@ SIGNATURES = {
     "cpx_head_wgrad_workspace_bytes": (_sz, [_i, _i]),
     "cpx_head_wgrad": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "cpx_adamw_step": (_i, [_p, _p, _p, _p, C.c_longlong, _d, _d, _d, _d, _d, _d, _d, _p]),
+    "cpx_hed_jitter_u8": (_i, [_p, _i, _i, _i, _p, _p, _d, _d, _i, _p, _p, _p]),
+    "cpx_warp_affine_u8": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "cpx_warp_affine_f32": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "cpx_normalize_stats_f32": (_i, [_p, _i, _i, _i, _i, _f, _i, _f, _p, _p]),
+    "cpx_normalize_apply_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),

@@ -1,0 +1,306 @@
+// Training-time augmentation on gfx950 (t2):
+//   stain jitter of uint8 patches in the HED colour space (HEDTransform.transform)
+//   affine warp of images (bilinear, constant border 0) and class maps (nearest)
+//   exact percentile normalisation of float32 planes (normalize_img -> normalize99 after the warp)
+// None of these is a throughput kernel: one thread per output pixel, planar stores, LDS histograms.
+// Built with -ffp-contract=off: the warp's coordinates equal numpy's float64 a * x + b * y + c, and the lerps and the
+// quantile arithmetic are the unfused float32 operations of tests/augment_reference.py.
+#include "cpx_common.h"
+
+#define NTHR 256
+
+// ---------------------------------------------------------------------------
+// stain jitter
+// ---------------------------------------------------------------------------
+// float32(scipy.linalg.inv(RGB_FROM_HED)) of the reference (tests/golden/reference_augment.npz: HED_FROM_RGB) and
+// float32 RGB_FROM_HED, row-major [from][to]
+__constant__ float c_hed_from_rgb[9] = {1.87798285f,    -1.00767875f, -0.556115806f, -0.0659080595f, 1.13473034f,
+                                        -0.135521799f,  -0.601907432f, -0.480414152f, 1.57358813f};
+__constant__ float c_rgb_from_hed[9] = {0.65f, 0.70f, 0.29f, 0.07f, 0.99f, 0.11f, 0.27f, 0.57f, 0.78f};
+
+__device__ __forceinline__ uint32_t byte_sum(uint32_t u) {
+    return (u & 0xffu) + ((u >> 8) & 0xffu) + ((u >> 16) & 0xffu) + (u >> 24);
+}
+// one workgroup per image: the exact integer sum of its bytes, then the reference's cut-off test in double
+__global__ void __launch_bounds__(1024) k_hed_decide(const uint8_t *__restrict__ img, long long count, double lo, double hi,
+                                                     int32_t *__restrict__ applied) {
+    __shared__ unsigned long long part[16];
+    const uint8_t *p = img + (size_t)blockIdx.x * count;
+    unsigned long long s = 0;
+    // bytes up to the first 16-byte boundary, then 16 per load, then the tail
+    const long long head = min(count, (long long)((16 - ((uintptr_t)p & 15)) & 15));
+    const long long nvec = (count - head) / 16;
+    const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
+    for (long long i = threadIdx.x; i < head; i += 1024) s += p[i];
+    for (long long i = threadIdx.x; i < nvec; i += 1024) {
+        const uint4 q = v[i];
+        s += byte_sum(q.x) + byte_sum(q.y) + byte_sum(q.z) + byte_sum(q.w);
+    }
+    for (long long i = head + nvec * 16 + threadIdx.x; i < count; i += 1024) s += p[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        for (int w = 0; w < 16; ++w) tot += part[w];
+        const double mean = ((double)tot / (double)count) / 255.0;      // np.mean(patch) / 255.0
+        applied[blockIdx.x] = (lo <= mean && mean <= hi) ? 1 : 0;
+    }
+}
+
+__global__ void k_hed_jitter(const uint8_t *__restrict__ img, const float *__restrict__ sigma, const float *__restrict__ bias,
+                             const int32_t *__restrict__ applied, int HW, int simple_mode, uint8_t *__restrict__ out) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= HW) return;
+    const size_t t = blockIdx.y;
+    const uint8_t *px = img + (t * HW + p) * 3;
+    uint8_t *o = out + (t * HW + p) * 3;
+    if (!applied[t]) { o[0] = px[0]; o[1] = px[1]; o[2] = px[2]; return; }
+    float l[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = (float)((double)px[c] / 255.0);                       // (patch / 255.0).astype(float32)
+        if (simple_mode) v = fminf(fmaxf(v, 1e-6f), 1.0f);
+        else v = v + 1.0f;                                              // shift = 1: the minimum of a uint8 patch is >= 0
+        l[c] = -logf(v);
+    }
+    float h[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        float s = l[0] * c_hed_from_rgb[j] + l[1] * c_hed_from_rgb[3 + j] + l[2] * c_hed_from_rgb[6 + j];
+        s = s * (1.0f + sigma[t * 3 + j]) + bias[t * 3 + j];
+        h[j] = -s;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float x = expf(h[0] * c_rgb_from_hed[c] + h[1] * c_rgb_from_hed[3 + c] + h[2] * c_rgb_from_hed[6 + c]);
+        if (!simple_mode) {
+            x = x - 1.0f;
+            x = fminf(fmaxf(x, -1.0f), 1.0f);                           // rescale_intensity(in_range=(-1, 1)) onto (-1, 1)
+            x = (x - (-1.0f)) / 2.0f * 2.0f + (-1.0f);
+        }
+        x = fminf(fmaxf(x, 0.0f), 1.0f);
+        o[c] = (uint8_t)(int)(x * 255.0f);                              // astype(uint8): truncation
+    }
+}
+
+extern "C" int cpx_hed_jitter_u8(const uint8_t *img, int n, int H, int W, const float *sigma, const float *bias,
+                                 double cutoff_lo, double cutoff_hi, int simple_mode, uint8_t *out, int32_t *applied,
+                                 void *stream) {
+    CPX_REQUIRE(img && sigma && bias && out && applied && img != out && n > 0 && n <= 65535 && H > 0 && W > 0);
+    CPX_REQUIRE((long long)H * W < (1ll << 29));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_hed_decide, dim3(n), dim3(1024), 0, s, img, (long long)H * W * 3, cutoff_lo, cutoff_hi, applied);
+    hipLaunchKernelGGL(k_hed_jitter, dim3(cpx_cdiv((long long)H * W, NTHR), n), dim3(NTHR), 0, s, img, sigma, bias, applied,
+                       H * W, simple_mode ? 1 : 0, out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// affine warp
+// ---------------------------------------------------------------------------
+// U8: src [n][sh][sw][3] uint8, else [n][3][sh][sw] float32.  A tap outside the source is 0 on its own.
+template <bool U8>
+__device__ __forceinline__ float warp_tap(const void *src, size_t t, int sh, int sw, int c, int y, int x) {
+    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) return 0.f;
+    if (U8) return (float)((const uint8_t *)src)[((t * sh + y) * sw + x) * 3 + c];
+    return ((const float *)src)[((t * 3 + c) * sh + y) * sw + x];
+}
+
+template <bool U8>
+__global__ void k_warp_affine(const void *__restrict__ src, const int16_t *__restrict__ lab, int sh, int sw,
+                              const double *__restrict__ inv, int dh, int dw, int label_fill, float *__restrict__ out,
+                              int16_t *__restrict__ lab_out) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= dh * dw) return;
+    const size_t t = blockIdx.y;
+    const int y = p / dw, x = p - y * dw;
+    const double *m = inv + t * 6;
+    const double sx = m[0] * (double)x + m[1] * (double)y + m[2];
+    const double sy = m[3] * (double)x + m[4] * (double)y + m[5];
+    float v[3] = {0.f, 0.f, 0.f};
+    // floor(sx) in [-1, sw - 1] and floor(sy) in [-1, sh - 1], or every tap is outside (NaN lands here too)
+    if (sx >= -1.0 && sx < (double)sw && sy >= -1.0 && sy < (double)sh) {
+        const double fx = floor(sx), fy = floor(sy);
+        const int x0 = (int)fx, y0 = (int)fy;
+        const float wx = (float)(sx - fx), wy = (float)(sy - fy);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float a = warp_tap<U8>(src, t, sh, sw, c, y0, x0), b = warp_tap<U8>(src, t, sh, sw, c, y0, x0 + 1);
+            const float d = warp_tap<U8>(src, t, sh, sw, c, y0 + 1, x0), e = warp_tap<U8>(src, t, sh, sw, c, y0 + 1, x0 + 1);
+            const float top = a + (b - a) * wx;
+            const float bot = d + (e - d) * wx;
+            v[c] = top + (bot - top) * wy;
+        }
+    }
+    const size_t plane = (size_t)dh * dw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
+    if (lab) {
+        int r = label_fill;
+        const double nx = floor(sx + 0.5), ny = floor(sy + 0.5);
+        if (nx >= 0.0 && nx < (double)sw && ny >= 0.0 && ny < (double)sh) r = lab[(t * sh + (int)ny) * sw + (int)nx];
+        lab_out[t * plane + p] = (int16_t)r;
+    }
+}
+
+template <bool U8>
+static int warp_launch(const void *src, const int16_t *labels, int n, int sh, int sw, const double *inv, int dh, int dw,
+                       int label_fill, float *out, int16_t *labels_out, void *stream) {
+    CPX_REQUIRE(src && inv && out && n > 0 && n <= 65535 && sh > 0 && sw > 0 && dh > 0 && dw > 0);
+    CPX_REQUIRE((labels == nullptr) == (labels_out == nullptr));
+    CPX_REQUIRE((long long)sh * sw < (1ll << 29) && (long long)dh * dw < (1ll << 29));
+    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
+    hipLaunchKernelGGL(k_warp_affine<U8>, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, (hipStream_t)stream,
+                       src, labels, sh, sw, inv, dh, dw, label_fill, out, labels_out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+extern "C" int cpx_warp_affine_u8(const uint8_t *src, const int16_t *labels, int n, int sh, int sw, const double *inv,
+                                  int dh, int dw, int label_fill, float *out, int16_t *labels_out, void *stream) {
+    return warp_launch<true>(src, labels, n, sh, sw, inv, dh, dw, label_fill, out, labels_out, stream);
+}
+extern "C" int cpx_warp_affine_f32(const float *src, const int16_t *labels, int n, int sh, int sw, const double *inv,
+                                   int dh, int dw, int label_fill, float *out, int16_t *labels_out, void *stream) {
+    CPX_REQUIRE((const void *)src != (const void *)out);
+    return warp_launch<false>(src, labels, n, sh, sw, inv, dh, dw, label_fill, out, labels_out, stream);
+}
+
+// ---------------------------------------------------------------------------
+// float32 percentile normalisation
+// ---------------------------------------------------------------------------
+// order-preserving 32-bit key of a float; -0.0 and 0.0 share one key
+__device__ __forceinline__ uint32_t f32_key(float x) {
+    if (x == 0.f) x = 0.f;
+    const uint32_t u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_f32(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ float np_lerp_f32(float a, float b, float t) {      // numpy _lerp in float32
+    const float diff = b - a;
+    float r = a + diff * t;
+    if (t >= 0.5f) r = b - diff * (1.0f - t);
+    return r;
+}
+
+#define SEL_THR 1024
+// One workgroup per (image, channel) plane.  Radix select, most significant byte first: four passes over the plane, each
+// a 256-bin LDS histogram per rank of the keys that still match the rank's prefix; wave r then scans histogram r (lane l
+// owns bins 4l .. 4l + 3) and picks the bin in which rank r falls.  Ranks with one prefix share a histogram (pass 0: all four).
+__global__ void __launch_bounds__(SEL_THR) k_norm_stats_f32(const float *__restrict__ x, int HW, int lo_prev, float lo_g,
+                                                            int hi_prev, float hi_g, float *__restrict__ stats) {
+    __shared__ uint32_t hist[4][256];
+    __shared__ uint32_t s_prefix[4], s_rank[4], s_min, s_max;
+    const float *pl = x + (size_t)blockIdx.x * HW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) {
+        s_rank[0] = lo_prev; s_rank[1] = min(lo_prev + 1, HW - 1);
+        s_rank[2] = hi_prev; s_rank[3] = min(hi_prev + 1, HW - 1);
+        s_prefix[0] = s_prefix[1] = s_prefix[2] = s_prefix[3] = 0;
+        s_min = 0xffffffffu; s_max = 0;
+    }
+    uint32_t kmin = 0xffffffffu, kmax = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        for (int i = tid; i < 4 * 256; i += SEL_THR) (&hist[0][0])[i] = 0;
+        __syncthreads();
+        uint32_t pre[4];
+        bool own[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            pre[r] = s_prefix[r];
+            own[r] = r == 0 || pre[r] != pre[r - 1];         // ranks ascend, so equal prefixes are neighbours
+        }
+        for (int i = tid; i < HW; i += SEL_THR) {
+            const uint32_t k = f32_key(pl[i]);
+            const uint32_t d = (k >> shift) & 255u;
+            if (pass == 0) {
+                // every value counts, and the sign and exponent bits of an image take a handful of values: 64 lanes adding
+                // to one LDS word would serialise, so each distinct digit of the wave is added once, by its first lane
+                kmin = min(kmin, k); kmax = max(kmax, k);
+                unsigned long long todo = __ballot(1);
+                while (todo) {
+                    const int l = __ffsll((long long)todo) - 1;
+                    const uint32_t dl = __shfl(d, l);
+                    const unsigned long long m = __ballot(d == dl);
+                    if (lane == l) atomicAdd(&hist[0][dl], (uint32_t)__popcll(m));
+                    todo &= ~m;
+                }
+                continue;
+            }
+            const uint32_t hi_bits = k >> (shift + 8);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (own[r] && hi_bits == pre[r]) atomicAdd(&hist[r][d], 1u);
+        }
+        if (pass == 0) { atomicMin(&s_min, kmin); atomicMax(&s_max, kmax); }
+        __syncthreads();
+        if (wave < 4) {
+            int r = wave;                                    // the histogram of rank `wave` is its owner's
+            while (!own[r]) --r;
+            const uint32_t *h = hist[r] + 4 * lane;
+            const uint32_t c0 = h[0], c1 = c0 + h[1], c2 = c1 + h[2], c3 = c2 + h[3];
+            uint32_t incl = c3;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = __shfl_up(incl, o);
+                if (lane >= o) incl += up;
+            }
+            const uint32_t excl = incl - c3, k = s_rank[wave];
+            const unsigned long long m = __ballot(incl > k);
+            const int l = __ffsll((long long)m) - 1;         // first lane whose cumulative count passes the rank
+            if (lane == l) {
+                const int sub = excl + c0 > k ? 0 : (excl + c1 > k ? 1 : (excl + c2 > k ? 2 : 3));
+                const uint32_t below = excl + (sub == 0 ? 0u : (sub == 1 ? c0 : (sub == 2 ? c1 : c2)));
+                s_prefix[wave] = (pre[wave] << 8) | (uint32_t)(4 * lane + sub);
+                s_rank[wave] = k - below;                    // rank among the keys that carry the longer prefix
+            }
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const float g0 = key_f32(s_prefix[0]), g1 = key_f32(s_prefix[1]), g2 = key_f32(s_prefix[2]), g3 = key_f32(s_prefix[3]);
+    const float x01 = np_lerp_f32(g0, g1, lo_g), x99 = np_lerp_f32(g2, g3, hi_g);
+    const float den = x99 - x01;
+    float mode;
+    if (s_max == s_min) mode = 0.f;                          // np.ptp == 0: channel left untouched
+    else if (den > (float)1e-3) mode = 1.f;
+    else mode = 2.f;
+    float *st = stats + (size_t)blockIdx.x * 4;
+    st[0] = x01; st[1] = den; st[2] = mode; st[3] = x99;
+}
+
+__global__ void k_norm_apply_f32(const float *__restrict__ x, const float *__restrict__ stats, int HW, float *__restrict__ out) {
+    const int i = blockIdx.x * NTHR + threadIdx.x;
+    if (i >= HW) return;
+    const size_t pl = blockIdx.y;
+    const float *st = stats + pl * 4;
+    float v = x[pl * HW + i];
+    const float mode = st[2];
+    if (mode == 1.f) { v = v - st[0]; v = __fdiv_rn(v, st[1]); }
+    else if (mode == 2.f) v = 0.f;
+    out[pl * HW + i] = v;
+}
+
+extern "C" int cpx_normalize_stats_f32(const float *img, int n, int H, int W, int lo_prev, float lo_gamma, int hi_prev,
+                                       float hi_gamma, float *stats, void *stream) {
+    CPX_REQUIRE(img && stats && n > 0 && n <= (1 << 20) && H > 0 && W > 0 && (long long)H * W < (1ll << 30));
+    CPX_REQUIRE(lo_prev >= 0 && hi_prev >= lo_prev && hi_prev < H * W);
+    hipLaunchKernelGGL(k_norm_stats_f32, dim3(n * 3), dim3(SEL_THR), 0, (hipStream_t)stream, img, H * W, lo_prev, lo_gamma,
+                       hi_prev, hi_gamma, stats);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+extern "C" int cpx_normalize_apply_f32(const float *img, const float *stats, int n, int H, int W, float *out, void *stream) {
+    CPX_REQUIRE(img && stats && out && n > 0 && n <= 21845 && H > 0 && W > 0 && (long long)H * W < (1ll << 30));
+    hipLaunchKernelGGL(k_norm_apply_f32, dim3(cpx_cdiv((long long)H * W, NTHR), n * 3), dim3(NTHR), 0, (hipStream_t)stream,
+                       img, stats, H * W, out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}

@@ -3,7 +3,7 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 (paper_experiments/run_training.py:92-98,354-358) reduced to arrays of fixed-size crops.
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
-        --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0
+        --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5]
 
 Images are ``(N, 256, 256, 3)`` uint8 (normalised per crop like inference does) or ``(N, 3, 256, 256)`` float32 (already
 normalised); labels ``(N, 256, 256)`` integer class maps with -100 where nothing is annotated.  The result is an ordinary
@@ -37,6 +37,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--cache_features", action=argparse.BooleanOptionalAction, default=True,
                    help="run the frozen backbone once per crop and train from the cached neck features")
+    p.add_argument("--augment", default=None, choices=["hed_only", "geometry", "enhanced"],
+                   help="augment every training batch on the device: hed_only = stain jitter + flip / rotation / scale / crop, "
+                        "geometry = the latter alone (enhanced is not built)")
+    p.add_argument("--scale_range", type=float, default=0.5, help="random scale in [1 - r/2, 1 + r/2] (with --augment)")
+    p.add_argument("--augment_label_fill", type=int, default=0,
+                   help="class of pixels the warp takes from outside the crop: 0 = background as in the reference, -100 = not annotated")
     p.add_argument("--save_only_trainable_params", action="store_true")
     p.add_argument("--random_seed", type=int, default=42)
     p.add_argument("--save_path", required=True)
@@ -57,7 +63,8 @@ def main(args) -> None:
     path, train_losses, test_losses = train_class_head(
         trainer, images, labels, test_images, test_labels, batch_size=args.batch_size, n_epochs=args.n_epochs,
         learning_rate=args.learning_rate, nimg_per_epoch=args.nimg_per_epoch, cache_features=args.cache_features,
-        save_path=args.save_path, model_name=args.model_name, random_seed=args.random_seed)
+        save_path=args.save_path, model_name=args.model_name, random_seed=args.random_seed,
+        augment=args.augment, scale_range=args.scale_range, label_fill=args.augment_label_fill)
     if args.save_only_trainable_params:
         trainer.save(path, save_only_trainable_params=True)
     logger.info(f"final train loss {train_losses[-1]:.4f}" + (f", test loss {test_losses[-1]:.4f}" if test_images is not None else ""))

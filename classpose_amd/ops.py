@@ -588,3 +588,74 @@ def adamw_step(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, e
 def round_weights(src: torch.Tensor, dst_ptr: int, dtype_code: int, keep_f32: bool) -> None:
     """``cpx_round_weights`` from a float32 device tensor into device memory at ``dst_ptr`` (16-byte aligned)."""
     check(_lib.lib().cpx_round_weights(ptr(src), dst_ptr, src.numel(), dtype_code, int(keep_f32), _stream(src.device)), "round_weights")
+
+
+# ---- t2: training-time augmentation (csrc/cpx_augment.hip) --------------------------------------------------------
+def hed_jitter(img_u8: torch.Tensor, sigma: torch.Tensor, bias: torch.Tensor, cutoff_range=(0.15, 0.85),
+               simple_mode: bool = False):
+    """``HEDTransform.transform`` on uint8 (n, H, W, 3) device patches with the per-image draws ``sigma`` / ``bias`` (n, 3) float32.
+    Returns (uint8 patches, int32 (n,) ``applied``: 0 where the patch mean lies outside ``cutoff_range`` and the patch is a copy)."""
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[3] != 3:
+        raise ValueError("hed_jitter: expected uint8 (n, H, W, 3)")
+    img_u8 = img_u8.contiguous()
+    n, H, W, _c = img_u8.shape
+    dev = img_u8.device
+    sigma = torch.as_tensor(sigma, dtype=torch.float32).to(dev).contiguous()
+    bias = torch.as_tensor(bias, dtype=torch.float32).to(dev).contiguous()
+    if sigma.shape != (n, 3) or bias.shape != (n, 3):
+        raise ValueError("hed_jitter: sigma and bias are (n, 3)")
+    out = torch.empty_like(img_u8)
+    applied = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().cpx_hed_jitter_u8(ptr(img_u8), n, H, W, ptr(sigma), ptr(bias), float(cutoff_range[0]), float(cutoff_range[1]),
+                                       int(bool(simple_mode)), ptr(out), ptr(applied), _stream(dev)), "hed_jitter_u8")
+    return out, applied
+
+
+def warp_affine(src: torch.Tensor, inv, out_hw, labels: torch.Tensor | None = None, label_fill: int = 0):
+    """Affine warp of uint8 (n, sh, sw, 3) or float32 (n, 3, sh, sw) device images by the per-image INVERSE maps ``inv`` (n, 6)
+    float64 (source = inv . (x, y, 1)) into float32 (n, 3, dh, dw): bilinear with a constant border of 0; int16 ``labels``
+    (n, sh, sw) are sampled at the nearest pixel, ``label_fill`` outside the source.  Returns (image, labels or None)."""
+    dh, dw = (int(v) for v in out_hw)
+    u8 = src.dtype == torch.uint8
+    if src.dim() != 4 or not ((u8 and src.shape[3] == 3) or (src.dtype == torch.float32 and src.shape[1] == 3)):
+        raise ValueError("warp_affine: expected uint8 (n, sh, sw, 3) or float32 (n, 3, sh, sw)")
+    src = src.contiguous()
+    n = src.shape[0]
+    sh, sw = (src.shape[1], src.shape[2]) if u8 else (src.shape[2], src.shape[3])
+    dev = src.device
+    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
+    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
+    if inv.shape != (n, 6):
+        raise ValueError("warp_affine: inv is (n, 6) float64")
+    lab_out = None
+    if labels is not None:
+        if labels.dtype != torch.int16 or labels.shape != (n, sh, sw) or labels.device != dev:
+            raise ValueError("warp_affine: labels must be int16 (n, sh, sw) on the images' device")
+        labels = labels.contiguous()
+        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
+    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
+    fn = _lib.lib().cpx_warp_affine_u8 if u8 else _lib.lib().cpx_warp_affine_f32
+    check(fn(ptr(src), ptr(labels), n, sh, sw, ptr(inv), dh, dw, int(label_fill), ptr(out), ptr(lab_out), _stream(dev)), "warp_affine")
+    return out, lab_out
+
+
+def normalize_stats_f32(x: torch.Tensor) -> torch.Tensor:
+    """(n, 3, 4) float32 {x01, x99 - x01, mode, x99} of float32 (n, 3, H, W) planes: np.percentile(plane, [1, 99]) exactly."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+        raise ValueError("normalize_stats_f32: expected contiguous float32 (n, 3, H, W)")
+    n, _c, H, W = x.shape
+    stats = torch.empty((n, 3, 4), dtype=torch.float32, device=x.device)
+    lo, hi = percentile_params(H * W, 1), percentile_params(H * W, 99)
+    check(_lib.lib().cpx_normalize_stats_f32(ptr(x), n, H, W, lo[0], lo[1], hi[0], hi[1], ptr(stats), _stream(x.device)),
+          "normalize_stats_f32")
+    return stats
+
+
+def normalize_img_f32(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """cellpose transforms.normalize_img on float32 NCHW (n, 3, H, W) crops, per crop and channel -> float32 (n, 3, H, W)."""
+    x = x.contiguous()
+    stats = normalize_stats_f32(x)
+    out = torch.empty_like(x) if out is None else out
+    check(_lib.lib().cpx_normalize_apply_f32(ptr(x), ptr(stats), x.shape[0], x.shape[2], x.shape[3], ptr(out), _stream(x.device)),
+          "normalize_apply_f32")
+    return out

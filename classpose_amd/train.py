@@ -11,7 +11,10 @@ Deliberately different from the reference:
   * the backbone runs as in inference.  The reference calls ``net.train()`` every epoch (train.py:609), which re-enables the
     stochastic layer drop of ``ClassTransformer.forward`` (vit_sam.py:165-173) even in a frozen backbone;
   * an image without a single annotated pixel raises ``ValueError`` (the reference's Tversky loss is NaN for such a batch);
-  * no augmentation stack, HDF5 datasets, oversampling, learned loss weighting, multi-GPU exchange or optimiser-state resume.
+  * augmentation is the device chain of ``classpose_amd.augment`` (stain jitter, flip / rotation / scale / crop, normalisation
+    after both), which samples at exact source coordinates where OpenCV quantises them; the ``enhanced`` pipeline and the
+    rescale by cell diameter are not built;
+  * no HDF5 datasets, oversampling, learned loss weighting, multi-GPU exchange or optimiser-state resume.
 
 A trainer owns its ``engine.NetWeights`` and updates the head operands in place: sharing them with an ``Engine`` that is running on
 another stream is the caller's risk.
@@ -25,7 +28,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import _lib, engine, ops
+from . import _lib, augment as _augment, engine, ops
 from ._lib import check, ptr
 from .log import get_logger
 
@@ -133,6 +136,10 @@ class HeadTrainer:
         dev = self.device
         if isinstance(X, np.ndarray):
             X = torch.from_numpy(np.ascontiguousarray(X))
+        if X.dim() == 2 and X.shape[1] == 192 and X.dtype == self.dtype and X.is_cuda:      # patch rows (augment.augment_batch)
+            if X.shape[0] % TOKENS:
+                raise ValueError("patch rows: 1024 per crop")
+            return X.contiguous()
         if X.dtype == torch.uint8:
             if X.dim() != 4 or X.shape[1:] != (CROP, CROP, 3):
                 raise ValueError(f"uint8 crops must be (n, {CROP}, {CROP}, 3), got {tuple(X.shape)}")
@@ -257,12 +264,17 @@ def _check_dataset(images, labels, what: str):
 
 def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, test_labels=None, batch_size: int = 8,
                      n_epochs: int = 100, learning_rate: float = 5e-5, nimg_per_epoch: int | None = None, cache_features: bool = True,
-                     save_path=None, model_name: str | None = None, random_seed: int = 42, transform=None):
+                     save_path=None, model_name: str | None = None, random_seed: int = 42, transform=None,
+                     augment: str | None = None, scale_range: float = 0.5, label_fill: int = 0):
     """The epoch loop of train.py:606-655 for the frozen-backbone mode: per-epoch learning rate from ``lr_schedule``, seeded sampling
     without replacement (with, when ``nimg_per_epoch`` exceeds the set), sample-weighted running means of CE / Tversky / total,
     validation once per epoch, ``checkpoint_last.pt`` and ``checkpoint_best.pt`` (lowest validation loss; training loss without a
     validation set) next to the final model.  ``cache_features`` runs the backbone once per image; ``transform(X, labels, rng) ->
     (X, labels)``, a host callback per batch for callers who augment, forces the uncached path.
+    ``augment`` ("hed_only": stain jitter + geometry, "geometry": flip / rotation / scale / crop alone) augments every training
+    batch on the device with ``augment.augment_batch`` (``scale_range``, ``label_fill`` as there), drawing from the epoch's
+    generator after the sampling order and after ``transform``, which still runs first.  The training path is then uncached;
+    validation is never augmented and its features are still cached when ``cache_features`` is set.
     Returns ``(path of the final model, train_losses, test_losses)``."""
     images, labels = _check_dataset(images, labels, "training")
     has_test = test_images is not None
@@ -275,13 +287,17 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     model_dir = (Path.cwd() if save_path is None else Path(save_path)) / model_name
     model_dir.mkdir(parents=True, exist_ok=True)
     filename = model_dir / model_name
-    cached = cache_features and transform is None
+    if augment is not None and augment != "geometry":
+        _augment.get_config(augment)                       # unknown names and "enhanced" raise before anything is computed
+    cached = cache_features and transform is None and augment is None
+    test_cached = cached or (cache_features and augment is not None)
     dev = trainer.device
     lab_dev = test_lab_dev = feats = test_feats = None
     if cached:
         train_logger.info(">>> caching neck features of %d training crops", nimg)
         feats = trainer.features(images).view(nimg, TOKENS, 256)
         lab_dev = _labels_i16(labels, dev)
+    if test_cached:
         if has_test:
             test_feats = trainer.features(test_images).view(len(test_images), TOKENS, 256)
             test_lab_dev = _labels_i16(test_labels, dev)
@@ -302,6 +318,9 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
                 x, y = images[idx], labels[idx]
                 if transform is not None:
                     x, y = transform(x, y, rng)
+                if augment is not None:
+                    x, y = _augment.augment_batch(x, y, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
+                                                  dtype=trainer.dtype, device=dev, out=CROP)
             r = trainer.step(x, y, float(LR[iepoch]))
             sums += np.array([r["ce"], r["tversky"], r["loss"]]) * len(idx)
             count += len(idx)
@@ -310,7 +329,7 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
         if has_test:
             tsum, tcount = 0.0, 0
             for s in range(0, len(test_images), batch_size):
-                if cached:
+                if test_cached:
                     x, y = test_feats[s:s + batch_size].reshape(-1, 256), test_lab_dev[s:s + batch_size]
                 else:
                     x, y = test_images[s:s + batch_size], test_labels[s:s + batch_size]

@@ -511,6 +511,45 @@ int cpx_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_a
                    double bias_correction2, void *stream);
 
 /* ------------------------------------------------------------------------
+ * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)
+ * replaces augment_single_image, /root/reference/src/classpose/dataset.py:23-56: the stain jitter, cellpose's
+ * random_rotate_and_resize and the normalize_img that follows them.  Every entry runs on `stream` and allocates nothing.
+ * ---------------------------------------------------------------------- */
+/* cpx_hed_jitter_u8: HEDTransform.transform on uint8 patches (transforms/hed.py:237-298 with separate_stains /
+ *   combine_stains, :48-110).  img, out [n][H][W][3] uint8 (distinct buffers), sigma / bias [n][3] float32 (the draws of
+ *   sample_sigma / sample_bias), applied [n] int32.  Image i is transformed when cutoff_lo <= (sum of its bytes / count) / 255.0
+ *   <= cutoff_hi in double (the sum is an exact integer, as np.mean of uint8 is in float64), else copied unchanged.
+ *   Complex mode (simple_mode 0; shift = 1 for uint8): float32(p / 255.0) + 1, -log, times float32 HED_FROM_RGB, * (1 + sigma) +
+ *   bias per stain, times -RGB_FROM_HED, exp, - 1, clip to [-1, 1], the affine round trip of rescale_intensity(in_range=(-1, 1)),
+ *   clip to [0, 1], (x * 255) truncated.  simple_mode 1: the input clipped to [1e-6, 1], no shift, the result clipped to [0, 1].
+ *   float32 throughout with full-precision logf / expf.                                                                      */
+int cpx_hed_jitter_u8(const uint8_t *img, int n, int H, int W, const float *sigma, const float *bias, double cutoff_lo,
+                      double cutoff_hi, int simple_mode, uint8_t *out, int32_t *applied, void *stream);
+
+/* cpx_warp_affine_u8 / cpx_warp_affine_f32: the cv2.warpAffine calls of cellpose's random_rotate_and_resize as called at
+ *   dataset.py:42-48 (INTER_LINEAR for the image, INTER_NEAREST for the labels, constant border).  src [n][sh][sw][3] uint8 or
+ *   [n][3][sh][sw] float32; labels [n][sh][sw] int16 or NULL (then labels_out is NULL too); inv [n][6] double, the INVERSE map:
+ *   source (sx, sy) = (inv[0] x + inv[1] y + inv[2], inv[3] x + inv[4] y + inv[5]) of output pixel (x, y), evaluated in double
+ *   left to right without fused operations.  out [n][3][dh][dw] float32 (what cpx_patchify_f32 reads), labels_out [n][dh][dw].
+ *   Image: x0 = floor(sx), weight float(sx - x0), four taps, a tap outside the source counts as 0 on its own; two horizontal
+ *   lerps and one vertical in float32, each a + (b - a) * w.  Labels: the source pixel (floor(sx + 0.5), floor(sy + 0.5)), or
+ *   label_fill outside the source.  NOT OpenCV's scheme, which quantises source coordinates to 1/32 pixel.               */
+int cpx_warp_affine_u8(const uint8_t *src, const int16_t *labels, int n, int sh, int sw, const double *inv, int dh, int dw,
+                       int label_fill, float *out, int16_t *labels_out, void *stream);
+int cpx_warp_affine_f32(const float *src, const int16_t *labels, int n, int sh, int sw, const double *inv, int dh, int dw,
+                        int label_fill, float *out, int16_t *labels_out, void *stream);
+
+/* cpx_normalize_stats_f32 / cpx_normalize_apply_f32: cellpose normalize_img -> normalize99 (dataset.py:55) on float32 planes
+ *   img [n][3][H][W], the twins of cpx_normalize_stats_u8 / cpx_normalize_apply_u8.  Per plane the order statistics at ranks
+ *   lo_prev, lo_prev + 1, hi_prev, hi_prev + 1 are found EXACTLY (radix select on order-preserving 32-bit keys, one workgroup
+ *   per plane, four histogram passes through LDS, no workspace), then numpy's float32 'linear' quantile arithmetic with the
+ *   host's gammas; stats [n][3][4] = {x01, x99 - x01, mode, x99}, mode 0 = constant plane (left untouched), 1 = (x - x01) /
+ *   (x99 - x01), 2 = range <= 1e-3 (zeros).  NaN is out of contract; -0.0 and 0.0 compare equal.  out may be img.        */
+int cpx_normalize_stats_f32(const float *img, int n, int H, int W, int lo_prev, float lo_gamma, int hi_prev, float hi_gamma,
+                            float *stats, void *stream);
+int cpx_normalize_apply_f32(const float *img, const float *stats, int n, int H, int W, float *out, void *stream);
+
+/* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
  * replaces, per instance, cv2.findContours(cell_mask, RETR_EXTERNAL,
  * CHAIN_APPROX_SIMPLE)[0] + shapely.Polygon(...).is_valid/.centroid/.area/.length
