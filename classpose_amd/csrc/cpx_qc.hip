@@ -236,6 +236,13 @@ extern "C" int cpx_qc_forward(const cpx_qc_op *ops, int n_ops, const uint8_t *pa
     const long long npix = (long long)nB * H * W;
     CPX_REQUIRE(input_off + (size_t)npix * 16 <= workspace_bytes);
     CPX_REQUIRE(logits_off + (size_t)npix * ld_logits * 4 <= workspace_bytes);
+    CPX_REQUIRE(input_off % 16 == 0 && logits_off % 4 == 0);
+    // a tensor the kernels read or write: channel slice [0, c) of `rows` rows of ld floats at byte offset off;
+    // float4 accesses need 16-byte offsets, the last row ends at its last channel (a slice may end the buffer)
+    auto fits = [&](size_t off, long long rows, int ld, int c) -> bool {
+        return off % 16 == 0 && rows > 0 && c > 0 && ld >= c && off <= workspace_bytes &&
+               ((size_t)(rows - 1) * ld + c) * 4 <= workspace_bytes - off;
+    };
     hipLaunchKernelGGL(k_qc_pre, dim3(cpx_cdiv(npix, 256)), dim3(256), 0, s, patches_u8, npix, at(input_off));
     CPX_CHECK_LAUNCH();
     for (int i = 0; i < n_ops; ++i) {
@@ -245,7 +252,12 @@ extern "C" int cpx_qc_forward(const cpx_qc_op *ops, int n_ops, const uint8_t *pa
         if (o.kind == 0) {
             CPX_REQUIRE(o.c_a % 4 == 0 && o.c_b % 4 == 0 && o.ld_a % 4 == 0 && o.ld_b % 4 == 0 && o.c_out > 0);
             CPX_REQUIRE(!o.up_a || (o.h_in % 2 == 0 && o.w_in % 2 == 0));
-            CPX_REQUIRE(o.dst + (size_t)P * o.ld_dst * 4 <= workspace_bytes);
+            CPX_REQUIRE(o.k > 0 && o.stride > 0 && o.h_in > 0 && o.w_in > 0 && o.h_out > 0 && o.w_out > 0);
+            CPX_REQUIRE(fits(o.dst, P, o.ld_dst, o.c_out));
+            CPX_REQUIRE(fits(o.src_a, (long long)nB * (o.h_in >> (o.up_a ? 1 : 0)) * (o.w_in >> (o.up_a ? 1 : 0)), o.ld_a, o.c_a));
+            CPX_REQUIRE(o.src_b == QC_NONE || fits(o.src_b, (long long)nB * o.h_in * o.w_in, o.ld_b, o.c_b));
+            CPX_REQUIRE(o.gate == QC_NONE || fits(o.gate, nB, o.c_a, o.c_a));
+            CPX_REQUIRE(o.res == QC_NONE || fits(o.res, P, o.ld_res, o.c_out));
             QcConvArgs g;
             g.a = at(o.src_a); g.b = at(o.src_b); g.gate = at(o.gate); g.w = o.w; g.bias = o.bias; g.res = at(o.res);
             g.d = at(o.dst);
@@ -259,15 +271,21 @@ extern "C" int cpx_qc_forward(const cpx_qc_op *ops, int n_ops, const uint8_t *pa
             else hipLaunchKernelGGL(k_qc_conv<64>, grid, dim3(256), 0, s, g);
         } else if (o.kind == 1) {
             CPX_REQUIRE(o.c_a % 4 == 0 && o.ld_a % 4 == 0 && o.bias);
-            CPX_REQUIRE(o.dst + (size_t)P * o.c_a * 4 <= workspace_bytes);
+            CPX_REQUIRE(o.ld_dst == o.c_a);                                    /* the kernel writes dense rows of c_a floats */
+            CPX_REQUIRE(o.k > 0 && o.stride > 0 && o.h_in > 0 && o.w_in > 0 && o.h_out > 0 && o.w_out > 0);
+            CPX_REQUIRE(fits(o.dst, P, o.c_a, o.c_a));
+            CPX_REQUIRE(fits(o.src_a, (long long)nB * o.h_in * o.w_in, o.ld_a, o.c_a));
             hipLaunchKernelGGL(k_qc_dw, dim3(cpx_cdiv(P * (o.c_a / 4), 256)), dim3(256), 0, s, at(o.src_a), o.ld_a,
                                o.w, o.bias, at(o.dst), o.c_a, nB, o.h_in, o.w_in, o.h_out, o.w_out, o.k, o.stride,
                                o.pad, o.act);
         } else if (o.kind == 2) {
             CPX_REQUIRE(o.res != QC_NONE && o.w2 && o.bias && o.bias2 && o.c_red > 0);
+            CPX_REQUIRE(o.ld_dst == o.c_a);                                    /* one gate row of c_a floats per image */
+            CPX_REQUIRE(o.c_a % 4 == 0 && o.h_in > 0 && o.w_in > 0);           /* the projection loads the gate as float4 */
             const int HW = o.h_in * o.w_in;
+            CPX_REQUIRE(fits(o.src_a, (long long)nB * HW, o.ld_a, o.c_a) && fits(o.dst, nB, o.c_a, o.c_a));
             const int slices = HW >= 16384 ? 16 : (HW >= 1024 ? 4 : 1);        /* scratch: 16 * nB * C floats */
-            CPX_REQUIRE(o.res + (size_t)16 * nB * o.c_a * 4 <= workspace_bytes);
+            CPX_REQUIRE(fits(o.res, (long long)16 * nB, o.c_a, o.c_a));
             hipLaunchKernelGGL(k_qc_pool, dim3(cpx_cdiv(o.c_a, 64), nB, slices), dim3(256), 0, s, at(o.src_a), o.ld_a,
                                o.c_a, HW, at(o.res));
             CPX_CHECK_LAUNCH();

@@ -34,6 +34,33 @@ class _Tensor:
         return (self.base + self.off) * 4
 
 
+def pack_dense_weights(w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, ca: int, cb: int, what: str = ""):
+    """float64 [Cout][Ca+Cb][k][k] with the folded per-cout scale / shift -> ([CoutPad][k*k][pad16(Ca)+pad16(Cb)],
+    bias [CoutPad]), CoutPad = Cout rounded up to the kernel's 32- or 64-wide tile; the stem's 3 inputs sit in Ca = 4."""
+    cout, cin, k, _ = w.shape
+    assert cin == ca + cb or (cin == 3 and ca == 4 and cb == 0), (what, cin, ca, cb)
+    w = w * scale[:, None, None, None]
+    tn = 32 if cout <= 32 else 64
+    cpad = (cout + tn - 1) // tn * tn
+    kc = _pad16(ca) + (_pad16(cb) if cb else 0)
+    out = torch.zeros((cpad, k * k, kc), dtype=torch.float64)
+    wt = w.permute(0, 2, 3, 1).reshape(cout, k * k, cin)
+    na = min(ca, cin)
+    out[:cout, :, :na] = wt[:, :, :na]
+    if cb:
+        out[:cout, :, _pad16(ca):_pad16(ca) + cb] = wt[:, :, ca:]
+    b = torch.zeros(cpad, dtype=torch.float64)
+    b[:cout] = shift
+    return out, b
+
+
+def pack_dw_weights(w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor):
+    """float64 depthwise [C][1][k][k] with the folded scale / shift -> ([k*k][C], bias [C])."""
+    c, _, k, _ = w.shape
+    wt = (w[:, 0] * scale[:, None, None]).permute(1, 2, 0).reshape(k * k, c)
+    return wt, shift
+
+
 class QcNet:
     """``smp.UnetPlusPlus("timm-efficientnet-b0", classes=n)`` flattened for ``cpx_qc_forward``."""
 
@@ -69,29 +96,22 @@ class QcNet:
     def _dense_weights(self, wkey: str, bn: str | None, ca: int, cb: int, bias_key: str | None = None):
         """[Cout][Ca+Cb][k][k] -> device [CoutPad][k*k][pad16(Ca)+pad16(Cb)] (BN folded), bias [CoutPad]."""
         w = self._sd[wkey]
-        cout, cin, k, _ = w.shape
-        assert cin == ca + cb or (cin == 3 and ca == 4 and cb == 0), (wkey, cin, ca, cb)
-        scale, shift = self._bn_fold(bn, cout, self._sd[bias_key] if bias_key else None)
-        w = w * scale[:, None, None, None]
-        tn = 32 if cout <= 32 else 64
-        cpad = (cout + tn - 1) // tn * tn
-        kc = _pad16(ca) + (_pad16(cb) if cb else 0)
-        out = torch.zeros((cpad, k * k, kc), dtype=torch.float64)
-        wt = w.permute(0, 2, 3, 1).reshape(cout, k * k, cin)
-        na = min(ca, cin)
-        out[:cout, :, :na] = wt[:, :, :na]
-        if cb:
-            out[:cout, :, _pad16(ca):_pad16(ca) + cb] = wt[:, :, ca:]
-        b = torch.zeros(cpad, dtype=torch.float64)
-        b[:cout] = shift
+        scale, shift = self._bn_fold(bn, w.shape[0], self._sd[bias_key] if bias_key else None)
+        out, b = pack_dense_weights(w, scale, shift, ca, cb, wkey)
         return self._dev(out), self._dev(b)
 
     def _dw_weights(self, wkey: str, bn: str):
         w = self._sd[wkey]                                   # [C][1][k][k]
-        c, _, k, _ = w.shape
-        scale, shift = self._bn_fold(bn, c)
-        wt = (w[:, 0] * scale[:, None, None]).permute(1, 2, 0).reshape(k * k, c)
-        return self._dev(wt), self._dev(shift)
+        scale, shift = self._bn_fold(bn, w.shape[0])
+        wt, b = pack_dw_weights(w, scale, shift)
+        return self._dev(wt), self._dev(b)
+
+    def weight_tensor(self, data_ptr: int) -> torch.Tensor:
+        """The kept float32 tensor behind a raw pointer of an op (``w``, ``bias``, ``w2``, ``bias2``)."""
+        for t in self._keep:
+            if t.data_ptr() == data_ptr:
+                return t
+        raise KeyError(f"no kept weight tensor at {data_ptr:#x}")
 
     # ---- plan: buffers + op list for (nB, H, W) --------------------------------------------
     def plan(self, nB: int, H: int, W: int):
@@ -140,12 +160,14 @@ class QcNet:
         logits = _Tensor(alloc(1, ld_logits), ld_logits, 0, self.n_classes, 1)
 
         ops: list[CpxQcOp] = []
+        names: list[str] = []                                # state-dict key behind each op, for diagnostics
 
         def conv(a: _Tensor, b: _Tensor | None, dst: _Tensor, wkey, bn, k, stride, act, up=0, gate_off=None,
                  res: _Tensor | None = None, bias_key=None):
             h_in = H // a.stride * (2 if up else 1)
             w_in = W // a.stride * (2 if up else 1)
             wp, bp = self._dense_weights(wkey, bn, a.c, b.c if b else 0, bias_key)
+            names.append(wkey)
             o = CpxQcOp(kind=0, k=k, stride=stride, pad=k // 2, act=act, h_in=h_in, w_in=w_in,
                         h_out=h_in // stride, w_out=w_in // stride,
                         src_a=a.byte_off(), src_b=b.byte_off() if b else NONE,
@@ -158,6 +180,7 @@ class QcNet:
 
         def dwconv(a: _Tensor, dst: _Tensor, wkey, bn, k, stride):
             wp, bp = self._dw_weights(wkey, bn)
+            names.append(wkey)
             h_in, w_in = H // a.stride, W // a.stride
             ops.append(CpxQcOp(kind=1, k=k, stride=stride, pad=k // 2, act=2, h_in=h_in, w_in=w_in,
                                h_out=h_in // stride, w_out=w_in // stride, src_a=a.byte_off(), src_b=NONE, gate=NONE,
@@ -166,6 +189,7 @@ class QcNet:
 
         def se(a: _Tensor, p: str, cr: int):
             sd = self._sd
+            names.append(p + "conv_reduce.weight")
             ops.append(CpxQcOp(kind=2, k=1, stride=1, pad=0, act=0, h_in=H // a.stride, w_in=W // a.stride,
                                h_out=1, w_out=1, src_a=a.byte_off(), src_b=NONE, gate=NONE, res=pool * 4,
                                dst=gate * 4, c_a=a.c, ld_a=a.ld, up_a=0, c_b=0, ld_b=0, ld_res=0, c_out=a.c,
@@ -223,7 +247,7 @@ class QcNet:
         conv(t["x_0_4"], None, logits, "segmentation_head.0.weight", None, 3, 1, 0,
              bias_key="segmentation_head.0.bias")
         arr = (CpxQcOp * len(ops))(*ops)
-        plan = dict(ops=arr, n_ops=len(ops), ws_bytes=cursor[0] * 4, input_off=inp.byte_off(),
+        plan = dict(ops=arr, n_ops=len(ops), names=names, ws_bytes=cursor[0] * 4, input_off=inp.byte_off(),
                     logits_off=logits.byte_off(), ld_logits=ld_logits,
                     ws=torch.empty(cursor[0] * 4, dtype=torch.uint8, device=self.device))
         self._plans = {key: plan}                            # one live plan (workspace) at a time
