@@ -10,13 +10,14 @@
 // axis order against r^2, box pruning is monotone in floating point) -- so it is computed here
 // exactly; the order-dependent grouping stays on the host over this pair list (geojson.py).
 //
-// Uniform grid with cell edge >= r: points are bucketed by a deterministic counting sort
+// Uniform grid with a power-of-two cell edge > r (see cpx_dedup_pairs): points are bucketed by a deterministic counting sort
 // (atomic histogram -> exclusive scan -> scatter -> per-cell insertion sort by point index), then
 // one thread per point scans the 3 x 3 neighbouring cells twice (count, write) with an exclusive
 // scan between the passes, so the output is compact, sorted lexicographically by (i, j) and identical
 // from run to run.  HBM-bound integer / double work: every pass is a coalesced sweep over the point arrays,
 // the cell table (4 B per 8 x 8 px cell) is touched once per pass.
 #include "cpx_common.h"
+#include <cmath>
 
 #define DD_THR 256
 #define SCAN_PER 2048            // elements per scan block (8 per thread)
@@ -186,12 +187,21 @@ extern "C" size_t cpx_dedup_pairs_workspace_bytes(int n_points, int grid_w, int 
 
 // Pass 1 (pairs == NULL): buckets the points and counts the pairs -> *n_pairs (device, int64).
 // Pass 2 (pairs != NULL, same workspace, untouched in between): writes min(n_pairs, max_pairs) pairs (i < j),
-// sorted by i.  centers_xy [n][2] double (x, y); the grid covers [x0, x0 + grid_w * cell) x [y0, ...), cell >= max_dist.
+// sorted by i.  centers_xy [n][2] double (x, y); the grid covers [x0, x0 + grid_w * cell) x [y0, ...).
+// `cell` must be a power of two with cell * (1 - 2^-20) >= max_dist (checked).  A pair is found only if its points are at
+// most one cell apart, and cell >= max_dist alone does not give that: floor((x - x0) * (1 / cell)) with a rounded
+// reciprocal put points 9.3 apart two cells of edge 9.3 apart.  With a power of two the scaling is exact and only
+// fl(x - x0) rounds, by at most 2^-53 |x - x0| < 2^-22 cell per point (grid_w * grid_h < 2^31 cells); a pair that passes
+// d2 <= r2 has |dx| <= max_dist (1 + 2^-51) <= cell (1 - 2^-21), so its scaled coordinates differ by at most 1 and their
+// floors by at most 1.  Points outside the grid fall into its border cells (the clamp is monotone: still at most 1 apart).
 extern "C" int cpx_dedup_pairs(const double *centers_xy, int n, double x0, double y0, double cell, int grid_w, int grid_h,
                                double max_dist, int32_t *pairs, long long max_pairs, long long *n_pairs,
                                void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(centers_xy && n > 0 && grid_w > 0 && grid_h > 0 && n_pairs && workspace);
-    CPX_REQUIRE(cell >= max_dist && max_dist > 0 && (size_t)grid_w * grid_h < ((size_t)1 << 31));
+    CPX_REQUIRE(max_dist > 0 && (size_t)grid_w * grid_h < ((size_t)1 << 31));
+    int cell_exp;
+    CPX_REQUIRE(cell > 0 && std::isfinite(cell) && std::frexp(cell, &cell_exp) == 0.5);       // a power of two
+    CPX_REQUIRE(cell * (1.0 - 0x1p-20) >= max_dist);
     const size_t n_cells = (size_t)grid_w * grid_h;
     const DdWs L = dd_ws(n, n_cells);
     CPX_REQUIRE(workspace_bytes >= L.total);

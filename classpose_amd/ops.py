@@ -308,6 +308,23 @@ def gemm_ln(A, Wt, epilogue="bf16", bias=None, aux=None, ln_stats=None, ln_colsu
 
 
 # ---- f2 ---------------------------------------------------------------------
+def dedup_grid(centers: np.ndarray, max_dist: float) -> tuple[float, float, float, int, int]:
+    """(x0, y0, cell, grid_w, grid_h) of the bucket grid ``cpx_dedup_pairs`` wants for these centres.  The cell edge is a
+    power of two (8 up to max_dist 7.99999, then 16, 32, ...) with cell * (1 - 2^-20) >= max_dist: the kernel's
+    ``(x - x0) * (1 / cell)`` is then exact but for the rounding of the difference, and that margin absorbs it, so two
+    points within max_dist of each other are never more than one cell apart (a cell edge of max_dist itself, with an
+    inexact reciprocal, put some two cells apart and the 3 x 3 scan lost the pair)."""
+    if not (np.isfinite(max_dist) and max_dist > 0):
+        raise ValueError(f"max_dist must be positive and finite, got {max_dist}")
+    cell = 8.0
+    while cell * (1.0 - 2.0 ** -20) < max_dist:
+        cell *= 2.0
+    lo, hi = centers.min(0), centers.max(0)
+    x0, y0 = float(np.floor(lo[0])) - cell, float(np.floor(lo[1])) - cell
+    gw, gh = int((hi[0] - x0) // cell) + 2, int((hi[1] - y0) // cell) + 2
+    return x0, y0, cell, gw, gh
+
+
 def dedup_pairs(centers: np.ndarray, max_dist: float = 15 / 2, device=None) -> np.ndarray:
     """``KDTree(centers).query_pairs(max_dist)`` (predict_wsi.py:923-927) as an int32 (P, 2) array of (i, j),
     i < j, sorted by i: the uniform-grid radius search of ``cpx_dedup_pairs`` on the device.
@@ -317,10 +334,7 @@ def dedup_pairs(centers: np.ndarray, max_dist: float = 15 / 2, device=None) -> n
     if n < 2:
         return np.zeros((0, 2), np.int32)
     dev = torch.device(device if device is not None else "cuda")
-    cell = 8.0 if max_dist <= 8.0 else float(max_dist)
-    lo, hi = centers.min(0), centers.max(0)
-    x0, y0 = float(np.floor(lo[0])) - cell, float(np.floor(lo[1])) - cell
-    gw, gh = int((hi[0] - x0) // cell) + 2, int((hi[1] - y0) // cell) + 2
+    x0, y0, cell, gw, gh = dedup_grid(centers, max_dist)
     L = _lib.lib()
     c = torch.from_numpy(centers).to(dev)
     nbytes = L.cpx_dedup_pairs_workspace_bytes(n, gw, gh)

@@ -591,7 +591,9 @@ int cpx_polygonize_device(const uint16_t *masks_u16, const cpx_record *records, 
  * ---------------------------------------------------------------------- */
 /* centers_xy [n][2] double (x, y) = the rounded centroids of every cell of the slide.  The pair set
  * {(i, j), i < j : (xi-xj)^2 + (yi-yj)^2 <= max_dist^2} (double arithmetic, products and sum unfused: exactly
- * scipy's test) via a uniform grid of `cell` >= max_dist covering [x0, x0 + grid_w*cell) x [y0, y0 + grid_h*cell).
+ * scipy's test) via a uniform grid of edge `cell` covering [x0, x0 + grid_w*cell) x [y0, y0 + grid_h*cell).  `cell` must be
+ * a power of two with cell * (1 - 2^-20) >= max_dist (anything else is refused): the bucketing is then exact enough that
+ * no two points within max_dist of each other land more than one cell apart, whatever max_dist and the coordinates are.
  * Two calls on the same workspace: pairs == NULL buckets + counts (-> *n_pairs, device int64); then with
  * pairs [max_pairs][2] int32 writes them sorted by i (deterministic).  The greedy grouping of :929-960 follows
  * the iteration order of a Python set and stays on the host (classpose_amd.geojson.dedup_from_pairs).   */

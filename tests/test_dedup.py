@@ -179,3 +179,209 @@ def test_device_pairs_equal_kdtree_query_pairs_synthetic(cuda, n_cells, extent):
     full = _reference_loop(len(c), a.tolist(), set(zip(pairs[:, 0].tolist(), pairs[:, 1].tolist())))
     print(f"   (the reference's loop over the whole pair set: {time.perf_counter() - t3:.2f} s)")
     _assert_same_up_to_ambiguous_clusters(len(c), pairs, keep.tolist(), full, 0.002)
+
+
+# ---- the device radius search at other radii and at its edges ---------------------------------------------------------------
+# Reference: scipy KDTree.query_pairs, which on every input below equals the brute-force float64 test
+# dx * dx + dy * dy <= r * r over all pairs (asserted where the reference is built).
+RADII = [0.7, 2.5, 5, 7.5, 8, 8.01, 9.3, 10, 13]
+# Three points on a line whose pair (1, 2) a cell edge of max_dist itself loses: floor((x - x0) * (1 / cell)) with the rounded
+# reciprocal puts points 1 and 2 two cells apart.  The third set is the edge of a power-of-two cell equal to max_dist:
+# fl(15 - (7 - 2^-50)) is exactly 8, the pair counts, and the points sit in cells [-1, 7) and [15, 23) of a grid from -17.
+THREE_POINTS = [(9.3, [-500.0, -81.5, -72.2]), (8.01, [-499.98, 1718.77, 1726.78]), (8.0, [-8.5, 7.0 - 2.0 ** -50, 15.0])]
+
+
+def _dd_thr():
+    import os
+    import re
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "classpose_amd", "csrc", "cpx_dedup.hip")
+    with open(src) as f:
+        return int(re.search(r"^#define\s+DD_THR\s+(\d+)", f.read(), re.M).group(1))
+
+
+def _brute_pairs(c, r):
+    """{(i, j), i < j : dx * dx + dy * dy <= r * r} in float64, sorted by (i, j)"""
+    dx = c[:, None, 0] - c[None, :, 0]
+    dy = c[:, None, 1] - c[None, :, 1]
+    i, j = np.nonzero(np.triu(dx * dx + dy * dy <= np.float64(r) * np.float64(r), 1))
+    return np.stack([i, j], 1).astype(np.int32)
+
+
+def _edge_points(r):
+    """~1000 shuffled points: a 26 x 26 half-integer lattice from a negative origin scaled by r / 2.5 (step r / 5: the (3, 4) and
+    (5, 0) steps are partners at exactly r wherever the step is exact, across cell borders), 40 exact duplicates, and a clump
+    of 300 points of 2 decimals inside a 5 x 5 box (one or two cells: hundreds of partners per point at the larger radii)"""
+    rng = np.random.default_rng(int(r * 100))
+    k = np.arange(26) * 0.5
+    gx, gy = np.meshgrid(k, k)
+    lat = np.stack([gx.ravel(), gy.ravel()], 1) * (r / 2.5) + np.array([-10.5, -3.0])
+    dup = lat[rng.choice(len(lat), 40, replace=False)]
+    clump = np.round(rng.uniform(0, 5, (300, 2)) + np.array([5 * r + 20.25, -1.5]), 2)
+    pts = np.concatenate([lat, dup, clump])
+    return np.ascontiguousarray(pts[rng.permutation(len(pts))])
+
+
+_EDGE_REF = {}
+
+
+def _edge_case(r, n=None, collinear=False):
+    """(points, reference pairs) built once per case and left unchanged"""
+    key = (r, n, collinear)
+    if key not in _EDGE_REF:
+        c = _edge_points(r)
+        if collinear:
+            c[:, 1] = -3.0
+        if n is not None:
+            c = np.ascontiguousarray(c[:n])
+        ref = _scipy_pairs(c, r)
+        assert np.array_equal(ref, _brute_pairs(c, r))
+        c.setflags(write=False)
+        ref.setflags(write=False)
+        _EDGE_REF[key] = (c, ref)
+    return _EDGE_REF[key]
+
+
+def _assert_pairs_equal(got, ref, what):
+    """exact equality of two (P, 2) pair lists sorted by (i, j); a failure counts what is missing / extra and shows the first"""
+    if got.shape == ref.shape and np.array_equal(got, ref):
+        return
+    g, f = set(map(tuple, got.tolist())), set(map(tuple, ref.tolist()))
+    missing, extra = sorted(f - g), sorted(g - f)
+    if not missing and not extra:
+        bad = np.argwhere(got != ref) if got.shape == ref.shape else []
+        raise AssertionError(f"{what}: same pair set in another order or with repeats ({len(got)} vs {len(ref)} rows), "
+                             f"first differing element {bad[0].tolist() if len(bad) else None}")
+    raise AssertionError(f"{what}: {len(got)} pairs, reference {len(ref)}; {len(missing)} missing (first {missing[:1]}), "
+                         f"{len(extra)} extra (first {extra[:1]})")
+
+
+def test_edge_point_sets_hold_what_they_are_for():
+    """host check of the inputs: partners at exactly r, zero-distance pairs, negative coordinates, crowded points"""
+    for r in (2.5, 5, 7.5, 10):                                    # r / 5 and every lattice coordinate exact
+        c, ref = _edge_case(r)
+        d = c[ref[:, 0]] - c[ref[:, 1]]
+        d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+        assert (d2 == r * r).sum() >= 600 and (d2 == 0).sum() >= 40
+        assert (c < 0).any() and np.bincount(ref[:, 0]).max() >= (200 if r >= 7.5 else 5)
+    for r in RADII:
+        c, ref = _edge_case(r)
+        assert len(c) == 26 * 26 + 340 and len(ref) > 2000
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", RADII)
+def test_device_pairs_equal_query_pairs_at_every_radius(cuda, r):
+    from classpose_amd import ops
+    c, ref = _edge_case(r)
+    _assert_pairs_equal(ops.dedup_pairs(c.copy(), r, cuda), ref, f"r = {r}, {len(c)} points")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", [2.5, 7.5, 9.3])
+def test_device_pairs_equal_query_pairs_collinear(cuda, r):
+    """all y equal: a grid two cells high, every lattice column collapsed into 26 exact duplicates"""
+    from classpose_amd import ops
+    c, ref = _edge_case(r, collinear=True)
+    _assert_pairs_equal(ops.dedup_pairs(c.copy(), r, cuda), ref, f"collinear, r = {r}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", [7.5, 13])
+@pytest.mark.parametrize("dn", [None, -1, 0, 1])
+def test_device_pairs_equal_query_pairs_around_a_block_of_points(cuda, dn, r):
+    """n = 2 and n = DD_THR - 1, DD_THR, DD_THR + 1: the last block of one thread per point empty but for one, full, absent"""
+    from classpose_amd import ops
+    n = 2 if dn is None else _dd_thr() + dn
+    c, ref = _edge_case(r, n=n)
+    _assert_pairs_equal(ops.dedup_pairs(c.copy(), r, cuda), ref, f"n = {n}, r = {r}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r,xs", THREE_POINTS)
+def test_device_pairs_do_not_lose_a_pair_two_cells_apart(cuda, r, xs):
+    from classpose_amd import ops
+    c = np.stack([np.array(xs), np.zeros(3)], 1)
+    ref = _scipy_pairs(c, r)
+    assert ref.tolist() == [[1, 2]] and np.array_equal(ref, _brute_pairs(c, r))
+    _assert_pairs_equal(ops.dedup_pairs(c.copy(), r, cuda), ref, f"r = {r}, x = {xs}")
+
+
+def test_dedup_grid_cell_edge():
+    """host: the cell edge is a power of two with room above max_dist; 8 for the production radius, as before"""
+    from classpose_amd import ops
+    c = np.array([[-3.5, 2.0], [40.0, 9.0]])
+    assert ops.dedup_grid(c, 7.5) == (-12.0, -6.0, 8.0, 8, 3)
+    for r, cell in [(0.7, 8.0), (7.5, 8.0), (7.99999, 8.0), (8.0, 16.0), (8.01, 16.0), (9.3, 16.0), (13, 16.0), (16, 32.0), (100, 128.0)]:
+        assert ops.dedup_grid(c, r)[2] == cell
+    for r in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            ops.dedup_grid(c, r)
+
+
+def _dedup_two_pass(c, r, max_pairs_of, dev, guard=512):
+    """cpx_dedup_pairs called directly: pass 1, then pass 2 with max_pairs = max_pairs_of(n_pairs) into a buffer of
+    max_pairs + guard rows pre-filled with a sentinel.  Returns (n_pairs, max_pairs, the whole buffer as numpy)."""
+    import torch
+    from classpose_amd import _lib, ops
+    from classpose_amd._lib import ptr
+    x0, y0, cell, gw, gh = ops.dedup_grid(c, r)
+    L = _lib.lib()
+    cd = torch.from_numpy(c.copy()).to(dev)
+    nbytes = L.cpx_dedup_pairs_workspace_bytes(len(c), gw, gh)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tot = torch.zeros(1, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(L.cpx_dedup_pairs(ptr(cd), len(c), x0, y0, cell, gw, gh, float(r), None, 0, ptr(tot), ptr(ws), nbytes, st), "count")
+    P = int(tot.item())
+    mp = max_pairs_of(P)
+    buf = torch.full((mp + guard, 2), -777, dtype=torch.int32, device=dev)
+    _lib.check(L.cpx_dedup_pairs(ptr(cd), len(c), x0, y0, cell, gw, gh, float(r), ptr(buf), mp, ptr(tot), ptr(ws), nbytes, st), "write")
+    return P, mp, buf.cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", [7.5, 13])
+def test_device_pairs_pass_two_stops_at_max_pairs(cuda, r):
+    """pass 2 with room for about half of the pairs: nothing behind max_pairs is written, every written pair is one of the
+    reference's, and every point whose whole slice lies before the limit has exactly the reference's partners"""
+    c, ref = _edge_case(r)
+    P, mp, buf = _dedup_two_pass(c, r, lambda P: P // 2 + 3, cuda)
+    assert P == len(ref) and 0 < mp < P
+    bad = np.argwhere(buf[mp:] != -777)
+    assert len(bad) == 0, f"{len(bad)} elements written behind max_pairs = {mp}, first at row {mp + bad[0][0]}"
+    cnt = np.bincount(ref[:, 0], minlength=len(c))
+    off = np.cumsum(cnt) - cnt                                      # the reference list is sorted by i: slices are the kernel's
+    whole = off + cnt <= mp
+    last = int(np.nonzero(whole & (cnt > 0))[0].max())
+    n_whole = int(off[last] + cnt[last])
+    assert n_whole > mp - 400
+    _assert_pairs_equal(buf[:n_whole], ref[:n_whole], f"r = {r}: slices that end before max_pairs = {mp}")
+    ref_set = set(map(tuple, ref.tolist()))
+    rest = buf[n_whole:mp]
+    assert len(rest) and (rest[:, 0] == rest[0, 0]).all()          # one point straddles the limit
+    stray = [p for p in map(tuple, rest.tolist()) if p not in ref_set]
+    assert not stray, f"{len(stray)} written pairs are not in the reference, first {stray[0]}"
+    assert len(set(map(tuple, rest.tolist()))) == len(rest)
+
+
+@pytest.mark.gpu
+def test_device_pairs_cut_slice_holds_the_smallest_partners_of_a_one_cell_clump(cuda):
+    """301 points: an anchor at (0.5, 0.5), which puts the cell borders on multiples of 8, and 300 inside the cell
+    [96, 104)^2, most of them partners of each other at r = 7.5.  A cell's slice is sorted by point index (k_dd_cell_sort),
+    so where max_pairs cuts a point's partners the ones written are its SMALLEST partners; without the sort they would be
+    whichever the bucketing's atomics placed first."""
+    rng = np.random.default_rng(5)
+    c = np.concatenate([[[0.5, 0.5]], np.round(rng.uniform(96.5, 103.5, (300, 2)), 2)])
+    c = np.ascontiguousarray(c[rng.permutation(len(c))])
+    from classpose_amd import ops
+    assert ops.dedup_grid(c, 7.5)[:3] == (-8.0, -8.0, 8.0)
+    ref = _scipy_pairs(c, 7.5)
+    assert np.array_equal(ref, _brute_pairs(c, 7.5))
+    cnt = np.bincount(ref[:, 0], minlength=len(c))
+    off = np.cumsum(cnt) - cnt
+    i = int(np.nonzero(cnt >= 100)[0][40])                          # a point with many partners, some way into the list
+    mp = int(off[i] + cnt[i] // 2)
+    P, _, buf = _dedup_two_pass(c, 7.5, lambda P: mp, cuda)
+    assert P == len(ref)
+    assert (buf[mp:] == -777).all()
+    _assert_pairs_equal(buf[:mp], ref[:mp], f"first {mp} pairs: point {i} keeps {cnt[i] // 2} of its {cnt[i]} partners")

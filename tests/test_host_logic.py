@@ -61,6 +61,50 @@ def test_make_tiling_matches_oracle(H, W, aug):
     assert list(t.ystart[: t.ny]) == ys and list(t.xstart[: t.nx]) == xs
 
 
+def _edge_shapes(b):
+    return [(b, b), (b - 1, b + 1), (5, 3 * b + 7), (2 * b + 9, b // 2), (1, 1), (7 * b // 2, 16)]
+
+
+@pytest.mark.parametrize("aug", [False, True])
+@pytest.mark.parametrize("bsize,H,W", [(b, H, W) for b in (32, 64, 224) for H, W in _edge_shapes(b)]
+                         + [(256, 208, 208), (32, 240, 16), (32, 400, 16)])
+def test_make_tiling_matches_oracle_at_other_sub_tile_sizes(bsize, H, W, aug):
+    """sub-tile sizes other than 256, tiles smaller than the sub-tile, and the 16-row grids (240 rows augmented, 400 plain)"""
+    if (bsize, H, aug) == (32, 400, True):                         # 26 rows augmented: only the plain grid fits
+        with pytest.raises(ValueError):
+            engine.make_tiling(H, W, bsize, aug)
+        return
+    t = engine.make_tiling(H, W, bsize, aug)
+    x = np.zeros((1, H, W, 3), np.float32)
+    sub, geom = tiling.subtile_batch(x, bsize, aug)
+    assert sub.shape[1:] == (3, bsize, bsize)
+    assert (t.ny, t.nx) == (geom["ny"], geom["nx"])
+    assert (t.Ly, t.Lx) == (geom["Ly"], geom["Lx"])
+    assert (t.ypad1, t.xpad1) == (geom["pads"][0], geom["pads"][2])
+    assert (t.H, t.W, t.bsize, t.augment) == (H, W, bsize, int(aug))
+    ys = sorted({a for a, _ in geom["ysub"]})
+    xs = sorted({a for a, _ in geom["xsub"]})
+    assert list(t.ystart[: t.ny]) == ys and list(t.xstart[: t.nx]) == xs
+    if (H, W) == (240, 16) and aug:
+        assert (t.ny, t.nx) == (16, 3)
+    if (H, W) == (400, 16) and not aug:
+        assert t.ny == 16
+
+
+@pytest.mark.parametrize("H,aug", [(241, True), (401, False)])
+def test_make_tiling_refuses_a_17_row_grid(H, aug):
+    assert engine.make_tiling(H - 1, 16, 32, aug).ny == 16
+    with pytest.raises(ValueError, match="at most 16x16"):
+        engine.make_tiling(H, 16, 32, aug)
+
+
+@pytest.mark.parametrize("bsize", [32, 64, 224])
+def test_taper_matches_oracle_at_other_sub_tile_sizes(bsize):
+    assert engine.taper_1d(bsize).shape == (bsize,)
+    assert np.array_equal(engine.taper_1d(bsize), tiling.taper_mask_1d(bsize))
+    assert np.array_equal(np.outer(engine.taper_1d(bsize), engine.taper_1d(bsize)), tiling.taper_mask(bsize, bsize))
+
+
 def test_sub_tile_counts_of_the_baseline_configs():
     assert engine.make_tiling(256, 256).ny * engine.make_tiling(256, 256).nx == 4
     assert engine.make_tiling(256, 256, augment=True).ny ** 2 == 9
