@@ -156,6 +156,8 @@ SIGNATURES = {
     "cpx_warp_affine_f32": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "cpx_normalize_stats_f32": (_i, [_p, _i, _i, _i, _i, _f, _i, _f, _p, _p]),
     "cpx_normalize_apply_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "cpx_label_stats_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "cpx_label_stats": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),

@@ -9,7 +9,8 @@ Random draws come from the numpy ``Generator`` passed in, in the order documente
 global ``np.random`` state, so its sample stream is not reproduced; its distributions are.
 
 Still different from the reference: the warp samples at exact double-precision source coordinates (OpenCV quantises them to
-1 / 32 pixel), the ``enhanced`` pipeline is not built, and there is no rescale-by-diameter (it needs instance masks).
+1 / 32 pixel) and the ``enhanced`` pipeline is not built.  The rescale by cell diameter (dataset.py:35-45) is the ``rescale``
+argument of the samplers: per crop ``diameter / diam_mean``, the diameters from ``dataset_stats.label_stats``.
 """
 from __future__ import annotations
 
@@ -87,29 +88,45 @@ def affine_forward(theta, scale, dxy, sh: int, sw: int, out: int = 256) -> np.nd
     return fwd
 
 
+def _check_rescale(rescale, n: int) -> np.ndarray | None:
+    if rescale is None:
+        return None
+    rescale = np.asarray(rescale, np.float64)
+    if rescale.shape != (n,) or not np.all(rescale > 0):
+        raise ValueError(f"rescale: {n} positive factors (diameter / diam_mean per crop) expected")
+    return rescale
+
+
 def sample_affine_params(rng: np.random.Generator, n: int, sh: int, sw: int, out: int = 256, scale_range: float = 0.5,
-                         do_flip: bool = True, rotate: bool = True) -> dict:
+                         do_flip: bool = True, rotate: bool = True, rescale=None) -> dict:
     """The random parameters behind ``sample_affine``: ``flip`` (n,) bool, ``theta``, ``scale`` (n,), ``dxy`` (n, 2).
     Draw order, always all four so that the stream does not depend on the switches: ``rng.random(n)`` for the flips, ``rng.random(n)``
-    for theta, ``rng.random(n)`` for the scale, ``rng.random((n, 2))`` for the shift (x, y)."""
+    for theta, ``rng.random(n)`` for the scale, ``rng.random((n, 2))`` for the shift (x, y).  ``rescale`` (n,) float64, the per-crop
+    ``diameter / diam_mean`` (dataset.py:35-38), divides the scale; the crop room behind ``dxy`` follows from the divided scale.
+    It changes neither the number nor the order of the draws, and ``rescale=None`` is bitwise the sampler without it."""
     r = float(np.clip(scale_range, 0.0, 2.0))
+    rescale = _check_rescale(rescale, n)
     u_flip, u_theta, u_scale, u_dxy = rng.random(n), rng.random(n), rng.random(n), rng.random((n, 2))
     flip = (u_flip > 0.5) & bool(do_flip)
     theta = 2 * np.pi * u_theta if rotate else np.zeros(n)
     scale = (1 - r / 2) + r * u_scale
+    if rescale is not None:
+        scale = scale / rescale
     room = np.maximum(0.0, np.stack([sw * scale - out, sh * scale - out], 1))
     return dict(flip=flip, theta=theta, scale=scale, dxy=(u_dxy - 0.5) * room)
 
 
 def sample_affine(rng: np.random.Generator, n: int, sh: int, sw: int, out: int = 256, scale_range: float = 0.5,
-                  do_flip: bool = True, rotate: bool = True):
+                  do_flip: bool = True, rotate: bool = True, rescale=None):
     """(flips (n,) bool, inverse maps (n, 6) float64) of ``n`` random flip / rotation / scale / crop transforms from a
     ``sh`` x ``sw`` source into ``out`` x ``out``, in the parametrisation of cellpose's ``random_rotate_and_resize``.
 
     Restated from cellpose 4.0.x, whose wheel is not available to pin against (unpinned): ``flip = u > 0.5``, ``theta = 2 pi u``,
     ``scale = (1 - r / 2) + r u`` with ``r = clamp(scale_range, 0, 2)``, ``dxy = (u2 - 0.5) * max(0, [sw * scale - out,
-    sh * scale - out])``; see ``affine_inverse`` for the map and ``sample_affine_params`` for the order of the draws."""
-    p = sample_affine_params(rng, n, sh, sw, out, scale_range, do_flip, rotate)
+    sh * scale - out])``; with ``rescale`` the scale is ``((1 - r / 2) + r u) / rescale`` before ``dxy`` is formed from it, also
+    restated from cellpose and unpinned for the same reason.  See ``affine_inverse`` for the map and ``sample_affine_params`` for
+    the order of the draws."""
+    p = sample_affine_params(rng, n, sh, sw, out, scale_range, do_flip, rotate, rescale)
     return p["flip"], affine_inverse(p["flip"], p["theta"], p["scale"], p["dxy"], sh, sw, out)
 
 
@@ -137,13 +154,16 @@ class BatchParams:
 
 
 def sample_batch_params(rng: np.random.Generator, n: int, sh: int, sw: int, config: dict | None, scale_range: float = 0.5,
-                        geometry: bool = True, out: int = 256) -> BatchParams:
-    """Draw order per batch: ``sample_hed`` (when ``config`` is given), then ``sample_affine`` (when ``geometry``)."""
+                        geometry: bool = True, out: int = 256, rescale=None) -> BatchParams:
+    """Draw order per batch: ``sample_hed`` (when ``config`` is given), then ``sample_affine`` (when ``geometry``), which takes
+    ``rescale`` (n,) -- without geometry there is no scale to divide and ``rescale`` is refused."""
+    if rescale is not None and not geometry:
+        raise ValueError("rescale needs the geometric augmentation")
     sigma = bias = None
     if config is not None:
         sigma, bias = sample_hed(rng, n, config["sigma_ranges"], config["bias_ranges"])
     if geometry:
-        flip, inv = sample_affine(rng, n, sh, sw, out, scale_range)
+        flip, inv = sample_affine(rng, n, sh, sw, out, scale_range, rescale=rescale)
     else:
         flip, inv = np.zeros(n, bool), identity_maps(n)
     return BatchParams(sigma, bias, inv, flip)
@@ -179,18 +199,22 @@ def _to_device(X, labels, device):
 
 
 def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed_only", scale_range: float = 0.5,
-                  label_fill: int = 0, geometry: bool = True, dtype: torch.dtype = torch.bfloat16, device=None, out: int = 256):
+                  label_fill: int = 0, geometry: bool = True, dtype: torch.dtype = torch.bfloat16, device=None, out: int = 256,
+                  rescale=None):
     """One augmented training batch on the device: (patch rows (n * (out / 8)^2, 192) in ``dtype``, int16 labels (n, out, out)), what
     ``HeadTrainer.step`` takes.  Stain jitter (``config``: a name of ``AUGMENT_CONFIGS``, or None / "geometry" for none), warp
     (``geometry``), float32 normalisation, ``ops.patchify_f32``.  ``label_fill`` is the class of out-of-frame pixels: 0 as in the
     reference, where out-of-frame is background, or -100 to leave them out of the loss.  A crop whose warped labels are all -100
     gets a new transform, at most ``MAX_RESAMPLE`` times.  Draw order of a resampling round: one ``sample_batch_params`` call for the
     k crops that are still empty, in ascending crop order -- so fresh stain values (k, 2, 3) first when ``config`` is set, then the
-    four affine draws of size k -- after everything the batch drew before."""
+    four affine draws of size k -- after everything the batch drew before.  ``rescale`` (n,) float64, the per-crop
+    ``diameter / diam_mean``, divides the random scale (``sample_affine_params``); a resampling round passes the factors of the
+    crops that are still empty."""
     cfg = get_config(config)
     X, labels, sh, sw = _to_device(X, labels, device)
     n = X.shape[0]
-    p = sample_batch_params(rng, n, sh, sw, cfg, scale_range, geometry, out)
+    rescale = _check_rescale(rescale, n)
+    p = sample_batch_params(rng, n, sh, sw, cfg, scale_range, geometry, out, rescale)
     x, lab = apply_params(X, labels, p, cfg, label_fill, (out, out))
     for _ in range(MAX_RESAMPLE):
         empty = torch.nonzero((lab == -100).flatten(1).all(1)).flatten()
@@ -198,7 +222,8 @@ def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed
             break
         if not geometry:
             raise ValueError(f"augment_batch: crop {int(empty[0])} has no annotated pixel")
-        q = sample_batch_params(rng, int(empty.numel()), sh, sw, cfg, scale_range, geometry, out)
+        q = sample_batch_params(rng, int(empty.numel()), sh, sw, cfg, scale_range, geometry, out,
+                                None if rescale is None else rescale[empty.cpu().numpy()])
         x2, lab2 = apply_params(X[empty], labels[empty], q, cfg, label_fill, (out, out))
         x[empty], lab[empty] = x2, lab2
     else:

@@ -1,0 +1,125 @@
+"""Dataset statistics for training from instance annotations: class weights, oversampling probabilities and
+cell diameters, from one device pass over the instance and class maps (``ops.label_stats``, csrc/cpx_labelstats.hip).
+
+The reference makes that pass on the host: ``get_class_counts`` / ``get_instance_counts`` (train_utils.py:387-436) and
+``cellpose.utils.diameters`` per image (train_utils.py:256-268).  ``get_class_weights`` and ``compute_oversampling_probabilities``
+are host restatements of the reference functions of the same names (train_utils.py:439-496): a handful of float64 operations on
+``n_classes`` numbers, pinned on the reference's own results by tests/golden/reference_label_stats.npz.
+
+Not built: ``label_instances=True`` of ``get_instance_counts`` (connected-component relabelling).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .log import get_logger
+
+logger = get_logger(__name__)
+
+
+@dataclass
+class LabelStats:
+    """``class_counts`` (ncls,) int64: ``get_class_counts``; ``instance_counts`` (N, ncls) float64: ``get_instance_counts``;
+    ``n_masks`` (N,) int64: ``len(cellpose.utils.diameters(masks)[1])``; ``diameters`` (N,) float64: its first value, RAW -- the
+    reference's clamp ``diam[diam < 5] = 5`` (train_utils.py:268) is ``clamp_diameters``, a separate step."""
+    class_counts: np.ndarray
+    instance_counts: np.ndarray
+    n_masks: np.ndarray
+    diameters: np.ndarray
+
+
+def diameters_from_mid_areas(mid_area: np.ndarray) -> np.ndarray:
+    """``np.median(counts ** 0.5) / (pi ** 0.5 / 2)`` of cellpose.utils.diameters from the two middle areas of the sorted counts:
+    the median of m values is the mean of those at ranks (m - 1) / 2 and m / 2.  float64 on the host; {0, 0} (no mask) gives 0."""
+    a = np.asarray(mid_area, np.float64).reshape(-1, 2)
+    return (np.sqrt(a[:, 0]) + np.sqrt(a[:, 1])) / 2 / (np.pi ** 0.5 / 2)
+
+
+def clamp_diameters(diameters: np.ndarray, minimum: float = 5.0) -> np.ndarray:
+    """train_utils.py:268: ``diam_train[diam_train < 5] = 5.0`` (a copy)."""
+    d = np.array(diameters, np.float64)
+    d[d < minimum] = minimum
+    return d
+
+
+def _chunk_to_device(x, lo: int, hi: int, dtype: torch.dtype, dev) -> torch.Tensor:
+    part = x[lo:hi]
+    if not isinstance(part, torch.Tensor):
+        part = np.asarray(part)
+        if not np.issubdtype(part.dtype, np.integer):
+            raise ValueError(f"label_stats: integer maps expected, got {part.dtype}")
+        info = torch.iinfo(dtype)
+        if part.size and (part.min() < info.min or part.max() > info.max):
+            raise ValueError(f"label_stats: values outside the range of {dtype}")
+        part = torch.from_numpy(np.ascontiguousarray(part.astype(np.int32 if dtype == torch.int32 else np.int16, copy=False)))
+    elif part.dtype.is_floating_point:
+        raise ValueError(f"label_stats: integer maps expected, got {part.dtype}")
+    return part.to(device=dev, dtype=dtype).contiguous()
+
+
+def label_stats(instances, classes, n_classes: int, device="cuda:0", chunk: int = 1024) -> LabelStats:
+    """Statistics of N training crops: ``instances`` / ``classes`` (N, H, W) integer numpy arrays or tensors (device tensors are
+    used where they are).  The device pass runs on ``chunk`` images at a time, so its workspace (two hash tables of >= 2 * H * W
+    slots and one area list per image: 2.75 MB per 256 x 256 crop) stays bounded.  Raises ``ValueError`` for a negative id or a
+    class >= ``n_classes``, naming the image."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("label_stats runs HIP kernels: pass a cuda device (there is no CPU path)")
+    if len(instances) != len(classes) or tuple(instances.shape) != tuple(classes.shape) or len(instances.shape) != 3:
+        raise ValueError("label_stats: instances and classes are (N, H, W) maps of one shape")
+    if chunk < 1:
+        raise ValueError("label_stats: chunk must be positive")
+    N, H, W = (int(v) for v in instances.shape)
+    chunk = min(int(chunk), 65535)
+    class_px = np.zeros((N, n_classes), np.int64)
+    ipc = np.zeros((N, n_classes), np.int64)
+    n_masks = np.zeros(N, np.int64)
+    mid = np.zeros((N, 2), np.int64)
+    ws = None
+    if N:
+        nbytes = _lib.lib().cpx_label_stats_workspace_bytes(min(chunk, N), H, W, int(n_classes))
+        if nbytes == 0:
+            raise ValueError(f"label_stats: unsupported H={H}, W={W}, n_classes={n_classes} (1 <= n_classes <= 64)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        out = ops.label_stats(_chunk_to_device(instances, lo, hi, torch.int32, dev),
+                              _chunk_to_device(classes, lo, hi, torch.int16, dev), n_classes, workspace=ws, check_status=False)
+        px, ic, nm, ma, st = (t.cpu().numpy() for t in out)
+        bad = np.flatnonzero(st)
+        if len(bad):
+            what = "a negative instance id" if st[bad[0]] & 1 else f"a class >= {n_classes}"
+            raise ValueError(f"label_stats: image {lo + int(bad[0])} has {what}")
+        class_px[lo:hi], ipc[lo:hi], n_masks[lo:hi], mid[lo:hi] = px, ic, nm, ma
+    return LabelStats(class_counts=class_px.sum(0), instance_counts=ipc.astype(np.float64), n_masks=n_masks,
+                      diameters=diameters_from_mid_areas(mid))
+
+
+def get_class_weights(class_counts: np.ndarray) -> np.ndarray:
+    """train_utils.py:439-467: ``sqrt(median(positive counts) / count)`` rounded to 4 decimals, 0 for an absent class."""
+    class_counts = np.asarray(class_counts)
+    positive = class_counts[class_counts > 0]
+    if positive.size == 0:
+        raise ValueError("Cannot compute class weights with no positive class counts")
+    median_count = np.median(positive)
+    inv_freq = np.zeros_like(class_counts, dtype=np.float64)
+    inv_freq[class_counts > 0] = median_count / class_counts[class_counts > 0]
+    inv_freq = inv_freq ** 0.5
+    return inv_freq.round(4)
+
+
+def compute_oversampling_probabilities(class_counts: np.ndarray, instance_counts: np.ndarray, power: float = 1) -> np.ndarray:
+    """train_utils.py:470-496: per image ``sum_j instance_counts[i, j] / class_counts[j]`` over the classes present, the class-0
+    weight forced to 0, raised to ``power`` and normalised to sum 1.  Like the reference, a set without a single instance of a
+    class above 0 yields NaN (0 / 0)."""
+    class_counts = np.asarray(class_counts)
+    class_weights = np.zeros_like(class_counts, dtype=np.float64)
+    class_weights[class_counts > 0] = 1.0 / class_counts[class_counts > 0]
+    class_weights[0] = 0
+    weights = np.sum(np.asarray(instance_counts) * class_weights[None], 1)
+    weights = weights ** power
+    return weights / weights.sum()

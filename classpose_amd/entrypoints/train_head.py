@@ -3,11 +3,18 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 (paper_experiments/run_training.py:92-98,354-358) reduced to arrays of fixed-size crops.
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
-        --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5]
+        --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
+        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1]
 
 Images are ``(N, 256, 256, 3)`` uint8 (normalised per crop like inference does) or ``(N, 3, 256, 256)`` float32 (already
 normalised); labels ``(N, 256, 256)`` integer class maps with -100 where nothing is annotated.  The result is an ordinary
 checkpoint in the reference's key layout: ``predict_wsi`` and ``ClassposeModel`` load it unchanged.
+
+With ``--instances`` (``(N, 256, 256)`` integer instance maps aligned with ``--labels``) one device pass over both maps
+(``classpose_amd.dataset_stats``) yields what the reference derives from its datasets: class weights (``--auto_class_weights``),
+oversampling probabilities (``--oversampling_method custom``), cell diameters (``--rescale``) and mask counts
+(``--min_train_masks``).  The reference's ``run_training.py`` has class weights and ``custom`` oversampling ON by default; here all
+four are opt-in, so that a command line without them trains exactly as before.
 """
 from __future__ import annotations
 
@@ -32,7 +39,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=8)
     p.add_argument("--learning_rate", type=float, default=5e-5)
     p.add_argument("--weight_decay", type=float, default=0.1)
-    p.add_argument("--class_weights", type=float, nargs="+", default=None)
+    cw = p.add_mutually_exclusive_group()
+    cw.add_argument("--class_weights", type=float, nargs="+", default=None)
+    cw.add_argument("--auto_class_weights", action="store_true",
+                    help="class weights from the training set, sqrt(median count / count) as the reference computes them by "
+                         "default (there --no_class_weights switches them off; here they are opt-in); needs --instances")
     p.add_argument("--nimg_per_epoch", type=int, default=None)
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--cache_features", action=argparse.BooleanOptionalAction, default=True,
@@ -43,6 +54,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--scale_range", type=float, default=0.5, help="random scale in [1 - r/2, 1 + r/2] (with --augment)")
     p.add_argument("--augment_label_fill", type=int, default=0,
                    help="class of pixels the warp takes from outside the crop: 0 = background as in the reference, -100 = not annotated")
+    p.add_argument("--instances", default=None, help=".npy, (N,256,256) integer instance maps aligned with --labels (0 = background)")
+    p.add_argument("--test_instances", default=None, help=".npy, instance maps of the validation set (its diameter range is logged)")
+    p.add_argument("--oversampling_method", default="none", choices=["none", "custom"],
+                   help="custom = draw every epoch with probabilities that favour crops with rare-class instances (the reference's "
+                        "default; here the default is none, a plain permutation); needs --instances")
+    p.add_argument("--oversampling_power", type=float, default=1.0, help="exponent of the oversampling weights")
+    p.add_argument("--rescale", action="store_true",
+                   help="divide the random scale of the augmentation by (cell diameter of the crop / --diam_mean); needs --instances "
+                        "and --augment")
+    p.add_argument("--diam_mean", type=float, default=30.0)
+    p.add_argument("--min_train_masks", type=int, default=0,
+                   help="drop training crops with fewer masks (the reference's default is 5; here 0 keeps every crop); needs --instances")
     p.add_argument("--save_only_trainable_params", action="store_true")
     p.add_argument("--random_seed", type=int, default=42)
     p.add_argument("--save_path", required=True)
@@ -51,20 +74,81 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def main(args) -> None:
-    from ..train import HeadTrainer, train_class_head
+def check_args(args) -> None:
+    """The combinations the parser cannot express; raises ``SystemExit`` with the reason."""
     if (args.test_images is None) != (args.test_labels is None):
         raise SystemExit("--test_images and --test_labels go together")
+    needs = [flag for flag, on in (("--auto_class_weights", args.auto_class_weights),
+                                   ("--oversampling_method custom", args.oversampling_method != "none"),
+                                   ("--rescale", args.rescale), ("--min_train_masks", args.min_train_masks > 0),
+                                   ("--test_instances", args.test_instances is not None)) if on]
+    if needs and args.instances is None:
+        raise SystemExit(f"{', '.join(needs)}: needs --instances")
+    if args.test_instances is not None and args.test_labels is None:
+        raise SystemExit("--test_instances needs --test_images and --test_labels")
+    if args.rescale and args.augment is None:
+        raise SystemExit("--rescale divides the random scale of the augmentation: it needs --augment")
+
+
+def _load_instances(path, labels, what: str) -> np.ndarray:
+    inst = np.load(path)
+    if inst.shape != labels.shape or not np.issubdtype(inst.dtype, np.integer):
+        raise SystemExit(f"{what}: expected integer instance maps {labels.shape}, got {inst.shape} {inst.dtype}")
+    return inst
+
+
+def main(args) -> None:
+    from .. import dataset_stats
+    from ..train import HeadTrainer, train_class_head
+    check_args(args)
     images, labels = np.load(args.images), np.load(args.labels)
     test_images = np.load(args.test_images) if args.test_images else None
     test_labels = np.load(args.test_labels) if args.test_labels else None
     trainer = HeadTrainer(args.pretrained_model, nclasses=args.nclasses, device=args.device, precision=args.precision,
                           class_weights=args.class_weights, weight_decay=args.weight_decay)
+    train_probs = diameters = None
+    if args.instances is not None:
+        stats = dataset_stats.label_stats(_load_instances(args.instances, labels, "--instances"), labels, trainer.nclasses,
+                                          device=args.device)
+        diameters = dataset_stats.clamp_diameters(stats.diameters)                # train_utils.py:268
+        logger.info(f"diameters: {diameters.min():.2f} to {diameters.max():.2f} px, masks per image: {int(stats.n_masks.min())} to "
+                    f"{int(stats.n_masks.max())}")
+        if args.test_instances is not None:
+            tstats = dataset_stats.label_stats(_load_instances(args.test_instances, test_labels, "--test_instances"), test_labels,
+                                               trainer.nclasses, device=args.device)
+            tdiam = dataset_stats.clamp_diameters(tstats.diameters)
+            logger.info(f"test diameters: {tdiam.min():.2f} to {tdiam.max():.2f} px")
+        if args.min_train_masks > 0:                                               # train_utils.py:288-308
+            keep = np.nonzero(stats.n_masks >= args.min_train_masks)[0]
+            nremove = len(images) - len(keep)
+            if nremove > 0:
+                logger.warning(f"{nremove} train images with number of masks less than min_train_masks ({args.min_train_masks}), "
+                               "removing from train set")
+                if len(keep) == 0:
+                    raise SystemExit("--min_train_masks leaves no training image")
+                images, labels, diameters = images[keep], labels[keep], diameters[keep]
+                stats = dataset_stats.LabelStats(stats.class_counts, stats.instance_counts[keep], stats.n_masks[keep],
+                                                 stats.diameters[keep])
+        # like the reference, weights and probabilities use the class counts of the whole set as loaded (run_training.py computes
+        # them before process_and_build_dataset removes images); the probabilities of removed images leave with them
+        if args.auto_class_weights:
+            logger.info("Computing class weights using inverse frequency with square root scaling")
+            weights = dataset_stats.get_class_weights(stats.class_counts)
+            logger.info(f"class weights = {weights.tolist()}")
+            trainer.set_class_weights(weights)
+        if args.oversampling_method == "custom":
+            logger.info(f"Computing oversampling probabilities with power {args.oversampling_power}")
+            train_probs = dataset_stats.compute_oversampling_probabilities(stats.class_counts, stats.instance_counts,
+                                                                           args.oversampling_power)
+            if not np.all(np.isfinite(train_probs)):
+                raise SystemExit("--oversampling_method custom: the training set has no instance of a class above 0")
+            logger.info(f"Custom oversampling - probability range: {train_probs.min():.6f} to {train_probs.max():.6f}")
     path, train_losses, test_losses = train_class_head(
         trainer, images, labels, test_images, test_labels, batch_size=args.batch_size, n_epochs=args.n_epochs,
         learning_rate=args.learning_rate, nimg_per_epoch=args.nimg_per_epoch, cache_features=args.cache_features,
         save_path=args.save_path, model_name=args.model_name, random_seed=args.random_seed,
-        augment=args.augment, scale_range=args.scale_range, label_fill=args.augment_label_fill)
+        augment=args.augment, scale_range=args.scale_range, label_fill=args.augment_label_fill, train_probs=train_probs,
+        diameters=diameters if args.rescale else None, diam_mean=args.diam_mean, rescale=args.rescale)
     if args.save_only_trainable_params:
         trainer.save(path, save_only_trainable_params=True)
     logger.info(f"final train loss {train_losses[-1]:.4f}" + (f", test loss {test_losses[-1]:.4f}" if test_images is not None else ""))

@@ -673,3 +673,41 @@ def normalize_img_f32(x: torch.Tensor, out: torch.Tensor | None = None) -> torch
     check(_lib.lib().cpx_normalize_apply_f32(ptr(x), ptr(stats), x.shape[0], x.shape[2], x.shape[3], ptr(out), _stream(x.device)),
           "normalize_apply_f32")
     return out
+
+
+# ---- t3: dataset statistics of (instance, class) maps (csrc/cpx_labelstats.hip) -----------------------------------
+def label_stats(inst: torch.Tensor, cls: torch.Tensor, ncls: int, workspace: torch.Tensor | None = None, check_status: bool = True):
+    """``cpx_label_stats`` on device maps: inst (n, H, W) int32 instance ids (any non-negative values), cls (n, H, W) int16 class
+    maps.  Returns five device tensors ``(class_px (n, ncls) int64, inst_per_class (n, ncls) int32, n_masks (n,) int32,
+    mid_area (n, 2) int32, status (n,) int32)``: pixels per class, ``np.unique(inst[cls == j]).size``, the number of ids that
+    cellpose's ``diameters`` keeps (all but the smallest) and the two middle order statistics of their areas.  Raises
+    ``ValueError`` naming the first image with a negative id or a class >= ``ncls``.  ``workspace``: a uint8 device tensor of at
+    least ``cpx_label_stats_workspace_bytes`` to reuse between calls (allocated here when absent or too small)."""
+    if inst.dtype != torch.int32 or cls.dtype != torch.int16 or inst.dim() != 3 or inst.shape != cls.shape:
+        raise ValueError("label_stats: inst must be int32 (n, H, W) and cls int16 of the same shape")
+    if not inst.is_cuda or inst.device != cls.device:
+        raise ValueError("label_stats: both maps must be on one cuda device")
+    inst, cls = inst.contiguous(), cls.contiguous()
+    n, H, W = inst.shape
+    dev = inst.device
+    L = _lib.lib()
+    nbytes = L.cpx_label_stats_workspace_bytes(n, H, W, int(ncls))
+    if nbytes == 0:
+        raise ValueError(f"label_stats: unsupported arguments n={n}, H={H}, W={W}, ncls={ncls} (1 <= ncls <= 64, n <= 65535)")
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev or workspace.dtype != torch.uint8:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    class_px = torch.empty((n, ncls), dtype=torch.int64, device=dev)
+    inst_per_class = torch.empty((n, ncls), dtype=torch.int32, device=dev)
+    n_masks = torch.empty(n, dtype=torch.int32, device=dev)
+    mid_area = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(L.cpx_label_stats(ptr(inst), ptr(cls), n, H, W, int(ncls), ptr(class_px), ptr(inst_per_class), ptr(n_masks), ptr(mid_area),
+                            ptr(status), ptr(workspace), workspace.numel(), _stream(dev)), "label_stats")
+    if check_status:
+        bad = torch.nonzero(status).flatten()
+        if bad.numel():
+            i = int(bad[0])
+            bits = int(status[i])
+            what = "a negative instance id" if bits & 1 else f"a class >= {ncls}"
+            raise ValueError(f"label_stats: image {i} has {what}")
+    return class_px, inst_per_class, n_masks, mid_area, status

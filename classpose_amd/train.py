@@ -12,9 +12,10 @@ Deliberately different from the reference:
     stochastic layer drop of ``ClassTransformer.forward`` (vit_sam.py:165-173) even in a frozen backbone;
   * an image without a single annotated pixel raises ``ValueError`` (the reference's Tversky loss is NaN for such a batch);
   * augmentation is the device chain of ``classpose_amd.augment`` (stain jitter, flip / rotation / scale / crop, normalisation
-    after both), which samples at exact source coordinates where OpenCV quantises them; the ``enhanced`` pipeline and the
-    rescale by cell diameter are not built;
-  * no HDF5 datasets, oversampling, learned loss weighting, multi-GPU exchange or optimiser-state resume.
+    after both), which samples at exact source coordinates where OpenCV quantises them; the ``enhanced`` pipeline is not built;
+  * oversampling (``train_probs``) and the rescale by cell diameter (``rescale``, ``diameters``) are opt-in arguments of
+    ``train_class_head``, fed by ``classpose_amd.dataset_stats``; the reference's command line has both on by default;
+  * no HDF5 datasets, learned loss weighting, multi-GPU exchange or optimiser-state resume.
 
 A trainer owns its ``engine.NetWeights`` and updates the head operands in place: sharing them with an ``Engine`` that is running on
 another stream is the caller's risk.
@@ -113,11 +114,7 @@ class HeadTrainer:
         self.w_ce, self.w_tv = 1.0, 1.0                  # LossAggregator(optimise=False): both multipliers exp(-0) = 1
         ncols = self.nclasses * 64
         dev = self.device
-        if class_weights is not None:
-            class_weights = torch.as_tensor(np.float32(class_weights)).to(dev)          # train.py:444-448
-            if class_weights.numel() != self.nclasses:
-                raise ValueError("class_weights: one weight per class")
-        self.class_weights = class_weights
+        self.set_class_weights(class_weights)
         self.w = self.sd["out_class.weight"].detach().float().reshape(ncols, 256).contiguous().to(dev)      # master copies
         self.b = self.sd["out_class.bias"].detach().float().contiguous().to(dev)
         self.m_w, self.v_w, self.m_b, self.v_b = (torch.zeros_like(t) for t in (self.w, self.w, self.b, self.b))
@@ -130,6 +127,15 @@ class HeadTrainer:
         self._head_fb = torch.empty((nS * TOKENS, c.ld_head), dtype=torch.float32, device=dev)
         self._es = torch.empty(0, dtype=self.dtype).element_size()
         self._buf: dict = {}
+
+    def set_class_weights(self, class_weights) -> None:
+        """Replace the per-class loss weights (None: unweighted) -- for weights that are computed from the training set after the
+        trainer exists (``dataset_stats.get_class_weights``).  Takes effect from the next ``step`` / ``evaluate``."""
+        if class_weights is not None:
+            class_weights = torch.as_tensor(np.float32(class_weights)).to(self.device)  # train.py:444-448
+            if class_weights.numel() != self.nclasses:
+                raise ValueError("class_weights: one weight per class")
+        self.class_weights = class_weights
 
     # -- forward pieces ----------------------------------------------------------------------------------------
     def _patches(self, X) -> torch.Tensor:
@@ -265,7 +271,8 @@ def _check_dataset(images, labels, what: str):
 def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, test_labels=None, batch_size: int = 8,
                      n_epochs: int = 100, learning_rate: float = 5e-5, nimg_per_epoch: int | None = None, cache_features: bool = True,
                      save_path=None, model_name: str | None = None, random_seed: int = 42, transform=None,
-                     augment: str | None = None, scale_range: float = 0.5, label_fill: int = 0):
+                     augment: str | None = None, scale_range: float = 0.5, label_fill: int = 0, train_probs=None, diameters=None,
+                     diam_mean: float = 30.0, rescale: bool = False):
     """The epoch loop of train.py:606-655 for the frozen-backbone mode: per-epoch learning rate from ``lr_schedule``, seeded sampling
     without replacement (with, when ``nimg_per_epoch`` exceeds the set), sample-weighted running means of CE / Tversky / total,
     validation once per epoch, ``checkpoint_last.pt`` and ``checkpoint_best.pt`` (lowest validation loss; training loss without a
@@ -275,6 +282,11 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     batch on the device with ``augment.augment_batch`` (``scale_range``, ``label_fill`` as there), drawing from the epoch's
     generator after the sampling order and after ``transform``, which still runs first.  The training path is then uncached;
     validation is never augmented and its features are still cached when ``cache_features`` is set.
+    ``train_probs`` (one non-negative weight per image, positive sum; normalised here, checked as the reference's
+    ``DistributedEpochSampler`` checks them, dataset.py:560-570) turns the epoch's order into ``rng.choice(nimg, nimg_per_epoch,
+    p=train_probs)``, the oversampling draw of dataset.py:597-601.  ``rescale=True`` divides the random scale of every augmented
+    crop by ``diameters[i] / diam_mean`` (dataset.py:35-45): it needs ``augment`` and ``diameters`` (one per image, e.g.
+    ``dataset_stats.clamp_diameters(label_stats(...).diameters)``).  With the defaults neither changes anything.
     Returns ``(path of the final model, train_losses, test_losses)``."""
     images, labels = _check_dataset(images, labels, "training")
     has_test = test_images is not None
@@ -282,6 +294,25 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
         test_images, test_labels = _check_dataset(test_images, test_labels, "validation")
     nimg = len(images)
     nimg_per_epoch = nimg if nimg_per_epoch is None else int(nimg_per_epoch)
+    if train_probs is not None:
+        train_probs = np.asarray(train_probs, dtype=np.float64)
+        if train_probs.ndim != 1 or train_probs.shape[0] != nimg:
+            raise ValueError("train_probs must have the same length as the dataset")
+        if np.any(train_probs < 0):
+            raise ValueError("train_probs must be non-negative")
+        if not float(train_probs.sum()) > 0.0:
+            raise ValueError("train_probs must sum to a positive value")
+        train_probs = train_probs / train_probs.sum()
+    rsc = None
+    if rescale:
+        if augment is None:
+            raise ValueError("rescale=True divides the random scale of the augmentation: it needs augment")
+        if diameters is None:
+            raise ValueError("rescale=True needs the diameters of the training images")
+        diameters = np.asarray(diameters, dtype=np.float64)
+        if diameters.shape != (nimg,) or not np.all(diameters > 0) or not diam_mean > 0:
+            raise ValueError("diameters: one positive diameter per training image, and a positive diam_mean")
+        rsc = diameters / float(diam_mean)
     LR = lr_schedule(learning_rate, n_epochs)
     model_name = "classpose_head" if model_name is None else model_name
     model_dir = (Path.cwd() if save_path is None else Path(save_path)) / model_name
@@ -307,7 +338,10 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     best = np.inf
     for iepoch in range(n_epochs):
         rng = np.random.default_rng([random_seed, iepoch])
-        order = rng.permutation(nimg)[:nimg_per_epoch] if nimg_per_epoch <= nimg else rng.choice(nimg, nimg_per_epoch)
+        if train_probs is not None:
+            order = rng.choice(nimg, nimg_per_epoch, p=train_probs)
+        else:
+            order = rng.permutation(nimg)[:nimg_per_epoch] if nimg_per_epoch <= nimg else rng.choice(nimg, nimg_per_epoch)
         sums, count = np.zeros(3), 0
         for s in range(0, len(order), batch_size):
             idx = order[s:s + batch_size]
@@ -320,7 +354,8 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
                     x, y = transform(x, y, rng)
                 if augment is not None:
                     x, y = _augment.augment_batch(x, y, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
-                                                  dtype=trainer.dtype, device=dev, out=CROP)
+                                                  dtype=trainer.dtype, device=dev, out=CROP,
+                                                  rescale=None if rsc is None else rsc[idx])
             r = trainer.step(x, y, float(LR[iepoch]))
             sums += np.array([r["ce"], r["tversky"], r["loss"]]) * len(idx)
             count += len(idx)

@@ -550,6 +550,34 @@ int cpx_normalize_stats_f32(const float *img, int n, int H, int W, int lo_prev, 
 int cpx_normalize_apply_f32(const float *img, const float *stats, int n, int H, int W, float *out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * t3  dataset statistics of (instance, class) training maps (csrc/cpx_labelstats.hip)
+ * replaces the host passes behind class weights, oversampling and the rescale by cell diameter: get_class_counts and
+ * get_instance_counts (classpose/train_utils.py:387-436 of the reference) and the `unique(masks, return_counts=True)` of
+ * cellpose.utils.diameters (train_utils.py:256-268).  Runs on `stream`, allocates nothing, integer atomics only: every output
+ * is an exact integer that does not depend on scheduling.
+ * ---------------------------------------------------------------------- */
+/* cpx_label_stats: inst [nI][H][W] int32 instance ids (any non-negative values, neither contiguous nor small; up to H * W
+ *   distinct ones per image), cls [nI][H][W] int16 class maps, 1 <= ncls <= 64, nI <= 65535, H * W <= 2^28.
+ *   class_px [nI][ncls] int64        pixels with cls == j: np.bincount of the non-negative classes (the reference drops EVERY
+ *                                    negative class, not only -100, train_utils.py:401);
+ *   inst_per_class [nI][ncls]        np.unique(inst[cls == j]).size (train_utils.py:435): the background id 0 counts as an id when
+ *                                    it carries class j, an id that carries two classes counts in both, and pixels of a negative
+ *                                    class take no part;
+ *   n_masks [nI]                     m = (distinct ids of the image) - 1: cellpose.utils.diameters takes `counts[1:]` of a sorted
+ *                                    unique, which drops the SMALLEST id present -- the background when there is one, else the
+ *                                    smallest real cell;
+ *   mid_area [nI][2]                 with the m remaining areas (pixels of an id over the whole image, whatever the class) sorted
+ *                                    ascending and ranked from 0: {a[(m - 1) / 2], a[m / 2]}, {0, 0} when m == 0.  The host forms
+ *                                    median(sqrt(area)) = (sqrt(a0) + sqrt(a1)) / 2 and divides by sqrt(pi) / 2 in float64;
+ *   status [nI]                      bit 0: a negative id, bit 1: a class >= ncls; the image's other outputs are then void.
+ *   The tables are open-addressing hash tables of a power of two >= 2 * H * W slots per image in the workspace, which therefore
+ *   never fill up.  cpx_label_stats_workspace_bytes is host only and returns 0 for arguments the entry would refuse.            */
+size_t cpx_label_stats_workspace_bytes(int nI, int H, int W, int ncls);
+int cpx_label_stats(const int32_t *inst, const int16_t *cls, int nI, int H, int W, int ncls, int64_t *class_px,
+                    int32_t *inst_per_class, int32_t *n_masks, int32_t *mid_area, int32_t *status,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
  * replaces, per instance, cv2.findContours(cell_mask, RETR_EXTERNAL,
  * CHAIN_APPROX_SIMPLE)[0] + shapely.Polygon(...).is_valid/.centroid/.area/.length
