@@ -185,7 +185,6 @@ _PRIVATE = {
     "cpx_gemm_set_4w": (None, [_i]),
     "cpx_net_set_mlp_parts": (None, [_i]),
     "cpx_gemm_set_balanced": (None, [_i]),
-    "cpx_gemm_set_dbg": (None, [_i]),
     "cpx_gemm_set_l2_block": (None, [_i]),
     "cpx_gemm_ln_dt": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),
     "cpx_row_stats_dt": (_i, [_i, _p, _i, _p, _p]),

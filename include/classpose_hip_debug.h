@@ -22,8 +22,7 @@ void cpx_gemm_set_direct(int mode);         /* 1 (default): direct-store epilogu
 void cpx_gemm_set_balanced(int on);         /* 1 (default): balanced fragment-read schedule of the persistent 256^2 main loop for the bf16 residual + row-statistics epilogue (proj, mlp.lin2); 0: plain schedule */
 int cpx_gemm4w(const void *A, const void *W, int M, int N, int K, const float *bias, void *out, int ld_out, void *stream);   /* the 256^2 GEMM tile with ONE wave per SIMD (4 waves x 128 x 128, AGPR accumulators), persistent, bias epilogue, bf16 (csrc/cpx_gemm4w.hip) */
 void cpx_gemm_set_4w(int on);               /* 1 (default): mlp.lin1 (bf16, folded LayerNorm + GELU) on the one-wave-per-SIMD kernel; 0: on the 8-wave persistent kernel (same bits) */
-void cpx_gemm4w_set_variant(int v);         /* experiment switches of cpx_gemm4w (0 default) */
-void cpx_gemm_set_dbg(int mask);            /* timing-only ablations of the 256^2 epilogue (0 default)   */
+void cpx_gemm4w_set_variant(int v);         /* mlp.lin1's output stores on the one-wave-per-SIMD kernel: 0 (default) at agent scope (sc1, written through), 4096: ordinary stores (same bits); every other value acts as 0 (the timing-only ablations and abandoned store scopes that other values once selected are removed) */
 void cpx_net_set_mlp_parts(int on);         /* 1 (default): the MLP of a layer in row parts of 16 384 tokens (hidden activations stay in the Infinity Cache); 0: one launch pair */
 void cpx_attention_set_xcd_order(int on);   /* 1 (default): (sub-tile, head) pairs pinned to one XCD     */
 void cpx_attention_set_variant(int v);      /* 2 (default): two query rows per wave, two workgroups per CU (production); 7: 4-wave, LDS-DMA ring + pipelined S (rounds 2-5, the bitwise reference); any other value: the attention entries fail with CPX_EINVAL */

@@ -1,6 +1,6 @@
 """In-process interleaved A/B of a private debug switch on the whole engine step.
 usage: python tools/ab_switch.py cpx_gemm_set_reverse [cpx_other_switch ...]      (values 0 and 1)
-       python tools/ab_switch.py cpx_gemm_set_dbg=32,48                            (two explicit values; restored to AB_RESTORE)"""
+       python tools/ab_switch.py cpx_gemm_set_direct=0,1                           (two explicit values; restored to AB_RESTORE)"""
 import os as _os
 _os.environ.setdefault("CLASSPOSE_HIP_DEBUG", "1")      # the A/B switches live in the -DCPX_DEBUG library (libclasspose_hip_debug.so)
 import sys, os, time
