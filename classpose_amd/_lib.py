@@ -158,6 +158,8 @@ SIGNATURES = {
     "cpx_normalize_apply_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "cpx_label_stats_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_label_stats": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "cpx_pool_byte_sums": (_i, [_p, _p, _p, _i, C.c_longlong, _p, _p, _p]),
+    "cpx_warp_affine_pool_u8": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),

@@ -8,6 +8,11 @@ parameters; the pixels stay on the device: ``ops.hed_jitter`` -> ``ops.warp_affi
 Random draws come from the numpy ``Generator`` passed in, in the order documented on each sampler.  The reference draws from the
 global ``np.random`` state, so its sample stream is not reproduced; its distributions are.
 
+Whole annotated images of any size live in an ``ImagePool``: uploaded once, packed back to back, and
+``augment_batch_pool`` cuts every crop of a batch out of its own image with one fused launch (``ops.warp_affine_pool``: the stain
+jitter on the taps, the warp) -- the fresh random window per epoch of dataset.py:23-56.  ``grid_crops`` are the deterministic
+windows used where nothing is augmented.
+
 Still different from the reference: the warp samples at exact double-precision source coordinates (OpenCV quantises them to
 1 / 32 pixel) and the ``enhanced`` pipeline is not built.  The rescale by cell diameter (dataset.py:35-45) is the ``rescale``
 argument of the samplers: per crop ``diameter / diam_mean``, the diameters from ``dataset_stats.label_stats``.
@@ -53,38 +58,51 @@ def get_config(name: str | None) -> dict | None:
     return AUGMENT_CONFIGS[name]
 
 
-def affine_inverse(flip, theta, scale, dxy, sh: int, sw: int, out: int = 256) -> np.ndarray:
+def _source_shapes(sh, sw, n: int):
+    """(sh, sw) as float64 (n,) arrays: a scalar source shape for every crop, or one per crop.  Sizes are integers, so the
+    conversion is exact and what follows is bitwise the arithmetic on the integers themselves."""
+    sh, sw = np.asarray(sh, np.float64), np.asarray(sw, np.float64)
+    if sh.shape not in ((), (n,)) or sw.shape not in ((), (n,)):
+        raise ValueError(f"source shapes: a scalar or one value per crop ({n}) expected")
+    if not (np.all(sh > 0) and np.all(sw > 0)):
+        raise ValueError("source shapes must be positive")
+    return np.broadcast_to(sh, (n,)), np.broadcast_to(sw, (n,))
+
+
+def affine_inverse(flip, theta, scale, dxy, sh, sw, out: int = 256) -> np.ndarray:
     """(n, 6) float64 inverse maps, source (sx, sy) = inv . (x, y, 1), of cellpose's forward map
     ``dst = scale * R(theta) * (src - cc) + cc1`` with ``R = [[cos, -sin], [sin, cos]]``, ``cc = (sw / 2, sh / 2)`` and
     ``cc1 = cc - ([sw, sh] - out) / 2 + dxy``.  Where ``flip`` is set the horizontal flip of the source, ``sx -> sw - 1 - sx``,
-    is folded into the map."""
+    is folded into the map.  ``sh`` / ``sw``: the source shape, a scalar or one per crop."""
     flip, theta, scale = np.asarray(flip, bool), np.asarray(theta, np.float64), np.asarray(scale, np.float64)
     dxy = np.asarray(dxy, np.float64).reshape(-1, 2)
-    cc = np.array([sw / 2, sh / 2], np.float64)
-    cc1 = cc - (np.array([sw, sh], np.float64) - out) / 2 + dxy                     # (n, 2)
+    sh, sw = _source_shapes(sh, sw, len(theta))
+    cc = np.stack([sw / 2, sh / 2], 1)                                              # (n, 2)
+    cc1 = cc - (np.stack([sw, sh], 1) - out) / 2 + dxy
     c, s = np.cos(theta) / scale, np.sin(theta) / scale
     inv = np.empty((len(theta), 6), np.float64)
     inv[:, 0], inv[:, 1] = c, s                                                     # (1 / scale) R^T
     inv[:, 3], inv[:, 4] = -s, c
-    inv[:, 2] = cc[0] - (c * cc1[:, 0] + s * cc1[:, 1])
-    inv[:, 5] = cc[1] - (-s * cc1[:, 0] + c * cc1[:, 1])
+    inv[:, 2] = cc[:, 0] - (c * cc1[:, 0] + s * cc1[:, 1])
+    inv[:, 5] = cc[:, 1] - (-s * cc1[:, 0] + c * cc1[:, 1])
     inv[flip, 0:2] = -inv[flip, 0:2]
-    inv[flip, 2] = (sw - 1) - inv[flip, 2]
+    inv[flip, 2] = (sw[flip] - 1) - inv[flip, 2]
     return inv
 
 
-def affine_forward(theta, scale, dxy, sh: int, sw: int, out: int = 256) -> np.ndarray:
+def affine_forward(theta, scale, dxy, sh, sw, out: int = 256) -> np.ndarray:
     """(n, 6) float64 forward maps ``dst = fwd . (sx, sy, 1)`` of the same parametrisation, without the flip."""
     theta, scale = np.asarray(theta, np.float64), np.asarray(scale, np.float64)
     dxy = np.asarray(dxy, np.float64).reshape(-1, 2)
-    cc = np.array([sw / 2, sh / 2], np.float64)
-    cc1 = cc - (np.array([sw, sh], np.float64) - out) / 2 + dxy
+    sh, sw = _source_shapes(sh, sw, len(theta))
+    cc = np.stack([sw / 2, sh / 2], 1)
+    cc1 = cc - (np.stack([sw, sh], 1) - out) / 2 + dxy
     c, s = np.cos(theta) * scale, np.sin(theta) * scale
     fwd = np.empty((len(theta), 6), np.float64)
     fwd[:, 0], fwd[:, 1] = c, -s
     fwd[:, 3], fwd[:, 4] = s, c
-    fwd[:, 2] = cc1[:, 0] - (c * cc[0] - s * cc[1])
-    fwd[:, 5] = cc1[:, 1] - (s * cc[0] + c * cc[1])
+    fwd[:, 2] = cc1[:, 0] - (c * cc[:, 0] - s * cc[:, 1])
+    fwd[:, 5] = cc1[:, 1] - (s * cc[:, 0] + c * cc[:, 1])
     return fwd
 
 
@@ -97,15 +115,18 @@ def _check_rescale(rescale, n: int) -> np.ndarray | None:
     return rescale
 
 
-def sample_affine_params(rng: np.random.Generator, n: int, sh: int, sw: int, out: int = 256, scale_range: float = 0.5,
+def sample_affine_params(rng: np.random.Generator, n: int, sh, sw, out: int = 256, scale_range: float = 0.5,
                          do_flip: bool = True, rotate: bool = True, rescale=None) -> dict:
     """The random parameters behind ``sample_affine``: ``flip`` (n,) bool, ``theta``, ``scale`` (n,), ``dxy`` (n, 2).
     Draw order, always all four so that the stream does not depend on the switches: ``rng.random(n)`` for the flips, ``rng.random(n)``
     for theta, ``rng.random(n)`` for the scale, ``rng.random((n, 2))`` for the shift (x, y).  ``rescale`` (n,) float64, the per-crop
     ``diameter / diam_mean`` (dataset.py:35-38), divides the scale; the crop room behind ``dxy`` follows from the divided scale.
-    It changes neither the number nor the order of the draws, and ``rescale=None`` is bitwise the sampler without it."""
+    It changes neither the number nor the order of the draws, and ``rescale=None`` is bitwise the sampler without it.
+    ``sh`` / ``sw`` are a scalar or one value per crop (crops of an ``ImagePool``): every crop's room follows from its own source,
+    and neither the number nor the order of the draws depends on the shapes."""
     r = float(np.clip(scale_range, 0.0, 2.0))
     rescale = _check_rescale(rescale, n)
+    sh, sw = _source_shapes(sh, sw, n)
     u_flip, u_theta, u_scale, u_dxy = rng.random(n), rng.random(n), rng.random(n), rng.random((n, 2))
     flip = (u_flip > 0.5) & bool(do_flip)
     theta = 2 * np.pi * u_theta if rotate else np.zeros(n)
@@ -116,7 +137,7 @@ def sample_affine_params(rng: np.random.Generator, n: int, sh: int, sw: int, out
     return dict(flip=flip, theta=theta, scale=scale, dxy=(u_dxy - 0.5) * room)
 
 
-def sample_affine(rng: np.random.Generator, n: int, sh: int, sw: int, out: int = 256, scale_range: float = 0.5,
+def sample_affine(rng: np.random.Generator, n: int, sh, sw, out: int = 256, scale_range: float = 0.5,
                   do_flip: bool = True, rotate: bool = True, rescale=None):
     """(flips (n,) bool, inverse maps (n, 6) float64) of ``n`` random flip / rotation / scale / crop transforms from a
     ``sh`` x ``sw`` source into ``out`` x ``out``, in the parametrisation of cellpose's ``random_rotate_and_resize``.
@@ -153,7 +174,7 @@ class BatchParams:
     flip: np.ndarray                # (n,) bool
 
 
-def sample_batch_params(rng: np.random.Generator, n: int, sh: int, sw: int, config: dict | None, scale_range: float = 0.5,
+def sample_batch_params(rng: np.random.Generator, n: int, sh, sw, config: dict | None, scale_range: float = 0.5,
                         geometry: bool = True, out: int = 256, rescale=None) -> BatchParams:
     """Draw order per batch: ``sample_hed`` (when ``config`` is given), then ``sample_affine`` (when ``geometry``), which takes
     ``rescale`` (n,) -- without geometry there is no scale to divide and ``rescale`` is refused."""
@@ -230,3 +251,184 @@ def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed
         if bool((lab == -100).flatten(1).all(1).any()):
             raise ValueError(f"augment_batch: a crop had no annotated pixel after {MAX_RESAMPLE} resampled transforms")
     return ops.patchify_f32(x, dtype), lab
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# whole annotated images of any size: the device-resident pool
+# ---------------------------------------------------------------------------------------------------------------------
+def pool_table(shapes) -> tuple[np.ndarray, np.ndarray, int]:
+    """(px_off (nI,) int64, hw (nI, 2) int32, pool_px) of images of ``shapes`` [(h, w), ...] packed back to back."""
+    hw = np.asarray(shapes, np.int64).reshape(-1, 2)
+    if len(hw) == 0 or np.any(hw <= 0) or np.any(hw > np.iinfo(np.int32).max):
+        raise ValueError("pool_table: at least one image, and positive sizes")
+    px = hw[:, 0] * hw[:, 1]
+    px_off = np.concatenate([[0], np.cumsum(px)[:-1]]).astype(np.int64)
+    return px_off, hw.astype(np.int32), int(px.sum())
+
+
+def check_pool_table(px_off, hw, pool_px: int) -> None:
+    """What the kernels rely on: positive sizes, image i + 1 starts where image i ends (so the offsets are monotone and nothing
+    overlaps), and the pool is exactly the sum of h * w pixels long."""
+    px_off, hw = np.asarray(px_off), np.asarray(hw)
+    if px_off.ndim != 1 or len(px_off) == 0 or hw.shape != (len(px_off), 2):
+        raise ValueError("pool table: px_off (nI,) and hw (nI, 2) expected")
+    if np.any(hw <= 0):
+        raise ValueError("pool table: image sizes must be positive")
+    px = hw[:, 0].astype(np.int64) * hw[:, 1].astype(np.int64)
+    if px_off[0] != 0 or np.any(np.diff(px_off) != px[:-1]):
+        raise ValueError("pool table: offsets must start at 0 and grow by h * w from image to image")
+    if int(px_off[-1] + px[-1]) != int(pool_px):
+        raise ValueError(f"pool table: the pool holds {pool_px} pixels, the images {int(px_off[-1] + px[-1])}")
+
+
+class ImagePool:
+    """Whole annotated images of any size on the device, uploaded once: ``pool_u8`` the (h_i, w_i, 3) uint8 images packed back to
+    back, ``pool_lab`` the int16 class maps at the same pixel offsets, ``px_off`` / ``hw`` the table (host copies ``px_off_host`` /
+    ``hw_host``), ``byte_sums`` (nI,) int64 on the host -- the exact byte sum of every image, from which ``applied`` forms the stain
+    jitter's cut-off decision per image.  ``diameters`` (nI,) float64 or None travel with the images for ``rescale``.
+
+    images: a sequence of (H, W, 3) uint8 arrays; labels: (H, W) integer class maps (-100 = not annotated) in int16 range."""
+
+    def __init__(self, images, labels, diameters=None, device="cuda:0"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("an ImagePool lives on the device: pass a cuda device (there is no CPU path)")
+        images, labels = list(images), list(labels)
+        if len(images) == 0 or len(images) != len(labels):
+            raise ValueError("ImagePool: one class map per image, and at least one image")
+        for i, (im, lab) in enumerate(zip(images, labels)):
+            im, lab = np.asarray(im), np.asarray(lab)
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError(f"ImagePool: image {i} must be (H, W, 3) uint8, got {im.shape} {im.dtype}")
+            if lab.shape != im.shape[:2] or not np.issubdtype(lab.dtype, np.integer):
+                raise ValueError(f"ImagePool: class map {i} must be an integer map {im.shape[:2]}, got {lab.shape} {lab.dtype}")
+            if lab.size and (lab.min() < -32768 or lab.max() > 32767):
+                raise ValueError(f"ImagePool: class map {i} has values outside int16")
+        self.px_off_host, self.hw_host, self.pool_px = pool_table([np.asarray(im).shape[:2] for im in images])
+        check_pool_table(self.px_off_host, self.hw_host, self.pool_px)
+        host_u8 = np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in images])
+        host_lab = np.concatenate([np.asarray(lab).astype(np.int16).reshape(-1) for lab in labels])
+        if host_u8.size != 3 * self.pool_px or host_lab.size != self.pool_px:
+            raise ValueError("ImagePool: the packed pool does not have the length of its table")
+        dev = self.device
+        self.pool_u8, self.pool_lab = torch.from_numpy(host_u8).to(dev), torch.from_numpy(host_lab).to(dev)
+        self.px_off, self.hw = torch.from_numpy(self.px_off_host).to(dev), torch.from_numpy(self.hw_host).to(dev)
+        self.byte_sums = ops.pool_byte_sums(self.pool_u8, self.px_off, self.hw).cpu().numpy()
+        self.annotated = np.array([bool((np.asarray(lab) != -100).any()) for lab in labels])
+        if diameters is not None:
+            diameters = np.asarray(diameters, np.float64)
+            if diameters.shape != (len(images),) or not np.all(diameters > 0):
+                raise ValueError("ImagePool: one positive diameter per image")
+        self.diameters = diameters
+        self._grid = None
+
+    def __len__(self) -> int:
+        return len(self.px_off_host)
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes of the pool: 3 per pixel of image, 2 per pixel of class map, 16 per table row."""
+        return 5 * self.pool_px + 16 * len(self)
+
+    def applied(self, cutoff_range) -> np.ndarray:
+        """(nI,) int32: 1 where ``lo <= (byte sum / byte count) / 255.0 <= hi`` in double, the test of ``cpx_hed_jitter_u8`` on the
+        WHOLE image (dataset.py:41 hands the whole image to the transform)."""
+        count = 3.0 * self.hw_host[:, 0].astype(np.float64) * self.hw_host[:, 1].astype(np.float64)
+        mean = (self.byte_sums.astype(np.float64) / count) / 255.0
+        return ((float(cutoff_range[0]) <= mean) & (mean <= float(cutoff_range[1]))).astype(np.int32)
+
+
+def sample_batch_params_pool(pool: ImagePool, idx, rng: np.random.Generator, config: dict | None, scale_range: float = 0.5,
+                             geometry: bool = True, out: int = 256, rescale=None) -> BatchParams:
+    """``sample_batch_params`` for crops out of images ``idx`` of a pool: the same draws in the same order, every crop's room from
+    its own image.  Without geometry the map is the identity: the window at the image's origin."""
+    idx = np.asarray(idx, np.int64)
+    return sample_batch_params(rng, len(idx), pool.hw_host[idx, 0], pool.hw_host[idx, 1], config, scale_range, geometry, out, rescale)
+
+
+def apply_params_pool(pool: ImagePool, idx, p: BatchParams, config: dict | None, label_fill: int = 0, out_hw=(256, 256)):
+    """The device chain of ``apply_params`` for crops out of images ``idx`` of a pool: one fused launch (stain jitter on the taps
+    of the images inside the cut-off, warp), then the float32 normalisation."""
+    idx = np.asarray(idx, np.int64)
+    sigma = bias = applied = None
+    simple = False
+    if config is not None and p.sigma is not None:
+        sigma, bias, applied = p.sigma, p.bias, pool.applied(config["cutoff_range"])[idx]
+        simple = config.get("simple_mode", False)
+    x, lab, _status = ops.warp_affine_pool(pool.pool_u8, pool.pool_lab, pool.px_off, pool.hw, idx, p.inv, out_hw, sigma, bias, applied,
+                                           simple, label_fill)
+    return ops.normalize_img_f32(x, out=x), lab
+
+
+def augment_batch_pool(pool: ImagePool, idx, rng: np.random.Generator, config: str | None = "hed_only", scale_range: float = 0.5,
+                       label_fill: int = 0, geometry: bool = True, dtype: torch.dtype = torch.bfloat16, out: int = 256,
+                       rescale=None):
+    """``augment_batch`` for one window out of each of the images ``idx`` (repeats allowed) of an ``ImagePool``: (patch rows, int16
+    labels (n, out, out)).  The draws, their order, the resampling of crops whose labels are all -100 and the tail
+    (``normalize_img_f32`` -> ``patchify_f32``) are those of ``augment_batch``; on a pool of equal-sized images the result is bitwise
+    ``augment_batch`` of the same images.  The stain jitter's cut-off test sees the whole image, as in the reference."""
+    cfg = get_config(config)
+    idx = np.asarray(idx, np.int64)
+    n = len(idx)
+    if idx.ndim != 1 or n == 0 or idx.min() < 0 or idx.max() >= len(pool):
+        raise ValueError(f"augment_batch_pool: image indices in [0, {len(pool)}) expected")
+    rescale = _check_rescale(rescale, n)
+    p = sample_batch_params_pool(pool, idx, rng, cfg, scale_range, geometry, out, rescale)
+    x, lab = apply_params_pool(pool, idx, p, cfg, label_fill, (out, out))
+    for _ in range(MAX_RESAMPLE):
+        empty = torch.nonzero((lab == -100).flatten(1).all(1)).flatten()
+        if empty.numel() == 0:
+            break
+        if not geometry:
+            raise ValueError(f"augment_batch_pool: crop {int(empty[0])} has no annotated pixel")
+        e = empty.cpu().numpy()
+        q = sample_batch_params_pool(pool, idx[e], rng, cfg, scale_range, geometry, out, None if rescale is None else rescale[e])
+        x2, lab2 = apply_params_pool(pool, idx[e], q, cfg, label_fill, (out, out))
+        x[empty], lab[empty] = x2, lab2
+    else:
+        if bool((lab == -100).flatten(1).all(1).any()):
+            raise ValueError(f"augment_batch_pool: a crop had no annotated pixel after {MAX_RESAMPLE} resampled transforms")
+    return ops.patchify_f32(x, dtype), lab
+
+
+def grid_origins(h: int, crop: int = 256) -> list[int]:
+    """Window origins along an axis of length ``h``: ``n = max(1, ceil(h / crop))`` windows, the first at 0 and the last at
+    ``h - crop``, origin k at ``(k * (h - crop)) // (n - 1)``; one window at 0 where the axis is no longer than the crop."""
+    h, crop = int(h), int(crop)
+    n = max(1, -(-h // crop))
+    if n == 1:
+        return [0]
+    return [(k * (h - crop)) // (n - 1) for k in range(n)]
+
+
+def grid_windows(hw, crop: int = 256) -> np.ndarray:
+    """(M, 3) int64 rows (image, y0, x0): the windows of ``grid_origins`` of every image, images in order, rows before columns."""
+    rows = [(i, y0, x0) for i, (h, w) in enumerate(np.asarray(hw).reshape(-1, 2))
+            for y0 in grid_origins(h, crop) for x0 in grid_origins(w, crop)]
+    return np.asarray(rows, np.int64).reshape(-1, 3)
+
+
+def grid_crops(pool: ImagePool, crop: int = 256, chunk: int = 64):
+    """The deterministic windows used where nothing is augmented (validation, and training without ``augment``): (uint8
+    (M, crop, crop, 3), int16 (M, crop, crop), windows (M, 3) int64 rows (image, y0, x0)), the first two on the device.  Cut by the
+    pool kernel with integer-translation maps, so every pixel is exact; beyond the image the pixels are 0 and the labels -100,
+    always.  A window without an annotated pixel is dropped.  Cached on the pool for the default arguments."""
+    if crop == 256 and pool._grid is not None:
+        return pool._grid
+    win = grid_windows(pool.hw_host, crop)
+    xs, labs, keep = [], [], []
+    for s in range(0, len(win), chunk):
+        w = win[s:s + chunk]
+        inv = np.zeros((len(w), 6), np.float64)
+        inv[:, 0] = inv[:, 4] = 1.0
+        inv[:, 2], inv[:, 5] = w[:, 2], w[:, 1]
+        x, lab, _status = ops.warp_affine_pool(pool.pool_u8, pool.pool_lab, pool.px_off, pool.hw, w[:, 0], inv, (crop, crop),
+                                               label_fill=-100)
+        k = (lab != -100).flatten(1).any(1)
+        xs.append(x[k].to(torch.uint8).permute(0, 2, 3, 1).contiguous())
+        labs.append(lab[k])
+        keep.append(k.cpu().numpy())
+    res = (torch.cat(xs), torch.cat(labs), win[np.concatenate(keep)])
+    if crop == 256:
+        pool._grid = res
+    return res

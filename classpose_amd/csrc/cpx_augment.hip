@@ -1,6 +1,8 @@
-// Training-time augmentation on gfx950 (t2):
+// Training-time augmentation on gfx950 (t2, t4):
 //   stain jitter of uint8 patches in the HED colour space (HEDTransform.transform)
 //   affine warp of images (bilinear, constant border 0) and class maps (nearest)
+//   the same two fused over a device-resident pool of whole images of any size (t4): the random 256 x 256 window that the
+//   reference's loader cuts out of the whole image every epoch (dataset.py:23-56), one launch per batch
 //   exact percentile normalisation of float32 planes (normalize_img -> normalize99 after the warp)
 // None of these is a throughput kernel: one thread per output pixel, planar stores, LDS histograms.
 // Built with -ffp-contract=off: the warp's coordinates equal numpy's float64 a * x + b * y + c, and the lerps and the
@@ -49,14 +51,9 @@ __global__ void __launch_bounds__(1024) k_hed_decide(const uint8_t *__restrict__
     }
 }
 
-__global__ void k_hed_jitter(const uint8_t *__restrict__ img, const float *__restrict__ sigma, const float *__restrict__ bias,
-                             const int32_t *__restrict__ applied, int HW, int simple_mode, uint8_t *__restrict__ out) {
-    const int p = blockIdx.x * NTHR + threadIdx.x;
-    if (p >= HW) return;
-    const size_t t = blockIdx.y;
-    const uint8_t *px = img + (t * HW + p) * 3;
-    uint8_t *o = out + (t * HW + p) * 3;
-    if (!applied[t]) { o[0] = px[0]; o[1] = px[1]; o[2] = px[2]; return; }
+// HEDTransform.transform of one uint8 pixel with the stain draws sigma[3] / bias[3] of its image
+__device__ __forceinline__ void hed_pixel(const uint8_t *__restrict__ px, const float *__restrict__ sigma,
+                                          const float *__restrict__ bias, int simple_mode, uint8_t *o) {
     float l[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -69,7 +66,7 @@ __global__ void k_hed_jitter(const uint8_t *__restrict__ img, const float *__res
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         float s = l[0] * c_hed_from_rgb[j] + l[1] * c_hed_from_rgb[3 + j] + l[2] * c_hed_from_rgb[6 + j];
-        s = s * (1.0f + sigma[t * 3 + j]) + bias[t * 3 + j];
+        s = s * (1.0f + sigma[j]) + bias[j];
         h[j] = -s;
     }
 #pragma unroll
@@ -83,6 +80,19 @@ __global__ void k_hed_jitter(const uint8_t *__restrict__ img, const float *__res
         x = fminf(fmaxf(x, 0.0f), 1.0f);
         o[c] = (uint8_t)(int)(x * 255.0f);                              // astype(uint8): truncation
     }
+}
+
+__global__ void k_hed_jitter(const uint8_t *__restrict__ img, const float *__restrict__ sigma, const float *__restrict__ bias,
+                             const int32_t *__restrict__ applied, int HW, int simple_mode, uint8_t *__restrict__ out) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= HW) return;
+    const size_t t = blockIdx.y;
+    const uint8_t *px = img + (t * HW + p) * 3;
+    uint8_t *o = out + (t * HW + p) * 3;
+    if (!applied[t]) { o[0] = px[0]; o[1] = px[1]; o[2] = px[2]; return; }
+    uint8_t r[3];
+    hed_pixel(px, sigma + t * 3, bias + t * 3, simple_mode, r);
+    o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
 }
 
 extern "C" int cpx_hed_jitter_u8(const uint8_t *img, int n, int H, int W, const float *sigma, const float *bias,
@@ -167,6 +177,157 @@ extern "C" int cpx_warp_affine_f32(const float *src, const int16_t *labels, int 
                                    int dh, int dw, int label_fill, float *out, int16_t *labels_out, void *stream) {
     CPX_REQUIRE((const void *)src != (const void *)out);
     return warp_launch<false>(src, labels, n, sh, sw, inv, dh, dw, label_fill, out, labels_out, stream);
+}
+
+// ---------------------------------------------------------------------------
+// ragged image pool (t4): whole annotated images of any size, packed back to back
+// ---------------------------------------------------------------------------
+// image i: pool_u8 + 3 * px_off[i], hw[i] = {h, w}; a table entry that does not lie inside the pool's pool_px pixels is never read
+__device__ __forceinline__ bool pool_entry_ok(long long off, int h, int w, long long pool_px) {
+    return off >= 0 && h > 0 && w > 0 && off <= pool_px && (long long)h * w <= pool_px - off;
+}
+
+// one workgroup per image: the exact integer sum of its bytes (what k_hed_decide forms per patch)
+__global__ void __launch_bounds__(1024) k_pool_byte_sums(const uint8_t *__restrict__ pool, const int64_t *__restrict__ px_off,
+                                                         const int32_t *__restrict__ hw, long long pool_px,
+                                                         unsigned long long *__restrict__ sums, int32_t *__restrict__ status) {
+    __shared__ unsigned long long part[16];
+    const int i = blockIdx.x;
+    const long long off = px_off[i];
+    const int h = hw[2 * i], w = hw[2 * i + 1];
+    if (!pool_entry_ok(off, h, w, pool_px)) {                           // uniform over the workgroup
+        if (threadIdx.x == 0) { sums[i] = 0; atomicOr(status, 2); }
+        return;
+    }
+    const uint8_t *p = pool + 3 * off;
+    const long long count = 3ll * h * w;
+    unsigned long long s = 0;
+    // 3 * px_off is odd for many sizes: bytes up to the first 16-byte boundary, then 16 per load, then the tail
+    const long long head = min(count, (long long)((16 - ((uintptr_t)p & 15)) & 15));
+    const long long nvec = (count - head) / 16;
+    const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
+    for (long long k = threadIdx.x; k < head; k += 1024) s += p[k];
+    for (long long k = threadIdx.x; k < nvec; k += 1024) {
+        const uint4 q = v[k];
+        s += byte_sum(q.x) + byte_sum(q.y) + byte_sum(q.z) + byte_sum(q.w);
+    }
+    for (long long k = head + nvec * 16 + threadIdx.x; k < count; k += 1024) s += p[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        for (int k = 0; k < 16; ++k) tot += part[k];
+        sums[i] = tot;
+    }
+}
+
+extern "C" int cpx_pool_byte_sums(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                                  uint64_t *sums, int32_t *status, void *stream) {
+    CPX_REQUIRE(pool_u8 && px_off && hw && sums && status && nI > 0 && pool_px > 0);
+    hipStream_t s = (hipStream_t)stream;
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_pool_byte_sums, dim3(nI), dim3(1024), 0, s, pool_u8, px_off, hw, pool_px,
+                       reinterpret_cast<unsigned long long *>(sums), status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// one tap of crop t's source: 0 outside it; inside, the pixel's three channels, through hed_pixel when the crop's image is jittered
+template <bool JIT>
+__device__ __forceinline__ void pool_tap(const uint8_t *__restrict__ img, int sh, int sw, int y, int x, const float *sigma,
+                                         const float *bias, int simple_mode, float *v) {
+    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) { v[0] = v[1] = v[2] = 0.f; return; }
+    const uint8_t *px = img + ((long long)y * sw + x) * 3;
+    uint8_t r[3] = {px[0], px[1], px[2]};
+    if (JIT) hed_pixel(px, sigma, bias, simple_mode, r);
+    v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
+}
+
+// k_warp_affine<true> with a source per crop, image_of[t] of the pool, and k_hed_jitter folded into the taps: jitter(tap) of an
+// in-source tap, 0 (not jitter(0)) outside -- bitwise the jitter of the whole image followed by the warp
+__global__ void k_warp_affine_pool(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
+                                   const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI, long long pool_px,
+                                   const int32_t *__restrict__ image_of, const double *__restrict__ inv,
+                                   const float *__restrict__ sigma, const float *__restrict__ bias,
+                                   const int32_t *__restrict__ applied, int simple_mode, int dh, int dw, int label_fill,
+                                   float *__restrict__ out, int16_t *__restrict__ lab_out, int32_t *__restrict__ status) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= dh * dw) return;
+    const size_t t = blockIdx.y;
+    const size_t plane = (size_t)dh * dw;
+    const int im = image_of[t];
+    int bad = 0, sh = 0, sw = 0;
+    long long off = 0;
+    if (im < 0 || im >= nI) bad = 1;
+    else {
+        off = px_off[im]; sh = hw[2 * im]; sw = hw[2 * im + 1];
+        if (!pool_entry_ok(off, sh, sw, pool_px)) bad = 2;
+    }
+    if (bad) {                                                          // nothing of the pool is read for this crop
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = 0.f;
+        if (lab_out) lab_out[t * plane + p] = (int16_t)label_fill;
+        if (p == 0) atomicOr(status, bad);
+        return;
+    }
+    const uint8_t *img = pool + 3 * off;
+    const int y = p / dw, x = p - y * dw;
+    const double *m = inv + t * 6;
+    const double sx = m[0] * (double)x + m[1] * (double)y + m[2];
+    const double sy = m[3] * (double)x + m[4] * (double)y + m[5];
+    float v[3] = {0.f, 0.f, 0.f};
+    if (sx >= -1.0 && sx < (double)sw && sy >= -1.0 && sy < (double)sh) {
+        const double fx = floor(sx), fy = floor(sy);
+        const int x0 = (int)fx, y0 = (int)fy;
+        const float wx = (float)(sx - fx), wy = (float)(sy - fy);
+        float a[3], b[3], d[3], e[3];
+        if (sigma && applied[t]) {
+            const float *sg = sigma + t * 3, *bs = bias + t * 3;
+            pool_tap<true>(img, sh, sw, y0, x0, sg, bs, simple_mode, a);
+            pool_tap<true>(img, sh, sw, y0, x0 + 1, sg, bs, simple_mode, b);
+            pool_tap<true>(img, sh, sw, y0 + 1, x0, sg, bs, simple_mode, d);
+            pool_tap<true>(img, sh, sw, y0 + 1, x0 + 1, sg, bs, simple_mode, e);
+        } else {
+            pool_tap<false>(img, sh, sw, y0, x0, nullptr, nullptr, 0, a);
+            pool_tap<false>(img, sh, sw, y0, x0 + 1, nullptr, nullptr, 0, b);
+            pool_tap<false>(img, sh, sw, y0 + 1, x0, nullptr, nullptr, 0, d);
+            pool_tap<false>(img, sh, sw, y0 + 1, x0 + 1, nullptr, nullptr, 0, e);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float top = a[c] + (b[c] - a[c]) * wx;
+            const float bot = d[c] + (e[c] - d[c]) * wx;
+            v[c] = top + (bot - top) * wy;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
+    if (lab_out) {
+        int r = label_fill;
+        const double nx = floor(sx + 0.5), ny = floor(sy + 0.5);
+        if (nx >= 0.0 && nx < (double)sw && ny >= 0.0 && ny < (double)sh) r = pool_lab[off + (long long)(int)ny * sw + (int)nx];
+        lab_out[t * plane + p] = (int16_t)r;
+    }
+}
+
+extern "C" int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw,
+                                       int nI, long long pool_px, const int32_t *image_of, const double *inv, int n,
+                                       const float *sigma, const float *bias, const int32_t *applied, int simple_mode, int dh,
+                                       int dw, int label_fill, float *out, int16_t *labels_out, int32_t *status, void *stream) {
+    CPX_REQUIRE(pool_u8 && px_off && hw && image_of && inv && out && status && nI > 0 && pool_px > 0);
+    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
+    CPX_REQUIRE((pool_lab == nullptr) == (labels_out == nullptr));
+    CPX_REQUIRE((sigma == nullptr) == (bias == nullptr) && (sigma == nullptr) == (applied == nullptr));
+    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
+    hipStream_t s = (hipStream_t)stream;
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_warp_affine_pool, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
+                       px_off, hw, nI, pool_px, image_of, inv, sigma, bias, applied, simple_mode ? 1 : 0, dh, dw, label_fill, out,
+                       labels_out, status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
 }
 
 // ---------------------------------------------------------------------------

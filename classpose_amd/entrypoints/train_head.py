@@ -5,6 +5,8 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
         --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
         [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1]
+    python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
+        [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
 Images are ``(N, 256, 256, 3)`` uint8 (normalised per crop like inference does) or ``(N, 3, 256, 256)`` float32 (already
 normalised); labels ``(N, 256, 256)`` integer class maps with -100 where nothing is annotated.  The result is an ordinary
@@ -15,6 +17,13 @@ With ``--instances`` (``(N, 256, 256)`` integer instance maps aligned with ``--l
 oversampling probabilities (``--oversampling_method custom``), cell diameters (``--rescale``) and mask counts
 (``--min_train_masks``).  The reference's ``run_training.py`` has class weights and ``custom`` oversampling ON by default; here all
 four are opt-in, so that a command line without them trains exactly as before.
+
+``--data_path`` is the reference's data directory instead of the three arrays: ``images.npy`` with ``(H, W, 3)`` images of ANY size
+(an object array when they differ) and ``labels.npy`` with ``(H, W, 2)`` maps, channel 0 = instance, channel 1 = class
+(``classpose_amd.train_data``).  The images go to the device once (``augment.ImagePool``); with ``--augment`` every draw of an epoch
+is a fresh random 256 x 256 window of a whole image, without it training runs on a fixed grid of windows, and validation always
+does.  Without ``--test_data_path`` the directory is split by ``--train_fraction`` as the reference splits it.  The class count is
+inferred from the labels, and the four options above work from channel 0 without ``--instances``.
 """
 from __future__ import annotations
 
@@ -29,8 +38,15 @@ logger = get_logger(__name__)
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Train the 1x1 semantic class head on the device with the backbone frozen")
-    p.add_argument("--images", required=True, help=".npy, (N,256,256,3) uint8 or (N,3,256,256) float32")
-    p.add_argument("--labels", required=True, help=".npy, (N,256,256) integer class maps, -100 = not annotated")
+    p.add_argument("--images", default=None, help=".npy, (N,256,256,3) uint8 or (N,3,256,256) float32 (with --labels; or --data_path)")
+    p.add_argument("--labels", default=None, help=".npy, (N,256,256) integer class maps, -100 = not annotated")
+    p.add_argument("--data_path", default=None,
+                   help="directory with images.npy ((H,W,3) images of any size) and labels.npy ((H,W,2): instance, class), the "
+                        "reference's layout; instead of --images / --labels / --instances")
+    p.add_argument("--test_data_path", default=None, help="validation directory of the same layout (with --data_path)")
+    p.add_argument("--train_fraction", type=float, default=0.8,
+                   help="with --data_path and no --test_data_path: the share of the images that trains, the rest validates; 1 = no validation")
+    p.add_argument("--subsample_fraction", type=float, default=None, help="with --data_path: train from a random share of the images")
     p.add_argument("--test_images", default=None)
     p.add_argument("--test_labels", default=None)
     p.add_argument("--pretrained_model", required=True, help="checkpoint (state dict) to adapt")
@@ -76,6 +92,23 @@ def build_parser() -> argparse.ArgumentParser:
 
 def check_args(args) -> None:
     """The combinations the parser cannot express; raises ``SystemExit`` with the reason."""
+    if args.data_path is not None:
+        given = [f for f, v in (("--images", args.images), ("--labels", args.labels), ("--instances", args.instances),
+                                ("--test_images", args.test_images), ("--test_labels", args.test_labels),
+                                ("--test_instances", args.test_instances)) if v is not None]
+        if given:
+            raise SystemExit(f"--data_path replaces {', '.join(given)}: give one or the other")
+        if not 0.0 < args.train_fraction <= 1.0:
+            raise SystemExit("--train_fraction must lie in (0, 1]")
+        if args.subsample_fraction is not None and not 0.0 < args.subsample_fraction <= 1.0:
+            raise SystemExit("--subsample_fraction must lie in (0, 1]")
+        if args.rescale and args.augment is None:
+            raise SystemExit("--rescale divides the random scale of the augmentation: it needs --augment")
+        return
+    if args.images is None or args.labels is None:
+        raise SystemExit("give --images and --labels, or --data_path")
+    if args.test_data_path is not None or args.subsample_fraction is not None:
+        raise SystemExit("--test_data_path and --subsample_fraction go with --data_path")
     if (args.test_images is None) != (args.test_labels is None):
         raise SystemExit("--test_images and --test_labels go together")
     needs = [flag for flag, on in (("--auto_class_weights", args.auto_class_weights),
@@ -97,10 +130,73 @@ def _load_instances(path, labels, what: str) -> np.ndarray:
     return inst
 
 
+def main_data_path(args) -> None:
+    """``--data_path``: whole annotated images of any size, from the reference's directory to a device pool."""
+    from .. import augment, dataset_stats, train_data
+    from ..train import HeadTrainer, train_class_head
+    data = train_data.load_dataset(args.data_path)
+    logger.info(f"{args.data_path}: {len(data)} images, inferred number of classes: {data.n_classes}")
+    data = data.subset(train_data.subsample_indices(len(data), args.subsample_fraction, args.random_seed))
+    if args.test_data_path is not None:
+        test = train_data.load_dataset(args.test_data_path)
+    else:
+        tr, te = train_data.split_indices(len(data), args.train_fraction, args.random_seed)
+        data, test = data.subset(tr), (None if te is None or len(te) == 0 else data.subset(te))
+    logger.info(f"{len(data)} training images, {len(test) if test is not None else 0} validation images")
+    nclasses = data.n_classes if args.nclasses is None else args.nclasses
+    trainer = HeadTrainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
+                          class_weights=args.class_weights, weight_decay=args.weight_decay)
+    if data.n_classes > trainer.nclasses:
+        raise SystemExit(f"the labels hold class {data.n_classes - 1} but the head has {trainer.nclasses} classes")
+    train_probs = diameters = None
+    if args.auto_class_weights or args.oversampling_method != "none" or args.rescale or args.min_train_masks > 0:
+        stats = train_data.ragged_label_stats(data.instances, data.classes, trainer.nclasses, device=args.device)
+        diameters = dataset_stats.clamp_diameters(stats.diameters)
+        logger.info(f"diameters: {diameters.min():.2f} to {diameters.max():.2f} px, masks per image: {int(stats.n_masks.min())} to "
+                    f"{int(stats.n_masks.max())}")
+        if args.min_train_masks > 0:
+            keep = np.nonzero(stats.n_masks >= args.min_train_masks)[0]
+            if len(keep) < len(data):
+                logger.warning(f"{len(data) - len(keep)} train images with number of masks less than min_train_masks "
+                               f"({args.min_train_masks}), removing from train set")
+                if len(keep) == 0:
+                    raise SystemExit("--min_train_masks leaves no training image")
+                data, diameters = data.subset(keep), diameters[keep]
+                stats = dataset_stats.LabelStats(stats.class_counts, stats.instance_counts[keep], stats.n_masks[keep],
+                                                 stats.diameters[keep])
+        if args.auto_class_weights:
+            logger.info("Computing class weights using inverse frequency with square root scaling")
+            weights = dataset_stats.get_class_weights(stats.class_counts)
+            logger.info(f"class weights = {weights.tolist()}")
+            trainer.set_class_weights(weights)
+        if args.oversampling_method == "custom":
+            logger.info(f"Computing oversampling probabilities with power {args.oversampling_power}")
+            train_probs = dataset_stats.compute_oversampling_probabilities(stats.class_counts, stats.instance_counts,
+                                                                           args.oversampling_power)
+            if not np.all(np.isfinite(train_probs)):
+                raise SystemExit("--oversampling_method custom: the training set has no instance of a class above 0")
+            logger.info(f"Custom oversampling - probability range: {train_probs.min():.6f} to {train_probs.max():.6f}")
+    pool = augment.ImagePool(data.images, data.classes, diameters if args.rescale else None, device=args.device)
+    test_pool = None if test is None else augment.ImagePool(test.images, test.classes, device=args.device)
+    logger.info(f"image pool: {pool.nbytes / 2 ** 20:.1f} MB on the device for {len(pool)} images")
+    path, train_losses, test_losses = train_class_head(
+        trainer, pool, None, test_pool, None, batch_size=args.batch_size, n_epochs=args.n_epochs,
+        learning_rate=args.learning_rate, nimg_per_epoch=args.nimg_per_epoch, cache_features=args.cache_features,
+        save_path=args.save_path, model_name=args.model_name, random_seed=args.random_seed,
+        augment=args.augment, scale_range=args.scale_range, label_fill=args.augment_label_fill, train_probs=train_probs,
+        diam_mean=args.diam_mean, rescale=args.rescale)
+    if args.save_only_trainable_params:
+        trainer.save(path, save_only_trainable_params=True)
+    logger.info(f"final train loss {train_losses[-1]:.4f}" + (f", test loss {test_losses[-1]:.4f}" if test_pool is not None else ""))
+    print(path)
+
+
 def main(args) -> None:
     from .. import dataset_stats
     from ..train import HeadTrainer, train_class_head
     check_args(args)
+    if args.data_path is not None:
+        return main_data_path(args)
     images, labels = np.load(args.images), np.load(args.labels)
     test_images = np.load(args.test_images) if args.test_images else None
     test_labels = np.load(args.test_labels) if args.test_labels else None

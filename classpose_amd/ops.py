@@ -653,6 +653,74 @@ def warp_affine(src: torch.Tensor, inv, out_hw, labels: torch.Tensor | None = No
     return out, lab_out
 
 
+def _pool_table(pool_u8, px_off, hw, what: str):
+    if pool_u8.dtype != torch.uint8 or pool_u8.dim() != 1 or pool_u8.numel() % 3 or not pool_u8.is_contiguous() or not pool_u8.is_cuda:
+        raise ValueError(f"{what}: pool_u8 is a contiguous uint8 device vector of 3 bytes per pixel")
+    dev = pool_u8.device
+    nI = px_off.numel()
+    if px_off.dtype != torch.int64 or px_off.dim() != 1 or nI == 0 or px_off.device != dev or not px_off.is_contiguous():
+        raise ValueError(f"{what}: px_off is int64 (nI,) on the pool's device")
+    if hw.dtype != torch.int32 or hw.shape != (nI, 2) or hw.device != dev or not hw.is_contiguous():
+        raise ValueError(f"{what}: hw is int32 (nI, 2) on the pool's device")
+    return dev, nI, pool_u8.numel() // 3
+
+
+def pool_byte_sums(pool_u8: torch.Tensor, px_off: torch.Tensor, hw: torch.Tensor) -> torch.Tensor:
+    """Exact integer byte sum of every image of a ragged pool (``cpx_pool_byte_sums``): pool_u8 the images packed back to back as
+    (h_i, w_i, 3) uint8, px_off (nI,) int64 pixel offsets, hw (nI, 2) int32.  Returns int64 (nI,) on the device; raises ``ValueError``
+    when a table entry does not lie inside the pool (nothing is read through it)."""
+    dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "pool_byte_sums")
+    sums = torch.empty(nI, dtype=torch.int64, device=dev)                     # a sum is below 2^63: the uint64 of the kernel, as int64
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(_lib.lib().cpx_pool_byte_sums(ptr(pool_u8), ptr(px_off), ptr(hw), nI, pool_px, ptr(sums), ptr(status), _stream(dev)),
+          "pool_byte_sums")
+    if int(status.item()):
+        raise ValueError("pool_byte_sums: an image of the table lies outside the pool")
+    return sums
+
+
+def warp_affine_pool(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None, px_off: torch.Tensor, hw: torch.Tensor, image_of, inv,
+                     out_hw, sigma=None, bias=None, applied=None, simple_mode: bool = False, label_fill: int = 0,
+                     check_status: bool = True):
+    """``cpx_warp_affine_pool_u8``: crop t is ``warp_affine`` of image ``image_of[t]`` of the pool by ``inv[t]``; with ``sigma`` / ``bias``
+    (n, 3) float32 and ``applied`` (n,) int32, all per crop, the stain jitter of ``hed_jitter`` is applied to the in-source taps of the
+    crops with ``applied != 0`` -- bitwise ``hed_jitter`` of the whole image, then ``warp_affine``.  pool_lab: int16 class maps at the
+    pool's pixel offsets, or None.  Returns (float32 (n, 3, dh, dw), int16 (n, dh, dw) or None, int32 (1,) status: bit 0 an
+    ``image_of`` outside the pool's images, bit 1 a table entry outside the pool; such crops are zeros / ``label_fill``).
+    ``check_status`` raises ``ValueError`` on a non-zero status."""
+    dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "warp_affine_pool")
+    dh, dw = (int(v) for v in out_hw)
+    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
+    n = image_of.numel()
+    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
+    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
+    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6):
+        raise ValueError("warp_affine_pool: image_of is (n,) and inv (n, 6) float64")
+    if (sigma is None) != (bias is None) or (sigma is None) != (applied is None):
+        raise ValueError("warp_affine_pool: sigma, bias and applied go together")
+    if sigma is not None:
+        sigma = torch.as_tensor(sigma, dtype=torch.float32).to(dev).contiguous()
+        bias = torch.as_tensor(bias, dtype=torch.float32).to(dev).contiguous()
+        applied = torch.as_tensor(applied).to(device=dev, dtype=torch.int32).contiguous()
+        if sigma.shape != (n, 3) or bias.shape != (n, 3) or applied.shape != (n,):
+            raise ValueError("warp_affine_pool: sigma and bias are (n, 3), applied (n,)")
+    lab_out = None
+    if pool_lab is not None:
+        if pool_lab.dtype != torch.int16 or pool_lab.shape != (pool_px,) or pool_lab.device != dev or not pool_lab.is_contiguous():
+            raise ValueError("warp_affine_pool: pool_lab is a contiguous int16 vector of one label per pool pixel on the pool's device")
+        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
+    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(_lib.lib().cpx_warp_affine_pool_u8(ptr(pool_u8), ptr(pool_lab), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv), n,
+                                             ptr(sigma), ptr(bias), ptr(applied), int(bool(simple_mode)), dh, dw, int(label_fill),
+                                             ptr(out), ptr(lab_out), ptr(status), _stream(dev)), "warp_affine_pool_u8")
+    if check_status:
+        bits = int(status.item())
+        if bits:
+            raise ValueError("warp_affine_pool: " + ("an image index outside the pool" if bits & 1 else "a table entry outside the pool"))
+    return out, lab_out, status
+
+
 def normalize_stats_f32(x: torch.Tensor) -> torch.Tensor:
     """(n, 3, 4) float32 {x01, x99 - x01, mode, x99} of float32 (n, 3, H, W) planes: np.percentile(plane, [1, 99]) exactly."""
     if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():

@@ -268,6 +268,31 @@ def _check_dataset(images, labels, what: str):
     return images, labels
 
 
+def _pool_annotated(pool, what: str) -> None:
+    empty = np.flatnonzero(~pool.annotated)
+    if len(empty):
+        raise ValueError(f"{what} image {int(empty[0])} has no annotated pixel (every label is -100): drop it")
+
+
+def _pool_training_set(pool, labels, transform, augment, train_probs, diameters):
+    """What ``train_class_head`` trains on when it is handed an ``ImagePool``: with ``augment`` the pool itself, else its cached grid
+    crops as device arrays.  Returns ``(images, labels, pool or None, train_probs, diameters)``."""
+    if labels is not None:
+        raise ValueError("an ImagePool carries its own class maps: pass labels=None")
+    if transform is not None:
+        raise ValueError("transform is a host callback on crops: an ImagePool has none to hand it")
+    _pool_annotated(pool, "training")
+    if augment is not None:
+        return None, None, pool, train_probs, pool.diameters if diameters is None else diameters
+    x, y, win = _augment.grid_crops(pool)
+    if train_probs is not None:
+        train_probs = np.asarray(train_probs, dtype=np.float64)
+        if train_probs.shape != (len(pool),):
+            raise ValueError("train_probs must have the same length as the dataset")
+        train_probs = train_probs[win[:, 0]]
+    return x, y, None, train_probs, None
+
+
 def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, test_labels=None, batch_size: int = 8,
                      n_epochs: int = 100, learning_rate: float = 5e-5, nimg_per_epoch: int | None = None, cache_features: bool = True,
                      save_path=None, model_name: str | None = None, random_seed: int = 42, transform=None,
@@ -287,12 +312,27 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     p=train_probs)``, the oversampling draw of dataset.py:597-601.  ``rescale=True`` divides the random scale of every augmented
     crop by ``diameters[i] / diam_mean`` (dataset.py:35-45): it needs ``augment`` and ``diameters`` (one per image, e.g.
     ``dataset_stats.clamp_diameters(label_stats(...).diameters)``).  With the defaults neither changes anything.
+    ``images`` may be an ``augment.ImagePool`` of whole annotated images of any size (then ``labels`` is None; likewise the
+    validation set).  The epoch's order is then drawn over the IMAGES and every draw is one fresh 256 x 256 window of its image
+    (dataset.py:23-56): with ``augment`` the batches come from ``augment.augment_batch_pool``, ``train_probs`` / ``diameters`` are
+    per image (``diameters`` defaults to the pool's), and ``transform`` is refused (there is no host crop to hand it).  Without
+    ``augment`` the training set is the pool's cached ``augment.grid_crops``, one entry per window (``train_probs`` of an image go
+    to each of its windows); validation always runs on the cached grid crops of its pool.  Array inputs behave as before.
     Returns ``(path of the final model, train_losses, test_losses)``."""
-    images, labels = _check_dataset(images, labels, "training")
+    pool = None
+    if isinstance(images, _augment.ImagePool):
+        images, labels, pool, train_probs, diameters = _pool_training_set(images, labels, transform, augment, train_probs, diameters)
+    else:
+        images, labels = _check_dataset(images, labels, "training")
     has_test = test_images is not None
-    if has_test:
+    if has_test and isinstance(test_images, _augment.ImagePool):
+        if test_labels is not None:
+            raise ValueError("a validation ImagePool carries its own class maps: pass test_labels=None")
+        _pool_annotated(test_images, "validation")
+        test_images, test_labels, _win = _augment.grid_crops(test_images)
+    elif has_test:
         test_images, test_labels = _check_dataset(test_images, test_labels, "validation")
-    nimg = len(images)
+    nimg = len(pool) if pool is not None else len(images)
     nimg_per_epoch = nimg if nimg_per_epoch is None else int(nimg_per_epoch)
     if train_probs is not None:
         train_probs = np.asarray(train_probs, dtype=np.float64)
@@ -320,7 +360,7 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     filename = model_dir / model_name
     if augment is not None and augment != "geometry":
         _augment.get_config(augment)                       # unknown names and "enhanced" raise before anything is computed
-    cached = cache_features and transform is None and augment is None
+    cached = cache_features and transform is None and augment is None        # a pool without augment trains on its grid crops
     test_cached = cached or (cache_features and augment is not None)
     dev = trainer.device
     lab_dev = test_lab_dev = feats = test_feats = None
@@ -348,6 +388,9 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
             if cached:
                 ti = torch.from_numpy(idx).to(dev)
                 x, y = feats[ti].reshape(-1, 256), lab_dev[ti]
+            elif pool is not None:
+                x, y = _augment.augment_batch_pool(pool, idx, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
+                                                   dtype=trainer.dtype, out=CROP, rescale=None if rsc is None else rsc[idx])
             else:
                 x, y = images[idx], labels[idx]
                 if transform is not None:

@@ -578,6 +578,36 @@ int cpx_label_stats(const int32_t *inst, const int16_t *cls, int nI, int H, int 
                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * t4  training windows from a device-resident pool of whole annotated images of any size (csrc/cpx_augment.hip)
+ * replaces what ClassposeDataset.__getitem__ -> augment_single_image (classpose/dataset.py:23-56 of the reference) does to the
+ * WHOLE image of a draw: the HEDTransform call with its cut-off test on the whole image's mean (:41) and the
+ * random_rotate_and_resize window (:42-48), without an upload per step or a launch per source shape.
+ * Pool layout: pool_u8 holds the images back to back as [h_i][w_i][3] uint8 without padding, pool_lab int16 class maps at the same
+ * pixel offsets, px_off [nI] int64 the pixel offset of image i (its bytes start at 3 * px_off[i], an odd address for many
+ * sizes: nothing assumes alignment), hw [nI][2] int32 {h_i, w_i}, pool_px the pixels of the whole pool.  A table entry that does
+ * not lie inside [0, pool_px) is never dereferenced: status bit 1 is set instead.  status is ONE int32 word that the entry clears
+ * first.  Both entries run on `stream` and allocate nothing.
+ * ---------------------------------------------------------------------- */
+/* cpx_pool_byte_sums: sums [nI] uint64, the exact integer sum of the bytes of each image -- the numerator of the stain jitter's
+ *   cut-off test lo <= (sum / count) / 255.0 <= hi (cpx_hed_jitter_u8), which the reference applies to the whole image.  A
+ *   per-image constant: computed once per pool.  0 and status bit 1 for an entry outside the pool.                          */
+int cpx_pool_byte_sums(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                       uint64_t *sums, int32_t *status, void *stream);
+
+/* cpx_warp_affine_pool_u8: crop t is cpx_warp_affine_u8 of image image_of[t] of the pool by the inverse map inv[t][6] -- the
+ *   coordinates, the four taps, the three lerps and the nearest-label rule are those of cpx_warp_affine_u8, operation for
+ *   operation.  out [n][3][dh][dw] float32, labels_out [n][dh][dw] int16 (NULL exactly when pool_lab is NULL).
+ *   sigma / bias [n][3] float32 and applied [n] int32 (all three or none; NULL = no stain jitter) are per CROP: where
+ *   applied[t] != 0 every tap INSIDE the source goes through the per-pixel function of cpx_hed_jitter_u8 (simple_mode as
+ *   there) before the interpolation; a tap outside the source is 0, not jitter(0).  That is bitwise cpx_hed_jitter_u8 of the
+ *   whole image followed by cpx_warp_affine_u8, at four jitter evaluations per output pixel instead of one per source pixel.
+ *   An image_of[t] outside [0, nI) is never dereferenced: the crop is zeros / label_fill and status bit 0 is set.          */
+int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw, int nI,
+                            long long pool_px, const int32_t *image_of, const double *inv, int n, const float *sigma,
+                            const float *bias, const int32_t *applied, int simple_mode, int dh, int dw, int label_fill,
+                            float *out, int16_t *labels_out, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
  * replaces, per instance, cv2.findContours(cell_mask, RETR_EXTERNAL,
  * CHAIN_APPROX_SIMPLE)[0] + shapely.Polygon(...).is_valid/.centroid/.area/.length
