@@ -160,6 +160,11 @@ SIGNATURES = {
     "cpx_label_stats": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cpx_pool_byte_sums": (_i, [_p, _p, _p, _i, C.c_longlong, _p, _p, _p]),
     "cpx_warp_affine_pool_u8": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "cpx_stain_samples_workspace_bytes": (_sz, [_i, C.c_longlong]),
+    "cpx_stain_samples": (_i, [_p, _p, _p, _i, C.c_longlong, _p, _d, _p, C.c_longlong, _p, _p, _p, _p, _sz, _p]),
+    "cpx_he_stain_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "cpx_warp_affine_pool_stain_u8": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _p, _p, _i, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p,
+                                           _p, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),

@@ -13,8 +13,13 @@ Whole annotated images of any size live in an ``ImagePool``: uploade
 jitter on the taps, the warp) -- the fresh random window per epoch of dataset.py:23-56.  ``grid_crops`` are the deterministic
 windows used where nothing is augmented.
 
+The H&E stain-matrix perturbation (configurations ``he_staining`` and ``hed_he``) re-renders every crop from its image's
+own two-stain basis: the basis is fitted once per image on the host (``stain.stain_basis`` on the samples of ``ops.stain_samples``,
+cached on the ``ImagePool``), the draws perturb it, and the pixels go through ``ops.he_stain`` or, on a pool, through the taps of
+``ops.warp_affine_pool_stain``.
+
 Still different from the reference: the warp samples at exact double-precision source coordinates (OpenCV quantises them to
-1 / 32 pixel) and the ``enhanced`` pipeline is not built.  The rescale by cell diameter (dataset.py:35-45) is the ``rescale``
+1 / 32 pixel) and the ``enhanced`` pipeline is not built (its Gaussian blur and hue / brightness / saturation jitter are missing).  The rescale by cell diameter (dataset.py:35-45) is the ``rescale``
 argument of the samplers: per crop ``diameter / diam_mean``, the diameters from ``dataset_stats.label_stats``.
 """
 from __future__ import annotations
@@ -24,7 +29,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, stain
+from .stain import stain_basis  # noqa: F401  (augment.stain_basis: the two-stain basis of an image from its samples)
 
 # float32 stain matrices of transforms/hed.py:11-14: RGB_FROM_HED as written there, HED_FROM_RGB = float32(scipy.linalg.inv(RGB_FROM_HED))
 # (the nine values of tests/golden/reference_augment.npz; the kernel carries the same literals)
@@ -42,6 +48,19 @@ AUGMENT_CONFIGS = {
         "cutoff_range": (0.15, 0.85),
         "simple_mode": False,
     },
+    # augmentation_configs.py:36-46 (he_staining_config, hed_probability of ENHANCED_CONFIG), under names of their own:
+    # the stain-matrix perturbation alone, and the colour stage of `enhanced` (per image the HED jitter or the perturbation)
+    "he_staining": {
+        "he_staining": {"amount_matrix": 0.15, "amount_stains": 0.4, "probability": 0.9},
+    },
+    "hed_he": {
+        "sigma_ranges": [(-_HED_VALUE, _HED_VALUE)] * 3,
+        "bias_ranges": [(-_HED_VALUE, _HED_VALUE)] * 3,
+        "cutoff_range": (0.15, 0.85),
+        "simple_mode": False,
+        "hed_probability": 0.5,
+        "he_staining": {"amount_matrix": 0.15, "amount_stains": 0.4, "probability": 0.9},
+    },
 }
 MAX_RESAMPLE = 8
 
@@ -51,8 +70,8 @@ def get_config(name: str | None) -> dict | None:
     if name is None or name == "geometry":
         return None
     if name == "enhanced":
-        raise NotImplementedError("the 'enhanced' augmentation is not built: it needs the H&E stain-matrix perturbation, Gaussian "
-                                  "blur, additive noise and the hue / brightness / saturation jitter")
+        raise NotImplementedError("the 'enhanced' augmentation is not built: its colour stage is 'hed_he', but the Gaussian blur and "
+                                  "the hue / brightness / saturation jitter that follow it are missing")
     if name not in AUGMENT_CONFIGS:
         raise ValueError(f"unknown augmentation {name!r}: one of {sorted(AUGMENT_CONFIGS) + ['geometry']}")
     return AUGMENT_CONFIGS[name]
@@ -165,38 +184,145 @@ def sample_hed(rng: np.random.Generator, n: int, sigma_ranges, bias_ranges):
     return u[:, 0].astype(np.float32), u[:, 1].astype(np.float32)
 
 
+def _has_hed(config: dict | None) -> bool:
+    return config is not None and "sigma_ranges" in config
+
+
+def _has_he(config: dict | None) -> bool:
+    return config is not None and "he_staining" in config
+
+
+def sample_he(rng: np.random.Generator, n: int):
+    """(u_gate (n,), U (n, 2, 3), u (n, 2)) float64 of the stain perturbation: ``rng.random(n)`` for the probability gate, then
+    ``rng.uniform(-1, 1, (n, 2, 3))`` for the stain matrix, then ``rng.uniform(-1, 1, (n, 2))`` for the two concentrations -- the
+    order of ``HEStainingTransform.transform`` / ``augment_stains``.  All three are drawn for every crop, whatever the gate decides
+    (the reference draws nothing for a skipped image, and draws from a legacy ``RandomState`` seeded per image)."""
+    return rng.random(n), rng.uniform(-1.0, 1.0, size=(n, 2, 3)), rng.uniform(-1.0, 1.0, size=(n, 2))
+
+
+@dataclass
+class StainBases:
+    """The two-stain bases of a set of images: H (n, 2, 3), Hinv (n, 3, 2) float64, ok (n,) bool -- False where the fit gave no
+    finite basis and the image stays unaugmented (its rows are zeros)."""
+    H: np.ndarray
+    Hinv: np.ndarray
+    ok: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.ok)
+
+    def take(self, idx) -> "StainBases":
+        idx = np.asarray(idx, np.int64)
+        return StainBases(self.H[idx], self.Hinv[idx], self.ok[idx])
+
+    @classmethod
+    def from_samples(cls, samples) -> "StainBases":
+        """One ``stain.stain_basis`` per entry of ``samples`` (each (m, 3) uint8)."""
+        n = len(samples)
+        H, Hinv, ok = np.zeros((n, 2, 3)), np.zeros((n, 3, 2)), np.zeros(n, bool)
+        for i, smp in enumerate(samples):
+            h, hinv = stain.stain_basis(smp)
+            if h is not None:
+                H[i], Hinv[i], ok[i] = h, hinv, True
+        return cls(H, Hinv, ok)
+
+
+def stain_bases_of(X, device=None, chunk: int = 64) -> StainBases:
+    """The stain bases of uint8 crops (n, H, W, 3), numpy or torch: the samples come from ``ops.stain_samples`` (the crops as a
+    pool of equal-sized images, ``chunk`` at a time), the fit runs on the host.  Once per training set."""
+    if isinstance(X, np.ndarray):
+        X = torch.from_numpy(np.ascontiguousarray(X))
+    if X.dtype != torch.uint8 or X.dim() != 4 or X.shape[3] != 3:
+        raise ValueError("stain_bases_of: crops must be uint8 (n, H, W, 3)")
+    dev = torch.device(device) if device is not None else (X.device if X.is_cuda else torch.device("cuda"))
+    samples = []
+    for s in range(0, X.shape[0], chunk):
+        x = X[s:s + chunk].to(dev).contiguous()
+        px_off, hw, _px = pool_table([(x.shape[1], x.shape[2])] * x.shape[0])
+        _k, smp, _st, _raw = ops.stain_samples(x.view(-1), torch.from_numpy(px_off).to(dev), torch.from_numpy(hw).to(dev))
+        samples += smp
+    return StainBases.from_samples(samples)
+
+
 @dataclass
 class BatchParams:
     """What ``augment_batch`` drew for one batch: everything ``apply_params`` needs."""
-    sigma: np.ndarray | None        # (n, 3) float32, None without colour augmentation
+    sigma: np.ndarray | None        # (n, 3) float32, None without the HED jitter
     bias: np.ndarray | None
     inv: np.ndarray                 # (n, 6) float64 inverse maps (identity without geometry)
     flip: np.ndarray                # (n,) bool
+    use_hed: np.ndarray | None = None   # (n,) bool, "hed_he" only: True = the HED jitter for this crop, False = the stain perturbation
+    he_gate: np.ndarray | None = None   # (n,) float64 in [0, 1): the perturbation applies where he_gate <= probability
+    he_matrix: np.ndarray | None = None     # (n, 2, 3) float64 in [-1, 1): U of M = max(H + amount_matrix * U, 0)
+    he_stains: np.ndarray | None = None     # (n, 2) float64 in [-1, 1): u of the factors 1 + amount_stains * u
+
+
+def stain_mode_params(p: BatchParams, config: dict, bases: StainBases, hed_applied=None):
+    """(mode (n,) int32, params (n, 14) float64) of a batch for ``ops.he_stain`` / ``ops.warp_affine_pool_stain``.  Mode per crop:
+    where ``p.use_hed`` (all False without the HED jitter in ``config``) 1 if ``hed_applied`` (the jitter's cut-off decision of the
+    crop's image; None = all inside) else 0; elsewhere 2 if ``he_gate <= probability`` and the image has a finite basis, else 0."""
+    he = config["he_staining"]
+    n = len(p.he_gate)
+    if len(bases) != n:
+        raise ValueError(f"stain bases: one per crop ({n}) expected, got {len(bases)}")
+    use_hed = np.zeros(n, bool) if p.use_hed is None else p.use_hed
+    applied = np.ones(n, bool) if hed_applied is None else np.asarray(hed_applied).astype(bool)
+    mode = np.where(use_hed, np.where(applied, 1, 0), np.where((p.he_gate <= he["probability"]) & bases.ok, 2, 0)).astype(np.int32)
+    params = np.zeros((n, 14), np.float64)
+    for t in np.flatnonzero(mode == 2):
+        params[t] = stain.stain_params(bases.H[t], bases.Hinv[t], p.he_matrix[t], p.he_stains[t], he["amount_matrix"],
+                                       he["amount_stains"])
+    return mode, params
 
 
 def sample_batch_params(rng: np.random.Generator, n: int, sh, sw, config: dict | None, scale_range: float = 0.5,
                         geometry: bool = True, out: int = 256, rescale=None) -> BatchParams:
-    """Draw order per batch: ``sample_hed`` (when ``config`` is given), then ``sample_affine`` (when ``geometry``), which takes
-    ``rescale`` (n,) -- without geometry there is no scale to divide and ``rescale`` is refused."""
+    """Draw order per batch: ``rng.random(n)`` for the choice between the HED jitter (``u < hed_probability``) and the stain
+    perturbation (when ``config`` has both: "hed_he"), then ``sample_hed`` (when ``config`` has the jitter), then ``sample_he`` (when
+    it has the perturbation), then ``sample_affine`` (when ``geometry``), which takes ``rescale`` (n,) -- without geometry there is
+    no scale to divide and ``rescale`` is refused.  Every draw is made for every crop, whatever the choice and the gates decide.
+    "hed_only" and "geometry" draw what they always drew."""
     if rescale is not None and not geometry:
         raise ValueError("rescale needs the geometric augmentation")
-    sigma = bias = None
-    if config is not None:
+    sigma = bias = use_hed = gate = U = u = None
+    if _has_hed(config) and _has_he(config):
+        use_hed = rng.random(n) < config["hed_probability"]
+    if _has_hed(config):
         sigma, bias = sample_hed(rng, n, config["sigma_ranges"], config["bias_ranges"])
+    if _has_he(config):
+        gate, U, u = sample_he(rng, n)
     if geometry:
         flip, inv = sample_affine(rng, n, sh, sw, out, scale_range, rescale=rescale)
     else:
         flip, inv = np.zeros(n, bool), identity_maps(n)
-    return BatchParams(sigma, bias, inv, flip)
+    return BatchParams(sigma, bias, inv, flip, use_hed, gate, U, u)
+
+
+def _colour_stage(X: torch.Tensor, p: BatchParams, config: dict, bases: StainBases | None) -> torch.Tensor:
+    """The colour stage of a configuration with the stain perturbation on uint8 crops: ``ops.he_stain`` on the crops it falls to,
+    ``ops.hed_jitter`` on those the choice gave to the jitter."""
+    if bases is None:
+        bases = stain_bases_of(X)
+    mode, params = stain_mode_params(p, config, bases)
+    out = ops.he_stain(X, params, np.where(mode == 2, 2, 0))
+    if p.use_hed is not None and p.use_hed.any():
+        ci = torch.from_numpy(np.flatnonzero(p.use_hed)).to(X.device)
+        jit, _applied = ops.hed_jitter(X[ci], p.sigma[p.use_hed], p.bias[p.use_hed], config["cutoff_range"],
+                                       config.get("simple_mode", False))
+        out[ci] = jit
+    return out
 
 
 def apply_params(X: torch.Tensor, labels: torch.Tensor, p: BatchParams, config: dict | None, label_fill: int = 0,
-                 out_hw=(256, 256)):
-    """The device chain up to the normalised float32 crops: (float32 (n, 3, dh, dw), int16 (n, dh, dw)).  uint8 crops get the stain
-    jitter (when ``config`` and the draws are given), the warp and the float32 normalisation; float32 crops are by contract already
-    normalised and get the warp only."""
+                 out_hw=(256, 256), stain_bases: StainBases | None = None):
+    """The device chain up to the normalised float32 crops: (float32 (n, 3, dh, dw), int16 (n, dh, dw)).  uint8 crops get the colour
+    stage (when ``config`` and the draws are given: the stain jitter, the stain perturbation, or per crop one of the two), the warp
+    and the float32 normalisation; float32 crops are by contract already normalised and get the warp only.  ``stain_bases``: one
+    basis per crop for the stain perturbation; computed here from the crops when absent."""
     if X.dtype == torch.uint8:
-        if config is not None and p.sigma is not None:
+        if _has_he(config) and p.he_gate is not None:
+            X = _colour_stage(X, p, config, stain_bases)
+        elif config is not None and p.sigma is not None:
             X, _applied = ops.hed_jitter(X, p.sigma, p.bias, config["cutoff_range"], config.get("simple_mode", False))
         x, lab = ops.warp_affine(X, p.inv, out_hw, labels, label_fill)
         return ops.normalize_img_f32(x, out=x), lab
@@ -221,7 +347,7 @@ def _to_device(X, labels, device):
 
 def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed_only", scale_range: float = 0.5,
                   label_fill: int = 0, geometry: bool = True, dtype: torch.dtype = torch.bfloat16, device=None, out: int = 256,
-                  rescale=None):
+                  rescale=None, stain_bases: StainBases | None = None):
     """One augmented training batch on the device: (patch rows (n * (out / 8)^2, 192) in ``dtype``, int16 labels (n, out, out)), what
     ``HeadTrainer.step`` takes.  Stain jitter (``config``: a name of ``AUGMENT_CONFIGS``, or None / "geometry" for none), warp
     (``geometry``), float32 normalisation, ``ops.patchify_f32``.  ``label_fill`` is the class of out-of-frame pixels: 0 as in the
@@ -230,13 +356,16 @@ def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed
     k crops that are still empty, in ascending crop order -- so fresh stain values (k, 2, 3) first when ``config`` is set, then the
     four affine draws of size k -- after everything the batch drew before.  ``rescale`` (n,) float64, the per-crop
     ``diameter / diam_mean``, divides the random scale (``sample_affine_params``); a resampling round passes the factors of the
-    crops that are still empty."""
+    crops that are still empty.  ``stain_bases`` (``stain_bases_of`` of these crops, in their order) spares the configurations with
+    the stain perturbation ("he_staining", "hed_he") the fit per call; a resampling round reuses the bases of its crops."""
     cfg = get_config(config)
     X, labels, sh, sw = _to_device(X, labels, device)
     n = X.shape[0]
     rescale = _check_rescale(rescale, n)
+    if _has_he(cfg) and X.dtype == torch.uint8 and stain_bases is None:
+        stain_bases = stain_bases_of(X)
     p = sample_batch_params(rng, n, sh, sw, cfg, scale_range, geometry, out, rescale)
-    x, lab = apply_params(X, labels, p, cfg, label_fill, (out, out))
+    x, lab = apply_params(X, labels, p, cfg, label_fill, (out, out), stain_bases)
     for _ in range(MAX_RESAMPLE):
         empty = torch.nonzero((lab == -100).flatten(1).all(1)).flatten()
         if empty.numel() == 0:
@@ -245,7 +374,8 @@ def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed
             raise ValueError(f"augment_batch: crop {int(empty[0])} has no annotated pixel")
         q = sample_batch_params(rng, int(empty.numel()), sh, sw, cfg, scale_range, geometry, out,
                                 None if rescale is None else rescale[empty.cpu().numpy()])
-        x2, lab2 = apply_params(X[empty], labels[empty], q, cfg, label_fill, (out, out))
+        x2, lab2 = apply_params(X[empty], labels[empty], q, cfg, label_fill, (out, out),
+                                None if stain_bases is None else stain_bases.take(empty.cpu().numpy()))
         x[empty], lab[empty] = x2, lab2
     else:
         if bool((lab == -100).flatten(1).all(1).any()):
@@ -321,6 +451,7 @@ class ImagePool:
                 raise ValueError("ImagePool: one positive diameter per image")
         self.diameters = diameters
         self._grid = None
+        self._stain = None
 
     def __len__(self) -> int:
         return len(self.px_off_host)
@@ -337,6 +468,15 @@ class ImagePool:
         mean = (self.byte_sums.astype(np.float64) / count) / 255.0
         return ((float(cutoff_range[0]) <= mean) & (mean <= float(cutoff_range[1]))).astype(np.int32)
 
+    def stain_basis(self) -> StainBases:
+        """The two-stain basis of every image, fitted the first time a configuration with the stain perturbation asks
+        for it and kept: the samples from ``ops.stain_samples`` (one pass over the pool), ``stain.stain_basis`` per image on the
+        host."""
+        if self._stain is None:
+            _k, samples, _status, _raw = ops.stain_samples(self.pool_u8, self.px_off, self.hw)
+            self._stain = StainBases.from_samples(samples)
+        return self._stain
+
 
 def sample_batch_params_pool(pool: ImagePool, idx, rng: np.random.Generator, config: dict | None, scale_range: float = 0.5,
                              geometry: bool = True, out: int = 256, rescale=None) -> BatchParams:
@@ -348,10 +488,19 @@ def sample_batch_params_pool(pool: ImagePool, idx, rng: np.random.Generator, con
 
 def apply_params_pool(pool: ImagePool, idx, p: BatchParams, config: dict | None, label_fill: int = 0, out_hw=(256, 256)):
     """The device chain of ``apply_params`` for crops out of images ``idx`` of a pool: one fused launch (stain jitter on the taps
-    of the images inside the cut-off, warp), then the float32 normalisation."""
+    of the images inside the cut-off, warp), then the float32 normalisation.  With the stain perturbation in ``config`` the launch
+    is ``ops.warp_affine_pool_stain``: per crop the jitter, the perturbation from the pool's cached ``stain_basis()``, or neither."""
     idx = np.asarray(idx, np.int64)
     sigma = bias = applied = None
     simple = False
+    if _has_he(config) and p.he_gate is not None:
+        if p.sigma is not None:
+            sigma, bias, applied = p.sigma, p.bias, pool.applied(config["cutoff_range"])[idx]
+            simple = config.get("simple_mode", False)
+        mode, params = stain_mode_params(p, config, pool.stain_basis().take(idx), applied)
+        x, lab, _status = ops.warp_affine_pool_stain(pool.pool_u8, pool.pool_lab, pool.px_off, pool.hw, idx, p.inv, out_hw, mode, sigma,
+                                                     bias, simple, params, label_fill)
+        return ops.normalize_img_f32(x, out=x), lab
     if config is not None and p.sigma is not None:
         sigma, bias, applied = p.sigma, p.bias, pool.applied(config["cutoff_range"])[idx]
         simple = config.get("simple_mode", False)

@@ -245,14 +245,17 @@ __device__ __forceinline__ void pool_tap(const uint8_t *__restrict__ img, int sh
     v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
 }
 
-// k_warp_affine<true> with a source per crop, image_of[t] of the pool, and k_hed_jitter folded into the taps: jitter(tap) of an
-// in-source tap, 0 (not jitter(0)) outside -- bitwise the jitter of the whole image followed by the warp
-__global__ void k_warp_affine_pool(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
-                                   const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI, long long pool_px,
-                                   const int32_t *__restrict__ image_of, const double *__restrict__ inv,
-                                   const float *__restrict__ sigma, const float *__restrict__ bias,
-                                   const int32_t *__restrict__ applied, int simple_mode, int dh, int dw, int label_fill,
-                                   float *__restrict__ out, int16_t *__restrict__ lab_out, int32_t *__restrict__ status) {
+// k_warp_affine<true> with a source per crop, image_of[t] of the pool, and a per-pixel colour transform folded into the taps:
+// f(tap) of an in-source tap, 0 (not f(0)) outside -- bitwise the transform of the whole image followed by the warp.  `taps` fills
+// the four neighbours a, b (row y0) and d, e (row y0 + 1) of crop t; the coordinates, the lerps and the label rule are shared by
+// every pool kernel.
+template <class Taps>
+__device__ __forceinline__ void warp_pool_pixel(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
+                                                const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI,
+                                                long long pool_px, const int32_t *__restrict__ image_of,
+                                                const double *__restrict__ inv, int dh, int dw, int label_fill,
+                                                float *__restrict__ out, int16_t *__restrict__ lab_out,
+                                                int32_t *__restrict__ status, const Taps &taps) {
     const int p = blockIdx.x * NTHR + threadIdx.x;
     if (p >= dh * dw) return;
     const size_t t = blockIdx.y;
@@ -283,18 +286,7 @@ __global__ void k_warp_affine_pool(const uint8_t *__restrict__ pool, const int16
         const int x0 = (int)fx, y0 = (int)fy;
         const float wx = (float)(sx - fx), wy = (float)(sy - fy);
         float a[3], b[3], d[3], e[3];
-        if (sigma && applied[t]) {
-            const float *sg = sigma + t * 3, *bs = bias + t * 3;
-            pool_tap<true>(img, sh, sw, y0, x0, sg, bs, simple_mode, a);
-            pool_tap<true>(img, sh, sw, y0, x0 + 1, sg, bs, simple_mode, b);
-            pool_tap<true>(img, sh, sw, y0 + 1, x0, sg, bs, simple_mode, d);
-            pool_tap<true>(img, sh, sw, y0 + 1, x0 + 1, sg, bs, simple_mode, e);
-        } else {
-            pool_tap<false>(img, sh, sw, y0, x0, nullptr, nullptr, 0, a);
-            pool_tap<false>(img, sh, sw, y0, x0 + 1, nullptr, nullptr, 0, b);
-            pool_tap<false>(img, sh, sw, y0 + 1, x0, nullptr, nullptr, 0, d);
-            pool_tap<false>(img, sh, sw, y0 + 1, x0 + 1, nullptr, nullptr, 0, e);
-        }
+        taps(t, img, sh, sw, y0, x0, a, b, d, e);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float top = a[c] + (b[c] - a[c]) * wx;
@@ -312,6 +304,38 @@ __global__ void k_warp_affine_pool(const uint8_t *__restrict__ pool, const int16
     }
 }
 
+// the taps of cpx_warp_affine_pool_u8: through hed_pixel where the crop's image is jittered, else the bytes themselves
+struct HedTaps {
+    const float *sigma, *bias;
+    const int32_t *applied;
+    int simple_mode;
+    __device__ __forceinline__ void operator()(size_t t, const uint8_t *img, int sh, int sw, int y0, int x0, float *a, float *b,
+                                               float *d, float *e) const {
+        if (sigma && applied[t]) {
+            const float *sg = sigma + t * 3, *bs = bias + t * 3;
+            pool_tap<true>(img, sh, sw, y0, x0, sg, bs, simple_mode, a);
+            pool_tap<true>(img, sh, sw, y0, x0 + 1, sg, bs, simple_mode, b);
+            pool_tap<true>(img, sh, sw, y0 + 1, x0, sg, bs, simple_mode, d);
+            pool_tap<true>(img, sh, sw, y0 + 1, x0 + 1, sg, bs, simple_mode, e);
+        } else {
+            pool_tap<false>(img, sh, sw, y0, x0, nullptr, nullptr, 0, a);
+            pool_tap<false>(img, sh, sw, y0, x0 + 1, nullptr, nullptr, 0, b);
+            pool_tap<false>(img, sh, sw, y0 + 1, x0, nullptr, nullptr, 0, d);
+            pool_tap<false>(img, sh, sw, y0 + 1, x0 + 1, nullptr, nullptr, 0, e);
+        }
+    }
+};
+
+__global__ void k_warp_affine_pool(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
+                                   const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI, long long pool_px,
+                                   const int32_t *__restrict__ image_of, const double *__restrict__ inv,
+                                   const float *__restrict__ sigma, const float *__restrict__ bias,
+                                   const int32_t *__restrict__ applied, int simple_mode, int dh, int dw, int label_fill,
+                                   float *__restrict__ out, int16_t *__restrict__ lab_out, int32_t *__restrict__ status) {
+    warp_pool_pixel(pool, pool_lab, px_off, hw, nI, pool_px, image_of, inv, dh, dw, label_fill, out, lab_out, status,
+                    HedTaps{sigma, bias, applied, simple_mode});
+}
+
 extern "C" int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw,
                                        int nI, long long pool_px, const int32_t *image_of, const double *inv, int n,
                                        const float *sigma, const float *bias, const int32_t *applied, int simple_mode, int dh,
@@ -326,6 +350,313 @@ extern "C" int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *po
     hipLaunchKernelGGL(k_warp_affine_pool, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
                        px_off, hw, nI, pool_px, image_of, inv, sigma, bias, applied, simple_mode ? 1 : 0, dh, dw, label_fill, out,
                        labels_out, status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// H&E stain-matrix perturbation (t5): augment_stains / stains_to_rgb of transforms/he_staining.py
+// ---------------------------------------------------------------------------
+// The stain basis is a per-image constant that the host fits once (NMF on the samples of cpx_stain_samples); the device
+// re-renders.  float64 throughout, unfused.  The 256-entry density table max(-log(max(b, 1) / 255), 1e-6) comes from the host
+// (numpy's own values) and sits in LDS: a byte-indexed, lane-divergent 8-byte read that a constant-address-space table would
+// turn into a global gather.  The exp is the one double-precision transcendental per channel.
+#define HE_NPAR 14      // per crop: Hinv [3][2], M [2][3], the two stain factors 1 + amount_stains * u_j
+
+__device__ __forceinline__ void he_pixel(const uint8_t *__restrict__ px, const double *__restrict__ par,
+                                         const double *dens, uint8_t *o) {
+    const double d0 = dens[px[0]], d1 = dens[px[1]], d2 = dens[px[2]];
+    double s[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const double c = d0 * par[j] + d1 * par[2 + j] + d2 * par[4 + j];  // density @ Hinv
+        s[j] = fmax(c * par[12 + j], 0.0);                                  // np.maximum(stains * (1 + amount * u), 0)
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double x = s[0] * par[6 + c] + s[1] * par[9 + c];            // stains @ M
+        const double v = fmin(fmax(255.0 * exp(-x), 0.0), 255.0);           // np.clip(255 * np.exp(-x), 0, 255)
+        o[c] = (uint8_t)(int)v;                                             // astype(uint8): truncation
+    }
+}
+
+__global__ void __launch_bounds__(NTHR) k_he_stain(const uint8_t *__restrict__ img, const double *__restrict__ params,
+                                                   const int32_t *__restrict__ mode, const double *__restrict__ density, int HW,
+                                                   uint8_t *__restrict__ out) {
+    __shared__ double s_dens[256];
+    s_dens[threadIdx.x] = density[threadIdx.x];
+    __syncthreads();
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= HW) return;
+    const size_t t = blockIdx.y;
+    const uint8_t *px = img + (t * HW + p) * 3;
+    uint8_t *o = out + (t * HW + p) * 3;
+    if (mode[t] != 2) { o[0] = px[0]; o[1] = px[1]; o[2] = px[2]; return; }
+    uint8_t r[3];
+    he_pixel(px, params + t * HE_NPAR, s_dens, r);
+    o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+}
+
+extern "C" int cpx_he_stain_u8(const uint8_t *img, int n, int H, int W, const double *params, const int32_t *mode,
+                               const double *density, uint8_t *out, void *stream) {
+    CPX_REQUIRE(img && params && mode && density && out && img != out && n > 0 && n <= 65535 && H > 0 && W > 0);
+    CPX_REQUIRE((long long)H * W < (1ll << 29));
+    hipLaunchKernelGGL(k_he_stain, dim3(cpx_cdiv((long long)H * W, NTHR), n), dim3(NTHR), 0, (hipStream_t)stream, img, params,
+                       mode, density, H * W, out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+__device__ __forceinline__ void he_tap(const uint8_t *__restrict__ img, int sh, int sw, int y, int x, const double *par,
+                                       const double *dens, float *v) {
+    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) { v[0] = v[1] = v[2] = 0.f; return; }
+    uint8_t r[3];
+    he_pixel(img + ((long long)y * sw + x) * 3, par, dens, r);
+    v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
+}
+
+// the taps of cpx_warp_affine_pool_stain_u8: the crop's mode picks the per-pixel function
+struct StainTaps {
+    const float *sigma, *bias;
+    int simple_mode;
+    const double *params, *dens;
+    const int32_t *mode;
+    __device__ __forceinline__ void operator()(size_t t, const uint8_t *img, int sh, int sw, int y0, int x0, float *a, float *b,
+                                               float *d, float *e) const {
+        const int m = mode[t];
+        if (m == 2) {
+            const double *par = params + t * HE_NPAR;
+            he_tap(img, sh, sw, y0, x0, par, dens, a);
+            he_tap(img, sh, sw, y0, x0 + 1, par, dens, b);
+            he_tap(img, sh, sw, y0 + 1, x0, par, dens, d);
+            he_tap(img, sh, sw, y0 + 1, x0 + 1, par, dens, e);
+        } else if (m == 1) {
+            const float *sg = sigma + t * 3, *bs = bias + t * 3;
+            pool_tap<true>(img, sh, sw, y0, x0, sg, bs, simple_mode, a);
+            pool_tap<true>(img, sh, sw, y0, x0 + 1, sg, bs, simple_mode, b);
+            pool_tap<true>(img, sh, sw, y0 + 1, x0, sg, bs, simple_mode, d);
+            pool_tap<true>(img, sh, sw, y0 + 1, x0 + 1, sg, bs, simple_mode, e);
+        } else {
+            pool_tap<false>(img, sh, sw, y0, x0, nullptr, nullptr, 0, a);
+            pool_tap<false>(img, sh, sw, y0, x0 + 1, nullptr, nullptr, 0, b);
+            pool_tap<false>(img, sh, sw, y0 + 1, x0, nullptr, nullptr, 0, d);
+            pool_tap<false>(img, sh, sw, y0 + 1, x0 + 1, nullptr, nullptr, 0, e);
+        }
+    }
+};
+
+__global__ void __launch_bounds__(NTHR) k_warp_affine_pool_stain(
+    const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab, const int64_t *__restrict__ px_off,
+    const int32_t *__restrict__ hw, int nI, long long pool_px, const int32_t *__restrict__ image_of, const double *__restrict__ inv,
+    const float *__restrict__ sigma, const float *__restrict__ bias, int simple_mode, const double *__restrict__ params,
+    const double *__restrict__ density, const int32_t *__restrict__ mode, int dh, int dw, int label_fill, float *__restrict__ out,
+    int16_t *__restrict__ lab_out, int32_t *__restrict__ status) {
+    __shared__ double s_dens[256];
+    s_dens[threadIdx.x] = density[threadIdx.x];
+    __syncthreads();
+    warp_pool_pixel(pool, pool_lab, px_off, hw, nI, pool_px, image_of, inv, dh, dw, label_fill, out, lab_out, status,
+                    StainTaps{sigma, bias, simple_mode, params, s_dens, mode});
+}
+
+extern "C" int cpx_warp_affine_pool_stain_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off,
+                                             const int32_t *hw, int nI, long long pool_px, const int32_t *image_of,
+                                             const double *inv, int n, const float *sigma, const float *bias, int simple_mode,
+                                             const double *stain_params, const double *density, const int32_t *mode, int dh,
+                                             int dw, int label_fill, float *out, int16_t *labels_out, int32_t *status,
+                                             void *stream) {
+    CPX_REQUIRE(pool_u8 && px_off && hw && image_of && inv && out && status && nI > 0 && pool_px > 0);
+    CPX_REQUIRE(sigma && bias && stain_params && density && mode);
+    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
+    CPX_REQUIRE((pool_lab == nullptr) == (labels_out == nullptr));
+    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
+    hipStream_t s = (hipStream_t)stream;
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_warp_affine_pool_stain, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
+                       px_off, hw, nI, pool_px, image_of, inv, sigma, bias, simple_mode ? 1 : 0, stain_params, density, mode, dh,
+                       dw, label_fill, out, labels_out, status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// tissue samples of every image of a pool: values = density[tissue_mask] (all pixels when the mask is empty), values[::128]
+// when there are more than 128 (extract_stains, he_staining.py:74-93).  Density is a function of the byte, so the selected
+// pixels' bytes are what comes back.  An ordered stream compaction with a stride pick, in three launches: tissue pixels per
+// chunk of SS_CHUNK raster-ordered pixels (ballots), one workgroup per image scanning its chunk counts into exclusive prefixes
+// and k_i, then every tissue pixel's global rank and the store of the selected ranks.  Integer counts only, no atomics on
+// data: the result does not depend on the launch geometry.
+// Chunk c of image i sits in slot px_off[i] / SS_CHUNK + i + c of the workspace: for images packed back to back these ranges do
+// not overlap, and for every entry that lies inside the pool they end below pool_px / SS_CHUNK + nI + 1.  An image's
+// workgroups read nothing but their own table entry, so a bad entry costs its own image only.
+// ---------------------------------------------------------------------------
+#define SS_CHUNK 1024
+#define SS_IT (SS_CHUNK / NTHR)
+
+__device__ __forceinline__ int stain_cap(long long px) { return (int)max(128ll, (px + 127) / 128); }
+__device__ __forceinline__ bool stain_out_ok(long long oo, long long px, long long out_triples) {
+    return oo >= 0 && oo <= out_triples && (long long)stain_cap(px) <= out_triples - oo;
+}
+__device__ __forceinline__ long long stain_slot_base(const int64_t *px_off, int i) { return px_off[i] / SS_CHUNK + i; }
+__device__ __forceinline__ bool tissue_px(const uint8_t *px, const double *lin, double y_t) {
+    return (0.212671 * lin[px[0]] + 0.715160 * lin[px[1]]) + 0.072169 * lin[px[2]] < y_t;
+}
+
+// workgroups (i, 0 .. gridDim.y - 1) share the chunks of image i, chunk c going to workgroup c % gridDim.y: the counts land per
+// chunk, so the geometry shows nowhere in the result
+__global__ void __launch_bounds__(NTHR) k_stain_count(const uint8_t *__restrict__ pool, const int64_t *__restrict__ px_off,
+                                                      const int32_t *__restrict__ hw, long long pool_px,
+                                                      const double *__restrict__ lin, double y_t,
+                                                      unsigned long long *__restrict__ counts) {
+    __shared__ double s_lin[256];
+    __shared__ uint32_t part[NTHR / 64];
+    const int i = blockIdx.x;
+    const long long off = px_off[i];
+    const int h = hw[2 * i], w = hw[2 * i + 1];
+    if (!pool_entry_ok(off, h, w, pool_px)) return;                     // uniform over the workgroup
+    const long long px = (long long)h * w, nch = (px + SS_CHUNK - 1) / SS_CHUNK;
+    s_lin[threadIdx.x] = lin[threadIdx.x];
+    __syncthreads();
+    const uint8_t *img = pool + 3 * off;
+    unsigned long long *cnt_out = counts + stain_slot_base(px_off, i);
+    for (long long chunk = blockIdx.y; chunk < nch; chunk += gridDim.y) {
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int it = 0; it < SS_IT; ++it) {
+            const long long p = chunk * SS_CHUNK + it * NTHR + threadIdx.x;
+            const bool m = p < px && tissue_px(img + 3 * p, s_lin, y_t);
+            cnt += (uint32_t)__popcll(__ballot(m));
+        }
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t tot = 0;
+            for (int k = 0; k < NTHR / 64; ++k) tot += part[k];
+            cnt_out[chunk] = tot;
+        }
+        __syncthreads();
+    }
+}
+
+// one workgroup per image: chunk counts -> exclusive prefixes in place, k_i; status bit 1 for a table entry outside the pool,
+// bit 2 for an output range outside the sample buffer
+__global__ void __launch_bounds__(1024) k_stain_scan(const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw,
+                                                     long long pool_px, const int64_t *__restrict__ out_off, long long out_triples,
+                                                     unsigned long long *__restrict__ counts, int64_t *__restrict__ k_out,
+                                                     int32_t *__restrict__ status) {
+    __shared__ unsigned long long wtot[16];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long off = px_off[i];
+    const int h = hw[2 * i], w = hw[2 * i + 1];
+    if (!pool_entry_ok(off, h, w, pool_px)) {
+        if (tid == 0) { k_out[i] = 0; atomicOr(status, 2); }
+        return;
+    }
+    const long long px = (long long)h * w;
+    if (!stain_out_ok(out_off[i], px, out_triples)) {
+        if (tid == 0) { k_out[i] = 0; atomicOr(status, 4); }
+        return;
+    }
+    const long long nch = (px + SS_CHUNK - 1) / SS_CHUNK;
+    unsigned long long *cnt = counts + stain_slot_base(px_off, i);
+    unsigned long long carry = 0;
+    for (long long c0 = 0; c0 < nch; c0 += 1024) {
+        const long long c = c0 + tid;
+        const unsigned long long v = c < nch ? cnt[c] : 0ull;
+        unsigned long long incl = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        unsigned long long before = 0, total = 0;
+        for (int k = 0; k < 16; ++k) {
+            const unsigned long long t = wtot[k];
+            if (k < wave) before += t;
+            total += t;
+        }
+        if (c < nch) cnt[c] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) k_out[i] = (int64_t)carry;
+}
+
+__global__ void __launch_bounds__(NTHR) k_stain_select(const uint8_t *__restrict__ pool, const int64_t *__restrict__ px_off,
+                                                       const int32_t *__restrict__ hw, long long pool_px,
+                                                       const double *__restrict__ lin, double y_t,
+                                                       const unsigned long long *__restrict__ prefix,
+                                                       const int64_t *__restrict__ k_in, const int64_t *__restrict__ out_off,
+                                                       long long out_triples, uint8_t *__restrict__ samples) {
+    __shared__ double s_lin[256];
+    __shared__ uint32_t seg[SS_IT * (NTHR / 64)];
+    const int i = blockIdx.x;
+    const long long off = px_off[i];
+    const int h = hw[2 * i], w = hw[2 * i + 1];
+    if (!pool_entry_ok(off, h, w, pool_px)) return;                     // uniform over the workgroup, here and below
+    const long long px = (long long)h * w, nch = (px + SS_CHUNK - 1) / SS_CHUNK;
+    const long long oo = out_off[i];
+    if (!stain_out_ok(oo, px, out_triples)) return;
+    s_lin[threadIdx.x] = lin[threadIdx.x];
+    __syncthreads();
+    const long long k = k_in[i];
+    const bool all = k == 0;                                            // no tissue pixel: every pixel is a value
+    const long long N = all ? px : k;
+    const bool stride = N > 128;
+    const int cap = stain_cap(px), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint8_t *img = pool + 3 * off;
+    const unsigned long long *pre = prefix + stain_slot_base(px_off, i);
+    for (long long chunk = blockIdx.y; chunk < nch; chunk += gridDim.y) {
+        bool m[SS_IT];
+        unsigned long long bal[SS_IT];
+#pragma unroll
+        for (int it = 0; it < SS_IT; ++it) {
+            const long long p = chunk * SS_CHUNK + it * NTHR + threadIdx.x;
+            m[it] = p < px && (all || tissue_px(img + 3 * p, s_lin, y_t));
+            bal[it] = __ballot(m[it]);
+            if (lane == 0) seg[it * (NTHR / 64) + wave] = (uint32_t)__popcll(bal[it]);
+        }
+        __syncthreads();
+        const long long first = all ? chunk * SS_CHUNK : (long long)pre[chunk];
+#pragma unroll
+        for (int it = 0; it < SS_IT; ++it) {
+            if (!m[it]) continue;
+            long long r = first;                                        // the pixel's rank among the image's values
+            for (int q = 0; q < it * (NTHR / 64) + wave; ++q) r += seg[q];
+            r += __popcll(bal[it] & ((1ull << lane) - 1ull));
+            if (stride && (r & 127)) continue;
+            const long long slot = stride ? (r >> 7) : r;
+            if (slot >= cap) continue;                                  // cannot happen with a consistent table
+            const uint8_t *px3 = img + 3 * (chunk * SS_CHUNK + it * NTHR + threadIdx.x);
+            uint8_t *o = samples + 3 * (oo + slot);
+            o[0] = px3[0]; o[1] = px3[1]; o[2] = px3[2];
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" size_t cpx_stain_samples_workspace_bytes(int nI, long long pool_px) {
+    if (nI <= 0 || pool_px <= 0) return 0;
+    return (size_t)(pool_px / SS_CHUNK + nI + 1) * sizeof(unsigned long long);
+}
+
+extern "C" int cpx_stain_samples(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                                 const double *lin, double y_t, const int64_t *out_off, long long out_triples, int64_t *k,
+                                 uint8_t *samples, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+    CPX_REQUIRE(pool_u8 && px_off && hw && lin && out_off && k && samples && status && workspace);
+    CPX_REQUIRE(nI > 0 && nI <= (1 << 24) && pool_px > 0 && out_triples > 0);
+    CPX_REQUIRE(workspace_bytes >= cpx_stain_samples_workspace_bytes(nI, pool_px) && ((uintptr_t)workspace & 7) == 0);
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long *counts = reinterpret_cast<unsigned long long *>(workspace);
+    // workgroups per image: twice the mean chunk count, so that images of about one size get a workgroup per chunk
+    const long long mean_chunks = (pool_px / SS_CHUNK) / nI + 1;
+    const unsigned per_image = (unsigned)(2 * mean_chunks < 1024 ? 2 * mean_chunks : 1024);
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_stain_count, dim3(nI, per_image), dim3(NTHR), 0, s, pool_u8, px_off, hw, pool_px, lin, y_t, counts);
+    hipLaunchKernelGGL(k_stain_scan, dim3(nI), dim3(1024), 0, s, px_off, hw, pool_px, out_off, out_triples, counts, k, status);
+    hipLaunchKernelGGL(k_stain_select, dim3(nI, per_image), dim3(NTHR), 0, s, pool_u8, px_off, hw, pool_px, lin, y_t, counts, k,
+                       out_off, out_triples, samples);
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }

@@ -721,6 +721,132 @@ def warp_affine_pool(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None, px_of
     return out, lab_out, status
 
 
+# ---- t5: H&E stain-matrix perturbation (csrc/cpx_augment.hip, host side in stain.py) --------------------------------
+_stain_tables: dict = {}
+
+
+def _stain_table(dev, which: str) -> torch.Tensor:
+    """The 256-entry float64 table ``which`` ("density" / "linear") of ``stain`` on ``dev``, uploaded once per device."""
+    from . import stain
+    key = (which, str(dev))
+    if key not in _stain_tables:
+        host = stain.density_table() if which == "density" else stain.linear_table()
+        _stain_tables[key] = torch.from_numpy(np.ascontiguousarray(host, np.float64)).to(dev)
+    return _stain_tables[key]
+
+
+def stain_samples(pool_u8: torch.Tensor, px_off: torch.Tensor, hw: torch.Tensor, out_off=None, out_triples: int | None = None,
+                  check_status: bool = True):
+    """``cpx_stain_samples`` on a ragged pool (layout as ``pool_byte_sums``): per image the tissue-pixel count and the bytes of the
+    pixels ``extract_stains`` fits its NMF on (``stain.select_samples`` is the host statement).  Returns ``(k (nI,) int64 on the
+    host, samples: a list of (m_i, 3) uint8 host arrays, status (1,) int32 device, raw (out_triples, 3) uint8 device buffer)``.
+    ``out_off`` (nI,) int64, the triple offset of every image in the buffer, and ``out_triples`` default to the capacities
+    ``stain.sample_capacity`` packed back to back; the buffer starts zeroed.  Status bit 1: a table entry outside the pool, bit 2: an
+    output range outside the buffer -- ``check_status`` raises ``ValueError`` on either."""
+    from . import stain
+    dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "stain_samples")
+    hw_host = hw.cpu().numpy().astype(np.int64)
+    px = hw_host[:, 0] * hw_host[:, 1]
+    cap = stain.sample_capacity(np.maximum(px, 0))
+    if out_off is None:
+        out_off = np.concatenate([[0], np.cumsum(cap)[:-1]]).astype(np.int64)
+    out_off = np.ascontiguousarray(out_off, np.int64)
+    if out_off.shape != (nI,):
+        raise ValueError("stain_samples: out_off is (nI,) int64")
+    if out_triples is None:
+        out_triples = int(max(1, (out_off + cap).max()))
+    L = _lib.lib()
+    ws = torch.empty(max(8, L.cpx_stain_samples_workspace_bytes(nI, pool_px)), dtype=torch.uint8, device=dev)
+    raw = torch.zeros((int(out_triples), 3), dtype=torch.uint8, device=dev)
+    k = torch.zeros(nI, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    off_dev = torch.from_numpy(out_off).to(dev)
+    check(L.cpx_stain_samples(ptr(pool_u8), ptr(px_off), ptr(hw), nI, pool_px, ptr(_stain_table(dev, "linear")), float(stain.Y_THRESHOLD),
+                              ptr(off_dev), int(out_triples), ptr(k), ptr(raw), ptr(status), ptr(ws),
+                              ws.numel(), _stream(dev)), "stain_samples")
+    bits = int(status.item())
+    if check_status and bits:
+        raise ValueError("stain_samples: " + ("an image of the table lies outside the pool" if bits & 2
+                                              else "a sample range lies outside the output buffer"))
+    k_host, raw_host = k.cpu().numpy(), raw.cpu().numpy()
+    samples = []
+    for i in range(nI):
+        m = int(stain.n_selected(k_host[i], px[i])) if px[i] > 0 else 0
+        ok = 0 <= out_off[i] and out_off[i] + cap[i] <= out_triples
+        samples.append(raw_host[out_off[i]:out_off[i] + m].copy() if ok else np.zeros((0, 3), np.uint8))
+    return k_host, samples, status, raw
+
+
+def _stain_args(params, mode, n: int, dev, what: str):
+    params = torch.as_tensor(np.ascontiguousarray(params, dtype=np.float64) if not isinstance(params, torch.Tensor) else params)
+    params = params.to(device=dev, dtype=torch.float64).contiguous()
+    mode = torch.as_tensor(mode).to(device=dev, dtype=torch.int32).contiguous()
+    if params.shape != (n, 14) or mode.shape != (n,):
+        raise ValueError(f"{what}: params are (n, 14) float64 and mode (n,) int32")
+    return params, mode
+
+
+def he_stain(img_u8: torch.Tensor, params, mode) -> torch.Tensor:
+    """``augment_stains`` on uint8 (n, H, W, 3) device images with the per-image ``params`` (n, 14) float64 of
+    ``stain.stain_params`` (Hinv, M, the two stain factors); image t is transformed where ``mode[t] == 2`` and copied elsewhere."""
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[3] != 3:
+        raise ValueError("he_stain: expected uint8 (n, H, W, 3)")
+    img_u8 = img_u8.contiguous()
+    n, H, W, _c = img_u8.shape
+    dev = img_u8.device
+    params, mode = _stain_args(params, mode, n, dev, "he_stain")
+    out = torch.empty_like(img_u8)
+    check(_lib.lib().cpx_he_stain_u8(ptr(img_u8), n, H, W, ptr(params), ptr(mode), ptr(_stain_table(dev, "density")), ptr(out),
+                                     _stream(dev)), "he_stain_u8")
+    return out
+
+
+def warp_affine_pool_stain(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None, px_off: torch.Tensor, hw: torch.Tensor, image_of,
+                           inv, out_hw, mode, sigma=None, bias=None, simple_mode: bool = False, params=None, label_fill: int = 0,
+                           check_status: bool = True):
+    """``cpx_warp_affine_pool_stain_u8``: ``warp_affine_pool`` with a colour transform per crop, ``mode`` (n,) int32 -- 0 none, 1 the
+    stain jitter with ``sigma`` / ``bias`` (n, 3) (the cut-off already applied by the caller), 2 the stain perturbation of ``he_stain``
+    with ``params`` (n, 14).  ``sigma`` / ``bias`` / ``params`` left out are zeros (their modes must then not occur).  Returns what
+    ``warp_affine_pool`` returns."""
+    dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "warp_affine_pool_stain")
+    dh, dw = (int(v) for v in out_hw)
+    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
+    n = image_of.numel()
+    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
+    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
+    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6):
+        raise ValueError("warp_affine_pool_stain: image_of is (n,) and inv (n, 6) float64")
+    mode_host = np.asarray(mode.cpu() if isinstance(mode, torch.Tensor) else mode).astype(np.int64)
+    if mode_host.shape != (n,) or mode_host.min() < 0 or mode_host.max() > 2:
+        raise ValueError("warp_affine_pool_stain: mode is (n,) with values 0, 1, 2")
+    if (sigma is None) != (bias is None) or (sigma is None and (mode_host == 1).any()) or (params is None and (mode_host == 2).any()):
+        raise ValueError("warp_affine_pool_stain: mode 1 needs sigma and bias, mode 2 needs params")
+    sigma = torch.zeros((n, 3), dtype=torch.float32) if sigma is None else torch.as_tensor(sigma, dtype=torch.float32)
+    bias = torch.zeros((n, 3), dtype=torch.float32) if bias is None else torch.as_tensor(bias, dtype=torch.float32)
+    sigma, bias = sigma.to(dev).contiguous(), bias.to(dev).contiguous()
+    if sigma.shape != (n, 3) or bias.shape != (n, 3):
+        raise ValueError("warp_affine_pool_stain: sigma and bias are (n, 3)")
+    params, mode = _stain_args(np.zeros((n, 14)) if params is None else params, mode_host, n, dev, "warp_affine_pool_stain")
+    lab_out = None
+    if pool_lab is not None:
+        if pool_lab.dtype != torch.int16 or pool_lab.shape != (pool_px,) or pool_lab.device != dev or not pool_lab.is_contiguous():
+            raise ValueError("warp_affine_pool_stain: pool_lab is a contiguous int16 vector of one label per pool pixel on the pool's "
+                             "device")
+        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
+    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(_lib.lib().cpx_warp_affine_pool_stain_u8(ptr(pool_u8), ptr(pool_lab), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv),
+                                                   n, ptr(sigma), ptr(bias), int(bool(simple_mode)), ptr(params),
+                                                   ptr(_stain_table(dev, "density")), ptr(mode), dh, dw, int(label_fill), ptr(out),
+                                                   ptr(lab_out), ptr(status), _stream(dev)), "warp_affine_pool_stain_u8")
+    if check_status:
+        bits = int(status.item())
+        if bits:
+            raise ValueError("warp_affine_pool_stain: " + ("an image index outside the pool" if bits & 1
+                                                           else "a table entry outside the pool"))
+    return out, lab_out, status
+
+
 def normalize_stats_f32(x: torch.Tensor) -> torch.Tensor:
     """(n, 3, 4) float32 {x01, x99 - x01, mode, x99} of float32 (n, 3, H, W) planes: np.percentile(plane, [1, 99]) exactly."""
     if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():

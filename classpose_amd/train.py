@@ -268,6 +268,11 @@ def _check_dataset(images, labels, what: str):
     return images, labels
 
 
+def _is_u8_crops(images) -> bool:
+    dt = getattr(images, "dtype", None)
+    return (dt == np.uint8 or dt == torch.uint8) and images.ndim == 4 and images.shape[3] == 3
+
+
 def _pool_annotated(pool, what: str) -> None:
     empty = np.flatnonzero(~pool.annotated)
     if len(empty):
@@ -303,7 +308,8 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     validation once per epoch, ``checkpoint_last.pt`` and ``checkpoint_best.pt`` (lowest validation loss; training loss without a
     validation set) next to the final model.  ``cache_features`` runs the backbone once per image; ``transform(X, labels, rng) ->
     (X, labels)``, a host callback per batch for callers who augment, forces the uncached path.
-    ``augment`` ("hed_only": stain jitter + geometry, "geometry": flip / rotation / scale / crop alone) augments every training
+    ``augment`` ("hed_only": stain jitter + geometry, "he_staining": H&E stain-matrix perturbation + geometry, "hed_he": per image
+    one of the two colour transforms + geometry, "geometry": flip / rotation / scale / crop alone) augments every training
     batch on the device with ``augment.augment_batch`` (``scale_range``, ``label_fill`` as there), drawing from the epoch's
     generator after the sampling order and after ``transform``, which still runs first.  The training path is then uncached;
     validation is never augmented and its features are still cached when ``cache_features`` is set.
@@ -361,6 +367,11 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     if augment is not None and augment != "geometry":
         _augment.get_config(augment)                       # unknown names and "enhanced" raise before anything is computed
     cached = cache_features and transform is None and augment is None        # a pool without augment trains on its grid crops
+    # the stain perturbation re-renders from the image's own stain basis, a per-image constant: fitted once here for pre-cut
+    # crops (a pool caches its own).  A transform callback changes the crops per batch, so their bases are then fitted per batch.
+    bases = None
+    if pool is None and transform is None and _augment._has_he(_augment.get_config(augment)) and _is_u8_crops(images):
+        bases = _augment.stain_bases_of(images, trainer.device)
     test_cached = cached or (cache_features and augment is not None)
     dev = trainer.device
     lab_dev = test_lab_dev = feats = test_feats = None
@@ -398,7 +409,8 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
                 if augment is not None:
                     x, y = _augment.augment_batch(x, y, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
                                                   dtype=trainer.dtype, device=dev, out=CROP,
-                                                  rescale=None if rsc is None else rsc[idx])
+                                                  rescale=None if rsc is None else rsc[idx],
+                                                  stain_bases=None if bases is None else bases.take(idx))
             r = trainer.step(x, y, float(LR[iepoch]))
             sums += np.array([r["ce"], r["tversky"], r["loss"]]) * len(idx)
             count += len(idx)

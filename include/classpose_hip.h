@@ -608,6 +608,52 @@ int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *pool_lab, con
                             float *out, int16_t *labels_out, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
+ * t5  H&E stain-matrix perturbation (csrc/cpx_augment.hip)
+ * replaces HEStainingTransform.transform -> augment_stains (classpose/transforms/he_staining.py:110-164, :195-266 of the
+ * reference) as wired by StarDistAugmentation._build_color_transform (transforms/stardist_augmentation.py:48-81): the colour
+ * half of the `enhanced` strategy.  The reference refits the image's two-stain basis (extract_stains, :47-107: NMF on optical
+ * density) at every draw; here it is a per-image constant that the host fits once on the samples of cpx_stain_samples, and the
+ * device only re-renders.  float64, unfused, left to right.  Every entry runs on `stream` and allocates nothing.
+ * ---------------------------------------------------------------------- */
+/* cpx_stain_samples: the rows that extract_stains hands to NMF.fit (he_staining.py:74-93), as the RGB bytes of the selected
+ *   pixels (density is a function of the byte, rgb_to_density :23-27).  Pool layout as in t4.  Per image i, in raster order: the
+ *   tissue pixels are those with (0.212671 * lin[R] + 0.715160 * lin[G]) + 0.072169 * lin[B] < y_t in double -- lin [256] double
+ *   and y_t from the host: one threshold on linear luminance that restates `cv2.cvtColor(x, COLOR_RGB2LAB)[..., 0] < 200` (:78);
+ *   k[i] int64 is their count; the values are the tissue pixels, or ALL pixels when k[i] == 0 (:83-85); with N values, N > 128
+ *   keeps the values of rank 0, 128, 256, ... (`values[::128]`, :90-91), else all N.  They are written as byte triples from
+ *   samples + 3 * out_off[i] on; image i needs room for max(128, ceil(h_i w_i / 128)) triples inside the out_triples of the
+ *   buffer, nothing beyond what was selected is written.  status (ONE int32 word, cleared first): bit 1 a table entry outside
+ *   the pool, bit 2 an output range outside the buffer; such an image is neither read nor written and its k is 0.
+ *   Three launches (counts per 1024-pixel chunk by ballot, a scan per image, ranks and stores): integers only, no atomics on
+ *   data, the result does not depend on the launch geometry.  workspace: cpx_stain_samples_workspace_bytes (host only; 0 for
+ *   arguments the entry refuses), 8-byte aligned.                                                                            */
+size_t cpx_stain_samples_workspace_bytes(int nI, long long pool_px);
+int cpx_stain_samples(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                      const double *lin, double y_t, const int64_t *out_off, long long out_triples, int64_t *k,
+                      uint8_t *samples, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* cpx_he_stain_u8: augment_stains + stains_to_rgb (he_staining.py:110-164) on uint8 images of one shape, the twin of
+ *   cpx_hed_jitter_u8.  img, out [n][H][W][3] uint8 (distinct buffers); params [n][14] double = Hinv [3][2] (pinv of the stain
+ *   basis), M [2][3] = max(H + amount_matrix * U, 0), and the two factors 1 + amount_stains * u_j; mode [n] int32: image t is
+ *   transformed where mode[t] == 2, else copied; density [256] double = max(-log(max(b, 1) / 255), 1e-6) from the host.
+ *   Per pixel: d_c = density[byte_c]; s_j = max((d_0 Hinv[0][j] + d_1 Hinv[1][j] + d_2 Hinv[2][j]) * factor_j, 0);
+ *   x_c = s_0 M[0][c] + s_1 M[1][c]; byte = trunc(clip(255 * exp(-x_c), 0, 255)).                                          */
+int cpx_he_stain_u8(const uint8_t *img, int n, int H, int W, const double *params, const int32_t *mode, const double *density,
+                    uint8_t *out, void *stream);
+
+/* cpx_warp_affine_pool_stain_u8: cpx_warp_affine_pool_u8 with a colour transform per CROP, mode [n] int32: 0 none, 1 the
+ *   stain jitter of cpx_hed_jitter_u8 with sigma / bias [n][3] (the host has already applied the cut-off), 2 the per-pixel
+ *   function of cpx_he_stain_u8 with stain_params [n][14].  The transform runs on the four in-source taps of every output
+ *   pixel before the interpolation; the geometry code is the one cpx_warp_affine_pool_u8 runs.  Mode 2 is bitwise
+ *   cpx_he_stain_u8 of the whole image followed by cpx_warp_affine_u8; mode 1 bitwise cpx_warp_affine_pool_u8 with applied = 1,
+ *   mode 0 bitwise cpx_warp_affine_pool_u8 without jitter.  status as there.  No pointer but pool_lab / labels_out is NULL. */
+int cpx_warp_affine_pool_stain_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw,
+                                  int nI, long long pool_px, const int32_t *image_of, const double *inv, int n,
+                                  const float *sigma, const float *bias, int simple_mode, const double *stain_params,
+                                  const double *density, const int32_t *mode, int dh, int dw, int label_fill, float *out,
+                                  int16_t *labels_out, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
  * replaces, per instance, cv2.findContours(cell_mask, RETR_EXTERNAL,
  * CHAIN_APPROX_SIMPLE)[0] + shapely.Polygon(...).is_valid/.centroid/.area/.length
