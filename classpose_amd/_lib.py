@@ -165,6 +165,11 @@ SIGNATURES = {
     "cpx_he_stain_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "cpx_warp_affine_pool_stain_u8": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _p, _p, _i, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p,
                                            _p, _p]),
+    "cpx_hbs_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "cpx_blur_pool_rects_u8": (_i, [_p, _p, _p, _i, C.c_longlong, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p,
+                                    C.c_longlong, _p, _p]),
+    "cpx_warp_affine_pool_quality_u8": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
+                                             C.c_longlong, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),
@@ -179,6 +184,7 @@ _PRIVATE = {
     "cpx_attention_set_variant": (None, [_i]),
     "cpx_gemm_set_nt": (None, [_i]),
     "cpx_follow_set_early_exit": (None, [_i]),
+    "cpx_blur_set_tile": (None, [_i]),
     "cpx_follow_set_lds_window": (None, [_i]),
     "cpx_gemm_set_reverse": (None, [_i]),
     "cpx_attention_set_xcd_order": (None, [_i]),

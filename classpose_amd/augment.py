@@ -18,8 +18,13 @@ own two-stain basis: the basis is fitted once per image on the host (``stain.sta
 cached on the ``ImagePool``), the draws perturb it, and the pixels go through ``ops.he_stain`` or, on a pool, through the taps of
 ``ops.warp_affine_pool_stain``.
 
+The image-quality stage (configurations ``quality`` and ``hed_he_quality``, the latter the reference's whole ``enhanced``
+pipeline under a name of its own) follows the colour stage: a Gaussian blur (``ops.blur``; on a pool ``ops.blur_pool_rects`` on the
+footprint of each gated crop, read back by the taps of ``ops.warp_affine_pool_quality``) and the hue / brightness / saturation
+jitter (``ops.hbs``, or on the same taps).  The reference's additive noise is an identity on uint8 and is not built.
+
 Still different from the reference: the warp samples at exact double-precision source coordinates (OpenCV quantises them to
-1 / 32 pixel) and the ``enhanced`` pipeline is not built (its Gaussian blur and hue / brightness / saturation jitter are missing).  The rescale by cell diameter (dataset.py:35-45) is the ``rescale``
+1 / 32 pixel).  The rescale by cell diameter (dataset.py:35-45) is the ``rescale``
 argument of the samplers: per crop ``diameter / diam_mean``, the diameters from ``dataset_stats.label_stats``.
 """
 from __future__ import annotations
@@ -62,6 +67,14 @@ AUGMENT_CONFIGS = {
         "he_staining": {"amount_matrix": 0.15, "amount_stains": 0.4, "probability": 0.9},
     },
 }
+# augmentation_configs.py:47-60 (gaussian_blur_config, hbs_config of ENHANCED_CONFIG): the image-quality stage alone, and after the
+# colour stage of "hed_he" -- the latter is everything the reference's `enhanced` strategy does to a pixel
+_QUALITY = {
+    "gaussian_blur": {"sigma_range": (0, 2), "probability": 0.1},
+    "hbs": {"hue": 0.1, "brightness": 0.1, "saturation": (0.9, 1.1), "probability": 0.9},
+}
+AUGMENT_CONFIGS["quality"] = dict(_QUALITY)
+AUGMENT_CONFIGS["hed_he_quality"] = {**AUGMENT_CONFIGS["hed_he"], **_QUALITY}
 MAX_RESAMPLE = 8
 
 
@@ -70,8 +83,8 @@ def get_config(name: str | None) -> dict | None:
     if name is None or name == "geometry":
         return None
     if name == "enhanced":
-        raise NotImplementedError("the 'enhanced' augmentation is not built: its colour stage is 'hed_he', but the Gaussian blur and "
-                                  "the hue / brightness / saturation jitter that follow it are missing")
+        raise NotImplementedError("the name 'enhanced' is not enabled: 'hed_he_quality' runs the reference's pipeline (the colour stage "
+                                  "'hed_he', then the Gaussian blur and the hue / brightness / saturation jitter)")
     if name not in AUGMENT_CONFIGS:
         raise ValueError(f"unknown augmentation {name!r}: one of {sorted(AUGMENT_CONFIGS) + ['geometry']}")
     return AUGMENT_CONFIGS[name]
@@ -200,6 +213,70 @@ def sample_he(rng: np.random.Generator, n: int):
     return rng.random(n), rng.uniform(-1.0, 1.0, size=(n, 2, 3)), rng.uniform(-1.0, 1.0, size=(n, 2))
 
 
+def _has_quality(config: dict | None) -> bool:
+    return config is not None and "gaussian_blur" in config
+
+
+def sample_quality(rng: np.random.Generator, n: int, config: dict):
+    """(u_blur, sigma, u_hbs, hue, brightness, saturation), each (n,) float64, of the image-quality stage: ``rng.random(n)`` for the
+    blur's gate, ``rng.uniform(lo, hi, n)`` for sigma, ``rng.random(n)`` for the HBS gate, then ``rng.uniform`` for the hue shift in
+    +-hue, the brightness offset in +-brightness (the factor is 1 + offset) and the saturation factor in its range -- the order of
+    ``GaussianBlurTransform.transform`` and ``_hbs_adjust``.  All six are drawn for every crop, whatever the gates decide; a stage
+    applies where ``u <= probability`` (the reference skips where ``random() > probability``)."""
+    b, h = config["gaussian_blur"], config["hbs"]
+    u_blur = rng.random(n)
+    sigma = rng.uniform(b["sigma_range"][0], b["sigma_range"][1], n)
+    u_hbs = rng.random(n)
+    hue = rng.uniform(-h["hue"], h["hue"], n)
+    brightness = rng.uniform(-h["brightness"], h["brightness"], n)
+    saturation = rng.uniform(h["saturation"][0], h["saturation"][1], n)
+    return u_blur, sigma, u_hbs, hue, brightness, saturation
+
+
+def gauss_weights(sigma: float) -> tuple[int, np.ndarray]:
+    """(radius, weights (17,) float64) of ``scipy.ndimage.gaussian_filter(x, sigma)`` with its defaults (truncate 4, order 0):
+    ``radius = int(4 * sigma + 0.5)``, ``phi = exp(-0.5 / sigma**2 * x**2)`` for ``x = -radius .. radius``, ``phi / phi.sum()`` in
+    entries ``0 .. 2 * radius``, zeros beyond.  Radius 0 (sigma < 0.125) is the identity, weight 1."""
+    sigma = float(sigma)
+    if not 0.0 <= sigma <= 2.0:
+        raise ValueError(f"gauss_weights: sigma in [0, 2] expected (radius at most 8), got {sigma}")
+    radius = int(4.0 * sigma + 0.5)
+    w = np.zeros(17, np.float64)
+    if radius == 0:
+        w[0] = 1.0
+        return 0, w
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    w[:2 * radius + 1] = phi / phi.sum()
+    return radius, w
+
+
+def footprint_rects(inv, sh, sw, out_hw=(256, 256)):
+    """(rects (n, 4) int64 rows (y0, x0, h, w), ok (n,) bool): per crop the part of its ``sh`` x ``sw`` image that the bilinear taps of
+    the ``out_hw`` window under the inverse map ``inv`` can touch.  The source coordinates are affine in the output pixel and are
+    formed as the kernel forms them (``(a * x + b * y) + c`` in double, each rounding monotone), so their extremes lie at the four
+    corners of the window; the taps of a coordinate s are floor(s) and floor(s) + 1.  Clipped to the image; ``ok`` is False where
+    nothing of the image is left (or the map is not finite) and the rectangle is zeros."""
+    inv = np.asarray(inv, np.float64).reshape(-1, 6)
+    n = len(inv)
+    sh, sw = _source_shapes(sh, sw, n)
+    dh, dw = (int(v) for v in out_hw)
+    xs, ys = np.array([0.0, dw - 1.0, 0.0, dw - 1.0]), np.array([0.0, 0.0, dh - 1.0, dh - 1.0])
+    sx = (inv[:, 0:1] * xs + inv[:, 1:2] * ys) + inv[:, 2:3]
+    sy = (inv[:, 3:4] * xs + inv[:, 4:5] * ys) + inv[:, 5:6]
+    rects, ok = np.zeros((n, 4), np.int64), np.zeros(n, bool)
+    for t in range(n):
+        if not (np.all(np.isfinite(sx[t])) and np.all(np.isfinite(sy[t]))):
+            continue
+        x_lo, x_hi = max(np.floor(sx[t].min()), 0.0), min(np.floor(sx[t].max()) + 1.0, sw[t] - 1.0)
+        y_lo, y_hi = max(np.floor(sy[t].min()), 0.0), min(np.floor(sy[t].max()) + 1.0, sh[t] - 1.0)
+        if x_lo > x_hi or y_lo > y_hi:
+            continue
+        rects[t] = (int(y_lo), int(x_lo), int(y_hi - y_lo) + 1, int(x_hi - x_lo) + 1)
+        ok[t] = True
+    return rects, ok
+
+
 @dataclass
 class StainBases:
     """The two-stain bases of a set of images: H (n, 2, 3), Hinv (n, 3, 2) float64, ok (n,) bool -- False where the fit gave no
@@ -255,6 +332,28 @@ class BatchParams:
     he_gate: np.ndarray | None = None   # (n,) float64 in [0, 1): the perturbation applies where he_gate <= probability
     he_matrix: np.ndarray | None = None     # (n, 2, 3) float64 in [-1, 1): U of M = max(H + amount_matrix * U, 0)
     he_stains: np.ndarray | None = None     # (n, 2) float64 in [-1, 1): u of the factors 1 + amount_stains * u
+    blur_gate: np.ndarray | None = None     # (n,) float64 in [0, 1): the blur applies where blur_gate <= probability
+    blur_sigma: np.ndarray | None = None    # (n,) float64 in the sigma range
+    hbs_gate: np.ndarray | None = None      # (n,) float64 in [0, 1): the HBS jitter applies where hbs_gate <= probability
+    hbs_hue: np.ndarray | None = None       # (n,) float64 in +-hue
+    hbs_brightness: np.ndarray | None = None    # (n,) float64 in +-brightness: the factor is 1 + this
+    hbs_saturation: np.ndarray | None = None    # (n,) float64 in the saturation range
+
+
+def quality_params(p: BatchParams, config: dict):
+    """(blurred (n,) bool, radius (n,) int32, weights (n, 17) float64, hbs (n, 4) float32, hbs_apply (n,) int32) of a batch for
+    ``ops.blur`` / ``ops.blur_pool_rects`` and ``ops.hbs`` / ``ops.warp_affine_pool_quality``.  A crop is blurred where its gate passed
+    and its radius is not 0 (radius 0 is the identity).  hbs rows: float32 of {hue, 1 + brightness, saturation, 1 - saturation}, the
+    last formed in double first."""
+    n = len(p.blur_gate)
+    gated = p.blur_gate <= config["gaussian_blur"]["probability"]
+    radius, weights = np.zeros(n, np.int32), np.zeros((n, 17), np.float64)
+    weights[:, 0] = 1.0
+    for t in np.flatnonzero(gated):
+        radius[t], weights[t] = gauss_weights(p.blur_sigma[t])
+    hbs = np.stack([p.hbs_hue, 1.0 + p.hbs_brightness, p.hbs_saturation, 1.0 - p.hbs_saturation], 1).astype(np.float32)
+    apply = (p.hbs_gate <= config["hbs"]["probability"]).astype(np.int32)
+    return gated & (radius > 0), radius, weights, hbs, apply
 
 
 def stain_mode_params(p: BatchParams, config: dict, bases: StainBases, hed_applied=None):
@@ -279,7 +378,8 @@ def sample_batch_params(rng: np.random.Generator, n: int, sh, sw, config: dict |
                         geometry: bool = True, out: int = 256, rescale=None) -> BatchParams:
     """Draw order per batch: ``rng.random(n)`` for the choice between the HED jitter (``u < hed_probability``) and the stain
     perturbation (when ``config`` has both: "hed_he"), then ``sample_hed`` (when ``config`` has the jitter), then ``sample_he`` (when
-    it has the perturbation), then ``sample_affine`` (when ``geometry``), which takes ``rescale`` (n,) -- without geometry there is
+    it has the perturbation), then ``sample_quality`` (when it has the image-quality stage: "quality", "hed_he_quality"), then
+    ``sample_affine`` (when ``geometry``), which takes ``rescale`` (n,) -- without geometry there is
     no scale to divide and ``rescale`` is refused.  Every draw is made for every crop, whatever the choice and the gates decide.
     "hed_only" and "geometry" draw what they always drew."""
     if rescale is not None and not geometry:
@@ -291,11 +391,12 @@ def sample_batch_params(rng: np.random.Generator, n: int, sh, sw, config: dict |
         sigma, bias = sample_hed(rng, n, config["sigma_ranges"], config["bias_ranges"])
     if _has_he(config):
         gate, U, u = sample_he(rng, n)
+    quality = sample_quality(rng, n, config) if _has_quality(config) else (None,) * 6
     if geometry:
         flip, inv = sample_affine(rng, n, sh, sw, out, scale_range, rescale=rescale)
     else:
         flip, inv = np.zeros(n, bool), identity_maps(n)
-    return BatchParams(sigma, bias, inv, flip, use_hed, gate, U, u)
+    return BatchParams(sigma, bias, inv, flip, use_hed, gate, U, u, *quality)
 
 
 def _colour_stage(X: torch.Tensor, p: BatchParams, config: dict, bases: StainBases | None) -> torch.Tensor:
@@ -318,12 +419,21 @@ def apply_params(X: torch.Tensor, labels: torch.Tensor, p: BatchParams, config: 
     """The device chain up to the normalised float32 crops: (float32 (n, 3, dh, dw), int16 (n, dh, dw)).  uint8 crops get the colour
     stage (when ``config`` and the draws are given: the stain jitter, the stain perturbation, or per crop one of the two), the warp
     and the float32 normalisation; float32 crops are by contract already normalised and get the warp only.  ``stain_bases``: one
-    basis per crop for the stain perturbation; computed here from the crops when absent."""
+    basis per crop for the stain perturbation; computed here from the crops when absent.  With the image-quality stage in
+    ``config`` the gated crops go through ``ops.blur`` and ``ops.hbs`` between the colour stage and the warp."""
     if X.dtype == torch.uint8:
         if _has_he(config) and p.he_gate is not None:
             X = _colour_stage(X, p, config, stain_bases)
         elif config is not None and p.sigma is not None:
             X, _applied = ops.hed_jitter(X, p.sigma, p.bias, config["cutoff_range"], config.get("simple_mode", False))
+        if _has_quality(config) and p.blur_gate is not None:
+            blurred, radius, weights, hbs, hbs_apply = quality_params(p, config)
+            if blurred.any():
+                ci = torch.from_numpy(np.flatnonzero(blurred)).to(X.device)
+                Xb = X.clone()
+                Xb[ci] = ops.blur(X[ci], radius[blurred], weights[blurred])
+                X = Xb
+            X = ops.hbs(X, hbs, hbs_apply)
         x, lab = ops.warp_affine(X, p.inv, out_hw, labels, label_fill)
         return ops.normalize_img_f32(x, out=x), lab
     return ops.warp_affine(X, p.inv, out_hw, labels, label_fill)
@@ -486,18 +596,52 @@ def sample_batch_params_pool(pool: ImagePool, idx, rng: np.random.Generator, con
     return sample_batch_params(rng, len(idx), pool.hw_host[idx, 0], pool.hw_host[idx, 1], config, scale_range, geometry, out, rescale)
 
 
-def apply_params_pool(pool: ImagePool, idx, p: BatchParams, config: dict | None, label_fill: int = 0, out_hw=(256, 256)):
-    """The device chain of ``apply_params`` for crops out of images ``idx`` of a pool: one fused launch (stain jitter on the taps
-    of the images inside the cut-off, warp), then the float32 normalisation.  With the stain perturbation in ``config`` the launch
-    is ``ops.warp_affine_pool_stain``: per crop the jitter, the perturbation from the pool's cached ``stain_basis()``, or neither."""
+def pool_colour_args(pool: ImagePool, idx, p: BatchParams, config: dict):
+    """(mode (n,) int32, sigma, bias (n, 3) float32 or None, simple_mode, params (n, 14) float64 or None): the colour stage of the
+    crops out of images ``idx`` as ``ops.warp_affine_pool_stain`` / ``ops.blur_pool_rects`` / ``ops.warp_affine_pool_quality`` take it.
+    With the stain perturbation in ``config`` the modes are those of ``stain_mode_params`` (the jitter's cut-off from the pool's byte
+    sums, the bases from the pool's cached ``stain_basis()``); without it every crop is in mode 0."""
     idx = np.asarray(idx, np.int64)
-    sigma = bias = applied = None
+    sigma = bias = applied = params = None
     simple = False
+    mode = np.zeros(len(idx), np.int32)
     if _has_he(config) and p.he_gate is not None:
         if p.sigma is not None:
             sigma, bias, applied = p.sigma, p.bias, pool.applied(config["cutoff_range"])[idx]
             simple = config.get("simple_mode", False)
         mode, params = stain_mode_params(p, config, pool.stain_basis().take(idx), applied)
+    return mode, sigma, bias, simple, params
+
+
+def apply_params_pool(pool: ImagePool, idx, p: BatchParams, config: dict | None, label_fill: int = 0, out_hw=(256, 256)):
+    """The device chain of ``apply_params`` for crops out of images ``idx`` of a pool: one fused launch (stain jitter on the taps
+    of the images inside the cut-off, warp), then the float32 normalisation.  With the stain perturbation in ``config`` the launch
+    is ``ops.warp_affine_pool_stain``: per crop the jitter, the perturbation from the pool's cached ``stain_basis()``, or neither.
+    With the image-quality stage in ``config``: one ``ops.blur_pool_rects`` launch writes, for every blurred crop, the blur of its
+    colour-transformed image on the crop's ``footprint_rects`` rectangle into a scratch allocated here, and one
+    ``ops.warp_affine_pool_quality`` launch warps all crops, the blurred ones out of the scratch, with the HBS jitter on the taps."""
+    idx = np.asarray(idx, np.int64)
+    sigma = bias = applied = None
+    simple = False
+    if _has_quality(config) and p.blur_gate is not None:
+        n = len(idx)
+        mode, sigma, bias, simple, params = pool_colour_args(pool, idx, p, config)
+        blurred, radius, weights, hbs, hbs_apply = quality_params(p, config)
+        rects, ok = footprint_rects(p.inv, pool.hw_host[idx, 0], pool.hw_host[idx, 1], out_hw)
+        blurred &= ok
+        scratch, ov_off = None, np.full(n, -1, np.int64)
+        if blurred.any():
+            b = np.flatnonzero(blurred)
+            scratch, off, _status = ops.blur_pool_rects(
+                pool.pool_u8, pool.px_off, pool.hw, idx[b], rects[b], radius[b], weights[b], mode=mode[b],
+                sigma=None if sigma is None else sigma[b], bias=None if bias is None else bias[b], simple_mode=simple,
+                params=None if params is None else params[b])
+            ov_off[b] = off
+        x, lab, _status = ops.warp_affine_pool_quality(pool.pool_u8, pool.pool_lab, pool.px_off, pool.hw, idx, p.inv, out_hw, mode, sigma,
+                                                       bias, simple, params, hbs, hbs_apply, scratch, ov_off, rects, label_fill)
+        return ops.normalize_img_f32(x, out=x), lab
+    if _has_he(config) and p.he_gate is not None:
+        mode, sigma, bias, simple, params = pool_colour_args(pool, idx, p, config)
         x, lab, _status = ops.warp_affine_pool_stain(pool.pool_u8, pool.pool_lab, pool.px_off, pool.hw, idx, p.inv, out_hw, mode, sigma,
                                                      bias, simple, params, label_fill)
         return ops.normalize_img_f32(x, out=x), lab

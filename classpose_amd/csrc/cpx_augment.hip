@@ -796,3 +796,304 @@ extern "C" int cpx_normalize_apply_f32(const float *img, const float *stats, int
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }
+
+// ---------------------------------------------------------------------------
+// image quality (t6): Gaussian blur and hue / brightness / saturation jitter of transforms/image_quality.py
+// ---------------------------------------------------------------------------
+// the colour stage of one pixel, as the pool kernels' taps run it: mode 0 none, 1 hed_pixel, 2 he_pixel
+__device__ __forceinline__ void colour_pixel(const uint8_t *__restrict__ px, int m, const float *sg, const float *bs, int simple_mode,
+                                             const double *par, const double *dens, uint8_t *r) {
+    if (m == 2) he_pixel(px, par, dens, r);
+    else if (m == 1) hed_pixel(px, sg, bs, simple_mode, r);
+    else { r[0] = px[0]; r[1] = px[1]; r[2] = px[2]; }
+}
+
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+
+// _hbs_adjust of one uint8 pixel: torchvision's adjust_hue / adjust_brightness / adjust_saturation in float32, one rounding per
+// operation (ATen's add_(other, alpha=) being one operation: a fused multiply-add).  par = {hue, brightness, saturation, 1 - saturation}; unit = arange(256, float32) / float32(255) from the host.
+__device__ __forceinline__ void hbs_pixel(const uint8_t *px, const float *__restrict__ par, const float *unit, uint8_t *o) {
+    float r = unit[px[0]], g = unit[px[1]], b = unit[px[2]];
+    const float hue = par[0], bright = par[1], sat = par[2], one_minus_sat = par[3];
+    if (hue != 0.0f) {
+        const float maxc = fmaxf(fmaxf(r, g), b), minc = fminf(fminf(r, g), b);
+        const bool eq = maxc == minc;
+        const float cr = maxc - minc;
+        const float s = __fdiv_rn(cr, eq ? 1.0f : maxc);
+        const float d = eq ? 1.0f : cr;
+        const float rc = __fdiv_rn(maxc - r, d), gc = __fdiv_rn(maxc - g, d), bc = __fdiv_rn(maxc - b, d);
+        const float hr = (maxc == r) ? bc - gc : 0.0f;
+        const float hg = (maxc == g && maxc != r) ? (rc + 2.0f) - bc : 0.0f;
+        const float hb = (maxc != g && maxc != r) ? (gc + 4.0f) - rc : 0.0f;
+        float h = fmodf(((hr + hg) + hb) * (float)(1.0 / 6.0) + 1.0f, 1.0f);
+        h = fmodf(h + hue, 1.0f);                                       // remainder(h + hue, 1) with the divisor's sign
+        if (h < 0.0f) h = h + 1.0f;
+        const float h6 = h * 6.0f, fl = floorf(h6), f = h6 - fl;
+        const int i = ((int)fl) % 6;
+        const float v = maxc, sxf = s * f, oms = 1.0f - s;
+        const float q = clamp01((1.0f - sxf) * v), t = clamp01((sxf + oms) * v), p = clamp01(oms * v);
+        r = i == 0 ? v : (i == 1 ? q : (i == 2 ? p : (i == 3 ? p : (i == 4 ? t : v))));
+        g = i == 0 ? t : (i == 1 ? v : (i == 2 ? v : (i == 3 ? q : (i == 4 ? p : p))));
+        b = i == 0 ? p : (i == 1 ? p : (i == 2 ? t : (i == 3 ? v : (i == 4 ? v : q))));
+    }
+    r = clamp01(r * bright); g = clamp01(g * bright); b = clamp01(b * bright);
+    if (sat != 1.0f) {
+        // r.mul(0.2989).add_(g, alpha=0.587).add_(b, alpha=0.114) and x.mul(sat).add_(gray, alpha=1 - sat): ATen's add with
+        // alpha is a fused multiply-add
+        const float gray = __fmaf_rn(b, 0.114f, __fmaf_rn(g, 0.587f, r * 0.2989f));
+        r = clamp01(__fmaf_rn(gray, one_minus_sat, r * sat));
+        g = clamp01(__fmaf_rn(gray, one_minus_sat, g * sat));
+        b = clamp01(__fmaf_rn(gray, one_minus_sat, b * sat));
+    }
+    o[0] = (uint8_t)(int)fminf(fmaxf(r * 255.0f, 0.0f), 255.0f);        // clip(x * 255, 0, 255).astype(uint8): truncation
+    o[1] = (uint8_t)(int)fminf(fmaxf(g * 255.0f, 0.0f), 255.0f);
+    o[2] = (uint8_t)(int)fminf(fmaxf(b * 255.0f, 0.0f), 255.0f);
+}
+
+__global__ void __launch_bounds__(NTHR) k_hbs(const uint8_t *__restrict__ img, const float *__restrict__ hbs,
+                                              const int32_t *__restrict__ apply, const float *__restrict__ unit, int HW,
+                                              uint8_t *__restrict__ out) {
+    __shared__ float s_unit[256];
+    s_unit[threadIdx.x] = unit[threadIdx.x];
+    __syncthreads();
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= HW) return;
+    const size_t t = blockIdx.y;
+    const uint8_t *px = img + (t * HW + p) * 3;
+    uint8_t *o = out + (t * HW + p) * 3;
+    uint8_t r[3] = {px[0], px[1], px[2]};
+    if (apply[t]) hbs_pixel(r, hbs + t * 4, s_unit, r);
+    o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+}
+
+extern "C" int cpx_hbs_u8(const uint8_t *img, int n, int H, int W, const float *hbs, const int32_t *apply, const float *unit,
+                          uint8_t *out, void *stream) {
+    CPX_REQUIRE(img && hbs && apply && unit && out && img != out && n > 0 && n <= 65535 && H > 0 && W > 0);
+    CPX_REQUIRE((long long)H * W < (1ll << 29));
+    hipLaunchKernelGGL(k_hbs, dim3(cpx_cdiv((long long)H * W, NTHR), n), dim3(NTHR), 0, (hipStream_t)stream, img, hbs, apply, unit,
+                       H * W, out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// Gaussian blur of rectangles of pool images, after the colour stage: scipy.ndimage.gaussian_filter(plane, sigma) per channel
+// (mode reflect about the IMAGE's borders, rows first, a truncated uint8 intermediate, double accumulation from the outermost
+// pair of weights inwards).  One workgroup per BLUR_TILE x BLUR_TILE tile of a request's rectangle: the tile with a halo of the
+// request's radius goes through the colour functor once per pixel into three uint8 planes in LDS, the vertical pass writes a
+// second set of planes, the horizontal pass writes the scratch.  No global intermediate.
+// 32 x 32, by measurement: at radius 8 a tile loads and colours (48 / 32)^2 = 2.25 x its pixels against 1.56 x at
+// 64 x 64, but a step blurs a handful of footprints, and four times as many workgroups fill the device: 2.1 .. 2.9 x faster on
+// the blurred crops of a step, 1.2 x with 32 windows at radius 8.  3 * 48 * 48 + 3 * 32 * 48 = 11520 bytes of LDS planes.
+#define BLUR_TILE 32
+#define BLUR_RMAX 8
+#define BLUR_NW (2 * BLUR_RMAX + 1)
+
+__device__ __forceinline__ int reflect_index(int p, int n) {
+    const long long n2 = 2ll * n;
+    long long m = p % n2;
+    if (m < 0) m += n2;
+    return (int)(m < n ? m : n2 - 1 - m);
+}
+
+template <int TILE>
+__global__ void __launch_bounds__(NTHR) k_blur_pool_rects(
+    const uint8_t *__restrict__ pool, const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI, long long pool_px,
+    const int32_t *__restrict__ image_of, const int32_t *__restrict__ rects, const int32_t *__restrict__ radius,
+    const double *__restrict__ weights, const int64_t *__restrict__ scratch_off, int max_h, int max_w,
+    const float *__restrict__ sigma, const float *__restrict__ bias, int simple_mode, const double *__restrict__ params,
+    const double *__restrict__ density, const int32_t *__restrict__ mode, uint8_t *__restrict__ scratch, long long scratch_bytes,
+    int32_t *__restrict__ status) {
+    __shared__ double s_dens[256];
+    __shared__ double s_w[BLUR_NW];
+    constexpr int LD = TILE + 2 * BLUR_RMAX;
+    __shared__ uint8_t s_in[3][LD][LD];
+    __shared__ uint8_t s_mid[3][TILE][LD];
+    const size_t t = blockIdx.y;
+    const int tid = threadIdx.x;
+    // everything below up to the first barrier is uniform over the workgroup
+    const int im = image_of[t];
+    const int y0 = rects[4 * t], x0 = rects[4 * t + 1], rh = rects[4 * t + 2], rw = rects[4 * t + 3], r = radius[t];
+    const long long soff = scratch_off[t];
+    int bad = 0, sh = 0, sw = 0;
+    long long off = 0;
+    if (im < 0 || im >= nI) bad = 1;
+    else {
+        off = px_off[im]; sh = hw[2 * im]; sw = hw[2 * im + 1];
+        if (!pool_entry_ok(off, sh, sw, pool_px)) bad = 2;
+    }
+    if (!bad && (y0 < 0 || x0 < 0 || rh <= 0 || rw <= 0 || rh > max_h || rw > max_w || (long long)y0 + rh > sh ||
+                 (long long)x0 + rw > sw || r < 0 || r > BLUR_RMAX))
+        bad = 4;
+    if (!bad && (soff < 0 || soff > scratch_bytes || 3ll * rh * rw > scratch_bytes - soff)) bad = 8;
+    if (bad) {                                                          // nothing is read or written for this request
+        if (blockIdx.x == 0 && tid == 0) atomicOr(status, bad);
+        return;
+    }
+    const int tiles_x = (rw + TILE - 1) / TILE, tiles_y = (rh + TILE - 1) / TILE;
+    if ((int)blockIdx.x >= tiles_x * tiles_y) return;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int oy = y0 + ty * TILE, ox = x0 + tx * TILE;      // the tile's first output pixel, in image coordinates
+    const int th = min(TILE, y0 + rh - oy), tw = min(TILE, x0 + rw - ox);
+    const int m = mode[t];
+    s_dens[tid] = density[tid];
+    if (tid < BLUR_NW) s_w[tid] = weights[t * BLUR_NW + tid];
+    __syncthreads();
+    const uint8_t *img = pool + 3 * off;
+    const float *sg = sigma + t * 3, *bs = bias + t * 3;
+    const double *par = params + t * HE_NPAR;
+    // tile + halo through the colour functor, reflected about the image's borders
+    const int lh = th + 2 * r, lw = tw + 2 * r;
+    for (int i = tid; i < lh * lw; i += NTHR) {
+        const int ly = i / lw, lx = i - ly * lw;
+        const int gy = reflect_index(oy - r + ly, sh), gx = reflect_index(ox - r + lx, sw);
+        uint8_t c[3];
+        colour_pixel(img + ((long long)gy * sw + gx) * 3, m, sg, bs, simple_mode, par, s_dens, c);
+        s_in[0][ly][lx] = c[0]; s_in[1][ly][lx] = c[1]; s_in[2][ly][lx] = c[2];
+    }
+    __syncthreads();
+    // axis 0: output row ly of the tile is centred on loaded row ly + r
+    for (int i = tid; i < 3 * th * lw; i += NTHR) {
+        const int c = i / (th * lw), rem = i - c * (th * lw), ly = rem / lw, lx = rem - ly * lw;
+        double acc = (double)s_in[c][ly + r][lx] * s_w[r];
+        for (int k = r; k >= 1; --k) acc += ((double)s_in[c][ly + r - k][lx] + (double)s_in[c][ly + r + k][lx]) * s_w[r - k];
+        s_mid[c][ly][lx] = (uint8_t)(int)acc;
+    }
+    __syncthreads();
+    // axis 1, to the request's rectangle in the scratch
+    uint8_t *dst = scratch + soff;
+    for (int i = tid; i < th * tw * 3; i += NTHR) {
+        const int c = i % 3, p = i / 3, ly = p / tw, lx = p - ly * tw;
+        double acc = (double)s_mid[c][ly][lx + r] * s_w[r];
+        for (int k = r; k >= 1; --k) acc += ((double)s_mid[c][ly][lx + r - k] + (double)s_mid[c][ly][lx + r + k]) * s_w[r - k];
+        dst[((long long)(oy - y0 + ly) * rw + (ox - x0 + lx)) * 3 + c] = (uint8_t)(int)acc;
+    }
+}
+
+#ifdef CPX_DEBUG
+static int g_blur_tile = BLUR_TILE;
+extern "C" void cpx_blur_set_tile(int tile) { g_blur_tile = tile == 64 ? 64 : BLUR_TILE; }
+#endif
+
+extern "C" int cpx_blur_pool_rects_u8(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                                      const int32_t *image_of, const int32_t *rects, const int32_t *radius, const double *weights,
+                                      const int64_t *scratch_off, int k, int max_h, int max_w, const float *sigma,
+                                      const float *bias, int simple_mode, const double *stain_params, const double *density,
+                                      const int32_t *mode, uint8_t *scratch, long long scratch_bytes, int32_t *status,
+                                      void *stream) {
+    CPX_REQUIRE(pool_u8 && px_off && hw && image_of && rects && radius && weights && scratch_off && scratch && status);
+    CPX_REQUIRE(sigma && bias && stain_params && density && mode);
+    CPX_REQUIRE(nI > 0 && pool_px > 0 && k > 0 && k <= 65535 && max_h > 0 && max_w > 0 && scratch_bytes > 0);
+    int tile = BLUR_TILE;
+#ifdef CPX_DEBUG
+    tile = g_blur_tile;
+#endif
+    const long long tiles = (long long)cpx_cdiv(max_h, tile) * cpx_cdiv(max_w, tile);
+    CPX_REQUIRE(tiles < (1ll << 31));
+    hipStream_t s = (hipStream_t)stream;
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+#ifdef CPX_DEBUG
+    if (tile == 64)
+        hipLaunchKernelGGL(k_blur_pool_rects<64>, dim3((unsigned)tiles, k), dim3(NTHR), 0, s, pool_u8, px_off, hw, nI, pool_px,
+                           image_of, rects, radius, weights, scratch_off, max_h, max_w, sigma, bias, simple_mode ? 1 : 0, stain_params,
+                           density, mode, scratch, scratch_bytes, status);
+    else
+#endif
+    hipLaunchKernelGGL(k_blur_pool_rects<BLUR_TILE>, dim3((unsigned)tiles, k), dim3(NTHR), 0, s, pool_u8, px_off, hw, nI, pool_px,
+                       image_of, rects, radius, weights, scratch_off, max_h, max_w, sigma, bias, simple_mode ? 1 : 0, stain_params,
+                       density, mode, scratch, scratch_bytes, status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// the taps of cpx_warp_affine_pool_quality_u8: the colour stage of StainTaps, or the bytes of the crop's blurred rectangle in the
+// scratch in its place, then hbs_pixel where the crop's flag is set.  A tap inside the image that the rectangle does not cover is
+// 0, sets status bit 4 and reads nothing.
+struct QualityTaps {
+    const float *sigma, *bias;
+    int simple_mode;
+    const double *params, *dens;
+    const int32_t *mode;
+    const float *hbs, *unit;
+    const int32_t *hbs_apply;
+    const uint8_t *scratch;
+    long long scratch_bytes;
+    const int64_t *ov_off;
+    const int32_t *ov_rect;
+    int32_t *status;
+    __device__ __forceinline__ void tap(size_t t, const uint8_t *img, int sh, int sw, int y, int x, int m, long long so, int do_hbs,
+                                        float *v) const {
+        v[0] = v[1] = v[2] = 0.f;
+        if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) return;
+        uint8_t r[3];
+        if (so >= 0) {
+            const int *rc = ov_rect + 4 * t;
+            const int ry = y - rc[0], rx = x - rc[1];
+            if ((unsigned)ry >= (unsigned)rc[2] || (unsigned)rx >= (unsigned)rc[3]) { atomicOr(status, 16); return; }
+            const uint8_t *px = scratch + so + ((long long)ry * rc[3] + rx) * 3;
+            r[0] = px[0]; r[1] = px[1]; r[2] = px[2];
+        } else {
+            colour_pixel(img + ((long long)y * sw + x) * 3, m, sigma + t * 3, bias + t * 3, simple_mode, params + t * HE_NPAR, dens, r);
+        }
+        if (do_hbs) hbs_pixel(r, hbs + t * 4, unit, r);
+        v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
+    }
+    __device__ __forceinline__ void operator()(size_t t, const uint8_t *img, int sh, int sw, int y0, int x0, float *a, float *b,
+                                               float *d, float *e) const {
+        const int m = mode[t], do_hbs = hbs_apply[t];
+        long long so = ov_off[t];
+        if (so >= 0) {                                                  // a range outside the scratch is never read
+            const int *rc = ov_rect + 4 * t;
+            if (rc[2] <= 0 || rc[3] <= 0 || so > scratch_bytes || 3ll * rc[2] * rc[3] > scratch_bytes - so) {
+                atomicOr(status, 8);
+                a[0] = a[1] = a[2] = b[0] = b[1] = b[2] = d[0] = d[1] = d[2] = e[0] = e[1] = e[2] = 0.f;
+                return;
+            }
+        }
+        tap(t, img, sh, sw, y0, x0, m, so, do_hbs, a);
+        tap(t, img, sh, sw, y0, x0 + 1, m, so, do_hbs, b);
+        tap(t, img, sh, sw, y0 + 1, x0, m, so, do_hbs, d);
+        tap(t, img, sh, sw, y0 + 1, x0 + 1, m, so, do_hbs, e);
+    }
+};
+
+__global__ void __launch_bounds__(NTHR) k_warp_affine_pool_quality(
+    const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab, const int64_t *__restrict__ px_off,
+    const int32_t *__restrict__ hw, int nI, long long pool_px, const int32_t *__restrict__ image_of, const double *__restrict__ inv,
+    const float *__restrict__ sigma, const float *__restrict__ bias, int simple_mode, const double *__restrict__ params,
+    const double *__restrict__ density, const int32_t *__restrict__ mode, const float *__restrict__ hbs,
+    const int32_t *__restrict__ hbs_apply, const float *__restrict__ unit, const uint8_t *__restrict__ scratch,
+    long long scratch_bytes, const int64_t *__restrict__ ov_off, const int32_t *__restrict__ ov_rect, int dh, int dw, int label_fill,
+    float *__restrict__ out, int16_t *__restrict__ lab_out, int32_t *__restrict__ status) {
+    __shared__ double s_dens[256];
+    __shared__ float s_unit[256];
+    s_dens[threadIdx.x] = density[threadIdx.x];
+    s_unit[threadIdx.x] = unit[threadIdx.x];
+    __syncthreads();
+    warp_pool_pixel(pool, pool_lab, px_off, hw, nI, pool_px, image_of, inv, dh, dw, label_fill, out, lab_out, status,
+                    QualityTaps{sigma, bias, simple_mode, params, s_dens, mode, hbs, s_unit, hbs_apply, scratch, scratch_bytes, ov_off,
+                                ov_rect, status});
+}
+
+extern "C" int cpx_warp_affine_pool_quality_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off,
+                                               const int32_t *hw, int nI, long long pool_px, const int32_t *image_of,
+                                               const double *inv, int n, const float *sigma, const float *bias, int simple_mode,
+                                               const double *stain_params, const double *density, const int32_t *mode,
+                                               const float *hbs, const int32_t *hbs_apply, const float *unit, const uint8_t *scratch,
+                                               long long scratch_bytes, const int64_t *override_off, const int32_t *override_rect,
+                                               int dh, int dw, int label_fill, float *out, int16_t *labels_out, int32_t *status,
+                                               void *stream) {
+    CPX_REQUIRE(pool_u8 && px_off && hw && image_of && inv && out && status && nI > 0 && pool_px > 0);
+    CPX_REQUIRE(sigma && bias && stain_params && density && mode && hbs && hbs_apply && unit && override_off && override_rect);
+    CPX_REQUIRE(scratch_bytes >= 0 && (scratch != nullptr || scratch_bytes == 0));
+    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
+    CPX_REQUIRE((pool_lab == nullptr) == (labels_out == nullptr));
+    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
+    hipStream_t s = (hipStream_t)stream;
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_warp_affine_pool_quality, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
+                       px_off, hw, nI, pool_px, image_of, inv, sigma, bias, simple_mode ? 1 : 0, stain_params, density, mode, hbs,
+                       hbs_apply, unit, scratch, scratch_bytes, override_off, override_rect, dh, dw, label_fill, out, labels_out,
+                       status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}

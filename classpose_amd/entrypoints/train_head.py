@@ -23,7 +23,8 @@ four are opt-in, so that a command line without them trains exactly as before.
 (``classpose_amd.train_data``).  The images go to the device once (``augment.ImagePool``); with ``--augment`` every draw of an epoch
 is a fresh random 256 x 256 window of a whole image, without it training runs on a fixed grid of windows, and validation always
 does.  ``--augment he_staining`` / ``hed_he`` re-render the window from its image's own H&E stain basis, fitted once per
-image (``ImagePool.stain_basis``).  Without ``--test_data_path`` the directory is split by ``--train_fraction`` as the reference splits it.  The class count is
+image (``ImagePool.stain_basis``); ``--augment quality`` / ``hed_he_quality`` add the Gaussian blur and the hue /
+brightness / saturation jitter.  Without ``--test_data_path`` the directory is split by ``--train_fraction`` as the reference splits it.  The class count is
 inferred from the labels, and the four options above work from channel 0 without ``--instances``.
 """
 from __future__ import annotations
@@ -65,11 +66,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--cache_features", action=argparse.BooleanOptionalAction, default=True,
                    help="run the frozen backbone once per crop and train from the cached neck features")
-    p.add_argument("--augment", default=None, choices=["hed_only", "he_staining", "hed_he", "geometry", "enhanced"],
+    p.add_argument("--augment", default=None, choices=["hed_only", "he_staining", "hed_he", "quality", "hed_he_quality", "geometry", "enhanced"],
                    help="augment every training batch on the device: hed_only = stain jitter + flip / rotation / scale / crop, "
                         "he_staining = H&E stain-matrix perturbation + the same geometry, hed_he = per image one of the two colour "
-                        "transforms (the colour stage of enhanced) + geometry, geometry = the geometry alone (enhanced is not "
-                        "built: its Gaussian blur and hue / brightness / saturation jitter are missing)")
+                        "transforms (the colour stage of enhanced) + geometry, quality = Gaussian blur + hue / brightness / "
+                        "saturation jitter + geometry, hed_he_quality = hed_he followed by quality (the reference's whole enhanced "
+                        "pipeline; the name enhanced itself is not enabled), geometry = the geometry alone")
     p.add_argument("--scale_range", type=float, default=0.5, help="random scale in [1 - r/2, 1 + r/2] (with --augment)")
     p.add_argument("--augment_label_fill", type=int, default=0,
                    help="class of pixels the warp takes from outside the crop: 0 = background as in the reference, -100 = not annotated")

@@ -847,6 +847,184 @@ def warp_affine_pool_stain(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None,
     return out, lab_out, status
 
 
+# ---- t6: image quality -- Gaussian blur and hue / brightness / saturation (csrc/cpx_augment.hip) ------------------------------
+BLUR_MAX_RADIUS = 8
+_unit_tables: dict = {}
+
+
+def unit_table_host() -> np.ndarray:
+    """``arange(256, float32) / float32(255)``: the float32 value of every byte as ``_hbs_adjust`` forms it, numpy's own division."""
+    return np.arange(256, dtype=np.float32) / np.float32(255)
+
+
+def _unit_table(dev) -> torch.Tensor:
+    key = str(dev)
+    if key not in _unit_tables:
+        _unit_tables[key] = torch.from_numpy(unit_table_host()).to(dev)
+    return _unit_tables[key]
+
+
+def _hbs_args(hbs, apply, n: int, dev, what: str):
+    hbs = torch.zeros((n, 4), dtype=torch.float32) if hbs is None else torch.as_tensor(hbs, dtype=torch.float32)
+    apply = torch.zeros(n, dtype=torch.int32) if apply is None else torch.as_tensor(apply)
+    hbs, apply = hbs.to(dev).contiguous(), apply.to(device=dev, dtype=torch.int32).contiguous()
+    if hbs.shape != (n, 4) or apply.shape != (n,):
+        raise ValueError(f"{what}: hbs is (n, 4) float32 {{hue, brightness, saturation, 1 - saturation}} and apply (n,)")
+    return hbs, apply
+
+
+def hbs(img_u8: torch.Tensor, hbs, apply) -> torch.Tensor:
+    """``_hbs_adjust`` (hue shift, brightness, saturation in float32) on uint8 (n, H, W, 3) device images with the per-image values
+    ``hbs`` (n, 4) float32 {hue, brightness, saturation, 1 - saturation}; image t is transformed where ``apply[t] != 0`` and copied
+    elsewhere."""
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[3] != 3:
+        raise ValueError("hbs: expected uint8 (n, H, W, 3)")
+    img_u8 = img_u8.contiguous()
+    n, H, W, _c = img_u8.shape
+    dev = img_u8.device
+    par, apply = _hbs_args(hbs, apply, n, dev, "hbs")
+    out = torch.empty_like(img_u8)
+    check(_lib.lib().cpx_hbs_u8(ptr(img_u8), n, H, W, ptr(par), ptr(apply), ptr(_unit_table(dev)), ptr(out), _stream(dev)), "hbs_u8")
+    return out
+
+
+def _colour_args(mode, sigma, bias, params, n: int, dev, what: str):
+    """mode (n,) in {0, 1, 2} (None = all 0), sigma / bias (n, 3) float32 and params (n, 14) float64 of the pool kernels' colour
+    stage on ``dev``; what is left out is zeros, and its mode must then not occur."""
+    mode_host = np.zeros(n, np.int64) if mode is None else np.asarray(mode.cpu() if isinstance(mode, torch.Tensor) else mode).astype(np.int64)
+    if mode_host.shape != (n,) or mode_host.min() < 0 or mode_host.max() > 2:
+        raise ValueError(f"{what}: mode is (n,) with values 0, 1, 2")
+    if (sigma is None) != (bias is None) or (sigma is None and (mode_host == 1).any()) or (params is None and (mode_host == 2).any()):
+        raise ValueError(f"{what}: mode 1 needs sigma and bias, mode 2 needs params")
+    sigma = torch.zeros((n, 3), dtype=torch.float32) if sigma is None else torch.as_tensor(sigma, dtype=torch.float32)
+    bias = torch.zeros((n, 3), dtype=torch.float32) if bias is None else torch.as_tensor(bias, dtype=torch.float32)
+    sigma, bias = sigma.to(dev).contiguous(), bias.to(dev).contiguous()
+    if sigma.shape != (n, 3) or bias.shape != (n, 3):
+        raise ValueError(f"{what}: sigma and bias are (n, 3)")
+    params, mode = _stain_args(np.zeros((n, 14)) if params is None else params, mode_host, n, dev, what)
+    return mode, sigma, bias, params
+
+
+def blur_pool_rects(pool_u8: torch.Tensor, px_off: torch.Tensor, hw: torch.Tensor, image_of, rects, radius, weights,
+                    scratch: torch.Tensor | None = None, scratch_off=None, mode=None, sigma=None, bias=None, simple_mode: bool = False,
+                    params=None, check_status: bool = True):
+    """``cpx_blur_pool_rects_u8``: request j is the rectangle ``rects[j]`` = (y0, x0, h, w) of ``scipy.ndimage.gaussian_filter`` (per
+    channel, reflect about the image's borders, uint8 in and out) of image ``image_of[j]`` of the pool AFTER the colour stage of
+    ``warp_affine_pool_stain`` (``mode`` / ``sigma`` / ``bias`` / ``params`` per request; default none), with ``radius[j]`` in 0 .. 8 and
+    ``weights[j]`` (17,) float64 from ``augment.gauss_weights``.  The h * w * 3 bytes go to ``scratch`` (a uint8 device vector) from byte
+    ``scratch_off[j]`` on; both default to a fresh buffer with the rectangles packed back to back.  Returns (scratch, scratch_off (k,)
+    int64 on the host, status (1,) int32: bit 0 / 1 as ``warp_affine_pool``, bit 2 a bad rectangle, bit 3 a range outside the scratch;
+    such a request touches nothing).  ``check_status`` raises ``ValueError`` on a non-zero status."""
+    dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "blur_pool_rects")
+    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
+    k = image_of.numel()
+    rects_host = np.ascontiguousarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects, dtype=np.int64).reshape(-1, 4)
+    radius_host = np.ascontiguousarray(radius.cpu() if isinstance(radius, torch.Tensor) else radius, dtype=np.int64).reshape(-1)
+    weights_host = np.ascontiguousarray(weights.cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64)
+    if image_of.dim() != 1 or k == 0 or rects_host.shape != (k, 4) or radius_host.shape != (k,) or weights_host.shape != (k, 17):
+        raise ValueError("blur_pool_rects: image_of (k,), rects (k, 4), radius (k,) and weights (k, 17) float64 expected")
+    if radius_host.min() < 0 or radius_host.max() > BLUR_MAX_RADIUS:
+        raise ValueError(f"blur_pool_rects: a radius outside 0 .. {BLUR_MAX_RADIUS} (sigma above 2)")
+    if np.abs(rects_host).max() > np.iinfo(np.int32).max:
+        raise ValueError("blur_pool_rects: rectangles are int32")
+    nbytes = 3 * np.maximum(rects_host[:, 2], 0) * np.maximum(rects_host[:, 3], 0)
+    if scratch_off is None:
+        scratch_off = np.concatenate([[0], np.cumsum(nbytes)[:-1]])
+    scratch_off = np.ascontiguousarray(scratch_off, dtype=np.int64)
+    if scratch_off.shape != (k,):
+        raise ValueError("blur_pool_rects: scratch_off is (k,) int64")
+    if scratch is None:
+        scratch = torch.empty(int(max(1, (scratch_off + nbytes).max())), dtype=torch.uint8, device=dev)
+    if scratch.dtype != torch.uint8 or scratch.dim() != 1 or scratch.numel() == 0 or scratch.device != dev or not scratch.is_contiguous():
+        raise ValueError("blur_pool_rects: scratch is a contiguous uint8 vector on the pool's device")
+    max_h, max_w = int(max(1, rects_host[:, 2].max())), int(max(1, rects_host[:, 3].max()))
+    mode, sigma, bias, params = _colour_args(mode, sigma, bias, params, k, dev, "blur_pool_rects")
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    rects_dev = torch.from_numpy(rects_host.astype(np.int32)).to(dev)
+    radius_dev = torch.from_numpy(radius_host.astype(np.int32)).to(dev)
+    weights_dev, off_dev = torch.from_numpy(weights_host).to(dev), torch.from_numpy(scratch_off).to(dev)
+    check(_lib.lib().cpx_blur_pool_rects_u8(ptr(pool_u8), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(rects_dev),
+                                            ptr(radius_dev), ptr(weights_dev), ptr(off_dev), k, max_h, max_w, ptr(sigma), ptr(bias),
+                                            int(bool(simple_mode)), ptr(params), ptr(_stain_table(dev, "density")), ptr(mode),
+                                            ptr(scratch), scratch.numel(), ptr(status), _stream(dev)), "blur_pool_rects_u8")
+    if check_status:
+        bits = int(status.item())
+        if bits:
+            raise ValueError("blur_pool_rects: " + ("an image index outside the pool" if bits & 1 else
+                                                    "a table entry outside the pool" if bits & 2 else
+                                                    "a rectangle outside its image" if bits & 4 else "a range outside the scratch"))
+    return scratch, scratch_off, status
+
+
+def blur(img_u8: torch.Tensor, radius, weights) -> torch.Tensor:
+    """``scipy.ndimage.gaussian_filter(plane, sigma)`` per channel on uint8 (n, H, W, 3) device images, image t with ``radius[t]`` and
+    ``weights[t]`` (17,) float64 of ``augment.gauss_weights(sigma_t)`` (radius 0: a copy).  The images are viewed as a pool of
+    equal-sized images and blurred whole by ``blur_pool_rects``."""
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[3] != 3 or not img_u8.is_cuda:
+        raise ValueError("blur: expected uint8 (n, H, W, 3) on the device")
+    img_u8 = img_u8.contiguous()
+    n, H, W, _c = img_u8.shape
+    dev = img_u8.device
+    px_off = torch.arange(n, dtype=torch.int64, device=dev) * (H * W)
+    hw = torch.tensor([[H, W]] * n, dtype=torch.int32, device=dev)
+    out = torch.empty_like(img_u8)
+    blur_pool_rects(img_u8.view(-1), px_off, hw, np.arange(n), np.tile([0, 0, H, W], (n, 1)), radius, weights, out.view(-1))
+    return out
+
+
+def warp_affine_pool_quality(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None, px_off: torch.Tensor, hw: torch.Tensor, image_of,
+                             inv, out_hw, mode=None, sigma=None, bias=None, simple_mode: bool = False, params=None, hbs=None,
+                             hbs_apply=None, scratch: torch.Tensor | None = None, override_off=None, override_rect=None,
+                             label_fill: int = 0, check_status: bool = True):
+    """``cpx_warp_affine_pool_quality_u8``: ``warp_affine_pool_stain`` plus, per crop, the HBS jitter of ``ops.hbs`` on the in-image taps
+    (``hbs`` (n, 4), ``hbs_apply`` (n,)) and an override source: where ``override_off[t] >= 0`` the in-image taps are read from
+    ``scratch`` at that byte offset as the rectangle ``override_rect[t]`` = (y0, x0, h, w) of the crop's image (what ``blur_pool_rects``
+    wrote) and the colour stage is skipped.  Status bit 4: a tap inside the image but outside the rectangle (it is 0 and nothing is
+    read), bit 3: a range outside the scratch; bits 0 / 1 and the returns as ``warp_affine_pool``."""
+    dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "warp_affine_pool_quality")
+    dh, dw = (int(v) for v in out_hw)
+    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
+    n = image_of.numel()
+    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
+    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
+    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6):
+        raise ValueError("warp_affine_pool_quality: image_of is (n,) and inv (n, 6) float64")
+    mode, sigma, bias, params = _colour_args(mode, sigma, bias, params, n, dev, "warp_affine_pool_quality")
+    par, hbs_apply = _hbs_args(hbs, hbs_apply, n, dev, "warp_affine_pool_quality")
+    if (override_off is None) != (override_rect is None):
+        raise ValueError("warp_affine_pool_quality: override_off and override_rect go together")
+    ov_off = np.full(n, -1, np.int64) if override_off is None else np.ascontiguousarray(override_off, dtype=np.int64)
+    ov_rect = np.zeros((n, 4), np.int32) if override_rect is None else np.ascontiguousarray(override_rect, dtype=np.int32)
+    if ov_off.shape != (n,) or ov_rect.shape != (n, 4):
+        raise ValueError("warp_affine_pool_quality: override_off is (n,) int64 and override_rect (n, 4) int32")
+    if scratch is None and (ov_off >= 0).any():
+        raise ValueError("warp_affine_pool_quality: an override needs the scratch")
+    if scratch is not None and (scratch.dtype != torch.uint8 or scratch.dim() != 1 or scratch.device != dev or not scratch.is_contiguous()):
+        raise ValueError("warp_affine_pool_quality: scratch is a contiguous uint8 vector on the pool's device")
+    lab_out = None
+    if pool_lab is not None:
+        if pool_lab.dtype != torch.int16 or pool_lab.shape != (pool_px,) or pool_lab.device != dev or not pool_lab.is_contiguous():
+            raise ValueError("warp_affine_pool_quality: pool_lab is a contiguous int16 vector of one label per pool pixel on the pool's "
+                             "device")
+        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
+    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ov_off_dev, ov_rect_dev = torch.from_numpy(ov_off).to(dev), torch.from_numpy(ov_rect).to(dev)
+    check(_lib.lib().cpx_warp_affine_pool_quality_u8(
+        ptr(pool_u8), ptr(pool_lab), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv), n, ptr(sigma), ptr(bias),
+        int(bool(simple_mode)), ptr(params), ptr(_stain_table(dev, "density")), ptr(mode), ptr(par), ptr(hbs_apply), ptr(_unit_table(dev)),
+        ptr(scratch), 0 if scratch is None else scratch.numel(), ptr(ov_off_dev), ptr(ov_rect_dev), dh, dw, int(label_fill), ptr(out), ptr(lab_out), ptr(status), _stream(dev)),
+        "warp_affine_pool_quality_u8")
+    if check_status:
+        bits = int(status.item())
+        if bits:
+            raise ValueError("warp_affine_pool_quality: " + ("an image index outside the pool" if bits & 1 else
+                                                             "a table entry outside the pool" if bits & 2 else
+                                                             "a range outside the scratch" if bits & 8 else
+                                                             "a tap outside the crop's blurred rectangle"))
+    return out, lab_out, status
+
+
 def normalize_stats_f32(x: torch.Tensor) -> torch.Tensor:
     """(n, 3, 4) float32 {x01, x99 - x01, mode, x99} of float32 (n, 3, H, W) planes: np.percentile(plane, [1, 99]) exactly."""
     if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():

@@ -309,7 +309,9 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     validation set) next to the final model.  ``cache_features`` runs the backbone once per image; ``transform(X, labels, rng) ->
     (X, labels)``, a host callback per batch for callers who augment, forces the uncached path.
     ``augment`` ("hed_only": stain jitter + geometry, "he_staining": H&E stain-matrix perturbation + geometry, "hed_he": per image
-    one of the two colour transforms + geometry, "geometry": flip / rotation / scale / crop alone) augments every training
+    one of the two colour transforms + geometry, "quality": Gaussian blur and hue / brightness / saturation jitter + geometry,
+    "hed_he_quality": "hed_he" followed by "quality", the reference's whole `enhanced` pipeline, "geometry": flip / rotation /
+    scale / crop alone) augments every training
     batch on the device with ``augment.augment_batch`` (``scale_range``, ``label_fill`` as there), drawing from the epoch's
     generator after the sampling order and after ``transform``, which still runs first.  The training path is then uncached;
     validation is never augmented and its features are still cached when ``cache_features`` is set.

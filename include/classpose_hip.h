@@ -654,6 +654,62 @@ int cpx_warp_affine_pool_stain_u8(const uint8_t *pool_u8, const int16_t *pool_la
                                   int16_t *labels_out, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
+ * t6  image quality: Gaussian blur and hue / brightness / saturation jitter (csrc/cpx_augment.hip)
+ * replaces GaussianBlurTransform.transform (classpose/transforms/image_quality.py:41-75 of the reference) and
+ * HueBrightnessSaturationTransform.transform -> _hbs_adjust (image_quality.py:173-217, :239-276), the image-quality half of the
+ * `enhanced` strategy (transforms/augmentation_configs.py:28-61) as StarDistAugmentation applies it after the colour stage.
+ * The host draws sigma and the three HBS values and forms the Gaussian weights; the device does everything per pixel.
+ * The layout is always [H][W][3]: the reference's guess that an image with H <= 4 (blur) or H == 3 (HBS) is channel-first
+ * is not reproduced.  Every entry runs on `stream` and allocates nothing.
+ * ---------------------------------------------------------------------- */
+/* cpx_hbs_u8: _hbs_adjust (image_quality.py:173-217) on uint8 images of one shape.  img, out [n][H][W][3] (distinct buffers);
+ *   hbs [n][4] float32 = {hue, brightness, saturation, 1 - saturation (formed in double, then rounded)}; apply [n] int32: image t
+ *   is transformed where apply[t] != 0, else copied; unit [256] float32 = arange(256, float32) / float32(255) from the host.
+ *   float32, one rounding per operation: the hue shift (RGB -> HSV, remainder(h + hue, 1), HSV -> RGB) is skipped where
+ *   hue == 0, brightness is clamp(x * brightness, 0, 1), the saturation blend clamp(fma(gray, 1 - sat, x * sat), 0, 1) with
+ *   gray = fma(b, 0.114f, fma(g, 0.587f, r * 0.2989f)) is skipped where sat == 1 (torchvision's add_(other, alpha=) is a fused
+ *   multiply-add in ATen), byte = trunc(clip(x * 255, 0, 255)).                                                             */
+int cpx_hbs_u8(const uint8_t *img, int n, int H, int W, const float *hbs, const int32_t *apply, const float *unit,
+               uint8_t *out, void *stream);
+
+/* cpx_blur_pool_rects_u8: scipy.ndimage.gaussian_filter(plane, sigma) per channel (image_quality.py:57-73) of the
+ *   colour-transformed image, restricted to a rectangle.  Pool layout as in t4.  Request j of k: image image_of[j], rectangle
+ *   rects[j] = {y0, x0, h, w} inside that image (h <= max_h, w <= max_w: the launch covers max_h x max_w), radius[j] in
+ *   0 .. 8 = int(4 sigma + 0.5), weights[j][17] double = phi / sum(phi), phi = exp(-0.5 / sigma^2 * x^2) for
+ *   x = -radius .. radius in [0 .. 2 radius], formed on the host.  The colour stage is the one of cpx_warp_affine_pool_stain_u8
+ *   with the same per-request sigma / bias [k][3], stain_params [k][14], density [256], mode [k] (0 none, 1 jitter, 2 stain
+ *   perturbation).  Written: the h x w x 3 bytes of the rectangle, row-major, from scratch + scratch_off[j] on; the ranges of
+ *   two requests must not overlap.  Arithmetic, exactly scipy's: rows (axis 0) first, then columns; border `reflect` about the
+ *   IMAGE's borders, never the rectangle's (index m = p mod 2n, m < n ? m : 2n - 1 - m); per pass in double
+ *   acc = x[c] w[r], then acc += (x[c - k] + x[c + k]) w[r - k] for k = r .. 1; the value between the passes and the result
+ *   are uint8 by truncation.  One launch, a 32 x 32 tile plus halo per workgroup through LDS; no global intermediate.
+ *   status (ONE int32 word, cleared first): bit 0 an image_of outside [0, nI), bit 1 a table entry outside the pool, bit 2 a
+ *   rectangle that is empty, larger than max_h x max_w or not inside its image, or a radius outside 0 .. 8, bit 3 a scratch
+ *   range outside [0, scratch_bytes); such a request reads and writes nothing.  No pointer is NULL.                          */
+int cpx_blur_pool_rects_u8(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                           const int32_t *image_of, const int32_t *rects, const int32_t *radius, const double *weights,
+                           const int64_t *scratch_off, int k, int max_h, int max_w, const float *sigma, const float *bias,
+                           int simple_mode, const double *stain_params, const double *density, const int32_t *mode,
+                           uint8_t *scratch, long long scratch_bytes, int32_t *status, void *stream);
+
+/* cpx_warp_affine_pool_quality_u8: cpx_warp_affine_pool_stain_u8 with two more inputs per CROP.  hbs [n][4], hbs_apply [n],
+ *   unit [256] as in cpx_hbs_u8: where hbs_apply[t] != 0 every in-image tap goes through the per-pixel function of cpx_hbs_u8
+ *   after the colour stage.  override_off [n] int64, override_rect [n][4] int32 {y0, x0, h, w}: where override_off[t] >= 0 the
+ *   in-image taps of crop t are the bytes scratch[override_off[t] + ((y - y0) w + (x - x0)) 3 + c] (what
+ *   cpx_blur_pool_rects_u8 wrote: colour stage and blur already applied) and the colour stage is skipped; a tap inside the image
+ *   but outside the rectangle is 0, reads nothing and sets status bit 4; a range outside [0, scratch_bytes) sets bit 3 and the
+ *   crop's image is zeros.  Taps outside the image are 0 and the labels come from the pool, as in every pool entry.  Bitwise the
+ *   colour stage, the blur of the whole image, cpx_hbs_u8 of the whole image and cpx_warp_affine_u8, in that order; with no
+ *   flag and no override bitwise cpx_warp_affine_pool_stain_u8.  scratch may be NULL when scratch_bytes == 0.                */
+int cpx_warp_affine_pool_quality_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw,
+                                    int nI, long long pool_px, const int32_t *image_of, const double *inv, int n,
+                                    const float *sigma, const float *bias, int simple_mode, const double *stain_params,
+                                    const double *density, const int32_t *mode, const float *hbs, const int32_t *hbs_apply,
+                                    const float *unit, const uint8_t *scratch, long long scratch_bytes,
+                                    const int64_t *override_off, const int32_t *override_rect, int dh, int dw, int label_fill,
+                                    float *out, int16_t *labels_out, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
  * replaces, per instance, cv2.findContours(cell_mask, RETR_EXTERNAL,
  * CHAIN_APPROX_SIMPLE)[0] + shapely.Polygon(...).is_valid/.centroid/.area/.length
