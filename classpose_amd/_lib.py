@@ -151,6 +151,13 @@ SIGNATURES = {
     "cpx_head_wgrad_workspace_bytes": (_sz, [_i, _i]),
     "cpx_head_wgrad": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "cpx_adamw_step": (_i, [_p, _p, _p, _p, C.c_longlong, _d, _d, _d, _d, _d, _d, _d, _p]),
+    "cpx_unet_wgrad_slab_rows": (_i, []),
+    "cpx_unet_param_layout": (C.c_longlong, [C.POINTER(CpxConvOp), _i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                             C.POINTER(_i), C.POINTER(_i)]),
+    "cpx_unet_refresh_operands": (_i, [C.POINTER(CpxConvOp), _i, _p, _i, _p]),
+    "cpx_unet_backward_workspace_bytes": (_sz, [C.POINTER(CpxConvOp), _i, _i, _i]),
+    "cpx_unet_grad_layout": (_i, [C.POINTER(CpxConvOp), _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "cpx_unet_head_backward": (_i, [C.POINTER(CpxConvOp), _i, _p, _i, _i, _p, _sz, _p, _p, _p, _sz, _p]),
     "cpx_hed_jitter_u8": (_i, [_p, _i, _i, _i, _p, _p, _d, _d, _i, _p, _p, _p]),
     "cpx_warp_affine_u8": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "cpx_warp_affine_f32": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),

@@ -83,3 +83,4 @@ int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, f
 int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *feat, int nS, float *head, int ld_head,
                       int col0, void *workspace, size_t ws_bytes, void *stream);
 size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS);
+void cpx_unet_act_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, size_t *off, int *ld);   // n_ops <= 64

@@ -749,6 +749,12 @@ size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS) {
 extern "C" size_t cpx_unet_workspace_bytes(const cpx_conv_op *ops, int n_ops, int nS, int dtype) {
     return cpx_unet_ws_bytes(dtype, ops, n_ops, nS);
 }
+// the saved activations of the head's backward pass (cpx_train_unet.hip): byte offset and row stride of every op's stored output
+void cpx_unet_act_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, size_t *off, int *ld) {
+    UnetLayout L;
+    unet_layout(dtype, ops, n_ops, nS, L);
+    for (int i = 0; i < n_ops && i < 64; ++i) { off[i] = L.off[i]; ld[i] = L.ld[i]; }
+}
 #ifdef CPX_DEBUG
 // where cpx_unet_head_run leaves each op's output in its workspace: byte offset and row stride (elements).  Op i < n_ops - 1:
 // its output tensor [rows_pad][ld], channels 0 .. cout - 1 valid.  The last op (the convT into the head): its GEMM output

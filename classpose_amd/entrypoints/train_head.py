@@ -8,6 +8,10 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
     python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
         [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
+A checkpoint whose class head is the reference's UNet (``out_class.encoder_blocks.*`` keys) trains with the same flags
+(``classpose_amd.train_unet``); ``--feature_transformation_structure C1 C2 ...`` (at most 4 levels) puts a freshly initialised UNet
+head on a checkpoint's backbone instead, with ``--nclasses`` when the checkpoint has no classes.
+
 Images are ``(N, 256, 256, 3)`` uint8 (normalised per crop like inference does) or ``(N, 3, 256, 256)`` float32 (already
 normalised); labels ``(N, 256, 256)`` integer class maps with -100 where nothing is annotated.  The result is an ordinary
 checkpoint in the reference's key layout: ``predict_wsi`` and ``ClassposeModel`` load it unchanged.
@@ -39,7 +43,7 @@ logger = get_logger(__name__)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Train the 1x1 semantic class head on the device with the backbone frozen")
+    p = argparse.ArgumentParser(description="Train the semantic class head (1x1 or UNet) on the device with the backbone frozen")
     p.add_argument("--images", default=None, help=".npy, (N,256,256,3) uint8 or (N,3,256,256) float32 (with --labels; or --data_path)")
     p.add_argument("--labels", default=None, help=".npy, (N,256,256) integer class maps, -100 = not annotated")
     p.add_argument("--data_path", default=None,
@@ -87,6 +91,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--diam_mean", type=float, default=30.0)
     p.add_argument("--min_train_masks", type=int, default=0,
                    help="drop training crops with fewer masks (the reference's default is 5; here 0 keeps every crop); needs --instances")
+    p.add_argument("--feature_transformation_structure", type=int, nargs="+", default=None,
+                   help="channels per level of a UNet class head (the reference's flag): a checkpoint that has such a head trains it "
+                        "without this flag; given, a checkpoint without one gets a freshly initialised UNet head on its backbone "
+                        "(with --nclasses when it has no classes); at most 4 levels")
     p.add_argument("--save_only_trainable_params", action="store_true")
     p.add_argument("--random_seed", type=int, default=42)
     p.add_argument("--save_path", required=True)
@@ -97,6 +105,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 def check_args(args) -> None:
     """The combinations the parser cannot express; raises ``SystemExit`` with the reason."""
+    fts = getattr(args, "feature_transformation_structure", None)
+    if fts is not None and (len(fts) > 4 or min(fts) < 1):
+        raise SystemExit("--feature_transformation_structure: 1 to 4 positive channel counts (32 x 32 tokens halve once per level "
+                         "and once more in the bottleneck)")
     if args.data_path is not None:
         given = [f for f, v in (("--images", args.images), ("--labels", args.labels), ("--instances", args.instances),
                                 ("--test_images", args.test_images), ("--test_labels", args.test_labels),
@@ -138,7 +150,7 @@ def _load_instances(path, labels, what: str) -> np.ndarray:
 def main_data_path(args) -> None:
     """``--data_path``: whole annotated images of any size, from the reference's directory to a device pool."""
     from .. import augment, dataset_stats, train_data
-    from ..train import HeadTrainer, train_class_head
+    from ..train import make_trainer, train_class_head
     data = train_data.load_dataset(args.data_path)
     logger.info(f"{args.data_path}: {len(data)} images, inferred number of classes: {data.n_classes}")
     data = data.subset(train_data.subsample_indices(len(data), args.subsample_fraction, args.random_seed))
@@ -149,8 +161,9 @@ def main_data_path(args) -> None:
         data, test = data.subset(tr), (None if te is None or len(te) == 0 else data.subset(te))
     logger.info(f"{len(data)} training images, {len(test) if test is not None else 0} validation images")
     nclasses = data.n_classes if args.nclasses is None else args.nclasses
-    trainer = HeadTrainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
-                          class_weights=args.class_weights, weight_decay=args.weight_decay)
+    trainer = make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
+                           feature_transformation_structure=args.feature_transformation_structure,
+                           class_weights=args.class_weights, weight_decay=args.weight_decay)
     if data.n_classes > trainer.nclasses:
         raise SystemExit(f"the labels hold class {data.n_classes - 1} but the head has {trainer.nclasses} classes")
     train_probs = diameters = None
@@ -198,15 +211,16 @@ def main_data_path(args) -> None:
 
 def main(args) -> None:
     from .. import dataset_stats
-    from ..train import HeadTrainer, train_class_head
+    from ..train import make_trainer, train_class_head
     check_args(args)
     if args.data_path is not None:
         return main_data_path(args)
     images, labels = np.load(args.images), np.load(args.labels)
     test_images = np.load(args.test_images) if args.test_images else None
     test_labels = np.load(args.test_labels) if args.test_labels else None
-    trainer = HeadTrainer(args.pretrained_model, nclasses=args.nclasses, device=args.device, precision=args.precision,
-                          class_weights=args.class_weights, weight_decay=args.weight_decay)
+    trainer = make_trainer(args.pretrained_model, nclasses=args.nclasses, device=args.device, precision=args.precision,
+                           feature_transformation_structure=args.feature_transformation_structure,
+                           class_weights=args.class_weights, weight_decay=args.weight_decay)
     train_probs = diameters = None
     if args.instances is not None:
         stats = dataset_stats.label_stats(_load_instances(args.instances, labels, "--instances"), labels, trainer.nclasses,

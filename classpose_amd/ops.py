@@ -604,6 +604,32 @@ def round_weights(src: torch.Tensor, dst_ptr: int, dtype_code: int, keep_f32: bo
     check(_lib.lib().cpx_round_weights(ptr(src), dst_ptr, src.numel(), dtype_code, int(keep_f32), _stream(src.device)), "round_weights")
 
 
+def unet_head_backward(weights, feat: torch.Tensor, fwd_ws: torch.Tensor, dlogits: torch.Tensor, grads: torch.Tensor,
+                       workspace: torch.Tensor) -> torch.Tensor:
+    """``cpx_unet_head_backward``: the gradient of every packed operand and bias of the UNet head of ``weights``
+    (an ``engine.NetWeights``) into the flat float32 ``grads``.  ``feat`` (n * 1024, 256) in the network dtype, ``fwd_ws`` the
+    workspace ``cpx_unet_head_forward`` ran this batch in, ``dlogits`` (n * 1024, ncls * 64) float32, ``workspace`` uint8 of at
+    least ``cpx_unet_backward_workspace_bytes``."""
+    c = weights.c
+    L = _lib.lib()
+    if not c.n_unet_ops:
+        raise ValueError("unet_head_backward: the weights have no UNet head")
+    if feat.dim() != 2 or feat.shape[1] != 256 or feat.shape[0] % 1024 or feat.dtype not in _DT or _DT[feat.dtype] != c.dtype \
+            or not feat.is_contiguous():
+        raise ValueError("unet_head_backward: feat must be contiguous (n * 1024, 256) in the network dtype")
+    nS = feat.shape[0] // 1024
+    if dlogits.dtype != torch.float32 or tuple(dlogits.shape) != (feat.shape[0], c.ncls * 64) or not dlogits.is_contiguous():
+        raise ValueError("unet_head_backward: dlogits must be contiguous float32 (n * 1024, ncls * 64)")
+    if grads.dtype != torch.float32 or not grads.is_contiguous() or \
+            grads.numel() != L.cpx_unet_param_layout(c.unet_ops, c.n_unet_ops, None, None, None, None):
+        raise ValueError("unet_head_backward: grads must be the flat float32 buffer of cpx_unet_param_layout")
+    if workspace.dtype != torch.uint8 or fwd_ws.dtype != torch.uint8:
+        raise ValueError("unet_head_backward: workspaces are uint8 tensors")
+    check(L.cpx_unet_head_backward(c.unet_ops, c.n_unet_ops, ptr(feat), nS, c.dtype, ptr(fwd_ws), fwd_ws.numel(), ptr(dlogits),
+                                   ptr(grads), ptr(workspace), workspace.numel(), _stream(feat.device)), "unet_head_backward")
+    return grads
+
+
 # ---- t2: training-time augmentation (csrc/cpx_augment.hip) --------------------------------------------------------
 def hed_jitter(img_u8: torch.Tensor, sigma: torch.Tensor, bias: torch.Tensor, cutoff_range=(0.15, 0.85),
                simple_mode: bool = False):

@@ -17,6 +17,10 @@ Deliberately different from the reference:
     ``train_class_head``, fed by ``classpose_amd.dataset_stats``; the reference's command line has both on by default;
   * no HDF5 datasets, learned loss weighting, multi-GPU exchange or optimiser-state resume.
 
+The reference's other class head, the UNet of ``--feature_transformation_structure``, is trained by
+``train_unet.UNetHeadTrainer`` (same public surface; ``make_trainer`` picks the trainer from the checkpoint, and
+``train_class_head`` runs with either).
+
 A trainer owns its ``engine.NetWeights`` and updates the head operands in place: sharing them with an ``Engine`` that is running on
 another stream is the caller's risk.
 """
@@ -252,6 +256,14 @@ class HeadTrainer:
         if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
             sd = {k: sd[k] for k in ("out_class.weight", "out_class.bias")}
         torch.save(sd, os.fspath(path))
+
+
+def make_trainer(pretrained_model, nclasses: int | None = None, feature_transformation_structure=None, **kw):
+    """The trainer of a checkpoint's class head: ``train_unet.UNetHeadTrainer`` when the state dict has
+    ``out_class.encoder_blocks.*`` keys (or a fresh UNet head of ``feature_transformation_structure`` is asked for),
+    ``HeadTrainer`` otherwise.  ``kw``: the arguments both trainers share."""
+    from . import train_unet
+    return train_unet.make_trainer(pretrained_model, nclasses, feature_transformation_structure, **kw)
 
 
 def _check_dataset(images, labels, what: str):

@@ -1,0 +1,306 @@
+"""Fine-tuning the UNet semantic head (``--feature_transformation_structure``, classpose/unet.py:121-196) on the device with
+the backbone, the neck and the flow head frozen.
+
+The companion of ``train.HeadTrainer`` for checkpoints whose ``out_class`` is ``classpose.unet.UNet``: the forward is the
+inference head (``cpx_unet_head_forward``, which leaves every op's output in its workspace -- the saved activations), the loss and
+its gradient are ``cpx_class_loss``, the backward through the op list is ``cpx_unet_head_backward`` (csrc/cpx_train_unet.hip) and
+the update is ONE ``cpx_adamw_step`` over a flat float32 buffer that holds every packed operand ``[Npad][Kpad]`` followed by its
+bias ``[Npad]``, in op order -- the layout of ``engine.NetWeights._build_unet_ops``.  The reference's key layout
+(``out_class.encoder_blocks.N.block.conv1.weight`` ...) exists only in ``state_dict()``.
+
+Numerics contract: the forward multiplies operands rounded to the network dtype and stores every op's output in it; the backward
+is float32 throughout and treats both roundings as the identity (straight-through), with the ReLU mask "stored output > 0" and
+the data gradient taken through the ROUNDED operand.  Padded channels and the operand padding receive exact zero gradients, so
+they stay exact zeros under AdamW.  No atomics: a step is bitwise reproducible.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, engine, ops
+from ._lib import check, ptr
+from .train import TOKENS, HeadTrainer
+
+MAX_LEVELS = 4          # 32 x 32 tokens halve once per level and once more in the bottleneck (engine.NetWeights.from_state_dict)
+
+
+def _up(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
+
+
+def check_structure(fts) -> list[int]:
+    fts = [int(c) for c in fts]
+    if not fts or any(c < 1 for c in fts):
+        raise ValueError("feature_transformation_structure: one positive channel count per level")
+    if len(fts) > MAX_LEVELS:
+        raise ValueError(f"UNet semantic head: at most {MAX_LEVELS} encoder levels fit the 32 x 32 token grid")
+    return fts
+
+
+def unet_plan(fts, out_ch: int) -> list[tuple[str, int, int, int, int]]:
+    """The convolutions of classpose.unet.UNet(256, out_ch, fts) in the op order of ``_build_unet_ops``:
+    (state-dict prefix, kind, cin_a, cin_b, cout) with the REAL channel counts; kind 0: 3x3, 1: 2x2 stride 2, 2: transposed 2x2."""
+    plan = []
+
+    def block(pfx, cin_a, cin_b, cout):
+        plan.append((pfx + "block.conv1", 0, cin_a, cin_b, cout))
+        plan.append((pfx + "block.conv2", 0, cout, 0, cout))
+
+    cin = 256
+    for n, c in enumerate(fts):
+        p = f"out_class.encoder_blocks.{n}."
+        block(p, cin, 0, c)
+        plan.append((p + "downconv", 1, c, 0, c))
+        cin = c
+    c = fts[-1]
+    block("out_class.bottleneck_down.", c, 0, c)
+    plan.append(("out_class.bottleneck_down.downconv", 1, c, 0, c))
+    block("out_class.bottleneck_up.", c, 0, c)
+    plan.append(("out_class.bottleneck_up.upconv", 2, c, 0, c))
+    seq = [*fts[::-1], out_ch]
+    for i in range(len(fts)):
+        p = f"out_class.decoder_blocks.{i}."
+        block(p, seq[i], seq[i], seq[i + 1])
+        plan.append((p + "upconv", 2, seq[i + 1], 0, seq[i + 1]))
+    return plan
+
+
+def param_layout(fts, out_ch: int):
+    """(total elements, [(w_off, b_off, Npad, Kpad)] per op) of the flat parameter buffer -- what ``cpx_unet_param_layout`` returns
+    for the op list ``_build_unet_ops`` makes of this structure."""
+    p8 = lambda c: _up(c, 8)
+    off, lay = 0, []
+    for _key, kind, ca, cb, co in unet_plan(fts, out_ch):
+        taps = (9, 4, 1)[kind]
+        n_pad = _up(4 * p8(co) if kind == 2 else p8(co), 128)
+        k_pad = _up(taps * (p8(ca) + p8(cb)), 64)
+        lay.append((off, off + n_pad * k_pad, n_pad, k_pad))
+        off += n_pad * k_pad + n_pad
+    return off, lay
+
+
+def pack_params(sd: dict, fts, out_ch: int) -> torch.Tensor:
+    """State dict (reference keys) -> the flat float32 buffer; values are taken as they are (no rounding)."""
+    p8 = lambda c: _up(c, 8)
+    total, lay = param_layout(fts, out_ch)
+    flat = torch.zeros(total, dtype=torch.float32)
+    for (key, kind, cin_a, cin_b, cout), (w_off, b_off, n_pad, k_pad) in zip(unet_plan(fts, out_ch), lay):
+        w, b = sd[key + ".weight"].detach().float(), sd[key + ".bias"].detach().float()
+        ca, cb, co = p8(cin_a), p8(cin_b), p8(cout)
+        if kind == 2:           # ConvTranspose2d [cin][cout][2][2] -> rows (dy, dx, co), cols ci
+            if tuple(w.shape) != (cin_a, cout, 2, 2):
+                raise ValueError(f"{key}.weight: expected {(cin_a, cout, 2, 2)}, got {tuple(w.shape)}")
+            wt = torch.zeros(2, 2, co, ca)
+            wt[:, :, :cout, :cin_a] = w.permute(2, 3, 1, 0)
+            wm = wt.reshape(4 * co, ca)
+            bt = torch.zeros(4, co)
+            bt[:, :cout] = b[None, :]
+            bm = bt.reshape(-1)
+        else:                   # Conv2d [cout][cin_a + cin_b][k][k] -> cols (ky, kx, ci of a | ci of b)
+            k = 3 if kind == 0 else 2
+            if tuple(w.shape) != (cout, cin_a + cin_b, k, k):
+                raise ValueError(f"{key}.weight: expected {(cout, cin_a + cin_b, k, k)}, got {tuple(w.shape)}")
+            wt = torch.zeros(co, k, k, ca + cb)
+            wk = w.permute(0, 2, 3, 1)
+            wt[:cout, :, :, :cin_a] = wk[..., :cin_a]
+            wt[:cout, :, :, ca:ca + cin_b] = wk[..., cin_a:]
+            wm = wt.reshape(co, -1)
+            bm = torch.zeros(co)
+            bm[:cout] = b
+        W = flat[w_off:w_off + n_pad * k_pad].view(n_pad, k_pad)
+        W[:wm.shape[0], :wm.shape[1]] = wm
+        flat[b_off:b_off + bm.shape[0]] = bm
+    return flat
+
+
+def unpack_params(flat: torch.Tensor, fts, out_ch: int) -> dict:
+    """The inverse of ``pack_params``: {reference key: float32 tensor}."""
+    p8 = lambda c: _up(c, 8)
+    flat = flat.detach().float().cpu()
+    total, lay = param_layout(fts, out_ch)
+    if flat.numel() != total:
+        raise ValueError(f"unpack_params: {flat.numel()} elements, the structure has {total}")
+    sd = {}
+    for (key, kind, cin_a, cin_b, cout), (w_off, b_off, n_pad, k_pad) in zip(unet_plan(fts, out_ch), lay):
+        ca, cb, co = p8(cin_a), p8(cin_b), p8(cout)
+        W = flat[w_off:w_off + n_pad * k_pad].view(n_pad, k_pad)
+        if kind == 2:
+            wt = W[:4 * co, :ca].reshape(2, 2, co, ca)
+            sd[key + ".weight"] = wt[:, :, :cout, :cin_a].permute(3, 2, 0, 1).contiguous()
+            sd[key + ".bias"] = flat[b_off:b_off + cout].clone()
+        else:
+            k = 3 if kind == 0 else 2
+            wt = W[:co, :k * k * (ca + cb)].reshape(co, k, k, ca + cb)
+            wk = torch.cat([wt[:cout, :, :, :cin_a], wt[:cout, :, :, ca:ca + cin_b]], -1)
+            sd[key + ".weight"] = wk.permute(0, 3, 1, 2).contiguous()
+            sd[key + ".bias"] = flat[b_off:b_off + cout].clone()
+    return sd
+
+
+def fresh_unet_head(fts, nclasses: int, head_seed: int = 0) -> dict:
+    """A freshly initialised ``UNet(256, nclasses * 64, fts)`` as state-dict entries plus ``W3``: torch's default
+    ``Conv2d`` / ``ConvTranspose2d`` initialisation (kaiming_uniform_(a = sqrt(5)) and the matching bias bound, both
+    1 / sqrt(fan_in); a transposed conv's fan_in is cout * 4), drawn from a generator seeded with ``head_seed``."""
+    fts = check_structure(fts)
+    if nclasses is None or nclasses < 2:
+        raise ValueError("a fresh UNet head needs nclasses >= 2")
+    g = torch.Generator().manual_seed(head_seed)
+    oc = nclasses * 64
+    sd = {}
+    for key, kind, cin_a, cin_b, cout in unet_plan(fts, oc):
+        k = 3 if kind == 0 else 2
+        shape = (cin_a, cout, 2, 2) if kind == 2 else (cout, cin_a + cin_b, k, k)
+        bound = 1.0 / np.sqrt(float(shape[1] * k * k))
+        sd[key + ".weight"] = (torch.rand(shape, generator=g) * 2 - 1) * bound
+        sd[key + ".bias"] = (torch.rand(cout, generator=g) * 2 - 1) * bound
+    sd["W3"] = torch.eye(oc).reshape(oc, nclasses, 8, 8)
+    return sd
+
+
+def has_unet_head(sd: dict) -> bool:
+    return any(k.removeprefix("module.").startswith("out_class.encoder_blocks.") for k in sd)
+
+
+def prepare_unet_state_dict(pretrained_model, nclasses: int | None = None, head_seed: int = 0,
+                            feature_transformation_structure=None) -> tuple[dict, int, list[int]]:
+    """(state dict with a UNet ``out_class`` in the reference's key layout, class count, channel list).  With
+    ``feature_transformation_structure`` a checkpoint without a UNet head gets a fresh one on its backbone (its 1x1 head, if any, is
+    dropped; the class count is the checkpoint's, or ``nclasses`` when it has none); a checkpoint that has one must match.  Host only."""
+    sd = pretrained_model if isinstance(pretrained_model, dict) else \
+        torch.load(os.fspath(pretrained_model), map_location="cpu", weights_only=True)
+    sd = {k.removeprefix("module."): v for k, v in sd.items()}
+    want = None if feature_transformation_structure is None else check_structure(feature_transformation_structure)
+    if has_unet_head(sd):
+        fts, ncls, _depth = engine.NetWeights.infer_structure(sd)
+        fts = check_structure(fts)
+        if want is not None and want != fts:
+            raise ValueError(f"the checkpoint's UNet head has channels {fts}, not {want}")
+        if ncls < 2:
+            raise ValueError("the checkpoint's UNet head has no W3: cannot tell its class count")
+    else:
+        if want is None:
+            raise ValueError("the checkpoint has no UNet semantic head: pass feature_transformation_structure to initialise one")
+        ncls = sd["W3"].shape[1] if "W3" in sd and sd["W3"].shape[1] >= 2 else nclasses
+        if ncls is None or ncls < 2:
+            raise ValueError("the checkpoint has no semantic head: pass nclasses >= 2 to initialise one")
+        sd = {k: v for k, v in sd.items() if not k.startswith("out_class.")}
+        sd.update(fresh_unet_head(want, ncls, head_seed))
+        fts = want
+    if nclasses is not None and nclasses != ncls:
+        raise ValueError(f"nclasses={nclasses} but the checkpoint's head has {ncls} classes")
+    plan = unet_plan(fts, ncls * 64)
+    missing = [k + s for k, *_ in plan for s in (".weight", ".bias") if k + s not in sd]
+    if missing:
+        raise ValueError(f"UNet head: the checkpoint lacks {missing[0]} (and {len(missing) - 1} more)")
+    return sd, ncls, fts
+
+
+class UNetHeadTrainer(HeadTrainer):
+    """Trains ``out_class`` = ``classpose.unet.UNet(256, nclasses * 64, fts)`` of a checkpoint; everything else stays as loaded.
+    The public surface is ``HeadTrainer``'s, and ``train.train_class_head`` runs with either."""
+
+    def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
+                 weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
+                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, feature_transformation_structure=None):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
+        self.sd, self.nclasses, self.fts = prepare_unet_state_dict(pretrained_model, nclasses, head_seed, feature_transformation_structure)
+        self.precision = precision
+        self.weights = engine.NetWeights.from_state_dict(self.sd, precision, self.device)
+        self.dtype = engine.NET_DTYPES[precision]
+        self.weight_decay, self.alpha, self.gamma, self.eps = weight_decay, alpha, gamma, eps
+        self.betas, self.adam_eps = betas, adam_eps
+        self.w_ce, self.w_tv = 1.0, 1.0                  # LossAggregator(optimise=False): both multipliers exp(-0) = 1
+        dev = self.device
+        self.set_class_weights(class_weights)
+        c = self.weights.c
+        self._L = L = _lib.lib()
+        n = c.n_unet_ops
+        total, self.layout = param_layout(self.fts, self.nclasses * 64)
+        w_off, b_off, n_pad, k_pad = (C.c_longlong * n)(), (C.c_longlong * n)(), (C.c_int * n)(), (C.c_int * n)()
+        if L.cpx_unet_param_layout(c.unet_ops, n, w_off, b_off, n_pad, k_pad) != total or \
+                [tuple(t) for t in zip(w_off, b_off, n_pad, k_pad)] != self.layout:
+            raise _lib.CpxError("UNetHeadTrainer: the host's parameter layout differs from the library's")
+        self.params = pack_params(self.sd, self.fts, self.nclasses * 64).to(dev)         # float32 master copy
+        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
+        self.n_steps = 0
+        self.feature_batch = int(feature_batch)
+        nS = self.feature_batch
+        nbytes = L.cpx_net_workspace_bytes(nS, c.dtype) + L.cpx_unet_workspace_bytes(c.unet_ops, n, nS, c.dtype)
+        self._net_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._head_fb = torch.empty((nS * TOKENS, c.ld_head), dtype=torch.float32, device=dev)
+        self._es = torch.empty(0, dtype=self.dtype).element_size()
+        self._buf: dict = {}
+
+    def head(self, feat: torch.Tensor) -> torch.Tensor:
+        """The head launches of ``cpx_net_forward`` on ``feat``: float32 (rows, ld_head), flow columns 0..191 from the head GEMM,
+        class columns from 192 written by the UNet, whose workspace then holds the saved activations of this batch."""
+        out = super().head(feat)
+        c = self.weights.c
+        nS = feat.shape[0] // TOKENS
+        key = ("uws", nS)
+        if key not in self._buf:
+            self._buf[key] = torch.empty(self._L.cpx_unet_workspace_bytes(c.unet_ops, c.n_unet_ops, nS, c.dtype), dtype=torch.uint8,
+                                         device=self.device)
+        ws = self._buf[key]
+        check(self._L.cpx_unet_head_forward(c.unet_ops, c.n_unet_ops, ptr(feat), nS, ptr(out), c.ld_head, 192, c.dtype, ptr(ws),
+                                            ws.numel(), torch.cuda.current_stream(self.device).cuda_stream), "unet_head_forward")
+        return out
+
+    def backward(self, feat: torch.Tensor, dlogits: torch.Tensor) -> torch.Tensor:
+        """``self.grads`` (flat, float32) of the batch whose forward ``head(feat)`` ran last; ``dlogits`` from ``cpx_class_loss``."""
+        nS = feat.shape[0] // TOKENS
+        ops.unet_head_backward(self.weights, feat, self._buf[("uws", nS)], dlogits, self.grads, self._bwd_ws(nS))
+        return self.grads
+
+    def _bwd_ws(self, nS: int) -> torch.Tensor:
+        key = ("bws", nS)
+        if key not in self._buf:
+            c = self.weights.c
+            self._buf[key] = torch.empty(self._L.cpx_unet_backward_workspace_bytes(c.unet_ops, c.n_unet_ops, nS, c.dtype),
+                                         dtype=torch.uint8, device=self.device)
+        return self._buf[key]
+
+    def step(self, X, labels, lr: float) -> dict:
+        """One optimisation step on a batch of crops (or of cached ``features``) at learning rate ``lr``; returns the losses of the
+        batch BEFORE the update, like the reference's loop."""
+        feat, _head, o = self._loss(X, labels)            # raises before anything is updated
+        self.backward(feat, o.dlogits)
+        self.n_steps += 1
+        ops.adamw_step(self.params, self.grads, self.m, self.v, self.n_steps, lr, betas=self.betas, eps=self.adam_eps,
+                       weight_decay=self.weight_decay)    # net.parameters(): decay on the biases too
+        self._refresh_operands()
+        return self._result(o, feat.shape[0] // TOKENS)
+
+    def _refresh_operands(self) -> None:
+        """Master parameters -> the operands the op list points at, rounded as at load."""
+        c = self.weights.c
+        check(self._L.cpx_unet_refresh_operands(c.unet_ops, c.n_unet_ops, ptr(self.params), c.dtype,
+                                                torch.cuda.current_stream(self.device).cuda_stream), "unet_refresh_operands")
+
+    def state_dict(self) -> dict:
+        """The checkpoint in the reference's key layout: every ``out_class.*`` entry from the master parameters, the rest as loaded."""
+        sd = dict(self.sd)
+        sd.update(unpack_params(self.params, self.fts, self.nclasses * 64))
+        return sd
+
+    def save(self, path, save_only_trainable_params: bool = False) -> None:
+        sd = self.state_dict()
+        if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
+            sd = {k: v for k, v in sd.items() if k.startswith("out_class.")}
+        torch.save(sd, os.fspath(path))
+
+
+def make_trainer(pretrained_model, nclasses: int | None = None, feature_transformation_structure=None, **kw):
+    """``UNetHeadTrainer`` for a checkpoint with ``out_class.encoder_blocks.*`` keys (or when a structure is asked for),
+    ``HeadTrainer`` otherwise; ``kw`` are the trainers' common arguments."""
+    sd = pretrained_model if isinstance(pretrained_model, dict) else \
+        torch.load(os.fspath(pretrained_model), map_location="cpu", weights_only=True)
+    if feature_transformation_structure is not None or has_unet_head(sd):
+        return UNetHeadTrainer(sd, nclasses, feature_transformation_structure=feature_transformation_structure, **kw)
+    return HeadTrainer(sd, nclasses, **kw)

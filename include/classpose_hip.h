@@ -510,6 +510,33 @@ int cpx_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_a
                    double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
                    double bias_correction2, void *stream);
 
+/* Training the UNet semantic head (csrc/cpx_train_unet.hip): what autograd does for classpose.unet.UNet (unet.py:121-196) under
+ * train_class_seg (train.py:482-493) with the backbone and the neck frozen, on the op list that cpx_unet_head_forward runs.  That
+ * forward leaves every op's output, in the network dtype, in its workspace: those are the saved activations.
+ *   Parameters, gradients and the AdamW moments are ONE flat float32 buffer each: per op its packed operand [Npad][Kpad] (the
+ *   layout of cpx_conv_op.weight) followed by its bias [Npad]; cpx_unet_param_layout returns the element count and, where the
+ *   pointers are not NULL, the element offsets and the padded sizes per op.
+ *   cpx_unet_refresh_operands rounds the flat master parameters into the operands the ops point at (cpx_round_weights each: the
+ *   weight to the network dtype, the bias through it and back to float32), as NetWeights builds them at load.
+ *   cpx_unet_head_backward: feat [nS*1024][256] of `dtype` (tensor 0), the forward's workspace, dlogits [nS*1024][ncls*64] float32
+ *   (cpx_class_loss) -> grads (flat, float32).  Ops are walked in reverse; per op dW = dY^T im2col(X) and db = column sums of dY on
+ *   the exact float32 matrix instruction v_mfma_f32_32x32x2_f32 over slabs of cpx_unet_wgrad_slab_rows rows of an im2col operand
+ *   that is gathered from the stored tensors, never materialised (per-slab partials added in slab order in float64, rounded once),
+ *   and dX = col2im(dY W) with the rounded operand in float32 (the float32 GEMM of cpx_gemm on the transposed operand, then a gather
+ *   that adds the taps in tap order, splits the a|b concat, adds a second consumer's contribution to the first's and lets the
+ *   last one apply the producer's ReLU mask, stored output > 0).  Rounding to the network dtype is the identity in the backward
+ *   (straight-through); the neck output gets no gradient.  No atomics: bitwise reproducible.  Padded channels and the Npad / Kpad
+ *   padding get exact zeros.  The workspace holds, at cpx_unet_grad_layout's byte offsets, the gradient [rows_pad][ld] float32
+ *   with respect to every op's output but the last (whose gradient is dlogits), after the ReLU mask of that op.              */
+int cpx_unet_wgrad_slab_rows(void);
+long long cpx_unet_param_layout(const cpx_conv_op *ops_host, int n_ops, long long *w_off, long long *b_off, int *n_pad, int *k_pad);
+int cpx_unet_refresh_operands(const cpx_conv_op *ops_host, int n_ops, const float *params, int dtype, void *stream);
+size_t cpx_unet_backward_workspace_bytes(const cpx_conv_op *ops_host, int n_ops, int n_subtiles, int dtype);
+int cpx_unet_grad_layout(const cpx_conv_op *ops_host, int n_ops, int n_subtiles, int dtype, size_t *g_off, int *g_ld);
+int cpx_unet_head_backward(const cpx_conv_op *ops_host, int n_ops, const void *feat, int n_subtiles, int dtype,
+                           const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dlogits, float *grads,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------
  * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)
  * replaces augment_single_image, /root/reference/src/classpose/dataset.py:23-56: the stain jitter, cellpose's
