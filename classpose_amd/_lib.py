@@ -177,6 +177,10 @@ SIGNATURES = {
                                     C.c_longlong, _p, _p]),
     "cpx_warp_affine_pool_quality_u8": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
                                              C.c_longlong, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "cpx_masks_to_flows": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "cpx_warp_affine_pool_flow_f32": (_i, [_p, _p, _p, _i, C.c_longlong, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "cpx_seg_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cpx_seg_loss": (_i, [_p, _i, _p, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
     "cpx_find_contours_ccomp_host": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _i]),
     "cpx_polygonize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cpx_polygonize_device": (_i, [_p, _p, _p, _i, _i, _i, _i, _d, _p, _p, _i, _p, _p, _p, _p]),

@@ -187,6 +187,24 @@ def identity_maps(n: int) -> np.ndarray:
     return np.tile(np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), (n, 1))
 
 
+def flow_vec(flip, theta) -> np.ndarray:
+    """(n, 4) float64 vector matrices of ``ops.warp_flow_targets`` for the draws ``flip`` / ``theta`` of ``sample_affine_params``:
+    ``[cos t, f sin t, -sin t, f cos t]`` with ``f = -1`` where flipped, ``+1`` otherwise, so that ``Y' = vec[0] Y + vec[1] X`` and
+    ``X' = vec[2] Y + vec[3] X``.  Restated from the flow branch of cellpose 4.0.x ``transforms.random_rotate_and_resize`` (unpinned,
+    like ``sample_affine``): the X flow of a flipped source is negated, then ``Y' = X sin t + Y cos t``, ``X' = X cos t - Y sin t``.
+    The scale does not rescale the vectors."""
+    flip, theta = np.asarray(flip, bool).reshape(-1), np.asarray(theta, np.float64).reshape(-1)
+    if flip.shape != theta.shape:
+        raise ValueError("flow_vec: one flip and one theta per crop")
+    f = np.where(flip, -1.0, 1.0)
+    c, s = np.cos(theta), np.sin(theta)
+    return np.stack([c, f * s, -s, f * c], 1)
+
+
+def identity_vecs(n: int) -> np.ndarray:
+    return np.tile(np.array([1.0, 0.0, 0.0, 1.0]), (n, 1))
+
+
 def sample_hed(rng: np.random.Generator, n: int, sigma_ranges, bias_ranges):
     """(sigma, bias) float32 (n, 3): per image three sigmas, then three biases, uniform in their ranges -- the order of
     ``HEDTransform.sample_sigma`` / ``sample_bias``.  One ``rng.uniform`` call of shape (n, 2, 3); images outside the cut-off consume
@@ -338,6 +356,7 @@ class BatchParams:
     hbs_hue: np.ndarray | None = None       # (n,) float64 in +-hue
     hbs_brightness: np.ndarray | None = None    # (n,) float64 in +-brightness: the factor is 1 + this
     hbs_saturation: np.ndarray | None = None    # (n,) float64 in the saturation range
+    theta: np.ndarray | None = None         # (n,) float64, the rotation of the affine draw (zeros without geometry): ``flow_vec`` needs it
 
 
 def quality_params(p: BatchParams, config: dict):
@@ -392,11 +411,13 @@ def sample_batch_params(rng: np.random.Generator, n: int, sh, sw, config: dict |
     if _has_he(config):
         gate, U, u = sample_he(rng, n)
     quality = sample_quality(rng, n, config) if _has_quality(config) else (None,) * 6
-    if geometry:
-        flip, inv = sample_affine(rng, n, sh, sw, out, scale_range, rescale=rescale)
+    if geometry:                                              # sample_affine, keeping the rotation it drew
+        a = sample_affine_params(rng, n, sh, sw, out, scale_range, rescale=rescale)
+        flip, theta = a["flip"], a["theta"]
+        inv = affine_inverse(flip, theta, a["scale"], a["dxy"], sh, sw, out)
     else:
-        flip, inv = np.zeros(n, bool), identity_maps(n)
-    return BatchParams(sigma, bias, inv, flip, use_hed, gate, U, u, *quality)
+        flip, inv, theta = np.zeros(n, bool), identity_maps(n), np.zeros(n)
+    return BatchParams(sigma, bias, inv, flip, use_hed, gate, U, u, *quality, theta)
 
 
 def _colour_stage(X: torch.Tensor, p: BatchParams, config: dict, bases: StainBases | None) -> torch.Tensor:
@@ -457,7 +478,7 @@ def _to_device(X, labels, device):
 
 def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed_only", scale_range: float = 0.5,
                   label_fill: int = 0, geometry: bool = True, dtype: torch.dtype = torch.bfloat16, device=None, out: int = 256,
-                  rescale=None, stain_bases: StainBases | None = None):
+                  rescale=None, stain_bases: StainBases | None = None, flow_targets: torch.Tensor | None = None):
     """One augmented training batch on the device: (patch rows (n * (out / 8)^2, 192) in ``dtype``, int16 labels (n, out, out)), what
     ``HeadTrainer.step`` takes.  Stain jitter (``config``: a name of ``AUGMENT_CONFIGS``, or None / "geometry" for none), warp
     (``geometry``), float32 normalisation, ``ops.patchify_f32``.  ``label_fill`` is the class of out-of-frame pixels: 0 as in the
@@ -467,10 +488,16 @@ def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed
     four affine draws of size k -- after everything the batch drew before.  ``rescale`` (n,) float64, the per-crop
     ``diameter / diam_mean``, divides the random scale (``sample_affine_params``); a resampling round passes the factors of the
     crops that are still empty.  ``stain_bases`` (``stain_bases_of`` of these crops, in their order) spares the configurations with
-    the stain perturbation ("he_staining", "hed_he") the fit per call; a resampling round reuses the bases of its crops."""
+    the stain perturbation ("he_staining", "hed_he") the fit per call; a resampling round reuses the bases of its crops.
+    ``flow_targets`` (n, 3, sh, sw) float32 on the device, the (mask, flow Y, flow X) planes of the crops (``flow_targets_of``):
+    the result then has a third value, the planes under each crop's final transform (``ops.warp_flow_targets``), float32
+    (n, 3, out, out).  It changes no draw."""
     cfg = get_config(config)
     X, labels, sh, sw = _to_device(X, labels, device)
     n = X.shape[0]
+    if flow_targets is not None and (not isinstance(flow_targets, torch.Tensor) or flow_targets.dtype != torch.float32
+                                     or tuple(flow_targets.shape) != (n, 3, sh, sw) or flow_targets.device != X.device):
+        raise ValueError(f"augment_batch: flow_targets must be float32 {(n, 3, sh, sw)} on the crops' device")
     rescale = _check_rescale(rescale, n)
     if _has_he(cfg) and X.dtype == torch.uint8 and stain_bases is None:
         stain_bases = stain_bases_of(X)
@@ -487,10 +514,17 @@ def augment_batch(X, labels, rng: np.random.Generator, config: str | None = "hed
         x2, lab2 = apply_params(X[empty], labels[empty], q, cfg, label_fill, (out, out),
                                 None if stain_bases is None else stain_bases.take(empty.cpu().numpy()))
         x[empty], lab[empty] = x2, lab2
+        e = empty.cpu().numpy()
+        p.inv[e], p.flip[e], p.theta[e] = q.inv, q.flip, q.theta
     else:
         if bool((lab == -100).flatten(1).all(1).any()):
             raise ValueError(f"augment_batch: a crop had no annotated pixel after {MAX_RESAMPLE} resampled transforms")
-    return ops.patchify_f32(x, dtype), lab
+    if flow_targets is None:
+        return ops.patchify_f32(x, dtype), lab
+    px_off, hw, _px = pool_table([(sh, sw)] * n)                  # pre-cut crops of equal shape: a pool with a regular table
+    tgt, _status = ops.warp_flow_targets(flow_targets.contiguous().view(-1), torch.from_numpy(px_off).to(X.device),
+                                         torch.from_numpy(hw).to(X.device), np.arange(n), p.inv, flow_vec(p.flip, p.theta), (out, out))
+    return ops.patchify_f32(x, dtype), lab, tgt
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -524,12 +558,12 @@ def check_pool_table(px_off, hw, pool_px: int) -> None:
 class ImagePool:
     """Whole annotated images of any size on the device, uploaded once: ``pool_u8`` the (h_i, w_i, 3) uint8 images packed back to
     back, ``pool_lab`` the int16 class maps at the same pixel offsets, ``px_off`` / ``hw`` the table (host copies ``px_off_host`` /
-    ``hw_host``), ``byte_sums`` (nI,) int64 on the host -- the exact byte sum of every image, from which ``applied`` forms the stain
+    ``hw_host``), ``pool_tgt`` (with ``instances``: the flow-head targets, see ``flow_targets_of``; else None), ``byte_sums`` (nI,) int64 on the host -- the exact byte sum of every image, from which ``applied`` forms the stain
     jitter's cut-off decision per image.  ``diameters`` (nI,) float64 or None travel with the images for ``rescale``.
 
     images: a sequence of (H, W, 3) uint8 arrays; labels: (H, W) integer class maps (-100 = not annotated) in int16 range."""
 
-    def __init__(self, images, labels, diameters=None, device="cuda:0"):
+    def __init__(self, images, labels, diameters=None, device="cuda:0", instances=None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("an ImagePool lives on the device: pass a cuda device (there is no CPU path)")
@@ -562,14 +596,27 @@ class ImagePool:
         self.diameters = diameters
         self._grid = None
         self._stain = None
+        # with instance maps the pool also holds the flow-head targets: per image three float32 planes (mask, flow Y, flow X)
+        # as [3][h][w] from float 3 * px_off[i] of ``pool_tgt`` (12 more bytes per pixel)
+        self.pool_tgt = None
+        self._grid_tgt = None
+        if instances is not None:
+            instances = list(instances)
+            if len(instances) != len(images):
+                raise ValueError("ImagePool: one instance map per image")
+            for i, (im, inst) in enumerate(zip(images, instances)):
+                if np.asarray(inst).shape != np.asarray(im).shape[:2]:
+                    raise ValueError(f"ImagePool: instance map {i} must be {np.asarray(im).shape[:2]}, got {np.asarray(inst).shape}")
+            self.pool_tgt = torch.cat([t.reshape(-1) for t in flow_targets_of(instances, dev)])
 
     def __len__(self) -> int:
         return len(self.px_off_host)
 
     @property
     def nbytes(self) -> int:
-        """Device bytes of the pool: 3 per pixel of image, 2 per pixel of class map, 16 per table row."""
-        return 5 * self.pool_px + 16 * len(self)
+        """Device bytes of the pool: 3 per pixel of image, 2 per pixel of class map, 16 per table row; with instance maps 12 more
+        per pixel for the three float32 target planes."""
+        return (5 if self.pool_tgt is None else 17) * self.pool_px + 16 * len(self)
 
     def applied(self, cutoff_range) -> np.ndarray:
         """(nI,) int32: 1 where ``lo <= (byte sum / byte count) / 255.0 <= hi`` in double, the test of ``cpx_hed_jitter_u8`` on the
@@ -655,12 +702,16 @@ def apply_params_pool(pool: ImagePool, idx, p: BatchParams, config: dict | None,
 
 def augment_batch_pool(pool: ImagePool, idx, rng: np.random.Generator, config: str | None = "hed_only", scale_range: float = 0.5,
                        label_fill: int = 0, geometry: bool = True, dtype: torch.dtype = torch.bfloat16, out: int = 256,
-                       rescale=None):
+                       rescale=None, flow_targets: bool = False):
     """``augment_batch`` for one window out of each of the images ``idx`` (repeats allowed) of an ``ImagePool``: (patch rows, int16
     labels (n, out, out)).  The draws, their order, the resampling of crops whose labels are all -100 and the tail
     (``normalize_img_f32`` -> ``patchify_f32``) are those of ``augment_batch``; on a pool of equal-sized images the result is bitwise
-    ``augment_batch`` of the same images.  The stain jitter's cut-off test sees the whole image, as in the reference."""
+    ``augment_batch`` of the same images.  The stain jitter's cut-off test sees the whole image, as in the reference.
+    ``flow_targets=True`` (a pool built with ``instances``) adds a third value: the pool's target planes under each crop's final
+    transform, float32 (n, 3, out, out).  It changes no draw."""
     cfg = get_config(config)
+    if flow_targets and pool.pool_tgt is None:
+        raise ValueError("augment_batch_pool: flow_targets needs a pool built with instances")
     idx = np.asarray(idx, np.int64)
     n = len(idx)
     if idx.ndim != 1 or n == 0 or idx.min() < 0 or idx.max() >= len(pool):
@@ -678,10 +729,14 @@ def augment_batch_pool(pool: ImagePool, idx, rng: np.random.Generator, config: s
         q = sample_batch_params_pool(pool, idx[e], rng, cfg, scale_range, geometry, out, None if rescale is None else rescale[e])
         x2, lab2 = apply_params_pool(pool, idx[e], q, cfg, label_fill, (out, out))
         x[empty], lab[empty] = x2, lab2
+        p.inv[e], p.flip[e], p.theta[e] = q.inv, q.flip, q.theta
     else:
         if bool((lab == -100).flatten(1).all(1).any()):
             raise ValueError(f"augment_batch_pool: a crop had no annotated pixel after {MAX_RESAMPLE} resampled transforms")
-    return ops.patchify_f32(x, dtype), lab
+    if not flow_targets:
+        return ops.patchify_f32(x, dtype), lab
+    tgt, _status = ops.warp_flow_targets(pool.pool_tgt, pool.px_off, pool.hw, idx, p.inv, flow_vec(p.flip, p.theta), (out, out))
+    return ops.patchify_f32(x, dtype), lab, tgt
 
 
 def grid_origins(h: int, crop: int = 256) -> list[int]:
@@ -725,3 +780,70 @@ def grid_crops(pool: ImagePool, crop: int = 256, chunk: int = 64):
     if crop == 256:
         pool._grid = res
     return res
+
+
+def grid_flow_targets(pool: ImagePool, crop: int = 256, chunk: int = 64) -> torch.Tensor:
+    """The flow-head targets of the windows ``grid_crops`` keeps, float32 (M, 3, crop, crop) on the device: plain windows of the
+    pool's stored planes, cut by ``ops.warp_flow_targets`` with integer-translation maps and the identity vector matrix, so every
+    value is exact; beyond the image mask and flows are 0.  Cached on the pool for the default crop."""
+    if pool.pool_tgt is None:
+        raise ValueError("grid_flow_targets: the pool was built without instances")
+    if crop == 256 and pool._grid_tgt is not None:
+        return pool._grid_tgt
+    win = grid_crops(pool, crop, chunk)[2]
+    outs = []
+    for s in range(0, len(win), chunk):
+        w = win[s:s + chunk]
+        inv = identity_maps(len(w))
+        inv[:, 2], inv[:, 5] = w[:, 2], w[:, 1]
+        outs.append(ops.warp_flow_targets(pool.pool_tgt, pool.px_off, pool.hw, w[:, 0], inv, identity_vecs(len(w)), (crop, crop))[0])
+    res = torch.cat(outs)
+    if crop == 256:
+        pool._grid_tgt = res
+    return res
+
+
+FLOW_WS_LIMIT = 1 << 30         # bytes of post-processing workspace per ``ops.masks_to_flows`` call: larger groups run in chunks
+
+
+def renumber_instances(inst) -> np.ndarray:
+    """An integer instance map with arbitrary non-negative ids -> int32 with the ids compact in 1..n in ascending order of the old
+    ids, 0 stays the background (what ``fastremap.renumber`` gives the reference, up to the order).  Host, once per image."""
+    inst = np.asarray(inst)
+    if inst.ndim != 2 or not np.issubdtype(inst.dtype, np.integer):
+        raise ValueError(f"instance maps must be 2-D integer arrays, got {inst.shape} {inst.dtype}")
+    if inst.size and inst.min() < 0:
+        raise ValueError("instance ids must be non-negative (0 = background)")
+    u, inverse = np.unique(inst, return_inverse=True)
+    inverse = inverse.reshape(inst.shape)
+    return (inverse if len(u) and u[0] == 0 else inverse + 1).astype(np.int32)
+
+
+def flow_targets_of(instances, device="cuda:0", ws_limit: int = FLOW_WS_LIMIT) -> list:
+    """The flow-head targets of whole instance maps, once per data set: per map a float32 device tensor (3, h, w) = (mask, flow Y,
+    flow X) -- cellpose ``dynamics.labels_to_flows`` restated: the mask plane is ``instances > 0``, the flows those of
+    ``ops.masks_to_flows`` on the WHOLE image (its iteration count depends on the whole image, as in the reference).  Ids are
+    renumbered on the host, maps of one shape go to the device together, in chunks whose workspace stays below ``ws_limit``."""
+    from . import _lib
+    dev = torch.device(device)
+    maps = [renumber_instances(m) for m in instances]
+    out = [None] * len(maps)
+    by_shape: dict = {}
+    for i, m in enumerate(maps):
+        by_shape.setdefault(m.shape, []).append(i)
+    L = _lib.lib()
+    for (h, w), ids in by_shape.items():
+        if h < 2 or w < 2:
+            raise ValueError(f"flow targets: an instance map of {h} x {w} is too small")
+        per = max(1, L.cpx_postproc_workspace_bytes(1, h, w))
+        chunk = int(max(1, min(len(ids), ws_limit // per)))
+        for s in range(0, len(ids), chunk):
+            part = ids[s:s + chunk]
+            m = torch.from_numpy(np.stack([maps[i] for i in part])).to(dev)
+            flows = ops.masks_to_flows(m)
+            tgt = torch.cat([(m > 0).to(torch.float32)[:, None], flows], 1)
+            for k, i in enumerate(part):
+                out[i] = tgt[k].contiguous()
+        for k in {chunk, len(ids) % chunk}:                              # one-off: do not keep the workspaces of whole images
+            ops._ws_cache.pop(("pp", k, h, w, str(dev)), None)
+    return out

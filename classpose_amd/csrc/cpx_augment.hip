@@ -354,6 +354,78 @@ extern "C" int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *po
     return CPX_OK;
 }
 
+// t8: the flow-head targets (mask, flow Y, flow X), three float32 planes per image at float 3 * px_off[i], under the crop's map:
+// the flow branch of cellpose transforms.random_rotate_and_resize (lbl[1:] warped bilinearly, the X flow of a flipped source
+// negated, then the pair rotated by theta; restated from cellpose 4.0.x).  Coordinates, taps and lerps are warp_pool_pixel's.
+__device__ __forceinline__ float flow_tap(const float *__restrict__ plane, int sh, int sw, int y, int x) {
+    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) return 0.f;
+    return plane[(long long)y * sw + x];
+}
+
+__global__ void k_warp_affine_pool_flow(const float *__restrict__ pool_tgt, const int64_t *__restrict__ px_off,
+                                        const int32_t *__restrict__ hw, int nI, long long pool_px,
+                                        const int32_t *__restrict__ image_of, const double *__restrict__ inv,
+                                        const double *__restrict__ vec, int dh, int dw, float *__restrict__ out,
+                                        int32_t *__restrict__ status) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= dh * dw) return;
+    const size_t t = blockIdx.y;
+    const size_t plane = (size_t)dh * dw;
+    const int im = image_of[t];
+    int bad = 0, sh = 0, sw = 0;
+    long long off = 0;
+    if (im < 0 || im >= nI) bad = 1;
+    else {
+        off = px_off[im]; sh = hw[2 * im]; sw = hw[2 * im + 1];
+        if (!pool_entry_ok(off, sh, sw, pool_px)) bad = 2;
+    }
+    float v[3] = {0.f, 0.f, 0.f};
+    if (bad) {                                                          // nothing of the pool is read for this crop
+        if (p == 0) atomicOr(status, bad);
+    } else {
+        const float *img = pool_tgt + 3 * off;
+        const long long spx = (long long)sh * sw;
+        const int y = p / dw, x = p - y * dw;
+        const double *m = inv + t * 6;
+        const double sx = m[0] * (double)x + m[1] * (double)y + m[2];
+        const double sy = m[3] * (double)x + m[4] * (double)y + m[5];
+        if (sx >= -1.0 && sx < (double)sw && sy >= -1.0 && sy < (double)sh) {
+            const double fx = floor(sx), fy = floor(sy);
+            const int x0 = (int)fx, y0 = (int)fy;
+            const float wx = (float)(sx - fx), wy = (float)(sy - fy);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float *pl = img + c * spx;
+                const float a = flow_tap(pl, sh, sw, y0, x0), b = flow_tap(pl, sh, sw, y0, x0 + 1);
+                const float d = flow_tap(pl, sh, sw, y0 + 1, x0), e = flow_tap(pl, sh, sw, y0 + 1, x0 + 1);
+                const float top = a + (b - a) * wx;
+                const float bot = d + (e - d) * wx;
+                v[c] = top + (bot - top) * wy;
+            }
+        }
+        const double *r = vec + t * 4;
+        const float r0 = (float)r[0], r1 = (float)r[1], r2 = (float)r[2], r3 = (float)r[3];
+        const float y0p = r0 * v[1], y1p = r1 * v[2], x0p = r2 * v[1], x1p = r3 * v[2];     // (-ffp-contract=off: no fma)
+        v[1] = y0p + y1p;
+        v[2] = x0p + x1p;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
+}
+
+extern "C" int cpx_warp_affine_pool_flow_f32(const float *pool_tgt, const int64_t *px_off, const int32_t *hw, int nI,
+                                             long long pool_px, const int32_t *image_of, const double *inv, const double *vec,
+                                             int n, int dh, int dw, float *out, int32_t *status, void *stream) {
+    CPX_REQUIRE(pool_tgt && px_off && hw && image_of && inv && vec && out && status && nI > 0 && pool_px > 0);
+    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
+    hipStream_t s = (hipStream_t)stream;
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_warp_affine_pool_flow, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_tgt, px_off, hw,
+                       nI, pool_px, image_of, inv, vec, dh, dw, out, status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
 // ---------------------------------------------------------------------------
 // H&E stain-matrix perturbation (t5): augment_stains / stains_to_rgb of transforms/he_staining.py
 // ---------------------------------------------------------------------------

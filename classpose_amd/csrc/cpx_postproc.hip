@@ -2110,6 +2110,62 @@ extern "C" int cpx_remove_bad_flow_masks(int32_t *masks, const float *dP, int nT
     return bad_flow_impl(masks, dP, nT, H, W, threshold, flow_errors, ws, stream, false);
 }
 
+// ---------------------------------------------------------------------------
+// t8  target flows of the flow-head training: cellpose dynamics.masks_to_flows_gpu (labels_to_flows per image)
+// ---------------------------------------------------------------------------
+// The statistics, the centre pick and the fp64 diffusion are the launches of the flow-error filter above, on a checked copy
+// of the caller's map (an id that no per-label table has room for is 0 there, and flagged); k_mtf_write then forms the unit
+// vectors exactly as k_flow_err_label does and rounds them once to float32.
+__global__ void k_mtf_sanitize(const int32_t *__restrict__ masks, int32_t *__restrict__ clean, int32_t *__restrict__ status, PPLayout lay) {
+    const int idx = blockIdx.x * NTHR + threadIdx.x;
+    if (idx >= lay.HW) return;
+    const size_t p = (size_t)blockIdx.y * lay.HW + idx;
+    int lab = masks[p];
+    if (lab < 0) { atomicOr(status, CPX_MTF_BAD_ID); lab = 0; }
+    else if (lab >= lay.L) { atomicOr(status, CPX_MTF_TOO_MANY_LABELS); lab = 0; }
+    clean[p] = lab;
+}
+
+__global__ void k_mtf_write(const int32_t *__restrict__ masks, float *__restrict__ flows, PPLayout lay, void *ws) {
+    const int idx = blockIdx.x * NTHR + threadIdx.x;
+    if (idx >= lay.HW) return;
+    const size_t t = blockIdx.y;
+    float fy = 0.f, fx = 0.f;
+    if (masks[t * lay.HW + idx] > 0) {
+        const double *T = WS(double, off_T);
+        const int y = idx / lay.W, x = idx - y * lay.W;
+        const int c = (y + 1) * lay.TW + (x + 1);
+        const double dy = T[c + lay.TW] - T[c - lay.TW];
+        const double dx = T[c + 1] - T[c - 1];
+        const double a = dy * dy;
+        const double b = dx * dx;
+        const double den = 1e-60 + sqrt(a + b);
+        fy = (float)(dy / den); fx = (float)(dx / den);
+    }
+    flows[(t * 2 + 0) * lay.HW + idx] = fy;
+    flows[(t * 2 + 1) * lay.HW + idx] = fx;
+}
+
+extern "C" int cpx_masks_to_flows(const int32_t *masks, int nT, int H, int W, float *flows, int32_t *status, void *workspace,
+                                  void *stream) {
+    int rc = pp_check(nT, H, W); if (rc) return rc;
+    CPX_REQUIRE(masks && flows && status && workspace && nT <= 65535);
+    hipStream_t s = (hipStream_t)stream;
+    PPLayout lay = pp_layout(H, W);
+    int32_t *clean = (int32_t *)workspace;                  // the dense masks32 plane of the workspace
+    void *ws = pp_tiles(workspace, nT, H, W);
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    PP_LAUNCH(k_mtf_sanitize, GRID_PIX(lay, nT), dim3(NTHR), 0, s, masks, clean, status, lay);
+    pp_init(PPI_SCAL | PPI_STATS | PPI_T, nT, lay, ws, s);
+    PP_LAUNCH(k_lab_stats, GRID_RUN(lay, nT), dim3(NTHR), 0, s, clean, 0, lay, ws);
+    PP_LAUNCH(k_center_d2, GRID_RUN(lay, nT), dim3(NTHR), 0, s, clean, lay, ws);
+    PP_LAUNCH(k_center_pick, GRID_PIX(lay, nT), dim3(NTHR), 0, s, clean, lay, ws);
+    pp_launch_diffuse(clean, nT, lay, ws, s);
+    PP_LAUNCH(k_mtf_write, GRID_PIX(lay, nT), dim3(NTHR), 0, s, clean, flows, lay, ws);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
 static void pp_size_filter(int32_t *masks, int nT, int min_size, const PPLayout &lay, void *ws,
                            hipStream_t s, unsigned extra_init, int32_t *nlabels_out, double err_thr = 0.0) {
     pp_init(PPI_SCAL | PPI_STATS | extra_init, nT, lay, ws, s);

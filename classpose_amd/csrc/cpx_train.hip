@@ -5,6 +5,7 @@
 // `torch.optim.AdamW` (train.py:478-480).  The forward is cpx_net_forward; this file adds
 //   * k_patchify_f32     float32 NCHW crops -> patch rows in the network dtype
 //   * k_loss_sums / k_loss_finish / k_loss_grad    the two losses and d loss / d logits on the token-major head buffer
+//   * k_seg_loss / k_seg_finish                   the flow head's loss (cellpose _loss_fn_seg) and its gradient, columns 0..191
 //   * k_wgrad / k_wgrad_reduce                    dW = dlogits^T feat, db = column sums (exact-f32 MFMA, row slabs)
 //   * k_adamw                                     the parameter update on float32 master weights
 // Determinism: no floating-point atomics anywhere.  Every sum is a fixed tree inside a wave (xor butterfly), a fixed serial
@@ -383,6 +384,101 @@ extern "C" int cpx_class_loss(const float *head, int ld_head, int col0, const in
     CPX_CHECK_LAUNCH();
     if (reg) hipLaunchKernelGGL(k_loss_grad_reg<LOSS_REG_CLS>, grid, block, 0, s, g);
     else hipLaunchKernelGGL(k_loss_grad, grid, block, 0, s, g);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// segmentation loss of the flow head (`--freeze backbone neck`: seg_trainable, classpose/train.py:482-489)
+// ---------------------------------------------------------------------------
+// cellpose train._loss_fn_seg (restated from cellpose 4.0.x): MSELoss(mean)(flow logits, 5 * flow targets) / 2 +
+// BCEWithLogitsLoss(mean)(cellprob logits, mask > 0.5).  Neither mean depends on the data, so one pass writes the gradient and the
+// per-workgroup float64 partial sums; k_seg_finish adds them per image and then over the images, both in index order.
+struct SegArgs {
+    const float *head; int ld_head;
+    const float *tgt;
+    int nI, H, W, nblk;
+    float g_flow, g_cp;             // w_seg / (2 nI H W), w_seg / (nI H W)
+    double *part;
+    float *flow, *cp, *dlogits;
+};
+
+__global__ void __launch_bounds__(256) k_seg_loss(SegArgs g) {
+    __shared__ double sm[4][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y, blk = blockIdx.x;
+    const int tw = g.W >> 3, T = (g.H >> 3) * tw;
+    const int t_end = min(T, (blk + 1) * LOSS_TOK_PER_BLOCK);
+    const size_t HW = (size_t)g.H * g.W;
+    double s_flow = 0, s_cp = 0;
+    for (int t = blk * LOSS_TOK_PER_BLOCK + wave; t < t_end; t += 4) {
+        const int ph = t / tw, pw = t - ph * tw;
+        const size_t px = (size_t)(8 * ph + (lane >> 3)) * g.W + 8 * pw + (lane & 7);
+        const float *tg = g.tgt + (size_t)b * 3 * HW + px;
+        const float y = tg[0] > 0.5f ? 1.f : 0.f, ty = tg[HW], tx = tg[2 * HW];
+        const size_t row = (size_t)b * T + t;
+        const float *z = g.head + row * g.ld_head + lane;
+        const float zy = z[0], zx = z[64], zc = z[128];
+        const float dy = zy - 5.f * ty, dx = zx - 5.f * tx;
+        s_flow += 0.5 * ((double)dy * (double)dy) + 0.5 * ((double)dx * (double)dx);
+        const float e = expf(-fabsf(zc));                          // in (0, 1]: nothing overflows at any logit
+        s_cp += (double)(fmaxf(zc, 0.f) - zc * y) + (double)log1pf(e);
+        const float sig = zc >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+        float *d = g.dlogits + row * 192 + lane;
+        d[0] = dy * g.g_flow; d[64] = dx * g.g_flow; d[128] = (sig - y) * g.g_cp;
+    }
+    s_flow = wave_sum(s_flow); s_cp = wave_sum(s_cp);
+    if (lane == 0) { sm[wave][0] = s_flow; sm[wave][1] = s_cp; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const int k = threadIdx.x;
+        g.part[((size_t)b * g.nblk + blk) * 2 + k] = ((sm[0][k] + sm[1][k]) + sm[2][k]) + sm[3][k];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_seg_finish(SegArgs g) {
+    __shared__ double s_img[256][2];
+    double flow = 0, cp = 0;
+    for (int base = 0; base < g.nI; base += 256) {
+        const int b = base + threadIdx.x;
+        if (b < g.nI) {
+            double e0 = 0, e1 = 0;
+            for (int k = 0; k < g.nblk; ++k) {
+                const double *e = g.part + ((size_t)b * g.nblk + k) * 2;
+                e0 += e[0]; e1 += e[1];
+            }
+            s_img[threadIdx.x][0] = e0; s_img[threadIdx.x][1] = e1;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < 256 && base + k < g.nI; ++k) { flow += s_img[k][0]; cp += s_img[k][1]; }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double n = (double)g.nI * (double)g.H * (double)g.W;
+    *g.flow = (float)(flow / (2.0 * n));
+    *g.cp = (float)(cp / n);
+}
+
+static int seg_nblk(int H, int W) { return ((H / 8) * (W / 8) + LOSS_TOK_PER_BLOCK - 1) / LOSS_TOK_PER_BLOCK; }
+extern "C" size_t cpx_seg_loss_workspace_bytes(int nI, int H, int W) {
+    if (nI <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return 0;
+    return cpx_align_up((size_t)nI * seg_nblk(H, W) * 2 * sizeof(double), 256);
+}
+extern "C" int cpx_seg_loss(const float *head, int ld_head, const float *targets, int nI, int H, int W, float w_seg, float *flow,
+                            float *cp, float *dlogits, void *workspace, size_t workspace_bytes, void *stream) {
+    CPX_REQUIRE(head && targets && flow && cp && dlogits && workspace);
+    CPX_REQUIRE(nI > 0 && nI <= 65535 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && ld_head >= 192);
+    CPX_REQUIRE((size_t)nI * (H / 8) * (W / 8) < 0x7fffffffull);
+    CPX_REQUIRE(workspace_bytes >= cpx_seg_loss_workspace_bytes(nI, H, W) && ((uintptr_t)workspace & 7) == 0);
+    SegArgs g;
+    g.head = head; g.ld_head = ld_head; g.tgt = targets; g.nI = nI; g.H = H; g.W = W; g.nblk = seg_nblk(H, W);
+    const double n = (double)nI * (double)H * (double)W;
+    g.g_flow = (float)((double)w_seg / (2.0 * n)); g.g_cp = (float)((double)w_seg / n);
+    g.part = (double *)workspace; g.flow = flow; g.cp = cp; g.dlogits = dlogits;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_seg_loss, dim3(g.nblk, nI), dim3(256), 0, s, g);
+    CPX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_seg_finish, dim3(1), dim3(256), 0, s, g);
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }

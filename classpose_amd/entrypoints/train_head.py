@@ -95,6 +95,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="channels per level of a UNet class head (the reference's flag): a checkpoint that has such a head trains it "
                         "without this flag; given, a checkpoint without one gets a freshly initialised UNet head on its backbone "
                         "(with --nclasses when it has no classes); at most 4 levels")
+    p.add_argument("--train_flow_head", action="store_true",
+                   help="train the flow head (out, the flow / cell-probability logits) next to the class head, from the instance "
+                        "maps: the reference's --freeze backbone neck; needs --instances or --data_path")
+    p.add_argument("--freeze", nargs="+", default=None, choices=["none", "backbone", "segmentation_head", "neck"],
+                   help="the reference's spelling of the same choice: 'backbone neck' = --train_flow_head, 'backbone "
+                        "segmentation_head neck' = the default (class head only); nothing else is built")
     p.add_argument("--save_only_trainable_params", action="store_true")
     p.add_argument("--random_seed", type=int, default=42)
     p.add_argument("--save_path", required=True)
@@ -103,8 +109,33 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def flow_head_from_freeze(freeze, train_flow_head: bool) -> bool:
+    """Whether the flow head trains, from ``--freeze`` (the reference's flag, run_training.py:92-98) and ``--train_flow_head``.
+    Raises ``SystemExit`` naming what is not built for every other combination."""
+    if freeze is None:
+        return bool(train_flow_head)
+    parts = set(freeze)
+    if "none" in parts and len(parts) > 1:
+        raise SystemExit("--freeze none stands alone")
+    missing = [name for name in ("backbone", "neck") if name not in parts]
+    if missing:
+        what = " and ".join("training the " + m for m in missing)
+        raise SystemExit(f"--freeze {' '.join(freeze)}: {what} is not built; 'backbone neck' (both heads train) and 'backbone "
+                         "segmentation_head neck' (the class head trains) are")
+    if "segmentation_head" in parts:
+        if train_flow_head:
+            raise SystemExit("--train_flow_head contradicts --freeze ... segmentation_head ...: give one or the other")
+        return False
+    return True
+
+
 def check_args(args) -> None:
     """The combinations the parser cannot express; raises ``SystemExit`` with the reason."""
+    args.train_flow_head = flow_head_from_freeze(getattr(args, "freeze", None), getattr(args, "train_flow_head", False))
+    if args.train_flow_head and args.data_path is None and args.instances is None:
+        raise SystemExit("--train_flow_head (--freeze backbone neck): needs --instances or --data_path")
+    if args.train_flow_head and args.data_path is None and args.test_images is not None and args.test_instances is None:
+        raise SystemExit("--train_flow_head with a validation set: needs --test_instances")
     fts = getattr(args, "feature_transformation_structure", None)
     if fts is not None and (len(fts) > 4 or min(fts) < 1):
         raise SystemExit("--feature_transformation_structure: 1 to 4 positive channel counts (32 x 32 tokens halve once per level "
@@ -163,11 +194,11 @@ def main_data_path(args) -> None:
     nclasses = data.n_classes if args.nclasses is None else args.nclasses
     trainer = make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
                            feature_transformation_structure=args.feature_transformation_structure,
-                           class_weights=args.class_weights, weight_decay=args.weight_decay)
+                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head)
     if data.n_classes > trainer.nclasses:
         raise SystemExit(f"the labels hold class {data.n_classes - 1} but the head has {trainer.nclasses} classes")
     train_probs = diameters = None
-    if args.auto_class_weights or args.oversampling_method != "none" or args.rescale or args.min_train_masks > 0:
+    if args.auto_class_weights or args.oversampling_method != "none" or args.rescale or args.min_train_masks > 0 or args.train_flow_head:
         stats = train_data.ragged_label_stats(data.instances, data.classes, trainer.nclasses, device=args.device)
         diameters = dataset_stats.clamp_diameters(stats.diameters)
         logger.info(f"diameters: {diameters.min():.2f} to {diameters.max():.2f} px, masks per image: {int(stats.n_masks.min())} to "
@@ -194,15 +225,21 @@ def main_data_path(args) -> None:
             if not np.all(np.isfinite(train_probs)):
                 raise SystemExit("--oversampling_method custom: the training set has no instance of a class above 0")
             logger.info(f"Custom oversampling - probability range: {train_probs.min():.6f} to {train_probs.max():.6f}")
-    pool = augment.ImagePool(data.images, data.classes, diameters if args.rescale else None, device=args.device)
-    test_pool = None if test is None else augment.ImagePool(test.images, test.classes, device=args.device)
-    logger.info(f"image pool: {pool.nbytes / 2 ** 20:.1f} MB on the device for {len(pool)} images")
+    if args.train_flow_head:
+        logger.info(f"computing the flow targets of {len(data)} training images" + (f" and {len(test)} validation images" if test is not None else ""))
+        trainer.set_diam_labels(diameters)
+    pool = augment.ImagePool(data.images, data.classes, diameters if args.rescale else None, device=args.device,
+                             instances=data.instances if args.train_flow_head else None)
+    test_pool = None if test is None else augment.ImagePool(test.images, test.classes, device=args.device,
+                                                            instances=test.instances if args.train_flow_head else None)
+    logger.info(f"image pool: {pool.nbytes / 2 ** 20:.1f} MB on the device for {len(pool)} images"
+                + (" (12 of its 17 bytes per pixel are the flow targets)" if args.train_flow_head else ""))
     path, train_losses, test_losses = train_class_head(
         trainer, pool, None, test_pool, None, batch_size=args.batch_size, n_epochs=args.n_epochs,
         learning_rate=args.learning_rate, nimg_per_epoch=args.nimg_per_epoch, cache_features=args.cache_features,
         save_path=args.save_path, model_name=args.model_name, random_seed=args.random_seed,
         augment=args.augment, scale_range=args.scale_range, label_fill=args.augment_label_fill, train_probs=train_probs,
-        diam_mean=args.diam_mean, rescale=args.rescale)
+        diam_mean=args.diam_mean, rescale=args.rescale, train_flow_head=args.train_flow_head)
     if args.save_only_trainable_params:
         trainer.save(path, save_only_trainable_params=True)
     logger.info(f"final train loss {train_losses[-1]:.4f}" + (f", test loss {test_losses[-1]:.4f}" if test_pool is not None else ""))
@@ -220,17 +257,17 @@ def main(args) -> None:
     test_labels = np.load(args.test_labels) if args.test_labels else None
     trainer = make_trainer(args.pretrained_model, nclasses=args.nclasses, device=args.device, precision=args.precision,
                            feature_transformation_structure=args.feature_transformation_structure,
-                           class_weights=args.class_weights, weight_decay=args.weight_decay)
-    train_probs = diameters = None
+                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head)
+    train_probs = diameters = instances = test_instances = None
     if args.instances is not None:
-        stats = dataset_stats.label_stats(_load_instances(args.instances, labels, "--instances"), labels, trainer.nclasses,
-                                          device=args.device)
+        instances = _load_instances(args.instances, labels, "--instances")
+        stats = dataset_stats.label_stats(instances, labels, trainer.nclasses, device=args.device)
         diameters = dataset_stats.clamp_diameters(stats.diameters)                # train_utils.py:268
         logger.info(f"diameters: {diameters.min():.2f} to {diameters.max():.2f} px, masks per image: {int(stats.n_masks.min())} to "
                     f"{int(stats.n_masks.max())}")
         if args.test_instances is not None:
-            tstats = dataset_stats.label_stats(_load_instances(args.test_instances, test_labels, "--test_instances"), test_labels,
-                                               trainer.nclasses, device=args.device)
+            test_instances = _load_instances(args.test_instances, test_labels, "--test_instances")
+            tstats = dataset_stats.label_stats(test_instances, test_labels, trainer.nclasses, device=args.device)
             tdiam = dataset_stats.clamp_diameters(tstats.diameters)
             logger.info(f"test diameters: {tdiam.min():.2f} to {tdiam.max():.2f} px")
         if args.min_train_masks > 0:                                               # train_utils.py:288-308
@@ -241,7 +278,7 @@ def main(args) -> None:
                                "removing from train set")
                 if len(keep) == 0:
                     raise SystemExit("--min_train_masks leaves no training image")
-                images, labels, diameters = images[keep], labels[keep], diameters[keep]
+                images, labels, diameters, instances = images[keep], labels[keep], diameters[keep], instances[keep]
                 stats = dataset_stats.LabelStats(stats.class_counts, stats.instance_counts[keep], stats.n_masks[keep],
                                                  stats.diameters[keep])
         # like the reference, weights and probabilities use the class counts of the whole set as loaded (run_training.py computes
@@ -258,12 +295,16 @@ def main(args) -> None:
             if not np.all(np.isfinite(train_probs)):
                 raise SystemExit("--oversampling_method custom: the training set has no instance of a class above 0")
             logger.info(f"Custom oversampling - probability range: {train_probs.min():.6f} to {train_probs.max():.6f}")
+    if args.train_flow_head:
+        trainer.set_diam_labels(diameters)
     path, train_losses, test_losses = train_class_head(
         trainer, images, labels, test_images, test_labels, batch_size=args.batch_size, n_epochs=args.n_epochs,
         learning_rate=args.learning_rate, nimg_per_epoch=args.nimg_per_epoch, cache_features=args.cache_features,
         save_path=args.save_path, model_name=args.model_name, random_seed=args.random_seed,
         augment=args.augment, scale_range=args.scale_range, label_fill=args.augment_label_fill, train_probs=train_probs,
-        diameters=diameters if args.rescale else None, diam_mean=args.diam_mean, rescale=args.rescale)
+        diameters=diameters if args.rescale else None, diam_mean=args.diam_mean, rescale=args.rescale,
+        train_flow_head=args.train_flow_head, instances=instances if args.train_flow_head else None,
+        test_instances=test_instances if args.train_flow_head else None)
     if args.save_only_trainable_params:
         trainer.save(path, save_only_trainable_params=True)
     logger.info(f"final train loss {train_losses[-1]:.4f}" + (f", test loss {test_losses[-1]:.4f}" if test_images is not None else ""))

@@ -566,6 +566,102 @@ def class_loss(head: torch.Tensor, labels: torch.Tensor, ncls: int, col0: int = 
     return o
 
 
+class SegLossOut:
+    """Device results of ``seg_loss``: ``flow`` and ``cp`` (1,) float32 (the loss is their sum), ``dlogits`` (rows, 192)."""
+    __slots__ = ("flow", "cp", "dlogits")
+
+
+def seg_loss(head: torch.Tensor, targets: torch.Tensor, w_seg: float = 1.0, dlogits: torch.Tensor | None = None) -> SegLossOut:
+    """cellpose ``train._loss_fn_seg`` (restated from cellpose 4.0.x) on the flow columns 0..191 of the token-major ``head``
+    (n * H/8 * W/8, ld_head) float32 and its gradient: ``targets`` (n, 3, H, W) float32 = (mask, flow Y, flow X);
+    flow = mean((z - 5 t)^2) / 2 over both flow channels, cp = BCE-with-logits of the cellprob channel against mask > 0.5."""
+    if head.dtype != torch.float32 or head.dim() != 2 or not head.is_contiguous() or head.shape[1] < 192:
+        raise ValueError("seg_loss: head must be a contiguous float32 (rows, ld_head >= 192) tensor")
+    if targets.dtype != torch.float32 or targets.dim() != 4 or targets.shape[1] != 3 or targets.device != head.device:
+        raise ValueError("seg_loss: targets must be float32 (n, 3, H, W) on the head's device")
+    targets = targets.contiguous()
+    nI, _c, H, W = targets.shape
+    rows, ld = head.shape
+    if H % 8 or W % 8 or nI == 0 or rows != nI * (H // 8) * (W // 8):
+        raise ValueError(f"seg_loss: head {tuple(head.shape)} does not fit targets {tuple(targets.shape)}")
+    dev = head.device
+    L = _lib.lib()
+    o = SegLossOut()
+    o.flow = torch.empty(1, dtype=torch.float32, device=dev)
+    o.cp = torch.empty(1, dtype=torch.float32, device=dev)
+    o.dlogits = dlogits if dlogits is not None else torch.empty((rows, 192), dtype=torch.float32, device=dev)
+    if o.dlogits.shape != (rows, 192) or o.dlogits.dtype != torch.float32 or not o.dlogits.is_contiguous() or o.dlogits.device != dev:
+        raise ValueError("seg_loss: dlogits must be contiguous float32 (rows, 192)")
+    key = ("sloss", nI, H, W, str(dev))
+    if key not in _ws_cache:
+        _ws_cache[key] = torch.empty(L.cpx_seg_loss_workspace_bytes(nI, H, W), dtype=torch.uint8, device=dev)
+    ws = _ws_cache[key]
+    check(L.cpx_seg_loss(ptr(head), ld, ptr(targets), nI, H, W, float(w_seg), ptr(o.flow), ptr(o.cp), ptr(o.dlogits), ptr(ws),
+                         ws.numel(), _stream(dev)), "seg_loss")
+    return o
+
+
+def masks_to_flows(masks: torch.Tensor, check_status: bool = True):
+    """cellpose ``dynamics.masks_to_flows_gpu`` per image (restated; checked against ``oracle.dynamics.masks_to_flows``): int32
+    device ``masks`` (n, H, W) or (H, W), ids compact in 1..n and 0 = background -> float32 (n, 2, H, W) or (2, H, W) unit flows
+    (dY, dX), 0 on the background.  Raises ``ValueError`` on a negative id or on more labels than ``cpx_postproc_max_labels``
+    (with ``check_status=False`` returns ``(flows, status)`` instead)."""
+    if masks.dtype != torch.int32 or masks.dim() not in (2, 3) or not masks.is_cuda:
+        raise ValueError("masks_to_flows: expected int32 device masks (n, H, W) or (H, W)")
+    m, was = _batched(masks.contiguous(), 2)
+    nT, H, W = m.shape
+    dev = m.device
+    flows = torch.empty((nT, 2, H, W), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(_lib.lib().cpx_masks_to_flows(ptr(m), nT, H, W, ptr(flows), ptr(status), ptr(_pp_ws(nT, H, W, dev)), _stream(dev)),
+          "masks_to_flows")
+    flows = flows if was else flows[0]
+    if not check_status:
+        return flows, status
+    bits = int(status.item())
+    if bits & 2:
+        raise ValueError("masks_to_flows: an instance id is negative")
+    if bits & 1:
+        raise ValueError(f"masks_to_flows: an instance id is above the {_lib.lib().cpx_postproc_max_labels(H, W) - 1} labels a "
+                         f"{H} x {W} map may hold (ids must be compact in 1..n: renumber them)")
+    return flows
+
+
+def warp_flow_targets(pool_tgt: torch.Tensor, px_off: torch.Tensor, hw: torch.Tensor, image_of, inv, vec, out_hw,
+                      check_status: bool = True):
+    """``cpx_warp_affine_pool_flow_f32``: ``pool_tgt`` float32 (3 * pool_px,), per image of the table (px_off, hw) the planes
+    (mask, flow Y, flow X) as [3][h][w] from float 3 * px_off[i]; crop t samples image ``image_of[t]`` by ``inv[t]`` like
+    ``warp_affine`` and maps the flow pair through ``vec[t]`` (``augment.flow_vec``).  Returns (float32 (n, 3, dh, dw), status)."""
+    if pool_tgt.dtype != torch.float32 or pool_tgt.dim() != 1 or pool_tgt.numel() % 3 or not pool_tgt.is_contiguous() \
+            or not pool_tgt.is_cuda:
+        raise ValueError("warp_flow_targets: pool_tgt is a contiguous float32 device vector of 3 values per pixel")
+    dev, pool_px, nI = pool_tgt.device, pool_tgt.numel() // 3, px_off.numel()
+    if px_off.dtype != torch.int64 or px_off.dim() != 1 or nI == 0 or px_off.device != dev or not px_off.is_contiguous():
+        raise ValueError("warp_flow_targets: px_off is int64 (nI,) on the pool's device")
+    if hw.dtype != torch.int32 or hw.shape != (nI, 2) or hw.device != dev or not hw.is_contiguous():
+        raise ValueError("warp_flow_targets: hw is int32 (nI, 2) on the pool's device")
+    dh, dw = (int(v) for v in out_hw)
+    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
+    n = image_of.numel()
+
+    def f64(a):
+        a = torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64) if not isinstance(a, torch.Tensor) else a)
+        return a.to(device=dev, dtype=torch.float64).contiguous()
+    inv, vec = f64(inv), f64(vec)
+    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6) or vec.shape != (n, 4):
+        raise ValueError("warp_flow_targets: image_of is (n,), inv (n, 6) and vec (n, 4) float64")
+    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(_lib.lib().cpx_warp_affine_pool_flow_f32(ptr(pool_tgt), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv),
+                                                   ptr(vec), n, dh, dw, ptr(out), ptr(status), _stream(dev)),
+          "warp_affine_pool_flow_f32")
+    if check_status:
+        bits = int(status.item())
+        if bits:
+            raise ValueError("warp_flow_targets: " + ("an image index outside the pool" if bits & 1 else "a table entry outside the pool"))
+    return out, status
+
+
 def head_wgrad(dlogits: torch.Tensor, feat: torch.Tensor):
     """(dW (n_cols, 256), db (n_cols,)) float32 of the 1x1 head: dW = dlogits^T feat, db = column sums; dlogits (rows, n_cols)
     float32, feat (rows, 256) in the network dtype."""

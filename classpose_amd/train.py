@@ -1,4 +1,4 @@
-"""Fine-tuning the 1x1 semantic class head on the device with the backbone, the neck and the flow head frozen.
+"""Fine-tuning the 1x1 semantic class head (and, on request, the flow head) on the device with the backbone and the neck frozen.
 
 The reference's cheapest adaptation mode, ``--freeze backbone segmentation_head neck`` (paper_experiments/run_training.py:92-98,
 354-358; vit_sam.py:199-249): ``train_class_seg`` (train.py:356-655) then has two active losses with weight 1 each, the pixel
@@ -16,6 +16,9 @@ Deliberately different from the reference:
   * oversampling (``train_probs``) and the rescale by cell diameter (``rescale``, ``diameters``) are opt-in arguments of
     ``train_class_head``, fed by ``classpose_amd.dataset_stats``; the reference's command line has both on by default;
   * no HDF5 datasets, learned loss weighting, multi-GPU exchange or optimiser-state resume.
+
+``train_flow_head=True`` also trains the flow head ``out`` (``FlowHead``): the reference's ``--freeze backbone neck``, seg + CE +
+Tversky with multiplier 1 each (train.py:482-493), the seg loss being cellpose's ``_loss_fn_seg`` restated (``ops.seg_loss``).
 
 The reference's other class head, the UNet of ``--feature_transformation_structure``, is trained by
 ``train_unet.UNetHeadTrainer`` (same public surface; ``make_trainer`` picks the trainer from the checkpoint, and
@@ -95,6 +98,45 @@ def _labels_i16(labels, dev) -> torch.Tensor:
     return t.to(device=dev, dtype=torch.int16).contiguous()
 
 
+def _targets_f32(flow_targets, n: int, dev) -> torch.Tensor:
+    t = torch.as_tensor(flow_targets)
+    if t.dim() != 4 or tuple(t.shape) != (n, 3, CROP, CROP) or t.dtype != torch.float32:
+        raise ValueError(f"flow_targets: expected float32 (mask, flow Y, flow X) planes {(n, 3, CROP, CROP)}, got {tuple(t.shape)} {t.dtype}")
+    return t.to(dev).contiguous()
+
+
+class FlowHead:
+    """The trainable state of the flow head ``out`` = nn.Conv2d(256, 192, 1) (vit_sam.py:181-182; trained by the reference's
+    ``--freeze backbone neck``, run_training.py:92-98), shared by ``HeadTrainer`` and ``train_unet.UNetHeadTrainer``: the float32
+    master ``w`` [192, 256] and ``b`` [192], their AdamW moments, and the refresh of rows 0..191 of the head operands (``head_w`` /
+    ``head_b`` of the trainer's ``engine.NetWeights``), rounded as at load.  The pixel shuffle ``W2`` is fixed and stays as loaded."""
+
+    def __init__(self, sd: dict, weights, element_size: int):
+        if tuple(sd["out.weight"].shape) != (192, 256, 1, 1) or tuple(sd["out.bias"].shape) != (192,):
+            raise ValueError("out.weight / out.bias of the checkpoint do not describe a 1x1 flow head over 256 channels")
+        dev = weights.device
+        self.weights, self._es = weights, element_size
+        self.w = sd["out.weight"].detach().float().reshape(192, 256).contiguous().to(dev)
+        self.b = sd["out.bias"].detach().float().contiguous().to(dev)
+        self.m_w, self.v_w, self.m_b, self.v_b = (torch.zeros_like(t) for t in (self.w, self.w, self.b, self.b))
+
+    def update(self, dlogits: torch.Tensor, feat: torch.Tensor, step: int, lr: float, **kw) -> None:
+        """One AdamW step from the seg-loss gradient ``dlogits`` (rows, 192) and the features the head GEMM read."""
+        dW, db = ops.head_wgrad(dlogits, feat)
+        ops.adamw_step(self.w, dW, self.m_w, self.v_w, step, lr, **kw)
+        ops.adamw_step(self.b, db, self.m_b, self.v_b, step, lr, **kw)
+        self.refresh()
+
+    def refresh(self) -> None:
+        c = self.weights.c
+        half = c.dtype != _lib.DT_F32
+        ops.round_weights(self.w, c.head_w, c.dtype, keep_f32=not half)
+        ops.round_weights(self.b, c.head_b, c.dtype, keep_f32=True)
+
+    def state(self) -> dict:
+        return {"out.weight": self.w.detach().cpu().reshape(192, 256, 1, 1).clone(), "out.bias": self.b.detach().cpu().clone()}
+
+
 class HeadTrainer:
     """Trains ``out_class`` (nn.Conv2d(256, nclasses * 64, 1)) of a checkpoint; everything else stays as loaded.
 
@@ -105,7 +147,7 @@ class HeadTrainer:
 
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
-                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8):
+                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, train_flow_head: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
@@ -131,6 +173,20 @@ class HeadTrainer:
         self._head_fb = torch.empty((nS * TOKENS, c.ld_head), dtype=torch.float32, device=dev)
         self._es = torch.empty(0, dtype=self.dtype).element_size()
         self._buf: dict = {}
+        self._init_flow_head(train_flow_head)
+
+    def _init_flow_head(self, train_flow_head: bool) -> None:
+        """``train_flow_head``: the flow head ``out`` trains too (the reference's ``--freeze backbone neck``); ``step`` / ``evaluate``
+        then take ``flow_targets`` and add the seg loss, multiplier 1 like the other two (LossAggregator(optimise=False))."""
+        self.w_seg = 1.0
+        self.flow = FlowHead(self.sd, self.weights, self._es) if train_flow_head else None
+        self.diam_labels = None
+
+    def set_diam_labels(self, diameters) -> None:
+        """With the flow head training, ``diam_labels`` of the saved checkpoint becomes the mean diameter of the training set
+        (train.py:440-442); no-op otherwise."""
+        if self.flow is not None and diameters is not None and len(diameters):
+            self.diam_labels = float(np.mean(np.asarray(diameters, np.float64)))
 
     def set_class_weights(self, class_weights) -> None:
         """Replace the per-class loss weights (None: unweighted) -- for weights that are computed from the training set after the
@@ -211,30 +267,56 @@ class HeadTrainer:
                            dlogits=self._buf[key], check_status=True)
         return feat, head, o
 
-    def _result(self, o, n) -> dict:
+    def _seg_loss(self, head: torch.Tensor, flow_targets):
+        """The seg loss of the batch whose head buffer is ``head`` and its gradient on the flow columns; None without targets."""
+        if flow_targets is None:
+            return None
+        if self.flow is None:
+            raise ValueError("flow_targets: the trainer was built without train_flow_head")
+        rows = head.shape[0]
+        key = ("dlf", rows)
+        if key not in self._buf:
+            self._buf[key] = torch.empty((rows, 192), dtype=torch.float32, device=self.device)
+        return ops.seg_loss(head, _targets_f32(flow_targets, rows // TOKENS, self.device), self.w_seg, dlogits=self._buf[key])
+
+    def _result(self, o, n, seg=None) -> dict:
         ce, tv = float(o.ce.item()), float(o.tversky.item())
-        return {"ce": ce, "tversky": tv, "loss": self.w_ce * ce + self.w_tv * tv, "n": n}
+        if seg is None:
+            return {"ce": ce, "tversky": tv, "loss": self.w_ce * ce + self.w_tv * tv, "n": n}
+        fl, cp = float(seg.flow.item()), float(seg.cp.item())
+        return {"ce": ce, "tversky": tv, "seg": fl + cp, "seg_flow": fl, "seg_cp": cp,
+                "loss": self.w_seg * (fl + cp) + self.w_ce * ce + self.w_tv * tv, "n": n}
+
+    def _flow_kw(self) -> dict:
+        return dict(betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay)
 
     # -- public ------------------------------------------------------------------------------------------------
-    def evaluate(self, X, labels, return_head: bool = False) -> dict:
-        """Losses of a batch without an update.  ``return_head`` adds the float32 head buffer (a view that the next call overwrites)."""
+    def evaluate(self, X, labels, flow_targets=None, return_head: bool = False) -> dict:
+        """Losses of a batch without an update.  ``return_head`` adds the float32 head buffer (a view that the next call overwrites).
+        ``flow_targets`` (n, 3, 256, 256) float32 (mask, flow Y, flow X), for a trainer built with ``train_flow_head``: the result
+        gains "seg" and "loss" is seg + ce + tversky."""
         feat, head, o = self._loss(X, labels)
-        r = self._result(o, feat.shape[0] // TOKENS)
+        seg = self._seg_loss(head, flow_targets)
+        r = self._result(o, feat.shape[0] // TOKENS, seg)
         if return_head:
             r["head"] = head
         return r
 
-    def step(self, X, labels, lr: float) -> dict:
+    def step(self, X, labels, lr: float, flow_targets=None) -> dict:
         """One optimisation step on a batch of crops (or of cached ``features``) at learning rate ``lr``; returns the losses of the
-        batch BEFORE the update, like the reference's loop."""
-        feat, _head, o = self._loss(X, labels)            # raises before anything is updated
+        batch BEFORE the update, like the reference's loop.  With ``flow_targets`` (see ``evaluate``) the flow head takes the same
+        step from the seg loss: same step counter, betas and weight decay."""
+        feat, head, o = self._loss(X, labels)             # raises before anything is updated
+        seg = self._seg_loss(head, flow_targets)          # (so does this)
         dW, db = ops.head_wgrad(o.dlogits, feat)
         self.n_steps += 1
         kw = dict(betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay)     # net.parameters(): decay on the bias too
         ops.adamw_step(self.w, dW, self.m_w, self.v_w, self.n_steps, lr, **kw)
         ops.adamw_step(self.b, db, self.m_b, self.v_b, self.n_steps, lr, **kw)
         self._refresh_operands()
-        return self._result(o, feat.shape[0] // TOKENS)
+        if seg is not None:
+            self.flow.update(seg.dlogits, feat, self.n_steps, lr, **kw)
+        return self._result(o, feat.shape[0] // TOKENS, seg)
 
     def _refresh_operands(self) -> None:
         """Master weights -> the head operands of ``self.weights`` in place (rows 192... of head_w and head_b), rounded as at load."""
@@ -249,12 +331,21 @@ class HeadTrainer:
         sd = dict(self.sd)
         sd["out_class.weight"] = self.w.detach().cpu().reshape(self.nclasses * 64, 256, 1, 1).clone()
         sd["out_class.bias"] = self.b.detach().cpu().clone()
+        return self._flow_state(sd)
+
+    def _flow_state(self, sd: dict) -> dict:
+        """With the flow head training: ``out.weight`` [192, 256, 1, 1] and ``out.bias`` from the master copies (``W2`` as loaded),
+        and ``diam_labels`` when ``set_diam_labels`` was given the training diameters."""
+        if self.flow is not None:
+            sd.update(self.flow.state())
+            if self.diam_labels is not None and "diam_labels" in sd:
+                sd["diam_labels"] = torch.full_like(sd["diam_labels"], self.diam_labels)
         return sd
 
     def save(self, path, save_only_trainable_params: bool = False) -> None:
         sd = self.state_dict()
         if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
-            sd = {k: sd[k] for k in ("out_class.weight", "out_class.bias")}
+            sd = {k: sd[k] for k in ("out_class.weight", "out_class.bias") + (("out.weight", "out.bias") if self.flow is not None else ())}
         torch.save(sd, os.fspath(path))
 
 
@@ -278,6 +369,16 @@ def _check_dataset(images, labels, what: str):
     if len(empty):
         raise ValueError(f"{what} image {int(empty[0])} has no annotated pixel (every label is -100): drop it")
     return images, labels
+
+
+def _crop_targets(instances, n: int, dev, what: str) -> torch.Tensor:
+    """Flow-head targets (n, 3, 256, 256) float32 on the device of pre-cut crops from their instance maps, built once."""
+    if instances is None:
+        raise ValueError(f"train_flow_head needs {what}: integer instance maps aligned with the crops")
+    instances = np.asarray(instances)
+    if instances.shape != (n, CROP, CROP) or not np.issubdtype(instances.dtype, np.integer):
+        raise ValueError(f"{what}: expected integer instance maps {(n, CROP, CROP)}, got {instances.shape} {instances.dtype}")
+    return torch.stack(_augment.flow_targets_of(list(instances), dev))
 
 
 def _is_u8_crops(images) -> bool:
@@ -314,7 +415,8 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
                      n_epochs: int = 100, learning_rate: float = 5e-5, nimg_per_epoch: int | None = None, cache_features: bool = True,
                      save_path=None, model_name: str | None = None, random_seed: int = 42, transform=None,
                      augment: str | None = None, scale_range: float = 0.5, label_fill: int = 0, train_probs=None, diameters=None,
-                     diam_mean: float = 30.0, rescale: bool = False):
+                     diam_mean: float = 30.0, rescale: bool = False, train_flow_head: bool = False, instances=None,
+                     test_instances=None):
     """The epoch loop of train.py:606-655 for the frozen-backbone mode: per-epoch learning rate from ``lr_schedule``, seeded sampling
     without replacement (with, when ``nimg_per_epoch`` exceeds the set), sample-weighted running means of CE / Tversky / total,
     validation once per epoch, ``checkpoint_last.pt`` and ``checkpoint_best.pt`` (lowest validation loss; training loss without a
@@ -338,20 +440,49 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     per image (``diameters`` defaults to the pool's), and ``transform`` is refused (there is no host crop to hand it).  Without
     ``augment`` the training set is the pool's cached ``augment.grid_crops``, one entry per window (``train_probs`` of an image go
     to each of its windows); validation always runs on the cached grid crops of its pool.  Array inputs behave as before.
+    ``train_flow_head=True`` (a trainer built with ``train_flow_head``) trains the flow head too, the reference's ``--freeze backbone
+    neck``: every step and every validation batch also gets the flow targets of its crops, and the seg loss is logged and counted
+    next to CE / Tversky.  The targets come from ``instances`` / ``test_instances`` ((N, 256, 256) integer instance maps aligned
+    with the crops; ``augment.flow_targets_of``, once) or, for an ``ImagePool``, from the pool itself (built with ``instances``);
+    an augmented batch warps them with the crop, everything else uses plain windows of the stored planes.  ``transform`` is refused
+    (a host callback cannot move the targets).  ``diameters``, when given, also set the checkpoint's ``diam_labels``.
     Returns ``(path of the final model, train_losses, test_losses)``."""
     pool = None
+    tgts = test_tgts = None                               # flow-head targets of pre-cut / grid crops, float32 (N, 3, 256, 256) on the device
+    if train_flow_head:
+        if trainer.flow is None:
+            raise ValueError("train_flow_head=True needs a trainer built with train_flow_head=True")
+        if transform is not None:
+            raise ValueError("train_flow_head: transform is a host callback on crops and cannot move the flow targets")
+    elif instances is not None or test_instances is not None:
+        raise ValueError("instances / test_instances are the flow head's targets: they need train_flow_head=True")
     if isinstance(images, _augment.ImagePool):
+        src_pool = images
+        if train_flow_head and (src_pool.pool_tgt is None or instances is not None):
+            raise ValueError("train_flow_head: an ImagePool carries its own instances (build it with instances=..., pass instances=None)")
         images, labels, pool, train_probs, diameters = _pool_training_set(images, labels, transform, augment, train_probs, diameters)
+        if train_flow_head and pool is None:
+            tgts = _augment.grid_flow_targets(src_pool)
     else:
         images, labels = _check_dataset(images, labels, "training")
+        if train_flow_head:
+            tgts = _crop_targets(instances, len(images), trainer.device, "instances")
     has_test = test_images is not None
     if has_test and isinstance(test_images, _augment.ImagePool):
         if test_labels is not None:
             raise ValueError("a validation ImagePool carries its own class maps: pass test_labels=None")
         _pool_annotated(test_images, "validation")
+        if train_flow_head:
+            if test_images.pool_tgt is None or test_instances is not None:
+                raise ValueError("train_flow_head: a validation ImagePool carries its own instances (build it with instances=...)")
+            test_tgts = _augment.grid_flow_targets(test_images)
         test_images, test_labels, _win = _augment.grid_crops(test_images)
     elif has_test:
         test_images, test_labels = _check_dataset(test_images, test_labels, "validation")
+        if train_flow_head:
+            test_tgts = _crop_targets(test_instances, len(test_images), trainer.device, "test_instances")
+    if train_flow_head:
+        trainer.set_diam_labels(diameters)
     nimg = len(pool) if pool is not None else len(images)
     nimg_per_epoch = nimg if nimg_per_epoch is None else int(nimg_per_epoch)
     if train_probs is not None:
@@ -407,41 +538,49 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
             order = rng.choice(nimg, nimg_per_epoch, p=train_probs)
         else:
             order = rng.permutation(nimg)[:nimg_per_epoch] if nimg_per_epoch <= nimg else rng.choice(nimg, nimg_per_epoch)
-        sums, count = np.zeros(3), 0
+        sums, count = np.zeros(4), 0
         for s in range(0, len(order), batch_size):
             idx = order[s:s + batch_size]
+            t = None
+            if tgts is not None:
+                t = tgts[torch.from_numpy(idx).to(tgts.device)]
             if cached:
                 ti = torch.from_numpy(idx).to(dev)
                 x, y = feats[ti].reshape(-1, 256), lab_dev[ti]
             elif pool is not None:
-                x, y = _augment.augment_batch_pool(pool, idx, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
-                                                   dtype=trainer.dtype, out=CROP, rescale=None if rsc is None else rsc[idx])
+                res = _augment.augment_batch_pool(pool, idx, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
+                                                  dtype=trainer.dtype, out=CROP, rescale=None if rsc is None else rsc[idx],
+                                                  flow_targets=train_flow_head)
+                x, y, t = res if train_flow_head else (*res, None)
             else:
                 x, y = images[idx], labels[idx]
                 if transform is not None:
                     x, y = transform(x, y, rng)
                 if augment is not None:
-                    x, y = _augment.augment_batch(x, y, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
-                                                  dtype=trainer.dtype, device=dev, out=CROP,
-                                                  rescale=None if rsc is None else rsc[idx],
-                                                  stain_bases=None if bases is None else bases.take(idx))
-            r = trainer.step(x, y, float(LR[iepoch]))
-            sums += np.array([r["ce"], r["tversky"], r["loss"]]) * len(idx)
+                    res = _augment.augment_batch(x, y, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
+                                                 dtype=trainer.dtype, device=dev, out=CROP,
+                                                 rescale=None if rsc is None else rsc[idx],
+                                                 stain_bases=None if bases is None else bases.take(idx), flow_targets=t)
+                    x, y, t = res if t is not None else (*res, None)
+            r = trainer.step(x, y, float(LR[iepoch])) if t is None else trainer.step(x, y, float(LR[iepoch]), flow_targets=t)
+            sums += np.array([r["ce"], r["tversky"], r["loss"], r.get("seg", 0.0)]) * len(idx)
             count += len(idx)
         train_losses[iepoch] = sums[2] / count
-        msg = f"{iepoch}, train_loss={sums[2] / count:.4f} (ce={sums[0] / count:.4f}, tversky={sums[1] / count:.4f}), LR={LR[iepoch]:.6f}"
+        seg_msg = f"seg={sums[3] / count:.4f}, " if train_flow_head else ""
+        msg = f"{iepoch}, train_loss={sums[2] / count:.4f} ({seg_msg}ce={sums[0] / count:.4f}, tversky={sums[1] / count:.4f}), LR={LR[iepoch]:.6f}"
         if has_test:
-            tsum, tcount = 0.0, 0
+            tsum, tseg, tcount = 0.0, 0.0, 0
             for s in range(0, len(test_images), batch_size):
                 if test_cached:
                     x, y = test_feats[s:s + batch_size].reshape(-1, 256), test_lab_dev[s:s + batch_size]
                 else:
                     x, y = test_images[s:s + batch_size], test_labels[s:s + batch_size]
-                r = trainer.evaluate(x, y)
+                r = trainer.evaluate(x, y) if test_tgts is None else trainer.evaluate(x, y, flow_targets=test_tgts[s:s + batch_size])
                 tsum += r["loss"] * r["n"]
+                tseg += r.get("seg", 0.0) * r["n"]
                 tcount += r["n"]
             test_losses[iepoch] = tsum / tcount
-            msg += f", test_loss={test_losses[iepoch]:.4f}"
+            msg += f", test_loss={test_losses[iepoch]:.4f}" + (f" (seg={tseg / tcount:.4f})" if train_flow_head else "")
         train_logger.info(msg)
         trainer.save(model_dir / "checkpoint_last.pt")
         score = test_losses[iepoch] if has_test else train_losses[iepoch]

@@ -205,7 +205,8 @@ class UNetHeadTrainer(HeadTrainer):
 
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
-                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, feature_transformation_structure=None):
+                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, feature_transformation_structure=None,
+                 train_flow_head: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
@@ -236,6 +237,7 @@ class UNetHeadTrainer(HeadTrainer):
         self._head_fb = torch.empty((nS * TOKENS, c.ld_head), dtype=torch.float32, device=dev)
         self._es = torch.empty(0, dtype=self.dtype).element_size()
         self._buf: dict = {}
+        self._init_flow_head(train_flow_head)
 
     def head(self, feat: torch.Tensor) -> torch.Tensor:
         """The head launches of ``cpx_net_forward`` on ``feat``: float32 (rows, ld_head), flow columns 0..191 from the head GEMM,
@@ -266,16 +268,19 @@ class UNetHeadTrainer(HeadTrainer):
                                          dtype=torch.uint8, device=self.device)
         return self._buf[key]
 
-    def step(self, X, labels, lr: float) -> dict:
+    def step(self, X, labels, lr: float, flow_targets=None) -> dict:
         """One optimisation step on a batch of crops (or of cached ``features``) at learning rate ``lr``; returns the losses of the
-        batch BEFORE the update, like the reference's loop."""
-        feat, _head, o = self._loss(X, labels)            # raises before anything is updated
+        batch BEFORE the update, like the reference's loop.  ``flow_targets``: as ``HeadTrainer.step``."""
+        feat, head, o = self._loss(X, labels)             # raises before anything is updated
+        seg = self._seg_loss(head, flow_targets)          # (so does this)
         self.backward(feat, o.dlogits)
         self.n_steps += 1
         ops.adamw_step(self.params, self.grads, self.m, self.v, self.n_steps, lr, betas=self.betas, eps=self.adam_eps,
                        weight_decay=self.weight_decay)    # net.parameters(): decay on the biases too
         self._refresh_operands()
-        return self._result(o, feat.shape[0] // TOKENS)
+        if seg is not None:
+            self.flow.update(seg.dlogits, feat, self.n_steps, lr, **self._flow_kw())
+        return self._result(o, feat.shape[0] // TOKENS, seg)
 
     def _refresh_operands(self) -> None:
         """Master parameters -> the operands the op list points at, rounded as at load."""
@@ -287,12 +292,12 @@ class UNetHeadTrainer(HeadTrainer):
         """The checkpoint in the reference's key layout: every ``out_class.*`` entry from the master parameters, the rest as loaded."""
         sd = dict(self.sd)
         sd.update(unpack_params(self.params, self.fts, self.nclasses * 64))
-        return sd
+        return self._flow_state(sd)
 
     def save(self, path, save_only_trainable_params: bool = False) -> None:
         sd = self.state_dict()
         if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
-            sd = {k: v for k, v in sd.items() if k.startswith("out_class.")}
+            sd = {k: v for k, v in sd.items() if k.startswith("out_class.") or (self.flow is not None and k in ("out.weight", "out.bias"))}
         torch.save(sd, os.fspath(path))
 
 

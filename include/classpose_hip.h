@@ -737,6 +737,53 @@ int cpx_warp_affine_pool_quality_u8(const uint8_t *pool_u8, const int16_t *pool_
                                     float *out, int16_t *labels_out, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
+ * t8  training the flow head `out` = nn.Conv2d(256, 192, 1) next to the class head (additive, no ABI bump)
+ * The reference's `--freeze backbone neck` (paper_experiments/run_training.py:92-98, classpose/vit_sam.py:232-249): seg_trainable
+ * is then true (classpose/train.py:482-489) and the total loss is seg + CE + Tversky, multiplier 1 each.  The flow head is the
+ * first 192 columns of the head GEMM; cpx_head_wgrad, cpx_adamw_step and cpx_round_weights serve it unchanged.  The three entry
+ * points below take a stream, allocate nothing and use no floating-point atomics.
+ * cellpose.dynamics.labels_to_flows / masks_to_flows_gpu, the flow branch of cellpose.transforms.random_rotate_and_resize and
+ * cellpose.train._loss_fn_seg are RESTATED here from cellpose 4.0.x and not pinned against the installed wheel (cellpose is not
+ * a build dependency), as classpose_amd.augment.sample_affine already is.
+ * ---------------------------------------------------------------------- */
+/* cpx_masks_to_flows: masks [nT][H][W] int32 instance ids, compact in 1..n, 0 = background -> flows [nT][2][H][W] float32
+ *   (dY, dX): the fp64 in-mask heat diffusion of cpx_remove_bad_flow_masks (same label statistics, centre pick, n_iter =
+ *   2 * the largest extent of the tile, same launches), then the central differences mu of the result, mu / (1e-60 + |mu|),
+ *   0 on the background, rounded once to float32.  workspace: cpx_postproc_workspace_bytes(nT, H, W).
+ *   status is ONE int32 word that the entry clears first: an id < 0 sets CPX_MTF_BAD_ID, an id >= cpx_postproc_max_labels(H, W)
+ *   sets CPX_MTF_TOO_MANY_LABELS; such pixels count as background and nothing is read or written through the id.            */
+#define CPX_MTF_TOO_MANY_LABELS 1
+#define CPX_MTF_BAD_ID 2
+int cpx_masks_to_flows(const int32_t *masks, int nT, int H, int W, float *flows, int32_t *status, void *workspace,
+                       void *stream);
+
+/* cpx_warp_affine_pool_flow_f32: the training targets under the crop's geometry.  pool_tgt holds, for image i of the pool table
+ *   (px_off, hw, pool_px as in section t4), three float32 planes [3][h_i][w_i] = (mask, flow Y, flow X) starting at float
+ *   3 * px_off[i].  Crop t samples image image_of[t] by inv[t][6] with the coordinates, the four taps (0 outside the source)
+ *   and the three lerps of cpx_warp_affine_f32 on all three planes; then, in float32 with every product and the sum rounded on
+ *   their own (no fused multiply-add), v = (float)vec[t][.]:
+ *     fy' = v[0] * fy + v[1] * fx,   fx' = v[2] * fy + v[3] * fx.
+ *   The host forms vec = [cos th, f sin th, -sin th, f cos th] with f = -1 for a flipped source, +1 otherwise: cellpose negates
+ *   the X flow of a flipped image and then rotates, Y' = X sin th + Y cos th, X' = X cos th - Y sin th.  The scale does not
+ *   rescale the vectors and they are not renormalised.  out [n][3][dh][dw] float32 (mask, flow Y, flow X): channel 0 stays the
+ *   interpolated mask.  status as cpx_warp_affine_pool_u8 (bit 0: image_of outside [0, nI); bit 1: table entry outside the pool). */
+int cpx_warp_affine_pool_flow_f32(const float *pool_tgt, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                                  const int32_t *image_of, const double *inv, const double *vec, int n, int dh, int dw,
+                                  float *out, int32_t *status, void *stream);
+
+/* cpx_seg_loss: cellpose.train._loss_fn_seg and its gradient at the flow head's output.  head as cpx_class_loss reads it:
+ *   column k*64 + i*8 + j of token (ph, pw) is channel k of pixel (8 ph + i, 8 pw + j), k = 0 dY, 1 dX, 2 cellprob (the first
+ *   192 columns; later columns are not read).  targets [nI][3][H][W] float32 = (mask, flow Y, flow X).
+ *     flow = mean over (b, 2, H, W) of (z - 5 t)^2 / 2
+ *     cp   = mean over (b, H, W) of max(z, 0) - z y + log1p(exp(-|z|)),   y = [mask > 0.5]
+ *   Every pixel counts.  Out: flow [1], cp [1] float32 and dlogits [rows][192] float32 = w_seg * d(flow + cp) / d head:
+ *   w_seg (z - 5 t) / (2 nI H W) on the flow columns, w_seg (sigmoid(z) - y) / (nI H W) on the cellprob columns.
+ *   One pass over the logits and a one-workgroup kernel; sums are float64, added in a fixed order.                          */
+size_t cpx_seg_loss_workspace_bytes(int nI, int H, int W);
+int cpx_seg_loss(const float *head, int ld_head, const float *targets, int nI, int H, int W, float w_seg, float *flow,
+                 float *cp, float *dlogits, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * a17  polygonisation (HOST function: all pointers are host pointers)
  * replaces, per instance, cv2.findContours(cell_mask, RETR_EXTERNAL,
  * CHAIN_APPROX_SIMPLE)[0] + shapely.Polygon(...).is_valid/.centroid/.area/.length
