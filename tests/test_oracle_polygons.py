@@ -7,19 +7,8 @@ import numpy as np
 import pytest
 
 from classpose_amd import postprocess
-from classpose_amd.engine import RECORD_DTYPE
 from oracle import polygons as opoly
-
-
-def _records(m, cm=None):
-    """what cpx_instance_records emits; the class is the class map at the instance's first raster pixel when cm is given"""
-    labs = [l for l in np.unique(m) if l]
-    recs = np.zeros(len(labs), RECORD_DTYPE)
-    for i, l in enumerate(labs):
-        ys, xs = np.nonzero(m == l)
-        cls = 1 + int(l) % 6 if cm is None else int(cm[ys[0], xs[0]])
-        recs[i] = (0, l, cls, len(ys), ys.min(), xs.min(), ys.max() + 1, xs.max() + 1, ys.sum(), xs.sum())
-    return recs
+from polygon_shapes import blob_tile, compare_with_oracle as _compare_with_oracle, records as _records
 
 
 def _c(mask):
@@ -83,24 +72,6 @@ def test_ring_metrics_known_answers():
 
 
 # ---- product host polygoniser vs the oracle ----------------------------------------------------------------
-def _compare_with_oracle(m, cm, scale, origin, cells, xy):
-    ref = opoly.post_process_tile(m, cm, origin, scale)
-    valid = cells[cells["valid"] == 1]
-    assert len(valid) == len(ref)
-    labs = [l for l in np.unique(m) if l]
-    for c, lab in zip(cells, labs):
-        # every contour (valid or not) equals OpenCV-order contours[0]
-        ys, xs = np.nonzero(m == lab)
-        cont = opoly.find_contours_external_simple((m == lab)[ys.min(): ys.max() + 1, xs.min(): xs.max() + 1])[0]
-        exp = (cont + [xs.min(), ys.min()]) * scale + np.asarray(origin)
-        assert np.array_equal(xy[c["offset"]: c["offset"] + c["n_pts"]], exp), lab
-    for c, r in zip(valid, ref):
-        assert c["area"] == r["area"] and c["perimeter"] == pytest.approx(r["perimeter"], rel=1e-14)
-        assert abs(c["cx"] - r["centroid_raw"][0]) < 1e-9 and abs(c["cy"] - r["centroid_raw"][1]) < 1e-9
-        assert c["cls"] - 1 == r["class_int"]
-    return len(ref)
-
-
 def test_host_polygonizer_equals_oracle_hand_cases():
     m = np.zeros((48, 64), np.uint16)
     m[5:15, 10:30] = 1
@@ -124,13 +95,7 @@ def test_host_polygonizer_equals_oracle_hand_cases():
 
 @pytest.mark.parametrize("seed,thr", [(0, 0.02), (1, 0.0), (2, 0.05)])
 def test_host_polygonizer_equals_oracle_random_blobs(seed, thr):
-    rng = np.random.default_rng(seed)
-    from scipy.ndimage import binary_fill_holes, gaussian_filter, label
-    img = gaussian_filter(rng.standard_normal((96, 128)), 2.5) > thr
-    lab, n = label(binary_fill_holes(img))
-    # merge some labels so that multi-component instances occur
-    lab[lab == n] = 1
-    m = lab.astype(np.uint16)
+    m = blob_tile(seed, thr)                                 # 96 x 128, some labels merged so that multi-component instances occur
     recs = _records(m)
     cm = np.zeros(m.shape, np.uint8)
     for r in recs:
