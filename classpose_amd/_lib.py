@@ -158,6 +158,15 @@ SIGNATURES = {
     "cpx_unet_backward_workspace_bytes": (_sz, [C.POINTER(CpxConvOp), _i, _i, _i]),
     "cpx_unet_grad_layout": (_i, [C.POINTER(CpxConvOp), _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
     "cpx_unet_head_backward": (_i, [C.POINTER(CpxConvOp), _i, _p, _i, _i, _p, _sz, _p, _p, _p, _sz, _p]),
+    "cpx_net_backbone_offset": (_sz, [_i, _i]),
+    "cpx_neck_train_workspace_bytes": (_sz, [_i, _i]),
+    "cpx_neck_train_layout": (_i, [_i, _i, C.POINTER(_sz)]),
+    "cpx_neck_forward_train": (_i, [C.POINTER(CpxNetWeights), _p, _i, _p, _p, _sz, _p]),
+    "cpx_layernorm_backward_workspace_bytes": (_sz, [_i, _i]),
+    "cpx_layernorm_backward": (_i, [_i, _p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "cpx_neck_grad_layout": (C.c_longlong, [C.POINTER(C.c_longlong)]),
+    "cpx_neck_backward_workspace_bytes": (_sz, [_i, _i, _i, C.POINTER(_sz)]),
+    "cpx_neck_backward": (_i, [C.POINTER(CpxNetWeights), _p, _i, _p, _sz, _p, _p, _p, _sz, _p]),
     "cpx_hed_jitter_u8": (_i, [_p, _i, _i, _i, _p, _p, _d, _d, _i, _p, _p, _p]),
     "cpx_warp_affine_u8": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "cpx_warp_affine_f32": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),

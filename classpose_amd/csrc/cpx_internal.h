@@ -76,6 +76,9 @@ int cpx_attention_f32(const float *qkv, const float *rel_h, const float *rel_w, 
                       void *stream);
 size_t cpx_net_f32_workspace_bytes(int n_subtiles);
 size_t cpx_net_f32_neck_offset(int n_subtiles);        // byte offset of the neck output (head GEMM operand) in that workspace
+size_t cpx_net_f32_backbone_offset(int n_subtiles);    // ... of the last block's output x [n_subtiles * 1024][1024]
+// the neck's im2col: x [n_subtiles * 1024][256] -> out [n_subtiles * 1024][2304], k = tap * 256 + c
+int cpx_im2col3_f32(const float *x, int n_subtiles, float *out, void *stream);
 int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
                         size_t workspace_bytes, void *stream);
 
@@ -84,3 +87,29 @@ int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *
                       int col0, void *workspace, size_t ws_bytes, void *stream);
 size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS);
 void cpx_unet_act_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, size_t *off, int *ld);   // n_ops <= 64
+
+// kernels of the UNet head's backward (cpx_train_unet.hip) that the neck's backward (cpx_train_neck.hip) runs too
+struct UwArgs {
+    const float *dy;                   // [rows][Npad], zero beyond the valid columns
+    const void *xa, *xb;               // the op's source tensors in the network dtype
+    int lda, ca, ldb, cb;
+    int lh, lw;                        // log2 of the INPUT height / width
+    int rows, Npad, Kpad, k_valid;     // k_valid = taps * (ca + cb)
+    float *part_w; double *part_b;     // [slab][Npad][Kpad], [slab][Npad]
+};
+struct DxArgs {
+    const float *dcol; int ldc;        // [rows of the op's GEMM][Kp128]
+    int kind, ctot, coff, C;           // the source's channels are columns tap * ctot + coff + [0, C) of dcol
+    int lh, lw;                        // log2 of the source's (= the op's input) height / width
+    size_t rows_src;
+    float *gx; int ld_gx;              // the source's gradient tensor: holds the contributions of the consumers run before
+    const void *y; int ld_y; int mask; // mask: this is the source's last contribution and its producer has a ReLU
+};
+size_t cpx_uwgrad_part_w_bytes(size_t rows, int Npad, int Kpad);       // the float32 partials; the float64 bias partials follow them
+size_t cpx_uwgrad_workspace_bytes(size_t rows, int Npad, int Kpad);    // both
+// dW [Npad][Kpad] = dY^T im2col(X) of a conv of `kind` (cpx_conv_op.kind) and db [Npad]: k_uwgrad over the first n_valid (rounded up to 32)
+// columns of dY, then k_uwgrad_reduce
+int cpx_uwgrad_run(int dtype, int kind, const UwArgs &u, int n_valid, int bias_taps, int cout, float *dW, float *db, hipStream_t s);
+// W [Npad][Kpad] of `dtype` -> float32 [Kp128][Npad], rows Kpad.. zero
+int cpx_wt_run(int dtype, const void *w, int Npad, int Kpad, int Kp128, float *wt, hipStream_t s);
+int cpx_dx_gather_run(int dtype, const DxArgs &g, hipStream_t s);      // col2im, added to g.gx

@@ -475,6 +475,14 @@ extern "C" size_t cpx_net_neck_offset(int n_subtiles, int dtype) {
     return dtype == CPX_DT_F32 ? cpx_net_f32_neck_offset(n_subtiles) : net_ws(n_subtiles).off_neck2;
 }
 
+// where cpx_net_forward leaves the last block's output x [n_subtiles * 1024][1024] (network dtype; the operand of the neck's first GEMM):
+// what a step that trains the neck starts from (cpx_train_neck.hip).  The tail only reads it.  (size_t)-1 for an invalid argument: the
+// offset itself is 0 in both layouts.
+extern "C" size_t cpx_net_backbone_offset(int n_subtiles, int dtype) {
+    if (n_subtiles <= 0 || dtype < CPX_DT_BF16 || dtype > CPX_DT_F32) return (size_t)-1;
+    return dtype == CPX_DT_F32 ? cpx_net_f32_backbone_offset(n_subtiles) : net_ws(n_subtiles).off_x;
+}
+
 // ---------------------------------------------------------------------------
 // optional per-launch timing (bench.py's roofline lines): HIP events recorded on the launch
 // stream around the selected kernels of a forward.  The handle is created by the caller (never

@@ -341,14 +341,17 @@ __global__ void __launch_bounds__(256) k_im2col3_f32(const float *__restrict__ x
         v = *reinterpret_cast<const float4 *>(x + ((row & ~(size_t)1023) + yy * 32 + xx) * 256 + c4 * 4);
     *reinterpret_cast<float4 *>(out + row * 2304 + tap * 256 + c4 * 4) = v;
 }
-#ifdef CPX_DEBUG
-// the neck's im2col on its own: x [n_subtiles*1024][256] -> out [n_subtiles*1024][2304]
-extern "C" int cpx_im2col3_f32_debug(const float *x, int n_subtiles, float *out, void *stream) {
+int cpx_im2col3_f32(const float *x, int n_subtiles, float *out, void *stream) {
     CPX_REQUIRE(x && out && n_subtiles > 0);
     const size_t n_chunks = (size_t)n_subtiles * 1024 * 576;
     hipLaunchKernelGGL(k_im2col3_f32, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n_chunks, out);
     CPX_CHECK_LAUNCH();
     return CPX_OK;
+}
+#ifdef CPX_DEBUG
+// the neck's im2col on its own: x [n_subtiles*1024][256] -> out [n_subtiles*1024][2304]
+extern "C" int cpx_im2col3_f32_debug(const float *x, int n_subtiles, float *out, void *stream) {
+    return cpx_im2col3_f32(x, n_subtiles, out, stream);
 }
 #endif
 
@@ -367,6 +370,7 @@ static NetWsF32 net_ws_f32(int nS) {
 }
 size_t cpx_net_f32_workspace_bytes(int n_subtiles) { return n_subtiles > 0 ? net_ws_f32(n_subtiles).total : 0; }
 size_t cpx_net_f32_neck_offset(int n_subtiles) { return n_subtiles > 0 ? net_ws_f32(n_subtiles).off_neck2 : 0; }
+size_t cpx_net_f32_backbone_offset(int n_subtiles) { return net_ws_f32(n_subtiles).off_x; }
 
 int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
                         size_t workspace_bytes, void *stream) {
@@ -399,11 +403,7 @@ int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, f
     }
     RUN(cpx_gemm_f32(x, F(w->neck0_w), M, 256, 1024, CPX_EPI_F32, nullptr, nullptr, nk, 256, stream));
     RUN(cpx_layernorm_f32(nk, w->neck_ln1_w, w->neck_ln1_b, M, 256, 1e-6f, nk2, stream));
-    {
-        const size_t n_chunks = (size_t)M * 576;
-        hipLaunchKernelGGL(k_im2col3_f32, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, hs, nk2, n_chunks, col);
-        CPX_CHECK_LAUNCH();
-    }
+    RUN(cpx_im2col3_f32(nk2, nS, col, stream));
     RUN(cpx_gemm_f32(col, F(w->neck2_w), M, 256, 2304, CPX_EPI_F32, nullptr, nullptr, nk, 256, stream));
     RUN(cpx_layernorm_f32(nk, w->neck_ln2_w, w->neck_ln2_b, M, 256, 1e-6f, nk2, stream));
     RUN(cpx_gemm_f32(nk2, F(w->head_w), M, w->ld_head, 256, CPX_EPI_F32, w->head_b, nullptr, head, w->ld_head, stream));

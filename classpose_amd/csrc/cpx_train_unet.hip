@@ -58,14 +58,6 @@ static OpDims op_dims(const cpx_conv_op &o, int nS) {
 // ---------------------------------------------------------------------------
 // weight gradient
 // ---------------------------------------------------------------------------
-struct UwArgs {
-    const float *dy;                   // [rows][Npad], zero beyond the valid columns
-    const void *xa, *xb;               // the op's source tensors in the network dtype
-    int lda, ca, ldb, cb;
-    int lh, lw;                        // log2 of the INPUT height / width
-    int rows, Npad, Kpad, k_valid;     // k_valid = taps * (ca + cb)
-    float *part_w; double *part_b;     // [slab][Npad][Kpad], [slab][Npad]
-};
 
 // One wave = one (32 columns of dY) x (64 columns of im2col(X)) tile of one slab; lane (r, h2) feeds dY[row + h2][n0 + r] and
 // im2col(X)[row + h2][k0 + r], [k0 + 32 + r]: its tap and channel are fixed, only the row moves.
@@ -187,14 +179,6 @@ __global__ void __launch_bounds__(256) k_s2d(const float *__restrict__ gy, int l
     out[i] = v;
 }
 
-struct DxArgs {
-    const float *dcol; int ldc;        // [rows of the op's GEMM][Kp128]
-    int kind, ctot, coff, C;           // the source's channels are columns tap * ctot + coff + [0, C) of dcol
-    int lh, lw;                        // log2 of the source's (= the op's input) height / width
-    size_t rows_src;
-    float *gx; int ld_gx;              // the source's gradient tensor: holds the contributions of the consumers run before
-    const void *y; int ld_y; int mask; // mask: this is the source's last contribution and its producer has a ReLU
-};
 template <int DT>
 __global__ void __launch_bounds__(256) k_dx_gather(DxArgs g) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -227,15 +211,58 @@ __global__ void __launch_bounds__(256) k_dx_gather(DxArgs g) {
 }
 
 // ---------------------------------------------------------------------------
+// launchers (cpx_internal.h): this pass and the neck's backward (cpx_train_neck.hip) run the same kernels
+// ---------------------------------------------------------------------------
+size_t cpx_uwgrad_part_w_bytes(size_t rows, int Npad, int Kpad) {
+    const size_t n_slabs = (rows + UW_SLAB - 1) / UW_SLAB;
+    return cpx_align_up(n_slabs * Npad * Kpad * sizeof(float), 256);
+}
+size_t cpx_uwgrad_workspace_bytes(size_t rows, int Npad, int Kpad) {
+    const size_t n_slabs = (rows + UW_SLAB - 1) / UW_SLAB;
+    return cpx_uwgrad_part_w_bytes(rows, Npad, Kpad) + cpx_align_up(n_slabs * Npad * sizeof(double), 256);
+}
+int cpx_uwgrad_run(int dtype, int kind, const UwArgs &u, int n_valid, int bias_taps, int cout, float *dW, float *db, hipStream_t s) {
+    const int n_slabs = (u.rows + UW_SLAB - 1) / UW_SLAB;
+    CPX_REQUIRE(n_slabs <= 65535 && kind >= 0 && kind <= 2);
+    const int n_done = (n_valid + 31) / 32 * 32;                                  // (<= Npad)
+    const dim3 grid(n_done / 32, (u.Kpad / 64 + 3) / 4, n_slabs), block(256);
+#define UW(DT_) do { if (kind == 0) hipLaunchKernelGGL((k_uwgrad<DT_, 0>), grid, block, 0, s, u); \
+                     else if (kind == 1) hipLaunchKernelGGL((k_uwgrad<DT_, 1>), grid, block, 0, s, u); \
+                     else hipLaunchKernelGGL((k_uwgrad<DT_, 2>), grid, block, 0, s, u); } while (0)
+    if (dtype == CPX_DT_BF16) UW(CPX_DT_BF16); else if (dtype == CPX_DT_F16) UW(CPX_DT_F16); else UW(CPX_DT_F32);
+#undef UW
+    const size_t nw = (size_t)u.Npad * u.Kpad;
+    hipLaunchKernelGGL(k_uwgrad_reduce, dim3((unsigned)((nw + 255) / 256)), block, 0, s, u.part_w, u.part_b, n_slabs, nw, u.Npad, n_done,
+                       bias_taps, cout, dW, db);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+int cpx_wt_run(int dtype, const void *w, int Npad, int Kpad, int Kp128, float *wt, hipStream_t s) {
+    const size_t nt = (size_t)Kp128 * Npad;
+    const dim3 grid((unsigned)((nt + 255) / 256)), block(256);
+    if (dtype == CPX_DT_BF16) hipLaunchKernelGGL(k_wt<CPX_DT_BF16>, grid, block, 0, s, w, Npad, Kpad, Kp128, wt);
+    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_wt<CPX_DT_F16>, grid, block, 0, s, w, Npad, Kpad, Kp128, wt);
+    else hipLaunchKernelGGL(k_wt<CPX_DT_F32>, grid, block, 0, s, w, Npad, Kpad, Kp128, wt);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+int cpx_dx_gather_run(int dtype, const DxArgs &g, hipStream_t s) {
+    const size_t n = g.rows_src * g.C;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (dtype == CPX_DT_BF16) hipLaunchKernelGGL(k_dx_gather<CPX_DT_BF16>, grid, block, 0, s, g);
+    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_dx_gather<CPX_DT_F16>, grid, block, 0, s, g);
+    else hipLaunchKernelGGL(k_dx_gather<CPX_DT_F32>, grid, block, 0, s, g);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
 // layouts
 // ---------------------------------------------------------------------------
 // workspace: [gradient tensor [rows_pad][up128(cout)] float32 of every op but the last][space-to-depth staging]
 //            [transposed operand][weight-gradient partials | dCol]
 struct BwdLayout { size_t g_off[UNET_MAX_OPS]; int g_ld[UNET_MAX_OPS]; size_t g_bytes, s2d_off, wt_off, big_off, total; };
-static size_t uw_part_w_bytes(const OpDims &d) {
-    const size_t n_slabs = (d.rows + UW_SLAB - 1) / UW_SLAB;
-    return cpx_align_up(n_slabs * d.Npad * d.Kpad * sizeof(float), 256);
-}
+static size_t uw_part_w_bytes(const OpDims &d) { return cpx_uwgrad_part_w_bytes(d.rows, d.Npad, d.Kpad); }
 static void bwd_layout(const cpx_conv_op *ops, int n_ops, int nS, BwdLayout &L) {
     size_t off = 0, s2d = 0, wt = 0, big = 0;
     for (int i = 0; i < n_ops; ++i) {
@@ -356,26 +383,17 @@ static int unet_backward(const cpx_conv_op *ops, int n_ops, const void *feat, in
             dy = stage;
         } else CPX_REQUIRE(ld_gy == d.Npad);
         // weight gradient
-        const int n_slabs = (int)((d.rows + UW_SLAB - 1) / UW_SLAB);
-        CPX_REQUIRE(n_slabs <= 65535);
         UwArgs u;
         u.dy = dy; u.xa = A.p; u.lda = A.ld; u.ca = o.cin_a; u.xb = B.p; u.ldb = B.ld; u.cb = o.cin_b; u.lh = lh; u.lw = lw;
         u.rows = (int)d.rows; u.Npad = d.Npad; u.Kpad = d.Kpad; u.k_valid = d.taps * d.ctot;
         u.part_w = big; u.part_b = (double *)((char *)big + uw_part_w_bytes(d));
-        const int n_valid = o.kind == 2 ? 4 * o.cout : o.cout, n_done = (n_valid + 31) / 32 * 32;      // (<= Npad)
-        const dim3 grid(n_done / 32, (d.Kpad / 64 + 3) / 4, n_slabs), block(256);
-        if (o.kind == 0) hipLaunchKernelGGL((k_uwgrad<DT, 0>), grid, block, 0, s, u);
-        else if (o.kind == 1) hipLaunchKernelGGL((k_uwgrad<DT, 1>), grid, block, 0, s, u);
-        else hipLaunchKernelGGL((k_uwgrad<DT, 2>), grid, block, 0, s, u);
-        const size_t nw = (size_t)d.Npad * d.Kpad;
-        hipLaunchKernelGGL(k_uwgrad_reduce, dim3((unsigned)((nw + 255) / 256)), block, 0, s, u.part_w, u.part_b, n_slabs, nw, d.Npad, n_done,
-                           o.kind == 2 ? 4 : 1, o.cout, grads + w_off[i], grads + b_off[i]);
-        CPX_CHECK_LAUNCH();
+        int rc = cpx_uwgrad_run(DT, o.kind, u, o.kind == 2 ? 4 * o.cout : o.cout, o.kind == 2 ? 4 : 1, o.cout, grads + w_off[i], grads + b_off[i], s);
+        if (rc) return rc;
         // data gradient (none for the frozen neck output)
         if (o.src_a == 0 && o.src_b <= 0) continue;
-        const size_t nt = (size_t)d.Kp128 * d.Npad;
-        hipLaunchKernelGGL(k_wt<DT>, dim3((unsigned)((nt + 255) / 256)), block, 0, s, o.weight, d.Npad, d.Kpad, d.Kp128, wt);
-        const int rc = cpx_gemm_f32(dy, wt, up128i((long long)d.rows), d.Kp128, d.Npad, CPX_EPI_F32, nullptr, nullptr, big, d.Kp128, s);
+        rc = cpx_wt_run(DT, o.weight, d.Npad, d.Kpad, d.Kp128, wt, s);
+        if (rc) return rc;
+        rc = cpx_gemm_f32(dy, wt, up128i((long long)d.rows), d.Kp128, d.Npad, CPX_EPI_F32, nullptr, nullptr, big, d.Kp128, s);
         if (rc) return rc;
         for (int side = 0; side < 2; ++side) {
             const int id = side == 0 ? o.src_a : o.src_b;
@@ -386,10 +404,9 @@ static int unet_backward(const cpx_conv_op *ops, int n_ops, const void *feat, in
             g.lh = lh; g.lw = lw; g.rows_src = (size_t)nS * o.h * o.w;
             g.gx = (float *)(ws + L.g_off[id - 1]); g.ld_gx = L.g_ld[id - 1];
             g.y = X.p; g.ld_y = X.ld; g.mask = ops[id - 1].relu && last_consumer[id] == i;
-            const size_t n = g.rows_src * g.C;
-            hipLaunchKernelGGL(k_dx_gather<DT>, dim3((unsigned)((n + 255) / 256)), block, 0, s, g);
+            rc = cpx_dx_gather_run(DT, g, s);
+            if (rc) return rc;
         }
-        CPX_CHECK_LAUNCH();
     }
     return CPX_OK;
 }

@@ -4,7 +4,7 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
         --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
-        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1]
+        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck]
     python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
         [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
@@ -98,6 +98,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--train_flow_head", action="store_true",
                    help="train the flow head (out, the flow / cell-probability logits) next to the class head, from the instance "
                         "maps: the reference's --freeze backbone neck; needs --instances or --data_path")
+    p.add_argument("--train_neck", action="store_true",
+                   help="train the neck (encoder.neck.*: 1x1 conv, LayerNorm2d, 3x3 conv, LayerNorm2d) next to the class head, from "
+                        "cached backbone rows: the reference's --freeze backbone segmentation_head; with --train_flow_head its "
+                        "--freeze backbone; not with a UNet class head")
     p.add_argument("--freeze", nargs="+", default=None, choices=["none", "backbone", "segmentation_head", "neck"],
                    help="the reference's spelling of the same choice: 'backbone neck' = --train_flow_head, 'backbone "
                         "segmentation_head neck' = the default (class head only); nothing else is built")
@@ -121,7 +125,8 @@ def flow_head_from_freeze(freeze, train_flow_head: bool) -> bool:
     if missing:
         what = " and ".join("training the " + m for m in missing)
         raise SystemExit(f"--freeze {' '.join(freeze)}: {what} is not built; 'backbone neck' (both heads train) and 'backbone "
-                         "segmentation_head neck' (the class head trains) are")
+                         "segmentation_head neck' (the class head trains) are.  The neck trains with --train_neck (and "
+                         "--train_flow_head for the flow head) in place of --freeze")
     if "segmentation_head" in parts:
         if train_flow_head:
             raise SystemExit("--train_flow_head contradicts --freeze ... segmentation_head ...: give one or the other")
@@ -131,6 +136,11 @@ def flow_head_from_freeze(freeze, train_flow_head: bool) -> bool:
 
 def check_args(args) -> None:
     """The combinations the parser cannot express; raises ``SystemExit`` with the reason."""
+    args.train_neck = bool(getattr(args, "train_neck", False))
+    if args.train_neck and "neck" in (getattr(args, "freeze", None) or ()):
+        raise SystemExit("--train_neck contradicts --freeze ... neck ...: give one or the other")
+    if args.train_neck and getattr(args, "feature_transformation_structure", None) is not None:
+        raise SystemExit("--train_neck: the neck does not train under a UNet class head (its backward gives the neck output no gradient)")
     args.train_flow_head = flow_head_from_freeze(getattr(args, "freeze", None), getattr(args, "train_flow_head", False))
     if args.train_flow_head and args.data_path is None and args.instances is None:
         raise SystemExit("--train_flow_head (--freeze backbone neck): needs --instances or --data_path")
@@ -194,7 +204,8 @@ def main_data_path(args) -> None:
     nclasses = data.n_classes if args.nclasses is None else args.nclasses
     trainer = make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
                            feature_transformation_structure=args.feature_transformation_structure,
-                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head)
+                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
+                           train_neck=args.train_neck)
     if data.n_classes > trainer.nclasses:
         raise SystemExit(f"the labels hold class {data.n_classes - 1} but the head has {trainer.nclasses} classes")
     train_probs = diameters = None
@@ -257,7 +268,8 @@ def main(args) -> None:
     test_labels = np.load(args.test_labels) if args.test_labels else None
     trainer = make_trainer(args.pretrained_model, nclasses=args.nclasses, device=args.device, precision=args.precision,
                            feature_transformation_structure=args.feature_transformation_structure,
-                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head)
+                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
+                           train_neck=args.train_neck)
     train_probs = diameters = instances = test_instances = None
     if args.instances is not None:
         instances = _load_instances(args.instances, labels, "--instances")

@@ -726,6 +726,120 @@ def unet_head_backward(weights, feat: torch.Tensor, fwd_ws: torch.Tensor, dlogit
     return grads
 
 
+# ---- training the neck (csrc/cpx_train_neck.hip) ------------------------------------------------------------------
+def backbone_rows(net_ws: torch.Tensor, n_subtiles: int, dtype: torch.dtype) -> torch.Tensor:
+    """View of the last block's output x [n_subtiles * 1024, 1024] that ``cpx_net_forward`` left in its workspace ``net_ws`` (uint8),
+    the input of the neck (``cpx_net_backbone_offset``): valid until the next forward on that workspace -- clone it to keep it."""
+    off = _lib.lib().cpx_net_backbone_offset(n_subtiles, _DT[dtype])
+    if off == 2 ** 64 - 1:
+        raise ValueError("backbone_rows: invalid n_subtiles / dtype")
+    n = n_subtiles * 1024 * 1024 * torch.empty(0, dtype=dtype).element_size()
+    return net_ws[off:off + n].view(dtype).view(n_subtiles * 1024, 1024)
+
+
+class NeckForwardOut:
+    """Results of ``neck_forward_train``: ``head`` float32 (rows, ld_head) and views into ``workspace`` of the saved activations
+    ``y0`` (before LayerNorm 1), ``a1`` (after it), ``y2`` (before LayerNorm 2) and ``feat`` (the neck output), (rows, 256) each."""
+    __slots__ = ("head", "y0", "a1", "y2", "feat", "workspace")
+
+
+def neck_train_workspace(n_subtiles: int, dtype_code: int, device) -> torch.Tensor:
+    return torch.empty(_lib.lib().cpx_neck_train_workspace_bytes(n_subtiles, dtype_code), dtype=torch.uint8, device=device)
+
+
+def neck_forward_train(weights, x: torch.Tensor, head: torch.Tensor | None = None,
+                       workspace: torch.Tensor | None = None) -> NeckForwardOut:
+    """``cpx_neck_forward_train``: the tail of ``cpx_net_forward`` (neck and head GEMM of ``weights``, an ``engine.NetWeights``) on
+    the backbone rows ``x`` (n * 1024, 1024) in the network dtype, keeping every intermediate."""
+    c, L = weights.c, _lib.lib()
+    if x.dim() != 2 or x.shape[1] != 1024 or x.shape[0] == 0 or x.shape[0] % 1024 or x.dtype not in _DT or _DT[x.dtype] != c.dtype \
+            or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError("neck_forward_train: x must be contiguous device rows (n * 1024, 1024) in the network dtype")
+    if c.n_unet_ops:
+        raise NotImplementedError("neck_forward_train: the neck does not train under a UNet semantic head")
+    rows, nS, dev = x.shape[0], x.shape[0] // 1024, x.device
+    if workspace is None:
+        workspace = neck_train_workspace(nS, c.dtype, dev)
+    if head is None:
+        head = torch.empty((rows, c.ld_head), dtype=torch.float32, device=dev)
+    if head.dtype != torch.float32 or tuple(head.shape) != (rows, c.ld_head) or not head.is_contiguous() or workspace.dtype != torch.uint8:
+        raise ValueError("neck_forward_train: head must be contiguous float32 (rows, ld_head) and workspace uint8")
+    check(L.cpx_neck_forward_train(C.byref(c), ptr(x), nS, ptr(head), ptr(workspace), workspace.numel(), _stream(dev)), "neck_forward_train")
+    off = (C.c_size_t * 4)()
+    check(L.cpx_neck_train_layout(nS, c.dtype, off), "neck_train_layout")
+    o = NeckForwardOut()
+    o.head, o.workspace = head, workspace
+    n = rows * 256 * x.element_size()
+    o.y0, o.a1, o.y2, o.feat = (workspace[off[i]:off[i] + n].view(x.dtype).view(rows, 256) for i in range(4))
+    return o
+
+
+def layernorm_backward(y: torch.Tensor, gamma: torch.Tensor, dout: torch.Tensor, eps: float = 1e-6):
+    """``cpx_layernorm_backward``: (dy (rows, 256) float32, dgamma (256,), dbeta (256,)) of LayerNorm over the 256 channels of the
+    stored pre-norm tensor ``y`` (rows, 256) in the network dtype, from ``dout`` (rows, 256) float32; float64 inside, rounded once."""
+    if y.dim() != 2 or y.shape[1] != 256 or y.dtype not in _DT or not y.is_contiguous() or not y.is_cuda:
+        raise ValueError("layernorm_backward: y must be contiguous device rows (rows, 256) of bf16 / fp16 / fp32")
+    if dout.dtype != torch.float32 or dout.shape != y.shape or not dout.is_contiguous() or dout.device != y.device:
+        raise ValueError("layernorm_backward: dout must be contiguous float32 of y's shape on y's device")
+    if gamma.dtype != torch.float32 or gamma.numel() != 256 or not gamma.is_contiguous() or gamma.device != y.device:
+        raise ValueError("layernorm_backward: gamma must be float32 (256,) on y's device")
+    rows, dev, L = y.shape[0], y.device, _lib.lib()
+    dy = torch.empty((rows, 256), dtype=torch.float32, device=dev)
+    dgamma, dbeta = torch.empty(256, dtype=torch.float32, device=dev), torch.empty(256, dtype=torch.float32, device=dev)
+    key = ("lnbwd", rows, str(dev))
+    if key not in _ws_cache:
+        _ws_cache[key] = torch.empty(L.cpx_layernorm_backward_workspace_bytes(rows, 256), dtype=torch.uint8, device=dev)
+    ws = _ws_cache[key]
+    check(L.cpx_layernorm_backward(_DT[y.dtype], ptr(y), ptr(gamma), ptr(dout), rows, 256, eps, ptr(dy), ptr(dgamma), ptr(dbeta),
+                                   ptr(ws), ws.numel(), _stream(dev)), "layernorm_backward")
+    return dy, dgamma, dbeta
+
+
+NECK_GRAD_NAMES = ("W0", "gamma1", "beta1", "W2", "gamma2", "beta2")
+NECK_GRAD_SHAPES = ((256, 1024), (256,), (256,), (256, 2304), (256,), (256,))
+
+
+def neck_grad_layout() -> tuple[int, list[int]]:
+    """(element count, element offsets of W0, gamma1, beta1, W2, gamma2, beta2) of the flat gradient buffer of ``neck_backward``."""
+    off = (C.c_longlong * 6)()
+    n = _lib.lib().cpx_neck_grad_layout(off)
+    return int(n), [int(v) for v in off]
+
+
+def neck_backward_workspace(n_subtiles: int, dtype_code: int, ld_head: int, device):
+    """(uint8 workspace of ``neck_backward``, byte offsets of dfeat, dy2, da1, dy0 -- float32 (rows, 256) each -- inside it)."""
+    off = (C.c_size_t * 4)()
+    n = _lib.lib().cpx_neck_backward_workspace_bytes(n_subtiles, dtype_code, ld_head, off)
+    if n == 0:
+        raise ValueError("neck_backward_workspace: invalid n_subtiles / dtype / ld_head")
+    return torch.empty(n, dtype=torch.uint8, device=device), [int(v) for v in off]
+
+
+def neck_backward(weights, x: torch.Tensor, fwd: NeckForwardOut, dhead: torch.Tensor, grads: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """``cpx_neck_backward``: the gradients of the six neck tensors of ``weights`` into the flat float32 ``grads``
+    (``neck_grad_layout``), from ``x`` and ``fwd`` (what ``neck_forward_train`` ran this batch on and returned) and ``dhead``
+    (rows, ld_head) float32, the gradient with respect to the head buffer (padding columns 0)."""
+    c, L = weights.c, _lib.lib()
+    rows, dev = x.shape[0], x.device
+    if x.dim() != 2 or x.shape[1] != 1024 or rows == 0 or rows % 1024 or x.dtype not in _DT or _DT[x.dtype] != c.dtype or not x.is_contiguous():
+        raise ValueError("neck_backward: x must be contiguous (n * 1024, 1024) in the network dtype")
+    if dhead.dtype != torch.float32 or tuple(dhead.shape) != (rows, c.ld_head) or not dhead.is_contiguous() or dhead.device != dev:
+        raise ValueError("neck_backward: dhead must be contiguous float32 (rows, ld_head) on x's device")
+    n_g, _off = neck_grad_layout()
+    if grads is None:
+        grads = torch.empty(n_g, dtype=torch.float32, device=dev)
+    if grads.dtype != torch.float32 or grads.numel() != n_g or not grads.is_contiguous() or grads.device != dev:
+        raise ValueError("neck_backward: grads must be the flat float32 buffer of neck_grad_layout")
+    if workspace is None:
+        workspace, _o = neck_backward_workspace(rows // 1024, c.dtype, c.ld_head, dev)
+    if workspace.dtype != torch.uint8 or fwd.workspace.dtype != torch.uint8:
+        raise ValueError("neck_backward: workspaces are uint8 tensors")
+    check(L.cpx_neck_backward(C.byref(c), ptr(x), rows // 1024, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dhead), ptr(grads),
+                              ptr(workspace), workspace.numel(), _stream(dev)), "neck_backward")
+    return grads
+
+
 # ---- t2: training-time augmentation (csrc/cpx_augment.hip) --------------------------------------------------------
 def hed_jitter(img_u8: torch.Tensor, sigma: torch.Tensor, bias: torch.Tensor, cutoff_range=(0.15, 0.85),
                simple_mode: bool = False):

@@ -17,6 +17,10 @@ Deliberately different from the reference:
     ``train_class_head``, fed by ``classpose_amd.dataset_stats``; the reference's command line has both on by default;
   * no HDF5 datasets, learned loss weighting, multi-GPU exchange or optimiser-state resume.
 
+``train_neck=True`` also trains the neck (``NeckParams``; the reference's ``--freeze backbone segmentation_head``, with
+``train_flow_head`` its ``--freeze backbone``): the cache then holds the backbone's output rows and every step runs the neck's
+training forward and ``cpx_neck_backward``.
+
 ``train_flow_head=True`` also trains the flow head ``out`` (``FlowHead``): the reference's ``--freeze backbone neck``, seg + CE +
 Tversky with multiplier 1 each (train.py:482-493), the seg loss being cellpose's ``_loss_fn_seg`` restated (``ops.seg_loss``).
 
@@ -137,6 +141,58 @@ class FlowHead:
         return {"out.weight": self.w.detach().cpu().reshape(192, 256, 1, 1).clone(), "out.bias": self.b.detach().cpu().clone()}
 
 
+NECK_KEYS = ("encoder.neck.0.weight", "encoder.neck.1.weight", "encoder.neck.1.bias", "encoder.neck.2.weight", "encoder.neck.3.weight",
+             "encoder.neck.3.bias")
+
+
+class NeckParams:
+    """The trainable state of the neck (vit_sam.py:216-249; trained by the reference's ``--freeze backbone`` and ``--freeze backbone
+    segmentation_head``): float32 masters of its six tensors in operand layout, as views of ONE flat buffer in the order of
+    ``ops.neck_grad_layout`` -- ``W0`` [256, 1024], ``gamma1``, ``beta1``, ``W2`` [256, 2304] (``neck.2.weight`` permuted (0, 2, 3, 1) as
+    ``NetWeights`` does), ``gamma2``, ``beta2`` -- their AdamW moments and the gradient buffer ``cpx_neck_backward`` fills.  Weight
+    decay applies to every tensor, the LayerNorm vectors included: the reference hands ``net.parameters()`` to AdamW."""
+
+    def __init__(self, sd: dict, weights):
+        shapes = {"encoder.neck.0.weight": (256, 1024, 1, 1), "encoder.neck.2.weight": (256, 256, 3, 3)}
+        for k in NECK_KEYS:
+            if k not in sd or tuple(sd[k].shape) != shapes.get(k, (256,)):
+                raise ValueError(f"{k} of the checkpoint does not describe the Cellpose-SAM neck")
+        dev = weights.device
+        self.weights = weights
+        n, self.off = ops.neck_grad_layout()
+        src = (sd[NECK_KEYS[0]].reshape(256, 1024), sd[NECK_KEYS[1]], sd[NECK_KEYS[2]],
+               sd[NECK_KEYS[3]].permute(0, 2, 3, 1).reshape(256, 2304), sd[NECK_KEYS[4]], sd[NECK_KEYS[5]])
+        flat = torch.cat([t.detach().float().reshape(-1) for t in src])
+        if flat.numel() != n:
+            raise _lib.CpxError("NeckParams: the host's parameter layout differs from the library's")
+        self.params = flat.contiguous().to(dev)
+        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
+
+    def view(self, i: int) -> torch.Tensor:
+        """Master tensor ``i`` of ``ops.NECK_GRAD_NAMES`` (a view of ``params``)."""
+        shape = ops.NECK_GRAD_SHAPES[i]
+        return self.params[self.off[i]:self.off[i] + int(np.prod(shape))].view(shape)
+
+    def update(self, grads: torch.Tensor, step: int, lr: float, **kw) -> None:
+        """One AdamW step of all six tensors from the flat ``grads``, then ``refresh``."""
+        ops.adamw_step(self.params, grads, self.m, self.v, step, lr, **kw)
+        self.refresh()
+
+    def refresh(self) -> None:
+        """Masters -> ``neck0_w`` / ``neck2_w`` and the LayerNorm vectors of ``self.weights`` in place, rounded exactly as at load: the
+        GEMM operands to the network dtype, the vectors through it and back to float32."""
+        c = self.weights.c
+        half = c.dtype != _lib.DT_F32
+        dst = (c.neck0_w, c.neck_ln1_w, c.neck_ln1_b, c.neck2_w, c.neck_ln2_w, c.neck_ln2_b)
+        for i, d in enumerate(dst):
+            ops.round_weights(self.view(i), d, c.dtype, keep_f32=(not half) or i not in (0, 3))
+
+    def state(self) -> dict:
+        v = [self.view(i).detach().cpu().clone() for i in range(6)]
+        return {NECK_KEYS[0]: v[0].reshape(256, 1024, 1, 1), NECK_KEYS[1]: v[1], NECK_KEYS[2]: v[2],
+                NECK_KEYS[3]: v[3].view(256, 3, 3, 256).permute(0, 3, 1, 2).contiguous(), NECK_KEYS[4]: v[4], NECK_KEYS[5]: v[5]}
+
+
 class HeadTrainer:
     """Trains ``out_class`` (nn.Conv2d(256, nclasses * 64, 1)) of a checkpoint; everything else stays as loaded.
 
@@ -147,7 +203,8 @@ class HeadTrainer:
 
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
-                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, train_flow_head: bool = False):
+                 head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, train_flow_head: bool = False,
+                 train_neck: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
@@ -174,6 +231,9 @@ class HeadTrainer:
         self._es = torch.empty(0, dtype=self.dtype).element_size()
         self._buf: dict = {}
         self._init_flow_head(train_flow_head)
+        # ``train_neck``: the neck trains too (``NeckParams``) -- the reference's ``--freeze backbone segmentation_head``, with
+        # ``train_flow_head`` its ``--freeze backbone``.  ``step`` / ``evaluate`` then start from backbone rows (``backbone_features``)
+        self.neck = NeckParams(self.sd, self.weights) if train_neck else None
 
     def _init_flow_head(self, train_flow_head: bool) -> None:
         """``train_flow_head``: the flow head ``out`` trains too (the reference's ``--freeze backbone neck``); ``step`` / ``evaluate``
@@ -235,6 +295,58 @@ class HeadTrainer:
             out[s * TOKENS:(s + k) * TOKENS] = ops.neck_features(self._net_ws, FB, self.dtype)[:k * TOKENS]
         return out
 
+    def backbone_features(self, X) -> torch.Tensor:
+        """The last block's output (n * 1024, 1024) in the network dtype of n crops: the input of the neck, what a trainer built with
+        ``train_neck`` caches (2 MB per crop in bf16, against 512 KB of neck features)."""
+        patches = self._patches(X)
+        n = patches.shape[0] // TOKENS
+        FB, c, dev = self.feature_batch, self.weights.c, self.device
+        out = torch.empty((n * TOKENS, 1024), dtype=self.dtype, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for s in range(0, n, FB):
+            k = min(FB, n - s)
+            chunk = patches[s * TOKENS:(s + k) * TOKENS]
+            if k < FB:
+                chunk = torch.cat([chunk, torch.zeros(((FB - k) * TOKENS, 192), dtype=self.dtype, device=dev)])
+            check(self._L.cpx_net_forward(C.byref(c), ptr(chunk), FB, ptr(self._head_fb), ptr(self._net_ws), self._net_ws.numel(), st),
+                  "net_forward")
+            out[s * TOKENS:(s + k) * TOKENS] = ops.backbone_rows(self._net_ws, FB, self.dtype)[:k * TOKENS]
+        return out
+
+    def _as_backbone(self, X) -> torch.Tensor:
+        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == 1024 and X.dtype == self.dtype and X.is_cuda:
+            if X.shape[0] % TOKENS:
+                raise ValueError("backbone rows: 1024 rows per crop")
+            return X.contiguous()
+        return self.backbone_features(X)
+
+    def _neck_forward(self, X):
+        """The training tail on the backbone rows of ``X`` (or on ``X`` itself when it is such rows): (x, ``ops.NeckForwardOut``)."""
+        x = self._as_backbone(X)
+        rows, c = x.shape[0], self.weights.c
+        key = ("neck_fwd", rows)
+        if key not in self._buf:
+            self._buf[key] = (torch.empty((rows, c.ld_head), dtype=torch.float32, device=self.device),
+                              ops.neck_train_workspace(rows // TOKENS, c.dtype, self.device))
+        head, ws = self._buf[key]
+        return x, ops.neck_forward_train(self.weights, x, head=head, workspace=ws)
+
+    def _neck_backward(self, x, fwd, o, seg) -> torch.Tensor:
+        """``cpx_neck_backward`` from the packed gradient of the head buffer: flow columns from the seg loss (zeros without it), class
+        columns from the class loss, padding columns 0."""
+        rows, c, ncols = x.shape[0], self.weights.c, self.nclasses * 64
+        key = ("neck_bwd", rows)
+        if key not in self._buf:
+            self._buf[key] = (torch.zeros((rows, c.ld_head), dtype=torch.float32, device=self.device),
+                              ops.neck_backward_workspace(rows // TOKENS, c.dtype, c.ld_head, self.device)[0])
+        dhead, ws = self._buf[key]
+        if seg is None:
+            dhead[:, :192].zero_()
+        else:
+            dhead[:, :192].copy_(seg.dlogits)
+        dhead[:, 192:192 + ncols].copy_(o.dlogits)
+        return ops.neck_backward(self.weights, x, fwd, dhead, self.neck.grads, ws)
+
     def _as_features(self, X) -> torch.Tensor:
         if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == 256 and X.dtype == self.dtype and X.is_cuda:
             if X.shape[0] % TOKENS:
@@ -255,11 +367,17 @@ class HeadTrainer:
         return out
 
     def _loss(self, X, labels):
-        feat = self._as_features(X)
+        self._fwd = None
+        if self.neck is not None:
+            x, fwd = self._neck_forward(X)
+            self._fwd = (x, fwd)
+            feat = fwd.feat
+        else:
+            feat = self._as_features(X)
         lab = _labels_i16(labels, self.device)
         if lab.shape[0] * TOKENS != feat.shape[0]:
             raise ValueError(f"{feat.shape[0] // TOKENS} crops but {lab.shape[0]} label maps")
-        head = self.head(feat)
+        head = self.head(feat) if self.neck is None else fwd.head
         key = ("dl", feat.shape[0])
         if key not in self._buf:
             self._buf[key] = torch.empty((feat.shape[0], self.nclasses * 64), dtype=torch.float32, device=self.device)
@@ -308,6 +426,8 @@ class HeadTrainer:
         step from the seg loss: same step counter, betas and weight decay."""
         feat, head, o = self._loss(X, labels)             # raises before anything is updated
         seg = self._seg_loss(head, flow_targets)          # (so does this)
+        if self.neck is not None:                         # reads the head operand of THIS forward: before any refresh
+            self._neck_backward(*self._fwd, o, seg)
         dW, db = ops.head_wgrad(o.dlogits, feat)
         self.n_steps += 1
         kw = dict(betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay)     # net.parameters(): decay on the bias too
@@ -316,6 +436,8 @@ class HeadTrainer:
         self._refresh_operands()
         if seg is not None:
             self.flow.update(seg.dlogits, feat, self.n_steps, lr, **kw)
+        if self.neck is not None:
+            self.neck.update(self.neck.grads, self.n_steps, lr, **kw)
         return self._result(o, feat.shape[0] // TOKENS, seg)
 
     def _refresh_operands(self) -> None:
@@ -340,12 +462,15 @@ class HeadTrainer:
             sd.update(self.flow.state())
             if self.diam_labels is not None and "diam_labels" in sd:
                 sd["diam_labels"] = torch.full_like(sd["diam_labels"], self.diam_labels)
+        if self.neck is not None:                         # ``encoder.neck.*`` from the master copies
+            sd.update(self.neck.state())
         return sd
 
     def save(self, path, save_only_trainable_params: bool = False) -> None:
         sd = self.state_dict()
         if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
-            sd = {k: sd[k] for k in ("out_class.weight", "out_class.bias") + (("out.weight", "out.bias") if self.flow is not None else ())}
+            sd = {k: sd[k] for k in ("out_class.weight", "out_class.bias") + (("out.weight", "out.bias") if self.flow is not None else ())
+                  + (NECK_KEYS if self.neck is not None else ())}
         torch.save(sd, os.fspath(path))
 
 
@@ -520,13 +645,16 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     test_cached = cached or (cache_features and augment is not None)
     dev = trainer.device
     lab_dev = test_lab_dev = feats = test_feats = None
+    # a trainer that trains the neck starts from the backbone's output instead of the neck's
+    neck = getattr(trainer, "neck", None) is not None
+    cache, width = (trainer.backbone_features, 1024) if neck else (trainer.features, 256)
     if cached:
-        train_logger.info(">>> caching neck features of %d training crops", nimg)
-        feats = trainer.features(images).view(nimg, TOKENS, 256)
+        train_logger.info(">>> caching %s of %d training crops", "backbone rows" if neck else "neck features", nimg)
+        feats = cache(images).view(nimg, TOKENS, width)
         lab_dev = _labels_i16(labels, dev)
     if test_cached:
         if has_test:
-            test_feats = trainer.features(test_images).view(len(test_images), TOKENS, 256)
+            test_feats = cache(test_images).view(len(test_images), TOKENS, width)
             test_lab_dev = _labels_i16(test_labels, dev)
     train_logger.info(">>> n_epochs=%d, n_train=%d, n_test=%s, AdamW, learning_rate=%0.5f, weight_decay=%0.5f, cached features: %s",
                       n_epochs, nimg, len(test_images) if has_test else None, learning_rate, trainer.weight_decay, cached)
@@ -546,7 +674,7 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
                 t = tgts[torch.from_numpy(idx).to(tgts.device)]
             if cached:
                 ti = torch.from_numpy(idx).to(dev)
-                x, y = feats[ti].reshape(-1, 256), lab_dev[ti]
+                x, y = feats[ti].reshape(-1, width), lab_dev[ti]
             elif pool is not None:
                 res = _augment.augment_batch_pool(pool, idx, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
                                                   dtype=trainer.dtype, out=CROP, rescale=None if rsc is None else rsc[idx],
@@ -572,7 +700,7 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
             tsum, tseg, tcount = 0.0, 0.0, 0
             for s in range(0, len(test_images), batch_size):
                 if test_cached:
-                    x, y = test_feats[s:s + batch_size].reshape(-1, 256), test_lab_dev[s:s + batch_size]
+                    x, y = test_feats[s:s + batch_size].reshape(-1, width), test_lab_dev[s:s + batch_size]
                 else:
                     x, y = test_images[s:s + batch_size], test_labels[s:s + batch_size]
                 r = trainer.evaluate(x, y) if test_tgts is None else trainer.evaluate(x, y, flow_targets=test_tgts[s:s + batch_size])

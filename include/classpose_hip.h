@@ -537,6 +537,44 @@ int cpx_unet_head_backward(const cpx_conv_op *ops_host, int n_ops, const void *f
                            const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dlogits, float *grads,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* Training the neck (csrc/cpx_train_neck.hip; additive, no ABI bump): the reference's `--freeze backbone` (with the flow head) and
+ * `--freeze backbone segmentation_head` (vit_sam.py:216-249, run_training.py:92-98).  The neck is the tail of cpx_net_forward:
+ *   y0 = x W0^T -> a1 = LayerNorm2d(y0) -> y2 = conv3x3(a1, W2) -> feat = LayerNorm2d(y2) -> head = feat Wh^T + bh.
+ * Every entry takes a stream and allocates nothing; no floating-point atomics: bitwise reproducible.  Not with a UNet head
+ * (n_unet_ops > 0 is refused: that head's backward gives the neck output no gradient).
+ *   cpx_net_backbone_offset: byte offset, inside the workspace of cpx_net_forward for the same (n_subtiles, dtype), of the last
+ *   block's output x [n_subtiles * 1024][1024] (network dtype), valid after a forward until the next one (the tail only reads it).
+ *   (size_t)-1 = invalid argument (the offset itself is 0).
+ *   cpx_neck_forward_train: exactly the launches of that tail on a given x (16-byte aligned), in its order, writing y0 (before
+ *   LayerNorm 1), a1 (after it), y2 (before LayerNorm 2) and feat (the neck output), [n_subtiles * 1024][256] of the network dtype
+ *   each, at the four byte offsets of cpx_neck_train_layout in `workspace` (256-byte aligned): nothing is overwritten.  head and feat
+ *   are bitwise what cpx_net_forward produces for the same n_subtiles.
+ *   cpx_layernorm_backward: y [rows][C] as stored (dtype, widened exactly), gamma [C], dout [rows][C] float32, C = 256.  Per row, in
+ *   float64 from y: mean, biased var, rstd = 1 / sqrt(var + (double)eps), xhat = (y - mean) rstd, g = dout gamma,
+ *   dy = rstd (g - mean(g) - xhat mean(g xhat)); dgamma = sum over rows of dout xhat, dbeta = sum over rows of dout.  Row sums:
+ *   a fixed butterfly in one wave; column sums: per-workgroup partials over blocks of 64 rows, then one workgroup adds them in block
+ *   order.  Every output is rounded to float32 once.  Pointers 16-byte aligned.
+ *   cpx_neck_backward: x and the workspace cpx_neck_forward_train ran this batch in, dhead [rows][ld_head] float32 = d loss / d head
+ *   (flow columns 0..191 from cpx_seg_loss or zeros, class columns from cpx_class_loss, padding columns 0) -> grads, one flat float32
+ *   buffer W0 [256][1024] | gamma1 | beta1 | W2 [256][2304] (k = tap * 256 + c, the operand's layout) | gamma2 | beta2 at the element
+ *   offsets of cpx_neck_grad_layout (which returns the element count; off may be NULL).  Steps: dfeat = dhead Wh (the rounded
+ *   operand widened, float32 GEMM), LayerNorm 2 backward, dW2 and da1 = col2im(dy2 W2) by the kernels of cpx_unet_head_backward (slabs
+ *   of cpx_unet_wgrad_slab_rows rows), LayerNorm 1 backward, dW0 = dy0^T x.  Rounding to the network dtype is the identity
+ *   (straight-through); nothing flows to the backbone.  cpx_neck_backward_workspace_bytes also returns, where off is not NULL, the
+ *   byte offsets of dfeat, dy2, da1 and dy0 ([rows][256] float32 each) in that workspace.                                        */
+size_t cpx_net_backbone_offset(int n_subtiles, int dtype);
+size_t cpx_neck_train_workspace_bytes(int n_subtiles, int dtype);
+int cpx_neck_train_layout(int n_subtiles, int dtype, size_t *off /* [4]: y0, a1, y2, feat */);
+int cpx_neck_forward_train(const cpx_net_weights *w, const void *x, int n_subtiles, float *head, void *workspace,
+                           size_t workspace_bytes, void *stream);
+size_t cpx_layernorm_backward_workspace_bytes(int rows, int C);
+int cpx_layernorm_backward(int dtype, const void *y, const float *gamma, const float *dout, int rows, int C, float eps,
+                           float *dy, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+long long cpx_neck_grad_layout(long long *off /* [6] or NULL */);
+size_t cpx_neck_backward_workspace_bytes(int n_subtiles, int dtype, int ld_head, size_t *off /* [4] or NULL: dfeat, dy2, da1, dy0 */);
+int cpx_neck_backward(const cpx_net_weights *w, const void *x, int n_subtiles, const void *fwd_workspace, size_t fwd_workspace_bytes,
+                      const float *dhead, float *grads, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------
  * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)
  * replaces augment_single_image, /root/reference/src/classpose/dataset.py:23-56: the stain jitter, cellpose's
