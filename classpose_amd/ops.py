@@ -1319,3 +1319,112 @@ def label_stats(inst: torch.Tensor, cls: torch.Tensor, ncls: int, workspace: tor
             what = "a negative instance id" if bits & 1 else f"a class >= {ncls}"
             raise ValueError(f"label_stats: image {i} has {what}")
     return class_px, inst_per_class, n_masks, mid_area, status
+
+
+# ---- r1: polygon rings -> instance-id maps (csrc/cpx_rasterize.hip) ------------------------------------------------
+# the constants of csrc/cpx_rasterize.hip the tests probe both sides of (tests/test_rasterize_host.py pins them on the source)
+RASTER_SMALL_MAX_VERTICES = 256      # RS_SMALL_VERTS: a ring of more vertices takes the large-ring path
+RASTER_SMALL_MAX_AREA = 4096         # RS_SMALL_AREA: so does a ring whose clipped bounding box holds more pixels
+RASTER_EDGE_CHUNK = 512              # RL_CHUNK: edges the large-ring path compacts per pass
+RASTER_MAX_DIM = 32768               # RS_MAX_DIM: H, W limit
+
+
+def _rs_array(x, np_dtype, torch_dtype, what: str):
+    """a numpy array or a torch tensor of the one dtype the kernel reads; anything else raises (no silent casts of ids)"""
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch_dtype:
+            raise ValueError(f"rasterize_polygons: {what} must be {torch_dtype}, not {x.dtype}")
+        return x
+    x = np.asarray(x)
+    if x.dtype != np_dtype:
+        raise ValueError(f"rasterize_polygons: {what} must be {np.dtype(np_dtype).name}, not {x.dtype}")
+    return x
+
+
+def rasterize_polygons(xy, ring_off, ring_value, shape, ring_image=None, n_images: int = 1, out: torch.Tensor | None = None,
+                       device=None) -> torch.Tensor:
+    """``cpx_rasterize_polygons``: rings -> int32 instance maps ``(n_images, H, W)`` on the device, by the rule of
+    include/classpose_hip.h (pixel centre on the ring or odd crossing number; ``max`` with what the map holds).
+
+    xy (n_vertices, 2) float64 in image-local pixels, ring_off (n_rings + 1,) int64 offsets into xy, ring_value (n_rings,) int32
+    > 0, ring_image (n_rings,) int32 in ``0..n_images-1`` or None = image 0: numpy arrays (uploaded here) or tensors on the
+    device.  ``out``: an int32 device map to paint onto (composes with its contents); else a zeroed one on ``device``.  Every
+    argument is validated before the launch -- dtypes, offsets, values, image indices, finite coordinates -- and ``ValueError``
+    is raised; the kernel never sees a bad offset or a NaN."""
+    try:
+        H, W = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"rasterize_polygons: shape must be (H, W), not {shape!r}") from None
+    n_images = int(n_images)
+    if not (1 <= H <= RASTER_MAX_DIM and 1 <= W <= RASTER_MAX_DIM) or n_images < 1:
+        raise ValueError(f"rasterize_polygons: need 1 <= H, W <= {RASTER_MAX_DIM} and n_images >= 1, not {(n_images, H, W)}")
+    xy = _rs_array(xy, np.float64, torch.float64, "xy")
+    ring_off = _rs_array(ring_off, np.int64, torch.int64, "ring_off")
+    ring_value = _rs_array(ring_value, np.int32, torch.int32, "ring_value")
+    if ring_image is not None:
+        ring_image = _rs_array(ring_image, np.int32, torch.int32, "ring_image")
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError(f"rasterize_polygons: xy must be (n_vertices, 2), not {tuple(xy.shape)}")
+    if ring_off.ndim != 1 or ring_off.shape[0] < 1 or ring_value.ndim != 1 or ring_value.shape[0] != ring_off.shape[0] - 1:
+        raise ValueError("rasterize_polygons: ring_off must hold n_rings + 1 offsets for the n_rings entries of ring_value")
+    n_rings, n_vertices = int(ring_value.shape[0]), int(xy.shape[0])
+    if ring_image is not None and tuple(ring_image.shape) != (n_rings,):
+        raise ValueError("rasterize_polygons: ring_image must hold one image index per ring")
+    if int(ring_off[0]) < 0 or int(ring_off[-1]) > n_vertices or not bool((ring_off[1:] >= ring_off[:-1]).all()):
+        raise ValueError(f"rasterize_polygons: ring_off must be non-decreasing within 0..{n_vertices}")
+    if n_rings and not bool((ring_value > 0).all()):
+        raise ValueError("rasterize_polygons: every ring_value must be > 0")
+    if ring_image is not None and n_rings and not bool(((ring_image >= 0) & (ring_image < n_images)).all()):
+        raise ValueError(f"rasterize_polygons: ring_image must lie in 0..{n_images - 1}")
+    finite = torch.isfinite(xy).all() if isinstance(xy, torch.Tensor) else np.isfinite(xy).all()
+    if not bool(finite):
+        raise ValueError("rasterize_polygons: xy holds a NaN or an infinity")
+    given = [t for t in (xy, ring_off, ring_value, ring_image, out) if isinstance(t, torch.Tensor)]
+    if out is not None:
+        if out.dtype != torch.int32 or tuple(out.shape) != (n_images, H, W) or not out.is_contiguous():
+            raise ValueError(f"rasterize_polygons: out must be a contiguous int32 tensor of shape {(n_images, H, W)}")
+    dev = given[0].device if given else torch.device("cuda" if device is None else device)
+    if dev.type != "cuda" or any(t.device != dev for t in given):
+        raise ValueError("rasterize_polygons: tensors must be on one cuda device")
+    if out is None:
+        out = torch.zeros((n_images, H, W), dtype=torch.int32, device=dev)
+    if n_rings == 0:
+        return out
+    up = lambda t: None if t is None else (t.contiguous() if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t)).to(dev))
+    xy, ring_off, ring_value, ring_image = up(xy), up(ring_off), up(ring_value), up(ring_image)
+    L = _lib.lib()
+    nbytes = L.cpx_rasterize_workspace_bytes(n_rings, n_vertices, n_images, H, W)
+    if nbytes == 0:
+        raise ValueError(f"rasterize_polygons: unsupported arguments n_rings={n_rings}, n_images={n_images}, H={H}, W={W}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.cpx_rasterize_polygons(ptr(xy), ptr(ring_off), ptr(ring_value), ptr(ring_image), n_rings, n_images, H, W, ptr(out),
+                                   ptr(ws), nbytes, _stream(dev)), "rasterize_polygons")
+    return out
+
+
+def ids_to_classes(inst: torch.Tensor, class_of) -> torch.Tensor:
+    """``cpx_ids_to_classes``: uint8 ``class_of[inst]`` of an int32 device map; class_of (n_ids + 1,) uint8, numpy or on the
+    device, entry 0 = the background's class.  An id outside ``0..n_ids`` raises ``ValueError``."""
+    if not isinstance(inst, torch.Tensor) or inst.dtype != torch.int32:
+        raise ValueError("ids_to_classes: inst must be an int32 tensor")
+    if not isinstance(class_of, torch.Tensor):
+        class_of = np.asarray(class_of)
+        if class_of.dtype != np.uint8:
+            raise ValueError(f"ids_to_classes: class_of must be uint8, not {class_of.dtype}")
+        class_of = torch.from_numpy(np.ascontiguousarray(class_of))
+    if class_of.dtype != torch.uint8 or class_of.dim() != 1 or class_of.numel() < 1:
+        raise ValueError("ids_to_classes: class_of must be a uint8 vector with an entry for id 0")
+    if not inst.is_cuda:
+        raise ValueError("ids_to_classes: inst must be on a cuda device")
+    inst = inst.contiguous()
+    dev = inst.device
+    class_of = class_of.to(dev).contiguous()
+    n_ids = class_of.numel() - 1
+    cls = torch.empty(inst.shape, dtype=torch.uint8, device=dev)
+    if inst.numel() == 0:
+        return cls
+    lo, hi = int(inst.min()), int(inst.max())
+    if lo < 0 or hi > n_ids:
+        raise ValueError(f"ids_to_classes: ids span {lo}..{hi} but class_of covers 0..{n_ids}")
+    check(_lib.lib().cpx_ids_to_classes(ptr(inst), inst.numel(), ptr(class_of), n_ids, ptr(cls), _stream(dev)), "ids_to_classes")
+    return cls

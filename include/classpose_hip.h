@@ -900,6 +900,41 @@ int cpx_write_geojson(const char *contours_path, const char *centroids_path, con
 int cpx_find_contours_ccomp_host(const uint8_t *mask_host, int H, int W, int32_t *xy_pool, int max_pts,
                                  int32_t *offsets, int32_t *n_pts, int32_t *parent, int max_contours);
 
+/* ------------------------------------------------------------------------
+ * r1  polygon rings -> instance-id maps: the inverse of the polygoniser (csrc/cpx_rasterize.hip)
+ * replaces the host painting of annotations in paper_experiments/scripts/organise-datasets.py:626-652 of the reference
+ * (`mask[..., 0][draw.polygon(g[:, 1], g[:, 0])] = i` per ring of every feature, in file order; `mask[..., 1][...] = idx_class`).
+ * Runs on `stream`, allocates nothing, integer atomics only: the maps are bitwise reproducible.
+ * ---------------------------------------------------------------------- */
+/* cpx_rasterize_polygons: ring k = xy[ring_off[k] .. ring_off[k + 1]) as (x, y) float64 pairs in image-local pixels, painted
+ *   into image ring_image[k] (NULL = image 0) of inst [n_images][H][W] int32 as inst[p] = max(inst[p], ring_value[k]) by an
+ *   integer atomic max: with values that rise in feature order "the later feature wins" (the reference's painter's order) needs
+ *   no ordering between workgroups.  inst is read-modify-write: clear it first, or paint onto an earlier call's map.
+ *   THE RULE.  Pixel (r, c) has its centre at x = c, y = r.  A ring paints the pixel when the centre lies ON the ring (an edge or
+ *   a vertex) or has an odd crossing number: even-odd rule, half-open edge test min(y0, y1) <= y < max(y0, y1).  This is the
+ *   documented behaviour of skimage.draw.polygon with the boundary included, restated (not pinned against scikit-image).  A
+ *   closing vertex equal to the first changes nothing; a ring with fewer than three vertices (after that) paints nothing; a ring
+ *   partly or wholly outside the image is clipped to it; every ring paints, holes included, as the reference's `for g in
+ *   geometry` does, so a feature is the union of its rings.  A ring with ring_value <= 0 or an image outside 0..n_images-1 is
+ *   skipped.
+ *   ARITHMETIC.  One orientation predicate, d = (x1 - x0) * (py - y0) - (y1 - y0) * (px - x0), in float64 without contraction
+ *   and in this operand order; on the edge: d == 0 inside the edge's closed box; crossing: (y0 <= py < y1 and d > 0) or
+ *   (y1 <= py < y0 and d < 0).  EXACT for vertices that are multiples of 1/16 with |coordinate| <= 32768 and H, W <= 32768: the
+ *   differences are at most 2^20 sixteenths and each product stays below 2^53.  For other float64 coordinates a centre can be
+ *   misclassified only where d rounds through zero.  The bounding box is clamped to the image in double before any conversion
+ *   to int.  ring_off must be non-decreasing and inside xy (the caller's duty: the entry does not know the length of xy).
+ *   Rings of at most 256 vertices and 4096 box pixels take one wave each, any other ring one workgroup per band of 8 rows.
+ *   H, W <= 32768.  n_rings == 0 returns without a launch.  cpx_rasterize_workspace_bytes is host only and returns 0 for
+ *   arguments the entry would refuse.
+ * cpx_ids_to_classes: cls[p] = class_of[inst[p]] for inst[p] in 0..n_ids (class_of has n_ids + 1 entries; an id outside that
+ *   range gives 0): the second channel of the reference's mask from the first.                                               */
+size_t cpx_rasterize_workspace_bytes(long long n_rings, long long n_vertices, int n_images, int H, int W);
+int cpx_rasterize_polygons(const double *xy, const long long *ring_off, const int *ring_value, const int *ring_image,
+                           long long n_rings, int n_images, int H, int W, int *inst, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int cpx_ids_to_classes(const int *inst, long long n_px, const unsigned char *class_of, int n_ids, unsigned char *cls,
+                       void *stream);
+
 
 #ifdef __cplusplus
 }
