@@ -88,6 +88,31 @@ int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *
 size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS);
 void cpx_unet_act_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, size_t *off, int *ld);   // n_ops <= 64
 
+// what the training translation units (cpx_train*.hip) share
+static inline size_t es_of(int dtype) { return dtype == CPX_DT_F32 ? 4 : 2; }
+static inline bool dtype_ok(int dtype) { return dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32; }
+// runs the statement(s) with `DT` a compile-time constant equal to `dtype` (which the caller has checked with dtype_ok)
+#define CPX_DT_DISPATCH(dtype, DT, ...)                                                   \
+    do {                                                                                  \
+        if ((dtype) == CPX_DT_BF16) { constexpr int DT = CPX_DT_BF16; __VA_ARGS__; }      \
+        else if ((dtype) == CPX_DT_F16) { constexpr int DT = CPX_DT_F16; __VA_ARGS__; }   \
+        else { constexpr int DT = CPX_DT_F32; __VA_ARGS__; }                              \
+    } while (0)
+// element idx of a tensor of element type DT, widened exactly to float32
+template <int DT>
+__device__ __forceinline__ float load_f32(const void *p, size_t idx) {
+    if constexpr (DT == CPX_DT_F32) return ((const float *)p)[idx];
+    else if constexpr (DT == CPX_DT_F16) return (float)((const _Float16 *)p)[idx];
+    else return bf16_to_f32(((const unsigned short *)p)[idx]);
+}
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;               // every lane holds the same bits: a + b and b + a round alike
+}
+
+#define UW_SLAB 512                    // rows per slab of the weight gradients (k_wgrad, k_uwgrad) = longest serial accumulation chain L
+
 // kernels of the UNet head's backward (cpx_train_unet.hip) that the neck's backward (cpx_train_neck.hip) runs too
 struct UwArgs {
     const float *dy;                   // [rows][Npad], zero beyond the valid columns

@@ -19,7 +19,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define LOSS_TOK_PER_BLOCK 64      // tokens (8 x 8 pixel patches) per workgroup of the loss passes: 4 waves x 16 tokens
 #define LOSS_MAX_CLS 64            // general kernels: lane c of a wave carries class c's sums
 #define LOSS_REG_CLS 16            // up to here the per-class values of a lane live in registers (k_loss_*_reg)
-#define WG_SLAB 512                // rows per slab of cpx_head_wgrad = longest serial accumulation chain L
 #define WG_FEAT 256                // feature channels of the neck
 
 // ---------------------------------------------------------------------------
@@ -62,14 +61,12 @@ __global__ void __launch_bounds__(256) k_patchify_f32(const float *__restrict__ 
 
 extern "C" int cpx_patchify_f32(const float *x, int nS, int H, int W, int dtype, void *patches, void *stream) {
     CPX_REQUIRE(x && patches && nS > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0);
-    CPX_REQUIRE(dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32);
+    CPX_REQUIRE(dtype_ok(dtype));
     const size_t n_items = (size_t)nS * (H / 8) * (W / 8) * 24;
     CPX_REQUIRE(n_items / 256 < 0x7fffffffull);
     dim3 grid((unsigned)((n_items + 255) / 256)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CPX_DT_BF16) hipLaunchKernelGGL(k_patchify_f32<CPX_DT_BF16>, grid, block, 0, s, x, H, W, n_items, patches);
-    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_patchify_f32<CPX_DT_F16>, grid, block, 0, s, x, H, W, n_items, patches);
-    else hipLaunchKernelGGL(k_patchify_f32<CPX_DT_F32>, grid, block, 0, s, x, H, W, n_items, patches);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_patchify_f32<DT>, grid, block, 0, s, x, H, W, n_items, patches));
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }
@@ -94,12 +91,6 @@ static LossWs loss_ws(int nI, int H, int W, int ncls) {
 extern "C" size_t cpx_class_loss_workspace_bytes(int nI, int H, int W, int ncls) {
     if (nI <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8 || ncls < 2 || ncls > LOSS_MAX_CLS) return 0;
     return loss_ws(nI, H, W, ncls).total;
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;               // every lane holds the same bits: a + b and b + a round alike
 }
 
 struct LossArgs {
@@ -486,34 +477,27 @@ extern "C" int cpx_seg_loss(const float *head, int ld_head, const float *targets
 // ---------------------------------------------------------------------------
 // weight gradient of the 1x1 head: dW [N][256] = dlogits^T feat, db [N] = column sums of dlogits
 // ---------------------------------------------------------------------------
-// One workgroup = one (32-column tile of dlogits, slab of WG_SLAB rows); wave w owns feature channels [64 w, 64 w + 64).
+// One workgroup = one (32-column tile of dlogits, slab of UW_SLAB rows); wave w owns feature channels [64 w, 64 w + 64).
 // v_mfma_f32_32x32x2_f32 reduces over two ROWS per issue: lane (r, h2) feeds dlogits[row + h2][n0 + r] and
 // feat[row + h2][k0 + r] straight from global memory (128-byte row segments), the features widened exactly to float32.
 // Partials [slab][N][256] float32 and [slab][N] float64, added by k_wgrad_reduce in slab order in float64, rounded once.
-template <int DT>
-__device__ __forceinline__ float feat_load(const void *f, size_t idx) {
-    if constexpr (DT == CPX_DT_F32) return ((const float *)f)[idx];
-    else if constexpr (DT == CPX_DT_F16) return (float)((const _Float16 *)f)[idx];
-    else return bf16_to_f32(((const unsigned short *)f)[idx]);
-}
-
 template <int DT>
 __global__ void __launch_bounds__(256) k_wgrad(const float *__restrict__ dl, const void *__restrict__ feat, int rows, int N,
                                                float *__restrict__ part_w, double *__restrict__ part_b) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h2 = lane >> 5;
     const int n0 = blockIdx.x * 32, slab = blockIdx.y, k0 = wave * 64;
-    const int row0 = slab * WG_SLAB, row1 = min(rows, row0 + WG_SLAB);
+    const int row0 = slab * UW_SLAB, row1 = min(rows, row0 + UW_SLAB);
     f32x16 acc0, acc1;
 #pragma unroll
     for (int v = 0; v < 16; ++v) { acc0[v] = 0.f; acc1[v] = 0.f; }
     double bsum = 0;
 #pragma unroll 8
-    for (int i = 0; i < WG_SLAB / 2; ++i) {                           // (uniform trip count: the MFMA needs every lane)
+    for (int i = 0; i < UW_SLAB / 2; ++i) {                           // (uniform trip count: the MFMA needs every lane)
         const int row = row0 + 2 * i + h2;
         const bool in = row < row1;
         const float a = in ? dl[(size_t)row * N + n0 + r] : 0.f;
-        const float b0 = in ? feat_load<DT>(feat, (size_t)row * WG_FEAT + k0 + r) : 0.f;
-        const float b1 = in ? feat_load<DT>(feat, (size_t)row * WG_FEAT + k0 + 32 + r) : 0.f;
+        const float b0 = in ? load_f32<DT>(feat, (size_t)row * WG_FEAT + k0 + r) : 0.f;
+        const float b1 = in ? load_f32<DT>(feat, (size_t)row * WG_FEAT + k0 + 32 + r) : 0.f;
         acc0 = MFMA_F32(a, b0, acc0);
         acc1 = MFMA_F32(a, b1, acc1);
         bsum += (double)a;
@@ -548,29 +532,27 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce(const float *__restrict__ 
 }
 
 static size_t wgrad_part_b_off(int rows, int N) {
-    const size_t n_slabs = (size_t)(rows + WG_SLAB - 1) / WG_SLAB;
+    const size_t n_slabs = (size_t)(rows + UW_SLAB - 1) / UW_SLAB;
     return cpx_align_up(n_slabs * N * WG_FEAT * sizeof(float), 256);
 }
-extern "C" int cpx_head_wgrad_slab_rows(void) { return WG_SLAB; }
+extern "C" int cpx_head_wgrad_slab_rows(void) { return UW_SLAB; }
 extern "C" size_t cpx_head_wgrad_workspace_bytes(int rows, int n_cols) {
     if (rows <= 0 || n_cols <= 0 || n_cols % 32) return 0;
-    const size_t n_slabs = (size_t)(rows + WG_SLAB - 1) / WG_SLAB;
+    const size_t n_slabs = (size_t)(rows + UW_SLAB - 1) / UW_SLAB;
     return wgrad_part_b_off(rows, n_cols) + cpx_align_up(n_slabs * n_cols * sizeof(double), 256);
 }
 extern "C" int cpx_head_wgrad(const float *dlogits, const void *feat, int dtype, int rows, int n_cols, float *dW, float *db,
                               void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(dlogits && feat && dW && db && workspace && rows > 0 && n_cols > 0 && n_cols % 32 == 0);
-    CPX_REQUIRE(dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32);
+    CPX_REQUIRE(dtype_ok(dtype));
     CPX_REQUIRE(workspace_bytes >= cpx_head_wgrad_workspace_bytes(rows, n_cols) && ((uintptr_t)workspace & 7) == 0);
-    const int n_slabs = (rows + WG_SLAB - 1) / WG_SLAB;
+    const int n_slabs = (rows + UW_SLAB - 1) / UW_SLAB;
     CPX_REQUIRE(n_slabs <= 65535);
     float *part_w = (float *)workspace;
     double *part_b = (double *)((char *)workspace + wgrad_part_b_off(rows, n_cols));
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(n_cols / 32, n_slabs), block(256);
-    if (dtype == CPX_DT_BF16) hipLaunchKernelGGL(k_wgrad<CPX_DT_BF16>, grid, block, 0, s, dlogits, feat, rows, n_cols, part_w, part_b);
-    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_wgrad<CPX_DT_F16>, grid, block, 0, s, dlogits, feat, rows, n_cols, part_w, part_b);
-    else hipLaunchKernelGGL(k_wgrad<CPX_DT_F32>, grid, block, 0, s, dlogits, feat, rows, n_cols, part_w, part_b);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_wgrad<DT>, grid, block, 0, s, dlogits, feat, rows, n_cols, part_w, part_b));
     CPX_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_wgrad_reduce, dim3(cpx_cdiv((long long)n_cols * WG_FEAT, 256)), block, 0, s, part_w, part_b, n_slabs, n_cols, dW, db);
     CPX_CHECK_LAUNCH();

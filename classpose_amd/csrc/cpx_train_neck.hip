@@ -16,9 +16,6 @@
 #define NECK_K2 (9 * NECK_C)       // im2col width of the 3x3 conv, k = tap * 256 + c
 #define LNB_ROWS 64                // rows per workgroup of k_ln_bwd: 16 per wave
 
-static inline size_t es_of(int dtype) { return dtype == CPX_DT_F32 ? 4 : 2; }
-static inline bool dtype_ok(int dtype) { return dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32; }
-
 // ---------------------------------------------------------------------------
 // the training forward
 // ---------------------------------------------------------------------------
@@ -86,12 +83,6 @@ extern "C" int cpx_neck_forward_train(const cpx_net_weights *w, const void *x, i
 // ---------------------------------------------------------------------------
 // LayerNorm over channels, backward
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;               // every lane holds the same bits: a + b and b + a round alike
-}
-
 // the lane's four consecutive channels of a stored row, widened exactly: 16 bytes (float32) or 8 bytes (bf16 / fp16) per lane
 template <int DT>
 __device__ __forceinline__ void load4(const void *y, size_t idx, double v[4]) {
@@ -180,9 +171,7 @@ extern "C" int cpx_layernorm_backward(int dtype, const void *y, const float *gam
     const int nblk = ln_nblk(rows);
     double *part = (double *)workspace;
     const dim3 grid(nblk), block(256);
-    if (dtype == CPX_DT_BF16) hipLaunchKernelGGL(k_ln_bwd<CPX_DT_BF16>, grid, block, 0, s, y, gamma, dout, rows, (double)eps, dy, part);
-    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_ln_bwd<CPX_DT_F16>, grid, block, 0, s, y, gamma, dout, rows, (double)eps, dy, part);
-    else hipLaunchKernelGGL(k_ln_bwd<CPX_DT_F32>, grid, block, 0, s, y, gamma, dout, rows, (double)eps, dy, part);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_ln_bwd<DT>, grid, block, 0, s, y, gamma, dout, rows, (double)eps, dy, part));
     CPX_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_ln_bwd_finish, dim3(1), dim3(2 * NECK_C), 0, s, part, nblk, dgamma, dbeta);
     CPX_CHECK_LAUNCH();

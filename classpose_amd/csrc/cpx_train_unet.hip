@@ -24,20 +24,12 @@
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
-#define UW_SLAB 512                // rows per slab of the weight gradient = longest serial accumulation chain L
 #define UNET_MAX_OPS 64
 
 static inline int up128i(long long x) { return (int)((x + 127) / 128 * 128); }
 static inline int up64i(int x) { return (x + 63) / 64 * 64; }
 static inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 static inline bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-
-template <int DT>
-__device__ __forceinline__ float act_load(const void *f, size_t idx) {
-    if constexpr (DT == CPX_DT_F32) return ((const float *)f)[idx];
-    else if constexpr (DT == CPX_DT_F16) return (float)((const _Float16 *)f)[idx];
-    else return bf16_to_f32(((const unsigned short *)f)[idx]);
-}
 
 // GEMM view of an op: dY [rows][Npad] (kind 2: after space-to-depth), im2col(X) [rows][Kpad], W [Npad][Kpad]
 struct OpDims { int taps, ctot, Npad, Kpad, Kp128, ho, wo; size_t rows, rows_out; };
@@ -102,7 +94,7 @@ __global__ void __launch_bounds__(256) k_uwgrad(UwArgs g) {
             else { yy = y; xx = x; }
             const bool ok = in && kv[j] && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
             const size_t srow = ((size_t)s << (g.lh + g.lw)) + ((size_t)yy << g.lw) + xx;
-            b[j] = ok ? act_load<DT>(src[j], srow * ld[j] + ch[j]) : 0.f;
+            b[j] = ok ? load_f32<DT>(src[j], srow * ld[j] + ch[j]) : 0.f;
         }
         acc0 = MFMA_F32(a, b[0], acc0);
         acc1 = MFMA_F32(a, b[1], acc1);
@@ -158,7 +150,7 @@ __global__ void __launch_bounds__(256) k_wt(const void *__restrict__ w, int Npad
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)Kp128 * Npad) return;
     const int k = (int)(i / Npad), n = (int)(i - (size_t)k * Npad);
-    wt[i] = k < Kpad ? act_load<DT>(w, (size_t)n * Kpad + k) : 0.f;
+    wt[i] = k < Kpad ? load_f32<DT>(w, (size_t)n * Kpad + k) : 0.f;
 }
 
 // gradient of a transposed conv's output [4 rows][ld_g] -> [rows][Npad], column tap * cout + co; zero from 4 cout on
@@ -206,7 +198,7 @@ __global__ void __launch_bounds__(256) k_dx_gather(DxArgs g) {
     }
     float *d = g.gx + row * g.ld_gx + c;
     v = *d + v;
-    if (g.mask && !(act_load<DT>(g.y, row * g.ld_y + c) > 0.f)) v = 0.f;
+    if (g.mask && !(load_f32<DT>(g.y, row * g.ld_y + c) > 0.f)) v = 0.f;
     *d = v;
 }
 
@@ -226,11 +218,10 @@ int cpx_uwgrad_run(int dtype, int kind, const UwArgs &u, int n_valid, int bias_t
     CPX_REQUIRE(n_slabs <= 65535 && kind >= 0 && kind <= 2);
     const int n_done = (n_valid + 31) / 32 * 32;                                  // (<= Npad)
     const dim3 grid(n_done / 32, (u.Kpad / 64 + 3) / 4, n_slabs), block(256);
-#define UW(DT_) do { if (kind == 0) hipLaunchKernelGGL((k_uwgrad<DT_, 0>), grid, block, 0, s, u); \
-                     else if (kind == 1) hipLaunchKernelGGL((k_uwgrad<DT_, 1>), grid, block, 0, s, u); \
-                     else hipLaunchKernelGGL((k_uwgrad<DT_, 2>), grid, block, 0, s, u); } while (0)
-    if (dtype == CPX_DT_BF16) UW(CPX_DT_BF16); else if (dtype == CPX_DT_F16) UW(CPX_DT_F16); else UW(CPX_DT_F32);
-#undef UW
+    CPX_DT_DISPATCH(dtype, DT,
+                    if (kind == 0) hipLaunchKernelGGL((k_uwgrad<DT, 0>), grid, block, 0, s, u);
+                    else if (kind == 1) hipLaunchKernelGGL((k_uwgrad<DT, 1>), grid, block, 0, s, u);
+                    else hipLaunchKernelGGL((k_uwgrad<DT, 2>), grid, block, 0, s, u));
     const size_t nw = (size_t)u.Npad * u.Kpad;
     hipLaunchKernelGGL(k_uwgrad_reduce, dim3((unsigned)((nw + 255) / 256)), block, 0, s, u.part_w, u.part_b, n_slabs, nw, u.Npad, n_done,
                        bias_taps, cout, dW, db);
@@ -240,18 +231,14 @@ int cpx_uwgrad_run(int dtype, int kind, const UwArgs &u, int n_valid, int bias_t
 int cpx_wt_run(int dtype, const void *w, int Npad, int Kpad, int Kp128, float *wt, hipStream_t s) {
     const size_t nt = (size_t)Kp128 * Npad;
     const dim3 grid((unsigned)((nt + 255) / 256)), block(256);
-    if (dtype == CPX_DT_BF16) hipLaunchKernelGGL(k_wt<CPX_DT_BF16>, grid, block, 0, s, w, Npad, Kpad, Kp128, wt);
-    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_wt<CPX_DT_F16>, grid, block, 0, s, w, Npad, Kpad, Kp128, wt);
-    else hipLaunchKernelGGL(k_wt<CPX_DT_F32>, grid, block, 0, s, w, Npad, Kpad, Kp128, wt);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_wt<DT>, grid, block, 0, s, w, Npad, Kpad, Kp128, wt));
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }
 int cpx_dx_gather_run(int dtype, const DxArgs &g, hipStream_t s) {
     const size_t n = g.rows_src * g.C;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (dtype == CPX_DT_BF16) hipLaunchKernelGGL(k_dx_gather<CPX_DT_BF16>, grid, block, 0, s, g);
-    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_dx_gather<CPX_DT_F16>, grid, block, 0, s, g);
-    else hipLaunchKernelGGL(k_dx_gather<CPX_DT_F32>, grid, block, 0, s, g);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_dx_gather<DT>, grid, block, 0, s, g));
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }
@@ -295,7 +282,7 @@ static bool ops_ok(const cpx_conv_op *ops, int n_ops, int nS) {
 
 extern "C" int cpx_unet_wgrad_slab_rows(void) { return UW_SLAB; }
 extern "C" size_t cpx_unet_backward_workspace_bytes(const cpx_conv_op *ops, int n_ops, int nS, int dtype) {
-    if (!ops_ok(ops, n_ops, nS) || dtype < CPX_DT_BF16 || dtype > CPX_DT_F32) return 0;
+    if (!ops_ok(ops, n_ops, nS) || !dtype_ok(dtype)) return 0;
     BwdLayout L;
     bwd_layout(ops, n_ops, nS, L);
     return L.total;
@@ -328,7 +315,7 @@ extern "C" int cpx_unet_grad_layout(const cpx_conv_op *ops, int n_ops, int nS, i
 
 extern "C" int cpx_unet_refresh_operands(const cpx_conv_op *ops, int n_ops, const float *params, int dtype, void *stream) {
     CPX_REQUIRE(ops && n_ops > 0 && n_ops <= UNET_MAX_OPS && params && ((uintptr_t)params & 15) == 0);
-    CPX_REQUIRE(dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32);
+    CPX_REQUIRE(dtype_ok(dtype));
     long long w_off[UNET_MAX_OPS], b_off[UNET_MAX_OPS]; int n_pad[UNET_MAX_OPS], k_pad[UNET_MAX_OPS];
     param_layout(ops, n_ops, w_off, b_off, n_pad, k_pad);
     for (int i = 0; i < n_ops; ++i) {
@@ -415,12 +402,10 @@ extern "C" int cpx_unet_head_backward(const cpx_conv_op *ops, int n_ops, const v
                                       const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dlogits, float *grads,
                                       void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(ops_ok(ops, n_ops, nS) && feat && fwd_workspace && dlogits && grads && workspace);
-    CPX_REQUIRE(dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32);
+    CPX_REQUIRE(dtype_ok(dtype));
     CPX_REQUIRE(ops[n_ops - 1].h == 16 && ops[n_ops - 1].w == 16);                 // the last op writes the 32 x 32 token grid
     CPX_REQUIRE(fwd_workspace_bytes >= cpx_unet_ws_bytes(dtype, ops, n_ops, nS));
     CPX_REQUIRE(workspace_bytes >= cpx_unet_backward_workspace_bytes(ops, n_ops, nS, dtype) && ((uintptr_t)workspace & 255) == 0);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CPX_DT_BF16) return unet_backward<CPX_DT_BF16>(ops, n_ops, feat, nS, (const char *)fwd_workspace, dlogits, grads, (char *)workspace, s);
-    if (dtype == CPX_DT_F16) return unet_backward<CPX_DT_F16>(ops, n_ops, feat, nS, (const char *)fwd_workspace, dlogits, grads, (char *)workspace, s);
-    return unet_backward<CPX_DT_F32>(ops, n_ops, feat, nS, (const char *)fwd_workspace, dlogits, grads, (char *)workspace, s);
+    CPX_DT_DISPATCH(dtype, DT, return unet_backward<DT>(ops, n_ops, feat, nS, (const char *)fwd_workspace, dlogits, grads, (char *)workspace, s));
 }

@@ -109,36 +109,53 @@ def _targets_f32(flow_targets, n: int, dev) -> torch.Tensor:
     return t.to(dev).contiguous()
 
 
-class FlowHead:
-    """The trainable state of the flow head ``out`` = nn.Conv2d(256, 192, 1) (vit_sam.py:181-182; trained by the reference's
-    ``--freeze backbone neck``, run_training.py:92-98), shared by ``HeadTrainer`` and ``train_unet.UNetHeadTrainer``: the float32
-    master ``w`` [192, 256] and ``b`` [192], their AdamW moments, and the refresh of rows 0..191 of the head operands (``head_w`` /
-    ``head_b`` of the trainer's ``engine.NetWeights``), rounded as at load.  The pixel shuffle ``W2`` is fixed and stays as loaded."""
+class LinearHead:
+    """A parameter group -- a set of tensors that trains.  The trainer iterates over its groups; every group has ``keys`` (the
+    state-dict keys it owns, in the reference's layout), ``update(step, lr, **adam)`` (one AdamW step from the gradients the group
+    holds, then ``refresh``), ``refresh()`` (masters -> the operands of the trainer's ``engine.NetWeights``, rounded exactly as at
+    load) and ``state()`` ({key: cpu tensor} in the reference's layout).
 
-    def __init__(self, sd: dict, weights, element_size: int):
-        if tuple(sd["out.weight"].shape) != (192, 256, 1, 1) or tuple(sd["out.bias"].shape) != (192,):
-            raise ValueError("out.weight / out.bias of the checkpoint do not describe a 1x1 flow head over 256 channels")
+    This group is a 1x1 head ``prefix`` = nn.Conv2d(256, n_cols, 1) at rows ``row0 .. row0 + n_cols`` of ``head_w`` / ``head_b``: the
+    float32 masters ``w`` [n_cols, 256] and ``b`` [n_cols] and their AdamW moments.  The class head ``out_class`` sits at row 192, the
+    flow head ``out`` (vit_sam.py:181-182) at row 0; the pixel shuffles ``W3`` / ``W2`` are fixed and stay as loaded."""
+
+    def __init__(self, sd: dict, weights, prefix: str, row0: int, n_cols: int):
+        self.keys = (prefix + ".weight", prefix + ".bias")
+        w, b = (sd[k] for k in self.keys)
+        if tuple(w.shape) != (n_cols, 256, 1, 1) or tuple(b.shape) != (n_cols,):
+            raise ValueError(f"{prefix}.weight / {prefix}.bias of the checkpoint do not describe a 1x1 head of {n_cols} columns over 256 channels")
         dev = weights.device
-        self.weights, self._es = weights, element_size
-        self.w = sd["out.weight"].detach().float().reshape(192, 256).contiguous().to(dev)
-        self.b = sd["out.bias"].detach().float().contiguous().to(dev)
+        self.weights, self.row0 = weights, row0
+        self.w = w.detach().float().reshape(n_cols, 256).contiguous().to(dev)
+        self.b = b.detach().float().contiguous().to(dev)
         self.m_w, self.v_w, self.m_b, self.v_b = (torch.zeros_like(t) for t in (self.w, self.w, self.b, self.b))
+        self.dW = self.db = None
 
-    def update(self, dlogits: torch.Tensor, feat: torch.Tensor, step: int, lr: float, **kw) -> None:
-        """One AdamW step from the seg-loss gradient ``dlogits`` (rows, 192) and the features the head GEMM read."""
-        dW, db = ops.head_wgrad(dlogits, feat)
-        ops.adamw_step(self.w, dW, self.m_w, self.v_w, step, lr, **kw)
-        ops.adamw_step(self.b, db, self.m_b, self.v_b, step, lr, **kw)
+    def backward(self, feat: torch.Tensor, dlogits: torch.Tensor) -> None:
+        """Holds the gradients of the batch: ``dlogits`` (rows, n_cols) of the head's loss and the features the head GEMM read."""
+        self.dW, self.db = ops.head_wgrad(dlogits, feat)
+
+    def update(self, step: int, lr: float, **adam) -> None:
+        ops.adamw_step(self.w, self.dW, self.m_w, self.v_w, step, lr, **adam)
+        ops.adamw_step(self.b, self.db, self.m_b, self.v_b, step, lr, **adam)      # net.parameters(): decay on the bias too
         self.refresh()
 
     def refresh(self) -> None:
         c = self.weights.c
         half = c.dtype != _lib.DT_F32
-        ops.round_weights(self.w, c.head_w, c.dtype, keep_f32=not half)
-        ops.round_weights(self.b, c.head_b, c.dtype, keep_f32=True)
+        ops.round_weights(self.w, c.head_w + self.row0 * 256 * (2 if half else 4), c.dtype, keep_f32=not half)
+        ops.round_weights(self.b, c.head_b + self.row0 * 4, c.dtype, keep_f32=True)
 
     def state(self) -> dict:
-        return {"out.weight": self.w.detach().cpu().reshape(192, 256, 1, 1).clone(), "out.bias": self.b.detach().cpu().clone()}
+        return {self.keys[0]: self.w.detach().cpu().reshape(-1, 256, 1, 1).clone(), self.keys[1]: self.b.detach().cpu().clone()}
+
+
+class FlowHead(LinearHead):
+    """The flow head ``out`` = nn.Conv2d(256, 192, 1) as a group (trained by the reference's ``--freeze backbone neck``,
+    run_training.py:92-98), shared by ``HeadTrainer`` and ``train_unet.UNetHeadTrainer``."""
+
+    def __init__(self, sd: dict, weights, element_size: int | None = None):
+        super().__init__(sd, weights, "out", 0, 192)
 
 
 NECK_KEYS = ("encoder.neck.0.weight", "encoder.neck.1.weight", "encoder.neck.1.bias", "encoder.neck.2.weight", "encoder.neck.3.weight",
@@ -146,11 +163,12 @@ NECK_KEYS = ("encoder.neck.0.weight", "encoder.neck.1.weight", "encoder.neck.1.b
 
 
 class NeckParams:
-    """The trainable state of the neck (vit_sam.py:216-249; trained by the reference's ``--freeze backbone`` and ``--freeze backbone
+    """The neck as a group (vit_sam.py:216-249; trained by the reference's ``--freeze backbone`` and ``--freeze backbone
     segmentation_head``): float32 masters of its six tensors in operand layout, as views of ONE flat buffer in the order of
     ``ops.neck_grad_layout`` -- ``W0`` [256, 1024], ``gamma1``, ``beta1``, ``W2`` [256, 2304] (``neck.2.weight`` permuted (0, 2, 3, 1) as
     ``NetWeights`` does), ``gamma2``, ``beta2`` -- their AdamW moments and the gradient buffer ``cpx_neck_backward`` fills.  Weight
     decay applies to every tensor, the LayerNorm vectors included: the reference hands ``net.parameters()`` to AdamW."""
+    keys = NECK_KEYS
 
     def __init__(self, sd: dict, weights):
         shapes = {"encoder.neck.0.weight": (256, 1024, 1, 1), "encoder.neck.2.weight": (256, 256, 3, 3)}
@@ -173,9 +191,9 @@ class NeckParams:
         shape = ops.NECK_GRAD_SHAPES[i]
         return self.params[self.off[i]:self.off[i] + int(np.prod(shape))].view(shape)
 
-    def update(self, grads: torch.Tensor, step: int, lr: float, **kw) -> None:
+    def update(self, step: int, lr: float, **adam) -> None:
         """One AdamW step of all six tensors from the flat ``grads``, then ``refresh``."""
-        ops.adamw_step(self.params, grads, self.m, self.v, step, lr, **kw)
+        ops.adamw_step(self.params, self.grads, self.m, self.v, step, lr, **adam)
         self.refresh()
 
     def refresh(self) -> None:
@@ -193,13 +211,20 @@ class NeckParams:
                 NECK_KEYS[3]: v[3].view(256, 3, 3, 256).permute(0, 3, 1, 2).contiguous(), NECK_KEYS[4]: v[4], NECK_KEYS[5]: v[5]}
 
 
+def _of_class_group(name: str) -> property:
+    return property(lambda self: getattr(self.groups[0], name))
+
+
 class HeadTrainer:
     """Trains ``out_class`` (nn.Conv2d(256, nclasses * 64, 1)) of a checkpoint; everything else stays as loaded.
 
     The forward numerics are the inference engine's: GEMM operands rounded to the network dtype, a float32 master copy of the head kept
     here and re-rounded into the operands after every update, so a saved head run by ``predict_wsi`` computes the logits it was
     trained on.  ``feature_batch`` is the fixed number of crops per backbone launch (short batches are padded): kernel selection
-    depends on the row count, so a fixed one keeps a crop's features bitwise independent of how the crops are batched."""
+    depends on the row count, so a fixed one keeps a crop's features bitwise independent of how the crops are batched.
+
+    What trains is ``groups``, in order: the class head (``LinearHead``; ``w``, ``b`` and its moments are reachable from the trainer),
+    then ``flow`` (``train_flow_head``) and ``neck`` (``train_neck``), each None when it does not train."""
 
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
@@ -208,39 +233,42 @@ class HeadTrainer:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
-        self.sd, self.nclasses = prepare_state_dict(pretrained_model, nclasses, head_seed)
+        self.sd, self.nclasses = self._prepare(pretrained_model, nclasses, head_seed)
         self.precision = precision
         self.weights = engine.NetWeights.from_state_dict(self.sd, precision, self.device)
         self.dtype = engine.NET_DTYPES[precision]
         self.weight_decay, self.alpha, self.gamma, self.eps = weight_decay, alpha, gamma, eps
         self.betas, self.adam_eps = betas, adam_eps
-        self.w_ce, self.w_tv = 1.0, 1.0                  # LossAggregator(optimise=False): both multipliers exp(-0) = 1
-        ncols = self.nclasses * 64
+        self.w_ce, self.w_tv, self.w_seg = 1.0, 1.0, 1.0  # LossAggregator(optimise=False): every multiplier exp(-0) = 1
         dev = self.device
         self.set_class_weights(class_weights)
-        self.w = self.sd["out_class.weight"].detach().float().reshape(ncols, 256).contiguous().to(dev)      # master copies
-        self.b = self.sd["out_class.bias"].detach().float().contiguous().to(dev)
-        self.m_w, self.v_w, self.m_b, self.v_b = (torch.zeros_like(t) for t in (self.w, self.w, self.b, self.b))
         self.n_steps = 0
         self.feature_batch = int(feature_batch)
-        c = self.weights.c
         self._L = _lib.lib()
-        nS = self.feature_batch
-        self._net_ws = torch.empty(self._L.cpx_net_workspace_bytes(nS, c.dtype), dtype=torch.uint8, device=dev)
+        nS, c = self.feature_batch, self.weights.c
+        self._net_ws = torch.empty(self._net_workspace_bytes(nS), dtype=torch.uint8, device=dev)
         self._head_fb = torch.empty((nS * TOKENS, c.ld_head), dtype=torch.float32, device=dev)
-        self._es = torch.empty(0, dtype=self.dtype).element_size()
         self._buf: dict = {}
-        self._init_flow_head(train_flow_head)
-        # ``train_neck``: the neck trains too (``NeckParams``) -- the reference's ``--freeze backbone segmentation_head``, with
-        # ``train_flow_head`` its ``--freeze backbone``.  ``step`` / ``evaluate`` then start from backbone rows (``backbone_features``)
+        # ``train_flow_head``: the flow head ``out`` trains too (the reference's ``--freeze backbone neck``); ``step`` / ``evaluate``
+        # then take ``flow_targets`` and add the seg loss.  ``train_neck``: so does the neck -- the reference's ``--freeze
+        # backbone segmentation_head``, with ``train_flow_head`` its ``--freeze backbone``; ``step`` / ``evaluate`` then start from
+        # backbone rows (``backbone_features``)
+        self.flow = FlowHead(self.sd, self.weights) if train_flow_head else None
         self.neck = NeckParams(self.sd, self.weights) if train_neck else None
-
-    def _init_flow_head(self, train_flow_head: bool) -> None:
-        """``train_flow_head``: the flow head ``out`` trains too (the reference's ``--freeze backbone neck``); ``step`` / ``evaluate``
-        then take ``flow_targets`` and add the seg loss, multiplier 1 like the other two (LossAggregator(optimise=False))."""
-        self.w_seg = 1.0
-        self.flow = FlowHead(self.sd, self.weights, self._es) if train_flow_head else None
         self.diam_labels = None
+        self.groups = [g for g in (self._class_group(), self.flow, self.neck) if g is not None]
+
+    # what ``train_unet.UNetHeadTrainer`` replaces: the checkpoint's preparation, the class group and the forward workspace
+    def _prepare(self, pretrained_model, nclasses, head_seed) -> tuple[dict, int]:
+        return prepare_state_dict(pretrained_model, nclasses, head_seed)
+
+    def _class_group(self):
+        return LinearHead(self.sd, self.weights, "out_class", 192, self.nclasses * 64)
+
+    def _net_workspace_bytes(self, nS: int) -> int:
+        return self._L.cpx_net_workspace_bytes(nS, self.weights.c.dtype)
+
+    w, b, m_w, v_w, m_b, v_b = (_of_class_group(n) for n in ("w", "b", "m_w", "v_w", "m_b", "v_b"))
 
     def set_diam_labels(self, diameters) -> None:
         """With the flow head training, ``diam_labels`` of the saved checkpoint becomes the mean diameter of the training set
@@ -278,12 +306,12 @@ class HeadTrainer:
             raise ValueError("crops must be uint8 (n, 256, 256, 3) or float32 (n, 3, 256, 256)")
         return ops.patchify_f32(x, self.dtype)
 
-    def features(self, X) -> torch.Tensor:
-        """Neck features (n * 1024, 256) in the network dtype of n crops: the input of the class head."""
+    def _forward_rows(self, X, rows_of, width: int) -> torch.Tensor:
+        """``cpx_net_forward`` on n crops, ``feature_batch`` at a time; keeps ``rows_of(workspace, feature_batch, dtype)`` (n * 1024, width)."""
         patches = self._patches(X)
         n = patches.shape[0] // TOKENS
         FB, c, dev = self.feature_batch, self.weights.c, self.device
-        out = torch.empty((n * TOKENS, 256), dtype=self.dtype, device=dev)
+        out = torch.empty((n * TOKENS, width), dtype=self.dtype, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
         for s in range(0, n, FB):
             k = min(FB, n - s)
@@ -292,37 +320,29 @@ class HeadTrainer:
                 chunk = torch.cat([chunk, torch.zeros(((FB - k) * TOKENS, 192), dtype=self.dtype, device=dev)])
             check(self._L.cpx_net_forward(C.byref(c), ptr(chunk), FB, ptr(self._head_fb), ptr(self._net_ws), self._net_ws.numel(), st),
                   "net_forward")
-            out[s * TOKENS:(s + k) * TOKENS] = ops.neck_features(self._net_ws, FB, self.dtype)[:k * TOKENS]
+            out[s * TOKENS:(s + k) * TOKENS] = rows_of(self._net_ws, FB, self.dtype)[:k * TOKENS]
         return out
+
+    def features(self, X) -> torch.Tensor:
+        """Neck features (n * 1024, 256) in the network dtype of n crops: the input of the class head."""
+        return self._forward_rows(X, ops.neck_features, 256)
 
     def backbone_features(self, X) -> torch.Tensor:
         """The last block's output (n * 1024, 1024) in the network dtype of n crops: the input of the neck, what a trainer built with
         ``train_neck`` caches (2 MB per crop in bf16, against 512 KB of neck features)."""
-        patches = self._patches(X)
-        n = patches.shape[0] // TOKENS
-        FB, c, dev = self.feature_batch, self.weights.c, self.device
-        out = torch.empty((n * TOKENS, 1024), dtype=self.dtype, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        for s in range(0, n, FB):
-            k = min(FB, n - s)
-            chunk = patches[s * TOKENS:(s + k) * TOKENS]
-            if k < FB:
-                chunk = torch.cat([chunk, torch.zeros(((FB - k) * TOKENS, 192), dtype=self.dtype, device=dev)])
-            check(self._L.cpx_net_forward(C.byref(c), ptr(chunk), FB, ptr(self._head_fb), ptr(self._net_ws), self._net_ws.numel(), st),
-                  "net_forward")
-            out[s * TOKENS:(s + k) * TOKENS] = ops.backbone_rows(self._net_ws, FB, self.dtype)[:k * TOKENS]
-        return out
+        return self._forward_rows(X, ops.backbone_rows, 1024)
 
-    def _as_backbone(self, X) -> torch.Tensor:
-        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == 1024 and X.dtype == self.dtype and X.is_cuda:
+    def _as_rows(self, X, width: int, what: str) -> torch.Tensor:
+        """``X`` itself when it is cached rows of that width, else its crops through the backbone."""
+        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == width and X.dtype == self.dtype and X.is_cuda:
             if X.shape[0] % TOKENS:
-                raise ValueError("backbone rows: 1024 rows per crop")
+                raise ValueError(f"{what}: 1024 rows per crop")
             return X.contiguous()
-        return self.backbone_features(X)
+        return self.features(X) if width == 256 else self.backbone_features(X)
 
     def _neck_forward(self, X):
         """The training tail on the backbone rows of ``X`` (or on ``X`` itself when it is such rows): (x, ``ops.NeckForwardOut``)."""
-        x = self._as_backbone(X)
+        x = self._as_rows(X, 1024, "backbone rows")
         rows, c = x.shape[0], self.weights.c
         key = ("neck_fwd", rows)
         if key not in self._buf:
@@ -347,13 +367,6 @@ class HeadTrainer:
         dhead[:, 192:192 + ncols].copy_(o.dlogits)
         return ops.neck_backward(self.weights, x, fwd, dhead, self.neck.grads, ws)
 
-    def _as_features(self, X) -> torch.Tensor:
-        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == 256 and X.dtype == self.dtype and X.is_cuda:
-            if X.shape[0] % TOKENS:
-                raise ValueError("features: 1024 rows per crop")
-            return X.contiguous()
-        return self.features(X)
-
     def head(self, feat: torch.Tensor) -> torch.Tensor:
         """The head launch of ``cpx_net_forward`` on ``feat``: float32 (rows, ld_head), flow columns 0..191, class columns from 192."""
         c = self.weights.c
@@ -373,7 +386,7 @@ class HeadTrainer:
             self._fwd = (x, fwd)
             feat = fwd.feat
         else:
-            feat = self._as_features(X)
+            feat = self._as_rows(X, 256, "features")
         lab = _labels_i16(labels, self.device)
         if lab.shape[0] * TOKENS != feat.shape[0]:
             raise ValueError(f"{feat.shape[0] // TOKENS} crops but {lab.shape[0]} label maps")
@@ -405,9 +418,6 @@ class HeadTrainer:
         return {"ce": ce, "tversky": tv, "seg": fl + cp, "seg_flow": fl, "seg_cp": cp,
                 "loss": self.w_seg * (fl + cp) + self.w_ce * ce + self.w_tv * tv, "n": n}
 
-    def _flow_kw(self) -> dict:
-        return dict(betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay)
-
     # -- public ------------------------------------------------------------------------------------------------
     def evaluate(self, X, labels, flow_targets=None, return_head: bool = False) -> dict:
         """Losses of a batch without an update.  ``return_head`` adds the float32 head buffer (a view that the next call overwrites).
@@ -423,56 +433,42 @@ class HeadTrainer:
     def step(self, X, labels, lr: float, flow_targets=None) -> dict:
         """One optimisation step on a batch of crops (or of cached ``features``) at learning rate ``lr``; returns the losses of the
         batch BEFORE the update, like the reference's loop.  With ``flow_targets`` (see ``evaluate``) the flow head takes the same
-        step from the seg loss: same step counter, betas and weight decay."""
+        step from the seg loss: same step counter, betas and weight decay; without them it does not move."""
         feat, head, o = self._loss(X, labels)             # raises before anything is updated
         seg = self._seg_loss(head, flow_targets)          # (so does this)
-        if self.neck is not None:                         # reads the head operand of THIS forward: before any refresh
-            self._neck_backward(*self._fwd, o, seg)
-        dW, db = ops.head_wgrad(o.dlogits, feat)
-        self.n_steps += 1
-        kw = dict(betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay)     # net.parameters(): decay on the bias too
-        ops.adamw_step(self.w, dW, self.m_w, self.v_w, self.n_steps, lr, **kw)
-        ops.adamw_step(self.b, db, self.m_b, self.v_b, self.n_steps, lr, **kw)
-        self._refresh_operands()
-        if seg is not None:
-            self.flow.update(seg.dlogits, feat, self.n_steps, lr, **kw)
+        # every gradient from the operands of THIS forward (the neck's backward reads ``head_w``): before any refresh
         if self.neck is not None:
-            self.neck.update(self.neck.grads, self.n_steps, lr, **kw)
+            self._neck_backward(*self._fwd, o, seg)
+        self.groups[0].backward(feat, o.dlogits)
+        if seg is not None:
+            self.flow.backward(feat, seg.dlogits)
+        self.n_steps += 1
+        kw = dict(betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay)     # net.parameters(): decay on every tensor
+        for g in self.groups:
+            if g is not self.flow or seg is not None:
+                g.update(self.n_steps, lr, **kw)
         return self._result(o, feat.shape[0] // TOKENS, seg)
 
-    def _refresh_operands(self) -> None:
-        """Master weights -> the head operands of ``self.weights`` in place (rows 192... of head_w and head_b), rounded as at load."""
-        c = self.weights.c
-        half = c.dtype != _lib.DT_F32
-        ops.round_weights(self.w, c.head_w + 192 * 256 * self._es, c.dtype, keep_f32=not half)
-        ops.round_weights(self.b, c.head_b + 192 * 4, c.dtype, keep_f32=True)
-
     def state_dict(self) -> dict:
-        """The checkpoint in the reference's key layout (vit_sam.py:269-285): ``out_class.weight`` [ncls * 64, 256, 1, 1],
-        ``out_class.bias``, ``W3``; every other entry as loaded."""
+        """The checkpoint in the reference's key layout (vit_sam.py:269-285): every group's ``keys`` from its master copies
+        (``out_class.weight`` [ncls * 64, 256, 1, 1], ``out_class.bias``; ``out.*`` and ``encoder.neck.*`` when they train), every
+        other entry -- ``W3``, ``W2`` -- as loaded."""
         sd = dict(self.sd)
-        sd["out_class.weight"] = self.w.detach().cpu().reshape(self.nclasses * 64, 256, 1, 1).clone()
-        sd["out_class.bias"] = self.b.detach().cpu().clone()
+        for g in self.groups:
+            sd.update(g.state())
         return self._flow_state(sd)
 
     def _flow_state(self, sd: dict) -> dict:
-        """With the flow head training: ``out.weight`` [192, 256, 1, 1] and ``out.bias`` from the master copies (``W2`` as loaded),
-        and ``diam_labels`` when ``set_diam_labels`` was given the training diameters."""
-        if self.flow is not None:
-            sd.update(self.flow.state())
-            if self.diam_labels is not None and "diam_labels" in sd:
-                sd["diam_labels"] = torch.full_like(sd["diam_labels"], self.diam_labels)
-        if self.neck is not None:                         # ``encoder.neck.*`` from the master copies
-            sd.update(self.neck.state())
+        """With the flow head training, ``diam_labels`` when ``set_diam_labels`` was given the training diameters."""
+        if self.flow is not None and self.diam_labels is not None and "diam_labels" in sd:
+            sd["diam_labels"] = torch.full_like(sd["diam_labels"], self.diam_labels)
         return sd
 
     def save(self, path, save_only_trainable_params: bool = False) -> None:
         sd = self.state_dict()
         if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
-            sd = {k: sd[k] for k in ("out_class.weight", "out_class.bias") + (("out.weight", "out.bias") if self.flow is not None else ())
-                  + (NECK_KEYS if self.neck is not None else ())}
+            sd = {k: sd[k] for g in self.groups for k in g.keys}
         torch.save(sd, os.fspath(path))
-
 
 def make_trainer(pretrained_model, nclasses: int | None = None, feature_transformation_structure=None, **kw):
     """The trainer of a checkpoint's class head: ``train_unet.UNetHeadTrainer`` when the state dict has
@@ -511,29 +507,81 @@ def _is_u8_crops(images) -> bool:
     return (dt == np.uint8 or dt == torch.uint8) and images.ndim == 4 and images.shape[3] == 3
 
 
-def _pool_annotated(pool, what: str) -> None:
+# what differs between the two sets ``train_class_head`` resolves: (name in messages, name of the instances argument, the two refusals of a pool)
+_TRAINING = ("training", "instances", "an ImagePool carries its own class maps: pass labels=None",
+             "train_flow_head: an ImagePool carries its own instances (build it with instances=..., pass instances=None)")
+_VALIDATION = ("validation", "test_instances", "a validation ImagePool carries its own class maps: pass test_labels=None",
+               "train_flow_head: a validation ImagePool carries its own instances (build it with instances=...)")
+
+
+def _check_pool(pool, labels, instances, flow: bool, names) -> None:
+    what, _inst, own_labels, own_instances = names
+    if flow and (pool.pool_tgt is None or instances is not None):
+        raise ValueError(own_instances)
+    if labels is not None:
+        raise ValueError(own_labels)
     empty = np.flatnonzero(~pool.annotated)
     if len(empty):
         raise ValueError(f"{what} image {int(empty[0])} has no annotated pixel (every label is -100): drop it")
 
 
-def _pool_training_set(pool, labels, transform, augment, train_probs, diameters):
-    """What ``train_class_head`` trains on when it is handed an ``ImagePool``: with ``augment`` the pool itself, else its cached grid
-    crops as device arrays.  Returns ``(images, labels, pool or None, train_probs, diameters)``."""
-    if labels is not None:
-        raise ValueError("an ImagePool carries its own class maps: pass labels=None")
-    if transform is not None:
-        raise ValueError("transform is a host callback on crops: an ImagePool has none to hand it")
-    _pool_annotated(pool, "training")
-    if augment is not None:
-        return None, None, pool, train_probs, pool.diameters if diameters is None else diameters
-    x, y, win = _augment.grid_crops(pool)
+def _resolve_dataset(images, labels, instances, trainer, flow: bool, names):
+    """A set of fixed 256 x 256 crops from arrays or from an ``ImagePool`` (its cached ``augment.grid_crops``): ``(crops, class maps,
+    flow-head targets float32 (N, 3, 256, 256) on the device or None, the pool's window table or None)``.  The targets (``flow``) come
+    from ``instances`` or from the pool itself."""
+    if isinstance(images, _augment.ImagePool):
+        _check_pool(images, labels, instances, flow, names)
+        x, y, win = _augment.grid_crops(images)
+        return x, y, _augment.grid_flow_targets(images) if flow else None, win
+    images, labels = _check_dataset(images, labels, names[0])
+    return images, labels, _crop_targets(instances, len(images), trainer.device, names[1]) if flow else None, None
+
+
+def _probs(train_probs, n: int) -> np.ndarray:
+    train_probs = np.asarray(train_probs, dtype=np.float64)
+    if train_probs.ndim != 1 or train_probs.shape[0] != n:
+        raise ValueError("train_probs must have the same length as the dataset")
+    return train_probs
+
+
+def _normalised_probs(train_probs, n: int) -> np.ndarray:
+    train_probs = _probs(train_probs, n)
+    if np.any(train_probs < 0):
+        raise ValueError("train_probs must be non-negative")
+    if not float(train_probs.sum()) > 0.0:
+        raise ValueError("train_probs must sum to a positive value")
+    return train_probs / train_probs.sum()
+
+
+def _rescale_factors(augment, diameters, n: int, diam_mean: float) -> np.ndarray:
+    if augment is None:
+        raise ValueError("rescale=True divides the random scale of the augmentation: it needs augment")
+    if diameters is None:
+        raise ValueError("rescale=True needs the diameters of the training images")
+    diameters = np.asarray(diameters, dtype=np.float64)
+    if diameters.shape != (n,) or not np.all(diameters > 0) or not diam_mean > 0:
+        raise ValueError("diameters: one positive diameter per training image, and a positive diam_mean")
+    return diameters / float(diam_mean)
+
+
+def _epoch_order(rng, nimg: int, nimg_per_epoch: int, train_probs) -> np.ndarray:
     if train_probs is not None:
-        train_probs = np.asarray(train_probs, dtype=np.float64)
-        if train_probs.shape != (len(pool),):
-            raise ValueError("train_probs must have the same length as the dataset")
-        train_probs = train_probs[win[:, 0]]
-    return x, y, None, train_probs, None
+        return rng.choice(nimg, nimg_per_epoch, p=train_probs)
+    return rng.permutation(nimg)[:nimg_per_epoch] if nimg_per_epoch <= nimg else rng.choice(nimg, nimg_per_epoch)
+
+
+def _validate(trainer, X, labels, tgts, batch_size: int, cached: bool) -> tuple[float, float]:
+    """Sample-weighted mean (loss, seg loss) of the validation set, in order; ``X`` cached rows (N, 1024, width) or crops."""
+    tsum, tseg, tcount = 0.0, 0.0, 0
+    for s in range(0, len(X), batch_size):
+        x, y = X[s:s + batch_size], labels[s:s + batch_size]
+        if cached:
+            x = x.reshape(-1, X.shape[2])
+        r = trainer.evaluate(x, y) if tgts is None else trainer.evaluate(x, y, flow_targets=tgts[s:s + batch_size])
+        tsum += r["loss"] * r["n"]
+        tseg += r.get("seg", 0.0) * r["n"]
+        tcount += r["n"]
+    return tsum / tcount, tseg / tcount
 
 
 def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, test_labels=None, batch_size: int = 8,
@@ -572,8 +620,6 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     an augmented batch warps them with the crop, everything else uses plain windows of the stored planes.  ``transform`` is refused
     (a host callback cannot move the targets).  ``diameters``, when given, also set the checkpoint's ``diam_labels``.
     Returns ``(path of the final model, train_losses, test_losses)``."""
-    pool = None
-    tgts = test_tgts = None                               # flow-head targets of pre-cut / grid crops, float32 (N, 3, 256, 256) on the device
     if train_flow_head:
         if trainer.flow is None:
             raise ValueError("train_flow_head=True needs a trainer built with train_flow_head=True")
@@ -581,54 +627,30 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
             raise ValueError("train_flow_head: transform is a host callback on crops and cannot move the flow targets")
     elif instances is not None or test_instances is not None:
         raise ValueError("instances / test_instances are the flow head's targets: they need train_flow_head=True")
-    if isinstance(images, _augment.ImagePool):
-        src_pool = images
-        if train_flow_head and (src_pool.pool_tgt is None or instances is not None):
-            raise ValueError("train_flow_head: an ImagePool carries its own instances (build it with instances=..., pass instances=None)")
-        images, labels, pool, train_probs, diameters = _pool_training_set(images, labels, transform, augment, train_probs, diameters)
-        if train_flow_head and pool is None:
-            tgts = _augment.grid_flow_targets(src_pool)
+    pool = tgts = test_tgts = None                        # flow-head targets of pre-cut / grid crops, float32 (N, 3, 256, 256) on the device
+    if isinstance(images, _augment.ImagePool) and transform is not None:
+        raise ValueError("transform is a host callback on crops: an ImagePool has none to hand it")
+    if isinstance(images, _augment.ImagePool) and augment is not None:       # the pool itself is the training set: every draw a fresh window
+        pool, images = images, None
+        _check_pool(pool, labels, instances, train_flow_head, _TRAINING)
+        diameters = pool.diameters if diameters is None else diameters
     else:
-        images, labels = _check_dataset(images, labels, "training")
-        if train_flow_head:
-            tgts = _crop_targets(instances, len(images), trainer.device, "instances")
+        src = images
+        images, labels, tgts, win = _resolve_dataset(images, labels, instances, trainer, train_flow_head, _TRAINING)
+        if win is not None:                               # a pool's grid crops: an image's ``train_probs`` go to each of its windows
+            diameters = None
+            if train_probs is not None:
+                train_probs = _probs(train_probs, len(src))[win[:, 0]]
     has_test = test_images is not None
-    if has_test and isinstance(test_images, _augment.ImagePool):
-        if test_labels is not None:
-            raise ValueError("a validation ImagePool carries its own class maps: pass test_labels=None")
-        _pool_annotated(test_images, "validation")
-        if train_flow_head:
-            if test_images.pool_tgt is None or test_instances is not None:
-                raise ValueError("train_flow_head: a validation ImagePool carries its own instances (build it with instances=...)")
-            test_tgts = _augment.grid_flow_targets(test_images)
-        test_images, test_labels, _win = _augment.grid_crops(test_images)
-    elif has_test:
-        test_images, test_labels = _check_dataset(test_images, test_labels, "validation")
-        if train_flow_head:
-            test_tgts = _crop_targets(test_instances, len(test_images), trainer.device, "test_instances")
+    if has_test:
+        test_images, test_labels, test_tgts, _win = _resolve_dataset(test_images, test_labels, test_instances, trainer, train_flow_head, _VALIDATION)
     if train_flow_head:
         trainer.set_diam_labels(diameters)
     nimg = len(pool) if pool is not None else len(images)
     nimg_per_epoch = nimg if nimg_per_epoch is None else int(nimg_per_epoch)
     if train_probs is not None:
-        train_probs = np.asarray(train_probs, dtype=np.float64)
-        if train_probs.ndim != 1 or train_probs.shape[0] != nimg:
-            raise ValueError("train_probs must have the same length as the dataset")
-        if np.any(train_probs < 0):
-            raise ValueError("train_probs must be non-negative")
-        if not float(train_probs.sum()) > 0.0:
-            raise ValueError("train_probs must sum to a positive value")
-        train_probs = train_probs / train_probs.sum()
-    rsc = None
-    if rescale:
-        if augment is None:
-            raise ValueError("rescale=True divides the random scale of the augmentation: it needs augment")
-        if diameters is None:
-            raise ValueError("rescale=True needs the diameters of the training images")
-        diameters = np.asarray(diameters, dtype=np.float64)
-        if diameters.shape != (nimg,) or not np.all(diameters > 0) or not diam_mean > 0:
-            raise ValueError("diameters: one positive diameter per training image, and a positive diam_mean")
-        rsc = diameters / float(diam_mean)
+        train_probs = _normalised_probs(train_probs, nimg)
+    rsc = _rescale_factors(augment, diameters, nimg, diam_mean) if rescale else None
     LR = lr_schedule(learning_rate, n_epochs)
     model_name = "classpose_head" if model_name is None else model_name
     model_dir = (Path.cwd() if save_path is None else Path(save_path)) / model_name
@@ -642,9 +664,9 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     bases = None
     if pool is None and transform is None and _augment._has_he(_augment.get_config(augment)) and _is_u8_crops(images):
         bases = _augment.stain_bases_of(images, trainer.device)
-    test_cached = cached or (cache_features and augment is not None)
+    test_cached = cache_features and has_test and (cached or augment is not None)
     dev = trainer.device
-    lab_dev = test_lab_dev = feats = test_feats = None
+    lab_dev = feats = None
     # a trainer that trains the neck starts from the backbone's output instead of the neck's
     neck = getattr(trainer, "neck", None) is not None
     cache, width = (trainer.backbone_features, 1024) if neck else (trainer.features, 256)
@@ -653,62 +675,48 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
         feats = cache(images).view(nimg, TOKENS, width)
         lab_dev = _labels_i16(labels, dev)
     if test_cached:
-        if has_test:
-            test_feats = cache(test_images).view(len(test_images), TOKENS, width)
-            test_lab_dev = _labels_i16(test_labels, dev)
+        test_images, test_labels = cache(test_images).view(len(test_images), TOKENS, width), _labels_i16(test_labels, dev)
     train_logger.info(">>> n_epochs=%d, n_train=%d, n_test=%s, AdamW, learning_rate=%0.5f, weight_decay=%0.5f, cached features: %s",
                       n_epochs, nimg, len(test_images) if has_test else None, learning_rate, trainer.weight_decay, cached)
+    aug_kw = dict(config=augment, scale_range=scale_range, label_fill=label_fill, dtype=trainer.dtype, out=CROP)
+
+    def batch(idx, rng):
+        """(crops or cached rows, class maps, flow targets or None) of the images ``idx``; draws from ``rng``: transform, then augment."""
+        rs = None if rsc is None else rsc[idx]
+        if cached:
+            ti = torch.from_numpy(idx).to(dev)
+            return feats[ti].reshape(-1, width), lab_dev[ti], None if tgts is None else tgts[ti.to(tgts.device)]
+        if pool is not None:
+            res = _augment.augment_batch_pool(pool, idx, rng, rescale=rs, flow_targets=train_flow_head, **aug_kw)
+            return res if train_flow_head else (*res, None)
+        x, y, t = images[idx], labels[idx], None if tgts is None else tgts[torch.from_numpy(idx).to(tgts.device)]
+        if transform is not None:
+            x, y = transform(x, y, rng)
+        if augment is not None:
+            res = _augment.augment_batch(x, y, rng, device=dev, rescale=rs, stain_bases=None if bases is None else bases.take(idx),
+                                         flow_targets=t, **aug_kw)
+            x, y, t = res if t is not None else (*res, None)
+        return x, y, t
+
     train_losses, test_losses = np.zeros(n_epochs), np.zeros(n_epochs)
     best = np.inf
     for iepoch in range(n_epochs):
         rng = np.random.default_rng([random_seed, iepoch])
-        if train_probs is not None:
-            order = rng.choice(nimg, nimg_per_epoch, p=train_probs)
-        else:
-            order = rng.permutation(nimg)[:nimg_per_epoch] if nimg_per_epoch <= nimg else rng.choice(nimg, nimg_per_epoch)
+        order = _epoch_order(rng, nimg, nimg_per_epoch, train_probs)
+        lr = float(LR[iepoch])
         sums, count = np.zeros(4), 0
         for s in range(0, len(order), batch_size):
             idx = order[s:s + batch_size]
-            t = None
-            if tgts is not None:
-                t = tgts[torch.from_numpy(idx).to(tgts.device)]
-            if cached:
-                ti = torch.from_numpy(idx).to(dev)
-                x, y = feats[ti].reshape(-1, width), lab_dev[ti]
-            elif pool is not None:
-                res = _augment.augment_batch_pool(pool, idx, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
-                                                  dtype=trainer.dtype, out=CROP, rescale=None if rsc is None else rsc[idx],
-                                                  flow_targets=train_flow_head)
-                x, y, t = res if train_flow_head else (*res, None)
-            else:
-                x, y = images[idx], labels[idx]
-                if transform is not None:
-                    x, y = transform(x, y, rng)
-                if augment is not None:
-                    res = _augment.augment_batch(x, y, rng, config=augment, scale_range=scale_range, label_fill=label_fill,
-                                                 dtype=trainer.dtype, device=dev, out=CROP,
-                                                 rescale=None if rsc is None else rsc[idx],
-                                                 stain_bases=None if bases is None else bases.take(idx), flow_targets=t)
-                    x, y, t = res if t is not None else (*res, None)
-            r = trainer.step(x, y, float(LR[iepoch])) if t is None else trainer.step(x, y, float(LR[iepoch]), flow_targets=t)
+            x, y, t = batch(idx, rng)
+            r = trainer.step(x, y, lr) if t is None else trainer.step(x, y, lr, flow_targets=t)
             sums += np.array([r["ce"], r["tversky"], r["loss"], r.get("seg", 0.0)]) * len(idx)
             count += len(idx)
         train_losses[iepoch] = sums[2] / count
         seg_msg = f"seg={sums[3] / count:.4f}, " if train_flow_head else ""
         msg = f"{iepoch}, train_loss={sums[2] / count:.4f} ({seg_msg}ce={sums[0] / count:.4f}, tversky={sums[1] / count:.4f}), LR={LR[iepoch]:.6f}"
         if has_test:
-            tsum, tseg, tcount = 0.0, 0.0, 0
-            for s in range(0, len(test_images), batch_size):
-                if test_cached:
-                    x, y = test_feats[s:s + batch_size].reshape(-1, width), test_lab_dev[s:s + batch_size]
-                else:
-                    x, y = test_images[s:s + batch_size], test_labels[s:s + batch_size]
-                r = trainer.evaluate(x, y) if test_tgts is None else trainer.evaluate(x, y, flow_targets=test_tgts[s:s + batch_size])
-                tsum += r["loss"] * r["n"]
-                tseg += r.get("seg", 0.0) * r["n"]
-                tcount += r["n"]
-            test_losses[iepoch] = tsum / tcount
-            msg += f", test_loss={test_losses[iepoch]:.4f}" + (f" (seg={tseg / tcount:.4f})" if train_flow_head else "")
+            test_losses[iepoch], tseg = _validate(trainer, test_images, test_labels, test_tgts, batch_size, test_cached)
+            msg += f", test_loss={test_losses[iepoch]:.4f}" + (f" (seg={tseg:.4f})" if train_flow_head else "")
         train_logger.info(msg)
         trainer.save(model_dir / "checkpoint_last.pt")
         score = test_losses[iepoch] if has_test else train_losses[iepoch]

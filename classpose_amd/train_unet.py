@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, engine, ops
 from ._lib import check, ptr
-from .train import TOKENS, HeadTrainer
+from .train import TOKENS, HeadTrainer, _of_class_group
 
 MAX_LEVELS = 4          # 32 x 32 tokens halve once per level and once more in the bottleneck (engine.NetWeights.from_state_dict)
 
@@ -199,9 +199,64 @@ def prepare_unet_state_dict(pretrained_model, nclasses: int | None = None, head_
     return sd, ncls, fts
 
 
+class UNetParams:
+    """The UNet head as a parameter group (see ``train.LinearHead``): the flat float32 master ``params`` of ``param_layout`` --
+    checked against the library's -- with ``grads`` and the AdamW moments ``m``, ``v`` beside it, the head's forward (whose
+    workspace holds the saved activations) and backward, and the reference's key layout in ``keys`` / ``state()``."""
+
+    def __init__(self, sd: dict, weights, fts, out_ch: int):
+        self.weights, self.fts, self.out_ch = weights, fts, out_ch
+        self.keys = tuple(k + s for k, *_ in unet_plan(fts, out_ch) for s in (".weight", ".bias"))
+        c, self._L = weights.c, _lib.lib()
+        n = c.n_unet_ops
+        total, self.layout = param_layout(fts, out_ch)
+        w_off, b_off, n_pad, k_pad = (C.c_longlong * n)(), (C.c_longlong * n)(), (C.c_int * n)(), (C.c_int * n)()
+        if self._L.cpx_unet_param_layout(c.unet_ops, n, w_off, b_off, n_pad, k_pad) != total or \
+                [tuple(t) for t in zip(w_off, b_off, n_pad, k_pad)] != self.layout:
+            raise _lib.CpxError("UNetHeadTrainer: the host's parameter layout differs from the library's")
+        self.params = pack_params(sd, fts, out_ch).to(weights.device)         # float32 master copy
+        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
+        self._ws: dict = {}
+
+    def _workspace(self, size_fn: str, nS: int) -> torch.Tensor:
+        """The workspace of ``nS`` crops that the library's ``size_fn`` sizes, allocated once."""
+        if (size_fn, nS) not in self._ws:
+            c = self.weights.c
+            nbytes = getattr(self._L, size_fn)(c.unet_ops, c.n_unet_ops, nS, c.dtype)
+            self._ws[size_fn, nS] = torch.empty(nbytes, dtype=torch.uint8, device=self.params.device)
+        return self._ws[size_fn, nS]
+
+    def forward(self, feat: torch.Tensor, out: torch.Tensor) -> None:
+        """``cpx_unet_head_forward``: the class columns (from 192) of the head buffer ``out``."""
+        c, nS = self.weights.c, feat.shape[0] // TOKENS
+        ws = self._workspace("cpx_unet_workspace_bytes", nS)
+        check(self._L.cpx_unet_head_forward(c.unet_ops, c.n_unet_ops, ptr(feat), nS, ptr(out), c.ld_head, 192, c.dtype, ptr(ws),
+                                            ws.numel(), torch.cuda.current_stream(feat.device).cuda_stream), "unet_head_forward")
+
+    def backward(self, feat: torch.Tensor, dlogits: torch.Tensor) -> torch.Tensor:
+        """``grads`` of the batch whose ``forward(feat, ...)`` ran last; ``dlogits`` from ``cpx_class_loss``."""
+        nS = feat.shape[0] // TOKENS
+        return ops.unet_head_backward(self.weights, feat, self._workspace("cpx_unet_workspace_bytes", nS), dlogits, self.grads,
+                                      self._workspace("cpx_unet_backward_workspace_bytes", nS))
+
+    def update(self, step: int, lr: float, **adam) -> None:
+        ops.adamw_step(self.params, self.grads, self.m, self.v, step, lr, **adam)      # net.parameters(): decay on the biases too
+        self.refresh()
+
+    def refresh(self) -> None:
+        """Master parameters -> the operands the op list points at, rounded as at load."""
+        c = self.weights.c
+        check(self._L.cpx_unet_refresh_operands(c.unet_ops, c.n_unet_ops, ptr(self.params), c.dtype,
+                                                torch.cuda.current_stream(self.params.device).cuda_stream), "unet_refresh_operands")
+
+    def state(self) -> dict:
+        return unpack_params(self.params, self.fts, self.out_ch)
+
+
 class UNetHeadTrainer(HeadTrainer):
     """Trains ``out_class`` = ``classpose.unet.UNet(256, nclasses * 64, fts)`` of a checkpoint; everything else stays as loaded.
-    The public surface is ``HeadTrainer``'s, and ``train.train_class_head`` runs with either."""
+    The public surface is ``HeadTrainer``'s, and ``train.train_class_head`` runs with either; the class group is ``UNetParams``
+    (``params``, ``grads``, ``m``, ``v`` and ``layout`` are reachable from the trainer)."""
 
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
@@ -210,99 +265,33 @@ class UNetHeadTrainer(HeadTrainer):
         if train_neck:
             raise NotImplementedError("train_neck: the UNet head's backward gives the neck output no gradient; the neck trains "
                                       "under the 1x1 class head only")
-        self.neck = None
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
-        self.sd, self.nclasses, self.fts = prepare_unet_state_dict(pretrained_model, nclasses, head_seed, feature_transformation_structure)
-        self.precision = precision
-        self.weights = engine.NetWeights.from_state_dict(self.sd, precision, self.device)
-        self.dtype = engine.NET_DTYPES[precision]
-        self.weight_decay, self.alpha, self.gamma, self.eps = weight_decay, alpha, gamma, eps
-        self.betas, self.adam_eps = betas, adam_eps
-        self.w_ce, self.w_tv = 1.0, 1.0                  # LossAggregator(optimise=False): both multipliers exp(-0) = 1
-        dev = self.device
-        self.set_class_weights(class_weights)
+        self._structure = feature_transformation_structure
+        super().__init__(pretrained_model, nclasses, device, precision, class_weights, weight_decay, alpha, gamma, eps, feature_batch,
+                         head_seed, betas, adam_eps, train_flow_head=train_flow_head)
+
+    def _prepare(self, pretrained_model, nclasses, head_seed) -> tuple[dict, int]:
+        sd, ncls, self.fts = prepare_unet_state_dict(pretrained_model, nclasses, head_seed, self._structure)
+        return sd, ncls
+
+    def _class_group(self) -> UNetParams:
+        return UNetParams(self.sd, self.weights, self.fts, self.nclasses * 64)
+
+    def _net_workspace_bytes(self, nS: int) -> int:
         c = self.weights.c
-        self._L = L = _lib.lib()
-        n = c.n_unet_ops
-        total, self.layout = param_layout(self.fts, self.nclasses * 64)
-        w_off, b_off, n_pad, k_pad = (C.c_longlong * n)(), (C.c_longlong * n)(), (C.c_int * n)(), (C.c_int * n)()
-        if L.cpx_unet_param_layout(c.unet_ops, n, w_off, b_off, n_pad, k_pad) != total or \
-                [tuple(t) for t in zip(w_off, b_off, n_pad, k_pad)] != self.layout:
-            raise _lib.CpxError("UNetHeadTrainer: the host's parameter layout differs from the library's")
-        self.params = pack_params(self.sd, self.fts, self.nclasses * 64).to(dev)         # float32 master copy
-        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
-        self.n_steps = 0
-        self.feature_batch = int(feature_batch)
-        nS = self.feature_batch
-        nbytes = L.cpx_net_workspace_bytes(nS, c.dtype) + L.cpx_unet_workspace_bytes(c.unet_ops, n, nS, c.dtype)
-        self._net_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self._head_fb = torch.empty((nS * TOKENS, c.ld_head), dtype=torch.float32, device=dev)
-        self._es = torch.empty(0, dtype=self.dtype).element_size()
-        self._buf: dict = {}
-        self._init_flow_head(train_flow_head)
+        return super()._net_workspace_bytes(nS) + self._L.cpx_unet_workspace_bytes(c.unet_ops, c.n_unet_ops, nS, c.dtype)
+
+    params, grads, m, v, layout = (_of_class_group(n) for n in ("params", "grads", "m", "v", "layout"))
 
     def head(self, feat: torch.Tensor) -> torch.Tensor:
         """The head launches of ``cpx_net_forward`` on ``feat``: float32 (rows, ld_head), flow columns 0..191 from the head GEMM,
         class columns from 192 written by the UNet, whose workspace then holds the saved activations of this batch."""
         out = super().head(feat)
-        c = self.weights.c
-        nS = feat.shape[0] // TOKENS
-        key = ("uws", nS)
-        if key not in self._buf:
-            self._buf[key] = torch.empty(self._L.cpx_unet_workspace_bytes(c.unet_ops, c.n_unet_ops, nS, c.dtype), dtype=torch.uint8,
-                                         device=self.device)
-        ws = self._buf[key]
-        check(self._L.cpx_unet_head_forward(c.unet_ops, c.n_unet_ops, ptr(feat), nS, ptr(out), c.ld_head, 192, c.dtype, ptr(ws),
-                                            ws.numel(), torch.cuda.current_stream(self.device).cuda_stream), "unet_head_forward")
+        self.groups[0].forward(feat, out)
         return out
 
     def backward(self, feat: torch.Tensor, dlogits: torch.Tensor) -> torch.Tensor:
         """``self.grads`` (flat, float32) of the batch whose forward ``head(feat)`` ran last; ``dlogits`` from ``cpx_class_loss``."""
-        nS = feat.shape[0] // TOKENS
-        ops.unet_head_backward(self.weights, feat, self._buf[("uws", nS)], dlogits, self.grads, self._bwd_ws(nS))
-        return self.grads
-
-    def _bwd_ws(self, nS: int) -> torch.Tensor:
-        key = ("bws", nS)
-        if key not in self._buf:
-            c = self.weights.c
-            self._buf[key] = torch.empty(self._L.cpx_unet_backward_workspace_bytes(c.unet_ops, c.n_unet_ops, nS, c.dtype),
-                                         dtype=torch.uint8, device=self.device)
-        return self._buf[key]
-
-    def step(self, X, labels, lr: float, flow_targets=None) -> dict:
-        """One optimisation step on a batch of crops (or of cached ``features``) at learning rate ``lr``; returns the losses of the
-        batch BEFORE the update, like the reference's loop.  ``flow_targets``: as ``HeadTrainer.step``."""
-        feat, head, o = self._loss(X, labels)             # raises before anything is updated
-        seg = self._seg_loss(head, flow_targets)          # (so does this)
-        self.backward(feat, o.dlogits)
-        self.n_steps += 1
-        ops.adamw_step(self.params, self.grads, self.m, self.v, self.n_steps, lr, betas=self.betas, eps=self.adam_eps,
-                       weight_decay=self.weight_decay)    # net.parameters(): decay on the biases too
-        self._refresh_operands()
-        if seg is not None:
-            self.flow.update(seg.dlogits, feat, self.n_steps, lr, **self._flow_kw())
-        return self._result(o, feat.shape[0] // TOKENS, seg)
-
-    def _refresh_operands(self) -> None:
-        """Master parameters -> the operands the op list points at, rounded as at load."""
-        c = self.weights.c
-        check(self._L.cpx_unet_refresh_operands(c.unet_ops, c.n_unet_ops, ptr(self.params), c.dtype,
-                                                torch.cuda.current_stream(self.device).cuda_stream), "unet_refresh_operands")
-
-    def state_dict(self) -> dict:
-        """The checkpoint in the reference's key layout: every ``out_class.*`` entry from the master parameters, the rest as loaded."""
-        sd = dict(self.sd)
-        sd.update(unpack_params(self.params, self.fts, self.nclasses * 64))
-        return self._flow_state(sd)
-
-    def save(self, path, save_only_trainable_params: bool = False) -> None:
-        sd = self.state_dict()
-        if save_only_trainable_params:                    # the reference pops every parameter with requires_grad False
-            sd = {k: v for k, v in sd.items() if k.startswith("out_class.") or (self.flow is not None and k in ("out.weight", "out.bias"))}
-        torch.save(sd, os.fspath(path))
+        return self.groups[0].backward(feat, dlogits)
 
 
 def make_trainer(pretrained_model, nclasses: int | None = None, feature_transformation_structure=None, **kw):
