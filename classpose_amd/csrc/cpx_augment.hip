@@ -23,13 +23,11 @@ __constant__ float c_rgb_from_hed[9] = {0.65f, 0.70f, 0.29f, 0.07f, 0.99f, 0.11f
 __device__ __forceinline__ uint32_t byte_sum(uint32_t u) {
     return (u & 0xffu) + ((u >> 8) & 0xffu) + ((u >> 16) & 0xffu) + (u >> 24);
 }
-// one workgroup per image: the exact integer sum of its bytes, then the reference's cut-off test in double
-__global__ void __launch_bounds__(1024) k_hed_decide(const uint8_t *__restrict__ img, long long count, double lo, double hi,
-                                                     int32_t *__restrict__ applied) {
+// the exact integer sum of p[0 .. count) over a workgroup of 1024 threads; thread 0 returns the total.  Bytes up to the first 16-byte
+// boundary (3 * px_off is odd for many image sizes), then 16 per load, then the tail.
+__device__ __forceinline__ unsigned long long block_byte_sum(const uint8_t *__restrict__ p, long long count) {
     __shared__ unsigned long long part[16];
-    const uint8_t *p = img + (size_t)blockIdx.x * count;
     unsigned long long s = 0;
-    // bytes up to the first 16-byte boundary, then 16 per load, then the tail
     const long long head = min(count, (long long)((16 - ((uintptr_t)p & 15)) & 15));
     const long long nvec = (count - head) / 16;
     const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
@@ -43,13 +41,22 @@ __global__ void __launch_bounds__(1024) k_hed_decide(const uint8_t *__restrict__
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tot = 0;
+    unsigned long long tot = 0;
+    if (threadIdx.x == 0)
         for (int w = 0; w < 16; ++w) tot += part[w];
+    return tot;
+}
+
+// one workgroup per image: the exact integer sum of its bytes, then the reference's cut-off test in double
+__global__ void __launch_bounds__(1024) k_hed_decide(const uint8_t *__restrict__ img, long long count, double lo, double hi,
+                                                     int32_t *__restrict__ applied) {
+    const unsigned long long tot = block_byte_sum(img + (size_t)blockIdx.x * count, count);
+    if (threadIdx.x == 0) {
         const double mean = ((double)tot / (double)count) / 255.0;      // np.mean(patch) / 255.0
         applied[blockIdx.x] = (lo <= mean && mean <= hi) ? 1 : 0;
     }
 }
+
 
 // HEDTransform.transform of one uint8 pixel with the stain draws sigma[3] / bias[3] of its image
 __device__ __forceinline__ void hed_pixel(const uint8_t *__restrict__ px, const float *__restrict__ sigma,
@@ -109,324 +116,6 @@ extern "C" int cpx_hed_jitter_u8(const uint8_t *img, int n, int H, int W, const 
 }
 
 // ---------------------------------------------------------------------------
-// affine warp
-// ---------------------------------------------------------------------------
-// U8: src [n][sh][sw][3] uint8, else [n][3][sh][sw] float32.  A tap outside the source is 0 on its own.
-template <bool U8>
-__device__ __forceinline__ float warp_tap(const void *src, size_t t, int sh, int sw, int c, int y, int x) {
-    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) return 0.f;
-    if (U8) return (float)((const uint8_t *)src)[((t * sh + y) * sw + x) * 3 + c];
-    return ((const float *)src)[((t * 3 + c) * sh + y) * sw + x];
-}
-
-template <bool U8>
-__global__ void k_warp_affine(const void *__restrict__ src, const int16_t *__restrict__ lab, int sh, int sw,
-                              const double *__restrict__ inv, int dh, int dw, int label_fill, float *__restrict__ out,
-                              int16_t *__restrict__ lab_out) {
-    const int p = blockIdx.x * NTHR + threadIdx.x;
-    if (p >= dh * dw) return;
-    const size_t t = blockIdx.y;
-    const int y = p / dw, x = p - y * dw;
-    const double *m = inv + t * 6;
-    const double sx = m[0] * (double)x + m[1] * (double)y + m[2];
-    const double sy = m[3] * (double)x + m[4] * (double)y + m[5];
-    float v[3] = {0.f, 0.f, 0.f};
-    // floor(sx) in [-1, sw - 1] and floor(sy) in [-1, sh - 1], or every tap is outside (NaN lands here too)
-    if (sx >= -1.0 && sx < (double)sw && sy >= -1.0 && sy < (double)sh) {
-        const double fx = floor(sx), fy = floor(sy);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float wx = (float)(sx - fx), wy = (float)(sy - fy);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float a = warp_tap<U8>(src, t, sh, sw, c, y0, x0), b = warp_tap<U8>(src, t, sh, sw, c, y0, x0 + 1);
-            const float d = warp_tap<U8>(src, t, sh, sw, c, y0 + 1, x0), e = warp_tap<U8>(src, t, sh, sw, c, y0 + 1, x0 + 1);
-            const float top = a + (b - a) * wx;
-            const float bot = d + (e - d) * wx;
-            v[c] = top + (bot - top) * wy;
-        }
-    }
-    const size_t plane = (size_t)dh * dw;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
-    if (lab) {
-        int r = label_fill;
-        const double nx = floor(sx + 0.5), ny = floor(sy + 0.5);
-        if (nx >= 0.0 && nx < (double)sw && ny >= 0.0 && ny < (double)sh) r = lab[(t * sh + (int)ny) * sw + (int)nx];
-        lab_out[t * plane + p] = (int16_t)r;
-    }
-}
-
-template <bool U8>
-static int warp_launch(const void *src, const int16_t *labels, int n, int sh, int sw, const double *inv, int dh, int dw,
-                       int label_fill, float *out, int16_t *labels_out, void *stream) {
-    CPX_REQUIRE(src && inv && out && n > 0 && n <= 65535 && sh > 0 && sw > 0 && dh > 0 && dw > 0);
-    CPX_REQUIRE((labels == nullptr) == (labels_out == nullptr));
-    CPX_REQUIRE((long long)sh * sw < (1ll << 29) && (long long)dh * dw < (1ll << 29));
-    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
-    hipLaunchKernelGGL(k_warp_affine<U8>, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, (hipStream_t)stream,
-                       src, labels, sh, sw, inv, dh, dw, label_fill, out, labels_out);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
-}
-
-extern "C" int cpx_warp_affine_u8(const uint8_t *src, const int16_t *labels, int n, int sh, int sw, const double *inv,
-                                  int dh, int dw, int label_fill, float *out, int16_t *labels_out, void *stream) {
-    return warp_launch<true>(src, labels, n, sh, sw, inv, dh, dw, label_fill, out, labels_out, stream);
-}
-extern "C" int cpx_warp_affine_f32(const float *src, const int16_t *labels, int n, int sh, int sw, const double *inv,
-                                   int dh, int dw, int label_fill, float *out, int16_t *labels_out, void *stream) {
-    CPX_REQUIRE((const void *)src != (const void *)out);
-    return warp_launch<false>(src, labels, n, sh, sw, inv, dh, dw, label_fill, out, labels_out, stream);
-}
-
-// ---------------------------------------------------------------------------
-// ragged image pool (t4): whole annotated images of any size, packed back to back
-// ---------------------------------------------------------------------------
-// image i: pool_u8 + 3 * px_off[i], hw[i] = {h, w}; a table entry that does not lie inside the pool's pool_px pixels is never read
-__device__ __forceinline__ bool pool_entry_ok(long long off, int h, int w, long long pool_px) {
-    return off >= 0 && h > 0 && w > 0 && off <= pool_px && (long long)h * w <= pool_px - off;
-}
-
-// one workgroup per image: the exact integer sum of its bytes (what k_hed_decide forms per patch)
-__global__ void __launch_bounds__(1024) k_pool_byte_sums(const uint8_t *__restrict__ pool, const int64_t *__restrict__ px_off,
-                                                         const int32_t *__restrict__ hw, long long pool_px,
-                                                         unsigned long long *__restrict__ sums, int32_t *__restrict__ status) {
-    __shared__ unsigned long long part[16];
-    const int i = blockIdx.x;
-    const long long off = px_off[i];
-    const int h = hw[2 * i], w = hw[2 * i + 1];
-    if (!pool_entry_ok(off, h, w, pool_px)) {                           // uniform over the workgroup
-        if (threadIdx.x == 0) { sums[i] = 0; atomicOr(status, 2); }
-        return;
-    }
-    const uint8_t *p = pool + 3 * off;
-    const long long count = 3ll * h * w;
-    unsigned long long s = 0;
-    // 3 * px_off is odd for many sizes: bytes up to the first 16-byte boundary, then 16 per load, then the tail
-    const long long head = min(count, (long long)((16 - ((uintptr_t)p & 15)) & 15));
-    const long long nvec = (count - head) / 16;
-    const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
-    for (long long k = threadIdx.x; k < head; k += 1024) s += p[k];
-    for (long long k = threadIdx.x; k < nvec; k += 1024) {
-        const uint4 q = v[k];
-        s += byte_sum(q.x) + byte_sum(q.y) + byte_sum(q.z) + byte_sum(q.w);
-    }
-    for (long long k = head + nvec * 16 + threadIdx.x; k < count; k += 1024) s += p[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tot = 0;
-        for (int k = 0; k < 16; ++k) tot += part[k];
-        sums[i] = tot;
-    }
-}
-
-extern "C" int cpx_pool_byte_sums(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
-                                  uint64_t *sums, int32_t *status, void *stream) {
-    CPX_REQUIRE(pool_u8 && px_off && hw && sums && status && nI > 0 && pool_px > 0);
-    hipStream_t s = (hipStream_t)stream;
-    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_pool_byte_sums, dim3(nI), dim3(1024), 0, s, pool_u8, px_off, hw, pool_px,
-                       reinterpret_cast<unsigned long long *>(sums), status);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
-}
-
-// one tap of crop t's source: 0 outside it; inside, the pixel's three channels, through hed_pixel when the crop's image is jittered
-template <bool JIT>
-__device__ __forceinline__ void pool_tap(const uint8_t *__restrict__ img, int sh, int sw, int y, int x, const float *sigma,
-                                         const float *bias, int simple_mode, float *v) {
-    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) { v[0] = v[1] = v[2] = 0.f; return; }
-    const uint8_t *px = img + ((long long)y * sw + x) * 3;
-    uint8_t r[3] = {px[0], px[1], px[2]};
-    if (JIT) hed_pixel(px, sigma, bias, simple_mode, r);
-    v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
-}
-
-// k_warp_affine<true> with a source per crop, image_of[t] of the pool, and a per-pixel colour transform folded into the taps:
-// f(tap) of an in-source tap, 0 (not f(0)) outside -- bitwise the transform of the whole image followed by the warp.  `taps` fills
-// the four neighbours a, b (row y0) and d, e (row y0 + 1) of crop t; the coordinates, the lerps and the label rule are shared by
-// every pool kernel.
-template <class Taps>
-__device__ __forceinline__ void warp_pool_pixel(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
-                                                const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI,
-                                                long long pool_px, const int32_t *__restrict__ image_of,
-                                                const double *__restrict__ inv, int dh, int dw, int label_fill,
-                                                float *__restrict__ out, int16_t *__restrict__ lab_out,
-                                                int32_t *__restrict__ status, const Taps &taps) {
-    const int p = blockIdx.x * NTHR + threadIdx.x;
-    if (p >= dh * dw) return;
-    const size_t t = blockIdx.y;
-    const size_t plane = (size_t)dh * dw;
-    const int im = image_of[t];
-    int bad = 0, sh = 0, sw = 0;
-    long long off = 0;
-    if (im < 0 || im >= nI) bad = 1;
-    else {
-        off = px_off[im]; sh = hw[2 * im]; sw = hw[2 * im + 1];
-        if (!pool_entry_ok(off, sh, sw, pool_px)) bad = 2;
-    }
-    if (bad) {                                                          // nothing of the pool is read for this crop
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = 0.f;
-        if (lab_out) lab_out[t * plane + p] = (int16_t)label_fill;
-        if (p == 0) atomicOr(status, bad);
-        return;
-    }
-    const uint8_t *img = pool + 3 * off;
-    const int y = p / dw, x = p - y * dw;
-    const double *m = inv + t * 6;
-    const double sx = m[0] * (double)x + m[1] * (double)y + m[2];
-    const double sy = m[3] * (double)x + m[4] * (double)y + m[5];
-    float v[3] = {0.f, 0.f, 0.f};
-    if (sx >= -1.0 && sx < (double)sw && sy >= -1.0 && sy < (double)sh) {
-        const double fx = floor(sx), fy = floor(sy);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float wx = (float)(sx - fx), wy = (float)(sy - fy);
-        float a[3], b[3], d[3], e[3];
-        taps(t, img, sh, sw, y0, x0, a, b, d, e);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float top = a[c] + (b[c] - a[c]) * wx;
-            const float bot = d[c] + (e[c] - d[c]) * wx;
-            v[c] = top + (bot - top) * wy;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
-    if (lab_out) {
-        int r = label_fill;
-        const double nx = floor(sx + 0.5), ny = floor(sy + 0.5);
-        if (nx >= 0.0 && nx < (double)sw && ny >= 0.0 && ny < (double)sh) r = pool_lab[off + (long long)(int)ny * sw + (int)nx];
-        lab_out[t * plane + p] = (int16_t)r;
-    }
-}
-
-// the taps of cpx_warp_affine_pool_u8: through hed_pixel where the crop's image is jittered, else the bytes themselves
-struct HedTaps {
-    const float *sigma, *bias;
-    const int32_t *applied;
-    int simple_mode;
-    __device__ __forceinline__ void operator()(size_t t, const uint8_t *img, int sh, int sw, int y0, int x0, float *a, float *b,
-                                               float *d, float *e) const {
-        if (sigma && applied[t]) {
-            const float *sg = sigma + t * 3, *bs = bias + t * 3;
-            pool_tap<true>(img, sh, sw, y0, x0, sg, bs, simple_mode, a);
-            pool_tap<true>(img, sh, sw, y0, x0 + 1, sg, bs, simple_mode, b);
-            pool_tap<true>(img, sh, sw, y0 + 1, x0, sg, bs, simple_mode, d);
-            pool_tap<true>(img, sh, sw, y0 + 1, x0 + 1, sg, bs, simple_mode, e);
-        } else {
-            pool_tap<false>(img, sh, sw, y0, x0, nullptr, nullptr, 0, a);
-            pool_tap<false>(img, sh, sw, y0, x0 + 1, nullptr, nullptr, 0, b);
-            pool_tap<false>(img, sh, sw, y0 + 1, x0, nullptr, nullptr, 0, d);
-            pool_tap<false>(img, sh, sw, y0 + 1, x0 + 1, nullptr, nullptr, 0, e);
-        }
-    }
-};
-
-__global__ void k_warp_affine_pool(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
-                                   const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI, long long pool_px,
-                                   const int32_t *__restrict__ image_of, const double *__restrict__ inv,
-                                   const float *__restrict__ sigma, const float *__restrict__ bias,
-                                   const int32_t *__restrict__ applied, int simple_mode, int dh, int dw, int label_fill,
-                                   float *__restrict__ out, int16_t *__restrict__ lab_out, int32_t *__restrict__ status) {
-    warp_pool_pixel(pool, pool_lab, px_off, hw, nI, pool_px, image_of, inv, dh, dw, label_fill, out, lab_out, status,
-                    HedTaps{sigma, bias, applied, simple_mode});
-}
-
-extern "C" int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw,
-                                       int nI, long long pool_px, const int32_t *image_of, const double *inv, int n,
-                                       const float *sigma, const float *bias, const int32_t *applied, int simple_mode, int dh,
-                                       int dw, int label_fill, float *out, int16_t *labels_out, int32_t *status, void *stream) {
-    CPX_REQUIRE(pool_u8 && px_off && hw && image_of && inv && out && status && nI > 0 && pool_px > 0);
-    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
-    CPX_REQUIRE((pool_lab == nullptr) == (labels_out == nullptr));
-    CPX_REQUIRE((sigma == nullptr) == (bias == nullptr) && (sigma == nullptr) == (applied == nullptr));
-    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
-    hipStream_t s = (hipStream_t)stream;
-    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_warp_affine_pool, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
-                       px_off, hw, nI, pool_px, image_of, inv, sigma, bias, applied, simple_mode ? 1 : 0, dh, dw, label_fill, out,
-                       labels_out, status);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
-}
-
-// t8: the flow-head targets (mask, flow Y, flow X), three float32 planes per image at float 3 * px_off[i], under the crop's map:
-// the flow branch of cellpose transforms.random_rotate_and_resize (lbl[1:] warped bilinearly, the X flow of a flipped source
-// negated, then the pair rotated by theta; restated from cellpose 4.0.x).  Coordinates, taps and lerps are warp_pool_pixel's.
-__device__ __forceinline__ float flow_tap(const float *__restrict__ plane, int sh, int sw, int y, int x) {
-    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) return 0.f;
-    return plane[(long long)y * sw + x];
-}
-
-__global__ void k_warp_affine_pool_flow(const float *__restrict__ pool_tgt, const int64_t *__restrict__ px_off,
-                                        const int32_t *__restrict__ hw, int nI, long long pool_px,
-                                        const int32_t *__restrict__ image_of, const double *__restrict__ inv,
-                                        const double *__restrict__ vec, int dh, int dw, float *__restrict__ out,
-                                        int32_t *__restrict__ status) {
-    const int p = blockIdx.x * NTHR + threadIdx.x;
-    if (p >= dh * dw) return;
-    const size_t t = blockIdx.y;
-    const size_t plane = (size_t)dh * dw;
-    const int im = image_of[t];
-    int bad = 0, sh = 0, sw = 0;
-    long long off = 0;
-    if (im < 0 || im >= nI) bad = 1;
-    else {
-        off = px_off[im]; sh = hw[2 * im]; sw = hw[2 * im + 1];
-        if (!pool_entry_ok(off, sh, sw, pool_px)) bad = 2;
-    }
-    float v[3] = {0.f, 0.f, 0.f};
-    if (bad) {                                                          // nothing of the pool is read for this crop
-        if (p == 0) atomicOr(status, bad);
-    } else {
-        const float *img = pool_tgt + 3 * off;
-        const long long spx = (long long)sh * sw;
-        const int y = p / dw, x = p - y * dw;
-        const double *m = inv + t * 6;
-        const double sx = m[0] * (double)x + m[1] * (double)y + m[2];
-        const double sy = m[3] * (double)x + m[4] * (double)y + m[5];
-        if (sx >= -1.0 && sx < (double)sw && sy >= -1.0 && sy < (double)sh) {
-            const double fx = floor(sx), fy = floor(sy);
-            const int x0 = (int)fx, y0 = (int)fy;
-            const float wx = (float)(sx - fx), wy = (float)(sy - fy);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float *pl = img + c * spx;
-                const float a = flow_tap(pl, sh, sw, y0, x0), b = flow_tap(pl, sh, sw, y0, x0 + 1);
-                const float d = flow_tap(pl, sh, sw, y0 + 1, x0), e = flow_tap(pl, sh, sw, y0 + 1, x0 + 1);
-                const float top = a + (b - a) * wx;
-                const float bot = d + (e - d) * wx;
-                v[c] = top + (bot - top) * wy;
-            }
-        }
-        const double *r = vec + t * 4;
-        const float r0 = (float)r[0], r1 = (float)r[1], r2 = (float)r[2], r3 = (float)r[3];
-        const float y0p = r0 * v[1], y1p = r1 * v[2], x0p = r2 * v[1], x1p = r3 * v[2];     // (-ffp-contract=off: no fma)
-        v[1] = y0p + y1p;
-        v[2] = x0p + x1p;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
-}
-
-extern "C" int cpx_warp_affine_pool_flow_f32(const float *pool_tgt, const int64_t *px_off, const int32_t *hw, int nI,
-                                             long long pool_px, const int32_t *image_of, const double *inv, const double *vec,
-                                             int n, int dh, int dw, float *out, int32_t *status, void *stream) {
-    CPX_REQUIRE(pool_tgt && px_off && hw && image_of && inv && vec && out && status && nI > 0 && pool_px > 0);
-    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
-    hipStream_t s = (hipStream_t)stream;
-    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_warp_affine_pool_flow, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_tgt, px_off, hw,
-                       nI, pool_px, image_of, inv, vec, dh, dw, out, status);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
-}
-
-// ---------------------------------------------------------------------------
 // H&E stain-matrix perturbation (t5): augment_stains / stains_to_rgb of transforms/he_staining.py
 // ---------------------------------------------------------------------------
 // The stain basis is a per-image constant that the host fits once (NMF on the samples of cpx_stain_samples); the device
@@ -479,44 +168,344 @@ extern "C" int cpx_he_stain_u8(const uint8_t *img, int n, int H, int W, const do
     return CPX_OK;
 }
 
-__device__ __forceinline__ void he_tap(const uint8_t *__restrict__ img, int sh, int sw, int y, int x, const double *par,
-                                       const double *dens, float *v) {
-    if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) { v[0] = v[1] = v[2] = 0.f; return; }
-    uint8_t r[3];
-    he_pixel(img + ((long long)y * sw + x) * 3, par, dens, r);
-    v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
+// ---------------------------------------------------------------------------
+// the colour stage of the pool kernels' taps
+// ---------------------------------------------------------------------------
+// one pixel: mode 0 none, 1 hed_pixel, 2 he_pixel.  The three bytes are loaded before the mode's branches: inside them every load
+// waits for the one before it.
+__device__ __forceinline__ void colour_pixel(const uint8_t *__restrict__ px, int m, const float *sg, const float *bs, int simple_mode,
+                                             const double *par, const double *dens, uint8_t *r) {
+    const uint8_t b[3] = {px[0], px[1], px[2]};
+    if (m == 2) he_pixel(b, par, dens, r);
+    else if (m == 1) hed_pixel(b, sg, bs, simple_mode, r);
+    else { r[0] = b[0]; r[1] = b[1]; r[2] = b[2]; }
 }
 
-// the taps of cpx_warp_affine_pool_stain_u8: the crop's mode picks the per-pixel function
-struct StainTaps {
+__device__ __forceinline__ bool tap_inside(int sh, int sw, int y, int x) { return (unsigned)y < (unsigned)sh && (unsigned)x < (unsigned)sw; }
+
+// one tap of a crop's source [sh][sw][3]: zeros (not the colour stage of zeros) and false outside it, else colour_pixel of the pixel
+__device__ __forceinline__ bool colour_tap(const uint8_t *__restrict__ img, int sh, int sw, int y, int x, int m, const float *sg,
+                                           const float *bs, int simple_mode, const double *par, const double *dens, uint8_t *r) {
+    if (!tap_inside(sh, sw, y, x)) { r[0] = r[1] = r[2] = 0; return false; }
+    colour_pixel(img + ((long long)y * sw + x) * 3, m, sg, bs, simple_mode, par, dens, r);
+    return true;
+}
+
+// the taps of cpx_warp_affine_pool_u8 (m = 0 / 1, no tables) and cpx_warp_affine_pool_stain_u8: the crop's mode m picks the per-pixel
+// function.  The branch on m goes around the four taps, each then sees a constant: with the branch inside every tap
+// k_warp_affine_pool measured 1 to 2 % slower where the jitter is on.
+struct ColourTaps {
+    int m;
     const float *sigma, *bias;
     int simple_mode;
     const double *params, *dens;
-    const int32_t *mode;
+    __device__ __forceinline__ bool bytes(int mode, size_t t, const uint8_t *img, int sh, int sw, int y, int x, uint8_t *r) const {
+        return colour_tap(img, sh, sw, y, x, mode, sigma + t * 3, bias + t * 3, simple_mode, params + t * HE_NPAR, dens, r);
+    }
+    __device__ __forceinline__ void tap(int mode, size_t t, const uint8_t *img, int sh, int sw, int y, int x, float *v) const {
+        uint8_t r[3];
+        v[0] = v[1] = v[2] = 0.f;
+        if (bytes(mode, t, img, sh, sw, y, x, r)) { v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2]; }
+    }
+    __device__ __forceinline__ void four(int mode, size_t t, const uint8_t *img, int sh, int sw, int y0, int x0, float *a, float *b,
+                                         float *d, float *e) const {
+        tap(mode, t, img, sh, sw, y0, x0, a);
+        tap(mode, t, img, sh, sw, y0, x0 + 1, b);
+        tap(mode, t, img, sh, sw, y0 + 1, x0, d);
+        tap(mode, t, img, sh, sw, y0 + 1, x0 + 1, e);
+    }
     __device__ __forceinline__ void operator()(size_t t, const uint8_t *img, int sh, int sw, int y0, int x0, float *a, float *b,
                                                float *d, float *e) const {
-        const int m = mode[t];
-        if (m == 2) {
-            const double *par = params + t * HE_NPAR;
-            he_tap(img, sh, sw, y0, x0, par, dens, a);
-            he_tap(img, sh, sw, y0, x0 + 1, par, dens, b);
-            he_tap(img, sh, sw, y0 + 1, x0, par, dens, d);
-            he_tap(img, sh, sw, y0 + 1, x0 + 1, par, dens, e);
-        } else if (m == 1) {
-            const float *sg = sigma + t * 3, *bs = bias + t * 3;
-            pool_tap<true>(img, sh, sw, y0, x0, sg, bs, simple_mode, a);
-            pool_tap<true>(img, sh, sw, y0, x0 + 1, sg, bs, simple_mode, b);
-            pool_tap<true>(img, sh, sw, y0 + 1, x0, sg, bs, simple_mode, d);
-            pool_tap<true>(img, sh, sw, y0 + 1, x0 + 1, sg, bs, simple_mode, e);
-        } else {
-            pool_tap<false>(img, sh, sw, y0, x0, nullptr, nullptr, 0, a);
-            pool_tap<false>(img, sh, sw, y0, x0 + 1, nullptr, nullptr, 0, b);
-            pool_tap<false>(img, sh, sw, y0 + 1, x0, nullptr, nullptr, 0, d);
-            pool_tap<false>(img, sh, sw, y0 + 1, x0 + 1, nullptr, nullptr, 0, e);
-        }
+        if (m == 2) four(2, t, img, sh, sw, y0, x0, a, b, d, e);
+        else if (m == 1) four(1, t, img, sh, sw, y0, x0, a, b, d, e);
+        else four(0, t, img, sh, sw, y0, x0, a, b, d, e);
     }
 };
 
+// ---------------------------------------------------------------------------
+// affine warp
+// ---------------------------------------------------------------------------
+// where output pixel (x, y) samples an sh x sw source under the inverse map m[6]: source = m . (x, y, 1) in double
+struct WarpGeom {
+    double sx, sy;
+    bool inside;            // floor(sx) in [-1, sw - 1] and floor(sy) in [-1, sh - 1], or every tap is outside (NaN lands here too)
+    int x0, y0;             // the upper left of the four taps
+    float wx, wy;           // the bilinear weights
+    // the label rule: the nearest pixel (nx, ny) = floor(s + 0.5), false where it lies outside the source.  Left to the caller's label
+    // branch, behind the taps: formed ahead of them it sat on every pixel's way to its loads (k_warp_affine_pool 1 % slower)
+    __device__ __forceinline__ bool nearest(int sh, int sw, int *nx, int *ny) const {
+        const double fx = floor(sx + 0.5), fy = floor(sy + 0.5);
+        if (!(fx >= 0.0 && fx < (double)sw && fy >= 0.0 && fy < (double)sh)) return false;
+        *nx = (int)fx; *ny = (int)fy;
+        return true;
+    }
+};
+__device__ __forceinline__ WarpGeom warp_geom(const double *__restrict__ m, int x, int y, int sh, int sw) {
+    WarpGeom g = {};
+    g.sx = m[0] * (double)x + m[1] * (double)y + m[2];
+    g.sy = m[3] * (double)x + m[4] * (double)y + m[5];
+    g.inside = g.sx >= -1.0 && g.sx < (double)sw && g.sy >= -1.0 && g.sy < (double)sh;
+    if (g.inside) {
+        const double fx = floor(g.sx), fy = floor(g.sy);
+        g.x0 = (int)fx; g.y0 = (int)fy;
+        g.wx = (float)(g.sx - fx); g.wy = (float)(g.sy - fy);
+    }
+    return g;
+}
+// taps a, b of row y0 and d, e of row y0 + 1
+__device__ __forceinline__ float bilerp(float a, float b, float d, float e, float wx, float wy) {
+    const float top = a + (b - a) * wx;
+    const float bot = d + (e - d) * wx;
+    return top + (bot - top) * wy;
+}
+
+// U8: src [n][sh][sw][3] uint8, else [n][3][sh][sw] float32.  A tap outside the source is 0 on its own.
+template <bool U8>
+__device__ __forceinline__ float warp_tap(const void *src, size_t t, int sh, int sw, int c, int y, int x) {
+    if (!tap_inside(sh, sw, y, x)) return 0.f;
+    if (U8) return (float)((const uint8_t *)src)[((t * sh + y) * sw + x) * 3 + c];
+    return ((const float *)src)[((t * 3 + c) * sh + y) * sw + x];
+}
+
+template <bool U8>
+__global__ void k_warp_affine(const void *__restrict__ src, const int16_t *__restrict__ lab, int sh, int sw,
+                              const double *__restrict__ inv, int dh, int dw, int label_fill, float *__restrict__ out,
+                              int16_t *__restrict__ lab_out) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= dh * dw) return;
+    const size_t t = blockIdx.y;
+    const int y = p / dw, x = p - y * dw;
+    const WarpGeom g = warp_geom(inv + t * 6, x, y, sh, sw);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (g.inside) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            v[c] = bilerp(warp_tap<U8>(src, t, sh, sw, c, g.y0, g.x0), warp_tap<U8>(src, t, sh, sw, c, g.y0, g.x0 + 1),
+                          warp_tap<U8>(src, t, sh, sw, c, g.y0 + 1, g.x0), warp_tap<U8>(src, t, sh, sw, c, g.y0 + 1, g.x0 + 1), g.wx, g.wy);
+    }
+    const size_t plane = (size_t)dh * dw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
+    if (lab) {
+        int nx, ny;
+        lab_out[t * plane + p] = (int16_t)(g.nearest(sh, sw, &nx, &ny) ? lab[(t * sh + ny) * sw + nx] : label_fill);
+    }
+}
+
+
+template <bool U8>
+static int warp_launch(const void *src, const int16_t *labels, int n, int sh, int sw, const double *inv, int dh, int dw,
+                       int label_fill, float *out, int16_t *labels_out, void *stream) {
+    CPX_REQUIRE(src && inv && out && n > 0 && n <= 65535 && sh > 0 && sw > 0 && dh > 0 && dw > 0);
+    CPX_REQUIRE((labels == nullptr) == (labels_out == nullptr));
+    CPX_REQUIRE((long long)sh * sw < (1ll << 29) && (long long)dh * dw < (1ll << 29));
+    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
+    hipLaunchKernelGGL(k_warp_affine<U8>, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, (hipStream_t)stream,
+                       src, labels, sh, sw, inv, dh, dw, label_fill, out, labels_out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+extern "C" int cpx_warp_affine_u8(const uint8_t *src, const int16_t *labels, int n, int sh, int sw, const double *inv,
+                                  int dh, int dw, int label_fill, float *out, int16_t *labels_out, void *stream) {
+    return warp_launch<true>(src, labels, n, sh, sw, inv, dh, dw, label_fill, out, labels_out, stream);
+}
+extern "C" int cpx_warp_affine_f32(const float *src, const int16_t *labels, int n, int sh, int sw, const double *inv,
+                                   int dh, int dw, int label_fill, float *out, int16_t *labels_out, void *stream) {
+    CPX_REQUIRE((const void *)src != (const void *)out);
+    return warp_launch<false>(src, labels, n, sh, sw, inv, dh, dw, label_fill, out, labels_out, stream);
+}
+
+// ---------------------------------------------------------------------------
+// ragged image pool (t4): whole annotated images of any size, packed back to back
+// ---------------------------------------------------------------------------
+// image i: pool_u8 + 3 * px_off[i], hw[i] = {h, w}; a table entry that does not lie inside the pool's pool_px pixels is never read
+__device__ __forceinline__ bool pool_entry_ok(long long off, int h, int w, long long pool_px) {
+    return off >= 0 && h > 0 && w > 0 && off <= pool_px && (long long)h * w <= pool_px - off;
+}
+
+
+// crop t's source in the pool: bad = 1 for an image_of[t] outside the pool's images, 2 for a table entry outside the pool (nothing of
+// the pool may be read for such a crop), else 0 with the image's pixel offset and size
+struct PoolSource {
+    int bad, sh, sw;
+    long long off;
+};
+__device__ __forceinline__ PoolSource pool_source(const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI,
+                                                  long long pool_px, const int32_t *__restrict__ image_of, size_t t) {
+    PoolSource s = {0, 0, 0, 0};
+    const int im = image_of[t];
+    if (im < 0 || im >= nI) s.bad = 1;
+    else {
+        s.off = px_off[im]; s.sh = hw[2 * im]; s.sw = hw[2 * im + 1];
+        if (!pool_entry_ok(s.off, s.sh, s.sw, pool_px)) s.bad = 2;
+    }
+    return s;
+}
+
+// one workgroup per image: the exact integer sum of its bytes (what k_hed_decide forms per patch)
+__global__ void __launch_bounds__(1024) k_pool_byte_sums(const uint8_t *__restrict__ pool, const int64_t *__restrict__ px_off,
+                                                         const int32_t *__restrict__ hw, long long pool_px,
+                                                         unsigned long long *__restrict__ sums, int32_t *__restrict__ status) {
+    const int i = blockIdx.x;
+    const long long off = px_off[i];
+    const int h = hw[2 * i], w = hw[2 * i + 1];
+    if (!pool_entry_ok(off, h, w, pool_px)) {                           // uniform over the workgroup
+        if (threadIdx.x == 0) { sums[i] = 0; atomicOr(status, 2); }
+        return;
+    }
+    const unsigned long long tot = block_byte_sum(pool + 3 * off, 3ll * h * w);
+    if (threadIdx.x == 0) sums[i] = tot;
+}
+
+
+extern "C" int cpx_pool_byte_sums(const uint8_t *pool_u8, const int64_t *px_off, const int32_t *hw, int nI, long long pool_px,
+                                  uint64_t *sums, int32_t *status, void *stream) {
+    CPX_REQUIRE(pool_u8 && px_off && hw && sums && status && nI > 0 && pool_px > 0);
+    hipStream_t s = (hipStream_t)stream;
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_pool_byte_sums, dim3(nI), dim3(1024), 0, s, pool_u8, px_off, hw, pool_px,
+                       reinterpret_cast<unsigned long long *>(sums), status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// k_warp_affine<true> with a source per crop, image_of[t] of the pool, and a per-pixel colour transform folded into the taps:
+// f(tap) of an in-source tap, 0 (not f(0)) outside -- bitwise the transform of the whole image followed by the warp.  `taps` fills
+// the four neighbours a, b (row y0) and d, e (row y0 + 1) of crop t; the source lookup, the geometry and the label rule are shared
+// by every pool kernel.
+template <class Taps>
+__device__ __forceinline__ void warp_pool_pixel(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
+                                                const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI,
+                                                long long pool_px, const int32_t *__restrict__ image_of,
+                                                const double *__restrict__ inv, int dh, int dw, int label_fill,
+                                                float *__restrict__ out, int16_t *__restrict__ lab_out,
+                                                int32_t *__restrict__ status, const Taps &taps) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= dh * dw) return;
+    const size_t t = blockIdx.y;
+    const size_t plane = (size_t)dh * dw;
+    const PoolSource s = pool_source(px_off, hw, nI, pool_px, image_of, t);
+    if (s.bad) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = 0.f;
+        if (lab_out) lab_out[t * plane + p] = (int16_t)label_fill;
+        if (p == 0) atomicOr(status, s.bad);
+        return;
+    }
+    const int y = p / dw, x = p - y * dw;
+    const WarpGeom g = warp_geom(inv + t * 6, x, y, s.sh, s.sw);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (g.inside) {
+        float a[3], b[3], d[3], e[3];
+        taps(t, pool + 3 * s.off, s.sh, s.sw, g.y0, g.x0, a, b, d, e);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = bilerp(a[c], b[c], d[c], e[c], g.wx, g.wy);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
+    if (lab_out) {
+        int nx, ny;
+        lab_out[t * plane + p] = (int16_t)(g.nearest(s.sh, s.sw, &nx, &ny) ? pool_lab[s.off + (long long)ny * s.sw + nx] : label_fill);
+    }
+}
+
+// what the pool warps require of the arguments they share (pool: uint8 or float32); clears the status word
+static int pool_warp_require(const void *pool, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw, int nI,
+                             long long pool_px, const int32_t *image_of, const double *inv, int n, int dh, int dw, int label_fill,
+                             const float *out, const int16_t *labels_out, int32_t *status, hipStream_t s) {
+    CPX_REQUIRE(pool && px_off && hw && image_of && inv && out && status && nI > 0 && pool_px > 0);
+    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
+    CPX_REQUIRE((pool_lab == nullptr) == (labels_out == nullptr));
+    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
+    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    return CPX_OK;
+}
+
+
+__global__ void k_warp_affine_pool(const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab,
+                                   const int64_t *__restrict__ px_off, const int32_t *__restrict__ hw, int nI, long long pool_px,
+                                   const int32_t *__restrict__ image_of, const double *__restrict__ inv,
+                                   const float *__restrict__ sigma, const float *__restrict__ bias,
+                                   const int32_t *__restrict__ applied, int simple_mode, int dh, int dw, int label_fill,
+                                   float *__restrict__ out, int16_t *__restrict__ lab_out, int32_t *__restrict__ status) {
+    const int m = (sigma && applied[blockIdx.y]) ? 1 : 0;               // through hed_pixel where the crop's image is jittered
+    warp_pool_pixel(pool, pool_lab, px_off, hw, nI, pool_px, image_of, inv, dh, dw, label_fill, out, lab_out, status,
+                    ColourTaps{m, sigma, bias, simple_mode, nullptr, nullptr});
+}
+
+extern "C" int cpx_warp_affine_pool_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off, const int32_t *hw,
+                                       int nI, long long pool_px, const int32_t *image_of, const double *inv, int n,
+                                       const float *sigma, const float *bias, const int32_t *applied, int simple_mode, int dh,
+                                       int dw, int label_fill, float *out, int16_t *labels_out, int32_t *status, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    CPX_REQUIRE((sigma == nullptr) == (bias == nullptr) && (sigma == nullptr) == (applied == nullptr));
+    if (int rc = pool_warp_require(pool_u8, pool_lab, px_off, hw, nI, pool_px, image_of, inv, n, dh, dw, label_fill, out, labels_out,
+                                   status, s))
+        return rc;
+    hipLaunchKernelGGL(k_warp_affine_pool, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
+                       px_off, hw, nI, pool_px, image_of, inv, sigma, bias, applied, simple_mode ? 1 : 0, dh, dw, label_fill, out,
+                       labels_out, status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// t8: the flow-head targets (mask, flow Y, flow X), three float32 planes per image at float 3 * px_off[i], under the crop's map:
+// the flow branch of cellpose transforms.random_rotate_and_resize (lbl[1:] warped bilinearly, the X flow of a flipped source
+// negated, then the pair rotated by theta; restated from cellpose 4.0.x).  Source lookup, geometry and lerps are warp_pool_pixel's.
+__device__ __forceinline__ float flow_tap(const float *__restrict__ plane, int sh, int sw, int y, int x) {
+    return tap_inside(sh, sw, y, x) ? plane[(long long)y * sw + x] : 0.f;
+}
+
+__global__ void k_warp_affine_pool_flow(const float *__restrict__ pool_tgt, const int64_t *__restrict__ px_off,
+                                        const int32_t *__restrict__ hw, int nI, long long pool_px,
+                                        const int32_t *__restrict__ image_of, const double *__restrict__ inv,
+                                        const double *__restrict__ vec, int dh, int dw, float *__restrict__ out,
+                                        int32_t *__restrict__ status) {
+    const int p = blockIdx.x * NTHR + threadIdx.x;
+    if (p >= dh * dw) return;
+    const size_t t = blockIdx.y;
+    const size_t plane = (size_t)dh * dw;
+    const PoolSource s = pool_source(px_off, hw, nI, pool_px, image_of, t);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (s.bad) {
+        if (p == 0) atomicOr(status, s.bad);
+    } else {
+        const long long spx = (long long)s.sh * s.sw;
+        const int y = p / dw, x = p - y * dw;
+        const WarpGeom g = warp_geom(inv + t * 6, x, y, s.sh, s.sw);
+        if (g.inside) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float *pl = pool_tgt + 3 * s.off + c * spx;
+                v[c] = bilerp(flow_tap(pl, s.sh, s.sw, g.y0, g.x0), flow_tap(pl, s.sh, s.sw, g.y0, g.x0 + 1),
+                              flow_tap(pl, s.sh, s.sw, g.y0 + 1, g.x0), flow_tap(pl, s.sh, s.sw, g.y0 + 1, g.x0 + 1), g.wx, g.wy);
+            }
+        }
+        const double *r = vec + t * 4;
+        const float r0 = (float)r[0], r1 = (float)r[1], r2 = (float)r[2], r3 = (float)r[3];
+        const float y0p = r0 * v[1], y1p = r1 * v[2], x0p = r2 * v[1], x1p = r3 * v[2];     // (-ffp-contract=off: no fma)
+        v[1] = y0p + y1p;
+        v[2] = x0p + x1p;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(t * 3 + c) * plane + p] = v[c];
+}
+
+extern "C" int cpx_warp_affine_pool_flow_f32(const float *pool_tgt, const int64_t *px_off, const int32_t *hw, int nI,
+                                             long long pool_px, const int32_t *image_of, const double *inv, const double *vec,
+                                             int n, int dh, int dw, float *out, int32_t *status, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    CPX_REQUIRE(vec);
+    if (int rc = pool_warp_require(pool_tgt, nullptr, px_off, hw, nI, pool_px, image_of, inv, n, dh, dw, 0, out, nullptr, status, s))
+        return rc;
+    hipLaunchKernelGGL(k_warp_affine_pool_flow, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_tgt, px_off, hw,
+                       nI, pool_px, image_of, inv, vec, dh, dw, out, status);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// cpx_warp_affine_pool_u8 with the crop's mode out of a table, and the density table of he_pixel in LDS
 __global__ void __launch_bounds__(NTHR) k_warp_affine_pool_stain(
     const uint8_t *__restrict__ pool, const int16_t *__restrict__ pool_lab, const int64_t *__restrict__ px_off,
     const int32_t *__restrict__ hw, int nI, long long pool_px, const int32_t *__restrict__ image_of, const double *__restrict__ inv,
@@ -527,7 +516,7 @@ __global__ void __launch_bounds__(NTHR) k_warp_affine_pool_stain(
     s_dens[threadIdx.x] = density[threadIdx.x];
     __syncthreads();
     warp_pool_pixel(pool, pool_lab, px_off, hw, nI, pool_px, image_of, inv, dh, dw, label_fill, out, lab_out, status,
-                    StainTaps{sigma, bias, simple_mode, params, s_dens, mode});
+                    ColourTaps{mode[blockIdx.y], sigma, bias, simple_mode, params, s_dens});
 }
 
 extern "C" int cpx_warp_affine_pool_stain_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off,
@@ -536,19 +525,18 @@ extern "C" int cpx_warp_affine_pool_stain_u8(const uint8_t *pool_u8, const int16
                                              const double *stain_params, const double *density, const int32_t *mode, int dh,
                                              int dw, int label_fill, float *out, int16_t *labels_out, int32_t *status,
                                              void *stream) {
-    CPX_REQUIRE(pool_u8 && px_off && hw && image_of && inv && out && status && nI > 0 && pool_px > 0);
-    CPX_REQUIRE(sigma && bias && stain_params && density && mode);
-    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
-    CPX_REQUIRE((pool_lab == nullptr) == (labels_out == nullptr));
-    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
     hipStream_t s = (hipStream_t)stream;
-    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    CPX_REQUIRE(sigma && bias && stain_params && density && mode);
+    if (int rc = pool_warp_require(pool_u8, pool_lab, px_off, hw, nI, pool_px, image_of, inv, n, dh, dw, label_fill, out, labels_out,
+                                   status, s))
+        return rc;
     hipLaunchKernelGGL(k_warp_affine_pool_stain, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
                        px_off, hw, nI, pool_px, image_of, inv, sigma, bias, simple_mode ? 1 : 0, stain_params, density, mode, dh,
                        dw, label_fill, out, labels_out, status);
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }
+
 
 // ---------------------------------------------------------------------------
 // tissue samples of every image of a pool: values = density[tissue_mask] (all pixels when the mask is empty), values[::128]
@@ -872,14 +860,6 @@ extern "C" int cpx_normalize_apply_f32(const float *img, const float *stats, int
 // ---------------------------------------------------------------------------
 // image quality (t6): Gaussian blur and hue / brightness / saturation jitter of transforms/image_quality.py
 // ---------------------------------------------------------------------------
-// the colour stage of one pixel, as the pool kernels' taps run it: mode 0 none, 1 hed_pixel, 2 he_pixel
-__device__ __forceinline__ void colour_pixel(const uint8_t *__restrict__ px, int m, const float *sg, const float *bs, int simple_mode,
-                                             const double *par, const double *dens, uint8_t *r) {
-    if (m == 2) he_pixel(px, par, dens, r);
-    else if (m == 1) hed_pixel(px, sg, bs, simple_mode, r);
-    else { r[0] = px[0]; r[1] = px[1]; r[2] = px[2]; }
-}
-
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 
 // _hbs_adjust of one uint8 pixel: torchvision's adjust_hue / adjust_brightness / adjust_saturation in float32, one rounding per
@@ -983,16 +963,11 @@ __global__ void __launch_bounds__(NTHR) k_blur_pool_rects(
     const size_t t = blockIdx.y;
     const int tid = threadIdx.x;
     // everything below up to the first barrier is uniform over the workgroup
-    const int im = image_of[t];
     const int y0 = rects[4 * t], x0 = rects[4 * t + 1], rh = rects[4 * t + 2], rw = rects[4 * t + 3], r = radius[t];
     const long long soff = scratch_off[t];
-    int bad = 0, sh = 0, sw = 0;
-    long long off = 0;
-    if (im < 0 || im >= nI) bad = 1;
-    else {
-        off = px_off[im]; sh = hw[2 * im]; sw = hw[2 * im + 1];
-        if (!pool_entry_ok(off, sh, sw, pool_px)) bad = 2;
-    }
+    const PoolSource src = pool_source(px_off, hw, nI, pool_px, image_of, t);
+    const int sh = src.sh, sw = src.sw;
+    int bad = src.bad;
     if (!bad && (y0 < 0 || x0 < 0 || rh <= 0 || rw <= 0 || rh > max_h || rw > max_w || (long long)y0 + rh > sh ||
                  (long long)x0 + rw > sw || r < 0 || r > BLUR_RMAX))
         bad = 4;
@@ -1010,7 +985,7 @@ __global__ void __launch_bounds__(NTHR) k_blur_pool_rects(
     s_dens[tid] = density[tid];
     if (tid < BLUR_NW) s_w[tid] = weights[t * BLUR_NW + tid];
     __syncthreads();
-    const uint8_t *img = pool + 3 * off;
+    const uint8_t *img = pool + 3 * src.off;
     const float *sg = sigma + t * 3, *bs = bias + t * 3;
     const double *par = params + t * HE_NPAR;
     // tile + halo through the colour functor, reflected about the image's borders
@@ -1077,14 +1052,11 @@ extern "C" int cpx_blur_pool_rects_u8(const uint8_t *pool_u8, const int64_t *px_
     return CPX_OK;
 }
 
-// the taps of cpx_warp_affine_pool_quality_u8: the colour stage of StainTaps, or the bytes of the crop's blurred rectangle in the
-// scratch in its place, then hbs_pixel where the crop's flag is set.  A tap inside the image that the rectangle does not cover is
-// 0, sets status bit 4 and reads nothing.
+// the taps of cpx_warp_affine_pool_quality_u8: the shared colour tap, or the bytes of the crop's blurred rectangle in the scratch in
+// its place, then hbs_pixel where the crop's flag is set.  A tap inside the image that the rectangle does not cover is 0, sets
+// status bit 4 and reads nothing.
 struct QualityTaps {
-    const float *sigma, *bias;
-    int simple_mode;
-    const double *params, *dens;
-    const int32_t *mode;
+    ColourTaps colour;
     const float *hbs, *unit;
     const int32_t *hbs_apply;
     const uint8_t *scratch;
@@ -1092,26 +1064,26 @@ struct QualityTaps {
     const int64_t *ov_off;
     const int32_t *ov_rect;
     int32_t *status;
-    __device__ __forceinline__ void tap(size_t t, const uint8_t *img, int sh, int sw, int y, int x, int m, long long so, int do_hbs,
+    __device__ __forceinline__ bool scratch_tap(size_t t, int sh, int sw, int y, int x, long long so, uint8_t *r) const {
+        r[0] = r[1] = r[2] = 0;
+        if (!tap_inside(sh, sw, y, x)) return false;
+        const int *rc = ov_rect + 4 * t;
+        const int ry = y - rc[0], rx = x - rc[1];
+        if ((unsigned)ry >= (unsigned)rc[2] || (unsigned)rx >= (unsigned)rc[3]) { atomicOr(status, 16); return false; }
+        const uint8_t *px = scratch + so + ((long long)ry * rc[3] + rx) * 3;
+        r[0] = px[0]; r[1] = px[1]; r[2] = px[2];
+        return true;
+    }
+    __device__ __forceinline__ void tap(size_t t, const uint8_t *img, int sh, int sw, int y, int x, long long so, int do_hbs,
                                         float *v) const {
-        v[0] = v[1] = v[2] = 0.f;
-        if ((unsigned)y >= (unsigned)sh || (unsigned)x >= (unsigned)sw) return;
         uint8_t r[3];
-        if (so >= 0) {
-            const int *rc = ov_rect + 4 * t;
-            const int ry = y - rc[0], rx = x - rc[1];
-            if ((unsigned)ry >= (unsigned)rc[2] || (unsigned)rx >= (unsigned)rc[3]) { atomicOr(status, 16); return; }
-            const uint8_t *px = scratch + so + ((long long)ry * rc[3] + rx) * 3;
-            r[0] = px[0]; r[1] = px[1]; r[2] = px[2];
-        } else {
-            colour_pixel(img + ((long long)y * sw + x) * 3, m, sigma + t * 3, bias + t * 3, simple_mode, params + t * HE_NPAR, dens, r);
-        }
-        if (do_hbs) hbs_pixel(r, hbs + t * 4, unit, r);
+        const bool in = so >= 0 ? scratch_tap(t, sh, sw, y, x, so, r) : colour.bytes(colour.m, t, img, sh, sw, y, x, r);
+        if (in && do_hbs) hbs_pixel(r, hbs + t * 4, unit, r);
         v[0] = (float)r[0]; v[1] = (float)r[1]; v[2] = (float)r[2];
     }
     __device__ __forceinline__ void operator()(size_t t, const uint8_t *img, int sh, int sw, int y0, int x0, float *a, float *b,
                                                float *d, float *e) const {
-        const int m = mode[t], do_hbs = hbs_apply[t];
+        const int do_hbs = hbs_apply[t];
         long long so = ov_off[t];
         if (so >= 0) {                                                  // a range outside the scratch is never read
             const int *rc = ov_rect + 4 * t;
@@ -1121,10 +1093,10 @@ struct QualityTaps {
                 return;
             }
         }
-        tap(t, img, sh, sw, y0, x0, m, so, do_hbs, a);
-        tap(t, img, sh, sw, y0, x0 + 1, m, so, do_hbs, b);
-        tap(t, img, sh, sw, y0 + 1, x0, m, so, do_hbs, d);
-        tap(t, img, sh, sw, y0 + 1, x0 + 1, m, so, do_hbs, e);
+        tap(t, img, sh, sw, y0, x0, so, do_hbs, a);
+        tap(t, img, sh, sw, y0, x0 + 1, so, do_hbs, b);
+        tap(t, img, sh, sw, y0 + 1, x0, so, do_hbs, d);
+        tap(t, img, sh, sw, y0 + 1, x0 + 1, so, do_hbs, e);
     }
 };
 
@@ -1142,8 +1114,8 @@ __global__ void __launch_bounds__(NTHR) k_warp_affine_pool_quality(
     s_unit[threadIdx.x] = unit[threadIdx.x];
     __syncthreads();
     warp_pool_pixel(pool, pool_lab, px_off, hw, nI, pool_px, image_of, inv, dh, dw, label_fill, out, lab_out, status,
-                    QualityTaps{sigma, bias, simple_mode, params, s_dens, mode, hbs, s_unit, hbs_apply, scratch, scratch_bytes, ov_off,
-                                ov_rect, status});
+                    QualityTaps{ColourTaps{mode[blockIdx.y], sigma, bias, simple_mode, params, s_dens}, hbs, s_unit, hbs_apply, scratch,
+                                scratch_bytes, ov_off, ov_rect, status});
 }
 
 extern "C" int cpx_warp_affine_pool_quality_u8(const uint8_t *pool_u8, const int16_t *pool_lab, const int64_t *px_off,
@@ -1154,14 +1126,12 @@ extern "C" int cpx_warp_affine_pool_quality_u8(const uint8_t *pool_u8, const int
                                                long long scratch_bytes, const int64_t *override_off, const int32_t *override_rect,
                                                int dh, int dw, int label_fill, float *out, int16_t *labels_out, int32_t *status,
                                                void *stream) {
-    CPX_REQUIRE(pool_u8 && px_off && hw && image_of && inv && out && status && nI > 0 && pool_px > 0);
+    hipStream_t s = (hipStream_t)stream;
     CPX_REQUIRE(sigma && bias && stain_params && density && mode && hbs && hbs_apply && unit && override_off && override_rect);
     CPX_REQUIRE(scratch_bytes >= 0 && (scratch != nullptr || scratch_bytes == 0));
-    CPX_REQUIRE(n > 0 && n <= 65535 && dh > 0 && dw > 0 && (long long)dh * dw < (1ll << 29));
-    CPX_REQUIRE((pool_lab == nullptr) == (labels_out == nullptr));
-    CPX_REQUIRE(label_fill >= -32768 && label_fill <= 32767);
-    hipStream_t s = (hipStream_t)stream;
-    CPX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    if (int rc = pool_warp_require(pool_u8, pool_lab, px_off, hw, nI, pool_px, image_of, inv, n, dh, dw, label_fill, out, labels_out,
+                                   status, s))
+        return rc;
     hipLaunchKernelGGL(k_warp_affine_pool_quality, dim3(cpx_cdiv((long long)dh * dw, NTHR), n), dim3(NTHR), 0, s, pool_u8, pool_lab,
                        px_off, hw, nI, pool_px, image_of, inv, sigma, bias, simple_mode ? 1 : 0, stain_params, density, mode, hbs,
                        hbs_apply, unit, scratch, scratch_bytes, override_off, override_rect, dh, dw, label_fill, out, labels_out,

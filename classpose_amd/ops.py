@@ -632,33 +632,14 @@ def warp_flow_targets(pool_tgt: torch.Tensor, px_off: torch.Tensor, hw: torch.Te
     """``cpx_warp_affine_pool_flow_f32``: ``pool_tgt`` float32 (3 * pool_px,), per image of the table (px_off, hw) the planes
     (mask, flow Y, flow X) as [3][h][w] from float 3 * px_off[i]; crop t samples image ``image_of[t]`` by ``inv[t]`` like
     ``warp_affine`` and maps the flow pair through ``vec[t]`` (``augment.flow_vec``).  Returns (float32 (n, 3, dh, dw), status)."""
-    if pool_tgt.dtype != torch.float32 or pool_tgt.dim() != 1 or pool_tgt.numel() % 3 or not pool_tgt.is_contiguous() \
-            or not pool_tgt.is_cuda:
-        raise ValueError("warp_flow_targets: pool_tgt is a contiguous float32 device vector of 3 values per pixel")
-    dev, pool_px, nI = pool_tgt.device, pool_tgt.numel() // 3, px_off.numel()
-    if px_off.dtype != torch.int64 or px_off.dim() != 1 or nI == 0 or px_off.device != dev or not px_off.is_contiguous():
-        raise ValueError("warp_flow_targets: px_off is int64 (nI,) on the pool's device")
-    if hw.dtype != torch.int32 or hw.shape != (nI, 2) or hw.device != dev or not hw.is_contiguous():
-        raise ValueError("warp_flow_targets: hw is int32 (nI, 2) on the pool's device")
-    dh, dw = (int(v) for v in out_hw)
-    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
-    n = image_of.numel()
-
-    def f64(a):
-        a = torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64) if not isinstance(a, torch.Tensor) else a)
-        return a.to(device=dev, dtype=torch.float64).contiguous()
-    inv, vec = f64(inv), f64(vec)
-    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6) or vec.shape != (n, 4):
-        raise ValueError("warp_flow_targets: image_of is (n,), inv (n, 6) and vec (n, 4) float64")
-    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
+    dev, nI, pool_px = _pool_table(pool_tgt, px_off, hw, "warp_flow_targets", torch.float32)
+    image_of, inv, vec, n = _crop_maps(image_of, inv, dev, "warp_flow_targets", vec)
+    dh, dw, out, _lab_out, status = _pool_outputs(None, pool_px, n, out_hw, dev, "warp_flow_targets")
     check(_lib.lib().cpx_warp_affine_pool_flow_f32(ptr(pool_tgt), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv),
                                                    ptr(vec), n, dh, dw, ptr(out), ptr(status), _stream(dev)),
           "warp_affine_pool_flow_f32")
     if check_status:
-        bits = int(status.item())
-        if bits:
-            raise ValueError("warp_flow_targets: " + ("an image index outside the pool" if bits & 1 else "a table entry outside the pool"))
+        _raise_status(status, "warp_flow_targets", _POOL_BITS)
     return out, status
 
 
@@ -873,8 +854,7 @@ def warp_affine(src: torch.Tensor, inv, out_hw, labels: torch.Tensor | None = No
     n = src.shape[0]
     sh, sw = (src.shape[1], src.shape[2]) if u8 else (src.shape[2], src.shape[3])
     dev = src.device
-    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
-    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
+    inv = _f64(inv, dev)
     if inv.shape != (n, 6):
         raise ValueError("warp_affine: inv is (n, 6) float64")
     lab_out = None
@@ -889,16 +869,55 @@ def warp_affine(src: torch.Tensor, inv, out_hw, labels: torch.Tensor | None = No
     return out, lab_out
 
 
-def _pool_table(pool_u8, px_off, hw, what: str):
-    if pool_u8.dtype != torch.uint8 or pool_u8.dim() != 1 or pool_u8.numel() % 3 or not pool_u8.is_contiguous() or not pool_u8.is_cuda:
-        raise ValueError(f"{what}: pool_u8 is a contiguous uint8 device vector of 3 bytes per pixel")
-    dev = pool_u8.device
+def _f64(a, dev) -> torch.Tensor:
+    a = torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64) if not isinstance(a, torch.Tensor) else a)
+    return a.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _pool_table(pool, px_off, hw, what: str, dtype=torch.uint8):
+    """(device, nI, pool_px) of a ragged pool of 3 ``dtype`` values per pixel with its table (px_off, hw)."""
+    if pool.dtype != dtype or pool.dim() != 1 or pool.numel() % 3 or not pool.is_contiguous() or not pool.is_cuda:
+        name, unit = ("pool_u8", "uint8 device vector of 3 bytes") if dtype == torch.uint8 else ("pool_tgt", "float32 device vector of 3 values")
+        raise ValueError(f"{what}: {name} is a contiguous {unit} per pixel")
+    dev = pool.device
     nI = px_off.numel()
     if px_off.dtype != torch.int64 or px_off.dim() != 1 or nI == 0 or px_off.device != dev or not px_off.is_contiguous():
         raise ValueError(f"{what}: px_off is int64 (nI,) on the pool's device")
     if hw.dtype != torch.int32 or hw.shape != (nI, 2) or hw.device != dev or not hw.is_contiguous():
         raise ValueError(f"{what}: hw is int32 (nI, 2) on the pool's device")
-    return dev, nI, pool_u8.numel() // 3
+    return dev, nI, pool.numel() // 3
+
+
+def _crop_maps(image_of, inv, dev, what: str, vec=None):
+    """(image_of (n,) int32, inv (n, 6) float64, vec (n, 4) float64 or None, n) of a pool warp's crops on ``dev``."""
+    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
+    n = image_of.numel()
+    inv, vec = _f64(inv, dev), None if vec is None else _f64(vec, dev)
+    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6) or (vec is not None and vec.shape != (n, 4)):
+        raise ValueError(f"{what}: image_of is (n,), inv (n, 6)" + ("" if vec is None else " and vec (n, 4)") + " float64")
+    return image_of, inv, vec, n
+
+
+def _pool_outputs(pool_lab, pool_px: int, n: int, out_hw, dev, what: str):
+    """(dh, dw, float32 (n, 3, dh, dw), int16 (n, dh, dw) or None without ``pool_lab``, int32 (1,) status) of a pool warp."""
+    dh, dw = (int(v) for v in out_hw)
+    lab_out = None
+    if pool_lab is not None:
+        if pool_lab.dtype != torch.int16 or pool_lab.shape != (pool_px,) or pool_lab.device != dev or not pool_lab.is_contiguous():
+            raise ValueError(f"{what}: pool_lab is a contiguous int16 vector of one label per pool pixel on the pool's device")
+        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
+    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
+    return dh, dw, out, lab_out, torch.empty(1, dtype=torch.int32, device=dev)
+
+
+_POOL_BITS = ((1, "an image index outside the pool"), (2, "a table entry outside the pool"))
+
+
+def _raise_status(status: torch.Tensor, what: str, texts) -> None:
+    """``ValueError`` with the text of the first set bit of ``texts`` ((bit, text), ...) when the status word is not zero."""
+    bits = int(status.item())
+    if bits:
+        raise ValueError(f"{what}: " + next((text for bit, text in texts if bits & bit), f"status {bits}"))
 
 
 def pool_byte_sums(pool_u8: torch.Tensor, px_off: torch.Tensor, hw: torch.Tensor) -> torch.Tensor:
@@ -925,13 +944,7 @@ def warp_affine_pool(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None, px_of
     ``image_of`` outside the pool's images, bit 1 a table entry outside the pool; such crops are zeros / ``label_fill``).
     ``check_status`` raises ``ValueError`` on a non-zero status."""
     dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "warp_affine_pool")
-    dh, dw = (int(v) for v in out_hw)
-    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
-    n = image_of.numel()
-    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
-    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
-    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6):
-        raise ValueError("warp_affine_pool: image_of is (n,) and inv (n, 6) float64")
+    image_of, inv, _vec, n = _crop_maps(image_of, inv, dev, "warp_affine_pool")
     if (sigma is None) != (bias is None) or (sigma is None) != (applied is None):
         raise ValueError("warp_affine_pool: sigma, bias and applied go together")
     if sigma is not None:
@@ -940,20 +953,12 @@ def warp_affine_pool(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None, px_of
         applied = torch.as_tensor(applied).to(device=dev, dtype=torch.int32).contiguous()
         if sigma.shape != (n, 3) or bias.shape != (n, 3) or applied.shape != (n,):
             raise ValueError("warp_affine_pool: sigma and bias are (n, 3), applied (n,)")
-    lab_out = None
-    if pool_lab is not None:
-        if pool_lab.dtype != torch.int16 or pool_lab.shape != (pool_px,) or pool_lab.device != dev or not pool_lab.is_contiguous():
-            raise ValueError("warp_affine_pool: pool_lab is a contiguous int16 vector of one label per pool pixel on the pool's device")
-        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
-    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
+    dh, dw, out, lab_out, status = _pool_outputs(pool_lab, pool_px, n, out_hw, dev, "warp_affine_pool")
     check(_lib.lib().cpx_warp_affine_pool_u8(ptr(pool_u8), ptr(pool_lab), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv), n,
                                              ptr(sigma), ptr(bias), ptr(applied), int(bool(simple_mode)), dh, dw, int(label_fill),
                                              ptr(out), ptr(lab_out), ptr(status), _stream(dev)), "warp_affine_pool_u8")
     if check_status:
-        bits = int(status.item())
-        if bits:
-            raise ValueError("warp_affine_pool: " + ("an image index outside the pool" if bits & 1 else "a table entry outside the pool"))
+        _raise_status(status, "warp_affine_pool", _POOL_BITS)
     return out, lab_out, status
 
 
@@ -1014,8 +1019,7 @@ def stain_samples(pool_u8: torch.Tensor, px_off: torch.Tensor, hw: torch.Tensor,
 
 
 def _stain_args(params, mode, n: int, dev, what: str):
-    params = torch.as_tensor(np.ascontiguousarray(params, dtype=np.float64) if not isinstance(params, torch.Tensor) else params)
-    params = params.to(device=dev, dtype=torch.float64).contiguous()
+    params = _f64(params, dev)
     mode = torch.as_tensor(mode).to(device=dev, dtype=torch.int32).contiguous()
     if params.shape != (n, 14) or mode.shape != (n,):
         raise ValueError(f"{what}: params are (n, 14) float64 and mode (n,) int32")
@@ -1045,41 +1049,15 @@ def warp_affine_pool_stain(pool_u8: torch.Tensor, pool_lab: torch.Tensor | None,
     with ``params`` (n, 14).  ``sigma`` / ``bias`` / ``params`` left out are zeros (their modes must then not occur).  Returns what
     ``warp_affine_pool`` returns."""
     dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "warp_affine_pool_stain")
-    dh, dw = (int(v) for v in out_hw)
-    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
-    n = image_of.numel()
-    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
-    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
-    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6):
-        raise ValueError("warp_affine_pool_stain: image_of is (n,) and inv (n, 6) float64")
-    mode_host = np.asarray(mode.cpu() if isinstance(mode, torch.Tensor) else mode).astype(np.int64)
-    if mode_host.shape != (n,) or mode_host.min() < 0 or mode_host.max() > 2:
-        raise ValueError("warp_affine_pool_stain: mode is (n,) with values 0, 1, 2")
-    if (sigma is None) != (bias is None) or (sigma is None and (mode_host == 1).any()) or (params is None and (mode_host == 2).any()):
-        raise ValueError("warp_affine_pool_stain: mode 1 needs sigma and bias, mode 2 needs params")
-    sigma = torch.zeros((n, 3), dtype=torch.float32) if sigma is None else torch.as_tensor(sigma, dtype=torch.float32)
-    bias = torch.zeros((n, 3), dtype=torch.float32) if bias is None else torch.as_tensor(bias, dtype=torch.float32)
-    sigma, bias = sigma.to(dev).contiguous(), bias.to(dev).contiguous()
-    if sigma.shape != (n, 3) or bias.shape != (n, 3):
-        raise ValueError("warp_affine_pool_stain: sigma and bias are (n, 3)")
-    params, mode = _stain_args(np.zeros((n, 14)) if params is None else params, mode_host, n, dev, "warp_affine_pool_stain")
-    lab_out = None
-    if pool_lab is not None:
-        if pool_lab.dtype != torch.int16 or pool_lab.shape != (pool_px,) or pool_lab.device != dev or not pool_lab.is_contiguous():
-            raise ValueError("warp_affine_pool_stain: pool_lab is a contiguous int16 vector of one label per pool pixel on the pool's "
-                             "device")
-        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
-    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
+    image_of, inv, _vec, n = _crop_maps(image_of, inv, dev, "warp_affine_pool_stain")
+    mode, sigma, bias, params = _colour_args(mode, sigma, bias, params, n, dev, "warp_affine_pool_stain")
+    dh, dw, out, lab_out, status = _pool_outputs(pool_lab, pool_px, n, out_hw, dev, "warp_affine_pool_stain")
     check(_lib.lib().cpx_warp_affine_pool_stain_u8(ptr(pool_u8), ptr(pool_lab), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv),
                                                    n, ptr(sigma), ptr(bias), int(bool(simple_mode)), ptr(params),
                                                    ptr(_stain_table(dev, "density")), ptr(mode), dh, dw, int(label_fill), ptr(out),
                                                    ptr(lab_out), ptr(status), _stream(dev)), "warp_affine_pool_stain_u8")
     if check_status:
-        bits = int(status.item())
-        if bits:
-            raise ValueError("warp_affine_pool_stain: " + ("an image index outside the pool" if bits & 1
-                                                           else "a table entry outside the pool"))
+        _raise_status(status, "warp_affine_pool_stain", _POOL_BITS)
     return out, lab_out, status
 
 
@@ -1184,11 +1162,7 @@ def blur_pool_rects(pool_u8: torch.Tensor, px_off: torch.Tensor, hw: torch.Tenso
                                             int(bool(simple_mode)), ptr(params), ptr(_stain_table(dev, "density")), ptr(mode),
                                             ptr(scratch), scratch.numel(), ptr(status), _stream(dev)), "blur_pool_rects_u8")
     if check_status:
-        bits = int(status.item())
-        if bits:
-            raise ValueError("blur_pool_rects: " + ("an image index outside the pool" if bits & 1 else
-                                                    "a table entry outside the pool" if bits & 2 else
-                                                    "a rectangle outside its image" if bits & 4 else "a range outside the scratch"))
+        _raise_status(status, "blur_pool_rects", _POOL_BITS + ((4, "a rectangle outside its image"), (8, "a range outside the scratch")))
     return scratch, scratch_off, status
 
 
@@ -1218,13 +1192,7 @@ def warp_affine_pool_quality(pool_u8: torch.Tensor, pool_lab: torch.Tensor | Non
     wrote) and the colour stage is skipped.  Status bit 4: a tap inside the image but outside the rectangle (it is 0 and nothing is
     read), bit 3: a range outside the scratch; bits 0 / 1 and the returns as ``warp_affine_pool``."""
     dev, nI, pool_px = _pool_table(pool_u8, px_off, hw, "warp_affine_pool_quality")
-    dh, dw = (int(v) for v in out_hw)
-    image_of = torch.as_tensor(image_of).to(device=dev, dtype=torch.int32).contiguous()
-    n = image_of.numel()
-    inv = torch.as_tensor(np.ascontiguousarray(inv, dtype=np.float64) if not isinstance(inv, torch.Tensor) else inv)
-    inv = inv.to(device=dev, dtype=torch.float64).contiguous()
-    if image_of.dim() != 1 or n == 0 or inv.shape != (n, 6):
-        raise ValueError("warp_affine_pool_quality: image_of is (n,) and inv (n, 6) float64")
+    image_of, inv, _vec, n = _crop_maps(image_of, inv, dev, "warp_affine_pool_quality")
     mode, sigma, bias, params = _colour_args(mode, sigma, bias, params, n, dev, "warp_affine_pool_quality")
     par, hbs_apply = _hbs_args(hbs, hbs_apply, n, dev, "warp_affine_pool_quality")
     if (override_off is None) != (override_rect is None):
@@ -1237,14 +1205,7 @@ def warp_affine_pool_quality(pool_u8: torch.Tensor, pool_lab: torch.Tensor | Non
         raise ValueError("warp_affine_pool_quality: an override needs the scratch")
     if scratch is not None and (scratch.dtype != torch.uint8 or scratch.dim() != 1 or scratch.device != dev or not scratch.is_contiguous()):
         raise ValueError("warp_affine_pool_quality: scratch is a contiguous uint8 vector on the pool's device")
-    lab_out = None
-    if pool_lab is not None:
-        if pool_lab.dtype != torch.int16 or pool_lab.shape != (pool_px,) or pool_lab.device != dev or not pool_lab.is_contiguous():
-            raise ValueError("warp_affine_pool_quality: pool_lab is a contiguous int16 vector of one label per pool pixel on the pool's "
-                             "device")
-        lab_out = torch.empty((n, dh, dw), dtype=torch.int16, device=dev)
-    out = torch.empty((n, 3, dh, dw), dtype=torch.float32, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
+    dh, dw, out, lab_out, status = _pool_outputs(pool_lab, pool_px, n, out_hw, dev, "warp_affine_pool_quality")
     ov_off_dev, ov_rect_dev = torch.from_numpy(ov_off).to(dev), torch.from_numpy(ov_rect).to(dev)
     check(_lib.lib().cpx_warp_affine_pool_quality_u8(
         ptr(pool_u8), ptr(pool_lab), ptr(px_off), ptr(hw), nI, pool_px, ptr(image_of), ptr(inv), n, ptr(sigma), ptr(bias),
@@ -1252,12 +1213,8 @@ def warp_affine_pool_quality(pool_u8: torch.Tensor, pool_lab: torch.Tensor | Non
         ptr(scratch), 0 if scratch is None else scratch.numel(), ptr(ov_off_dev), ptr(ov_rect_dev), dh, dw, int(label_fill), ptr(out), ptr(lab_out), ptr(status), _stream(dev)),
         "warp_affine_pool_quality_u8")
     if check_status:
-        bits = int(status.item())
-        if bits:
-            raise ValueError("warp_affine_pool_quality: " + ("an image index outside the pool" if bits & 1 else
-                                                             "a table entry outside the pool" if bits & 2 else
-                                                             "a range outside the scratch" if bits & 8 else
-                                                             "a tap outside the crop's blurred rectangle"))
+        _raise_status(status, "warp_affine_pool_quality", _POOL_BITS + ((8, "a range outside the scratch"),
+                                                                        (16, "a tap outside the crop's blurred rectangle")))
     return out, lab_out, status
 
 

@@ -2,6 +2,7 @@
 tools/bench_train_quality.py).
 
     python tools/bench_train_flow.py [--rounds 9] [--crops 32] [--out profiles/train_flow_bench.txt]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_train_flow.py --depth 1 --profile-steps 5      (kernels only)
 
 Workload: `--images` uint8 images of 1024^2 of the synthetic slide with blocky class maps and a jittered grid of disc instances,
 `--crops` windows of 256^2 per step, a seeded ViT-L checkpoint with a fresh 7-class 1x1 head, bf16.
@@ -101,6 +102,7 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--depth", type=int, default=24)
     ap.add_argument("--classes", type=int, default=7)
+    ap.add_argument("--profile-steps", type=int, default=0, help="run this many (pf) pool steps with both heads and exit (for rocprofv3)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -137,6 +139,11 @@ def main():
     def step_pf(idx):
         xb, yb, tb = augment.augment_batch_pool(pool_f, idx, rng["pf"], "geometry", dtype=trf.dtype, flow_targets=True)
         return trf.step(xb, yb, lr, flow_targets=tb)
+    if args.profile_steps:
+        for _ in range(args.profile_steps):
+            step_pf(order.integers(0, nI, n))
+        torch.cuda.synchronize()
+        return
     fns = {"c": lambda i: trc.step(feat, y, lr), "f": lambda i: trf.step(feat, y, lr, flow_targets=tg), "pc": step_pc, "pf": step_pf,
            "e": lambda i: eager(feat, y, tg, lr)}
     for f in fns.values():

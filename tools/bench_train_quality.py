@@ -2,6 +2,7 @@
 from whole 1024^2 images.  One process, interleaved rounds, medians (the set-up of tools/bench_train_stain.py).
 
     python tools/bench_train_quality.py [--rounds 9] [--crops 32] [--out profiles/train_quality_bench.txt]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_train_quality.py --depth 1 --profile-steps 5      (kernels only)
 
 Workload: `--images` uint8 images of 1024^2 of the synthetic slide with blocky class maps, `--crops` windows of 256^2 per step, a
 seeded ViT-L checkpoint with a fresh 7-class head, bf16.
@@ -120,6 +121,7 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--depth", type=int, default=24)
     ap.add_argument("--classes", type=int, default=7)
+    ap.add_argument("--profile-steps", type=int, default=0, help="run this many hed_he_quality pool steps and exit (for rocprofv3)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -144,6 +146,11 @@ def main():
 
     def batch_h(idx, g):
         return augment.augment_batch(host_quality(big[idx], g, cfg), big_lab[idx], g, "geometry", dtype=tr.dtype, device=dev)
+    if args.profile_steps:
+        for _ in range(args.profile_steps):
+            tr.step(*batch_a(order.integers(0, nI, n), rng["a"]), lr)
+        torch.cuda.synchronize()
+        return
     fns = {"a": lambda i: tr.step(*batch_a(i, rng["a"]), lr), "p": lambda i: tr.step(*batch_p(i, rng["p"]), lr),
            "h": lambda i: tr.step(*batch_h(i, rng["h"]), lr)}
     for k, f in fns.items():                # warm-up: allocations, code objects (the host leg once: it takes seconds)
