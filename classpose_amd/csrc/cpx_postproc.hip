@@ -362,15 +362,243 @@ __global__ void __launch_bounds__(NTHR) k_follow(int niter, float shx, float shy
     }
 }
 
+// ===========================================================================
+// shared passes: what the stage-wise entry points (the public ABI) and the fused chain of cpx_compute_masks both do
+// ===========================================================================
+// The two chains must stay bit-identical, so what they both do is written ONCE, as one of the device functions below; the
+// fused chain's k_lab_stats_r and k_finish_f (below, with the chain's other kernels) call them too.  Three passes keep a
+// kernel of their own in each chain, for a measured reason that stands above the fused one: k_gather / k_gather_f,
+// k_count_labels + k_size_filter / k_count_labels_f, k_class_count / k_class_count_f.
+__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long ld_agent(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Label statistics visit RUNS, not pixels: a thread owns 8 consecutive pixels and calls f(label, first
+// linear index, run length, y, x of the first pixel) once per maximal run of one positive label on one image
+// row (instances are ~15 px wide, so this issues ~8x fewer atomics than one call per pixel; all updates are
+// integer min / max / add, so the results are identical).  Returns true if the thread saw a background pixel.
+#define RUN_PX 8
+#define GRID_RUN(lay, nT) dim3(cpx_cdiv(cpx_cdiv((lay).HW, RUN_PX), NTHR), (nT))
+template <typename F>
+__device__ __forceinline__ bool label_runs(const int (&lab)[RUN_PX], int base, int HW, int W, int limit, F &&f) {
+    bool bg = false;
+    int y = base / W, x = base - y * W;
+    int cur = 0, start = 0, sx = 0, sy = 0, n = 0;
+#pragma unroll
+    for (int i = 0; i < RUN_PX; ++i) {
+        int l = lab[i];
+        if (base + i < HW && l <= 0) bg = true;
+        if (l <= 0 || l >= limit) l = 0;
+        if (l != cur || x == 0) {                       // label change or a new image row: close the run
+            if (cur > 0) f(cur, start, n, sy, sx);
+            cur = l; start = base + i; sx = x; sy = y; n = 0;
+        }
+        ++n;
+        if (++x == W) { x = 0; ++y; }
+    }
+    if (cur > 0) f(cur, start, n, sy, sx);
+    return bg;
+}
+// the thread's RUN_PX labels of a map (pixels past its end: 0), as two 16-byte loads where the run is whole and aligned
+template <typename T>
+__device__ __forceinline__ void load_labels(const T *__restrict__ m, int base, int HW, int (&lab)[RUN_PX]) {
+    if (base + RUN_PX <= HW && sizeof(T) == 4 && (reinterpret_cast<size_t>(m + base) & 15) == 0) {
+        const int4 a = *reinterpret_cast<const int4 *>(m + base), b = *reinterpret_cast<const int4 *>(m + base + 4);
+        lab[0] = a.x; lab[1] = a.y; lab[2] = a.z; lab[3] = a.w; lab[4] = b.x; lab[5] = b.y; lab[6] = b.z; lab[7] = b.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < RUN_PX; ++i) lab[i] = base + i < HW ? (int)m[base + i] : 0;
+    }
+}
+__device__ __forceinline__ void store_labels(int32_t *__restrict__ dst, int base, int HW, const int (&lab)[RUN_PX]) {
+#pragma unroll
+    for (int i = 0; i < RUN_PX; ++i)
+        if (base + i < HW) dst[base + i] = lab[i];
+}
+// ... with every label l > 0 replaced by map(l) -- the previous stage's remap table, or 0 for a label that a filter removes --
+// and the run written back if that changed it
+template <typename M>
+__device__ __forceinline__ void load_labels_mapped(int32_t *__restrict__ m, int base, int HW, int (&lab)[RUN_PX], M &&map) {
+    load_labels(m, base, HW, lab);
+    bool changed = false;
+#pragma unroll
+    for (int i = 0; i < RUN_PX; ++i)
+        if (lab[i] > 0) { const int n = map(lab[i]); changed |= n != lab[i]; lab[i] = n; }
+    if (changed) store_labels(m, base, HW, lab);
+}
+// f over the label runs of the thread's pixels; copy_to: a verbatim copy of the map on the way (the hole fill's scratch plane)
+template <typename T, typename F>
+__device__ __forceinline__ bool for_label_runs(const T *__restrict__ m, int HW, int W, int limit, F &&f,
+                                               int32_t *__restrict__ copy_to = nullptr) {
+    const int base = (blockIdx.x * NTHR + threadIdx.x) * RUN_PX;
+    if (base >= HW) return false;
+    int lab[RUN_PX];
+    load_labels(m, base, HW, lab);
+    if (copy_to) store_labels(copy_to, base, HW, lab);
+    return label_runs(lab, base, HW, W, limit, f);
+}
+
+// Per-workgroup aggregation of per-label updates.  A label's table entries are 4-16 bytes apart, so the ~50 row runs of
+// each of a tile's ~80 labels all hit the same three or four cache lines, and the L2 serialises them (k_first: 13 us for a
+// pass that reads 2 MB).  A 256-slot LDS hash keyed by the label collects a workgroup's updates first (2 048 pixels =
+// 8 image rows see a few dozen labels); one global atomic per (label, workgroup) follows.  Integer min / max / add only,
+// so the tables end up identical.  lh_slot returns -1 when 8 probes find no slot: the caller then updates global memory.
+#define LH_SLOTS NTHR
+__device__ __forceinline__ int lh_slot(int *key, int lab) {
+    const unsigned h = ((unsigned)lab * 2654435761u) >> 24;
+#pragma unroll 1
+    for (int p = 0; p < 8; ++p) {
+        const int s = (int)((h + p) & (LH_SLOTS - 1));
+        const int old = atomicCAS(&key[s], 0, lab);
+        if (old == 0 || old == lab) return s;
+    }
+    return -1;
+}
+
+// per-label bbox / count / coordinate sums of a pixel pass, aggregated per workgroup in LDS (lh_slot).  A workgroup covers
+// 2 048 pixels, so its partial coordinate sums fit 32 bits (H, W <= 16 384).  WHAT: what the records need besides --
+#define LS_VMAX 1           // the largest label, into SC_VMAX
+#define LS_FIRST 2          // the first raster index per label
+struct LabStatsLds {
+    int key[LH_SLOTS], ymin[LH_SLOTS], xmin[LH_SLOTS], ymax[LH_SLOTS], xmax[LH_SLOTS], cnt[LH_SLOTS], first[LH_SLOTS];
+    unsigned sy[LH_SLOTS], sx[LH_SLOTS];
+    int vmax;
+};
+__device__ __forceinline__ void lab_stats_clear(LabStatsLds &L) {
+    const int i = threadIdx.x;
+    L.key[i] = 0; L.ymin[i] = 0x7FFFFFFF; L.xmin[i] = 0x7FFFFFFF; L.ymax[i] = -1; L.xmax[i] = -1; L.cnt[i] = 0;
+    L.first[i] = 0x7FFFFFFF; L.sy[i] = 0; L.sx[i] = 0;
+    if (i == 0) L.vmax = 0;
+    __syncthreads();
+}
+// one run: n pixels of `lab` from (y, x), linear index idx
+template <int WHAT>
+__device__ __forceinline__ void lab_stats_add(LabStatsLds &L, const PPLayout &lay, void *ws, int lab, int idx, int n, int y, int x) {
+    const unsigned long long ay = (unsigned long long)n * y;
+    const unsigned long long ax = (unsigned long long)n * x + (unsigned long long)(n * (n - 1) / 2);
+    const int sl = lh_slot(L.key, lab);
+    if (sl >= 0) {
+        atomicMin(&L.ymin[sl], y); atomicMin(&L.xmin[sl], x); atomicMax(&L.ymax[sl], y); atomicMax(&L.xmax[sl], x + n - 1);
+        atomicAdd(&L.cnt[sl], n);
+        atomicAdd(&L.sy[sl], (unsigned)ay); atomicAdd(&L.sx[sl], (unsigned)ax);
+        if (WHAT & LS_FIRST) atomicMin(&L.first[sl], idx);
+    } else {
+        int *bb = WS(int, off_bbox) + 4 * lab;
+        atomicMin(&bb[0], y); atomicMin(&bb[1], x); atomicMax(&bb[2], y); atomicMax(&bb[3], x + n - 1);
+        atomicAdd(&WS(int, off_cnt)[lab], n);
+        atomicAdd(&WS(unsigned long long, off_sumy)[lab], ay); atomicAdd(&WS(unsigned long long, off_sumx)[lab], ax);
+        if (WHAT & LS_FIRST) atomicMin(&WS(int, off_first)[lab], idx);
+    }
+}
+// the workgroup's slots into the tables; vmax: the largest label this thread added (LS_VMAX)
+template <int WHAT>
+__device__ __forceinline__ void lab_stats_flush(LabStatsLds &L, const PPLayout &lay, void *ws, int vmax) {
+    const int i = threadIdx.x;
+    if ((WHAT & LS_VMAX) && vmax > 0) atomicMax(&L.vmax, vmax);
+    __syncthreads();
+    const int lab = L.key[i];
+    if (lab) {
+        int *bb = WS(int, off_bbox) + 4 * lab;
+        atomicMin(&bb[0], L.ymin[i]); atomicMin(&bb[1], L.xmin[i]); atomicMax(&bb[2], L.ymax[i]); atomicMax(&bb[3], L.xmax[i]);
+        atomicAdd(&WS(int, off_cnt)[lab], L.cnt[i]);
+        atomicAdd(&WS(unsigned long long, off_sumy)[lab], (unsigned long long)L.sy[i]);
+        atomicAdd(&WS(unsigned long long, off_sumx)[lab], (unsigned long long)L.sx[i]);
+        if (WHAT & LS_FIRST) atomicMin(&WS(int, off_first)[lab], L.first[i]);
+    }
+    if ((WHAT & LS_VMAX) && i == 0 && L.vmax > 0) atomicMax(&WS(int, off_scal)[SC_VMAX], L.vmax);
+}
+
+// The light per-tile step behind a pixel pass ("tail": rank the labels, apply the size filter, write the records) is the
+// SAME kernel launched a second time with tail = 1 on a (1, nT) grid.  A first version let the last workgroup of the pixel
+// pass run it (a ticket behind __threadfence): bit-identical, 16 launches -- and 1 181 us per batch against 347 us, because an
+// agent-scope release on this part writes back the XCD's whole L2 (the eight L2s are not coherent with each other) and every
+// workgroup of every pass paid for one: k_fill 689 us, the class vote 139 us (profiles/r04_post_fused_first_build.csv).
+// A launch boundary is the cheap device-wide release here (~5 us); what the fused chain keeps is everything else.
+#define TAIL_LDS 1024        // up to this many labels the tail ranks by comparing every label with every other through an LDS copy (the bench's tiles: ~80)
+// remap[v] = 1 + #{kept j : first[j] < first[v]} for kept v in 1..vmax, 0 otherwise (fastremap.renumber on the map with the
+// removed labels zeroed); *nlab = number of kept labels.  One workgroup (NTHR threads); `removed(v)` decides per label.
+// More labels than TAIL_LDS (dense 512 / 1024-px tiles) are ranked by position, not by comparison: first[] are distinct pixel indices, so a
+// bitmap of the tile with the kept labels' first pixels set, the prefix counts of its words, and rank = prefix + popcount below the bit --
+// O(HW / 32 + n) for the workgroup instead of O(n^2).  (Until round 5: every label against every other, through LDS chunks above 6 144
+// labels: 8 649 labels in a 1024-px tile cost 3.7 ms per call, six calls per chain = 22 of the chain's 24.5 ms, tools/chain_size_scan.py.)
+// `bits`: 2 x cdiv(hw, 32) words of the tile's workspace (off_rankbits); `scratch`: the stage's unused rank table.
+template <typename R>
+__device__ __forceinline__ void tail_rank(int vmax, const int *first, int *remap, int *nlab_slot, int *scratch, unsigned *bits, int hw, R &&removed) {
+    __shared__ int s_first[TAIL_LDS + 1];
+    __shared__ int s_part[NTHR];
+    __shared__ int s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    int kept = 0;
+    if (vmax <= TAIL_LDS) {
+        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
+            int f = ld_agent(&first[v]);
+            if (f != 0x7FFFFFFF && removed(v)) f = 0x7FFFFFFF;
+            s_first[v] = f;
+        }
+        __syncthreads();
+        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
+            const int f = s_first[v];
+            if (f == 0x7FFFFFFF) { remap[v] = 0; continue; }
+            int r = 1;
+            for (int j = 1; j <= vmax; ++j) r += s_first[j] < f;
+            remap[v] = r;
+            ++kept;
+        }
+    } else {
+        const int nw = (hw + 31) >> 5, cw = (nw + NTHR - 1) / NTHR;        // words; words per thread (one contiguous chunk each)
+        unsigned *pref = bits + nw;
+        for (int w = threadIdx.x; w < nw; w += NTHR) bits[w] = 0u;
+        __threadfence_block();
+        __syncthreads();
+        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
+            int f = ld_agent(&first[v]);
+            if (f != 0x7FFFFFFF && removed(v)) f = 0x7FFFFFFF;
+            scratch[v] = f;                              // read back by this thread only
+            if (f != 0x7FFFFFFF) atomicOr(&bits[f >> 5], 1u << (f & 31));
+        }
+        __threadfence_block();
+        __syncthreads();
+        int run = 0;
+        for (int w = threadIdx.x * cw; w < min((int)(threadIdx.x + 1) * cw, nw); ++w) {
+            pref[w] = (unsigned)run;                     // kept first-pixels in this thread's chunk before word w
+            run += __popc(__hip_atomic_load(&bits[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+        s_part[threadIdx.x] = run;
+        __threadfence_block();
+        __syncthreads();
+        for (int o = 1; o < NTHR; o <<= 1) {             // inclusive scan of the chunk totals
+            const int tv = (int)threadIdx.x >= o ? s_part[threadIdx.x - o] : 0;
+            __syncthreads();
+            s_part[threadIdx.x] += tv;
+            __syncthreads();
+        }
+        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
+            const int f = scratch[v];
+            if (f == 0x7FFFFFFF) { remap[v] = 0; continue; }
+            const int w = f >> 5, t = w / cw;
+            const unsigned below = __hip_atomic_load(&bits[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ((1u << (f & 31)) - 1u);
+            remap[v] = 1 + (t > 0 ? s_part[t - 1] : 0) + (int)__hip_atomic_load(&pref[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + __popc(below);
+            ++kept;
+        }
+    }
+    if (kept) atomicAdd(&s_n, kept);
+    __syncthreads();
+    if (threadIdx.x == 0) *nlab_slot = s_n;
+}
+
+// the record of label v (n pixels) from the statistics tables; cls: its class, from the caller's source
+__device__ __forceinline__ cpx_record make_record(int v, int n, int cls, const PPLayout &lay, void *ws) {
+    const int *bb = WS(int, off_bbox) + 4 * v;
+    cpx_record r;
+    r.tile = blockIdx.y; r.label = v; r.cls = cls; r.area = n;
+    r.y0 = bb[0]; r.x0 = bb[1]; r.y1 = bb[2] + 1; r.x1 = bb[3] + 1;
+    r.sum_y = (int64_t)WS(unsigned long long, off_sumy)[v];
+    r.sum_x = (int64_t)WS(unsigned long long, off_sumx)[v];
+    return r;
+}
+
 // ---------------------------------------------------------------------------
 // a12  get_masks
 // ---------------------------------------------------------------------------
-__global__ void k_zero_i32(int *p, size_t per_tile_stride_bytes, size_t off, int n) {
-    int idx = blockIdx.x * NTHR + threadIdx.x;
-    if (idx >= n) return;
-    ((int *)((char *)p + (size_t)blockIdx.y * per_tile_stride_bytes + off))[idx] = 0;
-}
-
 __global__ void k_hist(const int32_t *__restrict__ p_final, PPLayout lay, void *ws) {
     int idx = blockIdx.x * NTHR + threadIdx.x;
     if (idx >= lay.HW) return;
@@ -484,70 +712,6 @@ __global__ void __launch_bounds__(NTHR) k_seed_grow(PPLayout lay, void *ws) {
     }
 }
 
-// Label statistics visit RUNS, not pixels: a thread owns 8 consecutive pixels and calls f(label, first
-// linear index, run length, y, x of the first pixel) once per maximal run of one positive label on one image
-// row (instances are ~15 px wide, so this issues ~8x fewer atomics than one call per pixel; all updates are
-// integer min / max / add, so the results are identical).  Returns true if the thread saw a background pixel.
-#define RUN_PX 8
-#define GRID_RUN(lay, nT) dim3(cpx_cdiv(cpx_cdiv((lay).HW, RUN_PX), NTHR), (nT))
-template <typename F>
-__device__ __forceinline__ bool label_runs(const int (&lab)[RUN_PX], int base, int HW, int W, int limit, F &&f) {
-    bool bg = false;
-    int y = base / W, x = base - y * W;
-    int cur = 0, start = 0, sx = 0, sy = 0, n = 0;
-#pragma unroll
-    for (int i = 0; i < RUN_PX; ++i) {
-        int l = lab[i];
-        if (base + i < HW && l <= 0) bg = true;
-        if (l <= 0 || l >= limit) l = 0;
-        if (l != cur || x == 0) {                       // label change or a new image row: close the run
-            if (cur > 0) f(cur, start, n, sy, sx);
-            cur = l; start = base + i; sx = x; sy = y; n = 0;
-        }
-        ++n;
-        if (++x == W) { x = 0; ++y; }
-    }
-    if (cur > 0) f(cur, start, n, sy, sx);
-    return bg;
-}
-template <typename T, typename F>
-__device__ __forceinline__ bool for_label_runs(const T *__restrict__ m, int HW, int W, int limit, F &&f,
-                                               int32_t *__restrict__ copy_to = nullptr) {
-    const int base = (blockIdx.x * NTHR + threadIdx.x) * RUN_PX;
-    if (base >= HW) return false;
-    int lab[RUN_PX];
-    if (base + RUN_PX <= HW && sizeof(T) == 4 && (reinterpret_cast<size_t>(m + base) & 15) == 0) {
-        const int4 a = *reinterpret_cast<const int4 *>(m + base), b = *reinterpret_cast<const int4 *>(m + base + 4);
-        lab[0] = a.x; lab[1] = a.y; lab[2] = a.z; lab[3] = a.w; lab[4] = b.x; lab[5] = b.y; lab[6] = b.z; lab[7] = b.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < RUN_PX; ++i) lab[i] = base + i < HW ? (int)m[base + i] : 0;
-    }
-    if (copy_to) {                                       // a verbatim copy of the map on the way (fill-holes scratch)
-#pragma unroll
-        for (int i = 0; i < RUN_PX; ++i)
-            if (base + i < HW) copy_to[base + i] = lab[i];
-    }
-    return label_runs(lab, base, HW, W, limit, f);
-}
-
-// Per-workgroup aggregation of per-label updates.  A label's table entries are 4-16 bytes apart, so the ~50 row runs of
-// each of a tile's ~80 labels all hit the same three or four cache lines, and the L2 serialises them (k_first: 13 us for a
-// pass that reads 2 MB).  A 256-slot LDS hash keyed by the label collects a workgroup's updates first (2 048 pixels =
-// 8 image rows see a few dozen labels); one global atomic per (label, workgroup) follows.  Integer min / max / add only,
-// so the tables end up identical.  lh_slot returns -1 when 8 probes find no slot: the caller then updates global memory.
-#define LH_SLOTS NTHR
-__device__ __forceinline__ int lh_slot(int *key, int lab) {
-    const unsigned h = ((unsigned)lab * 2654435761u) >> 24;
-#pragma unroll 1
-    for (int p = 0; p < 8; ++p) {
-        const int s = (int)((h + p) & (LH_SLOTS - 1));
-        const int old = atomicCAS(&key[s], 0, lab);
-        if (old == 0 || old == lab) return s;
-    }
-    return -1;
-}
-
 // label gather + per-label pixel count (label 0 not counted)
 __global__ void k_gather(const int32_t *__restrict__ p_final, int32_t *__restrict__ masks,
                          PPLayout lay, void *ws) {
@@ -619,18 +783,9 @@ __global__ void k_first(int32_t *__restrict__ masks, PPLayout lay, void *ws) {
     const int base = (blockIdx.x * NTHR + threadIdx.x) * RUN_PX;
     if (base < lay.HW) {
         int lab[RUN_PX];
-        bool changed = false;
         const int *flag = WS(int, off_flag);
-#pragma unroll
-        for (int i = 0; i < RUN_PX; ++i) {
-            lab[i] = base + i < lay.HW ? m[base + i] : 0;
-            if (APPLY_FLAGS && lab[i] > 0 && flag[lab[i]]) { lab[i] = 0; changed = true; }
-        }
-        if (APPLY_FLAGS && changed) {
-#pragma unroll
-            for (int i = 0; i < RUN_PX; ++i)
-                if (base + i < lay.HW) m[base + i] = lab[i];
-        }
+        if constexpr (APPLY_FLAGS) load_labels_mapped(m, base, lay.HW, lab, [&](int l) { return flag[l] ? 0 : l; });
+        else load_labels(m, base, lay.HW, lab);
         label_runs(lab, base, lay.HW, lay.W, 0x7FFFFFFF, [&](int l, int idx, int, int, int) {
             const int sl = lh_slot(key, l);
             if (sl >= 0) atomicMin(&vmin[sl], idx); else atomicMin(&first[l], idx);
@@ -684,101 +839,37 @@ __global__ void k_copy_scalar(int dst, int src, int zero_slot, PPLayout lay, voi
 // ---------------------------------------------------------------------------
 // a13  flow-error filter
 // ---------------------------------------------------------------------------
-// per-label bbox / count / coordinate sums (+ first raster index and the largest label for the records pass), aggregated
-// per workgroup in LDS (lh_slot).  A workgroup covers 2 048 pixels, so its partial coordinate sums fit 32 bits
-// (H, W <= 16 384).
-struct LabStatsLds {
-    int key[LH_SLOTS], ymin[LH_SLOTS], xmin[LH_SLOTS], ymax[LH_SLOTS], xmax[LH_SLOTS], cnt[LH_SLOTS], first[LH_SLOTS];
-    unsigned sy[LH_SLOTS], sx[LH_SLOTS];
-    int vmax;
-};
-template <typename T, bool REC>
+// per-label bbox / count / coordinate sums of a map (+ WHAT, for the records pass); copy_to: see for_label_runs
+template <typename T, int WHAT>
 __device__ __forceinline__ void lab_stats_pass(const T *__restrict__ m, int limit, LabStatsLds &L, const PPLayout &lay, void *ws,
                                                int32_t *copy_to = nullptr) {
-    const int i = threadIdx.x;
-    L.key[i] = 0; L.ymin[i] = 0x7FFFFFFF; L.xmin[i] = 0x7FFFFFFF; L.ymax[i] = -1; L.xmax[i] = -1; L.cnt[i] = 0;
-    L.first[i] = 0x7FFFFFFF; L.sy[i] = 0; L.sx[i] = 0;
-    if (i == 0) L.vmax = 0;
-    __syncthreads();
-    int *bbox = WS(int, off_bbox), *cnt = WS(int, off_cnt), *first = WS(int, off_first), *scal = WS(int, off_scal);
-    unsigned long long *sumy = WS(unsigned long long, off_sumy), *sumx = WS(unsigned long long, off_sumx);
+    lab_stats_clear(L);
     int vmax = 0;
     for_label_runs(m, lay.HW, lay.W, limit, [&](int lab, int idx, int n, int y, int x) {
-        const unsigned long long ay = (unsigned long long)n * y;
-        const unsigned long long ax = (unsigned long long)n * x + (unsigned long long)(n * (n - 1) / 2);
-        const int sl = lh_slot(L.key, lab);
-        if (sl >= 0) {
-            atomicMin(&L.ymin[sl], y); atomicMin(&L.xmin[sl], x); atomicMax(&L.ymax[sl], y); atomicMax(&L.xmax[sl], x + n - 1);
-            atomicAdd(&L.cnt[sl], n);
-            atomicAdd(&L.sy[sl], (unsigned)ay); atomicAdd(&L.sx[sl], (unsigned)ax);
-            if (REC) atomicMin(&L.first[sl], idx);
-        } else {
-            int *bb = bbox + 4 * lab;
-            atomicMin(&bb[0], y); atomicMin(&bb[1], x); atomicMax(&bb[2], y); atomicMax(&bb[3], x + n - 1);
-            atomicAdd(&cnt[lab], n);
-            atomicAdd(&sumy[lab], ay); atomicAdd(&sumx[lab], ax);
-            if (REC) atomicMin(&first[lab], idx);
-        }
+        lab_stats_add<WHAT>(L, lay, ws, lab, idx, n, y, x);
         vmax = max(vmax, lab);
     }, copy_to);
-    if (REC && vmax > 0) atomicMax(&L.vmax, vmax);
-    __syncthreads();
-    const int lab = L.key[i];
-    if (lab) {
-        int *bb = bbox + 4 * lab;
-        atomicMin(&bb[0], L.ymin[i]); atomicMin(&bb[1], L.xmin[i]); atomicMax(&bb[2], L.ymax[i]); atomicMax(&bb[3], L.xmax[i]);
-        atomicAdd(&cnt[lab], L.cnt[i]);
-        atomicAdd(&sumy[lab], (unsigned long long)L.sy[i]); atomicAdd(&sumx[lab], (unsigned long long)L.sx[i]);
-        if (REC) atomicMin(&first[lab], L.first[i]);
-    }
-    if (REC && i == 0 && L.vmax > 0) atomicMax(&scal[SC_VMAX], L.vmax);
+    lab_stats_flush<WHAT>(L, lay, ws, vmax);
 }
 // copy_to_tmp: also copy the map into the per-tile scratch plane the hole fill reads (was a kernel of its own)
 __global__ void k_lab_stats(const int32_t *__restrict__ masks, int copy_to_tmp, PPLayout lay, void *ws) {
     __shared__ LabStatsLds L;
-    lab_stats_pass<int32_t, false>(masks + (size_t)blockIdx.y * lay.HW, 0x7FFFFFFF, L, lay, ws,
-                                   copy_to_tmp ? WS(int32_t, off_tmp) : nullptr);
+    lab_stats_pass<int32_t, 0>(masks + (size_t)blockIdx.y * lay.HW, 0x7FFFFFFF, L, lay, ws,
+                               copy_to_tmp ? WS(int32_t, off_tmp) : nullptr);
 }
-
-__global__ void k_init_stats(PPLayout lay, void *ws) {
-    int v = blockIdx.x * NTHR + threadIdx.x;
-    if (v >= lay.L) return;
-    int *bb = WS(int, off_bbox) + 4 * v;
-    bb[0] = 0x7FFFFFFF; bb[1] = 0x7FFFFFFF; bb[2] = -1; bb[3] = -1;
-    WS(int, off_cnt)[v] = 0;
-    WS(unsigned long long, off_sumy)[v] = 0;
-    WS(unsigned long long, off_sumx)[v] = 0;
-    WS(unsigned long long, off_d2)[v] = 0xFFFFFFFFFFFFFFFFull;
-    WS(int, off_center)[v] = 0x7FFFFFFF;
-    WS(int, off_flag)[v] = 0;
-    WS(int, off_first)[v] = 0x7FFFFFFF;
-}
-
-// one launch for everything a stage needs initialised (was 3-5 k_fill_i32 / k_init_stats / k_zero_f64 launches):
-//   PPI_SCAL  the PP_NSCAL scalars = 0          PPI_STATS  the per-label tables of k_init_stats
+// one launch for everything a stage needs initialised (was 3-5 fill launches):
+//   PPI_SCAL  the PP_NSCAL scalars = 0          PPI_STATS  the per-label tables (pp_init_stats_entry)
 //   PPI_PAD   h1 and M1 (padded frames) = 0     PPI_T      the two fp64 diffusion planes = 0
-//   PPI_CLS   the class-vote table = 0          PPI_NLAB   scalar SC_NLAB = 0 only
+//   PPI_CLS   the class-vote table = 0
 #define PPI_SCAL 1
 #define PPI_STATS 2
 #define PPI_PAD 4
 #define PPI_T 8
 #define PPI_CLS 16
-#define PPI_NLAB 32
 __global__ void k_pp_init(unsigned what, PPLayout lay, void *ws) {
     const int i = blockIdx.x * NTHR + threadIdx.x;
     if ((what & PPI_SCAL) && i < PP_NSCAL) WS(int, off_scal)[i] = 0;
-    if ((what & PPI_NLAB) && i == 0) WS(int, off_scal)[SC_NLAB] = 0;
-    if ((what & PPI_STATS) && i < lay.L) {
-        int *bb = WS(int, off_bbox) + 4 * i;
-        bb[0] = 0x7FFFFFFF; bb[1] = 0x7FFFFFFF; bb[2] = -1; bb[3] = -1;
-        WS(int, off_cnt)[i] = 0;
-        WS(unsigned long long, off_sumy)[i] = 0;
-        WS(unsigned long long, off_sumx)[i] = 0;
-        WS(unsigned long long, off_d2)[i] = 0xFFFFFFFFFFFFFFFFull;
-        WS(int, off_center)[i] = 0x7FFFFFFF;
-        WS(int, off_flag)[i] = 0;
-        WS(int, off_first)[i] = 0x7FFFFFFF;
-    }
+    if ((what & PPI_STATS) && i < lay.L) pp_init_stats_entry((char *)ws + (size_t)blockIdx.y * lay.per_tile, lay, 0, i);
     if ((what & PPI_PAD) && i < lay.HWp) { WS(int, off_h1)[i] = 0; WS(int, off_M1)[i] = 0; }
     if ((what & PPI_T) && i < 2 * lay.THW) WS(double, off_T)[i] = 0.0;
     if ((what & PPI_CLS) && i < lay.L * PP_MAXCLS) WS(int, off_cls)[i] = 0;
@@ -1122,12 +1213,6 @@ __global__ void k_zero_flagged(int32_t *__restrict__ masks, PPLayout lay, void *
     size_t t = blockIdx.y;
     int lab = masks[t * lay.HW + idx];
     if (lab > 0 && WS(int, off_flag)[lab]) masks[t * lay.HW + idx] = 0;
-}
-
-__global__ void k_zero_f64(size_t off, int n, PPLayout lay, void *ws) {
-    int idx = blockIdx.x * NTHR + threadIdx.x;
-    if (idx >= n) return;
-    ((double *)((char *)ws + (size_t)blockIdx.y * lay.per_tile + off))[idx] = 0.0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1558,27 +1643,19 @@ __global__ void k_to_u16(const int32_t *__restrict__ masks, uint16_t *__restrict
 __global__ void k_rec_stats(const uint16_t *__restrict__ masks, int32_t *__restrict__ counts, PPLayout lay, void *ws) {
     __shared__ LabStatsLds L;
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[blockIdx.y] = 0;      // k_rec_write raises it with atomicMax
-    lab_stats_pass<uint16_t, true>(masks + (size_t)blockIdx.y * lay.HW, lay.L, L, lay, ws);
+    lab_stats_pass<uint16_t, LS_VMAX | LS_FIRST>(masks + (size_t)blockIdx.y * lay.HW, lay.L, L, lay, ws);
 }
 
+// records are emitted at slot label - 1 (labels are contiguous after the renumbering); counts[tile] = the largest label.
+// The class of a record is the class map's at the label's first pixel.
 __global__ void k_rec_write(const uint8_t *__restrict__ cm, int max_rec, cpx_record *__restrict__ rec,
                             int32_t *__restrict__ counts, PPLayout lay, void *ws) {
     int v = blockIdx.x * NTHR + threadIdx.x + 1;
     if (v >= lay.L) return;
     int n = WS(int, off_cnt)[v];
     if (n <= 0) return;
-    // records are emitted at slot label-1 (labels are contiguous after renumber);
-    // counts[tile] = max label
-    if (v - 1 < max_rec) {
-        cpx_record r;
-        const int *bb = WS(int, off_bbox) + 4 * v;
-        r.tile = blockIdx.y; r.label = v;
-        r.cls = cm ? cm[(size_t)blockIdx.y * lay.HW + WS(int, off_first)[v]] : 0;
-        r.area = n; r.y0 = bb[0]; r.x0 = bb[1]; r.y1 = bb[2] + 1; r.x1 = bb[3] + 1;
-        r.sum_y = (int64_t)WS(unsigned long long, off_sumy)[v];
-        r.sum_x = (int64_t)WS(unsigned long long, off_sumx)[v];
-        rec[(size_t)blockIdx.y * max_rec + v - 1] = r;
-    }
+    if (v - 1 < max_rec)
+        rec[(size_t)blockIdx.y * max_rec + v - 1] = make_record(v, n, cm ? cm[(size_t)blockIdx.y * lay.HW + WS(int, off_first)[v]] : 0, lay, ws);
     atomicMax(&counts[blockIdx.y], v);
 }
 
@@ -1595,89 +1672,16 @@ __global__ void k_rec_write(const uint8_t *__restrict__ cm, int max_rec, cpx_rec
 //     k_first<true> are gone too (the counting pass collects the first raster index itself);
 //   * the Euler loop feeds the histogram (k_hist); the size filter's flags and the ranks are one light launch, not two;
 //   * the class map, the uint16 id map and the per-cell statistics of cpx_instance_records leave in one final pass.
-// Results are bit-identical to the stage-wise entry points (same arithmetic, same tie rules; tests/test_gpu_postproc.py).
-__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long ld_agent(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// The light per-tile step behind a pixel pass ("tail": rank the labels, apply the size filter, write the records) is the
-// SAME kernel launched a second time with tail = 1 on a (1, nT) grid.  A first version let the last workgroup of the pixel
-// pass run it (a ticket behind __threadfence): bit-identical, 16 launches -- and 1 181 us per batch against 347 us, because an
-// agent-scope release on this part writes back the XCD's whole L2 (the eight L2s are not coherent with each other) and every
-// workgroup of every pass paid for one: k_fill 689 us, the class vote 139 us (profiles/r04_post_fused_first_build.csv).
-// A launch boundary is the cheap device-wide release here (~5 us); what the fused chain keeps is everything else.
-#define TAIL_LDS 1024        // up to this many labels the tail ranks by comparing every label with every other through an LDS copy (the bench's tiles: ~80)
-// remap[v] = 1 + #{kept j : first[j] < first[v]} for kept v in 1..vmax, 0 otherwise (fastremap.renumber on the map with the
-// removed labels zeroed); *nlab = number of kept labels.  One workgroup (NTHR threads); `removed(v)` decides per label.
-// More labels than TAIL_LDS (dense 512 / 1024-px tiles) are ranked by position, not by comparison: first[] are distinct pixel indices, so a
-// bitmap of the tile with the kept labels' first pixels set, the prefix counts of its words, and rank = prefix + popcount below the bit --
-// O(HW / 32 + n) for the workgroup instead of O(n^2).  (Until round 5: every label against every other, through LDS chunks above 6 144
-// labels: 8 649 labels in a 1024-px tile cost 3.7 ms per call, six calls per chain = 22 of the chain's 24.5 ms, tools/chain_size_scan.py.)
-// `bits`: 2 x cdiv(hw, 32) words of the tile's workspace (off_rankbits); `scratch`: the stage's unused rank table.
-template <typename R>
-__device__ __forceinline__ void tail_rank(int vmax, const int *first, int *remap, int *nlab_slot, int *scratch, unsigned *bits, int hw, R &&removed) {
-    __shared__ int s_first[TAIL_LDS + 1];
-    __shared__ int s_part[NTHR];
-    __shared__ int s_n;
-    if (threadIdx.x == 0) s_n = 0;
-    int kept = 0;
-    if (vmax <= TAIL_LDS) {
-        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
-            int f = ld_agent(&first[v]);
-            if (f != 0x7FFFFFFF && removed(v)) f = 0x7FFFFFFF;
-            s_first[v] = f;
-        }
-        __syncthreads();
-        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
-            const int f = s_first[v];
-            if (f == 0x7FFFFFFF) { remap[v] = 0; continue; }
-            int r = 1;
-            for (int j = 1; j <= vmax; ++j) r += s_first[j] < f;
-            remap[v] = r;
-            ++kept;
-        }
-    } else {
-        const int nw = (hw + 31) >> 5, cw = (nw + NTHR - 1) / NTHR;        // words; words per thread (one contiguous chunk each)
-        unsigned *pref = bits + nw;
-        for (int w = threadIdx.x; w < nw; w += NTHR) bits[w] = 0u;
-        __threadfence_block();
-        __syncthreads();
-        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
-            int f = ld_agent(&first[v]);
-            if (f != 0x7FFFFFFF && removed(v)) f = 0x7FFFFFFF;
-            scratch[v] = f;                              // read back by this thread only
-            if (f != 0x7FFFFFFF) atomicOr(&bits[f >> 5], 1u << (f & 31));
-        }
-        __threadfence_block();
-        __syncthreads();
-        int run = 0;
-        for (int w = threadIdx.x * cw; w < min((int)(threadIdx.x + 1) * cw, nw); ++w) {
-            pref[w] = (unsigned)run;                     // kept first-pixels in this thread's chunk before word w
-            run += __popc(__hip_atomic_load(&bits[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        }
-        s_part[threadIdx.x] = run;
-        __threadfence_block();
-        __syncthreads();
-        for (int o = 1; o < NTHR; o <<= 1) {             // inclusive scan of the chunk totals
-            const int tv = (int)threadIdx.x >= o ? s_part[threadIdx.x - o] : 0;
-            __syncthreads();
-            s_part[threadIdx.x] += tv;
-            __syncthreads();
-        }
-        for (int v = 1 + (int)threadIdx.x; v <= vmax; v += NTHR) {
-            const int f = scratch[v];
-            if (f == 0x7FFFFFFF) { remap[v] = 0; continue; }
-            const int w = f >> 5, t = w / cw;
-            const unsigned below = __hip_atomic_load(&bits[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ((1u << (f & 31)) - 1u);
-            remap[v] = 1 + (t > 0 ? s_part[t - 1] : 0) + (int)__hip_atomic_load(&pref[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + __popc(below);
-            ++kept;
-        }
-    }
-    if (kept) atomicAdd(&s_n, kept);
-    __syncthreads();
-    if (threadIdx.x == 0) *nlab_slot = s_n;
-}
-
+// Results are bit-identical to the stage-wise entry points (tests/test_gpu_postproc.py); what both chains do is one body, see
+// "shared passes" above.  The chain's kernels stay together here, in the order they run: with each of them next to its stage-wise
+// counterpart instead -- the same instructions, only placed apart in the library -- the chain lasted 0.9 us longer per 8-tile batch
+// and k_gather_f's tail 0.15 us (profiles/postproc_one_body_ab.txt).
 // a12 tail: label gather + per-label count + first raster index; the last workgroup removes the too-big labels and ranks
 // (k_gather + k_big_first + k_renumber_rank; the relabel rides on k_lab_stats_r)
+// (Its own body, not one template with the stage-wise kernel: as one template -- with the tail in it, and with the tail in a
+// kernel of its own -- the chain's light steps lasted 0.2 us longer per launch, 5.35 -> 5.55 and 7.12 -> 7.30 us, and the vote's
+// pass 5.6 -> 5.75 us in two sessions of three.  Those forms also stood apart from the chain's other kernels, which costs by
+// itself, see above; the two were not told apart.  profiles/postproc_one_body_ab.txt)
 __global__ void __launch_bounds__(NTHR) k_gather_f(const int32_t *__restrict__ p_final, int32_t *__restrict__ masks, double big,
                                                    int tail, PPLayout lay, void *ws) {
     __shared__ int key[LH_SLOTS], vadd[LH_SLOTS], vmin[LH_SLOTS];
@@ -1719,79 +1723,34 @@ __global__ void __launch_bounds__(NTHR) k_gather_f(const int32_t *__restrict__ p
     if (key[threadIdx.x]) { atomicAdd(&cnt[key[threadIdx.x]], vadd[threadIdx.x]); atomicMin(&first[key[threadIdx.x]], vmin[threadIdx.x]); }
 }
 
-// loads RUN_PX labels of the map; with `remap` the labels are first mapped through the previous stage's table and written back
-__device__ __forceinline__ void load_labels(int32_t *__restrict__ m, int base, int HW, const int *__restrict__ remap,
-                                            int32_t *__restrict__ copy_to, int (&lab)[RUN_PX]) {
-    if (base + RUN_PX <= HW && (reinterpret_cast<size_t>(m + base) & 15) == 0) {
-        const int4 a = *reinterpret_cast<const int4 *>(m + base), b = *reinterpret_cast<const int4 *>(m + base + 4);
-        lab[0] = a.x; lab[1] = a.y; lab[2] = a.z; lab[3] = a.w; lab[4] = b.x; lab[5] = b.y; lab[6] = b.z; lab[7] = b.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < RUN_PX; ++i) lab[i] = base + i < HW ? m[base + i] : 0;
-    }
-    if (remap) {
-        bool changed = false;
-#pragma unroll
-        for (int i = 0; i < RUN_PX; ++i)
-            if (lab[i] > 0) { const int n = remap[lab[i]]; changed |= n != lab[i]; lab[i] = n; }
-        if (changed) {
-#pragma unroll
-            for (int i = 0; i < RUN_PX; ++i)
-                if (base + i < HW) m[base + i] = lab[i];
-        }
-    }
-    if (copy_to) {
-#pragma unroll
-        for (int i = 0; i < RUN_PX; ++i)
-            if (base + i < HW) copy_to[base + i] = lab[i];
-    }
-}
 
-// k_relabel of the previous stage (through `prev`'s remap table) + k_lab_stats of this one (+ the pre-fill copy)
+// the fused chain's form: k_relabel of the previous stage on the way (labels through `prev`'s remap table, written back; its
+// label count becomes this stage's), then the same statistics
 __global__ void __launch_bounds__(NTHR) k_lab_stats_r(int32_t *__restrict__ masks, int copy_to_tmp, PPLayout prev, PPLayout lay, void *ws) {
     __shared__ LabStatsLds L;
-    const int i = threadIdx.x;
-    L.key[i] = 0; L.ymin[i] = 0x7FFFFFFF; L.xmin[i] = 0x7FFFFFFF; L.ymax[i] = -1; L.xmax[i] = -1; L.cnt[i] = 0;
-    L.first[i] = 0x7FFFFFFF; L.sy[i] = 0; L.sx[i] = 0;
-    __syncthreads();
+    lab_stats_clear(L);
     char *tb = (char *)ws + (size_t)blockIdx.y * lay.per_tile;
-    if (blockIdx.x == 0 && i == 0) WS(int, off_scal)[SC_NLAB] = ((const int *)(tb + prev.off_scal))[SC_NLAB];
-    int *bbox = WS(int, off_bbox), *cnt = WS(int, off_cnt);
-    unsigned long long *sumy = WS(unsigned long long, off_sumy), *sumx = WS(unsigned long long, off_sumx);
-    int32_t *m = masks + (size_t)blockIdx.y * lay.HW;
-    const int base = (blockIdx.x * NTHR + i) * RUN_PX;
+    if (blockIdx.x == 0 && threadIdx.x == 0) WS(int, off_scal)[SC_NLAB] = ((const int *)(tb + prev.off_scal))[SC_NLAB];
+    const int *remap = (const int *)(tb + prev.off_remap);
+    const int base = (blockIdx.x * NTHR + threadIdx.x) * RUN_PX;
     if (base < lay.HW) {
         int lab[RUN_PX];
-        load_labels(m, base, lay.HW, (const int *)(tb + prev.off_remap), copy_to_tmp ? WS(int32_t, off_tmp) : nullptr, lab);
-        label_runs(lab, base, lay.HW, lay.W, 0x7FFFFFFF, [&](int l, int, int n, int y, int x) {
-            const unsigned long long ay = (unsigned long long)n * y;
-            const unsigned long long ax = (unsigned long long)n * x + (unsigned long long)(n * (n - 1) / 2);
-            const int sl = lh_slot(L.key, l);
-            if (sl >= 0) {
-                atomicMin(&L.ymin[sl], y); atomicMin(&L.xmin[sl], x); atomicMax(&L.ymax[sl], y); atomicMax(&L.xmax[sl], x + n - 1);
-                atomicAdd(&L.cnt[sl], n);
-                atomicAdd(&L.sy[sl], (unsigned)ay); atomicAdd(&L.sx[sl], (unsigned)ax);
-            } else {
-                int *bb = bbox + 4 * l;
-                atomicMin(&bb[0], y); atomicMin(&bb[1], x); atomicMax(&bb[2], y); atomicMax(&bb[3], x + n - 1);
-                atomicAdd(&cnt[l], n);
-                atomicAdd(&sumy[l], ay); atomicAdd(&sumx[l], ax);
-            }
-        });
+        load_labels_mapped(masks + (size_t)blockIdx.y * lay.HW, base, lay.HW, lab, [&](int l) { return remap[l]; });
+        if (copy_to_tmp) store_labels(WS(int32_t, off_tmp), base, lay.HW, lab);
+        label_runs(lab, base, lay.HW, lay.W, 0x7FFFFFFF,
+                   [&](int l, int idx, int n, int y, int x) { lab_stats_add<0>(L, lay, ws, l, idx, n, y, x); });
     }
-    __syncthreads();
-    const int l = L.key[i];
-    if (l) {
-        int *bb = bbox + 4 * l;
-        atomicMin(&bb[0], L.ymin[i]); atomicMin(&bb[1], L.xmin[i]); atomicMax(&bb[2], L.ymax[i]); atomicMax(&bb[3], L.xmax[i]);
-        atomicAdd(&cnt[l], L.cnt[i]);
-        atomicAdd(&sumy[l], (unsigned long long)L.sy[i]); atomicAdd(&sumx[l], (unsigned long long)L.sx[i]);
-    }
+    lab_stats_flush<0>(L, lay, ws, 0);
 }
+
 
 // the size filter in one launch: count + first index per label (with the flow-error filter's removals applied on the way:
 // `errs` = that stage's error table), then in the last workgroup the positional size filter (k_size_filter) and the
 // first-appearance ranks with the flagged labels removed (k_first<true> + k_renumber_rank); nlabels_out: the label count
+// (Its own body, not one template with the stage-wise kernel: as one template -- with the tail in it, and with the tail in a
+// kernel of its own -- the chain's light steps lasted 0.2 us longer per launch, 5.35 -> 5.55 and 7.12 -> 7.30 us, and the vote's
+// pass 5.6 -> 5.75 us in two sessions of three.  Those forms also stood apart from the chain's other kernels, which costs by
+// itself, see above; the two were not told apart.  profiles/postproc_one_body_ab.txt)
 __global__ void __launch_bounds__(NTHR) k_count_labels_f(int32_t *__restrict__ masks, PPLayout errs, int err_thr_on, double err_thr,
                                                          int min_size, int32_t *__restrict__ nlabels_out, int tail, PPLayout lay, void *ws) {
     __shared__ int key[LH_SLOTS], vadd[LH_SLOTS], vmin[LH_SLOTS], s_max, s_bg;
@@ -1871,6 +1830,10 @@ __global__ void __launch_bounds__(NTHR) k_count_labels_f(int32_t *__restrict__ m
 
 // class vote with the size filter's relabel on the way (labels -> `prev`'s remap, written back), then in the last workgroup
 // the per-label arg-max (k_relabel + k_class_count + k_class_pick)
+// (Its own body, not one template with the stage-wise kernel: as one template -- with the tail in it, and with the tail in a
+// kernel of its own -- the chain's light steps lasted 0.2 us longer per launch, 5.35 -> 5.55 and 7.12 -> 7.30 us, and the vote's
+// pass 5.6 -> 5.75 us in two sessions of three.  Those forms also stood apart from the chain's other kernels, which costs by
+// itself, see above; the two were not told apart.  profiles/postproc_one_body_ab.txt)
 __global__ void __launch_bounds__(NTHR) k_class_count_f(int32_t *__restrict__ masks, const float *__restrict__ logits, int ncls,
                                                         PPLayout prev, PPLayout lay, void *ws) {
     __shared__ int key[LH_SLOTS], vadd[LH_SLOTS];           // key = label * PP_MAXCLS + class + 1
@@ -1905,51 +1868,36 @@ __global__ void __launch_bounds__(NTHR) k_class_count_f(int32_t *__restrict__ ma
     if (key[threadIdx.x]) atomicAdd(&cls[key[threadIdx.x] - 1], vadd[threadIdx.x]);
 }
 
-// the chain's last pass: class map + uint16 id map per pixel (k_class_write) and, with `rec`, the per-label statistics of
-// cpx_instance_records (k_rec_stats) whose records the last workgroup writes (k_rec_write).  `pick` = the stage table whose
-// remap holds the class of every label (null: no vote -> class 0); with REMAP the labels still go through `prev`'s table.
+// the fused chain's last pass: class map + uint16 id map per pixel (k_class_write) and, with `rec`, the per-label statistics of
+// cpx_instance_records (k_rec_stats, without the first pixels), from which the same kernel launched again with tail = 1 on a
+// (1, nT) grid writes the records (k_rec_write).  `pick` = the stage table whose remap holds the class of every label (no
+// vote: class 0), which is also where a record's class comes from; with has_prev the labels still go through `prev`'s table.
 __global__ void __launch_bounds__(NTHR) k_finish_f(int32_t *__restrict__ masks, uint8_t *__restrict__ cm, uint16_t *__restrict__ masks_u16,
                                                    int has_pick, PPLayout pick, int has_prev, PPLayout prev, int max_rec,
                                                    cpx_record *__restrict__ rec, int32_t *__restrict__ counts, int tail, PPLayout lay, void *ws) {
     __shared__ LabStatsLds L;
-    const int i = threadIdx.x;
-    if (tail) {
-        // records at slot label - 1 (labels are contiguous after the renumbering); counts[tile] = the largest label
-        char *tb = (char *)ws + (size_t)blockIdx.y * lay.per_tile;
-        const int *clsmap = has_pick ? (const int *)(tb + pick.off_remap) : nullptr;
-        const int *bbox = WS(int, off_bbox), *cnt = WS(int, off_cnt);
-        const unsigned long long *sumy = WS(unsigned long long, off_sumy), *sumx = WS(unsigned long long, off_sumx);
-        const int vm = min(WS(int, off_scal)[SC_VMAX], lay.L - 1);
-        for (int v = 1 + i; v <= vm; v += NTHR) {
-            const int n = cnt[v];
-            if (n <= 0 || v - 1 >= max_rec) continue;
-            cpx_record r;
-            r.tile = blockIdx.y; r.label = v;
-            r.cls = (cm && clsmap) ? (int)(uint8_t)clsmap[v] : 0;
-            r.area = n;
-            r.y0 = bbox[4 * v]; r.x0 = bbox[4 * v + 1]; r.y1 = bbox[4 * v + 2] + 1; r.x1 = bbox[4 * v + 3] + 1;
-            r.sum_y = (int64_t)sumy[v];
-            r.sum_x = (int64_t)sumx[v];
-            rec[(size_t)blockIdx.y * max_rec + v - 1] = r;
-        }
-        if (i == 0) counts[blockIdx.y] = vm;
-        return;
-    }
-    L.key[i] = 0; L.ymin[i] = 0x7FFFFFFF; L.xmin[i] = 0x7FFFFFFF; L.ymax[i] = -1; L.xmax[i] = -1; L.cnt[i] = 0;
-    L.first[i] = 0x7FFFFFFF; L.sy[i] = 0; L.sx[i] = 0;
-    if (i == 0) L.vmax = 0;
-    __syncthreads();
     char *tb = (char *)ws + (size_t)blockIdx.y * lay.per_tile;
     const int *clsmap = has_pick ? (const int *)(tb + pick.off_remap) : nullptr;
-    int *bbox = WS(int, off_bbox), *cnt = WS(int, off_cnt), *scal = WS(int, off_scal);
-    unsigned long long *sumy = WS(unsigned long long, off_sumy), *sumx = WS(unsigned long long, off_sumx);
+    if (tail) {
+        const int *cnt = WS(int, off_cnt);
+        const int vm = min(WS(int, off_scal)[SC_VMAX], lay.L - 1);
+        for (int v = 1 + (int)threadIdx.x; v <= vm; v += NTHR) {
+            const int n = cnt[v];
+            if (n <= 0 || v - 1 >= max_rec) continue;
+            rec[(size_t)blockIdx.y * max_rec + v - 1] = make_record(v, n, (cm && clsmap) ? (int)(uint8_t)clsmap[v] : 0, lay, ws);
+        }
+        if (threadIdx.x == 0) counts[blockIdx.y] = vm;
+        return;
+    }
+    lab_stats_clear(L);
     const size_t t = blockIdx.y;
-    int32_t *m = masks + t * lay.HW;
-    const int base = (blockIdx.x * NTHR + i) * RUN_PX;
+    const int *remap = (const int *)(tb + prev.off_remap);
+    const int base = (blockIdx.x * NTHR + threadIdx.x) * RUN_PX;
     int vmax = 0;
     if (base < lay.HW) {
         int lab[RUN_PX];
-        load_labels(m, base, lay.HW, has_prev ? (const int *)(tb + prev.off_remap) : nullptr, nullptr, lab);
+        if (has_prev) load_labels_mapped(masks + t * lay.HW, base, lay.HW, lab, [&](int l) { return remap[l]; });
+        else load_labels(masks + t * lay.HW, base, lay.HW, lab);
 #pragma unroll
         for (int k = 0; k < RUN_PX; ++k)
             if (base + k < lay.HW) {
@@ -1957,42 +1905,19 @@ __global__ void __launch_bounds__(NTHR) k_finish_f(int32_t *__restrict__ masks, 
                 masks_u16[t * lay.HW + base + k] = (uint16_t)lab[k];
             }
         if (rec) {
-            label_runs(lab, base, lay.HW, lay.W, lay.L, [&](int l, int, int n, int y, int x) {
-                const unsigned long long ay = (unsigned long long)n * y;
-                const unsigned long long ax = (unsigned long long)n * x + (unsigned long long)(n * (n - 1) / 2);
-                const int sl = lh_slot(L.key, l);
-                if (sl >= 0) {
-                    atomicMin(&L.ymin[sl], y); atomicMin(&L.xmin[sl], x); atomicMax(&L.ymax[sl], y); atomicMax(&L.xmax[sl], x + n - 1);
-                    atomicAdd(&L.cnt[sl], n);
-                    atomicAdd(&L.sy[sl], (unsigned)ay); atomicAdd(&L.sx[sl], (unsigned)ax);
-                } else {
-                    int *bb = bbox + 4 * l;
-                    atomicMin(&bb[0], y); atomicMin(&bb[1], x); atomicMax(&bb[2], y); atomicMax(&bb[3], x + n - 1);
-                    atomicAdd(&cnt[l], n);
-                    atomicAdd(&sumy[l], ay); atomicAdd(&sumx[l], ax);
-                }
+            label_runs(lab, base, lay.HW, lay.W, lay.L, [&](int l, int idx, int n, int y, int x) {
+                lab_stats_add<LS_VMAX>(L, lay, ws, l, idx, n, y, x);
                 vmax = max(vmax, l);
             });
         }
     }
     if (!rec) return;
-    if (vmax > 0) atomicMax(&L.vmax, vmax);
-    __syncthreads();
-    const int l = L.key[i];
-    if (l) {
-        int *bb = bbox + 4 * l;
-        atomicMin(&bb[0], L.ymin[i]); atomicMin(&bb[1], L.xmin[i]); atomicMax(&bb[2], L.ymax[i]); atomicMax(&bb[3], L.xmax[i]);
-        atomicAdd(&cnt[l], L.cnt[i]);
-        atomicAdd(&sumy[l], (unsigned long long)L.sy[i]); atomicAdd(&sumx[l], (unsigned long long)L.sx[i]);
-    }
-    if (i == 0 && L.vmax > 0) atomicMax(&scal[SC_VMAX], L.vmax);
+    lab_stats_flush<LS_VMAX>(L, lay, ws, vmax);
 }
 
 // ---------------------------------------------------------------------------
 // host-side launch sequences (C ABI)
 // ---------------------------------------------------------------------------
-extern "C" int cpx_instance_records(const uint16_t *masks_u16, const uint8_t *class_masks, int nT, int H, int W, int max_rec,
-                                    cpx_record *records, int32_t *counts, void *ws, void *stream);
 #define GRID_PIX(lay, nT) dim3(cpx_cdiv((lay).HW, NTHR), nT)
 #define GRID_PAD(lay, nT) dim3(cpx_cdiv((lay).HWp, NTHR), nT)
 #define GRID_LAB(lay, nT) dim3(cpx_cdiv((lay).L, NTHR), nT)
@@ -2190,8 +2115,6 @@ static int fill_holes_impl(int32_t *masks, int nT, int H, int W, int min_size, i
         PP_LAUNCH(k_copy_scalar, dim3(1, nT), dim3(64), 0, s, SC_NLAB, SC_VMAX, -1, lay, ws);
     }
     // find_objects(masks): bbox per label, then fill
-    int nlab_saved_slot = SC_NLAB;
-    (void)nlab_saved_slot;
     pp_init(PPI_STATS, nT, lay, ws, s);
     PP_LAUNCH(k_lab_stats, GRID_RUN(lay, nT), dim3(NTHR), 0, s, masks, 1, lay, ws);
     PP_LAUNCH(k_fill_parallel, dim3(cpx_cdiv(lay.L, NTHR / 64), nT), dim3(NTHR), 0, s, masks, lay, ws);
