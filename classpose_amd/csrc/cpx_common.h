@@ -48,6 +48,8 @@ extern thread_local char cpx_err_buf[256];
 
 static inline size_t cpx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int cpx_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// every workspace layout: consecutive requests at 256-byte boundaries; take() returns the request's offset, o ends as the total
+struct CpxArena { size_t o = 0; size_t take(size_t bytes) { const size_t r = o; o = cpx_align_up(o + bytes, 256); return r; } };
 
 // bf16 helpers (round-to-nearest-even, NaN preserved via the compiler's cast)
 typedef __bf16 bf16_t;

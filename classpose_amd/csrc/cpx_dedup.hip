@@ -172,12 +172,11 @@ __global__ void k_dd_total(const uint32_t *__restrict__ pair_cnt, const uint32_t
 
 struct DdWs { size_t cell_cnt, cell_off, cell_fill, pt_cell, order, pair_cnt, pair_off, scan, total; };
 static DdWs dd_ws(int n, size_t n_cells) {
-    DdWs w; size_t o = 0;
-    auto take = [&](size_t b) { size_t r = o; o = cpx_align_up(o + b, 256); return r; };
-    w.cell_cnt = take(n_cells * 4); w.cell_off = take(n_cells * 4); w.cell_fill = take(n_cells * 4);
-    w.pt_cell = take((size_t)n * 4); w.order = take((size_t)n * 4); w.pair_cnt = take((size_t)n * 4); w.pair_off = take((size_t)n * 4);
-    w.scan = take(scan_ws_elems(n_cells > (size_t)n ? n_cells : (size_t)n) * 4);
-    w.total = o;
+    DdWs w; CpxArena a;
+    w.cell_cnt = a.take(n_cells * 4); w.cell_off = a.take(n_cells * 4); w.cell_fill = a.take(n_cells * 4);
+    w.pt_cell = a.take((size_t)n * 4); w.order = a.take((size_t)n * 4); w.pair_cnt = a.take((size_t)n * 4); w.pair_off = a.take((size_t)n * 4);
+    w.scan = a.take(scan_ws_elems(n_cells > (size_t)n ? n_cells : (size_t)n) * 4);
+    w.total = a.o;
     return w;
 }
 extern "C" size_t cpx_dedup_pairs_workspace_bytes(int n_points, int grid_w, int grid_h) {

@@ -74,13 +74,18 @@ int cpx_layernorm_f32(const float *x, const float *w, const float *b, int rows, 
                       void *stream);
 int cpx_attention_f32(const float *qkv, const float *rel_h, const float *rel_w, int n_subtiles, float *out,
                       void *stream);
-size_t cpx_net_f32_workspace_bytes(int n_subtiles);
-size_t cpx_net_f32_neck_offset(int n_subtiles);        // byte offset of the neck output (head GEMM operand) in that workspace
-size_t cpx_net_f32_backbone_offset(int n_subtiles);    // ... of the last block's output x [n_subtiles * 1024][1024]
 // the neck's im2col: x [n_subtiles * 1024][256] -> out [n_subtiles * 1024][2304], k = tap * 256 + c
 int cpx_im2col3_f32(const float *x, int n_subtiles, float *out, void *stream);
 int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
                         size_t workspace_bytes, void *stream);
+
+// the forward workspace of either driver (cpx_net.hip): vt and st have size 0 for float32, col for the half types
+struct NetWs { size_t off_x, off_xn, off_qkv, off_vt, off_ao, off_h, off_neck, off_neck2, off_st, off_col, total; };
+NetWs cpx_net_ws(int nS, int dtype);
+// the network tail in w->dtype (cpx_net.hip): y0 = x W0^T -> a1 = LayerNorm2d(y0) -> y2 = conv3x3(a1) -> feat = LayerNorm2d(y2) ->
+// head = feat Wh^T + bh [-> UNet head over feat, in unet_ws].  y0 / y2 and a1 / feat may alias; col: float32 only, the im2col staging
+int cpx_net_tail(const cpx_net_weights *w, const void *x, int nS, void *y0, void *a1, void *y2, void *feat, void *col, float *head,
+                 void *unet_ws, size_t unet_ws_bytes, void *stream);
 
 // UNet semantic head over token-major tensors of any element type (cpx_net.hip)
 int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *feat, int nS, float *head, int ld_head,
@@ -88,9 +93,32 @@ int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *
 size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS);
 void cpx_unet_act_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, size_t *off, int *ld);   // n_ops <= 64
 
-// what the training translation units (cpx_train*.hip) share
 static inline size_t es_of(int dtype) { return dtype == CPX_DT_F32 ? 4 : 2; }
 static inline bool dtype_ok(int dtype) { return dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32; }
+static inline int up128(long long x) { return (int)((x + 127) / 128 * 128); }
+static inline int up64(int x) { return (x + 63) / 64 * 64; }
+// GEMM view of a cpx_conv_op, forward and backward: out [rows_pad][Npad] = im2col(X) [rows_pad][Kpad] W^T, W [Npad][Kpad].  rows runs over
+// the op's output grid ho x wo; kind 2 (convT): over its INPUT grid, Npad covers the 4 taps and depth-to-space makes 4 rows of each.
+// The op's stored output (and its gradient) is [rows_out_pad][ld]
+struct OpDims { int taps, ctot, Npad, Kpad, Kp128, ho, wo, ld, rows_pad, rows_out_pad; size_t rows; };
+static inline OpDims op_dims(const cpx_conv_op &o, int nS) {
+    OpDims d;
+    d.taps = o.kind == 0 ? 9 : (o.kind == 1 ? 4 : 1);
+    d.ctot = o.cin_a + o.cin_b;
+    d.Npad = up128(o.kind == 2 ? 4 * o.cout : o.cout);
+    d.Kpad = up64(d.taps * d.ctot);
+    d.Kp128 = up128(d.Kpad);
+    d.ho = o.kind == 0 ? o.h : (o.kind == 1 ? o.h / 2 : o.h * 2);
+    d.wo = o.kind == 0 ? o.w : (o.kind == 1 ? o.w / 2 : o.w * 2);
+    d.rows = o.kind == 2 ? (size_t)nS * o.h * o.w : (size_t)nS * d.ho * d.wo;
+    d.ld = up128(o.cout);
+    d.rows_pad = up128((long long)d.rows);
+    d.rows_out_pad = up128((long long)nS * d.ho * d.wo);
+    return d;
+}
+struct CpxTensor { const char *p; int ld, c, h, w; };     // a token-major tensor [nS * h * w][ld], channels 0 .. c - 1 valid
+
+// what the training translation units (cpx_train*.hip) share
 // runs the statement(s) with `DT` a compile-time constant equal to `dtype` (which the caller has checked with dtype_ok)
 #define CPX_DT_DISPATCH(dtype, DT, ...)                                                   \
     do {                                                                                  \

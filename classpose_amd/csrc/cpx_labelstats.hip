@@ -53,14 +53,13 @@ static size_t ls_cap(int H, int W) {
 }
 
 static LsLayout ls_layout(int nI, int H, int W) {
-    LsLayout L; size_t o = 0;
-    auto take = [&](size_t b) { size_t r = o; o = cpx_align_up(o + b, 256); return r; };
+    LsLayout L; CpxArena a;
     const size_t n = (size_t)nI * ls_cap(H, W);
-    L.id_key = take(n * 8); L.ic_key = take(n * 8); L.id_area = take(n * 4); L.count = take((size_t)nI * 4);
-    L.zero_bytes = o;
-    L.min_id = take((size_t)nI * 4);
-    L.areas = take((size_t)nI * H * W * 4);
-    L.total = o;
+    L.id_key = a.take(n * 8); L.ic_key = a.take(n * 8); L.id_area = a.take(n * 4); L.count = a.take((size_t)nI * 4);
+    L.zero_bytes = a.o;
+    L.min_id = a.take((size_t)nI * 4);
+    L.areas = a.take((size_t)nI * H * W * 4);
+    L.total = a.o;
     return L;
 }
 

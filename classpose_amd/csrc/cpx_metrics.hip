@@ -48,21 +48,20 @@ struct PqLayout {                    // byte offsets into the workspace; every a
 };
 
 static PqLayout pq_layout(int nI, int nr, size_t cap) {
-    PqLayout L; size_t o = 0;
-    auto take = [&](size_t b) { size_t r = o; o = cpx_align_up(o + b, 256); return r; };
+    PqLayout L; CpxArena a;
     const size_t n = (size_t)nI * cap;
-    for (int s = 0; s < 2; ++s) { L.inst_key[s] = take(n * 8); L.inst_area[s] = take(n * 4); L.inst_flag[s] = take(n * 4); }
-    L.paira_key = take(n * 8); L.paira_inter = take(n * 4);
-    for (int s = 0; s < 2; ++s) { L.cls_key[s] = take(n * 8); L.cls_area[s] = take(n * 4); L.cls_flag[s] = take(n * 4); }
-    L.pairc_key = take(n * 8); L.pairc_inter = take(n * 4);
-    L.acc = take((size_t)nI * nr * 4 * 8);
-    L.haszero = take((size_t)nI * 2 * 4);
-    L.drop = take((size_t)nI * 2 * 4);
-    L.zero_bytes = o;
-    L.first_begin = o;
-    for (int s = 0; s < 2; ++s) L.cls_first[s] = take(n * 4);
-    L.first_end = o;
-    L.total = o;
+    for (int s = 0; s < 2; ++s) { L.inst_key[s] = a.take(n * 8); L.inst_area[s] = a.take(n * 4); L.inst_flag[s] = a.take(n * 4); }
+    L.paira_key = a.take(n * 8); L.paira_inter = a.take(n * 4);
+    for (int s = 0; s < 2; ++s) { L.cls_key[s] = a.take(n * 8); L.cls_area[s] = a.take(n * 4); L.cls_flag[s] = a.take(n * 4); }
+    L.pairc_key = a.take(n * 8); L.pairc_inter = a.take(n * 4);
+    L.acc = a.take((size_t)nI * nr * 4 * 8);
+    L.haszero = a.take((size_t)nI * 2 * 4);
+    L.drop = a.take((size_t)nI * 2 * 4);
+    L.zero_bytes = a.o;
+    L.first_begin = a.o;
+    for (int s = 0; s < 2; ++s) L.cls_first[s] = a.take(n * 4);
+    L.first_end = a.o;
+    L.total = a.o;
     return L;
 }
 

@@ -2,6 +2,9 @@
 // LayerNorm, global attention with the decomposed relative-position bias fused
 // into the flash loop, the neck (its 3x3 conv is an implicit GEMM), and the launch sequence that
 // strings them together with the MFMA GEMM of cpx_gemm.hip.
+// Shared with the float32 driver (cpx_net_f32.hip) and the neck's training forward (cpx_train_neck.hip): the workspace layout of
+// all three dtypes (cpx_net_ws) and the network tail -- neck, head GEMM, optional UNet head -- as one launch sequence (cpx_net_tail).
+// The UNet head's layout and run read the op geometry the backward reads too (op_dims, cpx_internal.h).
 //
 // Attention design (T = 32x32 tokens, 16 heads x 64):
 //   * one wave owns one IMAGE ROW of queries (32 tokens, same qh) and walks the
@@ -445,34 +448,32 @@ int cpx_attention_half(int dtype, const void *qkv, const void *rel_h, const void
 // ---------------------------------------------------------------------------
 // forward driver
 // ---------------------------------------------------------------------------
-struct NetWs {
-    size_t off_x, off_xn, off_qkv, off_vt, off_ao, off_h, off_neck, off_neck2, off_st, total;
-};
-static NetWs net_ws(int nS) {
-    NetWs w; size_t o = 0; const size_t M = (size_t)nS * 1024;
-    auto take = [&](size_t b) { size_t r = o; o = cpx_align_up(o + b, 256); return r; };
-    w.off_x = take(M * 1024 * 2);
-    w.off_xn = take(M * 1024 * 2);
-    w.off_qkv = take(M * 3072 * 2);
-    w.off_vt = take(M * 1024 * 2);
-    w.off_ao = take(M * 1024 * 2);
-    w.off_h = take(M * 4096 * 2);
-    w.off_neck = take(M * 256 * 2);
-    w.off_neck2 = take(M * 256 * 2);
-    w.off_st = take(M * 8 * sizeof(float));
-    w.total = o;
+// one layout for both drivers: a zero-size request adds nothing to the offset, so the half types (no col) and float32 (no vt, no st)
+// each see their requests back to back
+NetWs cpx_net_ws(int nS, int dtype) {
+    NetWs w; CpxArena a; const size_t M = (size_t)nS * 1024, es = es_of(dtype);
+    w.off_x = a.take(M * 1024 * es);
+    w.off_xn = a.take(M * 1024 * es);
+    w.off_qkv = a.take(M * 3072 * es);
+    w.off_vt = a.take(es == 2 ? M * 1024 * es : 0);
+    w.off_ao = a.take(M * 1024 * es);
+    w.off_h = a.take(M * 4096 * es);
+    w.off_neck = a.take(M * 256 * es);
+    w.off_neck2 = a.take(M * 256 * es);
+    w.off_st = a.take(es == 2 ? M * 8 * sizeof(float) : 0);
+    w.off_col = a.take(es == 4 ? M * 2304 * es : 0);
+    w.total = a.o;
     return w;
 }
 extern "C" size_t cpx_net_workspace_bytes(int n_subtiles, int dtype) {
-    if (n_subtiles <= 0) return 0;
-    return dtype == CPX_DT_F32 ? cpx_net_f32_workspace_bytes(n_subtiles) : net_ws(n_subtiles).total;
+    return n_subtiles > 0 ? cpx_net_ws(n_subtiles, dtype).total : 0;
 }
 
 // where cpx_net_forward leaves the neck output [n_subtiles * 1024][256] (element type = network dtype; the operand of the head GEMM) in its
 // workspace: the features a frozen-backbone training step starts from (cpx_train.hip).  0 for an invalid argument (the offset is never 0).
 extern "C" size_t cpx_net_neck_offset(int n_subtiles, int dtype) {
     if (n_subtiles <= 0 || dtype < CPX_DT_BF16 || dtype > CPX_DT_F32) return 0;
-    return dtype == CPX_DT_F32 ? cpx_net_f32_neck_offset(n_subtiles) : net_ws(n_subtiles).off_neck2;
+    return cpx_net_ws(n_subtiles, dtype).off_neck2;
 }
 
 // where cpx_net_forward leaves the last block's output x [n_subtiles * 1024][1024] (network dtype; the operand of the neck's first GEMM):
@@ -480,7 +481,7 @@ extern "C" size_t cpx_net_neck_offset(int n_subtiles, int dtype) {
 // offset itself is 0 in both layouts.
 extern "C" size_t cpx_net_backbone_offset(int n_subtiles, int dtype) {
     if (n_subtiles <= 0 || dtype < CPX_DT_BF16 || dtype > CPX_DT_F32) return (size_t)-1;
-    return dtype == CPX_DT_F32 ? cpx_net_f32_backbone_offset(n_subtiles) : net_ws(n_subtiles).off_x;
+    return cpx_net_ws(n_subtiles, dtype).off_x;
 }
 
 // ---------------------------------------------------------------------------
@@ -560,13 +561,41 @@ static void mlp_part_rows(int n_subtiles, int parts, int pt, int &row0, int &row
     rows = pt + 1 < parts ? 16384 : n_subtiles * 1024 - row0;
 }
 
+// the network tail, for both forward drivers and the neck's training forward (cpx_train_neck.hip): one launch sequence per dtype.
+// The plain GEMMs take one epilogue code for all dtypes: float32 has a single store-as-is instantiation (cpx_gemm_f32)
+int cpx_net_tail(const cpx_net_weights *w, const void *x, int nS, void *y0, void *a1, void *y2, void *feat, void *col, float *head,
+                 void *unet_ws, size_t unet_ws_bytes, void *stream) {
+    const int dt = w->dtype, M = nS * 1024;
+    int rc;
+#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
+    // neck: 1x1 conv -> LN2d -> 3x3 conv -> LN2d
+    RUN(cpx_gemm(dt, x, w->neck0_w, M, 256, 1024, CPX_EPI_BF16, nullptr, nullptr, y0, 256, stream));
+    RUN(cpx_layernorm(dt, y0, w->neck_ln1_w, w->neck_ln1_b, M, 256, 1e-6f, a1, stream));
+    if (dt == CPX_DT_F32) {         // im2col [M][9 x 256], then the GEMM
+        RUN(cpx_im2col3_f32((const float *)a1, nS, (float *)col, stream));
+        RUN(cpx_gemm(dt, col, w->neck2_w, M, 256, 2304, CPX_EPI_BF16, nullptr, nullptr, y2, 256, stream));
+    } else {                        // an implicit GEMM (K = 9 x 256, the shifted operand is read by the LDS-DMA itself: no im2col buffer)
+        RUN(cpx_conv3_half(dt, a1, w->neck2_w, M, 256, 256, CPX_EPI_BF16, nullptr, y2, 256, stream));
+    }
+    RUN(cpx_layernorm(dt, y2, w->neck_ln2_w, w->neck_ln2_b, M, 256, 1e-6f, feat, stream));
+    // heads: out (192) | out_class (ncls*64), f32 token-major
+    RUN(cpx_gemm(dt, feat, w->head_w, M, w->ld_head, 256, CPX_EPI_F32, w->head_b, nullptr, head, w->ld_head, stream));
+    if (w->n_unet_ops > 0) {        // UNet semantic head overwrites the class columns (head_w rows there are zero)
+        const size_t need = cpx_unet_ws_bytes(dt, w->unet_ops, w->n_unet_ops, nS);
+        CPX_REQUIRE(unet_ws_bytes >= need);
+        RUN(cpx_unet_head_run(dt, w->unet_ops, w->n_unet_ops, feat, nS, head, w->ld_head, 192, unet_ws, need, stream));
+    }
+#undef RUN
+    return CPX_OK;
+}
+
 extern "C" int cpx_net_forward(const cpx_net_weights *w, const void *patches, int nS, float *head,
                                void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(w && patches && head && workspace && nS > 0);
     CPX_REQUIRE(w->depth > 0 && w->blocks && w->ld_head % 128 == 0 && w->ld_head >= w->n_head_cols);
     CPX_REQUIRE(w->dtype == CPX_DT_BF16 || w->dtype == CPX_DT_F16 || w->dtype == CPX_DT_F32);
     if (w->dtype == CPX_DT_F32) return cpx_net_forward_f32(w, patches, nS, head, workspace, workspace_bytes, stream);
-    NetWs L = net_ws(nS);
+    const NetWs L = cpx_net_ws(nS, w->dtype);
     CPX_REQUIRE(workspace_bytes >= L.total);
     const int dt = w->dtype;
     char *ws = (char *)workspace;
@@ -624,20 +653,8 @@ extern "C" int cpx_net_forward(const cpx_net_weights *w, const void *patches, in
         TIMED(CPX_PROF_FC1, i, GEMM(xn, b.fc1_w, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096));
         TIMED(CPX_PROF_FC2, i, GEMM(hb, b.fc2_w, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, x, x, 1024));
     }
-    // neck: 1x1 conv -> LN2d -> 3x3 conv -> LN2d
     const bool t_tail = cpx_prof_begin(prof, CPX_PROF_TAIL, 0, hs);
-    RUN(GEMM(x, w->neck0_w, 256, 1024, CPX_EPI_BF16, nullptr, nullptr, nk, 256));
-    RUN(cpx_layernorm_half(dt, nk, w->neck_ln1_w, w->neck_ln1_b, M, 256, 1e-6f, nk2, stream));
-    // 3x3 conv as an implicit GEMM (K = 9 x 256, the shifted operand is read by the LDS-DMA itself: no im2col buffer)
-    RUN(cpx_conv3_half(dt, nk2, w->neck2_w, M, 256, 256, CPX_EPI_BF16, nullptr, nk, 256, stream));
-    RUN(cpx_layernorm_half(dt, nk, w->neck_ln2_w, w->neck_ln2_b, M, 256, 1e-6f, nk2, stream));
-    // heads: out (192) | out_class (ncls*64), f32 token-major
-    RUN(GEMM(nk2, w->head_w, w->ld_head, 256, CPX_EPI_F32, w->head_b, nullptr, head, w->ld_head));
-    if (w->n_unet_ops > 0) {        // UNet semantic head overwrites the class columns (head_w rows there are zero)
-        const size_t need = cpx_unet_ws_bytes(dt, w->unet_ops, w->n_unet_ops, nS);
-        CPX_REQUIRE(workspace_bytes >= L.total + need);
-        RUN(cpx_unet_head_run(dt, w->unet_ops, w->n_unet_ops, nk2, nS, head, w->ld_head, 192, ws + L.total, need, stream));
-    }
+    RUN(cpx_net_tail(w, x, nS, nk, nk2, nk, nk2, nullptr, head, ws + L.total, workspace_bytes - L.total, stream));
     if (t_tail) cpx_prof_end(prof, hs);
 #undef TIMED
 #undef GEMM
@@ -712,10 +729,7 @@ __global__ void __launch_bounds__(256) k_depth2space(const char *__restrict__ in
     }
 }
 
-static inline int up128(long long x) { return (int)((x + 127) / 128 * 128); }
-static inline int up64(int x) { return (x + 63) / 64 * 64; }
-
-// workspace layout: [im2col staging][convT GEMM staging][one tensor [rows_pad][ld] per op] + 1024 bytes of slack.  The
+// workspace layout: [im2col staging][convT GEMM staging][one tensor [rows_out_pad][ld] per op] + 1024 bytes of slack.  The
 // LAST op (a convT into the head) gets a slot too but never writes it: its GEMM output stays in the convT staging buffer
 // and k_depth2space widens it straight into the head.  One helper for the size, the run and the debug layout entry.
 struct UnetLayout {
@@ -724,28 +738,22 @@ struct UnetLayout {
     int ld[64];                          // its row stride in elements
 };
 static void unet_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, UnetLayout &L) {
-    const size_t es = dtype == CPX_DT_F32 ? 4 : 2;
+    const size_t es = es_of(dtype);
     size_t col_max = 0, g_max = 0;
     for (int i = 0; i < n_ops; ++i) {     // sizes of the shared staging buffers first
-        const cpx_conv_op &o = ops[i];
-        const int ho = o.kind == 0 ? o.h : (o.kind == 1 ? o.h / 2 : o.h * 2), wo = o.kind == 0 ? o.w : (o.kind == 1 ? o.w / 2 : o.w * 2);
-        if (o.kind != 2) col_max = std::max(col_max, (size_t)up128((size_t)nS * ho * wo) * up64((o.kind == 0 ? 9 : 4) * (o.cin_a + o.cin_b)) * es);
-        else {
-            g_max = std::max(g_max, (size_t)up128((size_t)nS * o.h * o.w) * up128(4 * o.cout) * es);
-            col_max = std::max(col_max, (size_t)up128((size_t)nS * o.h * o.w) * up64(o.cin_a) * es);
-        }
+        const OpDims d = op_dims(ops[i], nS);
+        col_max = std::max(col_max, (size_t)d.rows_pad * d.Kpad * es);
+        if (ops[i].kind == 2) g_max = std::max(g_max, (size_t)d.rows_pad * d.Npad * es);
     }
-    L.col_off = 0;
-    L.g_off = cpx_align_up(col_max, 256);
-    size_t off = L.g_off + cpx_align_up(g_max, 256);
+    CpxArena a;
+    L.col_off = a.take(col_max);
+    L.g_off = a.take(g_max);
     for (int i = 0; i < n_ops && i < 64; ++i) {
-        const cpx_conv_op &o = ops[i];
-        const int ho = o.kind == 0 ? o.h : (o.kind == 1 ? o.h / 2 : o.h * 2), wo = o.kind == 0 ? o.w : (o.kind == 1 ? o.w / 2 : o.w * 2);
-        L.off[i] = off;
-        L.ld[i] = up128(o.cout);
-        off += cpx_align_up((size_t)up128((size_t)nS * ho * wo) * up128(o.cout) * es, 256);
+        const OpDims d = op_dims(ops[i], nS);
+        L.ld[i] = d.ld;
+        L.off[i] = a.take((size_t)d.rows_out_pad * d.ld * es);
     }
-    L.total = off + 1024;
+    L.total = a.o + 1024;
 }
 
 size_t cpx_unet_ws_bytes(int dtype, const cpx_conv_op *ops, int n_ops, int nS) {
@@ -773,7 +781,7 @@ extern "C" int cpx_unet_head_layout(const cpx_conv_op *ops, int n_ops, int nS, i
     unet_layout(dtype, ops, n_ops, nS, L);
     for (int i = 0; i < n_ops; ++i) { dst_off[i] = L.off[i]; ld[i] = L.ld[i]; }
     dst_off[n_ops - 1] = L.g_off;
-    ld[n_ops - 1] = up128(4 * ops[n_ops - 1].cout);
+    ld[n_ops - 1] = op_dims(ops[n_ops - 1], nS).Npad;
     return CPX_OK;
 }
 #endif
@@ -785,58 +793,41 @@ int cpx_unet_head_run(int dtype, const cpx_conv_op *ops, int n_ops, const void *
     CPX_REQUIRE(ops && n_ops > 0 && n_ops <= 64 && feat && head && workspace && nS > 0);
     CPX_REQUIRE(ws_bytes >= cpx_unet_ws_bytes(dtype, ops, n_ops, nS));
     hipStream_t s = (hipStream_t)stream;
-    const size_t es = dtype == CPX_DT_F32 ? 4 : 2;
-    struct T { const char *p; int ld, c, h, w; } tens[66];
+    const size_t es = es_of(dtype);
+    CpxTensor tens[66];
     tens[0] = {(const char *)feat, 256, 256, 32, 32};
     char *ws = (char *)workspace;
     UnetLayout lay;
     unet_layout(dtype, ops, n_ops, nS, lay);
     char *colbuf = ws + lay.col_off, *gbuf = ws + lay.g_off;
-    auto gather = [&](const T &A, int ca, const T &B, int cb, int kind, int h, int w, size_t rows, int Kp) {
-        const size_t n_chunks = rows * (Kp / (16 / es));
-        const dim3 grid((unsigned)((n_chunks + 255) / 256));
-        if (es == 4) hipLaunchKernelGGL(k_conv_gather<4>, grid, dim3(256), 0, s, A.p, A.ld, ca, B.p, B.ld, cb, kind, h, w, rows, Kp, colbuf);
-        else hipLaunchKernelGGL(k_conv_gather<2>, grid, dim3(256), 0, s, A.p, A.ld, ca, B.p, B.ld, cb, kind, h, w, rows, Kp, colbuf);
-    };
-    auto gemm = [&](const void *A, const void *W, int M, int N, int K, int epi, const float *bias, void *out) {
-        if (dtype == CPX_DT_F32) return cpx_gemm_f32((const float *)A, (const float *)W, M, N, K, epi, bias, nullptr, (float *)out, N, stream);
-        return cpx_gemm_half(dtype, A, W, M, N, K, epi, bias, nullptr, out, N, nullptr, nullptr, nullptr, stream);
-    };
-    int rc;
+    // (named float32 first: the order in which the instantiations have always stood in the code object; CPX_DT_DISPATCH would turn it round)
+    const auto gather = es == 4 ? k_conv_gather<4> : k_conv_gather<2>;
+    auto d2s = k_depth2space<CPX_DT_F32>;
+    if (dtype != CPX_DT_F32) d2s = dtype == CPX_DT_F16 ? k_depth2space<CPX_DT_F16> : k_depth2space<CPX_DT_BF16>;
     for (int i = 0; i < n_ops; ++i) {
         const cpx_conv_op &o = ops[i];
         CPX_REQUIRE(o.dst > 0 && o.dst < 66 && o.src_a >= 0 && o.src_a < 66 && o.src_b < 66);
         CPX_REQUIRE(o.cin_a % 8 == 0 && o.cin_b % 8 == 0 && o.cout % 8 == 0 && o.weight && o.bias);
-        const T &A = tens[o.src_a];
-        const T Bz = {nullptr, 0, 0, 0, 0};
-        const T &B = o.src_b >= 0 ? tens[o.src_b] : Bz;
+        const CpxTensor &A = tens[o.src_a];
+        const CpxTensor Bz = {nullptr, 0, 0, 0, 0};
+        const CpxTensor &B = o.src_b >= 0 ? tens[o.src_b] : Bz;
         CPX_REQUIRE(A.c == o.cin_a && A.h == o.h && A.w == o.w && (o.src_b < 0 || (B.c == o.cin_b && B.h == o.h && B.w == o.w)));
-        if (o.kind != 2) {
-            const int ho = o.kind == 0 ? o.h : o.h / 2, wo = o.kind == 0 ? o.w : o.w / 2;
-            const size_t rows = (size_t)nS * ho * wo;
-            const int Mp = up128(rows), Kp = up64((o.kind == 0 ? 9 : 4) * (o.cin_a + o.cin_b)), Np = up128(o.cout);
-            gather(A, o.cin_a, B, o.cin_b, o.kind, o.h, o.w, rows, Kp);
-            char *dst = ws + lay.off[i];
-            rc = gemm(colbuf, o.weight, Mp, Np, Kp, o.relu ? CPX_EPI_RELU_BF16 : CPX_EPI_BF16, o.bias, dst);
-            if (rc) return rc;
-            tens[o.dst] = {dst, Np, o.cout, ho, wo};
-        } else {
-            const size_t rows = (size_t)nS * o.h * o.w;
-            const int Mp = up128(rows), Kp = up64(o.cin_a), Np = up128(4 * o.cout);
-            CPX_REQUIRE(o.src_b < 0);
-            gather(A, o.cin_a, Bz, 0, 3, o.h, o.w, rows, Kp);
-            rc = gemm(colbuf, o.weight, Mp, Np, Kp, CPX_EPI_BF16, o.bias, gbuf);
-            if (rc) return rc;
+        if (o.kind == 2) CPX_REQUIRE(o.src_b < 0);
+        const OpDims d = op_dims(o, nS);
+        const bool convT = o.kind == 2;
+        // im2col (convT: a plain repack, kind 3) into the staging buffer, then the GEMM: a convT's output goes to its own staging
+        const dim3 grid_g((unsigned)((d.rows * (d.Kpad / (16 / es)) + 255) / 256));
+        hipLaunchKernelGGL(gather, grid_g, dim3(256), 0, s, A.p, A.ld, o.cin_a, B.p, B.ld, convT ? 0 : o.cin_b, convT ? 3 : o.kind, o.h, o.w, d.rows, d.Kpad, colbuf);
+        char *dst = ws + lay.off[i];
+        const int rc = cpx_gemm(dtype, colbuf, o.weight, d.rows_pad, d.Npad, d.Kpad, !convT && o.relu ? CPX_EPI_RELU_BF16 : CPX_EPI_BF16, o.bias, nullptr,
+                                convT ? gbuf : dst, d.Npad, stream);
+        if (rc) return rc;
+        if (convT) {                 // depth-to-space; the last op's goes into the head as float32
             const bool last = i == n_ops - 1;
-            char *dst = ws + lay.off[i];
-            const int ldo = lay.ld[i];
-            const size_t n_thr = rows * 4 * (o.cout / (16 / es));
-            const dim3 grid((unsigned)((n_thr + 255) / 256));
-#define D2S(DT_) hipLaunchKernelGGL(k_depth2space<DT_>, grid, dim3(256), 0, s, gbuf, Np, o.cout, o.h, o.w, rows, dst, ldo, last ? head : nullptr, ld_head, col0)
-            if (dtype == CPX_DT_F32) D2S(CPX_DT_F32); else if (dtype == CPX_DT_F16) D2S(CPX_DT_F16); else D2S(CPX_DT_BF16);
-#undef D2S
-            tens[o.dst] = {dst, ldo, o.cout, o.h * 2, o.w * 2};
+            const dim3 grid((unsigned)((d.rows * 4 * (o.cout / (16 / es)) + 255) / 256));
+            hipLaunchKernelGGL(d2s, grid, dim3(256), 0, s, gbuf, d.Npad, o.cout, o.h, o.w, d.rows, dst, d.ld, last ? head : nullptr, ld_head, col0);
         }
+        tens[o.dst] = {dst, d.ld, o.cout, d.ho, d.wo};
     }
     CPX_CHECK_LAUNCH();
     return CPX_OK;

@@ -15,6 +15,7 @@
 //                    accumulator registers (the k-slot of step j IS accumulator register j).
 // The MFMA k index is free to be permuted identically on both operands: lane half h2 takes
 // k = 8*h2 + s (GEMM) / d = 32*h2 + s (attention) so that fragments are 16-byte LDS / global reads.
+// The driver lays its workspace out with cpx_net_ws and ends in cpx_net_tail, both shared with the half-precision driver (cpx_net.hip).
 #include "cpx_internal.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -358,29 +359,15 @@ extern "C" int cpx_im2col3_f32_debug(const float *x, int n_subtiles, float *out,
 // ---------------------------------------------------------------------------
 // forward driver (ClassTransformer.forward, vit_sam.py:148-197)
 // ---------------------------------------------------------------------------
-struct NetWsF32 { size_t off_x, off_xn, off_qkv, off_ao, off_h, off_neck, off_neck2, off_col, total; };
-static NetWsF32 net_ws_f32(int nS) {
-    NetWsF32 w; size_t o = 0; const size_t M = (size_t)nS * 1024;
-    auto take = [&](size_t b) { size_t r = o; o = cpx_align_up(o + b, 256); return r; };
-    w.off_x = take(M * 1024 * 4); w.off_xn = take(M * 1024 * 4); w.off_qkv = take(M * 3072 * 4);
-    w.off_ao = take(M * 1024 * 4); w.off_h = take(M * 4096 * 4); w.off_neck = take(M * 256 * 4);
-    w.off_neck2 = take(M * 256 * 4); w.off_col = take(M * 2304 * 4);
-    w.total = o;
-    return w;
-}
-size_t cpx_net_f32_workspace_bytes(int n_subtiles) { return n_subtiles > 0 ? net_ws_f32(n_subtiles).total : 0; }
-size_t cpx_net_f32_neck_offset(int n_subtiles) { return n_subtiles > 0 ? net_ws_f32(n_subtiles).off_neck2 : 0; }
-size_t cpx_net_f32_backbone_offset(int n_subtiles) { return net_ws_f32(n_subtiles).off_x; }
-
 int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
                         size_t workspace_bytes, void *stream) {
-    const NetWsF32 L = net_ws_f32(nS);
+    const NetWs L = cpx_net_ws(nS, CPX_DT_F32);
     CPX_REQUIRE(workspace_bytes >= L.total && !w->fuse_ln);
     char *ws = (char *)workspace;
     const int M = nS * 1024;
     float *x = (float *)(ws + L.off_x), *xn = (float *)(ws + L.off_xn), *qkv = (float *)(ws + L.off_qkv),
           *ao = (float *)(ws + L.off_ao), *hb = (float *)(ws + L.off_h), *nk = (float *)(ws + L.off_neck),
-          *nk2 = (float *)(ws + L.off_neck2), *col = (float *)(ws + L.off_col);
+          *nk2 = (float *)(ws + L.off_neck2);
     CpxProf *prof = (CpxProf *)w->prof;
     hipStream_t hs = (hipStream_t)stream;
     int rc;
@@ -401,17 +388,7 @@ int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, f
         if (t) cpx_prof_end(prof, hs);
         RUN(cpx_gemm_f32(hb, F(b.fc2_w), M, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, x, x, 1024, stream));
     }
-    RUN(cpx_gemm_f32(x, F(w->neck0_w), M, 256, 1024, CPX_EPI_F32, nullptr, nullptr, nk, 256, stream));
-    RUN(cpx_layernorm_f32(nk, w->neck_ln1_w, w->neck_ln1_b, M, 256, 1e-6f, nk2, stream));
-    RUN(cpx_im2col3_f32(nk2, nS, col, stream));
-    RUN(cpx_gemm_f32(col, F(w->neck2_w), M, 256, 2304, CPX_EPI_F32, nullptr, nullptr, nk, 256, stream));
-    RUN(cpx_layernorm_f32(nk, w->neck_ln2_w, w->neck_ln2_b, M, 256, 1e-6f, nk2, stream));
-    RUN(cpx_gemm_f32(nk2, F(w->head_w), M, w->ld_head, 256, CPX_EPI_F32, w->head_b, nullptr, head, w->ld_head, stream));
-    if (w->n_unet_ops > 0) {
-        const size_t need = cpx_unet_ws_bytes(CPX_DT_F32, w->unet_ops, w->n_unet_ops, nS);
-        CPX_REQUIRE(workspace_bytes >= L.total + need);
-        RUN(cpx_unet_head_run(CPX_DT_F32, w->unet_ops, w->n_unet_ops, nk2, nS, head, w->ld_head, 192, ws + L.total, need, stream));
-    }
+    RUN(cpx_net_tail(w, x, nS, nk, nk2, nk, nk2, ws + L.off_col, head, ws + L.total, workspace_bytes - L.total, stream));
 #undef F
 #undef RUN
     return CPX_OK;

@@ -51,40 +51,38 @@ static PPLayout pp_layout(int H, int W) {
     PPLayout p;
     p.H = H; p.W = W; p.HW = H * W; p.Hp = H + 2 * RPAD; p.Wp = W + 2 * RPAD;
     p.HWp = p.Hp * p.Wp; p.L = p.HW / 11 + 2; p.TH = H + 2; p.TW = W + 2; p.THW = p.TH * p.TW;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = cpx_align_up(o + bytes, 256); return r; };
-    p.off_h1 = take(sizeof(int) * p.HWp);
-    p.off_M1 = take(sizeof(int) * p.HWp);
-    p.off_tmp = take(sizeof(int) * p.HW);
-    p.off_im = take(sizeof(float) * 2 * p.THW);      // zero-bordered interleaved flow field [H+2][W+2][dx, dy]
+    CpxArena a;
+    p.off_h1 = a.take(sizeof(int) * p.HWp);
+    p.off_M1 = a.take(sizeof(int) * p.HWp);
+    p.off_tmp = a.take(sizeof(int) * p.HW);
+    p.off_im = a.take(sizeof(float) * 2 * p.THW);      // zero-bordered interleaved flow field [H+2][W+2][dx, dy]
     p.nbx = cpx_cdiv(p.TW, FG_SIDE); p.nseg = p.nbx * cpx_cdiv(p.TH, FG_SIDE);   // (>= cdiv(THW, FG_BLOCK), the linear segmentation's count)
-    p.off_fg = take(sizeof(int) * FG_BLOCK * p.nseg);   // foreground pixels, one segment per k_prep_flow block
-    p.off_fgcnt = take(sizeof(int) * p.nseg);
-    p.off_rankbits = take(sizeof(unsigned) * 2 * cpx_cdiv(p.HW, 32));   // tail_rank: one bit per pixel + the words' prefix counts
-    p.off_T = take(sizeof(double) * 2 * p.THW);
-    p.off_e = take(sizeof(double) * 2 * p.HW);
-    p.off_cls = take(sizeof(int) * (size_t)p.L * PP_MAXCLS);
+    p.off_fg = a.take(sizeof(int) * FG_BLOCK * p.nseg);   // foreground pixels, one segment per k_prep_flow block
+    p.off_fgcnt = a.take(sizeof(int) * p.nseg);
+    p.off_rankbits = a.take(sizeof(unsigned) * 2 * cpx_cdiv(p.HW, 32));   // tail_rank: one bit per pixel + the words' prefix counts
+    p.off_T = a.take(sizeof(double) * 2 * p.THW);
+    p.off_e = a.take(sizeof(double) * 2 * p.HW);
+    p.off_cls = a.take(sizeof(int) * (size_t)p.L * PP_MAXCLS);
     // ---- the per-label tables + scalars: one contiguous block, PP_NSETS copies of it (the fused chain of
     // cpx_compute_masks gives every stage its own copy, all of them cleared by ONE pass at the start of the chain;
     // the stage-wise entry points use copy 0)
-    p.tab0 = o;
-    p.off_seed_pos = take(sizeof(int) * p.L);
-    p.off_seed_cnt = take(sizeof(int) * p.L);
-    p.off_rank = take(sizeof(int) * p.L);
-    p.off_cnt = take(sizeof(int) * p.L);
-    p.off_first = take(sizeof(int) * p.L);
-    p.off_remap = take(sizeof(int) * p.L);
-    p.off_flag = take(sizeof(int) * (p.L > 65536 ? p.L : 65536));   // border flags index raw uint16 ids
-    p.off_bbox = take(sizeof(int) * 4 * p.L);
-    p.off_sumy = take(sizeof(unsigned long long) * p.L);
-    p.off_sumx = take(sizeof(unsigned long long) * p.L);
-    p.off_d2 = take(sizeof(unsigned long long) * p.L);
-    p.off_center = take(sizeof(int) * p.L);
-    p.off_err = take(sizeof(double) * p.L);
-    p.off_scal = take(sizeof(int) * PP_NSCAL);
-    p.tab_bytes = o - p.tab0;
-    o = p.tab0 + p.tab_bytes * PP_NSETS;
-    p.per_tile = o;
+    p.tab0 = a.o;
+    p.off_seed_pos = a.take(sizeof(int) * p.L);
+    p.off_seed_cnt = a.take(sizeof(int) * p.L);
+    p.off_rank = a.take(sizeof(int) * p.L);
+    p.off_cnt = a.take(sizeof(int) * p.L);
+    p.off_first = a.take(sizeof(int) * p.L);
+    p.off_remap = a.take(sizeof(int) * p.L);
+    p.off_flag = a.take(sizeof(int) * (p.L > 65536 ? p.L : 65536));   // border flags index raw uint16 ids
+    p.off_bbox = a.take(sizeof(int) * 4 * p.L);
+    p.off_sumy = a.take(sizeof(unsigned long long) * p.L);
+    p.off_sumx = a.take(sizeof(unsigned long long) * p.L);
+    p.off_d2 = a.take(sizeof(unsigned long long) * p.L);
+    p.off_center = a.take(sizeof(int) * p.L);
+    p.off_err = a.take(sizeof(double) * p.L);
+    p.off_scal = a.take(sizeof(int) * PP_NSCAL);
+    p.tab_bytes = a.o - p.tab0;
+    p.per_tile = p.tab0 + p.tab_bytes * PP_NSETS;
     return p;
 }
 

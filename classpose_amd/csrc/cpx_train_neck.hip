@@ -2,7 +2,7 @@
 // (classpose/vit_sam.py:216-249, paper_experiments/run_training.py:92-98).  The neck is the tail of cpx_net_forward,
 //   y0 = x W0^T  ->  a1 = LayerNorm2d(y0)  ->  y2 = conv3x3(a1, W2)  ->  feat = LayerNorm2d(y2)  ->  head = feat Wh^T + bh,
 // on the last block's output x [nS * 1024][1024], which cpx_net_forward leaves in its workspace (cpx_net_backbone_offset).
-//   * cpx_neck_forward_train   the tail's own launches, in its order, into four tensors of their own: the saved activations
+//   * cpx_neck_forward_train   the tail itself (cpx_net_tail, cpx_net.hip) with four tensors of their own: the saved activations
 //   * k_ln_bwd / k_ln_bwd_finish   LayerNorm over channels, backward: one wave per row, everything formed in float64 and rounded once
 //   * cpx_neck_backward        head data gradient -> LN2 -> conv3x3 (weight and data gradient) -> LN1 -> conv1x1 weight gradient; the
 //                              convolutions run the kernels of the UNet head's backward (cpx_train_unet.hip, through cpx_internal.h)
@@ -22,11 +22,10 @@
 // workspace: [y0][a1][y2][feat], each [rows][256] in the network dtype; float32 adds the im2col staging [rows][2304]
 struct NeckFwdLayout { size_t off[4], off_col, total; };
 static NeckFwdLayout neck_fwd_layout(int nS, int dtype) {
-    NeckFwdLayout L; size_t o = 0; const size_t rows = (size_t)nS * 1024;
-    auto take = [&](size_t b) { size_t r = o; o = cpx_align_up(o + b, 256); return r; };
-    for (int i = 0; i < 4; ++i) L.off[i] = take(rows * NECK_C * es_of(dtype));
-    L.off_col = take(dtype == CPX_DT_F32 ? rows * NECK_K2 * sizeof(float) : 0);
-    L.total = o;
+    NeckFwdLayout L; CpxArena a; const size_t rows = (size_t)nS * 1024;
+    for (int i = 0; i < 4; ++i) L.off[i] = a.take(rows * NECK_C * es_of(dtype));
+    L.off_col = a.take(dtype == CPX_DT_F32 ? rows * NECK_K2 * sizeof(float) : 0);
+    L.total = a.o;
     return L;
 }
 extern "C" size_t cpx_neck_train_workspace_bytes(int nS, int dtype) {
@@ -49,35 +48,10 @@ static bool neck_weights_ok(const cpx_net_weights *w) {
 extern "C" int cpx_neck_forward_train(const cpx_net_weights *w, const void *x, int nS, float *head, void *workspace,
                                       size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(neck_weights_ok(w) && x && head && workspace && nS > 0 && (size_t)nS * 1024 < 0x7fffffffull);
-    const int dt = w->dtype, M = nS * 1024;
-    const NeckFwdLayout L = neck_fwd_layout(nS, dt);
+    const NeckFwdLayout L = neck_fwd_layout(nS, w->dtype);
     CPX_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0 && ((uintptr_t)x & 15) == 0);
     char *ws = (char *)workspace;
-    void *y0 = ws + L.off[0], *a1 = ws + L.off[1], *y2 = ws + L.off[2], *feat = ws + L.off[3];
-    int rc;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
-    if (dt == CPX_DT_F32) {         // the tail of cpx_net_forward_f32
-#define F(p) ((const float *)(p))
-        float *col = (float *)(ws + L.off_col);
-        RUN(cpx_gemm_f32(F(x), F(w->neck0_w), M, NECK_C, NECK_K0, CPX_EPI_F32, nullptr, nullptr, (float *)y0, NECK_C, stream));
-        RUN(cpx_layernorm_f32(F(y0), w->neck_ln1_w, w->neck_ln1_b, M, NECK_C, 1e-6f, (float *)a1, stream));
-        RUN(cpx_im2col3_f32(F(a1), nS, col, stream));
-        RUN(cpx_gemm_f32(col, F(w->neck2_w), M, NECK_C, NECK_K2, CPX_EPI_F32, nullptr, nullptr, (float *)y2, NECK_C, stream));
-        RUN(cpx_layernorm_f32(F(y2), w->neck_ln2_w, w->neck_ln2_b, M, NECK_C, 1e-6f, (float *)feat, stream));
-        RUN(cpx_gemm_f32(F(feat), F(w->head_w), M, w->ld_head, NECK_C, CPX_EPI_F32, w->head_b, nullptr, head, w->ld_head, stream));
-#undef F
-        return CPX_OK;
-    }
-    // the tail of cpx_net_forward
-#define GEMM(A_, W_, N_, K_, EPI_, B_, OUT_, LD_) cpx_gemm_half(dt, A_, W_, M, N_, K_, EPI_, B_, nullptr, OUT_, LD_, nullptr, nullptr, nullptr, stream)
-    RUN(GEMM(x, w->neck0_w, NECK_C, NECK_K0, CPX_EPI_BF16, nullptr, y0, NECK_C));
-    RUN(cpx_layernorm_half(dt, y0, w->neck_ln1_w, w->neck_ln1_b, M, NECK_C, 1e-6f, a1, stream));
-    RUN(cpx_conv3_half(dt, a1, w->neck2_w, M, NECK_C, NECK_C, CPX_EPI_BF16, nullptr, y2, NECK_C, stream));
-    RUN(cpx_layernorm_half(dt, y2, w->neck_ln2_w, w->neck_ln2_b, M, NECK_C, 1e-6f, feat, stream));
-    RUN(GEMM(feat, w->head_w, w->ld_head, NECK_C, CPX_EPI_F32, w->head_b, head, w->ld_head));
-#undef GEMM
-#undef RUN
-    return CPX_OK;
+    return cpx_net_tail(w, x, nS, ws + L.off[0], ws + L.off[1], ws + L.off[2], ws + L.off[3], ws + L.off_col, head, nullptr, 0, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -193,15 +167,14 @@ extern "C" long long cpx_neck_grad_layout(long long *off) {
 // sink (the convolutions have no bias) and the weight-gradient partials | dCol
 struct NeckBwdLayout { size_t off[4], off_wt, off_ln, off_db, off_big, total; };
 static NeckBwdLayout neck_bwd_layout(int nS, int ld_head) {
-    NeckBwdLayout L; size_t o = 0; const size_t rows = (size_t)nS * 1024;
-    auto take = [&](size_t b) { size_t r = o; o = cpx_align_up(o + b, 256); return r; };
-    for (int i = 0; i < 4; ++i) L.off[i] = take(rows * NECK_C * sizeof(float));
-    L.off_wt = take((size_t)std::max(ld_head, NECK_K2) * NECK_C * sizeof(float));
-    L.off_ln = take(cpx_layernorm_backward_workspace_bytes((int)rows, NECK_C));
-    L.off_db = take(NECK_C * sizeof(float));
-    L.off_big = take(std::max(std::max(cpx_uwgrad_workspace_bytes(rows, NECK_C, NECK_K2), cpx_uwgrad_workspace_bytes(rows, NECK_C, NECK_K0)),
+    NeckBwdLayout L; CpxArena a; const size_t rows = (size_t)nS * 1024;
+    for (int i = 0; i < 4; ++i) L.off[i] = a.take(rows * NECK_C * sizeof(float));
+    L.off_wt = a.take((size_t)std::max(ld_head, NECK_K2) * NECK_C * sizeof(float));
+    L.off_ln = a.take(cpx_layernorm_backward_workspace_bytes((int)rows, NECK_C));
+    L.off_db = a.take(NECK_C * sizeof(float));
+    L.off_big = a.take(std::max(std::max(cpx_uwgrad_workspace_bytes(rows, NECK_C, NECK_K2), cpx_uwgrad_workspace_bytes(rows, NECK_C, NECK_K0)),
                               rows * NECK_K2 * sizeof(float)));
-    L.total = o;
+    L.total = a.o;
     return L;
 }
 extern "C" size_t cpx_neck_backward_workspace_bytes(int nS, int dtype, int ld_head, size_t *off) {

@@ -26,26 +26,8 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define UNET_MAX_OPS 64
 
-static inline int up128i(long long x) { return (int)((x + 127) / 128 * 128); }
-static inline int up64i(int x) { return (x + 63) / 64 * 64; }
 static inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 static inline bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-
-// GEMM view of an op: dY [rows][Npad] (kind 2: after space-to-depth), im2col(X) [rows][Kpad], W [Npad][Kpad]
-struct OpDims { int taps, ctot, Npad, Kpad, Kp128, ho, wo; size_t rows, rows_out; };
-static OpDims op_dims(const cpx_conv_op &o, int nS) {
-    OpDims d;
-    d.taps = o.kind == 0 ? 9 : (o.kind == 1 ? 4 : 1);
-    d.ctot = o.cin_a + o.cin_b;
-    d.Npad = up128i(o.kind == 2 ? 4 * o.cout : o.cout);
-    d.Kpad = up64i(d.taps * d.ctot);
-    d.Kp128 = up128i(d.Kpad);
-    d.ho = o.kind == 0 ? o.h : (o.kind == 1 ? o.h / 2 : o.h * 2);
-    d.wo = o.kind == 0 ? o.w : (o.kind == 1 ? o.w / 2 : o.w * 2);
-    d.rows = o.kind == 2 ? (size_t)nS * o.h * o.w : (size_t)nS * d.ho * d.wo;
-    d.rows_out = (size_t)nS * d.ho * d.wo;
-    return d;
-}
 
 // ---------------------------------------------------------------------------
 // weight gradient
@@ -246,27 +228,25 @@ int cpx_dx_gather_run(int dtype, const DxArgs &g, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // layouts
 // ---------------------------------------------------------------------------
-// workspace: [gradient tensor [rows_pad][up128(cout)] float32 of every op but the last][space-to-depth staging]
+// workspace: [gradient tensor [rows_out_pad][ld] float32 of every op but the last][space-to-depth staging]
 //            [transposed operand][weight-gradient partials | dCol]
 struct BwdLayout { size_t g_off[UNET_MAX_OPS]; int g_ld[UNET_MAX_OPS]; size_t g_bytes, s2d_off, wt_off, big_off, total; };
 static size_t uw_part_w_bytes(const OpDims &d) { return cpx_uwgrad_part_w_bytes(d.rows, d.Npad, d.Kpad); }
 static void bwd_layout(const cpx_conv_op *ops, int n_ops, int nS, BwdLayout &L) {
-    size_t off = 0, s2d = 0, wt = 0, big = 0;
+    CpxArena a; size_t s2d = 0, wt = 0, big = 0;
     for (int i = 0; i < n_ops; ++i) {
         const OpDims d = op_dims(ops[i], nS);
-        L.g_off[i] = off; L.g_ld[i] = up128i(ops[i].cout);
-        if (i < n_ops - 1) off += cpx_align_up((size_t)up128i((long long)d.rows_out) * L.g_ld[i] * sizeof(float), 256);
-        const size_t Mp = (size_t)up128i((long long)d.rows), n_slabs = (d.rows + UW_SLAB - 1) / UW_SLAB;
-        if (ops[i].kind == 2) s2d = std::max(s2d, Mp * d.Npad * sizeof(float));
+        L.g_off[i] = a.o; L.g_ld[i] = d.ld;
+        if (i < n_ops - 1) a.take((size_t)d.rows_out_pad * d.ld * sizeof(float));
+        if (ops[i].kind == 2) s2d = std::max(s2d, (size_t)d.rows_pad * d.Npad * sizeof(float));
         wt = std::max(wt, (size_t)d.Kp128 * d.Npad * sizeof(float));
-        big = std::max(big, uw_part_w_bytes(d) + cpx_align_up(n_slabs * d.Npad * sizeof(double), 256));
-        big = std::max(big, Mp * d.Kp128 * sizeof(float));
+        big = std::max(big, std::max(cpx_uwgrad_workspace_bytes(d.rows, d.Npad, d.Kpad), (size_t)d.rows_pad * d.Kp128 * sizeof(float)));
     }
-    L.g_bytes = off;
-    L.s2d_off = off;
-    L.wt_off = L.s2d_off + cpx_align_up(s2d, 256);
-    L.big_off = L.wt_off + cpx_align_up(wt, 256);
-    L.total = L.big_off + cpx_align_up(big, 256);
+    L.g_bytes = a.o;
+    L.s2d_off = a.take(s2d);
+    L.wt_off = a.take(wt);
+    L.big_off = a.take(big);
+    L.total = a.o;
 }
 static bool ops_ok(const cpx_conv_op *ops, int n_ops, int nS) {
     if (!ops || n_ops <= 0 || n_ops > UNET_MAX_OPS || nS <= 0 || ops[n_ops - 1].kind != 2) return false;
@@ -345,9 +325,8 @@ static int unet_backward(const cpx_conv_op *ops, int n_ops, const void *feat, in
     for (int t = 0; t <= n_ops; ++t) last_consumer[t] = -1;
     for (int i = n_ops - 1; i >= 0; --i) { last_consumer[ops[i].src_a] = i; if (ops[i].src_b >= 0) last_consumer[ops[i].src_b] = i; }
     for (int t = 1; t < n_ops; ++t) CPX_REQUIRE(last_consumer[t] >= 0);          // every tensor but the head is read by somebody
-    struct T { const void *p; int ld, c, h, w; };
-    auto tensor = [&](int id) -> T {
-        if (id == 0) return {feat, 256, 256, 32, 32};
+    auto tensor = [&](int id) -> CpxTensor {
+        if (id == 0) return {(const char *)feat, 256, 256, 32, 32};
         const cpx_conv_op &p = ops[id - 1];
         const OpDims d = op_dims(p, nS);
         return {fws + a_off[id - 1], a_ld[id - 1], p.cout, d.ho, d.wo};
@@ -357,7 +336,7 @@ static int unet_backward(const cpx_conv_op *ops, int n_ops, const void *feat, in
     for (int i = n_ops - 1; i >= 0; --i) {
         const cpx_conv_op &o = ops[i];
         const OpDims d = op_dims(o, nS);
-        const T A = tensor(o.src_a), Bz = {nullptr, 0, 0, 0, 0}, B = o.src_b >= 0 ? tensor(o.src_b) : Bz;
+        const CpxTensor A = tensor(o.src_a), Bz = {nullptr, 0, 0, 0, 0}, B = o.src_b >= 0 ? tensor(o.src_b) : Bz;
         CPX_REQUIRE(A.c == o.cin_a && A.h == o.h && A.w == o.w && (o.src_b < 0 || (B.c == o.cin_b && B.h == o.h && B.w == o.w)));
         CPX_REQUIRE(o.weight && d.rows < 0x7fffffffull);
         const int lh = ilog2(o.h), lw = ilog2(o.w);
@@ -380,12 +359,12 @@ static int unet_backward(const cpx_conv_op *ops, int n_ops, const void *feat, in
         if (o.src_a == 0 && o.src_b <= 0) continue;
         rc = cpx_wt_run(DT, o.weight, d.Npad, d.Kpad, d.Kp128, wt, s);
         if (rc) return rc;
-        rc = cpx_gemm_f32(dy, wt, up128i((long long)d.rows), d.Kp128, d.Npad, CPX_EPI_F32, nullptr, nullptr, big, d.Kp128, s);
+        rc = cpx_gemm_f32(dy, wt, d.rows_pad, d.Kp128, d.Npad, CPX_EPI_F32, nullptr, nullptr, big, d.Kp128, s);
         if (rc) return rc;
         for (int side = 0; side < 2; ++side) {
             const int id = side == 0 ? o.src_a : o.src_b;
             if (id <= 0) continue;
-            const T X = side == 0 ? A : B;
+            const CpxTensor X = side == 0 ? A : B;
             DxArgs g;
             g.dcol = big; g.ldc = d.Kp128; g.kind = o.kind; g.ctot = d.ctot; g.coff = side == 0 ? 0 : o.cin_a; g.C = X.c;
             g.lh = lh; g.lw = lw; g.rows_src = (size_t)nS * o.h * o.w;
