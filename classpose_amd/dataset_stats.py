@@ -6,7 +6,11 @@ The reference makes that pass on the host: ``get_class_counts`` / ``get_instance
 are host restatements of the reference functions of the same names (train_utils.py:439-496): a handful of float64 operations on
 ``n_classes`` numbers, pinned on the reference's own results by tests/golden/reference_label_stats.npz.
 
-Not built: ``label_instances=True`` of ``get_instance_counts`` (connected-component relabelling).
+``label_instances=True`` of ``get_instance_counts`` (``skimage.measure.label`` of every instance map before counting) and the
+reference's recipe for semantic-only sets (``ndimage.label`` per class, paper_experiments/run_cellpose_semantic.py:89-100) run on
+the device too: ``ops.label_components`` (csrc/cpx_components.hip) behind ``label_stats(label_instances=True)`` and
+``instances_from_classes``.  scikit-image is not a dependency, so both are restatements of the documented rule that are NOT
+pinned on skimage results: the tests compare with scipy.ndimage.label and a breadth-first fill (tests/components_reference.py).
 """
 from __future__ import annotations
 
@@ -61,14 +65,60 @@ def _chunk_to_device(x, lo: int, hi: int, dtype: torch.dtype, dev) -> torch.Tens
     return part.to(device=dev, dtype=dtype).contiguous()
 
 
-def label_stats(instances, classes, n_classes: int, device="cuda:0", chunk: int = 1024) -> LabelStats:
+def instances_from_classes(classes, connectivity: int = 4, device="cuda:0", chunk: int = 1024):
+    """Instance maps of a semantic-only set: ``classes`` (N, H, W) integer class maps (numpy or tensor; device tensors are used
+    where they are) -> ``(instances, n_components)``: an int32 (N, H, W) tensor on ``device`` and the (N,) int64 numpy counts.
+    Classes <= 0 become background first -- class 0 and the -100 of pixels that are not annotated -- and every connected region
+    of one class becomes one instance (``ops.label_components``, ``chunk`` images per call).  ``connectivity=4`` is the default
+    because it is ``ndimage.label``'s in the reference's recipe (run_cellpose_semantic.py:89-100).  The ids are in raster order
+    of each region's first pixel over all classes, where the reference numbers class after class: the PARTITION is the same,
+    and nothing downstream depends on the numbering.  Touching cells of one class are one instance.  Restated, not pinned on the
+    reference's output (module docstring)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("instances_from_classes runs HIP kernels: pass a cuda device (there is no CPU path)")
+    if len(classes.shape) != 3:
+        raise ValueError("instances_from_classes: classes are (N, H, W) maps")
+    if chunk < 1:
+        raise ValueError("instances_from_classes: chunk must be positive")
+    if connectivity not in (4, 8):
+        raise ValueError(f"instances_from_classes: connectivity must be 4 or 8, not {connectivity!r}")
+    N, H, W = (int(v) for v in classes.shape)
+    chunk = min(int(chunk), 65535)
+    out = torch.empty((N, H, W), dtype=torch.int32, device=dev)
+    counts = np.zeros(N, np.int64)
+    ws = None
+    if N:
+        nbytes = _lib.lib().cpx_label_components_workspace_bytes(min(chunk, N), H, W)
+        if nbytes == 0:
+            raise ValueError(f"instances_from_classes: unsupported H={H}, W={W} (H, W >= 1, H * W <= 2^28)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        part = _chunk_to_device(classes, lo, hi, torch.int32, dev).clamp_min(0)
+        lab, cnt = ops.label_components(part, connectivity, workspace=ws)
+        out[lo:hi] = lab
+        counts[lo:hi] = cnt.cpu().numpy()
+    return out, counts
+
+
+def label_stats(instances, classes, n_classes: int, device="cuda:0", chunk: int = 1024, label_instances: bool = False,
+                connectivity: int = 8) -> LabelStats:
     """Statistics of N training crops: ``instances`` / ``classes`` (N, H, W) integer numpy arrays or tensors (device tensors are
     used where they are).  The device pass runs on ``chunk`` images at a time, so its workspace (two hash tables of >= 2 * H * W
     slots and one area list per image: 2.75 MB per 256 x 256 crop) stays bounded.  Raises ``ValueError`` for a negative id or a
-    class >= ``n_classes``, naming the image."""
+    class >= ``n_classes``, naming the image.
+
+    ``label_instances=True`` is the reference's ``get_instance_counts(label_instances=True)`` (train_utils.py:407-436):
+    ``instance_counts`` are counted on ``label(instances)`` -- the connected components of equal non-zero id, background 0, full
+    connectivity (``connectivity=8``, skimage's default in 2-D) -- so one id on two separate blobs counts twice.
+    ``class_counts``, ``n_masks`` and ``diameters`` still come from the maps as given, as in the reference, which relabels only
+    inside ``get_instance_counts``.  Restated, not pinned on skimage (module docstring)."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("label_stats runs HIP kernels: pass a cuda device (there is no CPU path)")
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_stats: connectivity must be 4 or 8, not {connectivity!r}")
     if len(instances) != len(classes) or tuple(instances.shape) != tuple(classes.shape) or len(instances.shape) != 3:
         raise ValueError("label_stats: instances and classes are (N, H, W) maps of one shape")
     if chunk < 1:
@@ -79,17 +129,22 @@ def label_stats(instances, classes, n_classes: int, device="cuda:0", chunk: int 
     ipc = np.zeros((N, n_classes), np.int64)
     n_masks = np.zeros(N, np.int64)
     mid = np.zeros((N, 2), np.int64)
-    ws = None
+    ws = cc_ws = None
     if N:
         nbytes = _lib.lib().cpx_label_stats_workspace_bytes(min(chunk, N), H, W, int(n_classes))
         if nbytes == 0:
             raise ValueError(f"label_stats: unsupported H={H}, W={W}, n_classes={n_classes} (1 <= n_classes <= 64)")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        if label_instances:
+            cc_ws = torch.empty(_lib.lib().cpx_label_components_workspace_bytes(min(chunk, N), H, W), dtype=torch.uint8, device=dev)
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
-        out = ops.label_stats(_chunk_to_device(instances, lo, hi, torch.int32, dev),
-                              _chunk_to_device(classes, lo, hi, torch.int16, dev), n_classes, workspace=ws, check_status=False)
+        inst, cls = _chunk_to_device(instances, lo, hi, torch.int32, dev), _chunk_to_device(classes, lo, hi, torch.int16, dev)
+        out = ops.label_stats(inst, cls, n_classes, workspace=ws, check_status=False)
         px, ic, nm, ma, st = (t.cpu().numpy() for t in out)
+        if label_instances and not st.any():
+            relabelled, _ = ops.label_components(inst, connectivity, workspace=cc_ws)
+            ic = ops.label_stats(relabelled, cls, n_classes, workspace=ws, check_status=False)[1].cpu().numpy()
         bad = np.flatnonzero(st)
         if len(bad):
             what = "a negative instance id" if st[bad[0]] & 1 else f"a class >= {n_classes}"

@@ -22,6 +22,12 @@ oversampling probabilities (``--oversampling_method custom``), cell diameters (`
 (``--min_train_masks``).  The reference's ``run_training.py`` has class weights and ``custom`` oversampling ON by default; here all
 four are opt-in, so that a command line without them trains exactly as before.
 
+``--instances_from_labels [--instance_connectivity {4,8}]`` is for semantic-only sets, one class per pixel and no cell ids: the
+instance maps are the connected regions of one class, labelled on the device from ``--labels`` (and ``--test_labels``) by
+``dataset_stats.instances_from_classes`` -- the reference's recipe for such sets (``ndimage.label`` per class,
+paper_experiments/run_cellpose_semantic.py:89-100) -- and then used exactly as if ``--instances`` had been given.  Touching cells
+of one class merge into one instance.
+
 ``--data_path`` is the reference's data directory instead of the three arrays: ``images.npy`` with ``(H, W, 3)`` images of ANY size
 (an object array when they differ) and ``labels.npy`` with ``(H, W, 2)`` maps, channel 0 = instance, channel 1 = class
 (``classpose_amd.train_data``).  The images go to the device once (``augment.ImagePool``); with ``--augment`` every draw of an epoch
@@ -81,6 +87,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="class of pixels the warp takes from outside the crop: 0 = background as in the reference, -100 = not annotated")
     p.add_argument("--instances", default=None, help=".npy, (N,256,256) integer instance maps aligned with --labels (0 = background)")
     p.add_argument("--test_instances", default=None, help=".npy, instance maps of the validation set (its diameter range is logged)")
+    p.add_argument("--instances_from_labels", action="store_true",
+                   help="semantic-only sets: derive the instance maps on the device from --labels (and --test_labels) as the connected "
+                        "regions of one class, the reference's recipe for such sets; then everything that needs --instances works.  "
+                        "Touching cells of one class become one instance.  Not with --instances, --test_instances or --data_path")
+    p.add_argument("--instance_connectivity", type=int, default=None, choices=[4, 8],
+                   help="neighbourhood of --instances_from_labels: 4 = edges (the default, ndimage.label's in the reference's recipe), "
+                        "8 = corners too")
     p.add_argument("--oversampling_method", default="none", choices=["none", "custom"],
                    help="custom = draw every epoch with probabilities that favour crops with rare-class instances (the reference's "
                         "default; here the default is none, a plain permutation); needs --instances")
@@ -142,10 +155,20 @@ def check_args(args) -> None:
     if args.train_neck and getattr(args, "feature_transformation_structure", None) is not None:
         raise SystemExit("--train_neck: the neck does not train under a UNet class head (its backward gives the neck output no gradient)")
     args.train_flow_head = flow_head_from_freeze(getattr(args, "freeze", None), getattr(args, "train_flow_head", False))
-    if args.train_flow_head and args.data_path is None and args.instances is None:
-        raise SystemExit("--train_flow_head (--freeze backbone neck): needs --instances or --data_path")
-    if args.train_flow_head and args.data_path is None and args.test_images is not None and args.test_instances is None:
-        raise SystemExit("--train_flow_head with a validation set: needs --test_instances")
+    args.instances_from_labels = derive = bool(getattr(args, "instances_from_labels", False))
+    args.instance_connectivity = getattr(args, "instance_connectivity", None)
+    if derive:
+        clash = [f for f, v in (("--instances", args.instances), ("--test_instances", args.test_instances),
+                                ("--data_path", args.data_path)) if v is not None]
+        if clash:
+            raise SystemExit(f"--instances_from_labels derives the instance maps from --labels: not with {', '.join(clash)}"
+                             + (" (channel 0 of its labels already carries instances)" if "--data_path" in clash else ""))
+    elif args.instance_connectivity is not None:
+        raise SystemExit("--instance_connectivity goes with --instances_from_labels")
+    if args.train_flow_head and args.data_path is None and args.instances is None and not derive:
+        raise SystemExit("--train_flow_head (--freeze backbone neck): needs --instances or --data_path, or --instances_from_labels")
+    if args.train_flow_head and args.data_path is None and args.test_images is not None and args.test_instances is None and not derive:
+        raise SystemExit("--train_flow_head with a validation set: needs --test_instances or --instances_from_labels")
     fts = getattr(args, "feature_transformation_structure", None)
     if fts is not None and (len(fts) > 4 or min(fts) < 1):
         raise SystemExit("--feature_transformation_structure: 1 to 4 positive channel counts (32 x 32 tokens halve once per level "
@@ -173,8 +196,8 @@ def check_args(args) -> None:
                                    ("--oversampling_method custom", args.oversampling_method != "none"),
                                    ("--rescale", args.rescale), ("--min_train_masks", args.min_train_masks > 0),
                                    ("--test_instances", args.test_instances is not None)) if on]
-    if needs and args.instances is None:
-        raise SystemExit(f"{', '.join(needs)}: needs --instances")
+    if needs and args.instances is None and not derive:
+        raise SystemExit(f"{', '.join(needs)}: needs --instances or --instances_from_labels")
     if args.test_instances is not None and args.test_labels is None:
         raise SystemExit("--test_instances needs --test_images and --test_labels")
     if args.rescale and args.augment is None:
@@ -186,6 +209,24 @@ def _load_instances(path, labels, what: str) -> np.ndarray:
     if inst.shape != labels.shape or not np.issubdtype(inst.dtype, np.integer):
         raise SystemExit(f"{what}: expected integer instance maps {labels.shape}, got {inst.shape} {inst.dtype}")
     return inst
+
+
+def _derive_instances(labels, args, what: str):
+    """``--instances_from_labels``: the connected regions of one class, labelled on the device (dataset_stats.instances_from_classes);
+    the int32 maps stay there for the statistics."""
+    from .. import dataset_stats
+    if labels.ndim != 3 or not np.issubdtype(labels.dtype, np.integer):
+        raise SystemExit(f"{what}: --instances_from_labels expects (N, H, W) integer class maps, got {labels.shape} {labels.dtype}")
+    connectivity = 4 if args.instance_connectivity is None else args.instance_connectivity
+    inst, counts = dataset_stats.instances_from_classes(labels, connectivity, device=args.device)
+    logger.info(f"{what}: derived {int(counts.sum())} instances from {len(labels)} class maps ({connectivity}-connected regions of one "
+                f"class; {int(counts.min()) if len(counts) else 0} to {int(counts.max()) if len(counts) else 0} per map)")
+    return inst
+
+
+def _host_maps(instances):
+    """instance maps for the flow targets, which renumber ids on the host: derived maps come from the device"""
+    return instances.cpu().numpy() if hasattr(instances, "cpu") else instances
 
 
 def main_data_path(args) -> None:
@@ -271,14 +312,21 @@ def main(args) -> None:
                            class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
                            train_neck=args.train_neck)
     train_probs = diameters = instances = test_instances = None
-    if args.instances is not None:
-        instances = _load_instances(args.instances, labels, "--instances")
+    if args.instances_from_labels:
+        instances = _derive_instances(labels, args, "--labels")
+        if test_labels is not None:
+            test_instances = _derive_instances(test_labels, args, "--test_labels")
+        logger.warning("--instances_from_labels: touching cells of one class merge into one instance")
+    if instances is not None or args.instances is not None:
+        if instances is None:
+            instances = _load_instances(args.instances, labels, "--instances")
         stats = dataset_stats.label_stats(instances, labels, trainer.nclasses, device=args.device)
         diameters = dataset_stats.clamp_diameters(stats.diameters)                # train_utils.py:268
         logger.info(f"diameters: {diameters.min():.2f} to {diameters.max():.2f} px, masks per image: {int(stats.n_masks.min())} to "
                     f"{int(stats.n_masks.max())}")
-        if args.test_instances is not None:
-            test_instances = _load_instances(args.test_instances, test_labels, "--test_instances")
+        if args.test_instances is not None or test_instances is not None:
+            if test_instances is None:
+                test_instances = _load_instances(args.test_instances, test_labels, "--test_instances")
             tstats = dataset_stats.label_stats(test_instances, test_labels, trainer.nclasses, device=args.device)
             tdiam = dataset_stats.clamp_diameters(tstats.diameters)
             logger.info(f"test diameters: {tdiam.min():.2f} to {tdiam.max():.2f} px")
@@ -315,8 +363,8 @@ def main(args) -> None:
         save_path=args.save_path, model_name=args.model_name, random_seed=args.random_seed,
         augment=args.augment, scale_range=args.scale_range, label_fill=args.augment_label_fill, train_probs=train_probs,
         diameters=diameters if args.rescale else None, diam_mean=args.diam_mean, rescale=args.rescale,
-        train_flow_head=args.train_flow_head, instances=instances if args.train_flow_head else None,
-        test_instances=test_instances if args.train_flow_head else None)
+        train_flow_head=args.train_flow_head, instances=_host_maps(instances) if args.train_flow_head else None,
+        test_instances=_host_maps(test_instances) if args.train_flow_head else None)
     if args.save_only_trainable_params:
         trainer.save(path, save_only_trainable_params=True)
     logger.info(f"final train loss {train_losses[-1]:.4f}" + (f", test loss {test_losses[-1]:.4f}" if test_images is not None else ""))

@@ -1385,3 +1385,39 @@ def ids_to_classes(inst: torch.Tensor, class_of) -> torch.Tensor:
         raise ValueError(f"ids_to_classes: ids span {lo}..{hi} but class_of covers 0..{n_ids}")
     check(_lib.lib().cpx_ids_to_classes(ptr(inst), inst.numel(), ptr(class_of), n_ids, ptr(cls), _stream(dev)), "ids_to_classes")
     return cls
+
+
+# ---- r2: value maps -> instance maps by connected components (csrc/cpx_components.hip) ------------------------------
+COMPONENTS_TILE = 64                 # CC_TILE: the tile side the device tests probe both sides of (pinned on the source)
+COMPONENTS_MAX_PIXELS = 1 << 28      # CC_MAX_PX: H * W limit
+
+
+def label_components(maps: torch.Tensor, connectivity: int = 8, workspace: torch.Tensor | None = None):
+    """``cpx_label_components`` on device maps: maps (n, H, W) int32, 0 = background, every other value (negatives included) is
+    foreground; neighbouring pixels of equal value are connected, by edges (``connectivity=4``) or edges and corners (8).
+    Returns two device tensors ``(labels (n, H, W) int32, n_components (n,) int32)``: per image, 0 on background and the
+    component's 1-based rank by the raster index of its first pixel -- the numbering of ``skimage.measure.label`` and
+    ``scipy.ndimage.label``.  ``workspace``: a uint8 device tensor of at least ``cpx_label_components_workspace_bytes`` to reuse
+    between calls (allocated here when absent or too small)."""
+    if not isinstance(maps, torch.Tensor) or maps.dtype != torch.int32 or maps.dim() != 3:
+        raise ValueError("label_components: maps must be an int32 (n, H, W) tensor")
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_components: connectivity must be 4 or 8, not {connectivity!r}")
+    if not maps.is_cuda:
+        raise ValueError("label_components: maps must be on a cuda device")
+    maps = maps.contiguous()
+    n, H, W = maps.shape
+    dev = maps.device
+    labels = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+    n_components = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return labels, n_components
+    L = _lib.lib()
+    nbytes = L.cpx_label_components_workspace_bytes(n, H, W)
+    if nbytes == 0:
+        raise ValueError(f"label_components: unsupported arguments n={n}, H={H}, W={W} (n <= 65535, H, W >= 1, H * W <= 2^28)")
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev or workspace.dtype != torch.uint8:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.cpx_label_components(ptr(maps), n, H, W, int(connectivity), ptr(labels), ptr(n_components), ptr(workspace),
+                                 workspace.numel(), _stream(dev)), "label_components")
+    return labels, n_components

@@ -161,9 +161,11 @@ def stats_chunk(H: int, W: int, n_classes: int, budget_bytes: int) -> int:
     return chunk
 
 
-def ragged_label_stats(instances, classes, n_classes: int, device="cuda:0", budget_bytes: int = 1 << 30):
+def ragged_label_stats(instances, classes, n_classes: int, device="cuda:0", budget_bytes: int = 1 << 30,
+                       label_instances: bool = False, connectivity: int = 8):
     """``dataset_stats.label_stats`` of maps of any sizes: one call per group of equal shape, each with the ``stats_chunk`` of its
-    shape, the per-image results scattered back into the order of the lists.  Returns a ``LabelStats``."""
+    shape, the per-image results scattered back into the order of the lists.  ``label_instances`` / ``connectivity`` are those of
+    ``dataset_stats.label_stats`` (instance counts of the connected components of every instance map).  Returns a ``LabelStats``."""
     from . import dataset_stats
     N = len(instances)
     groups: dict = {}
@@ -173,7 +175,8 @@ def ragged_label_stats(instances, classes, n_classes: int, device="cuda:0", budg
     ipc, n_masks, diam = np.zeros((N, n_classes), np.float64), np.zeros(N, np.int64), np.zeros(N, np.float64)
     for (H, W), idx in groups.items():
         st = dataset_stats.label_stats(np.stack([instances[i] for i in idx]), np.stack([classes[i] for i in idx]), n_classes,
-                                       device=device, chunk=stats_chunk(H, W, n_classes, budget_bytes))
+                                       device=device, chunk=stats_chunk(H, W, n_classes, budget_bytes),
+                                       label_instances=label_instances, connectivity=connectivity)
         class_counts += st.class_counts
         ipc[idx], n_masks[idx], diam[idx] = st.instance_counts, st.n_masks, st.diameters
     return dataset_stats.LabelStats(class_counts, ipc, n_masks, diam)

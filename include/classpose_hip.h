@@ -935,6 +935,34 @@ int cpx_rasterize_polygons(const double *xy, const long long *ring_off, const in
 int cpx_ids_to_classes(const int *inst, long long n_px, const unsigned char *class_of, int n_ids, unsigned char *cls,
                        void *stream);
 
+/* ------------------------------------------------------------------------
+ * r2  class or value maps -> instance maps by connected-component labelling (csrc/cpx_components.hip)
+ * replaces the host labelling of semantic-only annotations: `ndimage.label` per class in
+ * paper_experiments/run_cellpose_semantic.py:89-100 of the reference and `skimage.measure.label` behind
+ * get_instance_counts(label_instances=True) (classpose/train_utils.py:407-436).  Runs on `stream`, allocates nothing, integer
+ * atomics only: every output is an exact integer that does not depend on scheduling, so it is bitwise reproducible.
+ * ---------------------------------------------------------------------- */
+/* cpx_label_components: map [n][H][W] int32; 0 is background, EVERY other value is foreground, negatives included (the rule of
+ *   skimage.measure.label with background 0, restated here and not pinned against scikit-image).
+ *   THE RULE.  Two pixels are connected when they are neighbours and carry the same non-zero value.  connectivity 4: the edge
+ *   neighbours; connectivity 8: the corner neighbours too; any other connectivity is refused.  A component is a maximal set of
+ *   pixels connected through such steps.
+ *   labels [n][H][W]   0 on background; on foreground the component's 1-based rank among the components of ITS image, ordered
+ *                      by the raster index r * W + c of each component's first pixel -- the numbering of skimage.measure.label
+ *                      and scipy.ndimage.label.  labels may not alias map.
+ *   n_components [n]   the count per image (the largest label of the image).
+ *   1 <= n <= 65535, H, W >= 1, H * W <= 2^28; image offsets are 64-bit.  Anything else returns non-zero and the workspace query
+ *   returns 0, except that n == 0 is a successful no-op of the entry without a launch (its query still answers 0).
+ *   Six launches, each a phase the next one needs complete; no workgroup ever waits for another.  Tiles of 64 x 64 pixels are
+ *   labelled in LDS, the tile seams are merged by union-find on global parents with agent-scope integer atomic minima (the
+ *   smaller index always becomes the parent, so a component's root is its raster-first pixel whatever the order of the unions),
+ *   the roots are counted and ranked by a per-image scan in raster order.  The workspace holds one int32 parent per pixel and one
+ *   count per 4096 pixels; every word read is written first, so it need not be cleared.  cpx_label_components_workspace_bytes
+ *   is host only and returns 0 for arguments the entry would refuse.                                                          */
+size_t cpx_label_components_workspace_bytes(int n, int H, int W);
+int cpx_label_components(const int32_t *map, int n, int H, int W, int connectivity, int32_t *labels, int32_t *n_components,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 
 #ifdef __cplusplus
 }
