@@ -1579,7 +1579,10 @@ __global__ void k_class_count(const int32_t *__restrict__ masks, const float *__
         int bi = 0;
         for (int c = 1; c < ncls; ++c) {
             float v = lg[(size_t)c * lay.HW];
-            if (v > best) { best = v; bi = c; }        // first maximum wins (np.argmax)
+            // np.argmax: the first maximum wins, a NaN beats every number and the first NaN wins.  !(v <= best) is v > best or v is a
+            // NaN; two compares and two selects, no branch, and for numbers the same choice as v > best
+            const bool take = !(v <= best) & (best == best);
+            best = take ? v : best; bi = take ? c : bi;
         }
         const int k = lab * PP_MAXCLS + bi;
         const int sl = lh_slot(key, k + 1);
@@ -1856,7 +1859,10 @@ __global__ void __launch_bounds__(NTHR) k_class_count_f(int32_t *__restrict__ ma
         int bi = 0;
         for (int c = 1; c < ncls; ++c) {
             float v = lg[(size_t)c * lay.HW];
-            if (v > best) { best = v; bi = c; }        // first maximum wins (np.argmax)
+            // np.argmax: the first maximum wins, a NaN beats every number and the first NaN wins.  !(v <= best) is v > best or v is a
+            // NaN; two compares and two selects, no branch, and for numbers the same choice as v > best
+            const bool take = !(v <= best) & (best == best);
+            best = take ? v : best; bi = take ? c : bi;
         }
         const int k = lab * PP_MAXCLS + bi;
         const int sl = lh_slot(key, k + 1);

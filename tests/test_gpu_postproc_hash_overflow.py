@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import polygon_shapes as ps
+from postproc_shapes import _guaranteed_misses, _home
 from classpose_amd import _lib, engine, ops
 from classpose_amd._lib import ptr
 from oracle import classmask, dynamics
@@ -24,18 +25,6 @@ NCLS = 7
 LH_SLOTS, LH_PROBES, PP_MAXCLS = 256, 8, 32
 STATS_WG, VOTE_WG = 2048, 256                   # pixels per workgroup: the label-run passes (8 per thread), the class vote (1 per thread)
 WIN_LO, WIN_K = 99, 61                          # the window of home slots the map's labels come from
-
-
-def _home(key):
-    return ((int(key) * 2654435761) & 0xFFFFFFFF) >> 24
-
-
-def _guaranteed_misses(keys):
-    """the largest, over the windows [s, s + k) of home slots, of #keys in the window - (k + 7): a lower bound of the
-    updates that find no slot"""
-    per_slot = np.bincount([_home(k) for k in set(int(k) for k in keys)], minlength=LH_SLOTS)
-    below = np.concatenate([[0], np.cumsum(per_slot)])
-    return max(int(below[s + k] - below[s]) - (k + LH_PROBES - 1) for s in range(LH_SLOTS) for k in range(1, LH_SLOTS - s + 1))
 
 
 @pytest.fixture(scope="module")
