@@ -179,6 +179,9 @@ SIGNATURES = {
     "cpx_ids_to_classes": (_i, [_p, C.c_longlong, _p, _i, _p, _p]),
     "cpx_label_components_workspace_bytes": (_sz, [_i, _i, _i]),
     "cpx_label_components": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "cpx_distance_sq": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
+    "cpx_split_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "cpx_split_touching": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cpx_pool_byte_sums": (_i, [_p, _p, _p, _i, C.c_longlong, _p, _p, _p]),
     "cpx_warp_affine_pool_u8": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "cpx_stain_samples_workspace_bytes": (_sz, [_i, C.c_longlong]),

@@ -60,3 +60,25 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
     bf16_t b = (bf16_t)f;
     return *reinterpret_cast<unsigned short *>(&b);
 }
+
+// inclusive sum over a workgroup of 256 threads, every thread calling; *total = the sum of all 256 values.  s_w: 4 ints of LDS.
+__device__ __forceinline__ int cpx_block_scan256(int v, int *s_w, int *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) off += s_w[w];
+        tot += s_w[w];
+    }
+    __syncthreads();
+    *total = tot;
+    return incl + off;
+}

@@ -36,7 +36,7 @@
 #define CC_IDX(l) ((l) + ((l) >> 4))
 
 static_assert(CC_TILE * CC_TILE == CC_TILE_PX && CC_THR * CC_STRIP == CC_TILE_PX && CC_TILE % CC_STRIP == 0, "tile geometry");
-static_assert(CC_BLOCK % CC_THR == 0, "block geometry");
+static_assert(CC_BLOCK % CC_THR == 0 && CC_THR == 256, "block geometry (cpx_block_scan256)");
 
 struct CcArgs {
     const int32_t *map;
@@ -195,28 +195,6 @@ __global__ void __launch_bounds__(CC_THR) k_cc_roots(CcArgs a) {
     if (tid == 0) a.sums[(size_t)img * a.nblk + blockIdx.x] = s_cnt;
 }
 
-// inclusive sum over the workgroup's CC_THR values; *total = the sum of all of them.  s_w: CC_THR / 64 ints of LDS.
-__device__ __forceinline__ int cc_block_scan(int v, int *s_w, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(incl, o);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < CC_THR / 64; ++w) {
-        if (w < wave) off += s_w[w];
-        tot += s_w[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return incl + off;
-}
-
 __global__ void __launch_bounds__(CC_THR) k_cc_offsets(CcArgs a) {           // one workgroup per image: the scan stays inside it
     __shared__ int s_w[CC_THR / 64];
     const int tid = threadIdx.x, img = blockIdx.x;
@@ -225,7 +203,7 @@ __global__ void __launch_bounds__(CC_THR) k_cc_offsets(CcArgs a) {           // 
     for (int c0 = 0; c0 < a.nblk; c0 += CC_THR) {
         const int i = c0 + tid, v = i < a.nblk ? sums[i] : 0;
         int tot;
-        const int incl = cc_block_scan(v, s_w, &tot);
+        const int incl = cpx_block_scan256(v, s_w, &tot);
         if (i < a.nblk) sums[i] = carry + incl - v;
         carry += tot;
     }
@@ -241,7 +219,7 @@ __global__ void __launch_bounds__(CC_THR) k_cc_rank(CcArgs a) {
         const int p = blockIdx.x * CC_BLOCK + j * CC_THR + tid;
         const int flag = (p < a.HW && par[p] == p) ? 1 : 0;                  // its own parent: a component's first pixel
         int tot;
-        const int incl = cc_block_scan(flag, s_w, &tot);
+        const int incl = cpx_block_scan256(flag, s_w, &tot);
         if (flag) par[p] = -(running + incl);                               // 1-based rank, negated: no parent is negative
         running += tot;
     }

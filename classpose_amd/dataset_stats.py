@@ -11,6 +11,10 @@ reference's recipe for semantic-only sets (``ndimage.label`` per class, paper_ex
 the device too: ``ops.label_components`` (csrc/cpx_components.hip) behind ``label_stats(label_instances=True)`` and
 ``instances_from_classes``.  scikit-image is not a dependency, so both are restatements of the documented rule that are NOT
 pinned on skimage results: the tests compare with scipy.ndimage.label and a breadth-first fill (tests/components_reference.py).
+
+``split_touching=True`` of both cuts the regions that hold several touching cells: the peaks of the exact squared distance map
+are seeds and every pixel goes to the nearest seed of its own region (``ops.split_touching``, csrc/cpx_split.hip).
+An integer rule of this project's own, restated by tests/split_reference.py; not scikit-image's ``peak_local_max`` + ``watershed``.
 """
 from __future__ import annotations
 
@@ -65,7 +69,8 @@ def _chunk_to_device(x, lo: int, hi: int, dtype: torch.dtype, dev) -> torch.Tens
     return part.to(device=dev, dtype=dtype).contiguous()
 
 
-def instances_from_classes(classes, connectivity: int = 4, device="cuda:0", chunk: int = 1024):
+def instances_from_classes(classes, connectivity: int = 4, device="cuda:0", chunk: int = 1024, split_touching: bool = False,
+                           min_distance: int = 5, min_radius: int = 2):
     """Instance maps of a semantic-only set: ``classes`` (N, H, W) integer class maps (numpy or tensor; device tensors are used
     where they are) -> ``(instances, n_components)``: an int32 (N, H, W) tensor on ``device`` and the (N,) int64 numpy counts.
     Classes <= 0 become background first -- class 0 and the -100 of pixels that are not annotated -- and every connected region
@@ -73,7 +78,10 @@ def instances_from_classes(classes, connectivity: int = 4, device="cuda:0", chun
     because it is ``ndimage.label``'s in the reference's recipe (run_cellpose_semantic.py:89-100).  The ids are in raster order
     of each region's first pixel over all classes, where the reference numbers class after class: the PARTITION is the same,
     and nothing downstream depends on the numbering.  Touching cells of one class are one instance.  Restated, not pinned on the
-    reference's output (module docstring)."""
+    reference's output (module docstring).
+
+    ``split_touching=True`` then cuts every region at its distance peaks (``ops.split_touching`` with ``min_distance``,
+    ``min_radius`` and the same ``connectivity``); the counts are those after the cut.  ``False`` is exactly the above."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("instances_from_classes runs HIP kernels: pass a cuda device (there is no CPU path)")
@@ -97,13 +105,28 @@ def instances_from_classes(classes, connectivity: int = 4, device="cuda:0", chun
         hi = min(N, lo + chunk)
         part = _chunk_to_device(classes, lo, hi, torch.int32, dev).clamp_min(0)
         lab, cnt = ops.label_components(part, connectivity, workspace=ws)
+        if split_touching:
+            lab, cnt = ops.split_touching(lab, min_distance, min_radius, connectivity)
         out[lo:hi] = lab
         counts[lo:hi] = cnt.cpu().numpy()
     return out, counts
 
 
+def split_summary(before: torch.Tensor, after: torch.Tensor):
+    """``(components, split, instances)`` of instance maps before and after ``split_touching``: how many components there were,
+    how many of them were cut, and how many instances there are now.  Both (N, H, W) int32 on one device; a report, not a hot
+    path (``torch.unique`` over the (image, before, after) triples)."""
+    fg = before > 0
+    img = torch.arange(before.shape[0], device=before.device).view(-1, 1, 1).expand_as(before)[fg].long()
+    b, a = before[fg].long(), after[fg].long()
+    nb, na = int(before.max()) + 1 if b.numel() else 1, int(after.max()) + 1 if b.numel() else 1
+    pairs = torch.unique((img * nb + b) * na + a)
+    pieces = torch.unique(pairs // na, return_counts=True)[1]
+    return int(pieces.numel()), int((pieces > 1).sum()), int(pairs.numel())
+
+
 def label_stats(instances, classes, n_classes: int, device="cuda:0", chunk: int = 1024, label_instances: bool = False,
-                connectivity: int = 8) -> LabelStats:
+                connectivity: int = 8, split_touching: bool = False, min_distance: int = 5, min_radius: int = 2) -> LabelStats:
     """Statistics of N training crops: ``instances`` / ``classes`` (N, H, W) integer numpy arrays or tensors (device tensors are
     used where they are).  The device pass runs on ``chunk`` images at a time, so its workspace (two hash tables of >= 2 * H * W
     slots and one area list per image: 2.75 MB per 256 x 256 crop) stays bounded.  Raises ``ValueError`` for a negative id or a
@@ -113,10 +136,16 @@ def label_stats(instances, classes, n_classes: int, device="cuda:0", chunk: int 
     ``instance_counts`` are counted on ``label(instances)`` -- the connected components of equal non-zero id, background 0, full
     connectivity (``connectivity=8``, skimage's default in 2-D) -- so one id on two separate blobs counts twice.
     ``class_counts``, ``n_masks`` and ``diameters`` still come from the maps as given, as in the reference, which relabels only
-    inside ``get_instance_counts``.  Restated, not pinned on skimage (module docstring)."""
+    inside ``get_instance_counts``.  Restated, not pinned on skimage (module docstring).
+
+    ``split_touching=True`` goes with ``label_instances=True``: the relabelled components are cut at their distance peaks
+    (``ops.split_touching`` with ``min_distance`` and ``min_radius``) before ``instance_counts`` are counted, so three touching
+    cells of one id count three times.  ``False`` is exactly the above."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("label_stats runs HIP kernels: pass a cuda device (there is no CPU path)")
+    if split_touching and not label_instances:
+        raise ValueError("label_stats: split_touching goes with label_instances=True")
     if connectivity not in (4, 8):
         raise ValueError(f"label_stats: connectivity must be 4 or 8, not {connectivity!r}")
     if len(instances) != len(classes) or tuple(instances.shape) != tuple(classes.shape) or len(instances.shape) != 3:
@@ -144,6 +173,8 @@ def label_stats(instances, classes, n_classes: int, device="cuda:0", chunk: int 
         px, ic, nm, ma, st = (t.cpu().numpy() for t in out)
         if label_instances and not st.any():
             relabelled, _ = ops.label_components(inst, connectivity, workspace=cc_ws)
+            if split_touching:
+                relabelled, _ = ops.split_touching(relabelled, min_distance, min_radius, connectivity)
             ic = ops.label_stats(relabelled, cls, n_classes, workspace=ws, check_status=False)[1].cpu().numpy()
         bad = np.flatnonzero(st)
         if len(bad):

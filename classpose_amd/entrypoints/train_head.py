@@ -26,7 +26,10 @@ four are opt-in, so that a command line without them trains exactly as before.
 instance maps are the connected regions of one class, labelled on the device from ``--labels`` (and ``--test_labels``) by
 ``dataset_stats.instances_from_classes`` -- the reference's recipe for such sets (``ndimage.label`` per class,
 paper_experiments/run_cellpose_semantic.py:89-100) -- and then used exactly as if ``--instances`` had been given.  Touching cells
-of one class merge into one instance.
+of one class merge into one instance.  ``--split_touching_cells [--split_min_distance D] [--split_min_radius R]`` cuts them apart on
+the device (``ops.split_touching``): the peaks of each region's exact squared distance map that lie at least R pixels
+(default 2) inside it and that nothing within D pixels (default 5) beats are seeds, and every pixel goes to the nearest seed of its
+own region -- straight cuts, no flooding.
 
 ``--data_path`` is the reference's data directory instead of the three arrays: ``images.npy`` with ``(H, W, 3)`` images of ANY size
 (an object array when they differ) and ``labels.npy`` with ``(H, W, 2)`` maps, channel 0 = instance, channel 1 = class
@@ -94,6 +97,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--instance_connectivity", type=int, default=None, choices=[4, 8],
                    help="neighbourhood of --instances_from_labels: 4 = edges (the default, ndimage.label's in the reference's recipe), "
                         "8 = corners too")
+    p.add_argument("--split_touching_cells", action="store_true",
+                   help="with --instances_from_labels: cut regions that hold several touching cells at the peaks of their distance "
+                        "map, every pixel to the nearest peak of its own region (straight cuts, not a flooding watershed)")
+    p.add_argument("--split_min_distance", type=int, default=None,
+                   help="--split_touching_cells: two peaks of one region closer than this many pixels (Chebyshev) are one cell (default 5)")
+    p.add_argument("--split_min_radius", type=int, default=None,
+                   help="--split_touching_cells: a peak counts only this many pixels or more inside its region (default 2)")
     p.add_argument("--oversampling_method", default="none", choices=["none", "custom"],
                    help="custom = draw every epoch with probabilities that favour crops with rare-class instances (the reference's "
                         "default; here the default is none, a plain permutation); needs --instances")
@@ -165,6 +175,20 @@ def check_args(args) -> None:
                              + (" (channel 0 of its labels already carries instances)" if "--data_path" in clash else ""))
     elif args.instance_connectivity is not None:
         raise SystemExit("--instance_connectivity goes with --instances_from_labels")
+    args.split_touching_cells = split = bool(getattr(args, "split_touching_cells", False))
+    args.split_min_distance = getattr(args, "split_min_distance", None)
+    args.split_min_radius = getattr(args, "split_min_radius", None)
+    if split and not derive:
+        raise SystemExit("--split_touching_cells goes with --instances_from_labels")
+    for flag, value, limit in (("--split_min_distance", args.split_min_distance, "SPLIT_MAX_MIN_DISTANCE"),
+                               ("--split_min_radius", args.split_min_radius, "SPLIT_MAX_MIN_RADIUS")):
+        if value is None:
+            continue
+        if not split:
+            raise SystemExit(f"{flag} goes with --instances_from_labels --split_touching_cells")
+        from .. import ops
+        if not 1 <= value <= getattr(ops, limit):
+            raise SystemExit(f"{flag}: 1 to {getattr(ops, limit)} pixels, not {value}")
     if args.train_flow_head and args.data_path is None and args.instances is None and not derive:
         raise SystemExit("--train_flow_head (--freeze backbone neck): needs --instances or --data_path, or --instances_from_labels")
     if args.train_flow_head and args.data_path is None and args.test_images is not None and args.test_instances is None and not derive:
@@ -221,6 +245,15 @@ def _derive_instances(labels, args, what: str):
     inst, counts = dataset_stats.instances_from_classes(labels, connectivity, device=args.device)
     logger.info(f"{what}: derived {int(counts.sum())} instances from {len(labels)} class maps ({connectivity}-connected regions of one "
                 f"class; {int(counts.min()) if len(counts) else 0} to {int(counts.max()) if len(counts) else 0} per map)")
+    if args.split_touching_cells:
+        md = 5 if args.split_min_distance is None else args.split_min_distance
+        mr = 2 if args.split_min_radius is None else args.split_min_radius
+        cut, _ = dataset_stats.instances_from_classes(labels, connectivity, device=args.device, split_touching=True, min_distance=md,
+                                                      min_radius=mr)
+        n_comp, n_split, n_inst = dataset_stats.split_summary(inst, cut)
+        logger.info(f"{what}: --split_touching_cells cut {n_split} of {n_comp} components into pieces, {n_inst} instances in all "
+                    f"(min_distance {md}, min_radius {mr})")
+        inst = cut
     return inst
 
 
@@ -316,7 +349,8 @@ def main(args) -> None:
         instances = _derive_instances(labels, args, "--labels")
         if test_labels is not None:
             test_instances = _derive_instances(test_labels, args, "--test_labels")
-        logger.warning("--instances_from_labels: touching cells of one class merge into one instance")
+        if not args.split_touching_cells:
+            logger.warning("--instances_from_labels: touching cells of one class merge into one instance")
     if instances is not None or args.instances is not None:
         if instances is None:
             instances = _load_instances(args.instances, labels, "--instances")

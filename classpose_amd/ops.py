@@ -1421,3 +1421,81 @@ def label_components(maps: torch.Tensor, connectivity: int = 8, workspace: torch
     check(L.cpx_label_components(ptr(maps), n, H, W, int(connectivity), ptr(labels), ptr(n_components), ptr(workspace),
                                  workspace.numel(), _stream(dev)), "label_components")
     return labels, n_components
+
+
+# ---- r3: touching cells of one class -> separate instances by distance peaks (csrc/cpx_split.hip) --------------------
+SPLIT_MAX_DIAG2 = 1 << 30            # SP_MAX_DIAG2: H * H + W * W limit, so that squared distances and their sums are int32
+SPLIT_MAX_MIN_DISTANCE = 64          # SP_MAX_WINDOW
+SPLIT_MAX_MIN_RADIUS = 32768         # SP_MAX_RADIUS
+
+
+def _split_maps(inst, what: str) -> torch.Tensor:
+    if not isinstance(inst, torch.Tensor) or inst.dtype != torch.int32 or inst.dim() != 3:
+        raise ValueError(f"{what}: inst must be an int32 (n, H, W) tensor")
+    if not inst.is_cuda:
+        raise ValueError(f"{what}: inst must be on a cuda device")
+    n, H, W = inst.shape
+    if n and not (n <= 65535 and H >= 1 and W >= 1 and H * W <= COMPONENTS_MAX_PIXELS and H * H + W * W <= SPLIT_MAX_DIAG2):
+        raise ValueError(f"{what}: unsupported arguments n={n}, H={H}, W={W} (n <= 65535, H, W >= 1, H * W <= 2^28, "
+                         "H * H + W * W <= 2^30)")
+    return inst.contiguous()
+
+
+def distance_sq(inst: torch.Tensor) -> torch.Tensor:
+    """``cpx_distance_sq`` on device maps: inst (n, H, W) int32 -> (n, H, W) int32, per pixel of value v != 0 the exact squared
+    Euclidean distance to the nearest pixel of its image with another value (0 included), ``H * H + W * W`` where the image holds
+    no other value, 0 on pixels of value 0.  The image border is not a site."""
+    inst = _split_maps(inst, "distance_sq")
+    n, H, W = inst.shape
+    d2 = torch.empty((n, H, W), dtype=torch.int32, device=inst.device)
+    if n == 0:
+        return d2
+    ws = torch.empty((n, H, W), dtype=torch.int32, device=inst.device)
+    check(_lib.lib().cpx_distance_sq(ptr(inst), n, H, W, ptr(d2), ptr(ws), ws.numel() * 4, _stream(inst.device)), "distance_sq")
+    return d2
+
+
+def split_touching(inst: torch.Tensor, min_distance: int = 5, min_radius: int = 2, connectivity: int = 8,
+                   seed_cap: int | None = None, return_seeds: bool = False):
+    """``cpx_split_touching`` on device instance maps: inst (n, H, W) int32, 0 = background, ids 1 .. H * W as
+    ``label_components`` writes them.  The peaks of the squared distance map (``distance_sq``) that are at least ``min_radius``
+    from the instance's edge and that no pixel of the same instance within ``min_distance`` (Chebyshev) beats are seeds; an
+    instance with two or more seeds is cut into its seeds' Euclidean Voronoi cells; ``label_components`` with ``connectivity``
+    numbers the result.  Returns two device tensors ``(labels (n, H, W) int32, counts (n,) int32)``; with ``return_seeds`` also a
+    list of n int32 device tensors, the raster indices of each image's seeds by (instance id, raster index).  The seed lists
+    start at ``seed_cap`` entries per image (default: max(1024, H * W / 16)); when an image has more, the call is repeated once
+    with the largest count it reported.  The input is not modified."""
+    inst = _split_maps(inst, "split_touching")
+    if connectivity not in (4, 8):
+        raise ValueError(f"split_touching: connectivity must be 4 or 8, not {connectivity!r}")
+    if not 1 <= int(min_distance) <= SPLIT_MAX_MIN_DISTANCE:
+        raise ValueError(f"split_touching: min_distance must be in 1..{SPLIT_MAX_MIN_DISTANCE}, not {min_distance!r}")
+    if not 1 <= int(min_radius) <= SPLIT_MAX_MIN_RADIUS:
+        raise ValueError(f"split_touching: min_radius must be in 1..{SPLIT_MAX_MIN_RADIUS}, not {min_radius!r}")
+    n, H, W = inst.shape
+    dev = inst.device
+    labels = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return (labels, counts, []) if return_seeds else (labels, counts)
+    L = _lib.lib()
+    cap = min(H * W, max(1024, H * W // 16) if seed_cap is None else max(1, int(seed_cap)))
+    while True:
+        ws = torch.empty(L.cpx_split_workspace_bytes(n, H, W, cap), dtype=torch.uint8, device=dev)
+        seeds = torch.empty((n, cap), dtype=torch.int32, device=dev)
+        n_seeds = torch.empty(n, dtype=torch.int32, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        check(L.cpx_split_touching(ptr(inst), n, H, W, int(min_distance), int(min_radius), int(connectivity), cap, ptr(labels),
+                                   ptr(counts), ptr(seeds), ptr(n_seeds), ptr(status), ptr(ws), ws.numel(), _stream(dev)),
+              "split_touching")
+        st, ns = status.cpu().numpy(), n_seeds.cpu().numpy()
+        if (st & 2).any():
+            raise ValueError(f"split_touching: image {int(np.flatnonzero(st & 2)[0])} has an instance id outside 0..{H * W}")
+        if not st.any():
+            break
+        if int(ns.max()) <= cap:
+            raise RuntimeError(f"split_touching: status {st.tolist()} with {int(ns.max())} seeds in lists of {cap}")
+        cap = int(ns.max())                                             # <= H * W: one seed per pixel at the most
+    if return_seeds:
+        return labels, counts, [seeds[k, :int(ns[k])] for k in range(n)]
+    return labels, counts

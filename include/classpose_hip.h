@@ -963,6 +963,46 @@ size_t cpx_label_components_workspace_bytes(int n, int H, int W);
 int cpx_label_components(const int32_t *map, int n, int H, int W, int connectivity, int32_t *labels, int32_t *n_components,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * r3  touching cells of one class -> separate instances: distance peaks (csrc/cpx_split.hip)
+ * The connected regions that r2 makes of a class map merge cells that touch.  These entries split them by a rule stated in
+ * integers alone (restated on the CPU by tests/split_reference.py; NOT pinned against scikit-image's peak_local_max or
+ * watershed, which is not a dependency).  They run on `stream`, allocate nothing, use integer arithmetic and integer atomics
+ * only, and no workgroup ever waits for another: every output is a function of the map alone, bitwise reproducible.
+ * Shapes: 1 <= n <= 65535, H, W >= 1, H * W <= 2^28 as r2, and H * H + W * W <= 2^30 so that every squared distance and every
+ * sum of two of them is an int32.  Anything else returns non-zero, and the query returns 0; n == 0 is a successful no-op.
+ * ---------------------------------------------------------------------- */
+/* cpx_distance_sq: map [n][H][W] int32 -> d2 [n][H][W] int32 (may not alias map).  For a pixel p of value v != 0, d2[p] is the
+ *   exact squared Euclidean distance to the nearest pixel of the same image whose value differs from v; 0 is a value like any
+ *   other here.  The image border is not a site: a pixel whose image holds no other value gets H * H + W * W.  Pixels of value
+ *   0 get 0.  workspace: n * H * W * 4 bytes (one int32 per pixel, the vertical distances g; no query of its own).
+ *   Two launches.  A column sweep gives g[p], the vertical distance to the nearest other value in p's column.  Inside the
+ *   horizontal run of equal value that holds p = (x, y), d2[p] = min((x - x')^2 + g(x', y)^2) over the run, capped by the squared
+ *   distance to the first pixel past either run end; the scan walks outwards from x and stops once (x - x')^2 reaches the best. */
+int cpx_distance_sq(const int32_t *map, int n, int H, int W, int32_t *d2, void *workspace, size_t workspace_bytes, void *stream);
+/* cpx_split_touching: inst [n][H][W] int32 instance maps, 0 = background, ids 1 .. H * W (what r2 writes).
+ *   SEEDS.  A pixel p of instance v is a seed when d2[p] >= min_radius^2 and no pixel q of the same instance with
+ *   max(|dy|, |dx|) <= min_distance beats it; q beats p when d2[q] > d2[p], or d2[q] == d2[p] and q is earlier in raster order.
+ *   The order is total, so a plateau has exactly one seed.  1 <= min_distance <= 64, 1 <= min_radius <= 32768.
+ *   seeds [n][seed_cap] the raster indices y * W + x of an image's seeds, grouped by instance id in ascending order and in
+ *                       raster order inside an instance; n_seeds [n] how many there are, also when they do not fit.
+ *   status [n]          0, or bit 0: n_seeds > seed_cap, bit 1: an id outside 0 .. H * W.  An image with a non-zero status is
+ *                       VOID: its labels are 0, its count is 0, its seed list is not written -- repeat it with seed_cap >=
+ *                       n_seeds (H * W always suffices).  1 <= seed_cap <= H * W.
+ *   ASSIGNMENT.  An instance with 0 or 1 seed keeps its pixels together.  Otherwise a pixel goes to the seed of its own instance
+ *   with the smallest squared Euclidean distance, of equals to the one earlier in raster order: a straight bisector between two
+ *   seeds, not a geodesic flood.
+ *   labels [n][H][W], n_instances [n]: cpx_label_components with `connectivity` over that assignment, so the pieces of a seed's
+ *   cell that are not connected become instances of their own, and the ids are the ranks of the first raster pixels.  labels
+ *   may not alias inst, which is only read.
+ *   Nine launches and two clears before the six of cpx_label_components.  cpx_split_workspace_bytes is host only and returns 0
+ *   for arguments the entry would refuse: two int32 planes, two id tables of H * W + 1 entries, one seed list and the
+ *   labeller's workspace per image.                                                                                          */
+size_t cpx_split_workspace_bytes(int n, int H, int W, int seed_cap);
+int cpx_split_touching(const int32_t *inst, int n, int H, int W, int min_distance, int min_radius, int connectivity,
+                       int seed_cap, int32_t *labels, int32_t *n_instances, int32_t *seeds, int32_t *n_seeds, int32_t *status,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 
 #ifdef __cplusplus
 }
