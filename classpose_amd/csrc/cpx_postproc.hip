@@ -1288,6 +1288,31 @@ __global__ void __launch_bounds__(1024) k_size_filter(int min_size, PPLayout lay
     }
 }
 
+// min_size <= 0 (stage entry only): no filter and no renumbering by first appearance, but the reference's fill loop still writes
+// j + 1 where j counts the labels present before it, so ids with gaps come back as 1..n in the order of their VALUES:
+// remap[v] = rank of v among the present ids (k_relabel applies it), SC_NLAB = their number.  Same slices and scan as k_size_filter.
+__global__ void __launch_bounds__(1024) k_rank_present(PPLayout lay, void *ws) {
+    __shared__ int s_part[1024];
+    const int vmax = min(WS(int, off_scal)[SC_VMAX], lay.L - 1);
+    const int *cnt = WS(int, off_cnt);
+    int *remap = WS(int, off_remap);
+    const int per = (vmax + 1024) / 1024;
+    const int lo = 1 + threadIdx.x * per, hi = min(lo + per - 1, vmax);
+    int c = 0;
+    for (int v = lo; v <= hi; ++v) c += cnt[v] > 0;
+    s_part[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int t = threadIdx.x >= o ? s_part[threadIdx.x - o] : 0;
+        __syncthreads();
+        s_part[threadIdx.x] += t;
+        __syncthreads();
+    }
+    int rank = s_part[threadIdx.x] - c;
+    for (int v = lo; v <= hi; ++v) remap[v] = cnt[v] > 0 ? ++rank : 0;
+    if (threadIdx.x == 1023) WS(int, off_scal)[SC_NLAB] = s_part[1023];
+}
+
 // 64-bit Kogge-Stone flood along a row: spread set bits of o through runs of `fr`
 __device__ __forceinline__ unsigned long long hfill(unsigned long long o, unsigned long long fr) {
     unsigned long long x = o, f = fr;
@@ -2113,10 +2138,11 @@ static int fill_holes_impl(int32_t *masks, int nT, int H, int W, int min_size, i
     PPLayout lay = pp_layout(H, W);
     ws = pp_tiles(ws, nT, H, W);
     if (min_size > 0) pp_size_filter(masks, nT, min_size, lay, ws, s, 0, nullptr, pending_err_thr);
-    else {   // labels may be non-contiguous: bbox loop below handles absent labels (slc None)
+    else {   // no filter: the present ids become 1..n in the order of their values (k_rank_present), which is what the fill loop of the reference leaves
         pp_init(PPI_SCAL | PPI_STATS, nT, lay, ws, s);
         PP_LAUNCH(k_count_labels, GRID_RUN(lay, nT), dim3(NTHR), 0, s, masks, pending_err_thr > 0 ? 1 : 0, pending_err_thr, lay, ws);
-        PP_LAUNCH(k_copy_scalar, dim3(1, nT), dim3(64), 0, s, SC_NLAB, SC_VMAX, -1, lay, ws);
+        PP_LAUNCH(k_rank_present, dim3(1, nT), dim3(1024), 0, s, lay, ws);
+        PP_LAUNCH(k_relabel, GRID_PIX(lay, nT), dim3(NTHR), 0, s, masks, (int32_t *)nullptr, lay, ws);
     }
     // find_objects(masks): bbox per label, then fill
     pp_init(PPI_STATS, nT, lay, ws, s);

@@ -364,7 +364,16 @@ int cpx_get_masks(const int32_t *p_final, int nT, int H, int W, double max_size_
 int cpx_remove_bad_flow_masks(int32_t *masks, const float *dP, int nT, int H, int W,
                               double threshold, double *flow_errors, void *workspace,
                               void *stream);
-/* cellpose.utils.fill_holes_and_remove_small_masks.                          */
+/* cellpose.utils.fill_holes_and_remove_small_masks, in place; nlabels (nullable) [nT].
+ * Precondition: every id of every tile satisfies 0 <= id < cpx_postproc_max_labels(H, W); the
+ * per-label tables are indexed by the id without a check, so an id outside that range writes out
+ * of bounds.
+ * min_size > 0: small labels out (the reference's positional count quirk included), holes filled
+ * label by label, small labels out again; ids 1..n by first raster appearance, nlabels = n.
+ * min_size <= 0: no filter and no renumbering by appearance; like the reference's fill loop, the
+ * output id of a label is the rank of its id among the ids present BEFORE the fill (ids {2, 5} come
+ * back as {1, 2}) and nlabels is their number -- a label that another label's fill overwrites
+ * still counts, so the largest id of the output can be smaller than nlabels.               */
 int cpx_fill_holes_and_remove_small_masks(int32_t *masks, int nT, int H, int W, int min_size,
                                           int32_t *nlabels, void *workspace, void *stream);
 /* classpose.models.compute_class_masks, models.py:191-230.
