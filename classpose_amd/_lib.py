@@ -141,6 +141,8 @@ SIGNATURES = {
     "cpx_compute_masks": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _d, _i, _i, _d, _p, _p, _p, _p, _p]),
     "cpx_instance_records": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "cpx_compute_masks_records": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _d, _i, _i, _d, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "cpx_resize_linear_f32": (_i, [_p, _i, _i, _i, _p, _i, _i, _p]),
+    "cpx_resize_nearest": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p]),
     "cpx_pq_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "cpx_pq_stats": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _sz, _p]),
     "cpx_net_neck_offset": (_sz, [_i, _i]),

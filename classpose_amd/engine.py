@@ -375,7 +375,9 @@ class _Slot:
     """One in-flight batch: every buffer a batch touches after the shared network workspace."""
 
     def __init__(self, eng: "Engine"):
-        nT, H, W, ncls, d = eng.nT, eng.H, eng.W, eng.w.ncls, eng.dev
+        # H x W: what the network and the blend work at (the tile size, or net_hw of a rescaling engine); cH x cW: what the dynamics run at
+        nT, H, W, ncls, d = eng.nT, eng.nH, eng.nW, eng.w.ncls, eng.dev
+        cH, cW = eng.cH, eng.cW
         nS = nT * eng.n_sub
         self.stats = torch.empty(nT * 3 * 4, dtype=torch.float32, device=d)
         self.hist = torch.empty(nT * 768, dtype=torch.int32, device=d)
@@ -386,13 +388,23 @@ class _Slot:
         self.cellprob = torch.empty((nT, H, W), dtype=torch.float32, device=d)
         self.logits = torch.empty((nT, max(ncls, 1), H, W), dtype=torch.float32, device=d)
         self.pp_ws = torch.empty(eng.pp_ws_bytes, dtype=torch.uint8, device=d)
-        self.masks = torch.empty((nT, H, W), dtype=torch.int16, device=d)
-        self.class_masks = torch.empty((nT, H, W), dtype=torch.uint8, device=d)
+        self.masks = torch.empty((nT, cH, cW), dtype=torch.int16, device=d)
+        self.class_masks = torch.empty((nT, cH, cW), dtype=torch.uint8, device=d)
         self.nlabels = torch.empty(nT, dtype=torch.int32, device=d)
         self.records = torch.empty(nT * eng.max_rec * C.sizeof(CpxRecord), dtype=torch.uint8, device=d)
         self.rec_counts = torch.empty(nT, dtype=torch.int32, device=d)
         self.cells = self.xy_pool = self.n_pts_total = self.poly_ws = self.origins = None   # allocated on first use
         self.has_polygons = False
+        if eng.rescaled:
+            # eval(diameter=): the tiles at network size, the fields at tile size, and without resample the maps at tile size too
+            tH, tW = eng.H, eng.W
+            self.tiles_net = torch.empty((nT, H, W, 3), dtype=torch.uint8, device=d)
+            self.out_dP = torch.empty((nT, 2, tH, tW), dtype=torch.float32, device=d)
+            self.out_cellprob = torch.empty((nT, tH, tW), dtype=torch.float32, device=d)
+            self.out_logits = torch.empty((nT, max(ncls, 1), tH, tW), dtype=torch.float32, device=d)
+            if not eng.resample:
+                self.out_masks = torch.empty((nT, tH, tW), dtype=torch.int16, device=d)
+                self.out_class_masks = torch.empty((nT, tH, tW), dtype=torch.uint8, device=d)
         self.ev_net = torch.cuda.Event()
         self.ev_post = torch.cuda.Event()
         self.n = 0
@@ -407,6 +419,13 @@ class Engine:
     i+1 while the POST stream runs blend -> dynamics -> class vote -> records of batch i (the
     post-processing kernels are small and latency-bound: they slot into the gaps of the MFMA
     kernels).  ``submit`` / ``result`` expose the pipeline; ``run`` = submit + result.
+
+    ``net_hw = (Hs, Ws)`` different from the tile size is the ``diameter`` branch of ``ClassposeModel.eval``
+    (/root/reference/src/classpose/models.py:633-639, 733-748, 782-820): tiles arrive at H x W, are resized as uint8 to
+    Hs x Ws, and normalisation, sub-tiling, network and blend all work at Hs x Ws.  With ``resample`` the blended fields
+    are resized to H x W and the dynamics run there; without it the dynamics run at Hs x Ws and ids, classes (nearest)
+    and fields (linear) are resized to H x W afterwards.  ``TileOutputs`` is at tile size either way; ``inject`` fields
+    are at network size.  With ``net_hw`` absent or equal to the tile size nothing of this exists: no buffer, no launch.
     """
 
     N_SLOTS = 2
@@ -414,20 +433,27 @@ class Engine:
     def __init__(self, weights: NetWeights, tile_h: int = 256, tile_w: int | None = None,
                  batch_tiles: int = 8, augment: bool = False, tile_overlap: float = 0.1,
                  niter: int = 200, cellprob_threshold: float = 0.0, flow_threshold: float = 0.4,
-                 min_size: int = 15, max_size_fraction: float = 0.4):
+                 min_size: int = 15, max_size_fraction: float = 0.4, net_hw: tuple[int, int] | None = None,
+                 resample: bool = True):
         self.L = _lib.lib()
         self.w = weights
         self.dev = weights.device
         self.H, self.W = tile_h, tile_w or tile_h
         self.nT = batch_tiles
-        self.tiling = make_tiling(self.H, self.W, BSIZE, augment, tile_overlap)
+        self.nH, self.nW = (int(net_hw[0]), int(net_hw[1])) if net_hw is not None else (self.H, self.W)
+        if self.nH < 1 or self.nW < 1:
+            raise ValueError(f"Engine: net_hw = {net_hw} must be at least 1 x 1")
+        self.rescaled = (self.nH, self.nW) != (self.H, self.W)
+        self.resample = bool(resample) or not self.rescaled
+        self.cH, self.cW = (self.H, self.W) if self.resample else (self.nH, self.nW)      # where the dynamics run
+        self.tiling = make_tiling(self.nH, self.nW, BSIZE, augment, tile_overlap)
         self.n_sub = self.tiling.ny * self.tiling.nx
         self.niter, self.cp_thr, self.flow_thr = niter, cellprob_threshold, flow_threshold
         self.min_size, self.max_frac = min_size, max_size_fraction
-        nT, H, W = self.nT, self.H, self.W
+        nT, H, W = self.nT, self.cH, self.cW
         d = self.dev
-        lo = percentile_params(H * W, 1)
-        hi = percentile_params(H * W, 99)
+        lo = percentile_params(self.nH * self.nW, 1)
+        hi = percentile_params(self.nH * self.nW, 99)
         self.pct = (lo[0], lo[1], hi[0], hi[1])
         self.net_ws_bytes = self.L.cpx_net_workspace_bytes(nT * self.n_sub, weights.c.dtype)
         if weights.c.n_unet_ops:
@@ -471,12 +497,17 @@ class Engine:
             raise ValueError(f"Engine.submit: got {tuple(tiles_u8.shape)}, this engine takes at most {self.nT} tiles of {(self.H, self.W, 3)}")
         if tiles_u8.device != self.dev:
             raise ValueError(f"Engine.submit: tiles live on {tiles_u8.device}, the engine on {self.dev}")
+        if self.rescaled and not self.resample and (records or polygons is not None):
+            raise ValueError("Engine.submit: records / polygons of a resample=False engine would be in network-size coordinates; "
+                             "pass records=False")
         if inject is not None:
             # logits may be None for a model without a class head (ncls <= 1: the chain never takes its pointer); dP and cellprob may not
             if len(inject) != 3 or inject[0] is None or inject[1] is None or (inject[2] is None and self.w.ncls > 1):
                 raise ValueError("Engine.submit: inject = (dP, cellprob, logits) device tensors (logits may be None only without a class head)")
             if any(t is not None and (t.device != self.dev or not t.is_contiguous()) for t in inject):
                 raise ValueError("Engine.submit: inject = (dP, cellprob, logits) contiguous tensors on the engine's device")
+            if self.rescaled and any(t is not None and tuple(t.shape[-2:]) != (self.nH, self.nW) for t in inject):
+                raise ValueError(f"Engine.submit: inject fields of this engine are at network size {(self.nH, self.nW)}")
         sid = self._next
         self._next = (self._next + 1) % self.N_SLOTS
         sl = self.slots[sid]
@@ -492,9 +523,13 @@ class Engine:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if tm is not None else None
         if ev:
             ev[0].record(self.s_net)
-        check(self.L.cpx_normalize_stats_u8(ptr(tiles_u8), n, self.H, self.W, lo_p, lo_g, hi_p, hi_g,
+        src = tiles_u8
+        if self.rescaled:       # transforms.resize_image on the uint8 image (models.py:633-639): OpenCV's 8-bit path, then normalize_img on the result
+            check(self.L.cpx_resize_linear_u8(ptr(tiles_u8), n, self.H, self.W, ptr(sl.tiles_net), self.nH, self.nW, sn), "resize_linear_u8")
+            src = sl.tiles_net
+        check(self.L.cpx_normalize_stats_u8(ptr(src), n, self.nH, self.nW, lo_p, lo_g, hi_p, hi_g,
                                             ptr(sl.stats), ptr(sl.hist), sn), "normalize_stats")
-        check(self.L.cpx_make_patches(ptr(tiles_u8), ptr(sl.stats), n, C.byref(self.tiling), self.w.c.dtype,
+        check(self.L.cpx_make_patches(ptr(src), ptr(sl.stats), n, C.byref(self.tiling), self.w.c.dtype,
                                       ptr(sl.patches), sn), "make_patches")
         if ev:
             ev[1].record(self.s_net)
@@ -521,13 +556,24 @@ class Engine:
             ev[4].record(self.s_post)
             tm.append(ev)
         dP, cp, lg = (sl.dP, sl.cellprob, sl.logits) if inject is None else inject
+        if self.rescaled:
+            # the fields back at tile size: before the dynamics with resample (models.py:733-748), for the caller only without (782-792)
+            for a, b, planes in ((dP, sl.out_dP, 2), (cp, sl.out_cellprob, 1), (lg, sl.out_logits, ncls if ncls > 1 else 0)):
+                if planes:
+                    check(self.L.cpx_resize_linear_f32(ptr(a), n * planes, self.nH, self.nW, ptr(b), self.H, self.W, sp), "resize_linear_f32")
+            if self.resample:
+                dP, cp, lg = sl.out_dP, sl.out_cellprob, sl.out_logits
         # one fused chain: ids, classes and (when asked for) the per-cell records leave in its last pass
         check(self.L.cpx_compute_masks_records(ptr(dP), ptr(cp), ptr(lg) if ncls > 1 else None, n, ncls,
-                                               self.H, self.W, self.cp_thr, self.flow_thr, self.niter,
+                                               self.cH, self.cW, self.cp_thr, self.flow_thr, self.niter,
                                                self.min_size, self.max_frac, ptr(sl.masks), ptr(sl.class_masks),
                                                ptr(sl.nlabels), self.max_rec if records else 0,
                                                ptr(sl.records) if records else None, ptr(sl.rec_counts) if records else None,
                                                ptr(sl.pp_ws), sp), "compute_masks")
+        if self.rescaled and not self.resample:     # ids and classes of the network-size run, cv2.INTER_NEAREST (models.py:804-820)
+            check(self.L.cpx_resize_nearest(ptr(sl.masks), 2, n, self.nH, self.nW, ptr(sl.out_masks), self.H, self.W, sp), "resize_nearest")
+            check(self.L.cpx_resize_nearest(ptr(sl.class_masks), 1, n, self.nH, self.nW, ptr(sl.out_class_masks), self.H, self.W, sp),
+                  "resize_nearest")
         sl.has_polygons = polygons is not None
         if polygons is not None:
             if not records:
@@ -564,8 +610,10 @@ class Engine:
         sl.busy = False
         self._last = sl
         n = sl.n
-        return TileOutputs(sl.masks[:n], sl.class_masks[:n], sl.nlabels[:n], sl.dP[:n], sl.cellprob[:n],
-                           sl.logits[:n] if self.w.ncls > 1 else None, sl.records, sl.rec_counts,
+        masks, cm = (sl.masks, sl.class_masks) if self.resample else (sl.out_masks, sl.out_class_masks)
+        dP, cp, lg = (sl.out_dP, sl.out_cellprob, sl.out_logits) if self.rescaled else (sl.dP, sl.cellprob, sl.logits)
+        return TileOutputs(masks[:n], cm[:n], sl.nlabels[:n], dP[:n], cp[:n],
+                           lg[:n] if self.w.ncls > 1 else None, sl.records, sl.rec_counts,
                            *((sl.cells, sl.xy_pool, sl.n_pts_total) if sl.has_polygons else (None, None, None)))
 
     def run(self, tiles_u8: torch.Tensor, inject=None, records: bool = True, polygons=None) -> "TileOutputs":

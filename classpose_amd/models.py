@@ -4,8 +4,10 @@ Mirrors /root/reference/src/classpose/models.py:233-827 for the 2-D path used by
 worker (predict_wsi.py:716-756) and by paper_experiments/run_inference.py:196-208: same
 constructor arguments, same ``eval`` signature and return tuple
 ``(masks uint16, (rgb_flow, dP, cellprob, y_class, x.shape), class_masks int64, styles)``.
-Everything between the uint8 image and the id maps runs on the GPU through the C ABI; the
-3-D / stitching / diameter-rescale branches of the reference are outside the WSI path and
+Everything between the uint8 image and the id maps runs on the GPU through the C ABI.  ``diameter=`` is the
+reference's rescale to 30 px cells (models.py:633-639, 733-748, 782-820): the uint8 image is resized by 30 / diameter
+on the device, the network runs at that size, and the fields (``resample=True``) or the maps (``resample=False``) are
+resized back, see ``engine.Engine(net_hw=, resample=)``.  The 3-D / stitching / anisotropy branches of the reference
 raise NotImplementedError instead of silently doing something else.
 """
 from __future__ import annotations
@@ -107,11 +109,42 @@ class ClassposeModel:
                 m._pool[self.key]["idle"].append(self.eng)
                 m._cv.notify()
 
-    def _engine(self, H, W, augment, tile_overlap, kw):
-        """``with self._engine(...) as eng:`` -- an engine of the bounded pool for this tile shape and these options"""
-        key = (H, W, bool(augment), float(tile_overlap), tuple(sorted(kw.items())))
+    def _engine(self, H, W, augment, tile_overlap, kw, net_hw=None, resample=True):
+        """``with self._engine(...) as eng:`` -- an engine of the bounded pool for this tile shape, network shape and these options"""
+        resample = bool(resample) or net_hw is None          # without a rescale there is nothing to resample: one pool entry
+        key = (H, W, bool(augment), float(tile_overlap), tuple(sorted(kw.items())), net_hw, resample)
         return self._Lease(self, key, lambda: engine.Engine(self.weights, H, W, batch_tiles=self.max_batch_tiles,
-                                                            augment=augment, tile_overlap=tile_overlap, **kw))
+                                                            augment=augment, tile_overlap=tile_overlap, net_hw=net_hw,
+                                                            resample=resample, **kw))
+
+    @staticmethod
+    def _net_shapes(imgs, diameter, augment, tile_overlap):
+        """Per image the network size ``(int(H * 30 / d), int(W * 30 / d))`` of models.py:633-639 (truncated, in Python float
+        arithmetic), or None where that is the image's own size (``diameter=None``, or a diameter that changes nothing)."""
+        if diameter is None:
+            return [None] * len(imgs)
+        if isinstance(diameter, (list, tuple, np.ndarray)) and np.ndim(diameter) > 0:
+            ds = [d for d in diameter]
+            if len(ds) != len(imgs):
+                raise ValueError(f"diameter has {len(ds)} entries for {len(imgs)} images")
+        else:
+            ds = [diameter] * len(imgs)
+        out = []
+        for im, d in zip(imgs, ds):
+            d = float(d)
+            if not (np.isfinite(d) and d > 0):
+                raise ValueError(f"diameter must be positive and finite, got {d}")
+            scaling = 30.0 / d
+            H, W = im.shape[:2]
+            Hs, Ws = int(H * scaling), int(W * scaling)
+            if Hs < 1 or Ws < 1:
+                raise ValueError(f"diameter={d} would resize a {H}x{W} image to {Hs}x{Ws}")
+            try:
+                engine.make_tiling(Hs, Ws, engine.BSIZE, augment, tile_overlap)
+            except ValueError as e:
+                raise ValueError(f"diameter={d} resizes the {H}x{W} image to {Hs}x{Ws}: {e}") from None
+            out.append((Hs, Ws) if (Hs, Ws) != (H, W) else None)
+        return out
 
     def engines_alive(self) -> int:
         with self._cv:
@@ -123,9 +156,9 @@ class ClassposeModel:
              anisotropy=None, flow3D_smooth=0, stitch_threshold: float = 0.0, min_size: int = 15,
              max_size_fraction: float = 0.4, niter=None, augment: bool = False,
              tile_overlap: float = 0.1, bsize: int = 256, compute_masks: bool = True, progress=None):
-        if do_3D or stitch_threshold > 0 or diameter is not None or invert or normalize is not True:
-            raise NotImplementedError("only the 2-D WSI-tile path of ClassposeModel.eval is built "
-                                      "(no do_3D / stitch / diameter / invert / custom normalize)")
+        if do_3D or stitch_threshold > 0 or invert or normalize is not True:
+            raise NotImplementedError("only the 2-D path of ClassposeModel.eval is built "
+                                      "(no do_3D / stitch / invert / custom normalize)")
         if bsize != 256:
             raise NotImplementedError("bsize is fixed to 256 like the WSI worker (predict_wsi.py:1563)")
         is_list = isinstance(x, (list, tuple))
@@ -137,15 +170,19 @@ class ClassposeModel:
             im = np.asarray(im)
             if im.ndim != 3 or im.shape[-1] != 3 or im.dtype != np.uint8:
                 raise ValueError("expected uint8 (H, W, 3) RGB tiles")
-            groups.setdefault(im.shape, []).append(i)
+            imgs[i] = im
+        # (rescale= is ignored like in the reference, which only warns that it is deprecated)
+        net_shapes = self._net_shapes(imgs, diameter, augment, tile_overlap)
+        for i, im in enumerate(imgs):
+            groups.setdefault((im.shape, net_shapes[i]), []).append(i)
         kw = dict(niter=200 if not niter else int(niter), cellprob_threshold=cellprob_threshold,
                   flow_threshold=flow_threshold, min_size=min_size, max_size_fraction=max_size_fraction)
         nT = self.max_batch_tiles
-        for shape, idxs in groups.items():
+        for (shape, net_hw), idxs in groups.items():
             for s in range(0, len(idxs), nT):
                 chunk = idxs[s:s + nT]
                 tiles = torch.from_numpy(np.stack([np.ascontiguousarray(imgs[i]) for i in chunk])).to(self.device)
-                with self._engine(shape[0], shape[1], augment, tile_overlap, kw) as eng:     # held for this batch only
+                with self._engine(shape[0], shape[1], augment, tile_overlap, kw, net_hw, resample) as eng:     # held for this batch only
                     o = eng.run(tiles, records=False)
                     masks = ops.masks_to_numpy(o.masks) if compute_masks else None
                     cm = o.class_masks.cpu().numpy().astype(np.int64) if compute_masks else None
@@ -154,7 +191,8 @@ class ClassposeModel:
                 for k, i in enumerate(chunk):
                     outs[i] = (masks[k].copy() if compute_masks else np.zeros(0),
                                (dx_to_circ(dP[k]), dP[k].copy(), cp[k].copy(),
-                                yc[k].copy() if yc is not None else None, (1, *shape)),
+                                yc[k].copy() if yc is not None else None,
+                                (1, *shape) if net_hw is None else (1, *net_hw, shape[2])),      # x.shape: of the resized image
                                cm[k].copy() if compute_masks else np.zeros(0),
                                np.zeros(256, np.float32))          # styles: noise in the reference (vit_sam.py:197)
         if is_list:

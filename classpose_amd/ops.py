@@ -83,6 +83,49 @@ def resize_tile_to_target_mpp(tiles_u8: torch.Tensor, resize_factor: float,
     return out if was else out[0]
 
 
+def resize_u8(tiles_u8: torch.Tensor, dh: int, dw: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """cv2.resize(..., INTER_LINEAR) of uint8 (n,h,w,3) / (h,w,3) device tiles to exactly dh x dw: the image side of
+    ``eval(diameter=)`` (models.py:633-639), where the sizes are ``int(h * 30 / diameter)`` and not rounded."""
+    t, was = _batched(tiles_u8.contiguous(), 3)
+    if out is None:
+        out = torch.empty((t.shape[0], dh, dw, 3), dtype=torch.uint8, device=t.device)
+    check(_lib.lib().cpx_resize_linear_u8(ptr(t), t.shape[0], t.shape[1], t.shape[2], ptr(out), dh, dw,
+                                          _stream(t.device)), "resize_linear_u8")
+    return out if was else out[0]
+
+
+# ---- a10b -------------------------------------------------------------------
+def resize_fields(t: torch.Tensor, dh: int, dw: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """transforms.resize_image on network fields (models.py:733-748, 782-792): float32 [..., h, w] device tensor ->
+    [..., dh, dw], cv2.INTER_LINEAR plane by plane (``cpx_resize_linear_f32``)."""
+    if t.dtype != torch.float32 or t.dim() < 2 or not t.is_cuda:
+        raise ValueError("resize_fields: expected a float32 [..., h, w] device tensor")
+    t = t.contiguous()
+    sh, sw = t.shape[-2:]
+    n = t.numel() // (sh * sw)
+    if out is None:
+        out = torch.empty((*t.shape[:-2], dh, dw), dtype=torch.float32, device=t.device)
+    if n:
+        check(_lib.lib().cpx_resize_linear_f32(ptr(t), n, sh, sw, ptr(out), dh, dw, _stream(t.device)), "resize_linear_f32")
+    return out
+
+
+def resize_nearest(t: torch.Tensor, dh: int, dw: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """transforms.resize_image(..., interpolation=cv2.INTER_NEAREST) on id / class maps (models.py:804-820): uint8, or the
+    uint16 ids kept in an int16 tensor, [..., h, w] on the device -> [..., dh, dw] (``cpx_resize_nearest``)."""
+    if t.dtype not in (torch.uint8, torch.int16) or t.dim() < 2 or not t.is_cuda:
+        raise ValueError("resize_nearest: expected a uint8 or int16 [..., h, w] device tensor")
+    t = t.contiguous()
+    sh, sw = t.shape[-2:]
+    n = t.numel() // (sh * sw)
+    if out is None:
+        out = torch.empty((*t.shape[:-2], dh, dw), dtype=t.dtype, device=t.device)
+    if n:
+        check(_lib.lib().cpx_resize_nearest(ptr(t), t.element_size(), n, sh, sw, ptr(out), dh, dw, _stream(t.device)),
+              "resize_nearest")
+    return out
+
+
 # ---- a7 -------------------------------------------------------------------
 def make_subtiles(tiles_u8: torch.Tensor, bsize: int = 256, augment: bool = False,
                   tile_overlap: float = 0.1):

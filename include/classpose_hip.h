@@ -419,6 +419,26 @@ int cpx_compute_masks_records(const float *dP, const float *cellprob, const floa
                               int32_t *rec_counts, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------
+ * a10b  eval(diameter=): network-size fields and maps back to the image size
+ * replaces transforms.resize_image on dP / cellprob / y_class
+ * (/root/reference/src/classpose/models.py:733-748 with resample=True, the
+ * _resize_gradients / _resize_cellprob calls of models.py:782-792 otherwise)
+ * and on masks / class_masks with cv2.INTER_NEAREST (models.py:804-820)
+ * ---------------------------------------------------------------------- */
+/* src [n_planes][sh][sw] -> dst [n_planes][dh][dw] float32, every plane on its own: cv2.resize(..., INTER_LINEAR) on
+ * float32.  Equal sizes copy.  sh == 2 dh && sw == 2 dw is the area path, ((a + b) + (c + d)) * 0.25f with a, b the
+ * upper and c, d the lower pair of the 2 x 2 block, summed in that order.  Otherwise, per axis, scale = 1.0 / ((double)d /
+ * (double)s), f = (float)((i + 0.5) * scale - 0.5), s0 = floor(f), f -= s0; in x (s0 < 0) -> (0, 0) and
+ * (s0 >= sw - 1) -> (sw - 1, 0); in y the weight is kept and only the two row indices are clipped to [0, sh - 1];
+ * h = S[x0] * (1 - fx) + S[x1] * fx on both rows, then h0 * (1 - fy) + h1 * fy, every product and every sum rounded to
+ * float32 (no FMA).  Taps and weights are computed in the kernel: no table, no workspace, one launch.               */
+int cpx_resize_linear_f32(const float *src, int n_planes, int sh, int sw, float *dst, int dh, int dw, void *stream);
+/* The same geometry with cv2.INTER_NEAREST for elements of elem_bytes = 1 (class maps) or 2 (uint16 ids):
+ * sx = min((int)floor(x * (1.0 / ((double)dw / sw))), sw - 1), likewise in y.  Equal sizes copy.                    */
+int cpx_resize_nearest(const void *src, int elem_bytes, int n_planes, int sh, int sw, void *dst, int dh, int dw,
+                       void *stream);
+
+/* ------------------------------------------------------------------------
  * a16b  panoptic-quality statistics (offline evaluation against an annotated set)
  * replaces, per image pair, filter_out_unlabelled_cells (/root/reference/src/classpose/metrics/utils.py:162-252),
  * remove_border_instances (metrics/pq.py:65-92), get_multi_pq_info (metrics/stats_utils.py:8-61) and the pairing of
