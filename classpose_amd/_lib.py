@@ -166,6 +166,17 @@ SIGNATURES = {
     "cpx_neck_forward_train": (_i, [C.POINTER(CpxNetWeights), _p, _i, _p, _p, _sz, _p]),
     "cpx_layernorm_backward_workspace_bytes": (_sz, [_i, _i]),
     "cpx_layernorm_backward": (_i, [_i, _p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "cpx_blocks_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cpx_blocks_train_layout": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "cpx_blocks_forward_train": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _p, _sz, _p]),
+    "cpx_block_grad_layout": (C.c_longlong, [C.POINTER(C.c_longlong)]),
+    "cpx_blocks_backward_workspace_bytes": (_sz, [_i, _i]),
+    "cpx_blocks_backward_slab_crops": (_i, []),
+    "cpx_blocks_backward": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _sz, _p, _p, _p, _p, _sz, _p]),
+    "cpx_layernorm_backward_bytes": (_sz, [_i, _i]),
+    "cpx_attention_backward_workspace_bytes": (_sz, [_i]),
+    "cpx_attention_backward": (_i, [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    "cpx_gelu_backward": (_i, [_p, _p, _sz, _p, _p]),
     "cpx_neck_grad_layout": (C.c_longlong, [C.POINTER(C.c_longlong)]),
     "cpx_neck_backward_workspace_bytes": (_sz, [_i, _i, _i, C.POINTER(_sz)]),
     "cpx_neck_backward": (_i, [C.POINTER(CpxNetWeights), _p, _i, _p, _sz, _p, _p, _p, _sz, _p]),

@@ -1,0 +1,875 @@
+// Training the transformer blocks (gfx950): the backward kernels a block needs beyond the GEMMs and LayerNorm of the neck's backward.
+//   * cpx_attention_backward   the derivative of the function cpx_attention(CPX_DT_F32, ...) computes (k_attention_f32, cpx_net_f32.hip:
+//                              flash_forward with the decomposed rel-pos bias, vit_sam.py:15-65), in float32 on v_mfma_f32_32x32x2_f32
+//   * cpx_gelu_backward        the erf GELU of the mlp.lin1 epilogue
+// (cpx_layernorm_backward, cpx_train_neck.hip, takes the blocks' C = 1024 as well.)
+//
+// Attention, per (crop, head): Q, K, V [1024][64] from the stored qkv rows (widened exactly), tables Rh, Rw [64][64] in the operand
+// convention of cpx_block_weights.rel_h / rel_w (rel_pos / scale, row 63 zero).  With query i = (qy, qx) and key j = (ky, kx):
+//   S'[i][j] = q_i . (k_j + Rh[qy - ky + 31] + Rw[qx - kx + 31]),   P = softmax_j(scale S'),   O = P V,   scale = 64^-1/2
+// (the scale multiplies the bias too: that is why the tables hold rel_pos / scale).  The derivative (tests/block_train_reference.py,
+// attention_backward, pinned on float64 autograd by tests/test_block_train_host.py):
+//   delta_i = dO_i . O_i = sum_j P[i][j] dP[i][j],   dP[i][j] = dO_i . v_j,   dS'[i][j] = scale P[i][j] (dP[i][j] - delta_i)
+//   dv_j = sum_i P[i][j] dO_i,   dk_j = sum_i dS'[i][j] q_i
+//   G_h[i][ky] = sum_kx dS'[i][(ky, kx)],   G_w[i][kx] = sum_ky dS'[i][(ky, kx)]
+//   dq_i = sum_j dS'[i][j] k_j + sum_ky G_h[i][ky] Rh[qy - ky + 31] + sum_kx G_w[i][kx] Rw[qx - kx + 31]
+//   dRh[r] = sum over crops, heads, i, ky with qy - ky + 31 = r of G_h[i][ky] q_i        (dRw likewise with qx, kx)
+// Three kernels, no atomics, every sum in a fixed order:
+//   k_attn_bwd_dq    one wave = one image row of 32 queries (the forward's shape).  Pass 1 over the 32 key tiles: the row maximum m and
+//                    the sum l of exp(scale (S' - m)) and delta; pass 2: P recomputed, dS', dq, G_h, G_w.  It leaves m, 1 / l, delta and the bias
+//                    values q_i . Rh[..], q_i . Rw[..] for the second kernel.
+//   k_attn_bwd_dkv   one wave = one image row of 32 keys, looping over the 32 query tiles: P and dS' recomputed, dk and dv.
+//   k_rel_grad       per (crop, four heads, table row): float64 sums in query order; k_rel_finish adds the partials in crop order and
+//                    rounds once (row 63, the padding row, is written as zero).
+// No query of one crop sees a key of another: every tile index is taken inside the crop's 1024 rows.
+#include "cpx_internal.h"
+#include <algorithm>
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+#define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+#define AB_LD 68                        // tile row stride in floats (k_attention_f32's: b128 reads of 16 rows cover all banks)
+#define AB_GLD 97                       // per-query scratch row: [0, 64) q . table rows, [64, 96) the G_h sums
+#define AB_SLOT(v, h2) (((v) & 3) + 8 * ((v) >> 2) + 4 * (h2))      // the row of accumulator register v in lane half h2
+
+template <int DT>
+__device__ __forceinline__ float half_bits_to_f32(unsigned u) {
+    if constexpr (DT == CPX_DT_F16) { const unsigned short h = (unsigned short)u; return (float)*reinterpret_cast<const _Float16 *>(&h); }
+    else return bf16_to_f32((unsigned short)u);
+}
+// four consecutive elements (idx a multiple of 4) of a tensor of element type DT, widened exactly
+template <int DT>
+__device__ __forceinline__ float4 ld4(const void *p, size_t idx) {
+    if constexpr (DT == CPX_DT_F32) return *reinterpret_cast<const float4 *>((const float *)p + idx);
+    else {
+        const uint2 a = *reinterpret_cast<const uint2 *>((const unsigned short *)p + idx);
+        return make_float4(half_bits_to_f32<DT>(a.x & 0xFFFF), half_bits_to_f32<DT>(a.x >> 16), half_bits_to_f32<DT>(a.y & 0xFFFF),
+                           half_bits_to_f32<DT>(a.y >> 16));
+    }
+}
+
+// ---------------------------------------------------------------------------
+// dq, the row statistics and the row-group sums of dS'
+// ---------------------------------------------------------------------------
+// grid (8 row groups, 16 heads, crops), 4 waves: wave w of row group g owns the image row qh = 4 g + w.  Lane (r, h2): query qx = r,
+// head channels 32 h2 .. 32 h2 + 31 of Q and dO; accumulator register v belongs to key kx = AB_SLOT(v, h2) of the tile (S'^T, dP^T)
+// or to channel AB_SLOT(v, h2) (dq^T), as in k_attention_f32.  st_*, Bh, Bw, Gh, Gw are indexed by (crop * 16 + head) * 1024 + query.
+template <int DT>
+__global__ void __launch_bounds__(256) k_attn_bwd_dq(const void *__restrict__ qkv, const void *__restrict__ relh, const void *__restrict__ relw,
+                                                     const float *__restrict__ dO, float *__restrict__ dqkv,
+                                                     float *__restrict__ st_m, float *__restrict__ st_il, float *__restrict__ st_delta,
+                                                     float *__restrict__ Bh, float *__restrict__ Bw, float *__restrict__ Gh,
+                                                     float *__restrict__ Gw) {
+    // 84 480 bytes of static LDS (sK + sV + sG): above the 64 KB of older CDNA parts, inside gfx950's 160 KB per workgroup -- this
+    // kernel is gfx950-only, like the library
+    __shared__ __attribute__((aligned(16))) float sK[2][32 * AB_LD];
+    __shared__ __attribute__((aligned(16))) float sV[2][32 * AB_LD];
+    __shared__ float sG[4][32 * AB_GLD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h2 = lane >> 5;
+    const int head = blockIdx.y, s = blockIdx.z, qh = blockIdx.x * 4 + wave;
+    const size_t tok0 = (size_t)s * 1024;
+    const size_t qi = ((size_t)s * 16 + head) * 1024 + qh * 32 + r;
+
+    float qf[32], dof[32];
+    {
+        const size_t qo = (tok0 + qh * 32 + r) * 3072 + head * 64 + 32 * h2, oo = (tok0 + qh * 32 + r) * 1024 + head * 64 + 32 * h2;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float4 a = ld4<DT>(qkv, qo + 4 * c);
+            qf[4 * c] = a.x; qf[4 * c + 1] = a.y; qf[4 * c + 2] = a.z; qf[4 * c + 3] = a.w;
+            const float4 d = *reinterpret_cast<const float4 *>(dO + oo + 4 * c);
+            dof[4 * c] = d.x; dof[4 * c + 1] = d.y; dof[4 * c + 2] = d.z; dof[4 * c + 3] = d.w;
+        }
+    }
+    // G[q][j] = q . table[j] -> the wave's scratch
+    float *G = sG[wave];
+    auto compute_G = [&](const void *table) {
+#pragma unroll
+        for (int jb = 0; jb < 2; ++jb) {
+            f32x16 acc;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+            const size_t to = (size_t)(jb * 32 + r) * 64 + 32 * h2;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float4 t4 = ld4<DT>(table, to + 4 * c);
+                acc = MFMA_F32(t4.x, qf[4 * c], acc); acc = MFMA_F32(t4.y, qf[4 * c + 1], acc);
+                acc = MFMA_F32(t4.z, qf[4 * c + 2], acc); acc = MFMA_F32(t4.w, qf[4 * c + 3], acc);
+            }
+#pragma unroll
+            for (int v = 0; v < 16; ++v) G[r * AB_GLD + jb * 32 + AB_SLOT(v, h2)] = acc[v];
+        }
+        // G belongs to this wave alone, and its lane halves read each other's stores: a wave's LDS operations complete in order; the
+        // wave barrier keeps the compiler from moving a load above these stores
+        __builtin_amdgcn_wave_barrier();
+    };
+    compute_G(relw);
+    f32x16 GW;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) GW[v] = G[r * AB_GLD + (r - AB_SLOT(v, h2) + 31)];
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4)
+        *reinterpret_cast<float4 *>(Bw + qi * 32 + 8 * g4 + 4 * h2) = make_float4(GW[4 * g4], GW[4 * g4 + 1], GW[4 * g4 + 2], GW[4 * g4 + 3]);
+    __builtin_amdgcn_wave_barrier();                                   // the reads of q . Rw above, before q . Rh overwrites them
+    compute_G(relh);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) Bh[qi * 32 + h2 * 16 + k] = G[r * AB_GLD + (qh - (h2 * 16 + k) + 31)];
+
+    // K / V tiles: 32 keys x 64 channels, thread -> (key = tid >> 4 (+ 16), 4 channels at (tid & 15) * 4)
+    const int skey = tid >> 4, sc4 = (tid & 15) * 4;
+    const size_t kbase = (tok0 + skey) * 3072 + 1024 + head * 64 + sc4, vbase = kbase + 1024;
+    const int sdst0 = skey * AB_LD + sc4, sdst1 = sdst0 + 16 * AB_LD;
+    float4 k0r, k1r, v0r, v1r;
+    auto load_k = [&](int kh) {
+        const size_t o = (size_t)kh * 32 * 3072;
+        k0r = ld4<DT>(qkv, kbase + o); k1r = ld4<DT>(qkv, kbase + o + (size_t)16 * 3072);
+    };
+    auto load_v = [&](int kh) {
+        const size_t o = (size_t)kh * 32 * 3072;
+        v0r = ld4<DT>(qkv, vbase + o); v1r = ld4<DT>(qkv, vbase + o + (size_t)16 * 3072);
+    };
+    auto store_k = [&](int buf) {
+        *reinterpret_cast<float4 *>(&sK[buf][sdst0]) = k0r; *reinterpret_cast<float4 *>(&sK[buf][sdst1]) = k1r;
+    };
+    auto store_v = [&](int buf) {
+        *reinterpret_cast<float4 *>(&sV[buf][sdst0]) = v0r; *reinterpret_cast<float4 *>(&sV[buf][sdst1]) = v1r;
+    };
+    // S'^T = K . Q^T + the Rw bias (the Rh bias gh is one number per query and tile)
+    auto scores = [&](int buf) {
+        f32x16 S = GW;
+        const float *kp = &sK[buf][r * AB_LD + 32 * h2];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float4 kf = *reinterpret_cast<const float4 *>(kp + 4 * c);
+            S = MFMA_F32(kf.x, qf[4 * c], S); S = MFMA_F32(kf.y, qf[4 * c + 1], S);
+            S = MFMA_F32(kf.z, qf[4 * c + 2], S); S = MFMA_F32(kf.w, qf[4 * c + 3], S);
+        }
+        return S;
+    };
+    // dP^T = V . dO^T
+    auto dprobs = [&](int buf) {
+        f32x16 dP;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) dP[v] = 0.f;
+        const float *vp = &sV[buf][r * AB_LD + 32 * h2];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float4 vf = *reinterpret_cast<const float4 *>(vp + 4 * c);
+            dP = MFMA_F32(vf.x, dof[4 * c], dP); dP = MFMA_F32(vf.y, dof[4 * c + 1], dP);
+            dP = MFMA_F32(vf.z, dof[4 * c + 2], dP); dP = MFMA_F32(vf.w, dof[4 * c + 3], dP);
+        }
+        return dP;
+    };
+    const float cexp = 0.125f * 1.44269504088896340736f;      // scale * log2(e)
+
+    // pass 1: m = max_j S'[i][j], l = sum_j exp(scale (S'[i][j] - m)) and delta = sum_j P[i][j] dP[i][j] (= dO_i . O_i with the O of THIS
+    // arithmetic: the stored O is rounded to the network dtype, and 2^-9 in delta would be 2^-9 in every dS')
+    float m_run = -1e30f, l_run = 0.f, d_run = 0.f;
+    load_k(0); load_v(0);
+    store_k(0); store_v(0);
+    __syncthreads();
+    for (int kh = 0; kh < 32; ++kh) {
+        const int buf = kh & 1;
+        if (kh + 1 < 32) { load_k(kh + 1); load_v(kh + 1); }
+        const float gh = G[r * AB_GLD + (qh - kh + 31)];
+        const f32x16 S = scores(buf);
+        const f32x16 dP = dprobs(buf);
+        float mx = S[0];
+#pragma unroll
+        for (int v = 1; v < 16; ++v) mx = fmaxf(mx, S[v]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32)) + gh;
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cexp);
+        m_run = m_new;
+        // (S' - m) first, then the one multiplication: S' reaches hundreds, and a product S' * cexp rounded at that size would put its
+        // rounding into every exponent; the difference is small where P is not
+        const float off = gh - m_new;
+        float ps = 0.f, pd = 0.f;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) { const float p = __builtin_amdgcn_exp2f((S[v] + off) * cexp); ps += p; pd = fmaf(p, dP[v], pd); }
+        l_run = fmaf(l_run, alpha, ps);
+        d_run = fmaf(d_run, alpha, pd);
+        if (kh + 1 < 32) { store_k(buf ^ 1); store_v(buf ^ 1); }
+        __syncthreads();
+    }
+    const float inv_l = 1.0f / (l_run + __shfl_xor(l_run, 32));
+    const float delta = (d_run + __shfl_xor(d_run, 32)) * inv_l;
+    if (h2 == 0) { st_m[qi] = m_run; st_il[qi] = inv_l; st_delta[qi] = delta; }
+
+    // pass 2
+    f32x16 dQ[2];
+    float gw[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) { dQ[0][v] = 0.f; dQ[1][v] = 0.f; gw[v] = 0.f; }
+    load_k(0); load_v(0);
+    store_k(0); store_v(0);
+    __syncthreads();
+    for (int kh = 0; kh < 32; ++kh) {
+        const int buf = kh & 1;
+        if (kh + 1 < 32) { load_k(kh + 1); load_v(kh + 1); }
+        const float gh = G[r * AB_GLD + (qh - kh + 31)];
+        const f32x16 S = scores(buf);
+        const f32x16 dP = dprobs(buf);
+        const float off = gh - m_run;
+        float ds[16], gsum = 0.f;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const float p = __builtin_amdgcn_exp2f((S[v] + off) * cexp) * inv_l;
+            ds[v] = 0.125f * (p * (dP[v] - delta));
+            gsum += ds[v];
+            gw[v] += ds[v];
+        }
+        gsum += __shfl_xor(gsum, 32);
+        if (h2 == 0) G[r * AB_GLD + 64 + kh] = gsum;             // (read after the loop's last __syncthreads)
+        // dq^T[d][q] += K^T[d][key] dS'^T[key][q]: the k-slot of step j is the key of accumulator register j
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const float *kp = &sK[buf][AB_SLOT(j, h2) * AB_LD + r];
+            dQ[0] = MFMA_F32(kp[0], ds[j], dQ[0]);
+            dQ[1] = MFMA_F32(kp[32], ds[j], dQ[1]);
+        }
+        if (kh + 1 < 32) { store_k(buf ^ 1); store_v(buf ^ 1); }
+        __syncthreads();
+    }
+    // the row-group sums: G_w from the registers (through the scratch: both lane halves need all 32), G_h from the scratch
+#pragma unroll
+    for (int v = 0; v < 16; ++v) G[r * AB_GLD + AB_SLOT(v, h2)] = gw[v];
+    __builtin_amdgcn_wave_barrier();                                   // both lane halves read all 32 below
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        *reinterpret_cast<float4 *>(Gw + qi * 32 + 8 * g4 + 4 * h2) = make_float4(gw[4 * g4], gw[4 * g4 + 1], gw[4 * g4 + 2], gw[4 * g4 + 3]);
+        const float *gp = &G[r * AB_GLD + 64 + h2 * 16 + 4 * g4];
+        *reinterpret_cast<float4 *>(Gh + qi * 32 + h2 * 16 + 4 * g4) = make_float4(gp[0], gp[1], gp[2], gp[3]);
+    }
+    // the bias term of dq: 32 table rows weighted by G_h (row index uniform in the wave), 32 weighted by G_w (row index per query)
+    for (int k = 0; k < 32; ++k) {
+        const float g_h = G[r * AB_GLD + 64 + k], g_w = G[r * AB_GLD + k];
+        const size_t th = (size_t)(qh - k + 31) * 64, tw = (size_t)(r - k + 31) * 64;
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int d = db * 32 + 8 * g4 + 4 * h2;
+                const float4 a = ld4<DT>(relh, th + d), b = ld4<DT>(relw, tw + d);
+                dQ[db][4 * g4] = fmaf(g_w, b.x, fmaf(g_h, a.x, dQ[db][4 * g4]));
+                dQ[db][4 * g4 + 1] = fmaf(g_w, b.y, fmaf(g_h, a.y, dQ[db][4 * g4 + 1]));
+                dQ[db][4 * g4 + 2] = fmaf(g_w, b.z, fmaf(g_h, a.z, dQ[db][4 * g4 + 2]));
+                dQ[db][4 * g4 + 3] = fmaf(g_w, b.w, fmaf(g_h, a.w, dQ[db][4 * g4 + 3]));
+            }
+    }
+    float *orow = dqkv + (tok0 + qh * 32 + r) * 3072 + head * 64;
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+            *reinterpret_cast<float4 *>(orow + db * 32 + 8 * g4 + 4 * h2) =
+                make_float4(dQ[db][4 * g4], dQ[db][4 * g4 + 1], dQ[db][4 * g4 + 2], dQ[db][4 * g4 + 3]);
+}
+
+// ---------------------------------------------------------------------------
+// dk and dv
+// ---------------------------------------------------------------------------
+// grid as above; wave w of row group g owns the key row kh = 4 g + w: lane (r, h2) holds key kx = r, channels 32 h2 .. of K and V, and
+// accumulator register v belongs to query qx = AB_SLOT(v, h2) of the tile (S', dP) or to channel AB_SLOT(v, h2) (dk^T, dv^T).
+template <int DT>
+__global__ void __launch_bounds__(256) k_attn_bwd_dkv(const void *__restrict__ qkv, const float *__restrict__ dO, const float *__restrict__ st_m,
+                                                      const float *__restrict__ st_il, const float *__restrict__ st_delta,
+                                                      const float *__restrict__ Bh, const float *__restrict__ Bw, float *__restrict__ dqkv) {
+    __shared__ __attribute__((aligned(16))) float sQ[32 * AB_LD];
+    __shared__ __attribute__((aligned(16))) float sD[32 * AB_LD];
+    __shared__ __attribute__((aligned(16))) float sBw[32 * 36];
+    __shared__ float sBh[4][32], sM[32], sIl[32], sDl[32];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h2 = lane >> 5;
+    const int head = blockIdx.y, s = blockIdx.z, kh = blockIdx.x * 4 + wave;
+    const size_t tok0 = (size_t)s * 1024;
+    const size_t qi0 = ((size_t)s * 16 + head) * 1024;
+
+    float kf[32], vf[32];
+    {
+        const size_t ko = (tok0 + kh * 32 + r) * 3072 + 1024 + head * 64 + 32 * h2;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float4 a = ld4<DT>(qkv, ko + 4 * c), b = ld4<DT>(qkv, ko + 1024 + 4 * c);
+            kf[4 * c] = a.x; kf[4 * c + 1] = a.y; kf[4 * c + 2] = a.z; kf[4 * c + 3] = a.w;
+            vf[4 * c] = b.x; vf[4 * c + 1] = b.y; vf[4 * c + 2] = b.z; vf[4 * c + 3] = b.w;
+        }
+    }
+    f32x16 dK[2], dV[2];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) { dK[0][v] = 0.f; dK[1][v] = 0.f; dV[0][v] = 0.f; dV[1][v] = 0.f; }
+    const int sq = tid >> 4, sc4 = (tid & 15) * 4;
+    const float cexp = 0.125f * 1.44269504088896340736f;
+    for (int qt = 0; qt < 32; ++qt) {
+        __syncthreads();                                   // the previous tile has been read
+        {
+            const size_t row = tok0 + qt * 32 + sq;
+            *reinterpret_cast<float4 *>(&sQ[sq * AB_LD + sc4]) = ld4<DT>(qkv, row * 3072 + head * 64 + sc4);
+            *reinterpret_cast<float4 *>(&sQ[(sq + 16) * AB_LD + sc4]) = ld4<DT>(qkv, (row + 16) * 3072 + head * 64 + sc4);
+            *reinterpret_cast<float4 *>(&sD[sq * AB_LD + sc4]) = *reinterpret_cast<const float4 *>(dO + row * 1024 + head * 64 + sc4);
+            *reinterpret_cast<float4 *>(&sD[(sq + 16) * AB_LD + sc4]) = *reinterpret_cast<const float4 *>(dO + (row + 16) * 1024 + head * 64 + sc4);
+            const int bq = tid >> 3, bc = (tid & 7) * 4;   // the Rw bias of the tile: 32 queries x 32 kx
+            *reinterpret_cast<float4 *>(&sBw[bq * 36 + bc]) = *reinterpret_cast<const float4 *>(Bw + (qi0 + qt * 32 + bq) * 32 + bc);
+            if (tid < 128) sBh[tid >> 5][tid & 31] = Bh[(qi0 + qt * 32 + (tid & 31)) * 32 + blockIdx.x * 4 + (tid >> 5)];
+            else if (tid < 160) sM[tid - 128] = st_m[qi0 + qt * 32 + tid - 128];
+            else if (tid < 192) sIl[tid - 160] = st_il[qi0 + qt * 32 + tid - 160];
+            else if (tid < 224) sDl[tid - 192] = st_delta[qi0 + qt * 32 + tid - 192];
+        }
+        __syncthreads();
+        // S'[q][key] = Q . K^T and dP[q][key] = dO . V^T
+        f32x16 S, dP;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) { S[v] = 0.f; dP[v] = 0.f; }
+        const float *qp = &sQ[r * AB_LD + 32 * h2], *dp = &sD[r * AB_LD + 32 * h2];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float4 a = *reinterpret_cast<const float4 *>(qp + 4 * c), d = *reinterpret_cast<const float4 *>(dp + 4 * c);
+            S = MFMA_F32(a.x, kf[4 * c], S); S = MFMA_F32(a.y, kf[4 * c + 1], S);
+            S = MFMA_F32(a.z, kf[4 * c + 2], S); S = MFMA_F32(a.w, kf[4 * c + 3], S);
+            dP = MFMA_F32(d.x, vf[4 * c], dP); dP = MFMA_F32(d.y, vf[4 * c + 1], dP);
+            dP = MFMA_F32(d.z, vf[4 * c + 2], dP); dP = MFMA_F32(d.w, vf[4 * c + 3], dP);
+        }
+        float p[16], ds[16];
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int q = AB_SLOT(v, h2);
+            const float sp = (S[v] + sBw[q * 36 + r]) + sBh[wave][q];
+            p[v] = __builtin_amdgcn_exp2f((sp - sM[q]) * cexp) * sIl[q];
+            ds[v] = 0.125f * (p[v] * (dP[v] - sDl[q]));
+        }
+        // dv^T[d][key] += dO^T[d][q] P[q][key], dk^T[d][key] += Q^T[d][q] dS'[q][key]: the k-slot of step j is the query of register j
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int o = AB_SLOT(j, h2) * AB_LD + r;
+            dV[0] = MFMA_F32(sD[o], p[j], dV[0]);
+            dV[1] = MFMA_F32(sD[o + 32], p[j], dV[1]);
+            dK[0] = MFMA_F32(sQ[o], ds[j], dK[0]);
+            dK[1] = MFMA_F32(sQ[o + 32], ds[j], dK[1]);
+        }
+    }
+    float *krow = dqkv + (tok0 + kh * 32 + r) * 3072 + 1024 + head * 64, *vrow = krow + 1024;
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int d = db * 32 + 8 * g4 + 4 * h2;
+            *reinterpret_cast<float4 *>(krow + d) = make_float4(dK[db][4 * g4], dK[db][4 * g4 + 1], dK[db][4 * g4 + 2], dK[db][4 * g4 + 3]);
+            *reinterpret_cast<float4 *>(vrow + d) = make_float4(dV[db][4 * g4], dV[db][4 * g4 + 1], dV[db][4 * g4 + 2], dV[db][4 * g4 + 3]);
+        }
+}
+
+// ---------------------------------------------------------------------------
+// the gradients of the two tables
+// ---------------------------------------------------------------------------
+// grid (63 table rows, 2 tables, crops * 4), 4 waves: wave w takes head 4 * (blockIdx.z & 3) + w, lane d one channel.  Table 0 (Rh):
+// the pairs (a, b) = (qy, ky) with qy - ky + 31 = row, summed over qx; table 1 (Rw): (a, b) = (qx, kx), summed over qy.  One float64
+// chain per thread in (a, c) order, then wave 0 + 1 + 2 + 3 -> part [crops * 4][2][64][64] float64 (row 63 is never written or read).
+template <int DT>
+__global__ void __launch_bounds__(256) k_rel_grad(const void *__restrict__ qkv, const float *__restrict__ Gh, const float *__restrict__ Gw,
+                                                  double *__restrict__ part) {
+    __shared__ double sm[4][64];
+    const int d = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x, t = blockIdx.y, s = blockIdx.z >> 2, head = (blockIdx.z & 3) * 4 + wave;
+    const float *G = t ? Gw : Gh;
+    const size_t qi0 = ((size_t)s * 16 + head) * 1024, tok0 = (size_t)s * 1024;
+    double acc = 0;
+    for (int a = 0; a < 32; ++a) {
+        const int b = a - row + 31;
+        if (b < 0 || b >= 32) continue;                    // (uniform in the workgroup)
+#pragma unroll 8
+        for (int c = 0; c < 32; ++c) {
+            const int i = t ? c * 32 + a : a * 32 + c;
+            acc += (double)G[(qi0 + i) * 32 + b] * (double)load_f32<DT>(qkv, (tok0 + i) * 3072 + head * 64 + d);
+        }
+    }
+    sm[wave][d] = acc;
+    __syncthreads();
+    if (wave == 0) part[(((size_t)blockIdx.z * 2 + t) * 64 + row) * 64 + d] = ((sm[0][d] + sm[1][d]) + sm[2][d]) + sm[3][d];
+}
+// thread = one element of [2][64][64]: the partials in chunk order; `add`: on top of what the output holds (a later slab of crops)
+__global__ void __launch_bounds__(256) k_rel_finish(const double *__restrict__ part, int nchunk, int add, float *__restrict__ drel_h,
+                                                    float *__restrict__ drel_w) {
+    const int e = blockIdx.x * 256 + threadIdx.x, t = e >> 12, o = e & 4095;
+    float *out = (t ? drel_w : drel_h) + o;
+    if ((o >> 6) == 63) { *out = 0.f; return; }
+    double sum = add ? (double)*out : 0.0;
+    for (int k = 0; k < nchunk; ++k) sum += part[((size_t)k * 2 + t) * 4096 + o];
+    *out = (float)sum;
+}
+
+// workspace: m | 1 / l | delta [crops * 16 * 1024] float32, Bh | Bw | Gh | Gw [crops * 16 * 1024][32] float32, part float64
+struct AttnBwdLayout { size_t off_st[3], off_b[4], off_part, total; };
+static AttnBwdLayout attn_bwd_layout(int nS) {
+    AttnBwdLayout L; CpxArena a; const size_t n = (size_t)nS * 16 * 1024;
+    for (int i = 0; i < 3; ++i) L.off_st[i] = a.take(n * sizeof(float));
+    for (int i = 0; i < 4; ++i) L.off_b[i] = a.take(n * 32 * sizeof(float));
+    L.off_part = a.take((size_t)nS * 4 * 2 * 4096 * sizeof(double));
+    L.total = a.o;
+    return L;
+}
+extern "C" size_t cpx_attention_backward_workspace_bytes(int n_subtiles) {
+    if (n_subtiles <= 0 || n_subtiles > 16383) return 0;              // blockIdx.z = 4 * crops in k_rel_grad
+    return attn_bwd_layout(n_subtiles).total;
+}
+
+// `add_rel`: drel_h / drel_w receive their sums on top of what they hold (the caller runs a batch in slabs of crops, in order)
+int cpx_attention_backward_run(int dtype, const void *qkv, const void *rel_h, const void *rel_w, const void *O, const float *dO, int nS,
+                               float *dqkv, float *drel_h, float *drel_w, int add_rel, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+    CPX_REQUIRE(qkv && rel_h && rel_w && dO && dqkv && drel_h && drel_w && workspace && dtype_ok(dtype));
+    (void)O;                                   // not read: delta comes from the recomputed P (k_attn_bwd_dq, pass 1)
+    CPX_REQUIRE(nS > 0 && nS <= 16383);
+    const AttnBwdLayout L = attn_bwd_layout(nS);
+    CPX_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0);
+    CPX_REQUIRE((((uintptr_t)qkv | (uintptr_t)rel_h | (uintptr_t)rel_w | (uintptr_t)O | (uintptr_t)dO | (uintptr_t)dqkv) & 15) == 0);
+    char *ws = (char *)workspace;
+    float *st_m = (float *)(ws + L.off_st[0]), *st_il = (float *)(ws + L.off_st[1]), *st_dl = (float *)(ws + L.off_st[2]);
+    float *Bh = (float *)(ws + L.off_b[0]), *Bw = (float *)(ws + L.off_b[1]), *Gh = (float *)(ws + L.off_b[2]), *Gw = (float *)(ws + L.off_b[3]);
+    double *part = (double *)(ws + L.off_part);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(8, 16, nS), block(256);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_attn_bwd_dq<DT>, grid, block, 0, s, qkv, rel_h, rel_w, dO, dqkv, st_m, st_il, st_dl, Bh, Bw, Gh, Gw));
+    CPX_CHECK_LAUNCH();
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_attn_bwd_dkv<DT>, grid, block, 0, s, qkv, dO, st_m, st_il, st_dl, Bh, Bw, dqkv));
+    CPX_CHECK_LAUNCH();
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_rel_grad<DT>, dim3(63, 2, nS * 4), block, 0, s, qkv, Gh, Gw, part));
+    CPX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_rel_finish, dim3(32), block, 0, s, part, nS * 4, add_rel, drel_h, drel_w);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+extern "C" int cpx_attention_backward(int dtype, const void *qkv, const void *rel_h, const void *rel_w, const void *O, const float *dO,
+                                      int n_subtiles, float *dqkv, float *drel_h, float *drel_w, void *workspace, size_t workspace_bytes,
+                                      void *stream) {
+    return cpx_attention_backward_run(dtype, qkv, rel_h, rel_w, O, dO, n_subtiles, dqkv, drel_h, drel_w, 0, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------
+// GELU backward
+// ---------------------------------------------------------------------------
+// gelu(x) = x Phi(x), Phi(x) = erfc(-x / sqrt 2) / 2 (erfc, not 1 + erf: no cancellation in the left tail), so
+// gelu'(x) = Phi(x) + x phi(x), phi(x) = exp(-x^2 / 2) / sqrt(2 pi): 0 at -inf, 1 at +inf, never NaN for finite x
+__global__ void __launch_bounds__(256) k_gelu_bwd(const float *__restrict__ pre, const float *__restrict__ dh, size_t n4, float *__restrict__ dpre) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float4 x = *reinterpret_cast<const float4 *>(pre + 4 * i), g = *reinterpret_cast<const float4 *>(dh + 4 * i);
+    auto dg = [](float v) {
+        const float Phi = 0.5f * erfcf(-v * 0.70710678118654752440f);
+        const float phi = 0.39894228040143267794f * expf(-0.5f * v * v);
+        return fmaf(v, phi, Phi);
+    };
+    *reinterpret_cast<float4 *>(dpre + 4 * i) = make_float4(g.x * dg(x.x), g.y * dg(x.y), g.z * dg(x.z), g.w * dg(x.w));
+}
+extern "C" int cpx_gelu_backward(const float *pre, const float *dh, size_t n, float *dpre, void *stream) {
+    CPX_REQUIRE(pre && dh && dpre && n > 0 && n % 4 == 0 && n / 4 / 256 < 0x7fffffffull);
+    CPX_REQUIRE((((uintptr_t)pre | (uintptr_t)dh | (uintptr_t)dpre) & 15) == 0);
+    const size_t n4 = n / 4;
+    hipLaunchKernelGGL(k_gelu_bwd, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pre, dh, n4, dpre);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the training forward of the last K blocks
+// ---------------------------------------------------------------------------
+// workspace: per trained block j (block first_block + j) [x_in [M][1024]][qkv [M][3072]][ao [M][1024]][x_mid [M][1024]] in the network
+// dtype -- the block's input, its qkv rows, the attention output and the rows after the attention residual --, then x_out [M][1024],
+// the last block's output, then the workspace of cpx_neck_forward_train, then what the forward only passes through (V^T, the hidden
+// activations, the LayerNorm output of the unfused half path, the row statistics of the fused one).  Nothing kept is overwritten.
+// The backward recomputes in float32 from the kept tensors: both LayerNorm outputs, the lin1 pre-activation, the hidden activations
+// (rounded to the network dtype, as the forward rounds them) and the softmax.
+struct BlocksFwdLayout { size_t stride, o_x, o_qkv, o_ao, o_mid, off_out, off_neck, neck_bytes, off_vt, off_h, off_xn, off_st, total; };
+static BlocksFwdLayout blocks_fwd_layout(int nS, int dtype, int K) {
+    BlocksFwdLayout L; CpxArena a; const size_t M = (size_t)nS * 1024, es = es_of(dtype);
+    L.o_x = a.take(M * 1024 * es); L.o_qkv = a.take(M * 3072 * es); L.o_ao = a.take(M * 1024 * es); L.o_mid = a.take(M * 1024 * es);
+    L.stride = a.o;
+    a.o = L.stride * (size_t)K;
+    L.off_out = a.take(M * 1024 * es);
+    L.neck_bytes = cpx_neck_train_workspace_bytes(nS, dtype);
+    L.off_neck = a.take(L.neck_bytes);
+    L.off_vt = a.take(es == 2 ? M * 1024 * es : 0);
+    L.off_h = a.take(M * 4096 * es);
+    L.off_xn = a.take(M * 1024 * es);
+    L.off_st = a.take(es == 2 ? M * 8 * sizeof(float) : 0);
+    L.total = a.o;
+    return L;
+}
+static bool blocks_args_ok(int nS, int dtype, int K) { return nS > 0 && (size_t)nS * 1024 < 0x7fffffffull && dtype_ok(dtype) && K > 0 && K <= 4096; }
+extern "C" size_t cpx_blocks_train_workspace_bytes(int nS, int dtype, int K) {
+    return blocks_args_ok(nS, dtype, K) ? blocks_fwd_layout(nS, dtype, K).total : 0;
+}
+// off [4 K + 2]: per trained block x_in, qkv, ao, x_mid; then x_out and the workspace of cpx_neck_forward_train
+extern "C" int cpx_blocks_train_layout(int nS, int dtype, int K, size_t *off) {
+    CPX_REQUIRE(blocks_args_ok(nS, dtype, K) && off);
+    const BlocksFwdLayout L = blocks_fwd_layout(nS, dtype, K);
+    for (int j = 0; j < K; ++j) {
+        const size_t b = L.stride * (size_t)j;
+        off[4 * j] = b + L.o_x; off[4 * j + 1] = b + L.o_qkv; off[4 * j + 2] = b + L.o_ao; off[4 * j + 3] = b + L.o_mid;
+    }
+    off[4 * K] = L.off_out; off[4 * K + 1] = L.off_neck;
+    return CPX_OK;
+}
+
+// The half-precision qkv GEMM writes the V third transposed into vT [crop][channel 1024][token 1024] INSTEAD of the qkv rows
+// (CPX_EPI_QKV_BF16): the kept qkv rows get their V columns from it, an exact copy.  grid (32 token tiles, 32 channel tiles, crops)
+__global__ void __launch_bounds__(256) k_vt_to_rows(const unsigned short *__restrict__ vT, unsigned short *__restrict__ qkv) {
+    __shared__ unsigned short t[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const size_t s = blockIdx.z;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[ty + 8 * k][tx] = vT[(s * 1024 + c0 + ty + 8 * k) * 1024 + t0 + tx];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) qkv[(s * 1024 + t0 + ty + 8 * k) * 3072 + 2048 + c0 + tx] = t[tx][ty + 8 * k];
+}
+static int vt_to_rows_run(const void *vT, void *qkv, int nS, hipStream_t s) {
+    hipLaunchKernelGGL(k_vt_to_rows, dim3(32, 32, nS), dim3(256), 0, s, (const unsigned short *)vT, (unsigned short *)qkv);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+static bool blocks_weights_ok(const cpx_net_weights *w, int first_block) {
+    return w && dtype_ok(w->dtype) && w->blocks && w->depth > 0 && first_block >= 0 && first_block < w->depth &&
+           (w->dtype != CPX_DT_F32 || !w->fuse_ln) && w->n_unet_ops == 0;
+}
+
+// The launches of cpx_net_forward for blocks first_block .. depth - 1 in their order and with their MLP row parts, every GEMM writing to
+// a tensor of its own (plus, for the half types, the copy of V from vT into the kept qkv rows), then cpx_neck_forward_train.  Where cpx_net_forward takes a block's row statistics from the GEMM before it (the
+// fused half path from 16 crops up), the FIRST trained block takes them from cpx_row_stats, as cpx_net_forward itself does below 16 crops.
+extern "C" int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x, int nS, int first_block, float *head, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    CPX_REQUIRE(blocks_weights_ok(w, first_block) && x && head && workspace && blocks_args_ok(nS, w->dtype, w->depth - first_block));
+    const int dt = w->dtype, K = w->depth - first_block, M = nS * 1024;
+    const BlocksFwdLayout L = blocks_fwd_layout(nS, dt, K);
+    CPX_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0 && ((uintptr_t)x & 15) == 0);
+    char *ws = (char *)workspace;
+    const size_t es = es_of(dt);
+    hipStream_t hs = (hipStream_t)stream;
+    void *vt = ws + L.off_vt, *hb = ws + L.off_h, *xn = ws + L.off_xn;
+    float *st = (float *)(ws + L.off_st);
+    int rc;
+#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
+    CPX_HIP(hipMemcpyAsync(ws + L.o_x, x, (size_t)M * 1024 * es, hipMemcpyDeviceToDevice, hs));
+    const bool fuse = w->fuse_ln != 0 && dt != CPX_DT_F32;
+    const bool big_stats = fuse && cpx_gemm_half_uses_big_tile(M, 1024, 1024, CPX_EPI_RESID_BF16) &&
+                           cpx_gemm_half_uses_big_tile(M, 1024, 4096, CPX_EPI_RESID_BF16);
+    if (fuse) RUN(cpx_row_stats_half(dt, ws + L.o_x, M, st, stream));
+    for (int j = 0; j < K; ++j) {
+        const cpx_block_weights &b = w->blocks[first_block + j];
+        char *base = ws + L.stride * (size_t)j;
+        void *xin = base + L.o_x, *qkv = base + L.o_qkv, *ao = base + L.o_ao, *xmid = base + L.o_mid;
+        void *xout = j + 1 < K ? (void *)(base + L.stride + L.o_x) : (void *)(ws + L.off_out);
+        if (dt == CPX_DT_F32) {
+            RUN(cpx_layernorm_f32((const float *)xin, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, (float *)xn, stream));
+            RUN(cpx_gemm_f32((const float *)xn, (const float *)b.qkv_w, M, 3072, 1024, CPX_EPI_F32, b.qkv_b, nullptr, (float *)qkv, 3072, stream));
+            RUN(cpx_attention_f32((const float *)qkv, (const float *)b.rel_h, (const float *)b.rel_w, nS, (float *)ao, stream));
+            RUN(cpx_gemm_f32((const float *)ao, (const float *)b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, (const float *)xin, (float *)xmid, 1024, stream));
+            RUN(cpx_layernorm_f32((const float *)xmid, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, (float *)xn, stream));
+            RUN(cpx_gemm_f32((const float *)xn, (const float *)b.fc1_w, M, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, (float *)hb, 4096, stream));
+            RUN(cpx_gemm_f32((const float *)hb, (const float *)b.fc2_w, M, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, (const float *)xmid, (float *)xout, 1024, stream));
+        } else if (fuse) {
+            RUN(cpx_gemm_half(dt, xin, b.qkv_w, M, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072, st, b.qkv_colsum, nullptr, stream));
+            RUN(cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
+            RUN(vt_to_rows_run(vt, qkv, nS, hs));
+            RUN(cpx_gemm_half(dt, ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, xin, xmid, 1024, nullptr, nullptr, big_stats ? st : nullptr, stream));
+            if (!big_stats) RUN(cpx_row_stats_half(dt, xmid, M, st, stream));
+            const int parts = big_stats ? cpx_net_mlp_parts(nS, dt) : 1;
+            for (int pt = 0; pt < parts; ++pt) {           // (cpx_net_forward's parts: 16 384 rows each, the last one with the remainder)
+                const int r0 = pt * 16384, Mp = pt + 1 < parts ? 16384 : M - r0;
+                char *xp = (char *)xmid + (size_t)r0 * 1024 * 2, *op = (char *)xout + (size_t)r0 * 1024 * 2;
+                float *stp = st + (size_t)r0 * 8;
+                RUN(cpx_gemm_half(dt, xp, b.fc1_w, Mp, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096, stp, b.fc1_colsum, nullptr, stream));
+                RUN(cpx_gemm_half(dt, hb, b.fc2_w, Mp, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, xp, op, 1024, nullptr, nullptr, big_stats ? stp : nullptr, stream));
+            }
+            if (!big_stats) RUN(cpx_row_stats_half(dt, xout, M, st, stream));
+        } else {
+            RUN(cpx_layernorm_half(dt, xin, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, xn, stream));
+            RUN(cpx_gemm_half(dt, xn, b.qkv_w, M, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072, nullptr, nullptr, nullptr, stream));
+            RUN(cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
+            RUN(vt_to_rows_run(vt, qkv, nS, hs));
+            RUN(cpx_gemm_half(dt, ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, xin, xmid, 1024, nullptr, nullptr, nullptr, stream));
+            RUN(cpx_layernorm_half(dt, xmid, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, xn, stream));
+            RUN(cpx_gemm_half(dt, xn, b.fc1_w, M, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096, nullptr, nullptr, nullptr, stream));
+            RUN(cpx_gemm_half(dt, hb, b.fc2_w, M, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, xmid, xout, 1024, nullptr, nullptr, nullptr, stream));
+        }
+    }
+    RUN(cpx_neck_forward_train(w, ws + L.off_out, nS, head, ws + L.off_neck, L.neck_bytes, stream));
+#undef RUN
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// small kernels of the block backward
+// ---------------------------------------------------------------------------
+// LayerNorm over 1024 channels of a stored row, two-pass float32 statistics as k_layernorm_f32 -> float32; gamma == nullptr: xhat alone.
+// ROUND: the result goes through the network dtype, as the unfused half forward stores it.
+template <int DT, bool ROUND>
+__global__ void __launch_bounds__(256) k_ln_fwd1024(const void *__restrict__ x, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                    int rows, float eps, float *__restrict__ out) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const size_t base = (size_t)row * 1024 + lane * 16;
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 16; i += 4) { const float4 a = ld4<DT>(x, base + i); v[i] = a.x; v[i + 1] = a.y; v[i + 2] = a.z; v[i + 3] = a.w; }
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += v[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s * (1.0f / 1024);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { const float d = v[i] - mean; q += d * d; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.0f / sqrtf(q * (1.0f / 1024) + eps);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        float y = (v[i] - mean) * rstd;
+        if (gamma) y = y * gamma[lane * 16 + i] + beta[lane * 16 + i];
+        if constexpr (ROUND && DT == CPX_DT_BF16) y = bf16_to_f32(f32_to_bf16(y));
+        if constexpr (ROUND && DT == CPX_DT_F16) y = (float)(_Float16)y;
+        out[base + i] = y;
+    }
+}
+// in [R][Cc] of element type DT -> out [Cc][R] float32, 32 x 32 tiles through LDS; R and Cc multiples of 32
+template <int DT>
+__global__ void __launch_bounds__(256) k_transpose_f32(const void *__restrict__ in, int R, int Cc, float *__restrict__ out) {
+    __shared__ float t[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5, r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[ty + 8 * k][tx] = load_f32<DT>(in, (size_t)(r0 + ty + 8 * k) * Cc + c0 + tx);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[(size_t)(c0 + ty + 8 * k) * R + r0 + tx] = t[tx][ty + 8 * k];
+}
+template <int DT>
+__global__ void __launch_bounds__(256) k_widen_f32(const void *__restrict__ in, size_t n4, float *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) *reinterpret_cast<float4 *>(out + 4 * i) = ld4<DT>(in, 4 * i);
+}
+// h = gelu(pre) as the mlp.lin1 epilogue forms it, rounded through the network dtype as the forward stores it
+template <int DT>
+__global__ void __launch_bounds__(256) k_gelu_fwd_round(const float *__restrict__ pre, size_t n, float *__restrict__ h) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = pre[i];
+    float y = 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
+    if constexpr (DT == CPX_DT_BF16) y = bf16_to_f32(f32_to_bf16(y));
+    if constexpr (DT == CPX_DT_F16) y = (float)(_Float16)y;
+    h[i] = y;
+}
+// db[c] += sum over rows of dy[row][c]: one float64 chain per column in row order, added to what db holds, rounded once
+__global__ void __launch_bounds__(256) k_colsum_add(const float *__restrict__ dy, int rows, int N, float *__restrict__ db) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N) return;
+    double s = 0;
+#pragma unroll 8
+    for (int r = 0; r < rows; ++r) s += (double)dy[(size_t)r * N + c];
+    db[c] = (float)((double)db[c] + s);
+}
+// out = a + b (out may be a)
+__global__ void __launch_bounds__(256) k_add_f32(const float *a, const float *b, size_t n4, float *out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float4 x = *reinterpret_cast<const float4 *>(a + 4 * i), y = *reinterpret_cast<const float4 *>(b + 4 * i);
+    *reinterpret_cast<float4 *>(out + 4 * i) = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
+}
+
+// Where LayerNorm is folded into the Linear (cpx_fold_layernorm: Wf = round(W diag(gamma)), bf = b + W beta), the backward differentiates
+// what the forward multiplied by: the weight-gradient GEMM gives dWf = dpre^T xhat, and the chain rule through the fold (the rounding of
+// Wf passed straight through) gives, in place and per column k with one float64 chain over the N rows in order:
+//   dW[n][k] = dWf[n][k] gamma[k] + dbf[n] beta[k],   dgamma[k] = sum_n dWf[n][k] W[n][k],   dbeta[k] = sum_n dbf[n] W[n][k]   (db = dbf)
+__global__ void __launch_bounds__(256) k_unfold_grads(float *__restrict__ dW, const float *__restrict__ dbf, const float *__restrict__ W,
+                                                      const float *__restrict__ gamma, const float *__restrict__ beta, int N,
+                                                      float *__restrict__ dgamma, float *__restrict__ dbeta) {
+    const int k = blockIdx.x * 256 + threadIdx.x;                      // < 1024
+    const float g = gamma[k], b = beta[k];
+    double sg = 0, sb = 0;
+#pragma unroll 4
+    for (int n = 0; n < N; ++n) {
+        const size_t i = (size_t)n * 1024 + k;
+        const float dwf = dW[i], w = W[i], d = dbf[n];
+        sg += (double)dwf * (double)w;
+        sb += (double)d * (double)w;
+        dW[i] = fmaf(dwf, g, d * b);
+    }
+    dgamma[k] = (float)sg;
+    dbeta[k] = (float)sb;
+}
+__global__ void __launch_bounds__(256) k_fill_f32(float *__restrict__ p, int n, float v) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+static inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+static int transpose_run(int dtype, const void *in, int R, int Cc, float *out, hipStream_t s) {
+    CPX_REQUIRE(R % 32 == 0 && Cc % 32 == 0);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_transpose_f32<DT>, dim3(Cc / 32, R / 32), dim3(256), 0, s, in, R, Cc, out));
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+static int add_run(const float *a, const float *b, size_t n, float *out, hipStream_t s) {
+    hipLaunchKernelGGL(k_add_f32, grid1(n / 4), dim3(256), 0, s, a, b, n / 4, out);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the backward of the last K blocks
+// ---------------------------------------------------------------------------
+// grads / params of one block (float32 elements): ln1 gamma, beta | qkv W [3072][1024], b | rel_h, rel_w [64][64] (the operand tables) |
+// proj W [1024][1024], b | ln2 gamma, beta | fc1 W [4096][1024], b | fc2 W [1024][4096], b
+#define BLK_N 14
+extern "C" long long cpx_block_grad_layout(long long *off) {
+    const long long n[BLK_N] = {1024, 1024, 3072ll * 1024, 3072, 4096, 4096, 1024ll * 1024, 1024, 1024, 1024, 4096ll * 1024, 4096, 1024ll * 4096, 1024};
+    long long o = 0;
+    for (int i = 0; i < BLK_N; ++i) { if (off) off[i] = o; o += n[i]; }
+    return o;
+}
+
+// The crops are independent from the neck's dy0 down to the first trained block's input, so the backward runs them in slabs of
+// BLK_SLAB crops through ALL blocks, and every parameter gradient is the sum over the slabs in slab order: the workspace does not grow
+// with the batch.  Per slab of Ms rows (float32): dx, dxl, xn, xhat [Ms][1024]; three [Ms][4096] (pre, then dqkv | h, then dpre | dh);
+// two transposed GEMM operands [4096][Ms]; a transposed weight and the widened fc1 operand [4096][1024]; the workspaces of
+// cpx_attention_backward and cpx_layernorm_backward; three [1024] vectors.  8 and 32 crops alike: 241 MiB.
+#define BLK_SLAB 2
+struct BlocksBwdLayout { size_t dx, dxl, xn, xh, b1, b2, b3, t1, t2, wt, wop, attn, attn_bytes, ln, ln_bytes, vec, total; };
+static BlocksBwdLayout blocks_bwd_layout() {
+    BlocksBwdLayout L; CpxArena a; const size_t Ms = (size_t)BLK_SLAB * 1024;
+    L.dx = a.take(Ms * 1024 * 4); L.dxl = a.take(Ms * 1024 * 4); L.xn = a.take(Ms * 1024 * 4); L.xh = a.take(Ms * 1024 * 4);
+    L.b1 = a.take(Ms * 4096 * 4); L.b2 = a.take(Ms * 4096 * 4); L.b3 = a.take(Ms * 4096 * 4);
+    L.t1 = a.take(Ms * 4096 * 4); L.t2 = a.take(Ms * 4096 * 4);
+    L.wt = a.take((size_t)4096 * 1024 * 4); L.wop = a.take((size_t)4096 * 1024 * 4);
+    L.attn_bytes = cpx_attention_backward_workspace_bytes(BLK_SLAB); L.attn = a.take(L.attn_bytes);
+    L.ln_bytes = cpx_layernorm_backward_bytes((int)Ms, 1024); L.ln = a.take(L.ln_bytes);
+    L.vec = a.take(3 * 1024 * 4);
+    L.total = a.o;
+    return L;
+}
+extern "C" size_t cpx_blocks_backward_workspace_bytes(int nS, int dtype) {
+    if (nS <= 0 || !dtype_ok(dtype)) return 0;
+    return blocks_bwd_layout().total;
+}
+extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
+
+// w: the weights the forward ran with; params: the K blocks' UNFOLDED parameters as the forward reads them (every tensor rounded through
+// the network dtype, float32), K records of cpx_block_grad_layout (the rel slots are not read: the tables come from w); fwd_workspace:
+// what cpx_blocks_forward_train filled; dy0 [rows][256] float32: d loss / d (x_out W0^T), what cpx_neck_backward leaves at off[3] of its
+// workspace -- the gradient of the last block's output is dy0 W0, formed here.  grads: K records, gradients with respect to the
+// unfolded gamma, beta, W, b and to the operand tables.  dx_all (or NULL): [K + 1][rows][1024] float32, record j < K the gradient of
+// block first_block + j's input, record K that of the last block's output.
+extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+                                   size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
+                                   size_t workspace_bytes, void *stream) {
+    CPX_REQUIRE(blocks_weights_ok(w, first_block) && params && fwd_workspace && dy0 && grads && workspace && w->neck0_w);
+    CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block));
+    const int dt = w->dtype, K = w->depth - first_block;
+    const BlocksFwdLayout F = blocks_fwd_layout(nS, dt, K);
+    const BlocksBwdLayout L = blocks_bwd_layout();
+    CPX_REQUIRE(fwd_workspace_bytes >= F.total && workspace_bytes >= L.total);
+    CPX_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)fwd_workspace & 255) == 0);
+    CPX_REQUIRE((((uintptr_t)params | (uintptr_t)dy0 | (uintptr_t)grads | (uintptr_t)dx_all) & 15) == 0);
+    hipStream_t s = (hipStream_t)stream;
+    const char *fws = (const char *)fwd_workspace;
+    char *ws = (char *)workspace;
+    float *dx = (float *)(ws + L.dx), *dxl = (float *)(ws + L.dxl), *xn = (float *)(ws + L.xn), *xh = (float *)(ws + L.xh);
+    float *b1 = (float *)(ws + L.b1), *b2 = (float *)(ws + L.b2), *b3 = (float *)(ws + L.b3), *t1 = (float *)(ws + L.t1), *t2 = (float *)(ws + L.t2);
+    float *wt = (float *)(ws + L.wt), *wop = (float *)(ws + L.wop), *tg = (float *)(ws + L.vec), *tb = tg + 1024, *ones = tg + 2048;
+    long long go[BLK_N];
+    const long long gn = cpx_block_grad_layout(go);
+    const size_t es = es_of(dt), rows_all = (size_t)nS * 1024;
+    const bool half = dt != CPX_DT_F32, fuse = half && w->fuse_ln != 0;
+    int rc;
+#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
+    CPX_HIP(hipMemsetAsync(grads, 0, (size_t)gn * K * sizeof(float), s));
+    hipLaunchKernelGGL(k_fill_f32, dim3(4), dim3(256), 0, s, ones, 1024, 1.0f);
+    CPX_CHECK_LAUNCH();
+    // LayerNorm of stored rows -> xn (and xhat where the forward folds LayerNorm into the GEMM)
+    auto ln_fwd = [&](const void *x, const float *g, const float *b, int Ms, float *out, bool round) -> int {
+        const dim3 grid(cpx_cdiv(Ms, 4)), block(256);
+        if (round) CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL((k_ln_fwd1024<DT, true>), grid, block, 0, s, x, g, b, Ms, 1e-6f, out));
+        else CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL((k_ln_fwd1024<DT, false>), grid, block, 0, s, x, g, b, Ms, 1e-6f, out));
+        CPX_CHECK_LAUNCH();
+        return CPX_OK;
+    };
+    // a Linear y = a W^T + b with a [Ms][Kin] float32 (or `a_dt` rows of the network dtype), dy [Ms][N] float32:
+    // dW += dy^T a, db += column sums of dy, da = dy W
+    auto linear_bwd = [&](const float *dy, const void *a, int a_dt, const float *W, int Ms, int N, int Kin, float *dW, float *db, float *da) -> int {
+        RUN(transpose_run(CPX_DT_F32, dy, Ms, N, t1, s));
+        RUN(transpose_run(a_dt, a, Ms, Kin, t2, s));
+        RUN(cpx_gemm_f32(t1, t2, N, Kin, Ms, CPX_EPI_RESID_BF16, nullptr, dW, dW, Kin, stream));
+        hipLaunchKernelGGL(k_colsum_add, grid1(N), dim3(256), 0, s, dy, Ms, N, db);
+        CPX_CHECK_LAUNCH();
+        RUN(transpose_run(CPX_DT_F32, W, N, Kin, wt, s));
+        RUN(cpx_gemm_f32(dy, wt, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, stream));
+        return CPX_OK;
+    };
+    // folded: dout is the gradient of xhat (gamma = 1 here; dgamma and dbeta come from k_unfold_grads after the last slab)
+    auto ln_bwd = [&](const void *x, const float *g, const float *dout, int Ms, float *dgamma, float *dbeta) -> int {
+        RUN(cpx_layernorm_backward(dt, x, fuse ? ones : g, dout, Ms, 1024, 1e-6f, dxl, tg, tb, ws + L.ln, L.ln_bytes, stream));
+        if (!fuse) {
+            RUN(add_run(dgamma, tg, 1024, dgamma, s));
+            RUN(add_run(dbeta, tb, 1024, dbeta, s));
+        }
+        return add_run(dx, dxl, (size_t)Ms * 1024, dx, s);           // the residual: dx is now the gradient of the LayerNorm's input rows
+    };
+    auto widen = [&](const void *src, size_t n) -> int {
+        CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_widen_f32<DT>, grid1(n / 4), dim3(256), 0, s, src, n / 4, wop));
+        CPX_CHECK_LAUNCH();
+        return CPX_OK;
+    };
+    for (int c0 = 0; c0 < nS; c0 += BLK_SLAB) {
+        const int nc = std::min(BLK_SLAB, nS - c0), Ms = nc * 1024;
+        const size_t r0 = (size_t)c0 * 1024;
+        // the gradient of the last block's output: dy0 W0 (the rounded operand [256][1024], widened and transposed)
+        RUN(cpx_wt_run(dt, w->neck0_w, 256, 1024, 1024, wt, s));
+        RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, stream));
+        if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)K * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
+        for (int j = K - 1; j >= 0; --j) {
+            const cpx_block_weights &b = w->blocks[first_block + j];
+            const float *P = params + (size_t)gn * j;
+            float *Gd = grads + (size_t)gn * j;
+            const char *base = fws + F.stride * (size_t)j;
+            const void *xin = base + F.o_x + r0 * 1024 * es, *qkv = base + F.o_qkv + r0 * 3072 * es, *ao = base + F.o_ao + r0 * 1024 * es,
+                       *xmid = base + F.o_mid + r0 * 1024 * es;
+            // ---- the MLP: x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2 ----
+            if (fuse) RUN(ln_fwd(xmid, nullptr, nullptr, Ms, xh, false));
+            else RUN(ln_fwd(xmid, P + go[8], P + go[9], Ms, xn, half));
+            const float *w1op = (const float *)b.fc1_w;              // the operand the forward multiplied by (folded where it folds)
+            if (half) {
+                RUN(widen(b.fc1_w, (size_t)4096 * 1024));
+                w1op = wop;
+            }
+            RUN(cpx_gemm_f32(fuse ? xh : xn, w1op, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, stream));     // pre
+            CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_gelu_fwd_round<DT>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2));   // h
+            CPX_CHECK_LAUNCH();
+            RUN(linear_bwd(dx, b2, CPX_DT_F32, P + go[12], Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                // fc2 -> dh
+            RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                // dpre
+            RUN(linear_bwd(b2, fuse ? xh : xn, CPX_DT_F32, fuse ? w1op : P + go[10], Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));   // fc1 -> d LN2 output (folded: d xhat)
+            RUN(ln_bwd(xmid, P + go[8], b3, Ms, Gd + go[8], Gd + go[9]));                                                 // dx = d x_mid
+            // ---- attention: x_mid = x_in + attention(LN1(x_in) Wqkv^T + bqkv) Wp^T + bp ----
+            RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
+            RUN(cpx_attention_backward_run(dt, qkv, b.rel_h, b.rel_w, nullptr, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
+            if (fuse) {
+                RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
+                RUN(widen(b.qkv_w, (size_t)3072 * 1024));
+            } else RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, half));
+            RUN(linear_bwd(b1, fuse ? xh : xn, CPX_DT_F32, fuse ? wop : P + go[2], Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));       // qkv -> d LN1 output (folded: d xhat)
+            RUN(ln_bwd(xin, P + go[0], b3, Ms, Gd + go[0], Gd + go[1]));                                                  // dx = d x_in
+            if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)j * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    if (fuse)                                                          // the W slots hold dWf, the b slots dbf, summed over the slabs
+        for (int j = 0; j < K; ++j) {
+            const float *P = params + (size_t)gn * j;
+            float *Gd = grads + (size_t)gn * j;
+            hipLaunchKernelGGL(k_unfold_grads, dim3(4), dim3(256), 0, s, Gd + go[2], Gd + go[3], P + go[2], P + go[0], P + go[1], 3072, Gd + go[0], Gd + go[1]);
+            CPX_CHECK_LAUNCH();
+            hipLaunchKernelGGL(k_unfold_grads, dim3(4), dim3(256), 0, s, Gd + go[10], Gd + go[11], P + go[10], P + go[8], P + go[9], 4096, Gd + go[8], Gd + go[9]);
+            CPX_CHECK_LAUNCH();
+        }
+#undef RUN
+    return CPX_OK;
+}

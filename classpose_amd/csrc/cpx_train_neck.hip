@@ -3,7 +3,8 @@
 //   y0 = x W0^T  ->  a1 = LayerNorm2d(y0)  ->  y2 = conv3x3(a1, W2)  ->  feat = LayerNorm2d(y2)  ->  head = feat Wh^T + bh,
 // on the last block's output x [nS * 1024][1024], which cpx_net_forward leaves in its workspace (cpx_net_backbone_offset).
 //   * cpx_neck_forward_train   the tail itself (cpx_net_tail, cpx_net.hip) with four tensors of their own: the saved activations
-//   * k_ln_bwd / k_ln_bwd_finish   LayerNorm over channels, backward: one wave per row, everything formed in float64 and rounded once
+//   * k_ln_bwd / k_ln_bwd_finish   LayerNorm over channels (256, or the blocks' 1024), backward: one wave per row, everything formed in
+//                              float64 and rounded once
 //   * cpx_neck_backward        head data gradient -> LN2 -> conv3x3 (weight and data gradient) -> LN1 -> conv1x1 weight gradient; the
 //                              convolutions run the kernels of the UNet head's backward (cpx_train_unet.hip, through cpx_internal.h)
 // Rounding to the network dtype is the identity in the backward (straight-through).  No gradient leaves towards the backbone.
@@ -74,80 +75,106 @@ __device__ __forceinline__ void load4(const void *y, size_t idx, double v[4]) {
     }
 }
 
-// One wave owns whole rows (C = 256: four channels per lane); a workgroup owns LNB_ROWS consecutive rows, wave w rows 16 w .. 16 w + 15 of
-// them.  Per row mean, biased variance and rstd are recomputed from y as stored; part [workgroup][2][256] float64 receives the
-// workgroup's column sums of dout * xhat and of dout (rows in order inside a wave, then wave 0 + 1 + 2 + 3).
-template <int DT>
+// One wave owns whole rows: lane l holds C / 64 channels, four consecutive ones per group of 256 (channel 256 j + 4 l + k: C = 256, the
+// neck, is one group; C = 1024, a transformer block's LayerNorm, four).  A workgroup owns LNB_ROWS consecutive rows, wave w rows
+// 16 w .. 16 w + 15 of them.  Per row mean, biased variance and rstd are recomputed from y as stored; part [workgroup][2][C] float64
+// receives the workgroup's column sums of dout * xhat and of dout (rows in order inside a wave, then wave 0 + 1 + 2 + 3).
+template <int DT, int C>
 __global__ void __launch_bounds__(256) k_ln_bwd(const void *__restrict__ y, const float *__restrict__ gamma, const float *__restrict__ dout,
                                                 int rows, double eps, float *__restrict__ dy, double *__restrict__ part) {
-    __shared__ double sm[4][2][NECK_C];
+    constexpr int PER = C / 64, NG = PER / 4;
+    __shared__ double sm[4][2][C];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c0 = lane * 4;
-    const float4 gm = *reinterpret_cast<const float4 *>(gamma + c0);
-    const double ga[4] = {gm.x, gm.y, gm.z, gm.w};
-    double dg[4] = {0, 0, 0, 0}, db[4] = {0, 0, 0, 0};
+    double ga[PER], dg[PER], db[PER];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        const float4 gm = *reinterpret_cast<const float4 *>(gamma + 256 * j + c0);
+        ga[4 * j] = gm.x; ga[4 * j + 1] = gm.y; ga[4 * j + 2] = gm.z; ga[4 * j + 3] = gm.w;
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { dg[k] = 0; db[k] = 0; }
     const int row0 = blockIdx.x * LNB_ROWS + wave * (LNB_ROWS / 4);
     const int row1 = min(rows, row0 + LNB_ROWS / 4);
     for (int row = row0; row < row1; ++row) {                         // (wave-uniform bounds)
-        const size_t idx = (size_t)row * NECK_C + c0;
-        double v[4];
-        load4<DT>(y, idx, v);
-        const float4 d4 = *reinterpret_cast<const float4 *>(dout + idx);
-        const double d[4] = {d4.x, d4.y, d4.z, d4.w};
-        const double mean = wave_sum(((v[0] + v[1]) + v[2]) + v[3]) / NECK_C;
+        const size_t idx = (size_t)row * C + c0;
+        double v[PER], d[PER];
+#pragma unroll
+        for (int j = 0; j < NG; ++j) {
+            load4<DT>(y, idx + 256 * j, v + 4 * j);
+            const float4 d4 = *reinterpret_cast<const float4 *>(dout + idx + 256 * j);
+            d[4 * j] = d4.x; d[4 * j + 1] = d4.y; d[4 * j + 2] = d4.z; d[4 * j + 3] = d4.w;
+        }
+        double sv = v[0];
+#pragma unroll
+        for (int k = 1; k < PER; ++k) sv += v[k];
+        const double mean = wave_sum(sv) / C;
         double q = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k] -= mean; q += v[k] * v[k]; }
-        const double rstd = 1.0 / sqrt(wave_sum(q) / NECK_C + eps);
-        double g[4], sg = 0, sgx = 0;
+        for (int k = 0; k < PER; ++k) { v[k] -= mean; q += v[k] * v[k]; }
+        const double rstd = 1.0 / sqrt(wave_sum(q) / C + eps);
+        double g[PER], sg = 0, sgx = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k] *= rstd; g[k] = d[k] * ga[k]; sg += g[k]; sgx += g[k] * v[k]; }       // v is xhat from here
-        sg = wave_sum(sg) / NECK_C; sgx = wave_sum(sgx) / NECK_C;
-        float4 o;
-        o.x = (float)(rstd * ((g[0] - sg) - v[0] * sgx)); o.y = (float)(rstd * ((g[1] - sg) - v[1] * sgx));
-        o.z = (float)(rstd * ((g[2] - sg) - v[2] * sgx)); o.w = (float)(rstd * ((g[3] - sg) - v[3] * sgx));
-        *reinterpret_cast<float4 *>(dy + idx) = o;
+        for (int k = 0; k < PER; ++k) { v[k] *= rstd; g[k] = d[k] * ga[k]; sg += g[k]; sgx += g[k] * v[k]; }     // v is xhat from here
+        sg = wave_sum(sg) / C; sgx = wave_sum(sgx) / C;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { dg[k] += d[k] * v[k]; db[k] += d[k]; }
+        for (int j = 0; j < NG; ++j) {
+            const int k = 4 * j;
+            float4 o;
+            o.x = (float)(rstd * ((g[k] - sg) - v[k] * sgx)); o.y = (float)(rstd * ((g[k + 1] - sg) - v[k + 1] * sgx));
+            o.z = (float)(rstd * ((g[k + 2] - sg) - v[k + 2] * sgx)); o.w = (float)(rstd * ((g[k + 3] - sg) - v[k + 3] * sgx));
+            *reinterpret_cast<float4 *>(dy + idx + 256 * j) = o;
+        }
+#pragma unroll
+        for (int k = 0; k < PER; ++k) { dg[k] += d[k] * v[k]; db[k] += d[k]; }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { sm[wave][0][c0 + k] = dg[k]; sm[wave][1][c0 + k] = db[k]; }
+    for (int k = 0; k < PER; ++k) { sm[wave][0][256 * (k >> 2) + c0 + (k & 3)] = dg[k]; sm[wave][1][256 * (k >> 2) + c0 + (k & 3)] = db[k]; }
     __syncthreads();
-    const int c = threadIdx.x;
-    double *p = part + (size_t)blockIdx.x * 2 * NECK_C;
-    p[c] = ((sm[0][0][c] + sm[1][0][c]) + sm[2][0][c]) + sm[3][0][c];
-    p[NECK_C + c] = ((sm[0][1][c] + sm[1][1][c]) + sm[2][1][c]) + sm[3][1][c];
+    double *p = part + (size_t)blockIdx.x * 2 * C;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        p[c] = ((sm[0][0][c] + sm[1][0][c]) + sm[2][0][c]) + sm[3][0][c];
+        p[C + c] = ((sm[0][1][c] + sm[1][1][c]) + sm[2][1][c]) + sm[3][1][c];
+    }
 }
 
-// one workgroup of 512: thread (j, c) adds sum j of column c over the partials in workgroup order, as k_seg_finish adds its records
-// (the loads of eight partials are in flight together; the additions keep their order)
-__global__ void __launch_bounds__(512) k_ln_bwd_finish(const double *__restrict__ part, int nblk, float *__restrict__ dgamma,
+// workgroups of 512 over the 2 C sums: thread t = j * C + c (the offset inside a workgroup's record) adds sum j of column c over the
+// partials in workgroup order, as k_seg_finish adds its records (the loads of eight partials are in flight together; the additions
+// keep their order)
+__global__ void __launch_bounds__(512) k_ln_bwd_finish(const double *__restrict__ part, int nblk, int C, float *__restrict__ dgamma,
                                                        float *__restrict__ dbeta) {
-    const int t = threadIdx.x;                                         // = j * 256 + c: the offset inside a workgroup's record
+    const int t = blockIdx.x * 512 + threadIdx.x;
     double s = 0;
 #pragma unroll 8
-    for (int k = 0; k < nblk; ++k) s += part[(size_t)k * 2 * NECK_C + t];
-    if (t < NECK_C) dgamma[t] = (float)s;
-    else dbeta[t - NECK_C] = (float)s;
+    for (int k = 0; k < nblk; ++k) s += part[(size_t)k * 2 * C + t];
+    if (t < C) dgamma[t] = (float)s;
+    else dbeta[t - C] = (float)s;
 }
 
 static int ln_nblk(int rows) { return (rows + LNB_ROWS - 1) / LNB_ROWS; }
+static bool ln_c_ok(int C) { return C == NECK_C || C == NECK_K0; }
+// cpx_layernorm_backward_workspace_bytes answers for the neck's C = 256 alone, as it always has; cpx_layernorm_backward_bytes for
+// both widths
+extern "C" size_t cpx_layernorm_backward_bytes(int rows, int C) {
+    if (rows <= 0 || !ln_c_ok(C)) return 0;
+    return cpx_align_up((size_t)ln_nblk(rows) * 2 * C * sizeof(double), 256);
+}
 extern "C" size_t cpx_layernorm_backward_workspace_bytes(int rows, int C) {
-    if (rows <= 0 || C != NECK_C) return 0;
-    return cpx_align_up((size_t)ln_nblk(rows) * 2 * NECK_C * sizeof(double), 256);
+    return C == NECK_C ? cpx_layernorm_backward_bytes(rows, C) : 0;
 }
 extern "C" int cpx_layernorm_backward(int dtype, const void *y, const float *gamma, const float *dout, int rows, int C, float eps,
                                       float *dy, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(y && gamma && dout && dy && dgamma && dbeta && workspace && rows > 0 && dtype_ok(dtype));
-    CPX_REQUIRE(C == NECK_C);                                          // four channels per lane: the neck's LayerNorm2d
-    CPX_REQUIRE(eps >= 0.f && workspace_bytes >= cpx_layernorm_backward_workspace_bytes(rows, C) && ((uintptr_t)workspace & 7) == 0);
+    CPX_REQUIRE(ln_c_ok(C));                                           // 4 or 16 channels per lane: LayerNorm2d of the neck, LayerNorm of a block
+    CPX_REQUIRE(eps >= 0.f && workspace_bytes >= cpx_layernorm_backward_bytes(rows, C) && ((uintptr_t)workspace & 7) == 0);
     CPX_REQUIRE((((uintptr_t)y | (uintptr_t)gamma | (uintptr_t)dout | (uintptr_t)dy) & 15) == 0);
     hipStream_t s = (hipStream_t)stream;
     const int nblk = ln_nblk(rows);
     double *part = (double *)workspace;
     const dim3 grid(nblk), block(256);
-    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_ln_bwd<DT>, grid, block, 0, s, y, gamma, dout, rows, (double)eps, dy, part));
+    if (C == NECK_C) CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL((k_ln_bwd<DT, NECK_C>), grid, block, 0, s, y, gamma, dout, rows, (double)eps, dy, part));
+    else CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL((k_ln_bwd<DT, NECK_K0>), grid, block, 0, s, y, gamma, dout, rows, (double)eps, dy, part));
     CPX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ln_bwd_finish, dim3(1), dim3(2 * NECK_C), 0, s, part, nblk, dgamma, dbeta);
+    hipLaunchKernelGGL(k_ln_bwd_finish, dim3(2 * C / 512), dim3(512), 0, s, part, nblk, C, dgamma, dbeta);
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }

@@ -4,7 +4,7 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
         --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
-        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck]
+        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K]
     python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
         [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
@@ -125,6 +125,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="train the neck (encoder.neck.*: 1x1 conv, LayerNorm2d, 3x3 conv, LayerNorm2d) next to the class head, from "
                         "cached backbone rows: the reference's --freeze backbone segmentation_head; with --train_flow_head its "
                         "--freeze backbone; not with a UNet class head")
+    p.add_argument("--train_blocks", type=int, default=0, metavar="K",
+                   help="train the last K transformer blocks (encoder.blocks.*) next to the neck and the class head, from the cached "
+                        "input rows of block depth - K; turns --train_neck on; not with a UNet class head.  --train_blocks 24 "
+                        "--train_flow_head is what the reference trains without --freeze, except for the patch embedding and the "
+                        "position table, which stay fixed")
     p.add_argument("--freeze", nargs="+", default=None, choices=["none", "backbone", "segmentation_head", "neck"],
                    help="the reference's spelling of the same choice: 'backbone neck' = --train_flow_head, 'backbone "
                         "segmentation_head neck' = the default (class head only); nothing else is built")
@@ -160,6 +165,20 @@ def flow_head_from_freeze(freeze, train_flow_head: bool) -> bool:
 def check_args(args) -> None:
     """The combinations the parser cannot express; raises ``SystemExit`` with the reason."""
     args.train_neck = bool(getattr(args, "train_neck", False))
+    args.train_blocks = int(getattr(args, "train_blocks", 0) or 0)
+    if args.train_blocks < 0:
+        raise SystemExit("--train_blocks: a count of blocks, 0 for none")
+    if args.train_blocks:
+        if getattr(args, "feature_transformation_structure", None) is not None:
+            raise SystemExit("--train_blocks: the blocks do not train under a UNet class head (its backward gives the neck output no "
+                             "gradient, so none reaches the blocks)")
+        if "neck" in (getattr(args, "freeze", None) or ()):
+            raise SystemExit("--train_blocks contradicts --freeze ... neck ...: the blocks train through the neck, which then trains too; "
+                             "give one or the other")
+        if not args.train_neck:
+            get_logger("classpose_amd.train_head").info(">>> --train_blocks %d turns --train_neck on: the blocks' gradient comes through the neck",
+                                                        args.train_blocks)
+        args.train_neck = True
     if args.train_neck and "neck" in (getattr(args, "freeze", None) or ()):
         raise SystemExit("--train_neck contradicts --freeze ... neck ...: give one or the other")
     if args.train_neck and getattr(args, "feature_transformation_structure", None) is not None:
@@ -262,6 +281,19 @@ def _host_maps(instances):
     return instances.cpu().numpy() if hasattr(instances, "cpu") else instances
 
 
+def _trainer_of(args, make_trainer, nclasses):
+    """The trainer the arguments ask for; a block count the checkpoint does not have ends the run with the reason."""
+    try:
+        return make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
+                            feature_transformation_structure=args.feature_transformation_structure,
+                            class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
+                            train_neck=args.train_neck, train_blocks=args.train_blocks)
+    except (ValueError, NotImplementedError) as e:
+        if args.train_blocks and "train_blocks" in str(e):
+            raise SystemExit(f"--train_blocks {args.train_blocks}: {e}")
+        raise
+
+
 def main_data_path(args) -> None:
     """``--data_path``: whole annotated images of any size, from the reference's directory to a device pool."""
     from .. import augment, dataset_stats, train_data
@@ -276,10 +308,7 @@ def main_data_path(args) -> None:
         data, test = data.subset(tr), (None if te is None or len(te) == 0 else data.subset(te))
     logger.info(f"{len(data)} training images, {len(test) if test is not None else 0} validation images")
     nclasses = data.n_classes if args.nclasses is None else args.nclasses
-    trainer = make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
-                           feature_transformation_structure=args.feature_transformation_structure,
-                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
-                           train_neck=args.train_neck)
+    trainer = _trainer_of(args, make_trainer, nclasses)
     if data.n_classes > trainer.nclasses:
         raise SystemExit(f"the labels hold class {data.n_classes - 1} but the head has {trainer.nclasses} classes")
     train_probs = diameters = None
@@ -340,10 +369,7 @@ def main(args) -> None:
     images, labels = np.load(args.images), np.load(args.labels)
     test_images = np.load(args.test_images) if args.test_images else None
     test_labels = np.load(args.test_labels) if args.test_labels else None
-    trainer = make_trainer(args.pretrained_model, nclasses=args.nclasses, device=args.device, precision=args.precision,
-                           feature_transformation_structure=args.feature_transformation_structure,
-                           class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
-                           train_neck=args.train_neck)
+    trainer = _trainer_of(args, make_trainer, args.nclasses)
     train_probs = diameters = instances = test_instances = None
     if args.instances_from_labels:
         instances = _derive_instances(labels, args, "--labels")

@@ -799,22 +799,24 @@ def neck_forward_train(weights, x: torch.Tensor, head: torch.Tensor | None = Non
 
 
 def layernorm_backward(y: torch.Tensor, gamma: torch.Tensor, dout: torch.Tensor, eps: float = 1e-6):
-    """``cpx_layernorm_backward``: (dy (rows, 256) float32, dgamma (256,), dbeta (256,)) of LayerNorm over the 256 channels of the
-    stored pre-norm tensor ``y`` (rows, 256) in the network dtype, from ``dout`` (rows, 256) float32; float64 inside, rounded once."""
-    if y.dim() != 2 or y.shape[1] != 256 or y.dtype not in _DT or not y.is_contiguous() or not y.is_cuda:
-        raise ValueError("layernorm_backward: y must be contiguous device rows (rows, 256) of bf16 / fp16 / fp32")
+    """``cpx_layernorm_backward``: (dy (rows, C) float32, dgamma (C,), dbeta (C,)) of LayerNorm over the C = 256 (the neck) or 1024 (a
+    transformer block) channels of the stored pre-norm tensor ``y`` (rows, C) in the network dtype, from ``dout`` (rows, C) float32;
+    float64 inside, rounded once."""
+    if y.dim() != 2 or y.shape[1] not in (256, 1024) or y.dtype not in _DT or not y.is_contiguous() or not y.is_cuda:
+        raise ValueError("layernorm_backward: y must be contiguous device rows (rows, 256) or (rows, 1024) of bf16 / fp16 / fp32")
+    Cn = y.shape[1]
     if dout.dtype != torch.float32 or dout.shape != y.shape or not dout.is_contiguous() or dout.device != y.device:
         raise ValueError("layernorm_backward: dout must be contiguous float32 of y's shape on y's device")
-    if gamma.dtype != torch.float32 or gamma.numel() != 256 or not gamma.is_contiguous() or gamma.device != y.device:
-        raise ValueError("layernorm_backward: gamma must be float32 (256,) on y's device")
+    if gamma.dtype != torch.float32 or gamma.numel() != Cn or not gamma.is_contiguous() or gamma.device != y.device:
+        raise ValueError("layernorm_backward: gamma must be float32 (C,) on y's device")
     rows, dev, L = y.shape[0], y.device, _lib.lib()
-    dy = torch.empty((rows, 256), dtype=torch.float32, device=dev)
-    dgamma, dbeta = torch.empty(256, dtype=torch.float32, device=dev), torch.empty(256, dtype=torch.float32, device=dev)
-    key = ("lnbwd", rows, str(dev))
+    dy = torch.empty((rows, Cn), dtype=torch.float32, device=dev)
+    dgamma, dbeta = torch.empty(Cn, dtype=torch.float32, device=dev), torch.empty(Cn, dtype=torch.float32, device=dev)
+    key = ("lnbwd", rows, Cn, str(dev))
     if key not in _ws_cache:
-        _ws_cache[key] = torch.empty(L.cpx_layernorm_backward_workspace_bytes(rows, 256), dtype=torch.uint8, device=dev)
+        _ws_cache[key] = torch.empty(L.cpx_layernorm_backward_bytes(rows, Cn), dtype=torch.uint8, device=dev)
     ws = _ws_cache[key]
-    check(L.cpx_layernorm_backward(_DT[y.dtype], ptr(y), ptr(gamma), ptr(dout), rows, 256, eps, ptr(dy), ptr(dgamma), ptr(dbeta),
+    check(L.cpx_layernorm_backward(_DT[y.dtype], ptr(y), ptr(gamma), ptr(dout), rows, Cn, eps, ptr(dy), ptr(dgamma), ptr(dbeta),
                                    ptr(ws), ws.numel(), _stream(dev)), "layernorm_backward")
     return dy, dgamma, dbeta
 
@@ -839,6 +841,14 @@ def neck_backward_workspace(n_subtiles: int, dtype_code: int, ld_head: int, devi
     return torch.empty(n, dtype=torch.uint8, device=device), [int(v) for v in off]
 
 
+def neck_backward_workspace_offsets(n_subtiles: int, dtype_code: int, ld_head: int) -> list[int]:
+    """Byte offsets of dfeat, dy2, da1, dy0 inside the workspace of ``neck_backward`` (no allocation)."""
+    off = (C.c_size_t * 4)()
+    if _lib.lib().cpx_neck_backward_workspace_bytes(n_subtiles, dtype_code, ld_head, off) == 0:
+        raise ValueError("neck_backward_workspace_offsets: invalid n_subtiles / dtype / ld_head")
+    return [int(v) for v in off]
+
+
 def neck_backward(weights, x: torch.Tensor, fwd: NeckForwardOut, dhead: torch.Tensor, grads: torch.Tensor | None = None,
                   workspace: torch.Tensor | None = None) -> torch.Tensor:
     """``cpx_neck_backward``: the gradients of the six neck tensors of ``weights`` into the flat float32 ``grads``
@@ -861,6 +871,154 @@ def neck_backward(weights, x: torch.Tensor, fwd: NeckForwardOut, dhead: torch.Te
         raise ValueError("neck_backward: workspaces are uint8 tensors")
     check(L.cpx_neck_backward(C.byref(c), ptr(x), rows // 1024, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dhead), ptr(grads),
                               ptr(workspace), workspace.numel(), _stream(dev)), "neck_backward")
+    return grads
+
+
+# ---- training the transformer blocks (csrc/cpx_train_blocks.hip) ---------------------------------------------------
+def attention_backward_workspace(n_subtiles: int, device) -> torch.Tensor:
+    n = _lib.lib().cpx_attention_backward_workspace_bytes(n_subtiles)
+    if n == 0:
+        raise ValueError("attention_backward_workspace: invalid n_subtiles")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def attention_backward(qkv: torch.Tensor, rel_h: torch.Tensor, rel_w: torch.Tensor, out: torch.Tensor, dout: torch.Tensor,
+                       workspace: torch.Tensor | None = None):
+    """``cpx_attention_backward``: (dqkv (rows, 3072), drel_h (64, 64), drel_w (64, 64)), all float32, of the function
+    ``attention(qkv.float(), rel_h.float(), rel_w.float())`` computes, from the stored ``qkv`` (n * 1024, 3072) and attention output
+    ``out`` (n * 1024, 1024) in the network dtype, the operand tables (64, 64) of that dtype (rel_pos / scale, zero last row) and
+    ``dout`` (n * 1024, 1024) float32.  The table gradients are with respect to the operand tables, summed over heads and crops."""
+    rows, dev = qkv.shape[0], qkv.device
+    if qkv.dim() != 2 or qkv.shape[1] != 3072 or rows == 0 or rows % 1024 or qkv.dtype not in _DT or not qkv.is_contiguous() or not qkv.is_cuda:
+        raise ValueError("attention_backward: qkv must be contiguous device rows (n * 1024, 3072) of bf16 / fp16 / fp32")
+    for t, shape, what in ((rel_h, (64, 64), "rel_h"), (rel_w, (64, 64), "rel_w"), (out, (rows, 1024), "out")):
+        if t.dtype != qkv.dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"attention_backward: {what} must be contiguous {shape} of qkv's dtype on its device")
+    if dout.dtype != torch.float32 or tuple(dout.shape) != (rows, 1024) or not dout.is_contiguous() or dout.device != dev:
+        raise ValueError("attention_backward: dout must be contiguous float32 (rows, 1024) on qkv's device")
+    if workspace is None:
+        workspace = attention_backward_workspace(rows // 1024, dev)
+    if workspace.dtype != torch.uint8:
+        raise ValueError("attention_backward: the workspace is a uint8 tensor")
+    dqkv = torch.empty((rows, 3072), dtype=torch.float32, device=dev)
+    drh, drw = torch.empty((64, 64), dtype=torch.float32, device=dev), torch.empty((64, 64), dtype=torch.float32, device=dev)
+    check(_lib.lib().cpx_attention_backward(_DT[qkv.dtype], ptr(qkv), ptr(rel_h), ptr(rel_w), ptr(out), ptr(dout), rows // 1024, ptr(dqkv),
+                                            ptr(drh), ptr(drw), ptr(workspace), workspace.numel(), _stream(dev)), "attention_backward")
+    return dqkv, drh, drw
+
+
+def gelu_backward(pre: torch.Tensor, dh: torch.Tensor) -> torch.Tensor:
+    """``cpx_gelu_backward``: dh * gelu'(pre) for the erf GELU, float32 tensors of one shape (a multiple of 4 elements)."""
+    if pre.dtype != torch.float32 or dh.dtype != torch.float32 or pre.shape != dh.shape or not pre.is_contiguous() or not dh.is_contiguous() \
+            or not pre.is_cuda or dh.device != pre.device or pre.numel() == 0 or pre.numel() % 4:
+        raise ValueError("gelu_backward: pre and dh must be contiguous float32 device tensors of one shape, a multiple of 4 elements")
+    out = torch.empty_like(pre)
+    check(_lib.lib().cpx_gelu_backward(ptr(pre), ptr(dh), pre.numel(), ptr(out), _stream(pre.device)), "gelu_backward")
+    return out
+
+
+BLOCK_GRAD_NAMES = ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "rel_h", "rel_w", "proj_w", "proj_b", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
+BLOCK_GRAD_SHAPES = ((1024,), (1024,), (3072, 1024), (3072,), (64, 64), (64, 64), (1024, 1024), (1024,), (1024,), (1024,), (4096, 1024),
+                     (4096,), (1024, 4096), (1024,))
+
+
+def block_grad_layout() -> tuple[int, list[int]]:
+    """(element count, element offsets of the 14 tensors of ``BLOCK_GRAD_NAMES``) of one block's record in the flat float32 gradient
+    and parameter buffers of ``blocks_backward`` (``cpx_block_grad_layout``)."""
+    off = (C.c_longlong * 14)()
+    n = _lib.lib().cpx_block_grad_layout(off)
+    return int(n), [int(v) for v in off]
+
+
+class BlocksForwardOut:
+    """Results of ``blocks_forward_train``: ``head`` float32 (rows, ld_head); per trained block views ``x[j]``, ``qkv[j]``, ``ao[j]``,
+    ``x_mid[j]`` into ``workspace`` (the block's input, qkv rows, attention output, rows after the attention residual); ``x_out``, the
+    last block's output (the neck's input); and ``neck``, the ``NeckForwardOut`` of the tail."""
+    __slots__ = ("head", "x", "qkv", "ao", "x_mid", "x_out", "neck", "workspace", "first_block")
+
+
+def blocks_train_workspace(n_subtiles: int, dtype_code: int, n_blocks: int, device) -> torch.Tensor:
+    n = _lib.lib().cpx_blocks_train_workspace_bytes(n_subtiles, dtype_code, n_blocks)
+    if n == 0:
+        raise ValueError("blocks_train_workspace: invalid n_subtiles / dtype / n_blocks")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def blocks_forward_train(weights, x: torch.Tensor, first_block: int, head: torch.Tensor | None = None,
+                         workspace: torch.Tensor | None = None) -> BlocksForwardOut:
+    """``cpx_blocks_forward_train``: blocks ``first_block`` .. depth - 1 of ``weights`` (an ``engine.NetWeights``) and the tail on the rows
+    ``x`` (n * 1024, 1024) in the network dtype -- the input of block ``first_block`` --, keeping what the backward needs."""
+    c, L = weights.c, _lib.lib()
+    if x.dim() != 2 or x.shape[1] != 1024 or x.shape[0] == 0 or x.shape[0] % 1024 or x.dtype not in _DT or _DT[x.dtype] != c.dtype \
+            or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError("blocks_forward_train: x must be contiguous device rows (n * 1024, 1024) in the network dtype")
+    if c.n_unet_ops:
+        raise NotImplementedError("blocks_forward_train: the blocks do not train under a UNet semantic head (the neck does not)")
+    if not 0 <= first_block < c.depth:
+        raise ValueError(f"blocks_forward_train: first_block {first_block} outside 0 .. {c.depth - 1}")
+    rows, nS, dev, K = x.shape[0], x.shape[0] // 1024, x.device, c.depth - first_block
+    if workspace is None:
+        workspace = blocks_train_workspace(nS, c.dtype, K, dev)
+    if head is None:
+        head = torch.empty((rows, c.ld_head), dtype=torch.float32, device=dev)
+    if head.dtype != torch.float32 or tuple(head.shape) != (rows, c.ld_head) or not head.is_contiguous() or workspace.dtype != torch.uint8:
+        raise ValueError("blocks_forward_train: head must be contiguous float32 (rows, ld_head) and workspace uint8")
+    check(L.cpx_blocks_forward_train(C.byref(c), ptr(x), nS, first_block, ptr(head), ptr(workspace), workspace.numel(), _stream(dev)),
+          "blocks_forward_train")
+    off = (C.c_size_t * (4 * K + 2))()
+    check(L.cpx_blocks_train_layout(nS, c.dtype, K, off), "blocks_train_layout")
+    es = x.element_size()
+
+    def view(o, width):
+        return workspace[o:o + rows * width * es].view(x.dtype).view(rows, width)
+    o = BlocksForwardOut()
+    o.head, o.workspace, o.first_block = head, workspace, first_block
+    o.x, o.qkv, o.ao, o.x_mid = ([view(off[4 * j + i], wd) for j in range(K)] for i, wd in enumerate((1024, 3072, 1024, 1024)))
+    o.x_out = view(off[4 * K], 1024)
+    nb = L.cpx_neck_train_workspace_bytes(nS, c.dtype)
+    nws = workspace[off[4 * K + 1]:off[4 * K + 1] + nb]
+    noff = (C.c_size_t * 4)()
+    check(L.cpx_neck_train_layout(nS, c.dtype, noff), "neck_train_layout")
+    nk = NeckForwardOut()
+    nk.head, nk.workspace = head, nws
+    nk.y0, nk.a1, nk.y2, nk.feat = (nws[noff[i]:noff[i] + rows * 256 * es].view(x.dtype).view(rows, 256) for i in range(4))
+    o.neck = nk
+    return o
+
+
+def blocks_backward_workspace(n_subtiles: int, dtype_code: int, device) -> torch.Tensor:
+    n = _lib.lib().cpx_blocks_backward_workspace_bytes(n_subtiles, dtype_code)
+    if n == 0:
+        raise ValueError("blocks_backward_workspace: invalid n_subtiles / dtype")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: torch.Tensor, grads: torch.Tensor | None = None,
+                    workspace: torch.Tensor | None = None, dx_all: torch.Tensor | None = None) -> torch.Tensor:
+    """``cpx_blocks_backward``: the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
+    ``block_grad_layout``), from ``params`` (the K blocks' unfolded parameters as the forward reads them, same layout) and ``dy0``
+    (rows, 256) float32, which ``neck_backward`` leaves in its workspace.  ``dx_all`` (K + 1, rows, 1024) float32, when given, receives
+    the gradient of every trained block's input and (last) of the last block's output."""
+    c, L = weights.c, _lib.lib()
+    K, rows, dev = len(fwd.x), fwd.x_out.shape[0], fwd.x_out.device
+    n_g, _off = block_grad_layout()
+    if params.dtype != torch.float32 or params.numel() != n_g * K or not params.is_contiguous() or params.device != dev:
+        raise ValueError("blocks_backward: params must be the flat float32 buffer of K records of block_grad_layout")
+    if dy0.dtype != torch.float32 or tuple(dy0.shape) != (rows, 256) or not dy0.is_contiguous() or dy0.device != dev:
+        raise ValueError("blocks_backward: dy0 must be contiguous float32 (rows, 256) on the forward's device")
+    if grads is None:
+        grads = torch.empty(n_g * K, dtype=torch.float32, device=dev)
+    if grads.dtype != torch.float32 or grads.numel() != n_g * K or not grads.is_contiguous() or grads.device != dev:
+        raise ValueError("blocks_backward: grads must be the flat float32 buffer of K records of block_grad_layout")
+    if dx_all is not None and (dx_all.dtype != torch.float32 or tuple(dx_all.shape) != (K + 1, rows, 1024) or not dx_all.is_contiguous()
+                               or dx_all.device != dev):
+        raise ValueError("blocks_backward: dx_all must be contiguous float32 (K + 1, rows, 1024)")
+    if workspace is None:
+        workspace = blocks_backward_workspace(rows // 1024, c.dtype, dev)
+    if workspace.dtype != torch.uint8 or fwd.workspace.dtype != torch.uint8:
+        raise ValueError("blocks_backward: workspaces are uint8 tensors")
+    check(L.cpx_blocks_backward(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
+                                ptr(grads), ptr(dx_all), ptr(workspace), workspace.numel(), _stream(dev)), "blocks_backward")
     return grads
 
 

@@ -211,6 +211,126 @@ class NeckParams:
                 NECK_KEYS[3]: v[3].view(256, 3, 3, 256).permute(0, 3, 1, 2).contiguous(), NECK_KEYS[4]: v[4], NECK_KEYS[5]: v[5]}
 
 
+BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.rel_pos_h", "attn.rel_pos_w", "attn.proj.weight",
+              "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.lin1.weight", "mlp.lin1.bias", "mlp.lin2.weight", "mlp.lin2.bias")
+_REL = (4, 5)                     # rel_pos_h, rel_pos_w in BLOCK_KEYS / ops.BLOCK_GRAD_NAMES
+
+
+def rel_interp_matrix(n: int, size: int = 63) -> torch.Tensor:
+    """A [size, n] float32 with ``engine.interp_rel_pos(t) == A @ t`` (get_rel_pos's linear resize is a linear map): the identity when
+    the checkpoint's table already has ``size`` rows."""
+    return engine.interp_rel_pos(torch.eye(n, dtype=torch.float32), size).contiguous()
+
+
+class BlockParams:
+    """The last ``K`` transformer blocks as a group (the reference trains them whenever ``--freeze`` does not name the backbone):
+    float32 masters of every tensor of blocks ``first .. depth - 1`` as views of ONE flat buffer, ``K`` records in the order of
+    ``ops.block_grad_layout`` -- norm1 gamma, beta | qkv W, b | (rel_h, rel_w slots, unused) | proj W, b | norm2 gamma, beta | lin1 W, b |
+    lin2 W, b --, their AdamW moments, the gradient buffer ``cpx_blocks_backward`` fills and ``rounded``, the same record with every
+    tensor rounded through the network dtype: the UNFOLDED parameters as the forward reads them, which that backward takes.
+
+    The rel-pos tables keep the checkpoint's shape (``rel[j][t]`` [n, 64], e.g. n = 27): the kernels read the table interpolated to 63
+    rows and divided by the scale, and their gradient of that operand goes back to the master through the transpose of the
+    interpolation, a [63, n] matrix formed once on the host and kept on the device, times the 1 / scale = 8 of the operand convention.
+    Each table takes an AdamW launch of its own, and ``refresh`` brings it to the host, interpolates it there in the network dtype with
+    the load's own call and uploads it: 2 K small device-to-host synchronisations per step, the price of an operand that is bitwise the
+    load's (torch's CPU and device interpolation need not round alike).
+
+    ``refresh`` re-rounds every operand exactly as ``NetWeights.from_state_dict`` does, ``cpx_fold_layernorm`` included where LayerNorm
+    is folded into qkv / lin1, so the next forward -- and inference from the saved checkpoint -- computes what was trained.  Weight
+    decay applies to every tensor, as in the neck's group: the reference hands ``net.parameters()`` to AdamW."""
+
+    def __init__(self, sd: dict, weights, K: int):
+        depth = weights.depth
+        if not 1 <= K <= depth:
+            raise ValueError(f"train_blocks = {K}: the checkpoint has {depth} blocks")
+        self.weights, self.K, self.first = weights, K, depth - K
+        dev = weights.device
+        self.n, self.off = ops.block_grad_layout()
+        self.keys = tuple(f"encoder.blocks.{i}.{k}" for i in range(self.first, depth) for k in BLOCK_KEYS)
+        flat, self.rel, self._At = [], [], []
+        for i in range(self.first, depth):
+            for t, (k, shape) in enumerate(zip(BLOCK_KEYS, ops.BLOCK_GRAD_SHAPES)):
+                v = sd[f"encoder.blocks.{i}.{k}"].detach().float()
+                if t in _REL:
+                    if v.dim() != 2 or v.shape[1] != 64:
+                        raise ValueError(f"encoder.blocks.{i}.{k}: expected a [n, 64] rel-pos table")
+                    flat.append(torch.zeros(64 * 64))
+                else:
+                    if tuple(v.shape) != shape:
+                        raise ValueError(f"encoder.blocks.{i}.{k} of the checkpoint does not describe a ViT-L block")
+                    flat.append(v.reshape(-1))
+            self.rel.append([sd[f"encoder.blocks.{i}.{BLOCK_KEYS[t]}"].detach().float().contiguous().to(dev) for t in _REL])
+            self._At.append([(8.0 * rel_interp_matrix(r.shape[0]).T).contiguous().to(dev) for r in self.rel[-1]])
+        self.params = torch.cat(flat).contiguous().to(dev)
+        if self.params.numel() != self.n * K:
+            raise _lib.CpxError("BlockParams: the host's parameter layout differs from the library's")
+        self.grads, self.m, self.v, self.rounded = (torch.zeros_like(self.params) for _ in range(4))
+        self.rel_grads = [[torch.zeros_like(r) for r in pair] for pair in self.rel]
+        self.rel_m = [[torch.zeros_like(r) for r in pair] for pair in self.rel]
+        self.rel_v = [[torch.zeros_like(r) for r in pair] for pair in self.rel]
+        self._round_masters()
+
+    def view(self, j: int, t: int, buf: torch.Tensor | None = None) -> torch.Tensor:
+        """Tensor ``t`` of ``ops.BLOCK_GRAD_NAMES`` of trained block ``j`` (a view of ``params``, or of ``buf``: ``grads``, ``rounded``)."""
+        shape = ops.BLOCK_GRAD_SHAPES[t]
+        o = self.n * j + self.off[t]
+        return (self.params if buf is None else buf)[o:o + int(np.prod(shape))].view(shape)
+
+    def finish_backward(self) -> None:
+        """After ``cpx_blocks_backward``: the operand tables' gradients -> the masters' shape, and their slots of ``grads`` cleared so
+        that the one AdamW step over the flat buffer leaves the unused slots of ``params`` at zero."""
+        for j in range(self.K):
+            for a, t in enumerate(_REL):
+                g = self.view(j, t, self.grads)
+                torch.matmul(self._At[j][a], g[:63], out=self.rel_grads[j][a])
+                g.zero_()
+
+    def update(self, step: int, lr: float, **adam) -> None:
+        ops.adamw_step(self.params, self.grads, self.m, self.v, step, lr, **adam)
+        for j in range(self.K):
+            for a in range(2):
+                ops.adamw_step(self.rel[j][a], self.rel_grads[j][a], self.rel_m[j][a], self.rel_v[j][a], step, lr, **adam)
+        self.refresh()
+
+    def _round_masters(self) -> None:
+        ops.round_weights(self.params, self.rounded.data_ptr(), self.weights.c.dtype, keep_f32=True)
+
+    def refresh(self) -> None:
+        """Masters -> the operands of ``self.weights`` in place, as ``NetWeights.from_state_dict`` forms them, and -> ``rounded``."""
+        w = self.weights
+        c, L = w.c, _lib.lib()
+        half = c.dtype != _lib.DT_F32
+        hd = engine.NET_DTYPES[w.precision]
+        st = torch.cuda.current_stream(w.device).cuda_stream
+        self._round_masters()
+        for j in range(self.K):
+            b = w.blocks[self.first + j]
+            V = lambda t: self.view(j, t)
+            vec = lambda t, dst: ops.round_weights(V(t), dst, c.dtype, keep_f32=True)
+            mat = lambda t, dst: ops.round_weights(V(t), dst, c.dtype, keep_f32=not half)
+            vec(0, b.ln1_w); vec(1, b.ln1_b); vec(8, b.ln2_w); vec(9, b.ln2_b)
+            for tw, tb, tg, tbeta, dw, db, dcs, N in ((2, 3, 0, 1, b.qkv_w, b.qkv_b, b.qkv_colsum, 3072), (10, 11, 8, 9, b.fc1_w, b.fc1_b, b.fc1_colsum, 4096)):
+                if c.fuse_ln:
+                    check(L.cpx_fold_layernorm(ptr(V(tw)), ptr(V(tb)), ptr(V(tg)), ptr(V(tbeta)), N, 1024, c.dtype, dw, db, dcs, st), "fold_layernorm")
+                else:
+                    mat(tw, dw); vec(tb, db)
+            mat(6, b.proj_w); vec(7, b.proj_b); mat(12, b.fc2_w); vec(13, b.fc2_b)
+            for a, dst in enumerate((b.rel_h, b.rel_w)):
+                # the load's own steps (a [n, 64] table: the host is the place): interpolate in the network dtype, x 8, a zero row
+                t = engine.interp_rel_pos(self.rel[j][a].detach().cpu().to(hd)).float() * 8.0
+                t = torch.cat([t, torch.zeros(1, 64)], 0).contiguous().to(w.device)
+                ops.round_weights(t, dst, c.dtype, keep_f32=not half)
+
+    def state(self) -> dict:
+        out = {}
+        for j in range(self.K):
+            for t, k in enumerate(BLOCK_KEYS):
+                v = self.rel[j][_REL.index(t)] if t in _REL else self.view(j, t)
+                out[f"encoder.blocks.{self.first + j}.{k}"] = v.detach().cpu().clone()
+        return out
+
+
 def _of_class_group(name: str) -> property:
     return property(lambda self: getattr(self.groups[0], name))
 
@@ -229,8 +349,12 @@ class HeadTrainer:
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
                  head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, train_flow_head: bool = False,
-                 train_neck: bool = False):
+                 train_neck: bool = False, train_blocks: int = 0):
         self.device = torch.device(device)
+        self.train_blocks = int(train_blocks)
+        if self.train_blocks < 0:
+            raise ValueError("train_blocks: a count of blocks, 0 for none")
+        train_neck = bool(train_neck) or self.train_blocks > 0           # the blocks' gradient comes through the neck
         if self.device.type != "cuda":
             raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
         self.sd, self.nclasses = self._prepare(pretrained_model, nclasses, head_seed)
@@ -255,8 +379,12 @@ class HeadTrainer:
         # backbone rows (``backbone_features``)
         self.flow = FlowHead(self.sd, self.weights) if train_flow_head else None
         self.neck = NeckParams(self.sd, self.weights) if train_neck else None
+        # ``train_blocks`` = K: the last K transformer blocks train too -- with ``train_flow_head`` and K = depth the
+        # reference's run without ``--freeze``, except for the patch embedding and the position table; ``step`` / ``evaluate`` then
+        # start from the input rows of block depth - K (``backbone_features``)
+        self.blocks = BlockParams(self.sd, self.weights, self.train_blocks) if self.train_blocks else None
         self.diam_labels = None
-        self.groups = [g for g in (self._class_group(), self.flow, self.neck) if g is not None]
+        self.groups = [g for g in (self._class_group(), self.flow, self.neck, self.blocks) if g is not None]
 
     # what ``train_unet.UNetHeadTrainer`` replaces: the checkpoint's preparation, the class group and the forward workspace
     def _prepare(self, pretrained_model, nclasses, head_seed) -> tuple[dict, int]:
@@ -306,11 +434,13 @@ class HeadTrainer:
             raise ValueError("crops must be uint8 (n, 256, 256, 3) or float32 (n, 3, 256, 256)")
         return ops.patchify_f32(x, self.dtype)
 
-    def _forward_rows(self, X, rows_of, width: int) -> torch.Tensor:
-        """``cpx_net_forward`` on n crops, ``feature_batch`` at a time; keeps ``rows_of(workspace, feature_batch, dtype)`` (n * 1024, width)."""
+    def _forward_rows(self, X, rows_of, width: int, c=None) -> torch.Tensor:
+        """``cpx_net_forward`` on n crops, ``feature_batch`` at a time; keeps ``rows_of(workspace, feature_batch, dtype)`` (n * 1024, width).
+        ``c``: the weight struct to run (default: the trainer's own)."""
         patches = self._patches(X)
         n = patches.shape[0] // TOKENS
-        FB, c, dev = self.feature_batch, self.weights.c, self.device
+        FB, dev = self.feature_batch, self.device
+        c = self.weights.c if c is None else c
         out = torch.empty((n * TOKENS, width), dtype=self.dtype, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
         for s in range(0, n, FB):
@@ -328,9 +458,48 @@ class HeadTrainer:
         return self._forward_rows(X, ops.neck_features, 256)
 
     def backbone_features(self, X) -> torch.Tensor:
-        """The last block's output (n * 1024, 1024) in the network dtype of n crops: the input of the neck, what a trainer built with
-        ``train_neck`` caches (2 MB per crop in bf16, against 512 KB of neck features)."""
-        return self._forward_rows(X, ops.backbone_rows, 1024)
+        """The last FROZEN block's output (n * 1024, 1024) in the network dtype of n crops: the input of the neck, or with
+        ``train_blocks`` = K that of block depth - K; what a trainer built with ``train_neck`` caches (2 MB per crop in bf16, against
+        512 KB of neck features).  The frozen prefix is ``cpx_net_forward`` on a copy of the weight struct whose depth is depth - K (the
+        copy points at the same operands; its tail runs on and is ignored); with K = depth the rows are the patch embedding's launch
+        itself."""
+        K, c = self.train_blocks, self.weights.c
+        if K == 0:
+            return self._forward_rows(X, ops.backbone_rows, 1024)
+        if K == c.depth:
+            patches = self._patches(X)
+            out = torch.empty((patches.shape[0], 1024), dtype=self.dtype, device=self.device)
+            check(self._L.cpx_gemm(c.dtype, ptr(patches), c.pe_w, patches.shape[0], 1024, 192, ops.EPI["pos"], c.pe_b, c.pos, ptr(out), 1024,
+                                   torch.cuda.current_stream(self.device).cuda_stream), "patch embedding")
+            return out
+        prefix = type(c).from_buffer_copy(c)              # the trainer's own struct is never changed: other users see its full depth
+        prefix.depth = c.depth - K
+        return self._forward_rows(X, ops.backbone_rows, 1024, prefix)
+
+    def _blocks_forward(self, X):
+        """The training forward of the last K blocks and the tail on the rows of ``X``: (x_out, the tail's ``ops.NeckForwardOut``)."""
+        x = self._as_rows(X, 1024, "backbone rows")
+        rows, c = x.shape[0], self.weights.c
+        key = ("blk_fwd", rows)
+        if key not in self._buf:
+            self._buf[key] = (torch.empty((rows, c.ld_head), dtype=torch.float32, device=self.device),
+                              ops.blocks_train_workspace(rows // TOKENS, c.dtype, self.train_blocks, self.device))
+        head, ws = self._buf[key]
+        self._bfwd = ops.blocks_forward_train(self.weights, x, c.depth - self.train_blocks, head=head, workspace=ws)
+        return self._bfwd.x_out, self._bfwd.neck
+
+    def _blocks_backward(self) -> None:
+        """``cpx_blocks_backward`` from the dy0 the neck's backward has just left in its workspace."""
+        fwd = self._bfwd
+        rows, c = fwd.x_out.shape[0], self.weights.c
+        key = ("blk_bwd", rows)
+        if key not in self._buf:
+            self._buf[key] = ops.blocks_backward_workspace(rows // TOKENS, c.dtype, self.device)
+        nws = self._buf[("neck_bwd", rows)][1]
+        off = ops.neck_backward_workspace_offsets(rows // TOKENS, c.dtype, c.ld_head)[3]
+        dy0 = nws[off:off + rows * 256 * 4].view(torch.float32).view(rows, 256)
+        ops.blocks_backward(self.weights, self.blocks.rounded, fwd, dy0, self.blocks.grads, self._buf[key])
+        self.blocks.finish_backward()
 
     def _as_rows(self, X, width: int, what: str) -> torch.Tensor:
         """``X`` itself when it is cached rows of that width, else its crops through the backbone."""
@@ -382,7 +551,7 @@ class HeadTrainer:
     def _loss(self, X, labels):
         self._fwd = None
         if self.neck is not None:
-            x, fwd = self._neck_forward(X)
+            x, fwd = self._blocks_forward(X) if self.blocks is not None else self._neck_forward(X)
             self._fwd = (x, fwd)
             feat = fwd.feat
         else:
@@ -439,6 +608,8 @@ class HeadTrainer:
         # every gradient from the operands of THIS forward (the neck's backward reads ``head_w``): before any refresh
         if self.neck is not None:
             self._neck_backward(*self._fwd, o, seg)
+        if self.blocks is not None:
+            self._blocks_backward()                       # (reads the dy0 of that neck backward and the operands of this forward)
         self.groups[0].backward(feat, o.dlogits)
         if seg is not None:
             self.flow.backward(feat, seg.dlogits)

@@ -578,7 +578,7 @@ int cpx_unet_head_backward(const cpx_conv_op *ops_host, int n_ops, const void *f
  *   LayerNorm 1), a1 (after it), y2 (before LayerNorm 2) and feat (the neck output), [n_subtiles * 1024][256] of the network dtype
  *   each, at the four byte offsets of cpx_neck_train_layout in `workspace` (256-byte aligned): nothing is overwritten.  head and feat
  *   are bitwise what cpx_net_forward produces for the same n_subtiles.
- *   cpx_layernorm_backward: y [rows][C] as stored (dtype, widened exactly), gamma [C], dout [rows][C] float32, C = 256.  Per row, in
+ *   cpx_layernorm_backward: y [rows][C] as stored (dtype, widened exactly), gamma [C], dout [rows][C] float32, C = 256 (or 1024, below).  Per row, in
  *   float64 from y: mean, biased var, rstd = 1 / sqrt(var + (double)eps), xhat = (y - mean) rstd, g = dout gamma,
  *   dy = rstd (g - mean(g) - xhat mean(g xhat)); dgamma = sum over rows of dout xhat, dbeta = sum over rows of dout.  Row sums:
  *   a fixed butterfly in one wave; column sums: per-workgroup partials over blocks of 64 rows, then one workgroup adds them in block
@@ -603,6 +603,63 @@ long long cpx_neck_grad_layout(long long *off /* [6] or NULL */);
 size_t cpx_neck_backward_workspace_bytes(int n_subtiles, int dtype, int ld_head, size_t *off /* [4] or NULL: dfeat, dy2, da1, dy0 */);
 int cpx_neck_backward(const cpx_net_weights *w, const void *x, int n_subtiles, const void *fwd_workspace, size_t fwd_workspace_bytes,
                       const float *dhead, float *grads, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Training the transformer blocks: the backward kernels (csrc/cpx_train_blocks.hip; additive, no ABI bump).  Every entry takes a stream
+ * and allocates nothing; no floating-point atomics: bitwise reproducible.  All gradients are float32.
+ *   cpx_layernorm_backward also takes C = 1024 (a block's norm1 / norm2: 16 channels per lane of the one wave per row); its workspace
+ *   for either width is cpx_layernorm_backward_bytes(rows, C) (cpx_layernorm_backward_workspace_bytes keeps answering for C = 256
+ *   alone).  For C = 256 every output is bitwise what it was.
+ *   cpx_attention_backward: the derivative of the function cpx_attention(CPX_DT_F32, ...) computes, for the architecture's shape (1024
+ *   tokens = 32 x 32 per crop, 16 heads of 64), in float32 on v_mfma_f32_32x32x2_f32.  qkv [rows][3072] as stored in `dtype`, widened
+ *   exactly (O [rows][1024], the stored attention output, is accepted and not read: delta_i = dO_i . O_i is formed from the recomputed
+ *   P, since an O rounded to the network dtype would put its 2^-9 into every dS; it may be NULL); rel_h / rel_w [64][64] of `dtype` in the operand convention of
+ *   cpx_block_weights: rel_pos / scale, row 63 zero; dO [rows][1024] float32.  Outputs: dqkv [rows][3072] (dq | dk | dv), drel_h and
+ *   drel_w [64][64] float32: the gradients with respect to the OPERAND tables (the caller undoes the 1 / scale), summed over all heads
+ *   and crops in a fixed order with float64 partials and rounded once; row 63 is written as zero.  P is recomputed from row maxima and
+ *   sums found in a first pass.  Workspace: 8.44 MiB per crop (67.5 MiB for 8 crops, 270 MiB for 32).  Pointers 16-byte aligned, the
+ *   workspace 256-byte aligned.
+ *   cpx_gelu_backward: dpre = dh * (Phi(pre) + pre phi(pre)), the derivative of the erf GELU of the mlp.lin1 epilogue, n float32
+ *   elements (a multiple of 4).
+ *   cpx_blocks_forward_train: the launches of cpx_net_forward for blocks first_block .. depth - 1 (K = depth - first_block of them), in
+ *   their order and with their MLP row parts (cpx_net_mlp_parts), on x [n_subtiles * 1024][1024] (network dtype), the input of block
+ *   first_block -- what cpx_net_forward leaves at cpx_net_backbone_offset when run with a host copy of the weights whose depth is
+ *   first_block -- then cpx_neck_forward_train.  Kept per trained block, in the network dtype, at the 4 K + 2 byte offsets of
+ *   cpx_blocks_train_layout (per block x_in, qkv, ao, x_mid; then x_out, the last block's output, and the neck's training workspace):
+ *   the block input, the qkv rows (for the half types with their V third copied back from the transposed V^T the qkv GEMM writes
+ *   instead), the attention output and the rows after the attention residual.  Nothing kept is overwritten.  The
+ *   backward recomputes both LayerNorm outputs, the lin1 pre-activation, the hidden activations and the softmax in float32.  head, the
+ *   neck's tensors and x_out are bitwise cpx_net_forward's for the same n_subtiles for float32, for unfused weights, and for the fused
+ *   half types below 16 crops; from 16 crops up cpx_net_forward takes a block's row statistics from the GEMM before it, and the first
+ *   trained block takes them from cpx_row_stats instead (same sums, another order).  Not with a UNet head.
+ *   cpx_blocks_backward: walks the trained blocks in reverse from dy0 [rows][256] float32 = d loss / d (x_out W0^T), which
+ *   cpx_neck_backward leaves at off[3] of its workspace (d x_out = dy0 W0 is formed here).  Per block: lin2 (dW, db, dh), GELU backward,
+ *   lin1, LayerNorm 2 backward, the residual add; proj, attention backward, qkv, LayerNorm 1 backward, the residual add.  Every
+ *   dX = dY W and dW = dY^T X is the exact-float32 GEMM behind a transposing copy.  params: K records of cpx_block_grad_layout holding
+ *   the UNFOLDED parameters as the forward reads them (each rounded through the network dtype, float32; the rel slots are not read);
+ *   grads: K records of the same layout, ln1 gamma, beta | qkv W, b | rel_h, rel_w [64][64] | proj W, b | ln2 gamma, beta | fc1 W, b |
+ *   fc2 W, b: with respect to the unfolded gamma, beta, W, b (not the folded operands of fuse_ln) and to the operand tables.  Where the
+ *   forward folds LayerNorm into qkv / lin1, the data gradient and the recomputed pre-activation use the folded operand the forward
+ *   multiplied by, and dW, dgamma, dbeta follow from dWf = dpre^T xhat by the chain rule through the fold after the last slab.  Rounding
+ *   to the network dtype is the identity (straight-through).  The crops go through all blocks in slabs of
+ *   cpx_blocks_backward_slab_crops() = 2 and the slabs' gradients are added in slab order, so the workspace does not grow with the
+ *   batch: 241 MiB for 8 and for 32 crops.  dx_all: NULL, or [K + 1][rows][1024] float32 receiving the gradient of every trained
+ *   block's input (record j) and of x_out (record K).                                                                              */
+size_t cpx_blocks_train_workspace_bytes(int n_subtiles, int dtype, int n_blocks);
+int cpx_blocks_train_layout(int n_subtiles, int dtype, int n_blocks, size_t *off /* [4 * n_blocks + 2] */);
+int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x, int n_subtiles, int first_block, float *head, void *workspace,
+                             size_t workspace_bytes, void *stream);
+long long cpx_block_grad_layout(long long *off /* [14] or NULL */);
+size_t cpx_blocks_backward_workspace_bytes(int n_subtiles, int dtype);
+int cpx_blocks_backward_slab_crops(void);
+int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
+                        size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
+                        size_t workspace_bytes, void *stream);
+size_t cpx_layernorm_backward_bytes(int rows, int C);
+size_t cpx_attention_backward_workspace_bytes(int n_subtiles);
+int cpx_attention_backward(int dtype, const void *qkv, const void *rel_h, const void *rel_w, const void *O, const float *dO,
+                           int n_subtiles, float *dqkv, float *drel_h, float *drel_w, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int cpx_gelu_backward(const float *pre, const float *dh, size_t n, float *dpre, void *stream);
 
 /* ------------------------------------------------------------------------
  * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)
