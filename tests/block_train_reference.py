@@ -8,7 +8,8 @@ tests/test_gpu_block_train.py.
 For bf16 / fp16 it is the straight-through replay neck_train_reference uses: every tensor the device stores in the network dtype
 (qkv, the attention output, the rows after either residual, the hidden activations) is rounded in the forward and the gradient passes
 through the rounding; ``fold=True`` forms qkv and lin1 as the device does with LayerNorm folded into them (cpx_fold_layernorm: the
-operand is round(W diag(gamma)), the bias b + W beta), which has the same derivative with respect to W, b, gamma and beta.
+operand is round(W diag(gamma)), the bias b + W beta), which has the same derivative with respect to W, b, gamma and beta;
+``fold=False`` is the network built with fuse_ln=False, which stores the LayerNorm output in the network dtype: rounded here as well.
 
 A block's parameters travel as a dict in the order of cpx_block_grad_layout:
     ln1_g, ln1_b [1024] | qkv_w [3072, 1024], qkv_b | rel_h, rel_w (the checkpoint's shape, e.g. [27, 64]) | proj_w [1024, 1024], proj_b |
@@ -127,7 +128,9 @@ def _xhat(x):
 def _ln_linear(x, g, b, W, bias, net_dtype, fold):
     if fold and net_dtype not in (None, torch.float32):
         return _xhat(x) @ ste(W * g[None, :], net_dtype).T + (bias + W @ b)
-    return layernorm(x, g, b) @ W.T + bias
+    # unfolded: the half-precision network stores the LayerNorm output in the network dtype before the GEMM reads it (cpx_layernorm),
+    # and the backward's recompute rounds it the same way (k_ln_fwd1024<DT, true>); ste is the identity for None / float32
+    return ste(layernorm(x, g, b), net_dtype) @ W.T + bias
 
 
 def _held(computed: torch.Tensor, stored, key: str) -> torch.Tensor:

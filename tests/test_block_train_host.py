@@ -46,6 +46,65 @@ def test_block_forward_is_the_oracles_block():
     assert _rel(o2["out"], o3["out"]) < 2e-2
 
 
+def test_unfolded_half_forward_is_the_oracles_unfused_half_forward():
+    """fold=False with a half network dtype is the network built with fuse_ln=False: LayerNorm writes its output in the network dtype and
+    the GEMM reads that.  The oracle in bf16 / fp16 (torch CPU, every op's output in the dtype) does the same, so with the LayerNorm
+    output rounded the two GEMMs multiply the same operands and differ by the float32 summation order alone: d = sqrt(1024) 2^-24 =
+    2^-19 relative before the output rounding.  That rounding then lands on the neighbouring value for a fraction d / ulp of the
+    elements, an error of one ulp each: sqrt(d ulp) in relative L2, 1.0e-4 for bf16 (relative ulp about 2^-7.5) and 3.6e-5 for fp16
+    (2^-10.5).  Without the rounding of the LayerNorm output every element of the operand is off by ulp / sqrt 12 in the mean, so the
+    product is too (d' = 1.6e-3 / 2.0e-4), and the output rounding adds sqrt(d' ulp): 3e-3 / 3.7e-4 together.  The bounds, 2^-11 for
+    bf16 and 2^-13 for fp16, lie a factor 3 to 6 from either side.  One whole block against the oracle's, where the oracle also rounds
+    the pre-activation, the softmax and both branch outputs before the residual -- a few roundings of an ulp each on top of the
+    output's own: 2^-6 (bf16) and 2^-9 (fp16)."""
+    sd = _sd()
+    P = br.params_from_state_dict(sd, 0)
+    g = torch.Generator().manual_seed(6)
+    x32 = torch.randn(1024, 1024, generator=g) * torch.logspace(-0.5, 0.5, 1024)[:, None] + 0.3 * torch.randn(1024, 1, generator=g)
+    p = "encoder.blocks.0."
+    for hd, bound, whole in ((torch.bfloat16, 2.0 ** -11, 2.0 ** -6), (torch.float16, 2.0 ** -13, 2.0 ** -9)):
+        x = x32.to(hd)
+        R = br.rounded(P, torch.float32, hd)
+        for ln, lin, names in (("norm1", "attn.qkv", ("ln1_g", "ln1_b", "qkv_w", "qkv_b")), ("norm2", "mlp.lin1", ("ln2_g", "ln2_b", "fc1_w", "fc1_b"))):
+            h = F.layer_norm(x, (1024,), sd[p + ln + ".weight"].to(hd), sd[p + ln + ".bias"].to(hd), 1e-6)
+            want = F.linear(h, sd[p + lin + ".weight"].to(hd), sd[p + lin + ".bias"].to(hd)).float()
+            got = nr.ste(br._ln_linear(x.float(), *(R[n] for n in names), hd, False), hd)
+            plain = nr.ste(nr.layernorm(x.float(), R[names[0]], R[names[1]]) @ R[names[2]].T + R[names[3]], hd)
+            e, e_plain = _rel(got, want), _rel(plain, want)
+            print(f"{hd} {lin}: unfolded replay against the oracle {e:.3e} (bound {bound:.3e}); without the rounding of LayerNorm {e_plain:.3e}")
+            assert e <= bound < e_plain
+        sdh = {k: v.to(hd) for k, v in sd.items() if v.is_floating_point()}
+        xg = x.reshape(1, 32, 32, 1024)
+        h = F.layer_norm(xg, (1024,), sdh[p + "norm1.weight"], sdh[p + "norm1.bias"], 1e-6)
+        y = xg + onet._attention(sdh, p + "attn.", h, 16)
+        h = F.layer_norm(y, (1024,), sdh[p + "norm2.weight"], sdh[p + "norm2.bias"], 1e-6)
+        y = y + F.linear(F.gelu(F.linear(h, sdh[p + "mlp.lin1.weight"], sdh[p + "mlp.lin1.bias"])), sdh[p + "mlp.lin2.weight"], sdh[p + "mlp.lin2.bias"])
+        o = br.block_forward(R, x.float(), 1, hd, fold=False)
+        e = _rel(o["out"], y.reshape(1024, 1024).float())
+        print(f"{hd} one block, unfolded replay against the oracle's block in the dtype: {e:.3e} (bound {whole:.3e})")
+        assert e <= whole and torch.equal(o["out"].to(hd).float(), o["out"])
+
+
+def test_ln_linear_without_a_network_dtype_is_unchanged():
+    """net_dtype None (and float32): nothing is rounded, folded or not -- bit for bit the expression the branch held before"""
+    P = br.params_from_state_dict(_sd(), 0)
+    g = torch.Generator().manual_seed(7)
+    for dt in (torch.float64, torch.float32):
+        x = torch.randn(256, 1024, generator=g).to(dt)
+        a = [P[n].to(dt) for n in ("ln1_g", "ln1_b", "qkv_w", "qkv_b")]
+        want = nr.layernorm(x, a[0], a[1]) @ a[2].T + a[3]
+        for net in (None, torch.float32):
+            for fold in (False, True):
+                assert torch.equal(br._ln_linear(x, *a, net, fold), want), (dt, net, fold)
+    xx = torch.randn(256, 1024, generator=g, dtype=torch.float64).requires_grad_(True)
+    a = [P[n].double() for n in ("ln2_g", "ln2_b", "fc1_w", "fc1_b")]
+    w = torch.randn(256, 4096, generator=g, dtype=torch.float64)
+    (br._ln_linear(xx, *a, torch.bfloat16, False) * w).sum().backward()
+    got, xx.grad = xx.grad.clone(), None
+    (br._ln_linear(xx, *a, None, False) * w).sum().backward()
+    assert _rel(got, xx.grad) < 1e-14, "the rounding of the LayerNorm output passes the gradient straight through"
+
+
 def test_rel_operand_is_the_loaded_table():
     sd = _sd()
     rel = sd["encoder.blocks.0.attn.rel_pos_h"]

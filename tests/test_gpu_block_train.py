@@ -298,6 +298,12 @@ def test_backward_block_by_block(cuda, prec, nS):
     """K = 2: every block's every gradient and the data gradient handed to the block below, each block on the device's own stored
     tensors (its input rows, qkv, attention output and rows after the attention residual) and own incoming gradient"""
     sd, w = _weights(prec, cuda)
+    block_by_block(cuda, prec, nS, sd, w, fold=True)
+
+
+def block_by_block(cuda, prec, nS, sd, w, fold):
+    """``fold``: how ``w`` was built (fuse_ln), hence how the float64 replay forms qkv and lin1 (tests/test_gpu_block_train_batches.py
+    runs the half types with fuse_ln=False through here)"""
     net = None if prec == "fp32" else HD[prec]
     x = _rows_in(w, _patches(nS, prec, cuda, 13 + nS), nS, DEPTH, cuda)
     fwd = _forward_train(w, x, DEPTH, cuda)
@@ -315,11 +321,11 @@ def test_backward_block_by_block(cuda, prec, nS):
     for j in (1, 0):
         P = br.params_from_state_dict(sd, j)
         xin, dout = fwd.x[j].float().cpu(), dx[j + 1].cpu()
-        free = br.block_grads(P, xin, dout, nS, torch.float64, net)["fwd"]
+        free = br.block_grads(P, xin, dout, nS, torch.float64, net, fold)["fwd"]
         held = {"qkv": fwd.qkv[j].float().cpu(), "ao": fwd.ao[j].float().cpu(), "x_mid": fwd.x_mid[j].float().cpu()}
         print(f" block {j}: stored rows against the replay's own: " + ", ".join(f"{k} {tr.rel_l2(v, free[k]):.3e}" for k, v in held.items()))
-        r64 = br.block_grads(P, xin, dout, nS, torch.float64, net, stored=held)
-        r32 = br.block_grads(P, xin, dout, nS, torch.float32, net, stored=held)
+        r64 = br.block_grads(P, xin, dout, nS, torch.float64, net, fold, stored=held)
+        r32 = br.block_grads(P, xin, dout, nS, torch.float32, net, fold, stored=held)
         G = {k: v.cpu() for k, v in _grad_views(grads, j).items()}
         for k in br.NAMES:
             got = _table_grad(sd, j, k, G[k]) if k.startswith("rel_") else G[k]
