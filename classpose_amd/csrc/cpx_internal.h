@@ -76,12 +76,22 @@ int cpx_attention_f32(const float *qkv, const float *rel_h, const float *rel_w, 
                       void *stream);
 // the neck's im2col: x [n_subtiles * 1024][256] -> out [n_subtiles * 1024][2304], k = tap * 256 + c
 int cpx_im2col3_f32(const float *x, int n_subtiles, float *out, void *stream);
-int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
-                        size_t workspace_bytes, void *stream);
 
-// the forward workspace of either driver (cpx_net.hip): vt and st have size 0 for float32, col for the half types
+// returns the first non-zero status of a chain of launches from the enclosing function (or lambda)
+#define CPX_RUN(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
+// the forward workspace in any dtype (cpx_net.hip): vt and st have size 0 for float32, col for the half types
 struct NetWs { size_t off_x, off_xn, off_qkv, off_vt, off_ao, off_h, off_neck, off_neck2, off_st, off_col, total; };
 NetWs cpx_net_ws(int nS, int dtype);
+// One transformer block in w->dtype (cpx_net.hip), for cpx_net_forward and the training forward (cpx_train_blocks.hip): [LayerNorm or
+// its folded form ->] qkv GEMM -> attention -> x_mid = x_in + proj -> x_out = x_mid + MLP, the MLP in row parts (cpx_net_mlp_parts).
+// x_in / x_mid / x_out may be one buffer.  xn: the LayerNorm output (unfolded only); vt: V^T (half types); hb: the hidden activations;
+// st: the row statistics of x_in on entry and of x_out on return (folded only), emitted by the residual GEMMs themselves when
+// big_stats.  prof: the timing handle, or null
+struct CpxBlockBufs { const void *x_in; void *x_mid, *x_out, *xn, *qkv, *vt, *ao, *hb; float *st; };
+int cpx_net_block(const cpx_net_weights *w, int layer, int nS, const CpxBlockBufs &t, bool big_stats, CpxProf *prof, void *stream);
+// do the residual GEMMs of a folded half-precision forward over nS crops emit the row statistics themselves (the 256^2 kernel)?
+bool cpx_net_big_stats(const cpx_net_weights *w, int nS);
 // the network tail in w->dtype (cpx_net.hip): y0 = x W0^T -> a1 = LayerNorm2d(y0) -> y2 = conv3x3(a1) -> feat = LayerNorm2d(y2) ->
 // head = feat Wh^T + bh [-> UNet head over feat, in unet_ws].  y0 / y2 and a1 / feat may alias; col: float32 only, the im2col staging
 int cpx_net_tail(const cpx_net_weights *w, const void *x, int nS, void *y0, void *a1, void *y2, void *feat, void *col, float *head,
@@ -133,6 +143,25 @@ __device__ __forceinline__ float load_f32(const void *p, size_t idx) {
     else if constexpr (DT == CPX_DT_F16) return (float)((const _Float16 *)p)[idx];
     else return bf16_to_f32(((const unsigned short *)p)[idx]);
 }
+template <int DT>
+__device__ __forceinline__ float half_bits_to_f32(unsigned u) {
+    if constexpr (DT == CPX_DT_F16) { const unsigned short h = (unsigned short)u; return (float)*reinterpret_cast<const _Float16 *>(&h); }
+    else return bf16_to_f32((unsigned short)u);
+}
+// four consecutive elements (idx a multiple of 4) of a tensor of element type DT, widened exactly
+template <int DT>
+__device__ __forceinline__ float4 ld4(const void *p, size_t idx) {
+    if constexpr (DT == CPX_DT_F32) return *reinterpret_cast<const float4 *>((const float *)p + idx);
+    else {
+        const uint2 a = *reinterpret_cast<const uint2 *>((const unsigned short *)p + idx);
+        return make_float4(half_bits_to_f32<DT>(a.x & 0xFFFF), half_bits_to_f32<DT>(a.x >> 16), half_bits_to_f32<DT>(a.y & 0xFFFF),
+                           half_bits_to_f32<DT>(a.y >> 16));
+    }
+}
+// the exact-float32 matrix instruction: a 32 x 32 accumulator tile, two k per issue
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+#define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+static inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }      // one thread per item, 256 per workgroup
 __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);

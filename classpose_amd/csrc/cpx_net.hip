@@ -2,8 +2,9 @@
 // LayerNorm, global attention with the decomposed relative-position bias fused
 // into the flash loop, the neck (its 3x3 conv is an implicit GEMM), and the launch sequence that
 // strings them together with the MFMA GEMM of cpx_gemm.hip.
-// Shared with the float32 driver (cpx_net_f32.hip) and the neck's training forward (cpx_train_neck.hip): the workspace layout of
-// all three dtypes (cpx_net_ws) and the network tail -- neck, head GEMM, optional UNet head -- as one launch sequence (cpx_net_tail).
+// One driver for all three dtypes (cpx_net_forward; the float32 kernels are in cpx_net_f32.hip) on one workspace layout (cpx_net_ws).
+// Shared with the training forwards: one transformer block as one launch sequence (cpx_net_block; cpx_train_blocks.hip runs it on
+// tensors it keeps) and the network tail -- neck, head GEMM, optional UNet head -- as another (cpx_net_tail; cpx_train_neck.hip).
 // The UNet head's layout and run read the op geometry the backward reads too (op_dims, cpx_internal.h).
 //
 // Attention design (T = 32x32 tokens, 16 heads x 64):
@@ -25,7 +26,6 @@
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 template <bool F16>
 __device__ __forceinline__ f32x16 mfma32(const uint4 &a, const uint4 &b, f32x16 c) {
@@ -561,106 +561,111 @@ static void mlp_part_rows(int n_subtiles, int parts, int pt, int &row0, int &row
     rows = pt + 1 < parts ? 16384 : n_subtiles * 1024 - row0;
 }
 
-// the network tail, for both forward drivers and the neck's training forward (cpx_train_neck.hip): one launch sequence per dtype.
+// the network tail, for cpx_net_forward and the neck's training forward (cpx_train_neck.hip): one launch sequence per dtype.
 // The plain GEMMs take one epilogue code for all dtypes: float32 has a single store-as-is instantiation (cpx_gemm_f32)
 int cpx_net_tail(const cpx_net_weights *w, const void *x, int nS, void *y0, void *a1, void *y2, void *feat, void *col, float *head,
                  void *unet_ws, size_t unet_ws_bytes, void *stream) {
     const int dt = w->dtype, M = nS * 1024;
-    int rc;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
     // neck: 1x1 conv -> LN2d -> 3x3 conv -> LN2d
-    RUN(cpx_gemm(dt, x, w->neck0_w, M, 256, 1024, CPX_EPI_BF16, nullptr, nullptr, y0, 256, stream));
-    RUN(cpx_layernorm(dt, y0, w->neck_ln1_w, w->neck_ln1_b, M, 256, 1e-6f, a1, stream));
+    CPX_RUN(cpx_gemm(dt, x, w->neck0_w, M, 256, 1024, CPX_EPI_BF16, nullptr, nullptr, y0, 256, stream));
+    CPX_RUN(cpx_layernorm(dt, y0, w->neck_ln1_w, w->neck_ln1_b, M, 256, 1e-6f, a1, stream));
     if (dt == CPX_DT_F32) {         // im2col [M][9 x 256], then the GEMM
-        RUN(cpx_im2col3_f32((const float *)a1, nS, (float *)col, stream));
-        RUN(cpx_gemm(dt, col, w->neck2_w, M, 256, 2304, CPX_EPI_BF16, nullptr, nullptr, y2, 256, stream));
+        CPX_RUN(cpx_im2col3_f32((const float *)a1, nS, (float *)col, stream));
+        CPX_RUN(cpx_gemm(dt, col, w->neck2_w, M, 256, 2304, CPX_EPI_BF16, nullptr, nullptr, y2, 256, stream));
     } else {                        // an implicit GEMM (K = 9 x 256, the shifted operand is read by the LDS-DMA itself: no im2col buffer)
-        RUN(cpx_conv3_half(dt, a1, w->neck2_w, M, 256, 256, CPX_EPI_BF16, nullptr, y2, 256, stream));
+        CPX_RUN(cpx_conv3_half(dt, a1, w->neck2_w, M, 256, 256, CPX_EPI_BF16, nullptr, y2, 256, stream));
     }
-    RUN(cpx_layernorm(dt, y2, w->neck_ln2_w, w->neck_ln2_b, M, 256, 1e-6f, feat, stream));
+    CPX_RUN(cpx_layernorm(dt, y2, w->neck_ln2_w, w->neck_ln2_b, M, 256, 1e-6f, feat, stream));
     // heads: out (192) | out_class (ncls*64), f32 token-major
-    RUN(cpx_gemm(dt, feat, w->head_w, M, w->ld_head, 256, CPX_EPI_F32, w->head_b, nullptr, head, w->ld_head, stream));
+    CPX_RUN(cpx_gemm(dt, feat, w->head_w, M, w->ld_head, 256, CPX_EPI_F32, w->head_b, nullptr, head, w->ld_head, stream));
     if (w->n_unet_ops > 0) {        // UNet semantic head overwrites the class columns (head_w rows there are zero)
         const size_t need = cpx_unet_ws_bytes(dt, w->unet_ops, w->n_unet_ops, nS);
         CPX_REQUIRE(unet_ws_bytes >= need);
-        RUN(cpx_unet_head_run(dt, w->unet_ops, w->n_unet_ops, feat, nS, head, w->ld_head, 192, unet_ws, need, stream));
+        CPX_RUN(cpx_unet_head_run(dt, w->unet_ops, w->n_unet_ops, feat, nS, head, w->ld_head, 192, unet_ws, need, stream));
     }
-#undef RUN
     return CPX_OK;
 }
 
+#define TIMED(kind_, layer_, call_) do { const bool t_ = cpx_prof_begin(prof, kind_, layer_, hs); CPX_RUN(call_); if (t_) cpx_prof_end(prof, hs); } while (0)
+
+// LayerNorm fusion: the RESID GEMMs emit partial row statistics of the residual stream, the next GEMM applies (x - mean) * rstd
+// algebraically in its epilogue (weights pre-folded) -- where both RESID shapes run on the 256^2 kernel; else cpx_row_stats_half
+bool cpx_net_big_stats(const cpx_net_weights *w, int nS) {
+    const int M = nS * 1024;
+    return w->fuse_ln && w->dtype != CPX_DT_F32 && cpx_gemm_half_uses_big_tile(M, 1024, 1024, CPX_EPI_RESID_BF16) &&
+           cpx_gemm_half_uses_big_tile(M, 1024, 4096, CPX_EPI_RESID_BF16);
+}
+
+// one block (cpx_internal.h): two launch sequences, LayerNorm folded (half types) and plain (every dtype; float32 keeps its qkv rows
+// whole and has an attention kernel of its own)
+int cpx_net_block(const cpx_net_weights *w, int layer, int nS, const CpxBlockBufs &t, bool big_stats, CpxProf *prof, void *stream) {
+    const cpx_block_weights &b = w->blocks[layer];
+    const int dt = w->dtype, M = nS * 1024;
+    const bool f32 = dt == CPX_DT_F32;
+    hipStream_t hs = (hipStream_t)stream;
+    auto attention = [&] {
+        return f32 ? cpx_attention_f32((const float *)t.qkv, (const float *)b.rel_h, (const float *)b.rel_w, nS, (float *)t.ao, stream)
+                   : cpx_attention_half(dt, t.qkv, b.rel_h, b.rel_w, nS, t.vt, t.ao, stream, false);
+    };
+    if (w->fuse_ln) {
+        TIMED(CPX_PROF_QKV, layer, cpx_gemm_half(dt, t.x_in, b.qkv_w, M, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, t.vt, t.qkv, 3072, t.st, b.qkv_colsum, nullptr, stream));
+        TIMED(CPX_PROF_ATTN, layer, attention());
+        TIMED(CPX_PROF_PROJ, layer, cpx_gemm_half(dt, t.ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, t.x_in, t.x_mid, 1024, nullptr, nullptr, big_stats ? t.st : nullptr, stream));
+        if (!big_stats) CPX_RUN(cpx_row_stats_half(dt, t.x_mid, M, t.st, stream));
+        // the MLP in row parts of 16 384 tokens (cpx_net_mlp_parts): a part's hidden activations (134 MB) are written by mlp.lin1 and read
+        // back by mlp.lin2 straight away, from the 256 MB Infinity Cache, and every part re-uses the SAME hidden rows -- over all 32 768 rows
+        // the 268 MB hidden tensor goes out to HBM and comes back (one-process A/B, tools/ab_mlp_msplit.py: 451.8 -> 444.0 us per layer's
+        // MLP; with a hidden buffer of its own per part 457.5).  Rows are independent: same bits.
+        const int parts = big_stats ? cpx_net_mlp_parts(nS, dt) : 1;
+        for (int pt = 0; pt < parts; ++pt) {
+            int r0, Mp;
+            mlp_part_rows(nS, parts, pt, r0, Mp);
+            const char *xp = (const char *)t.x_mid + (size_t)r0 * 1024 * 2;
+            char *op = (char *)t.x_out + (size_t)r0 * 1024 * 2;
+            float *stp = t.st + (size_t)r0 * 8;
+            TIMED(CPX_PROF_FC1, layer, cpx_gemm_half(dt, xp, b.fc1_w, Mp, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, t.hb, 4096, stp, b.fc1_colsum, nullptr, stream));
+            TIMED(CPX_PROF_FC2, layer, cpx_gemm_half(dt, t.hb, b.fc2_w, Mp, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, xp, op, 1024, nullptr, nullptr, big_stats ? stp : nullptr, stream));
+        }
+        if (!big_stats) CPX_RUN(cpx_row_stats_half(dt, t.x_out, M, t.st, stream));
+        return CPX_OK;
+    }
+    CPX_RUN(cpx_layernorm(dt, t.x_in, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, t.xn, stream));
+    TIMED(CPX_PROF_QKV, layer, cpx_gemm(dt, t.xn, b.qkv_w, M, 3072, 1024, f32 ? CPX_EPI_F32 : CPX_EPI_QKV_BF16, b.qkv_b, f32 ? nullptr : t.vt, t.qkv, 3072, stream));
+    TIMED(CPX_PROF_ATTN, layer, attention());
+    TIMED(CPX_PROF_PROJ, layer, cpx_gemm(dt, t.ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, t.x_in, t.x_mid, 1024, stream));
+    CPX_RUN(cpx_layernorm(dt, t.x_mid, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, t.xn, stream));
+    TIMED(CPX_PROF_FC1, layer, cpx_gemm(dt, t.xn, b.fc1_w, M, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, t.hb, 4096, stream));
+    TIMED(CPX_PROF_FC2, layer, cpx_gemm(dt, t.hb, b.fc2_w, M, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, t.x_mid, t.x_out, 1024, stream));
+    return CPX_OK;
+}
+
+// ClassTransformer.forward (vit_sam.py:148-197) in w->dtype: patch embedding (+bias +pos_embed), the blocks, the tail
 extern "C" int cpx_net_forward(const cpx_net_weights *w, const void *patches, int nS, float *head,
                                void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(w && patches && head && workspace && nS > 0);
     CPX_REQUIRE(w->depth > 0 && w->blocks && w->ld_head % 128 == 0 && w->ld_head >= w->n_head_cols);
-    CPX_REQUIRE(w->dtype == CPX_DT_BF16 || w->dtype == CPX_DT_F16 || w->dtype == CPX_DT_F32);
-    if (w->dtype == CPX_DT_F32) return cpx_net_forward_f32(w, patches, nS, head, workspace, workspace_bytes, stream);
-    const NetWs L = cpx_net_ws(nS, w->dtype);
+    CPX_REQUIRE(dtype_ok(w->dtype) && (w->dtype != CPX_DT_F32 || !w->fuse_ln));
+    const int dt = w->dtype, M = nS * 1024;
+    const NetWs L = cpx_net_ws(nS, dt);
     CPX_REQUIRE(workspace_bytes >= L.total);
-    const int dt = w->dtype;
     char *ws = (char *)workspace;
-    const int M = nS * 1024;
-    void *x = ws + L.off_x, *xn = ws + L.off_xn, *qkv = ws + L.off_qkv, *vt = ws + L.off_vt,
-         *ao = ws + L.off_ao, *hb = ws + L.off_h, *nk = ws + L.off_neck, *nk2 = ws + L.off_neck2;
+    void *x = ws + L.off_x, *nk = ws + L.off_neck, *nk2 = ws + L.off_neck2;
+    float *st = (float *)(ws + L.off_st);
+    const CpxBlockBufs t = {x, x, x, ws + L.off_xn, ws + L.off_qkv, ws + L.off_vt, ws + L.off_ao, ws + L.off_h, st};
     CpxProf *prof = (CpxProf *)w->prof;
     if (prof) prof->phase = (prof->phase + 1) % prof->stride;
     hipStream_t hs = (hipStream_t)stream;
-    int rc;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
-#define GEMM(A_, W_, N_, K_, EPI_, B_, AUX_, OUT_, LD_) \
-    cpx_gemm_half(dt, A_, W_, M, N_, K_, EPI_, B_, AUX_, OUT_, LD_, nullptr, nullptr, nullptr, stream)
-#define TIMED(kind_, layer_, call_) do { const bool t_ = cpx_prof_begin(prof, kind_, layer_, hs); RUN(call_); if (t_) cpx_prof_end(prof, hs); } while (0)
-    // patch embed (+bias +pos_embed)
-    float *st = (float *)(ws + L.off_st);
-    // LayerNorm fusion: the RESID GEMMs emit partial row statistics of the residual stream, the
-    // next GEMM applies (x - mean) * rstd algebraically in its epilogue (weights pre-folded)
-    const bool fuse = w->fuse_ln != 0;
-    const bool big_stats = fuse && cpx_gemm_half_uses_big_tile(M, 1024, 1024, CPX_EPI_RESID_BF16) &&
-                           cpx_gemm_half_uses_big_tile(M, 1024, 4096, CPX_EPI_RESID_BF16);
+    const bool big_stats = cpx_net_big_stats(w, nS);
     // on the 256^2 kernel (three K tiles) the patch embedding emits the first layer's row statistics itself
     const bool pe_stats = big_stats && cpx_gemm_half_uses_big_tile(M, 1024, 192, CPX_EPI_POS_BF16);
-    TIMED(CPX_PROF_PE, 0, cpx_gemm_half(dt, patches, w->pe_w, M, 1024, 192, CPX_EPI_POS_BF16, w->pe_b, w->pos, x, 1024, nullptr, nullptr,
-                                        pe_stats ? st : nullptr, stream));
-    if (fuse && !pe_stats) RUN(cpx_row_stats_half(dt, x, M, st, stream));
-    for (int i = 0; i < w->depth; ++i) {
-        const cpx_block_weights &b = w->blocks[i];
-        if (fuse) {
-            TIMED(CPX_PROF_QKV, i, cpx_gemm_half(dt, x, b.qkv_w, M, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072, st, b.qkv_colsum, nullptr, stream));
-            TIMED(CPX_PROF_ATTN, i, cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
-            TIMED(CPX_PROF_PROJ, i, cpx_gemm_half(dt, ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, x, x, 1024, nullptr, nullptr, big_stats ? st : nullptr, stream));
-            if (!big_stats) RUN(cpx_row_stats_half(dt, x, M, st, stream));
-            // the MLP in row parts of 16 384 tokens (cpx_net_mlp_parts): a part's hidden activations (134 MB) are written by mlp.lin1 and read
-            // back by mlp.lin2 straight away, from the 256 MB Infinity Cache, and every part re-uses the SAME hidden rows -- over all 32 768 rows
-            // the 268 MB hidden tensor goes out to HBM and comes back (one-process A/B, tools/ab_mlp_msplit.py: 451.8 -> 444.0 us per layer's
-            // MLP; with a hidden buffer of its own per part 457.5).  Rows are independent: same bits.
-            const int parts = big_stats ? cpx_net_mlp_parts(nS, dt) : 1;
-            for (int pt = 0; pt < parts; ++pt) {
-                int r0, Mp;
-                mlp_part_rows(nS, parts, pt, r0, Mp);
-                char *xp = (char *)x + (size_t)r0 * 1024 * 2;
-                float *stp = st + (size_t)r0 * 8;
-                TIMED(CPX_PROF_FC1, i, cpx_gemm_half(dt, xp, b.fc1_w, Mp, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096, stp, b.fc1_colsum, nullptr, stream));
-                TIMED(CPX_PROF_FC2, i, cpx_gemm_half(dt, hb, b.fc2_w, Mp, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, xp, xp, 1024, nullptr, nullptr, big_stats ? stp : nullptr, stream));
-            }
-            if (!big_stats) RUN(cpx_row_stats_half(dt, x, M, st, stream));
-            continue;
-        }
-        RUN(cpx_layernorm_half(dt, x, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, xn, stream));
-        TIMED(CPX_PROF_QKV, i, GEMM(xn, b.qkv_w, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072));
-        TIMED(CPX_PROF_ATTN, i, cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
-        TIMED(CPX_PROF_PROJ, i, GEMM(ao, b.proj_w, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, x, x, 1024));
-        RUN(cpx_layernorm_half(dt, x, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, xn, stream));
-        TIMED(CPX_PROF_FC1, i, GEMM(xn, b.fc1_w, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096));
-        TIMED(CPX_PROF_FC2, i, GEMM(hb, b.fc2_w, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, x, x, 1024));
-    }
-    const bool t_tail = cpx_prof_begin(prof, CPX_PROF_TAIL, 0, hs);
-    RUN(cpx_net_tail(w, x, nS, nk, nk2, nk, nk2, nullptr, head, ws + L.total, workspace_bytes - L.total, stream));
-    if (t_tail) cpx_prof_end(prof, hs);
-#undef TIMED
-#undef GEMM
-#undef RUN
+    TIMED(CPX_PROF_PE, 0, pe_stats ? cpx_gemm_half(dt, patches, w->pe_w, M, 1024, 192, CPX_EPI_POS_BF16, w->pe_b, w->pos, x, 1024, nullptr, nullptr, st, stream)
+                                   : cpx_gemm(dt, patches, w->pe_w, M, 1024, 192, CPX_EPI_POS_BF16, w->pe_b, w->pos, x, 1024, stream));
+    if (w->fuse_ln && !pe_stats) CPX_RUN(cpx_row_stats_half(dt, x, M, st, stream));
+    for (int i = 0; i < w->depth; ++i) CPX_RUN(cpx_net_block(w, i, nS, t, big_stats, prof, stream));
+    TIMED(CPX_PROF_TAIL, 0, cpx_net_tail(w, x, nS, nk, nk2, nk, nk2, ws + L.off_col, head, ws + L.total, workspace_bytes - L.total, stream));
     return CPX_OK;
 }
+#undef TIMED
 
 // ---------------------------------------------------------------------------
 // UNet semantic head (unet.py:121-196) as a list of convolutions on token-major tensors

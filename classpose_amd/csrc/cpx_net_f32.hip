@@ -15,11 +15,8 @@
 //                    accumulator registers (the k-slot of step j IS accumulator register j).
 // The MFMA k index is free to be permuted identically on both operands: lane half h2 takes
 // k = 8*h2 + s (GEMM) / d = 32*h2 + s (attention) so that fragments are 16-byte LDS / global reads.
-// The driver lays its workspace out with cpx_net_ws and ends in cpx_net_tail, both shared with the half-precision driver (cpx_net.hip).
+// The forward driver is cpx_net_forward (cpx_net.hip), one for every dtype: cpx_net_block and cpx_net_tail call the kernels here.
 #include "cpx_internal.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-#define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 // ---------------------------------------------------------------------------
 // GEMM
@@ -355,41 +352,3 @@ extern "C" int cpx_im2col3_f32_debug(const float *x, int n_subtiles, float *out,
     return cpx_im2col3_f32(x, n_subtiles, out, stream);
 }
 #endif
-
-// ---------------------------------------------------------------------------
-// forward driver (ClassTransformer.forward, vit_sam.py:148-197)
-// ---------------------------------------------------------------------------
-int cpx_net_forward_f32(const cpx_net_weights *w, const void *patches, int nS, float *head, void *workspace,
-                        size_t workspace_bytes, void *stream) {
-    const NetWs L = cpx_net_ws(nS, CPX_DT_F32);
-    CPX_REQUIRE(workspace_bytes >= L.total && !w->fuse_ln);
-    char *ws = (char *)workspace;
-    const int M = nS * 1024;
-    float *x = (float *)(ws + L.off_x), *xn = (float *)(ws + L.off_xn), *qkv = (float *)(ws + L.off_qkv),
-          *ao = (float *)(ws + L.off_ao), *hb = (float *)(ws + L.off_h), *nk = (float *)(ws + L.off_neck),
-          *nk2 = (float *)(ws + L.off_neck2);
-    CpxProf *prof = (CpxProf *)w->prof;
-    hipStream_t hs = (hipStream_t)stream;
-    int rc;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
-#define F(p) ((const float *)(p))
-    RUN(cpx_gemm_f32(F(patches), F(w->pe_w), M, 1024, 192, CPX_EPI_POS_BF16, w->pe_b, w->pos, x, 1024, stream));
-    for (int i = 0; i < w->depth; ++i) {
-        const cpx_block_weights &b = w->blocks[i];
-        RUN(cpx_layernorm_f32(x, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, xn, stream));
-        RUN(cpx_gemm_f32(xn, F(b.qkv_w), M, 3072, 1024, CPX_EPI_F32, b.qkv_b, nullptr, qkv, 3072, stream));
-        bool t = cpx_prof_begin(prof, CPX_PROF_ATTN, i, hs);
-        RUN(cpx_attention_f32(qkv, F(b.rel_h), F(b.rel_w), nS, ao, stream));
-        if (t) cpx_prof_end(prof, hs);
-        RUN(cpx_gemm_f32(ao, F(b.proj_w), M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, x, x, 1024, stream));
-        RUN(cpx_layernorm_f32(x, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, xn, stream));
-        t = cpx_prof_begin(prof, CPX_PROF_FC1, i, hs);
-        RUN(cpx_gemm_f32(xn, F(b.fc1_w), M, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096, stream));
-        if (t) cpx_prof_end(prof, hs);
-        RUN(cpx_gemm_f32(hb, F(b.fc2_w), M, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, x, x, 1024, stream));
-    }
-    RUN(cpx_net_tail(w, x, nS, nk, nk2, nk, nk2, ws + L.off_col, head, ws + L.total, workspace_bytes - L.total, stream));
-#undef F
-#undef RUN
-    return CPX_OK;
-}

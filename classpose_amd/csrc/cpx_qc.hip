@@ -7,9 +7,8 @@
 // into the weights by the host, nearest x2 upsampling and the UNet++ channel concatenations are
 // index arithmetic in the gather (two sources: the low-resolution tensor and a channel slice of the
 // level's concat buffer), the squeeze-excite gate is applied while staging the projection's input.
-#include "cpx_common.h"
+#include "cpx_internal.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define QC_NONE ((size_t)-1)
 #define QC_TP 128          // output pixels per workgroup
 #define QC_CK 16           // channels per K chunk

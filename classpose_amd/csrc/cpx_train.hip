@@ -13,9 +13,6 @@
 // step is a function of its inputs only, bitwise.
 #include "cpx_internal.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-#define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
 #define LOSS_TOK_PER_BLOCK 64      // tokens (8 x 8 pixel patches) per workgroup of the loss passes: 4 waves x 16 tokens
 #define LOSS_MAX_CLS 64            // general kernels: lane c of a wave carries class c's sums
 #define LOSS_REG_CLS 16            // up to here the per-class values of a lane live in registers (k_loss_*_reg)

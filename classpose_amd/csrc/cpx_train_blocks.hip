@@ -25,27 +25,9 @@
 #include "cpx_internal.h"
 #include <algorithm>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-#define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 #define AB_LD 68                        // tile row stride in floats (k_attention_f32's: b128 reads of 16 rows cover all banks)
 #define AB_GLD 97                       // per-query scratch row: [0, 64) q . table rows, [64, 96) the G_h sums
 #define AB_SLOT(v, h2) (((v) & 3) + 8 * ((v) >> 2) + 4 * (h2))      // the row of accumulator register v in lane half h2
-
-template <int DT>
-__device__ __forceinline__ float half_bits_to_f32(unsigned u) {
-    if constexpr (DT == CPX_DT_F16) { const unsigned short h = (unsigned short)u; return (float)*reinterpret_cast<const _Float16 *>(&h); }
-    else return bf16_to_f32((unsigned short)u);
-}
-// four consecutive elements (idx a multiple of 4) of a tensor of element type DT, widened exactly
-template <int DT>
-__device__ __forceinline__ float4 ld4(const void *p, size_t idx) {
-    if constexpr (DT == CPX_DT_F32) return *reinterpret_cast<const float4 *>((const float *)p + idx);
-    else {
-        const uint2 a = *reinterpret_cast<const uint2 *>((const unsigned short *)p + idx);
-        return make_float4(half_bits_to_f32<DT>(a.x & 0xFFFF), half_bits_to_f32<DT>(a.x >> 16), half_bits_to_f32<DT>(a.y & 0xFFFF),
-                           half_bits_to_f32<DT>(a.y >> 16));
-    }
-}
 
 // ---------------------------------------------------------------------------
 // dq, the row statistics and the row-group sums of dS'
@@ -533,9 +515,11 @@ static bool blocks_weights_ok(const cpx_net_weights *w, int first_block) {
            (w->dtype != CPX_DT_F32 || !w->fuse_ln) && w->n_unet_ops == 0;
 }
 
-// The launches of cpx_net_forward for blocks first_block .. depth - 1 in their order and with their MLP row parts, every GEMM writing to
-// a tensor of its own (plus, for the half types, the copy of V from vT into the kept qkv rows), then cpx_neck_forward_train.  Where cpx_net_forward takes a block's row statistics from the GEMM before it (the
-// fused half path from 16 crops up), the FIRST trained block takes them from cpx_row_stats, as cpx_net_forward itself does below 16 crops.
+// cpx_net_forward's blocks first_block .. depth - 1 (cpx_net_block: its launches in its order, with its MLP row parts), every GEMM writing
+// to a tensor of its own, then cpx_neck_forward_train.  For the half types the V columns of the kept qkv rows are copied from vT after
+// each block: nothing reads them before the backward, and the next block's qkv GEMM overwrites vT.  Where cpx_net_forward takes a
+// block's row statistics from the GEMM before it (the fused half path from 16 crops up), the FIRST trained block takes them from
+// cpx_row_stats, as cpx_net_forward itself does below 16 crops.
 extern "C" int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x, int nS, int first_block, float *head, void *workspace,
                                         size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(blocks_weights_ok(w, first_block) && x && head && workspace && blocks_args_ok(nS, w->dtype, w->depth - first_block));
@@ -543,59 +527,19 @@ extern "C" int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x,
     const BlocksFwdLayout L = blocks_fwd_layout(nS, dt, K);
     CPX_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0 && ((uintptr_t)x & 15) == 0);
     char *ws = (char *)workspace;
-    const size_t es = es_of(dt);
     hipStream_t hs = (hipStream_t)stream;
-    void *vt = ws + L.off_vt, *hb = ws + L.off_h, *xn = ws + L.off_xn;
     float *st = (float *)(ws + L.off_st);
-    int rc;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
-    CPX_HIP(hipMemcpyAsync(ws + L.o_x, x, (size_t)M * 1024 * es, hipMemcpyDeviceToDevice, hs));
-    const bool fuse = w->fuse_ln != 0 && dt != CPX_DT_F32;
-    const bool big_stats = fuse && cpx_gemm_half_uses_big_tile(M, 1024, 1024, CPX_EPI_RESID_BF16) &&
-                           cpx_gemm_half_uses_big_tile(M, 1024, 4096, CPX_EPI_RESID_BF16);
-    if (fuse) RUN(cpx_row_stats_half(dt, ws + L.o_x, M, st, stream));
+    CPX_HIP(hipMemcpyAsync(ws + L.o_x, x, (size_t)M * 1024 * es_of(dt), hipMemcpyDeviceToDevice, hs));
+    if (w->fuse_ln) CPX_RUN(cpx_row_stats_half(dt, ws + L.o_x, M, st, stream));
+    const bool big_stats = cpx_net_big_stats(w, nS);
     for (int j = 0; j < K; ++j) {
-        const cpx_block_weights &b = w->blocks[first_block + j];
         char *base = ws + L.stride * (size_t)j;
-        void *xin = base + L.o_x, *qkv = base + L.o_qkv, *ao = base + L.o_ao, *xmid = base + L.o_mid;
         void *xout = j + 1 < K ? (void *)(base + L.stride + L.o_x) : (void *)(ws + L.off_out);
-        if (dt == CPX_DT_F32) {
-            RUN(cpx_layernorm_f32((const float *)xin, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, (float *)xn, stream));
-            RUN(cpx_gemm_f32((const float *)xn, (const float *)b.qkv_w, M, 3072, 1024, CPX_EPI_F32, b.qkv_b, nullptr, (float *)qkv, 3072, stream));
-            RUN(cpx_attention_f32((const float *)qkv, (const float *)b.rel_h, (const float *)b.rel_w, nS, (float *)ao, stream));
-            RUN(cpx_gemm_f32((const float *)ao, (const float *)b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, (const float *)xin, (float *)xmid, 1024, stream));
-            RUN(cpx_layernorm_f32((const float *)xmid, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, (float *)xn, stream));
-            RUN(cpx_gemm_f32((const float *)xn, (const float *)b.fc1_w, M, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, (float *)hb, 4096, stream));
-            RUN(cpx_gemm_f32((const float *)hb, (const float *)b.fc2_w, M, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, (const float *)xmid, (float *)xout, 1024, stream));
-        } else if (fuse) {
-            RUN(cpx_gemm_half(dt, xin, b.qkv_w, M, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072, st, b.qkv_colsum, nullptr, stream));
-            RUN(cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
-            RUN(vt_to_rows_run(vt, qkv, nS, hs));
-            RUN(cpx_gemm_half(dt, ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, xin, xmid, 1024, nullptr, nullptr, big_stats ? st : nullptr, stream));
-            if (!big_stats) RUN(cpx_row_stats_half(dt, xmid, M, st, stream));
-            const int parts = big_stats ? cpx_net_mlp_parts(nS, dt) : 1;
-            for (int pt = 0; pt < parts; ++pt) {           // (cpx_net_forward's parts: 16 384 rows each, the last one with the remainder)
-                const int r0 = pt * 16384, Mp = pt + 1 < parts ? 16384 : M - r0;
-                char *xp = (char *)xmid + (size_t)r0 * 1024 * 2, *op = (char *)xout + (size_t)r0 * 1024 * 2;
-                float *stp = st + (size_t)r0 * 8;
-                RUN(cpx_gemm_half(dt, xp, b.fc1_w, Mp, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096, stp, b.fc1_colsum, nullptr, stream));
-                RUN(cpx_gemm_half(dt, hb, b.fc2_w, Mp, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, xp, op, 1024, nullptr, nullptr, big_stats ? stp : nullptr, stream));
-            }
-            if (!big_stats) RUN(cpx_row_stats_half(dt, xout, M, st, stream));
-        } else {
-            RUN(cpx_layernorm_half(dt, xin, b.ln1_w, b.ln1_b, M, 1024, 1e-6f, xn, stream));
-            RUN(cpx_gemm_half(dt, xn, b.qkv_w, M, 3072, 1024, CPX_EPI_QKV_BF16, b.qkv_b, vt, qkv, 3072, nullptr, nullptr, nullptr, stream));
-            RUN(cpx_attention_half(dt, qkv, b.rel_h, b.rel_w, nS, vt, ao, stream, false));
-            RUN(vt_to_rows_run(vt, qkv, nS, hs));
-            RUN(cpx_gemm_half(dt, ao, b.proj_w, M, 1024, 1024, CPX_EPI_RESID_BF16, b.proj_b, xin, xmid, 1024, nullptr, nullptr, nullptr, stream));
-            RUN(cpx_layernorm_half(dt, xmid, b.ln2_w, b.ln2_b, M, 1024, 1e-6f, xn, stream));
-            RUN(cpx_gemm_half(dt, xn, b.fc1_w, M, 4096, 1024, CPX_EPI_GELU_BF16, b.fc1_b, nullptr, hb, 4096, nullptr, nullptr, nullptr, stream));
-            RUN(cpx_gemm_half(dt, hb, b.fc2_w, M, 1024, 4096, CPX_EPI_RESID_BF16, b.fc2_b, xmid, xout, 1024, nullptr, nullptr, nullptr, stream));
-        }
+        const CpxBlockBufs t = {base + L.o_x, base + L.o_mid, xout, ws + L.off_xn, base + L.o_qkv, ws + L.off_vt, base + L.o_ao, ws + L.off_h, st};
+        CPX_RUN(cpx_net_block(w, first_block + j, nS, t, big_stats, nullptr, stream));
+        if (dt != CPX_DT_F32) CPX_RUN(vt_to_rows_run(t.vt, t.qkv, nS, hs));
     }
-    RUN(cpx_neck_forward_train(w, ws + L.off_out, nS, head, ws + L.off_neck, L.neck_bytes, stream));
-#undef RUN
-    return CPX_OK;
+    return cpx_neck_forward_train(w, ws + L.off_out, nS, head, ws + L.off_neck, L.neck_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -703,7 +647,6 @@ __global__ void __launch_bounds__(256) k_fill_f32(float *__restrict__ p, int n, 
     if (i < n) p[i] = v;
 }
 
-static inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 static int transpose_run(int dtype, const void *in, int R, int Cc, float *out, hipStream_t s) {
     CPX_REQUIRE(R % 32 == 0 && Cc % 32 == 0);
     CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_transpose_f32<DT>, dim3(Cc / 32, R / 32), dim3(256), 0, s, in, R, Cc, out));
@@ -781,8 +724,6 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
     const long long gn = cpx_block_grad_layout(go);
     const size_t es = es_of(dt), rows_all = (size_t)nS * 1024;
     const bool half = dt != CPX_DT_F32, fuse = half && w->fuse_ln != 0;
-    int rc;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
     CPX_HIP(hipMemsetAsync(grads, 0, (size_t)gn * K * sizeof(float), s));
     hipLaunchKernelGGL(k_fill_f32, dim3(4), dim3(256), 0, s, ones, 1024, 1.0f);
     CPX_CHECK_LAUNCH();
@@ -797,21 +738,21 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
     // a Linear y = a W^T + b with a [Ms][Kin] float32 (or `a_dt` rows of the network dtype), dy [Ms][N] float32:
     // dW += dy^T a, db += column sums of dy, da = dy W
     auto linear_bwd = [&](const float *dy, const void *a, int a_dt, const float *W, int Ms, int N, int Kin, float *dW, float *db, float *da) -> int {
-        RUN(transpose_run(CPX_DT_F32, dy, Ms, N, t1, s));
-        RUN(transpose_run(a_dt, a, Ms, Kin, t2, s));
-        RUN(cpx_gemm_f32(t1, t2, N, Kin, Ms, CPX_EPI_RESID_BF16, nullptr, dW, dW, Kin, stream));
+        CPX_RUN(transpose_run(CPX_DT_F32, dy, Ms, N, t1, s));
+        CPX_RUN(transpose_run(a_dt, a, Ms, Kin, t2, s));
+        CPX_RUN(cpx_gemm_f32(t1, t2, N, Kin, Ms, CPX_EPI_RESID_BF16, nullptr, dW, dW, Kin, stream));
         hipLaunchKernelGGL(k_colsum_add, grid1(N), dim3(256), 0, s, dy, Ms, N, db);
         CPX_CHECK_LAUNCH();
-        RUN(transpose_run(CPX_DT_F32, W, N, Kin, wt, s));
-        RUN(cpx_gemm_f32(dy, wt, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, stream));
+        CPX_RUN(transpose_run(CPX_DT_F32, W, N, Kin, wt, s));
+        CPX_RUN(cpx_gemm_f32(dy, wt, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, stream));
         return CPX_OK;
     };
     // folded: dout is the gradient of xhat (gamma = 1 here; dgamma and dbeta come from k_unfold_grads after the last slab)
     auto ln_bwd = [&](const void *x, const float *g, const float *dout, int Ms, float *dgamma, float *dbeta) -> int {
-        RUN(cpx_layernorm_backward(dt, x, fuse ? ones : g, dout, Ms, 1024, 1e-6f, dxl, tg, tb, ws + L.ln, L.ln_bytes, stream));
+        CPX_RUN(cpx_layernorm_backward(dt, x, fuse ? ones : g, dout, Ms, 1024, 1e-6f, dxl, tg, tb, ws + L.ln, L.ln_bytes, stream));
         if (!fuse) {
-            RUN(add_run(dgamma, tg, 1024, dgamma, s));
-            RUN(add_run(dbeta, tb, 1024, dbeta, s));
+            CPX_RUN(add_run(dgamma, tg, 1024, dgamma, s));
+            CPX_RUN(add_run(dbeta, tb, 1024, dbeta, s));
         }
         return add_run(dx, dxl, (size_t)Ms * 1024, dx, s);           // the residual: dx is now the gradient of the LayerNorm's input rows
     };
@@ -824,8 +765,8 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
         const int nc = std::min(BLK_SLAB, nS - c0), Ms = nc * 1024;
         const size_t r0 = (size_t)c0 * 1024;
         // the gradient of the last block's output: dy0 W0 (the rounded operand [256][1024], widened and transposed)
-        RUN(cpx_wt_run(dt, w->neck0_w, 256, 1024, 1024, wt, s));
-        RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, stream));
+        CPX_RUN(cpx_wt_run(dt, w->neck0_w, 256, 1024, 1024, wt, s));
+        CPX_RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, stream));
         if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)K * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
         for (int j = K - 1; j >= 0; --j) {
             const cpx_block_weights &b = w->blocks[first_block + j];
@@ -835,29 +776,29 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
             const void *xin = base + F.o_x + r0 * 1024 * es, *qkv = base + F.o_qkv + r0 * 3072 * es, *ao = base + F.o_ao + r0 * 1024 * es,
                        *xmid = base + F.o_mid + r0 * 1024 * es;
             // ---- the MLP: x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2 ----
-            if (fuse) RUN(ln_fwd(xmid, nullptr, nullptr, Ms, xh, false));
-            else RUN(ln_fwd(xmid, P + go[8], P + go[9], Ms, xn, half));
+            if (fuse) CPX_RUN(ln_fwd(xmid, nullptr, nullptr, Ms, xh, false));
+            else CPX_RUN(ln_fwd(xmid, P + go[8], P + go[9], Ms, xn, half));
             const float *w1op = (const float *)b.fc1_w;              // the operand the forward multiplied by (folded where it folds)
             if (half) {
-                RUN(widen(b.fc1_w, (size_t)4096 * 1024));
+                CPX_RUN(widen(b.fc1_w, (size_t)4096 * 1024));
                 w1op = wop;
             }
-            RUN(cpx_gemm_f32(fuse ? xh : xn, w1op, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, stream));     // pre
+            CPX_RUN(cpx_gemm_f32(fuse ? xh : xn, w1op, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, stream));     // pre
             CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_gelu_fwd_round<DT>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2));   // h
             CPX_CHECK_LAUNCH();
-            RUN(linear_bwd(dx, b2, CPX_DT_F32, P + go[12], Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                // fc2 -> dh
-            RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                // dpre
-            RUN(linear_bwd(b2, fuse ? xh : xn, CPX_DT_F32, fuse ? w1op : P + go[10], Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));   // fc1 -> d LN2 output (folded: d xhat)
-            RUN(ln_bwd(xmid, P + go[8], b3, Ms, Gd + go[8], Gd + go[9]));                                                 // dx = d x_mid
+            CPX_RUN(linear_bwd(dx, b2, CPX_DT_F32, P + go[12], Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                // fc2 -> dh
+            CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                // dpre
+            CPX_RUN(linear_bwd(b2, fuse ? xh : xn, CPX_DT_F32, fuse ? w1op : P + go[10], Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));   // fc1 -> d LN2 output (folded: d xhat)
+            CPX_RUN(ln_bwd(xmid, P + go[8], b3, Ms, Gd + go[8], Gd + go[9]));                                                 // dx = d x_mid
             // ---- attention: x_mid = x_in + attention(LN1(x_in) Wqkv^T + bqkv) Wp^T + bp ----
-            RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
-            RUN(cpx_attention_backward_run(dt, qkv, b.rel_h, b.rel_w, nullptr, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
+            CPX_RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
+            CPX_RUN(cpx_attention_backward_run(dt, qkv, b.rel_h, b.rel_w, nullptr, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
             if (fuse) {
-                RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
-                RUN(widen(b.qkv_w, (size_t)3072 * 1024));
-            } else RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, half));
-            RUN(linear_bwd(b1, fuse ? xh : xn, CPX_DT_F32, fuse ? wop : P + go[2], Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));       // qkv -> d LN1 output (folded: d xhat)
-            RUN(ln_bwd(xin, P + go[0], b3, Ms, Gd + go[0], Gd + go[1]));                                                  // dx = d x_in
+                CPX_RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
+                CPX_RUN(widen(b.qkv_w, (size_t)3072 * 1024));
+            } else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, half));
+            CPX_RUN(linear_bwd(b1, fuse ? xh : xn, CPX_DT_F32, fuse ? wop : P + go[2], Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));       // qkv -> d LN1 output (folded: d xhat)
+            CPX_RUN(ln_bwd(xin, P + go[0], b3, Ms, Gd + go[0], Gd + go[1]));                                                  // dx = d x_in
             if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)j * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
         }
     }
@@ -870,6 +811,5 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
             hipLaunchKernelGGL(k_unfold_grads, dim3(4), dim3(256), 0, s, Gd + go[10], Gd + go[11], P + go[10], P + go[8], P + go[9], 4096, Gd + go[8], Gd + go[9]);
             CPX_CHECK_LAUNCH();
         }
-#undef RUN
     return CPX_OK;
 }

@@ -229,32 +229,29 @@ extern "C" int cpx_neck_backward(const cpx_net_weights *w, const void *x, int nS
     const size_t ln_bytes = L.off_db - L.off_ln;
     long long go[6];
     cpx_neck_grad_layout(go);
-    int rc;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
     // 1. dfeat = dhead Wh: the rounded head operand [ld_head][256] widened and transposed once, then the float32 GEMM
-    RUN(cpx_wt_run(dt, w->head_w, ldh, NECK_C, NECK_C, wt, s));
-    RUN(cpx_gemm_f32(dhead, wt, rows, NECK_C, ldh, CPX_EPI_F32, nullptr, nullptr, dfeat, NECK_C, stream));
+    CPX_RUN(cpx_wt_run(dt, w->head_w, ldh, NECK_C, NECK_C, wt, s));
+    CPX_RUN(cpx_gemm_f32(dhead, wt, rows, NECK_C, ldh, CPX_EPI_F32, nullptr, nullptr, dfeat, NECK_C, stream));
     // 2. LayerNorm 2
-    RUN(cpx_layernorm_backward(dt, y2, w->neck_ln2_w, dfeat, rows, NECK_C, 1e-6f, dy2, grads + go[4], grads + go[5], ln_ws, ln_bytes, stream));
+    CPX_RUN(cpx_layernorm_backward(dt, y2, w->neck_ln2_w, dfeat, rows, NECK_C, 1e-6f, dy2, grads + go[4], grads + go[5], ln_ws, ln_bytes, stream));
     // 3. the 3x3 conv: dW2 [256][2304] = dy2^T im2col(a1), da1 = col2im(dy2 W2)
     UwArgs u;
     u.dy = dy2; u.xa = a1; u.lda = NECK_C; u.ca = NECK_C; u.xb = nullptr; u.ldb = 0; u.cb = 0; u.lh = 5; u.lw = 5;
     u.rows = rows; u.Npad = NECK_C; u.Kpad = NECK_K2; u.k_valid = NECK_K2;
     u.part_w = big; u.part_b = (double *)((char *)big + cpx_uwgrad_part_w_bytes(rows, NECK_C, NECK_K2));
-    RUN(cpx_uwgrad_run(dt, 0, u, NECK_C, 1, NECK_C, grads + go[3], db_sink, s));
-    RUN(cpx_wt_run(dt, w->neck2_w, NECK_C, NECK_K2, NECK_K2, wt, s));
-    RUN(cpx_gemm_f32(dy2, wt, rows, NECK_K2, NECK_C, CPX_EPI_F32, nullptr, nullptr, big, NECK_K2, stream));
+    CPX_RUN(cpx_uwgrad_run(dt, 0, u, NECK_C, 1, NECK_C, grads + go[3], db_sink, s));
+    CPX_RUN(cpx_wt_run(dt, w->neck2_w, NECK_C, NECK_K2, NECK_K2, wt, s));
+    CPX_RUN(cpx_gemm_f32(dy2, wt, rows, NECK_K2, NECK_C, CPX_EPI_F32, nullptr, nullptr, big, NECK_K2, stream));
     CPX_HIP(hipMemsetAsync(da1, 0, (size_t)rows * NECK_C * sizeof(float), s));
     DxArgs g;
     g.dcol = big; g.ldc = NECK_K2; g.kind = 0; g.ctot = NECK_C; g.coff = 0; g.C = NECK_C; g.lh = 5; g.lw = 5; g.rows_src = (size_t)rows;
     g.gx = da1; g.ld_gx = NECK_C; g.y = nullptr; g.ld_y = 0; g.mask = 0;
-    RUN(cpx_dx_gather_run(dt, g, s));
+    CPX_RUN(cpx_dx_gather_run(dt, g, s));
     // 4. LayerNorm 1
-    RUN(cpx_layernorm_backward(dt, y0, w->neck_ln1_w, da1, rows, NECK_C, 1e-6f, dy0, grads + go[1], grads + go[2], ln_ws, ln_bytes, stream));
+    CPX_RUN(cpx_layernorm_backward(dt, y0, w->neck_ln1_w, da1, rows, NECK_C, 1e-6f, dy0, grads + go[1], grads + go[2], ln_ws, ln_bytes, stream));
     // 5. the 1x1 conv: dW0 [256][1024] = dy0^T x
     u.dy = dy0; u.xa = x; u.lda = NECK_K0; u.ca = NECK_K0; u.Kpad = NECK_K0; u.k_valid = NECK_K0;
     u.part_b = (double *)((char *)big + cpx_uwgrad_part_w_bytes(rows, NECK_C, NECK_K0));
-    RUN(cpx_uwgrad_run(dt, 2, u, NECK_C, 1, NECK_C, grads + go[0], db_sink, s));
-#undef RUN
+    CPX_RUN(cpx_uwgrad_run(dt, 2, u, NECK_C, 1, NECK_C, grads + go[0], db_sink, s));
     return CPX_OK;
 }

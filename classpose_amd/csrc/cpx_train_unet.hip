@@ -21,9 +21,6 @@
 #include "cpx_internal.h"
 #include <algorithm>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-#define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
 #define UNET_MAX_OPS 64
 
 static inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
@@ -300,10 +297,8 @@ extern "C" int cpx_unet_refresh_operands(const cpx_conv_op *ops, int n_ops, cons
     param_layout(ops, n_ops, w_off, b_off, n_pad, k_pad);
     for (int i = 0; i < n_ops; ++i) {
         CPX_REQUIRE(ops[i].weight && ops[i].bias);
-        int rc = cpx_round_weights(params + w_off[i], const_cast<void *>(ops[i].weight), (long long)n_pad[i] * k_pad[i], dtype, dtype == CPX_DT_F32, stream);
-        if (rc) return rc;
-        rc = cpx_round_weights(params + b_off[i], const_cast<float *>(ops[i].bias), n_pad[i], dtype, 1, stream);
-        if (rc) return rc;
+        CPX_RUN(cpx_round_weights(params + w_off[i], const_cast<void *>(ops[i].weight), (long long)n_pad[i] * k_pad[i], dtype, dtype == CPX_DT_F32, stream));
+        CPX_RUN(cpx_round_weights(params + b_off[i], const_cast<float *>(ops[i].bias), n_pad[i], dtype, 1, stream));
     }
     return CPX_OK;
 }
@@ -353,14 +348,11 @@ static int unet_backward(const cpx_conv_op *ops, int n_ops, const void *feat, in
         u.dy = dy; u.xa = A.p; u.lda = A.ld; u.ca = o.cin_a; u.xb = B.p; u.ldb = B.ld; u.cb = o.cin_b; u.lh = lh; u.lw = lw;
         u.rows = (int)d.rows; u.Npad = d.Npad; u.Kpad = d.Kpad; u.k_valid = d.taps * d.ctot;
         u.part_w = big; u.part_b = (double *)((char *)big + uw_part_w_bytes(d));
-        int rc = cpx_uwgrad_run(DT, o.kind, u, o.kind == 2 ? 4 * o.cout : o.cout, o.kind == 2 ? 4 : 1, o.cout, grads + w_off[i], grads + b_off[i], s);
-        if (rc) return rc;
+        CPX_RUN(cpx_uwgrad_run(DT, o.kind, u, o.kind == 2 ? 4 * o.cout : o.cout, o.kind == 2 ? 4 : 1, o.cout, grads + w_off[i], grads + b_off[i], s));
         // data gradient (none for the frozen neck output)
         if (o.src_a == 0 && o.src_b <= 0) continue;
-        rc = cpx_wt_run(DT, o.weight, d.Npad, d.Kpad, d.Kp128, wt, s);
-        if (rc) return rc;
-        rc = cpx_gemm_f32(dy, wt, d.rows_pad, d.Kp128, d.Npad, CPX_EPI_F32, nullptr, nullptr, big, d.Kp128, s);
-        if (rc) return rc;
+        CPX_RUN(cpx_wt_run(DT, o.weight, d.Npad, d.Kpad, d.Kp128, wt, s));
+        CPX_RUN(cpx_gemm_f32(dy, wt, d.rows_pad, d.Kp128, d.Npad, CPX_EPI_F32, nullptr, nullptr, big, d.Kp128, s));
         for (int side = 0; side < 2; ++side) {
             const int id = side == 0 ? o.src_a : o.src_b;
             if (id <= 0) continue;
@@ -370,8 +362,7 @@ static int unet_backward(const cpx_conv_op *ops, int n_ops, const void *feat, in
             g.lh = lh; g.lw = lw; g.rows_src = (size_t)nS * o.h * o.w;
             g.gx = (float *)(ws + L.g_off[id - 1]); g.ld_gx = L.g_ld[id - 1];
             g.y = X.p; g.ld_y = X.ld; g.mask = ops[id - 1].relu && last_consumer[id] == i;
-            rc = cpx_dx_gather_run(DT, g, s);
-            if (rc) return rc;
+            CPX_RUN(cpx_dx_gather_run(DT, g, s));
         }
     }
     return CPX_OK;

@@ -189,7 +189,7 @@ def test_gemm_f32_edges_every_epilogue(cuda, M, N, K):
 
 @pytest.mark.parametrize("nS", [1, 3, 32])
 def test_gemm_f32_network_shapes(cuda, nS):
-    """the fp32 forward's GEMMs with the epilogue each takes in cpx_net_forward_f32: patch embedding (K 192, +b +pos),
+    """the fp32 forward's GEMMs with the epilogue each takes in the float32 cpx_net_forward: patch embedding (K 192, +b +pos),
     qkv, attn.proj (residual in place), mlp.lin1 (GELU), mlp.lin2 (K 4096, residual in place), neck0, neck2 (K 2304), and
     the head at ld_head 640 and 896"""
     M = nS * 1024

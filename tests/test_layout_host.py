@@ -6,7 +6,8 @@ statistics entries each lay their workspace out through a few shared pieces (cpx
 allocate by these numbers and read saved activations at these offsets, so the numbers are part of the ABI: a change to
 the shared pieces must not move them.
 
-EXPECTED was recorded from the library of the commit before the layouts were shared, by this file itself:
+EXPECTED was recorded from the library of the commit before the layouts were shared (the block-training and head weight-gradient
+entries: of the commit before the block launch sequence was shared), by this file itself:
     python tests/test_layout_host.py path/to/libclasspose_hip.so
 prints the table for any product library (the op list comes from the package on disk; the answers from the library named).
 """
@@ -56,6 +57,19 @@ def layout_table(L):
     t["pq (2, 256, 256, 6, 4096)"] = L.cpx_pq_workspace_bytes(2, 256, 256, 6, 4096)
     t["dedup (1000, 37, 41)"] = L.cpx_dedup_pairs_workspace_bytes(1000, 37, 41)
     t["label_stats (2, 256, 256, 6)"] = L.cpx_label_stats_workspace_bytes(2, 256, 256, 6)
+    # block training: the forward's record of K trained blocks, the backward's slab workspace and the pieces it is made of
+    for name, dt in DTYPES.items():
+        for nS in (1, 3, 32):
+            for K in (1, 2):
+                off = (C.c_size_t * (4 * K + 2))()
+                assert L.cpx_blocks_train_layout(nS, dt, K, off) == 0
+                t[f"blocks {name} {nS} K={K}"] = (L.cpx_blocks_train_workspace_bytes(nS, dt, K), tuple(off))
+        t[f"blocks backward {name}"] = (L.cpx_blocks_backward_workspace_bytes(1, dt), L.cpx_blocks_backward_workspace_bytes(32, dt))
+    g_off = (C.c_longlong * 14)()
+    t["blocks pieces"] = (L.cpx_blocks_backward_slab_crops(), L.cpx_block_grad_layout(g_off), tuple(g_off),
+                          L.cpx_attention_backward_workspace_bytes(2), L.cpx_layernorm_backward_bytes(2048, 1024))
+    t["head_wgrad (1000, 448) (8192, 192) (1000, 100)"] = (L.cpx_head_wgrad_workspace_bytes(1000, 448), L.cpx_head_wgrad_workspace_bytes(8192, 192),
+                                                          L.cpx_head_wgrad_workspace_bytes(1000, 100))
     # invalid arguments: 0, and (size_t)-1 where 0 is a valid offset
     t["invalid"] = (L.cpx_net_workspace_bytes(0, 0), L.cpx_net_neck_offset(0, 0), L.cpx_net_neck_offset(1, 3), L.cpx_net_neck_offset(1, -1),
                     L.cpx_net_backbone_offset(0, 2), L.cpx_net_backbone_offset(1, 3), L.cpx_net_backbone_offset(1, -1),
@@ -65,7 +79,31 @@ def layout_table(L):
     return t
 
 
-EXPECTED = {'dedup (1000, 37, 41)': 35072,
+EXPECTED = {'blocks backward bf16': (253112320, 253112320),
+ 'blocks backward fp16': (253112320, 253112320),
+ 'blocks backward fp32': (253112320, 253112320),
+ 'blocks bf16 1 K=1': (29392896, (0, 2097152, 8388608, 10485760, 12582912, 14680064)),
+ 'blocks bf16 1 K=2': (41975808, (0, 2097152, 8388608, 10485760, 12582912, 14680064, 20971520, 23068672, 25165824, 27262976)),
+ 'blocks bf16 3 K=1': (88178688, (0, 6291456, 25165824, 31457280, 37748736, 44040192)),
+ 'blocks bf16 3 K=2': (125927424, (0, 6291456, 25165824, 31457280, 37748736, 44040192, 62914560, 69206016, 75497472, 81788928)),
+ 'blocks bf16 32 K=1': (940572672, (0, 67108864, 268435456, 335544320, 402653184, 469762048)),
+ 'blocks bf16 32 K=2': (1343225856, (0, 67108864, 268435456, 335544320, 402653184, 469762048, 671088640, 738197504, 805306368, 872415232)),
+ 'blocks fp16 1 K=1': (29392896, (0, 2097152, 8388608, 10485760, 12582912, 14680064)),
+ 'blocks fp16 1 K=2': (41975808, (0, 2097152, 8388608, 10485760, 12582912, 14680064, 20971520, 23068672, 25165824, 27262976)),
+ 'blocks fp16 3 K=1': (88178688, (0, 6291456, 25165824, 31457280, 37748736, 44040192)),
+ 'blocks fp16 3 K=2': (125927424, (0, 6291456, 25165824, 31457280, 37748736, 44040192, 62914560, 69206016, 75497472, 81788928)),
+ 'blocks fp16 32 K=1': (940572672, (0, 67108864, 268435456, 335544320, 402653184, 469762048)),
+ 'blocks fp16 32 K=2': (1343225856, (0, 67108864, 268435456, 335544320, 402653184, 469762048, 671088640, 738197504, 805306368, 872415232)),
+ 'blocks fp32 1 K=1': (63963136, (0, 4194304, 16777216, 20971520, 25165824, 29360128)),
+ 'blocks fp32 1 K=2': (89128960, (0, 4194304, 16777216, 20971520, 25165824, 29360128, 41943040, 46137344, 50331648, 54525952)),
+ 'blocks fp32 3 K=1': (191889408, (0, 12582912, 50331648, 62914560, 75497472, 88080384)),
+ 'blocks fp32 3 K=2': (267386880, (0, 12582912, 50331648, 62914560, 75497472, 88080384, 125829120, 138412032, 150994944, 163577856)),
+ 'blocks fp32 32 K=1': (2046820352, (0, 134217728, 536870912, 671088640, 805306368, 939524096)),
+ 'blocks fp32 32 K=2': (2852126720, (0, 134217728, 536870912, 671088640, 805306368, 939524096, 1342177280, 1476395008, 1610612736, 1744830464)),
+ 'blocks pieces': (2, 12604416, (0, 1024, 2048, 3147776, 3150848, 3154944, 3159040, 4207616, 4208640, 4209664, 4210688, 8404992, 8409088, 12603392),
+                   17694720, 524288),
+ 'dedup (1000, 37, 41)': 35072,
+ 'head_wgrad (1000, 448) (8192, 192) (1000, 100)': (924672, 3170304, 0),
  'invalid': (0, 0, 0, 0, 18446744073709551615, 18446744073709551615, 18446744073709551615, 0, 0, 0, 0, 0, 0),
  'label_stats (2, 256, 256, 6)': 5767680,
  'net bf16 1': (24150016, 23592960, 0, 2097152, (0, 524288, 1048576, 1572864), 16057344, (0, 1048576, 2097152, 3145728)),
@@ -118,7 +156,7 @@ def table():
 
 
 def test_every_query_is_pinned(table):
-    assert sorted(table) == sorted(EXPECTED) and len(EXPECTED) == 9 + 1 + 6 + 4 + 1
+    assert sorted(table) == sorted(EXPECTED) and len(EXPECTED) == 9 + 1 + 6 + 4 + 1 + 18 + 3 + 1 + 1
 
 
 @pytest.mark.parametrize("key", sorted(EXPECTED))

@@ -1,5 +1,5 @@
 """Old library against new library, one process: the host-side drivers of the network and of its training passes, bit for bit.
-    python tools/ab_net_drivers.py OLD/libclasspose_hip.so classpose_amd/libclasspose_hip.so [n_subtiles]
+    python tools/ab_net_drivers.py OLD/libclasspose_hip.so classpose_amd/libclasspose_hip.so [n_subtiles[,n_subtiles...]]
 Both files are PRODUCT libraries; each is loaded privately (RTLD_LOCAL), as tools/ab_libs.py loads its pair.  The weights are
 built once through the package's own library (cpx_net_weights is the same struct for both).  Every buffer a driver writes
 is zero-filled first and compared WHOLE, padding and staging included:
@@ -8,6 +8,11 @@ is zero-filled first and compared WHOLE, padding and staging included:
   * cpx_neck_forward_train (workspace = the four saved tensors, and the head) and cpx_neck_backward (gradients and workspace),
     in all three dtypes, on the backbone rows the forward left behind
   * cpx_unet_head_forward + cpx_unet_head_backward (gradients and workspace) for bf16 and fp32, on the forward's neck output
+  * cpx_blocks_forward_train (workspace and head) with K = 2 and cpx_blocks_backward (gradients, dx_all and workspace) on that
+    forward's record, in the four configurations of cpx_net_forward
+  * cpx_head_wgrad (dW, db and workspace) for the three feature dtypes: 3 x 1024 rows with 192 and 448 columns, 1000 rows (a short last
+    slab that ends on an odd row) with 192
+The default is 3 sub-tiles; 16 adds the row statistics emitted by the residual GEMMs and 33 a second MLP row part with a remainder.
 One line per comparison; exit status 1 when any differs."""
 import ctypes as C
 import os
@@ -17,7 +22,7 @@ import torch
 from classpose_amd import _lib, engine, synth
 
 paths = sys.argv[1:3]
-nS = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+SIZES = [int(v) for v in sys.argv[3].split(",")] if len(sys.argv) > 3 else [3]
 NCLS, FTS = 7, [64, 128]
 HD = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 dev = torch.device("cuda:0")
@@ -41,56 +46,86 @@ def report(what, pairs):
                                     for k, (a, b) in pairs.items()), flush=True)
 
 
-print(f"A = {paths[0]}\nB = {paths[1]}\n{nS} sub-tiles, depth-2 synthetic checkpoints, {NCLS} classes")
+print(f"A = {paths[0]}\nB = {paths[1]}\ndepth-2 synthetic checkpoints, {NCLS} classes")
 sds = {"1x1": synth.make_state_dict(NCLS, None, depth=2, seed=51), "unet": synth.make_state_dict(NCLS, FTS, depth=2, seed=52)}
 g = torch.Generator(device=dev).manual_seed(7)
-for prec, fuse in (("bf16", True), ("bf16", False), ("fp16", True), ("fp32", False)):
-    patches = torch.randn(nS * 1024, 192, generator=g, device=dev).to(HD[prec])
-    for head_kind, sd in sds.items():
-        w = engine.NetWeights.from_state_dict(sd, prec, dev, fuse_ln=fuse)
-        c = w.c
-        tag = f"{prec}{'' if fuse or prec == 'fp32' else ' fuse_ln=False'} {head_kind}"
+for nS in SIZES:
+    print(f"--- {nS} sub-tiles")
+    for prec, fuse in (("bf16", True), ("bf16", False), ("fp16", True), ("fp32", False)):
+        patches = torch.randn(nS * 1024, 192, generator=g, device=dev).to(HD[prec])
+        for head_kind, sd in sds.items():
+            w = engine.NetWeights.from_state_dict(sd, prec, dev, fuse_ln=fuse)
+            c = w.c
+            tag = f"{prec}{'' if fuse or prec == 'fp32' else ' fuse_ln=False'} {head_kind}"
+            out = []
+            for L in libs:
+                nb = L.cpx_net_workspace_bytes(nS, c.dtype) + (L.cpx_unet_workspace_bytes(c.unet_ops, c.n_unet_ops, nS, c.dtype) if c.n_unet_ops else 0)
+                ws, head = zeros(nb), torch.zeros((nS * 1024, c.ld_head), dtype=torch.float32, device=dev)
+                _lib.check(L.cpx_net_forward(C.byref(c), patches.data_ptr(), nS, head.data_ptr(), ws.data_ptr(), ws.numel(), st), "net_forward")
+                out.append((ws, head))
+            report(f"cpx_net_forward {tag}", {"workspace": (out[0][0], out[1][0]), "head": (out[0][1], out[1][1])})
+            es = patches.element_size()
+            ws = out[1][0]
+            if head_kind == "1x1" and fuse == (prec != "fp32"):        # the neck's training passes, once per dtype
+                o = libs[1].cpx_net_backbone_offset(nS, c.dtype)
+                x = ws[o:o + nS * 1024 * 1024 * es].clone()
+                dhead = torch.randn(nS * 1024, c.ld_head, generator=g, device=dev)
+                n_g = libs[1].cpx_neck_grad_layout(None)
+                out = []
+                for L in libs:
+                    fws, head = zeros(L.cpx_neck_train_workspace_bytes(nS, c.dtype)), torch.zeros((nS * 1024, c.ld_head), dtype=torch.float32, device=dev)
+                    _lib.check(L.cpx_neck_forward_train(C.byref(c), x.data_ptr(), nS, head.data_ptr(), fws.data_ptr(), fws.numel(), st), "neck_forward_train")
+                    bws, grads = zeros(L.cpx_neck_backward_workspace_bytes(nS, c.dtype, c.ld_head, None)), torch.zeros(n_g, dtype=torch.float32, device=dev)
+                    _lib.check(L.cpx_neck_backward(C.byref(c), x.data_ptr(), nS, fws.data_ptr(), fws.numel(), dhead.data_ptr(), grads.data_ptr(),
+                                                   bws.data_ptr(), bws.numel(), st), "neck_backward")
+                    out.append((fws, head, grads, bws))
+                report(f"cpx_neck_forward_train {prec}", {"four tensors": (out[0][0], out[1][0]), "head": (out[0][1], out[1][1])})
+                report(f"cpx_neck_backward {prec}", {"gradients": (out[0][2], out[1][2]), "workspace": (out[0][3], out[1][3])})
+            if head_kind == "unet" and prec in ("bf16", "fp32") and fuse == (prec != "fp32"):
+                o = libs[1].cpx_net_neck_offset(nS, c.dtype)
+                feat = ws[o:o + nS * 1024 * 256 * es].clone()
+                n = c.n_unet_ops
+                dl = torch.randn(nS * 1024, c.unet_ops[n - 1].cout, generator=g, device=dev)
+                out = []
+                for L in libs:
+                    fws, head = zeros(L.cpx_unet_workspace_bytes(c.unet_ops, n, nS, c.dtype)), torch.zeros((nS * 1024, c.ld_head), dtype=torch.float32, device=dev)
+                    _lib.check(L.cpx_unet_head_forward(c.unet_ops, n, feat.data_ptr(), nS, head.data_ptr(), c.ld_head, 192, c.dtype, fws.data_ptr(), fws.numel(), st),
+                               "unet_head_forward")
+                    bws = zeros(L.cpx_unet_backward_workspace_bytes(c.unet_ops, n, nS, c.dtype))
+                    grads = torch.zeros(L.cpx_unet_param_layout(c.unet_ops, n, None, None, None, None), dtype=torch.float32, device=dev)
+                    _lib.check(L.cpx_unet_head_backward(c.unet_ops, n, feat.data_ptr(), nS, c.dtype, fws.data_ptr(), fws.numel(), dl.data_ptr(), grads.data_ptr(),
+                                                        bws.data_ptr(), bws.numel(), st), "unet_head_backward")
+                    out.append((fws, head, grads, bws))
+                report(f"cpx_unet_head_forward {prec}", {"workspace": (out[0][0], out[1][0]), "head": (out[0][1], out[1][1])})
+                report(f"cpx_unet_head_backward {prec}", {"gradients": (out[0][2], out[1][2]), "workspace": (out[0][3], out[1][3])})
+            if head_kind == "1x1":                                     # the blocks' training passes, in every configuration
+                x = torch.randn(nS * 1024, 1024, generator=g, device=dev).to(HD[prec])
+                dy0 = torch.randn(nS * 1024, 256, generator=g, device=dev)
+                n_b = libs[1].cpx_block_grad_layout(None)
+                params = torch.randn(2 * n_b, generator=g, device=dev) * 0.05
+                out = []
+                for L in libs:
+                    fws, head = zeros(L.cpx_blocks_train_workspace_bytes(nS, c.dtype, 2)), torch.zeros((nS * 1024, c.ld_head), dtype=torch.float32, device=dev)
+                    _lib.check(L.cpx_blocks_forward_train(C.byref(c), x.data_ptr(), nS, 0, head.data_ptr(), fws.data_ptr(), fws.numel(), st), "blocks_forward_train")
+                    bws, grads = zeros(L.cpx_blocks_backward_workspace_bytes(nS, c.dtype)), torch.zeros(2 * n_b, dtype=torch.float32, device=dev)
+                    dx_all = torch.zeros((3, nS * 1024, 1024), dtype=torch.float32, device=dev)
+                    _lib.check(L.cpx_blocks_backward(C.byref(c), params.data_ptr(), nS, 0, fws.data_ptr(), fws.numel(), dy0.data_ptr(), grads.data_ptr(),
+                                                     dx_all.data_ptr(), bws.data_ptr(), bws.numel(), st), "blocks_backward")
+                    out.append((fws, head, grads, dx_all, bws))
+                report(f"cpx_blocks_forward_train {tag[:-4]}", {"workspace": (out[0][0], out[1][0]), "head": (out[0][1], out[1][1])})
+                report(f"cpx_blocks_backward {tag[:-4]}", {"gradients": (out[0][2], out[1][2]), "dx_all": (out[0][3], out[1][3]), "workspace": (out[0][4], out[1][4])})
+                del out
+            del w
+print("--- cpx_head_wgrad")
+for prec in ("bf16", "fp16", "fp32"):
+    for rows, N in ((3 * 1024, 192), (3 * 1024, 448), (1000, 192)):
+        feat = torch.randn(rows, 256, generator=g, device=dev).to(HD[prec])
+        dl = torch.randn(rows, N, generator=g, device=dev)
         out = []
         for L in libs:
-            nb = L.cpx_net_workspace_bytes(nS, c.dtype) + (L.cpx_unet_workspace_bytes(c.unet_ops, c.n_unet_ops, nS, c.dtype) if c.n_unet_ops else 0)
-            ws, head = zeros(nb), torch.zeros((nS * 1024, c.ld_head), dtype=torch.float32, device=dev)
-            _lib.check(L.cpx_net_forward(C.byref(c), patches.data_ptr(), nS, head.data_ptr(), ws.data_ptr(), ws.numel(), st), "net_forward")
-            out.append((ws, head))
-        report(f"cpx_net_forward {tag}", {"workspace": (out[0][0], out[1][0]), "head": (out[0][1], out[1][1])})
-        es = patches.element_size()
-        ws = out[1][0]
-        if head_kind == "1x1" and fuse == (prec != "fp32"):        # the neck's training passes, once per dtype
-            o = libs[1].cpx_net_backbone_offset(nS, c.dtype)
-            x = ws[o:o + nS * 1024 * 1024 * es].clone()
-            dhead = torch.randn(nS * 1024, c.ld_head, generator=g, device=dev)
-            n_g = libs[1].cpx_neck_grad_layout(None)
-            out = []
-            for L in libs:
-                fws, head = zeros(L.cpx_neck_train_workspace_bytes(nS, c.dtype)), torch.zeros((nS * 1024, c.ld_head), dtype=torch.float32, device=dev)
-                _lib.check(L.cpx_neck_forward_train(C.byref(c), x.data_ptr(), nS, head.data_ptr(), fws.data_ptr(), fws.numel(), st), "neck_forward_train")
-                bws, grads = zeros(L.cpx_neck_backward_workspace_bytes(nS, c.dtype, c.ld_head, None)), torch.zeros(n_g, dtype=torch.float32, device=dev)
-                _lib.check(L.cpx_neck_backward(C.byref(c), x.data_ptr(), nS, fws.data_ptr(), fws.numel(), dhead.data_ptr(), grads.data_ptr(),
-                                               bws.data_ptr(), bws.numel(), st), "neck_backward")
-                out.append((fws, head, grads, bws))
-            report(f"cpx_neck_forward_train {prec}", {"four tensors": (out[0][0], out[1][0]), "head": (out[0][1], out[1][1])})
-            report(f"cpx_neck_backward {prec}", {"gradients": (out[0][2], out[1][2]), "workspace": (out[0][3], out[1][3])})
-        if head_kind == "unet" and prec in ("bf16", "fp32") and fuse == (prec != "fp32"):
-            o = libs[1].cpx_net_neck_offset(nS, c.dtype)
-            feat = ws[o:o + nS * 1024 * 256 * es].clone()
-            n = c.n_unet_ops
-            dl = torch.randn(nS * 1024, c.unet_ops[n - 1].cout, generator=g, device=dev)
-            out = []
-            for L in libs:
-                fws, head = zeros(L.cpx_unet_workspace_bytes(c.unet_ops, n, nS, c.dtype)), torch.zeros((nS * 1024, c.ld_head), dtype=torch.float32, device=dev)
-                _lib.check(L.cpx_unet_head_forward(c.unet_ops, n, feat.data_ptr(), nS, head.data_ptr(), c.ld_head, 192, c.dtype, fws.data_ptr(), fws.numel(), st),
-                           "unet_head_forward")
-                bws = zeros(L.cpx_unet_backward_workspace_bytes(c.unet_ops, n, nS, c.dtype))
-                grads = torch.zeros(L.cpx_unet_param_layout(c.unet_ops, n, None, None, None, None), dtype=torch.float32, device=dev)
-                _lib.check(L.cpx_unet_head_backward(c.unet_ops, n, feat.data_ptr(), nS, c.dtype, fws.data_ptr(), fws.numel(), dl.data_ptr(), grads.data_ptr(),
-                                                    bws.data_ptr(), bws.numel(), st), "unet_head_backward")
-                out.append((fws, head, grads, bws))
-            report(f"cpx_unet_head_forward {prec}", {"workspace": (out[0][0], out[1][0]), "head": (out[0][1], out[1][1])})
-            report(f"cpx_unet_head_backward {prec}", {"gradients": (out[0][2], out[1][2]), "workspace": (out[0][3], out[1][3])})
-        del w
+            ws, dW, db = zeros(L.cpx_head_wgrad_workspace_bytes(rows, N)), torch.zeros((N, 256), dtype=torch.float32, device=dev), torch.zeros(N, dtype=torch.float32, device=dev)
+            _lib.check(L.cpx_head_wgrad(dl.data_ptr(), feat.data_ptr(), _lib.DTYPE_CODE[prec], rows, N, dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), st), "head_wgrad")
+            out.append((dW, db, ws))
+        report(f"cpx_head_wgrad {prec} {rows} x {N}", {"dW": (out[0][0], out[1][0]), "db": (out[0][1], out[1][1]), "workspace": (out[0][2], out[1][2])})
 print("ALL BITWISE EQUAL" if not bad else f"{bad} COMPARISONS DIFFER")
 sys.exit(1 if bad else 0)
