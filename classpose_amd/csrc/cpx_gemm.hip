@@ -77,12 +77,22 @@ struct GemmArgs {
     int conv_c;
 };
 #define LN_SLOTS 4
+// a row's (mean, rstd) from its four (sum, sum of squares) slots, already loaded
+__device__ __forceinline__ float2 ln_mean_rstd(float4 a, float4 b, float inv_k) {
+    const float sum = (a.x + a.z) + (b.x + b.z), sq = (a.y + a.w) + (b.y + b.w);
+    const float mean = sum * inv_k;
+    return make_float2(mean, rsqrtf(fmaxf(sq * inv_k - mean * mean, 0.f) + 1e-6f));
+}
 __device__ __forceinline__ void ln_row_params(const float *st, int m, float inv_k, float &mean, float &rstd) {
     const float4 a = *reinterpret_cast<const float4 *>(st + (size_t)m * 8);
     const float4 b = *reinterpret_cast<const float4 *>(st + (size_t)m * 8 + 4);
-    const float sum = (a.x + a.z) + (b.x + b.z), sq = (a.y + a.w) + (b.y + b.w);
-    mean = sum * inv_k;
-    rstd = rsqrtf(fmaxf(sq * inv_k - mean * mean, 0.f) + 1e-6f);
+    const float2 p = ln_mean_rstd(a, b, inv_k);
+    mean = p.x; rstd = p.y;
+}
+// the form the 256^2 epilogues multiply with: (rstd, -mean * rstd)
+__device__ __forceinline__ float2 ln_row_scale(float4 a, float4 b, float inv_k) {
+    const float2 p = ln_mean_rstd(a, b, inv_k);
+    return make_float2(p.y, -p.x * p.y);
 }
 
 // v + (v permuted by a DPP control): one VALU instruction, no LDS traffic (ds_bpermute-based __shfl_xor
@@ -208,11 +218,7 @@ __global__ void __launch_bounds__(GEMM_THREADS, 2) k_gemm(GemmArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     // XCD-aware remap: blocks with equal (id % 8) share an XCD -> give them a contiguous id range
-    int bid = blockIdx.x;
-    {
-        const int nxcd = 8, q = g.n_blocks / nxcd, r = g.n_blocks % nxcd, x = bid % nxcd;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / nxcd;
-    }
+    const int bid = xcd_contiguous_id(blockIdx.x, g.n_blocks);
     const int tile_m = bid / g.tiles_n, tile_n = bid - tile_m * g.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nk = g.K / BK;
@@ -402,6 +408,136 @@ __device__ __forceinline__ void g2_mma(f32x4 (&acc)[4][2], const u32x4 (&fx)[4][
 #define G2_BAR() __builtin_amdgcn_s_barrier()
 #define G2_LGKM0() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
+// ---- what k_gemm256 and k_gemm256p share ("One body per piece of the 256^2 kernels").  A piece is a macro over the
+// kernel's own names (g, smem, tid, c16, m0, n0, lds0, wm, wn, fr, fq, F16, EPI, LN_IN) where the same text as an inlined function
+// gave one of the two kernels other code; the device code of every instantiation is what it was with the pieces written out twice
+//
+// L2 blocking: the 32 workgroups an XCD runs at a time cover an 8 (M) x 4 (N) super-tile, i.e.
+// 12 distinct operand panels instead of the 18 of a 2 x 16 strip (fabric reads -1/3, measured).
+// g.l2_block 1: column groups innermost (an XCD sweeps N for a fixed band of 8 row tiles); 2: row groups
+// innermost (an XCD keeps ONE 4-tile W panel, 2 MB, and streams the activation rows past it); 0, or tile counts
+// that are no multiples of 8 x 4: row-major.  One if / else statement: (tile_m, tile_n) of the XCD-contiguous id bid
+#define G2_TILE_OF(bid, tiles_m, tile_m, tile_n)                                            \
+    if (g.l2_block && ((tiles_m) & 7) == 0 && (g.tiles_n & 3) == 0) {                       \
+        const int grp = bid >> 5, w_ = bid & 31, cgn = g.tiles_n >> 2, rgn = (tiles_m) >> 3; \
+        const int rg = g.l2_block == 2 ? grp % rgn : grp / cgn, cg = g.l2_block == 2 ? grp / rgn : grp - rg * cgn; \
+        tile_m = rg * 8 + (w_ >> 2);                                                        \
+        tile_n = cg * 4 + (w_ & 3);                                                         \
+    } else {                                                                                \
+        tile_m = bid / g.tiles_n;                                                           \
+        tile_n = bid - tile_m * g.tiles_n;                                                  \
+    }
+// fragment read bases (LDS byte addresses), one per K-tile buffer and k-substep
+// (a macro over the kernel's lds0, wm, wn, fr, fq: as a function it changed k_gemm256's code)
+#define G2_FRAG_BASES(xb, wb)                                                               \
+    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                      \
+        const unsigned sw = (unsigned)(((ks * 4 + fq) ^ (fr & 7)) << 4);                    \
+        xb[0][ks] = lds0 + (wm * 64 + fr) * 128 + sw;                                       \
+        wb[0][ks] = lds0 + (wn * 32 + fr) * 128 + sw;                                       \
+        xb[1][ks] = xb[0][ks] + G2_BUF;                                                     \
+        wb[1][ks] = wb[0][ks] + G2_BUF;                                                     \
+    }
+// the four phases of K tile t_ in buffer B (schedule in the header above).  Uses the kernel's stage(), fx, fw, xb, wb, acc; the
+// two end conditions (K tile t_ + 1 / t_ + 2 exists) come from the call site, each kernel in its own spelling: written in place
+// or hoisted into two bools, they give the compiler different code, and each kernel keeps the one it was tuned with
+#define G2_PHASES(B, FIRST, C1, C2)                                                         \
+        /* p1 */                                                                            \
+        g2_read_w<0>(fw, wb[B][0], wb[B][1]);                                               \
+        g2_read_x<0>(fx, xb[B][0], xb[B][1]);                                               \
+        if (C1) stage(1, t_ + 1);                                                           \
+        G2_BAR(); G2_LGKM0();                                                               \
+        g2_mma<F16, FIRST>(acc[0][0], fx, fw);                                              \
+        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
+        /* p2 */                                                                            \
+        g2_read_w<1>(fw, wb[B][0], wb[B][1]);                                               \
+        if (C1) stage(2, t_ + 1);                                                           \
+        G2_BAR(); G2_LGKM0();                                                               \
+        g2_mma<F16, FIRST>(acc[0][1], fx, fw);                                              \
+        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
+        /* p3 */                                                                            \
+        g2_read_x<1>(fx, xb[B][0], xb[B][1]);                                               \
+        if (C2) stage(0, t_ + 2);                                                           \
+        G2_BAR(); G2_LGKM0();                                                               \
+        g2_mma<F16, FIRST>(acc[1][1], fx, fw);                                              \
+        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
+        /* p4 */                                                                            \
+        g2_read_w<0>(fw, wb[B][0], wb[B][1]);                                               \
+        if (C2) { stage(3, t_ + 2); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }      \
+        else if (C1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       \
+        G2_BAR(); G2_LGKM0();                                                               \
+        g2_mma<F16, FIRST>(acc[1][0], fx, fw);                                              \
+        __builtin_amdgcn_sched_barrier(0); G2_BAR();
+// epilogue value of one accumulator (4 consecutive channels of one token): the folded LayerNorm
+//   rstd * (acc - mean * colsum) + bias = fma(acc, rstd, fma(-mean * rstd, colsum, bias))      (rs = rstd, nm = -mean * rstd)
+// or + bias, then the activation.  The operands are passed in loaded: every site keeps its own load order and loop nest.
+// (The 128^2 k_gemm computes (acc - mean * colsum) * rstd + bias, which rounds differently, and is not served from here.)
+// In place on the f32x4 v, inside the kernels' templates (EPI, LN_IN); rs, nm, cs are not evaluated without LN_IN
+#define G2_EPI_VALUE(v, rs, nm, cs, b)                                                      \
+    {                                                                                       \
+        if constexpr (LN_IN) {                                                              \
+            v[0] = fmaf(v[0], rs, fmaf(nm, (cs).x, (b).x)); v[1] = fmaf(v[1], rs, fmaf(nm, (cs).y, (b).y)); \
+            v[2] = fmaf(v[2], rs, fmaf(nm, (cs).z, (b).z)); v[3] = fmaf(v[3], rs, fmaf(nm, (cs).w, (b).w)); \
+        } else {                                                                            \
+            v[0] += (b).x; v[1] += (b).y; v[2] += (b).z; v[3] += (b).w;                     \
+        }                                                                                   \
+        if constexpr (EPI == CPX_EPI_GELU_BF16) {                                           \
+            _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);            \
+        } else if constexpr (EPI == CPX_EPI_RELU_BF16) {                                    \
+            _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);          \
+        }                                                                                   \
+    }
+// V third of the qkv projection: one accumulator into the transposed image [channel nl .. nl + 3][token ml] over the whole LDS
+#define G2_STAGE_VT(v, nl, ml)                                                              \
+    {                                                                                       \
+        const unsigned p01 = pack2<F16>(v[0], v[1]), p23 = pack2<F16>(v[2], v[3]);          \
+        *reinterpret_cast<unsigned short *>(smem + (nl + 0) * G2_EPI_LD + ml * 2) = (unsigned short)p01; \
+        *reinterpret_cast<unsigned short *>(smem + (nl + 1) * G2_EPI_LD + ml * 2) = (unsigned short)(p01 >> 16); \
+        *reinterpret_cast<unsigned short *>(smem + (nl + 2) * G2_EPI_LD + ml * 2) = (unsigned short)p23; \
+        *reinterpret_cast<unsigned short *>(smem + (nl + 3) * G2_EPI_LD + ml * 2) = (unsigned short)(p23 >> 16); \
+    }
+// ... and its rows out: LDS row = channel c (head = c / 64, d = c % 64), 256 tokens contiguous -> vT[s][head][d][t0 .. t0 + 255].
+// STORE: the caller's 16-byte store, an expression over the destination p_ and the value v_
+#define G2_STORE_VT_ROWS(STORE)                                                             \
+    {                                                                                       \
+        unsigned short *vT = (unsigned short *)g.aux;                                       \
+        const size_t s_ = (size_t)(m0 >> 10), t0 = (size_t)(m0 & 1023);                     \
+        _Pragma("unroll 4") for (int it = 0; it < 16; ++it) {                               \
+            const int row = it * 16 + (tid >> 5);                                           \
+            const int c = n0 - 2048 + row;                                                  \
+            uint4 v_ = *reinterpret_cast<const uint4 *>(smem + row * G2_EPI_LD + c16 * 16); \
+            unsigned short *p_ = vT + ((s_ * 16 + (c >> 6)) * 64 + (c & 63)) * 1024 + t0 + c16 * 8; \
+            STORE;                                                                          \
+        }                                                                                   \
+    }
+// one 16-byte piece (chunk c16 of 32) of a staged output row on its way out, around the caller's own store: [G2_ADD_RESID: + the
+// residual, added in the half type and rounded again = the reference's double rounding] -> the store -> [g2_row_stats: the partial
+// LayerNorm statistics of the ROUNDED row over this tile's 256 columns: 32 lanes share a row; slot = column tile, written whole ->
+// deterministic, no atomics]
+#define G2_ADD_RESID(v, rres_it)                                                            \
+    {                                                                                       \
+        const uint4 rr = rres_it;                                                           \
+        unsigned a[4] = {v.x, v.y, v.z, v.w}, b[4] = {rr.x, rr.y, rr.z, rr.w};              \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                     \
+            float lo = from_half<F16>(a[i] & 0xFFFF) + from_half<F16>(b[i] & 0xFFFF);       \
+            float hi = from_half<F16>(a[i] >> 16) + from_half<F16>(b[i] >> 16);             \
+            a[i] = pack2<F16>(lo, hi);                                                      \
+        }                                                                                   \
+        v = make_uint4(a[0], a[1], a[2], a[3]);                                             \
+    }
+template <bool F16>
+__device__ __forceinline__ void g2_row_stats(uint4 v, int c16, float *stats_out, size_t m, int tile_n) {
+    unsigned a[4] = {v.x, v.y, v.z, v.w};
+    float sm = 0.f, sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float lo = from_half<F16>(a[i] & 0xFFFF), hi = from_half<F16>(a[i] >> 16);
+        sm += lo + hi; sq += lo * lo + hi * hi;
+    }
+    sm = half_wave_sum(sm); sq = half_wave_sum(sq);
+    if (c16 == 16)
+        *reinterpret_cast<float2 *>(stats_out + (m * LN_SLOTS + tile_n) * 2) = make_float2(sm, sq);
+}
+
 // FLAGS (compile time, so that none of these tests sits inside the unrolled epilogue loops -- the runtime
 // versions cost ~250 scalar branches per lane and tile): 1 = consume a folded LayerNorm (g.ln_stats),
 // 2 = emit row statistics (g.stats_out, residual epilogue only).  (4 was the flag of timing-only ablations, removed; the other
@@ -419,27 +555,14 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256(GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
     const int fr = lane & 15, fq = lane >> 4;
+    // (this spelling -- the id in two statements, tiles_m scoped and written out again below -- is the parent's: with tiles_m hoisted
+    // the three residual + statistics instantiations come out with other register numbers)
     int bid = blockIdx.x;
-    {
-        const int nxcd = 8, q = g.n_blocks / nxcd, r = g.n_blocks % nxcd, x = bid % nxcd;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / nxcd;
-    }
-    // L2 blocking: the 32 workgroups an XCD runs at a time cover an 8 (M) x 4 (N) super-tile, i.e.
-    // 12 distinct operand panels instead of the 18 of a 2 x 16 strip (fabric reads -1/3, measured)
+    bid = xcd_contiguous_id(bid, g.n_blocks);
     int tile_m, tile_n;
     {
         const int tiles_m = g.n_blocks / g.tiles_n;
-        if (g.l2_block && (tiles_m & 7) == 0 && (g.tiles_n & 3) == 0) {
-            const int grp = bid >> 5, w_ = bid & 31, cgn = g.tiles_n >> 2, rgn = tiles_m >> 3;
-            // mode 1: column groups innermost (an XCD sweeps N for a fixed band of 8 row tiles); mode 2: row groups
-            // innermost (an XCD keeps ONE 4-tile W panel, 2 MB, and streams the activation rows past it)
-            const int rg = g.l2_block == 2 ? grp % rgn : grp / cgn, cg = g.l2_block == 2 ? grp / rgn : grp - rg * cgn;
-            tile_m = rg * 8 + (w_ >> 2);
-            tile_n = cg * 4 + (w_ & 3);
-        } else {
-            tile_m = bid / g.tiles_n;
-            tile_n = bid - tile_m * g.tiles_n;
-        }
+        G2_TILE_OF(bid, tiles_m, tile_m, tile_n)
     }
     if (g.rev_m) tile_m = g.n_blocks / g.tiles_n - 1 - tile_m;
     const int m0 = tile_m * 256, n0 = tile_n * 256;
@@ -460,17 +583,9 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256(GemmArgs g) {
                                          (__attribute__((address_space(3))) void *)(d + 8192), 16, 0, 0);
     };
 
-    // fragment read bases (LDS byte addresses), one per k-substep and buffer
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
     unsigned xb[2][2], wb[2][2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const unsigned sw = (unsigned)(((ks * 4 + fq) ^ (fr & 7)) << 4);
-        xb[0][ks] = lds0 + (wm * 64 + fr) * 128 + sw;
-        wb[0][ks] = lds0 + (wn * 32 + fr) * 128 + sw;
-        xb[1][ks] = xb[0][ks] + G2_BUF;
-        wb[1][ks] = wb[0][ks] + G2_BUF;
-    }
+    G2_FRAG_BASES(xb, wb)
 
     f32x4 acc[2][2][4][2];
 #pragma unroll
@@ -496,11 +611,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256(GemmArgs g) {
     stage(0, 0); stage(2, 0); stage(3, 0); stage(1, 0);
     if (nk > 1) { stage(0, 1); stage(3, 1); }
     if (ln_in) {
-        const float inv_k = 1.0f / K;
-        const float sum = (st_a.x + st_a.z) + (st_b.x + st_b.z), sq = (st_a.y + st_a.w) + (st_b.y + st_b.w);
-        const float mean = sum * inv_k;
-        const float rstd = rsqrtf(fmaxf(sq * inv_k - mean * mean, 0.f) + 1e-6f);
-        *reinterpret_cast<float2 *>(smem + G2_LN_OFF + tid * 8) = make_float2(rstd, -mean * rstd);
+        *reinterpret_cast<float2 *>(smem + G2_LN_OFF + tid * 8) = ln_row_scale(st_a, st_b, 1.0f / K);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     if (nk > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -508,36 +619,8 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256(GemmArgs g) {
     G2_BAR();
     if (wm == 1) G2_BAR();                       // stagger the second wave row by one barrier
 
-#define G2_TILE(T, B)                                                                       \
-    {                                                                                       \
-        const int t_ = (T);                                                                 \
-        /* p1 */                                                                            \
-        g2_read_w<0>(fw, wb[B][0], wb[B][1]);                                               \
-        g2_read_x<0>(fx, xb[B][0], xb[B][1]);                                               \
-        if (t_ + 1 < nk) stage(1, t_ + 1);                                                  \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16>(acc[0][0], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        /* p2 */                                                                            \
-        g2_read_w<1>(fw, wb[B][0], wb[B][1]);                                               \
-        if (t_ + 1 < nk) stage(2, t_ + 1);                                                  \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16>(acc[0][1], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        /* p3 */                                                                            \
-        g2_read_x<1>(fx, xb[B][0], xb[B][1]);                                               \
-        if (t_ + 2 < nk) stage(0, t_ + 2);                                                  \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16>(acc[1][1], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        /* p4 */                                                                            \
-        g2_read_w<0>(fw, wb[B][0], wb[B][1]);                                               \
-        if (t_ + 2 < nk) { stage(3, t_ + 2); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); } \
-        else if (t_ + 1 < nk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16>(acc[1][0], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-    }
+// (the end conditions written in place: this kernel's spelling)
+#define G2_TILE(T, B) { const int t_ = (T); G2_PHASES(B, false, t_ + 1 < nk, t_ + 2 < nk) }
 
     for (int t = 0; t + 1 < nk; t += 2) {
         G2_TILE(t, 0)
@@ -593,32 +676,13 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256(GemmArgs g) {
                     const int ml = hm * 128 + wm * 64 + mb * 16 + fr;
                     const int nl = hn * 128 + wn * 32 + nb * 16 + fq * 4;
                     f32x4 v = acc[hm][hn][mb][nb];
-                    const float4 b = colb[hn][nb];
-                    if constexpr (LN_IN) {
-                        // rstd * (acc - mean * colsum) + bias = fma(acc, rstd, fma(-mean * rstd, colsum, bias))
-                        const float4 cs = colc[hn][nb];
-                        const float nm = ln_mean[hm][mb], rs = ln_rstd[hm][mb];      // ln_mean holds -mean * rstd
-                        v[0] = fmaf(v[0], rs, fmaf(nm, cs.x, b.x)); v[1] = fmaf(v[1], rs, fmaf(nm, cs.y, b.y));
-                        v[2] = fmaf(v[2], rs, fmaf(nm, cs.z, b.z)); v[3] = fmaf(v[3], rs, fmaf(nm, cs.w, b.w));
-                    } else {
-                        v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-                    }
-                    if constexpr (EPI == CPX_EPI_GELU_BF16) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-                    } else if constexpr (EPI == CPX_EPI_RELU_BF16) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                    } else if constexpr (EPI == CPX_EPI_POS_BF16) {      // + pos_embed[token within its sub-tile][channel], float32
+                    G2_EPI_VALUE(v, ln_rstd[hm][mb], ln_mean[hm][mb], colc[hn][nb], colb[hn][nb])      // ln_mean holds -mean * rstd
+                    if constexpr (EPI == CPX_EPI_POS_BF16) {      // + pos_embed[token within its sub-tile][channel], float32
                         const float4 pe = *reinterpret_cast<const float4 *>((const float *)g.aux + (size_t)((m0 + ml) & 1023) * g.N + n0 + nl);
                         v[0] += pe.x; v[1] += pe.y; v[2] += pe.z; v[3] += pe.w;
                     }
                     if constexpr (VT) {          // transposed image [channel][token] for the V^T layout
-                        const unsigned p01 = pack2<F16>(v[0], v[1]), p23 = pack2<F16>(v[2], v[3]);
-                        *reinterpret_cast<unsigned short *>(smem + (nl + 0) * G2_EPI_LD + ml * 2) = (unsigned short)p01;
-                        *reinterpret_cast<unsigned short *>(smem + (nl + 1) * G2_EPI_LD + ml * 2) = (unsigned short)(p01 >> 16);
-                        *reinterpret_cast<unsigned short *>(smem + (nl + 2) * G2_EPI_LD + ml * 2) = (unsigned short)p23;
-                        *reinterpret_cast<unsigned short *>(smem + (nl + 3) * G2_EPI_LD + ml * 2) = (unsigned short)(p23 >> 16);
+                        G2_STAGE_VT(v, nl, ml)
                     } else {
                         uint2 o;
                         o.x = pack2<F16>(v[0], v[1]);
@@ -631,48 +695,16 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256(GemmArgs g) {
     else convert_and_stage(std::false_type{});
     __syncthreads();
     if (vt_tile) {
-        // LDS row = channel c (head = c/64, d = c%64), 256 tokens contiguous -> vT[s][head][d][t0..t0+255]
-        unsigned short *vT = (unsigned short *)g.aux;
-        const size_t s_ = (size_t)(m0 >> 10), t0 = (size_t)(m0 & 1023);
-#pragma unroll 4
-        for (int it = 0; it < 16; ++it) {
-            const int row = it * 16 + (tid >> 5);
-            const int c = n0 - 2048 + row;
-            uint4 v = *reinterpret_cast<const uint4 *>(smem + row * G2_EPI_LD + c16 * 16);
-            *reinterpret_cast<uint4 *>(vT + ((s_ * 16 + (c >> 6)) * 64 + (c & 63)) * 1024 + t0 + c16 * 8) = v;
-        }
+        G2_STORE_VT_ROWS(*reinterpret_cast<uint4 *>(p_) = v_)
     } else {
 #pragma unroll
         for (int it = 0; it < 16; ++it) {
             const int ml = it * 16 + (tid >> 5);
             uint4 v = *reinterpret_cast<const uint4 *>(smem + ml * G2_EPI_LD + c16 * 16);
             const size_t go = (size_t)(m0 + ml) * g.ld_out + n0 + c16 * 8;
-            if constexpr (EPI == CPX_EPI_RESID_BF16) {
-                const uint4 rr = rres[it];
-                unsigned a[4] = {v.x, v.y, v.z, v.w}, b[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float lo = from_half<F16>(a[i] & 0xFFFF) + from_half<F16>(b[i] & 0xFFFF);
-                    float hi = from_half<F16>(a[i] >> 16) + from_half<F16>(b[i] >> 16);
-                    a[i] = pack2<F16>(lo, hi);
-                }
-                v = make_uint4(a[0], a[1], a[2], a[3]);
-            }
+            if constexpr (EPI == CPX_EPI_RESID_BF16) G2_ADD_RESID(v, rres[it])
             *reinterpret_cast<uint4 *>((unsigned short *)g.out + go) = v;
-            if constexpr (STATS) {
-                // partial LayerNorm statistics of the (rounded) output row over this block's 256 columns:
-                // 32 lanes share a row; slot = column tile, written whole -> deterministic, no atomics
-                unsigned a[4] = {v.x, v.y, v.z, v.w};
-                float sm = 0.f, sq = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float lo = from_half<F16>(a[i] & 0xFFFF), hi = from_half<F16>(a[i] >> 16);
-                    sm += lo + hi; sq += lo * lo + hi * hi;
-                }
-                sm = half_wave_sum(sm); sq = half_wave_sum(sq);
-                if (c16 == 16)
-                    *reinterpret_cast<float2 *>(g.stats_out + ((size_t)(m0 + ml) * LN_SLOTS + tile_n) * 2) = make_float2(sm, sq);
-            }
+            if constexpr (STATS) g2_row_stats<F16>(v, c16, g.stats_out, (size_t)(m0 + ml), tile_n);
         }
     }
 }
@@ -707,8 +739,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
     const int wm = wave >> 2, wn = wave & 3;
     const int K = g.K, nk = K / 64, nblk = g.n_blocks, tiles_m = g.n_blocks / g.tiles_n;
     auto coords = [&](int v, int &m0_, int &n0_, int &tn_) {
-        const int nxcd = 8, q = nblk / nxcd, r = nblk % nxcd, x = v % nxcd;
-        int bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + v / nxcd;
+        const int bid = xcd_contiguous_id(v, nblk);
         int tile_m, tile_n;
         if (EPI == CPX_EPI_QKV_BF16 && g.l2_block == 3) {
             // balanced list for the qkv projection (launcher: 256 workgroups, tiles_m % 64 == 0, 12 column tiles): the
@@ -728,17 +759,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
             }
             tile_m = x * rx + rg * 8 + (slot >> 2);
             tile_n = cg * 4 + (slot & 3);
-        } else if (g.l2_block && (tiles_m & 7) == 0 && (g.tiles_n & 3) == 0) {
-            const int grp = bid >> 5, w_ = bid & 31, cgn = g.tiles_n >> 2, rgn = tiles_m >> 3;
-            // mode 1: column groups innermost (an XCD sweeps N for a fixed band of 8 row tiles); mode 2: row groups
-            // innermost (an XCD keeps ONE 4-tile W panel, 2 MB, and streams the activation rows past it)
-            const int rg = g.l2_block == 2 ? grp % rgn : grp / cgn, cg = g.l2_block == 2 ? grp / rgn : grp - rg * cgn;
-            tile_m = rg * 8 + (w_ >> 2);
-            tile_n = cg * 4 + (w_ & 3);
-        } else {
-            tile_m = bid / g.tiles_n;
-            tile_n = bid - tile_m * g.tiles_n;
-        }
+        } else G2_TILE_OF(bid, tiles_m, tile_m, tile_n)
         if (g.rev_m) tile_m = tiles_m - 1 - tile_m;
         m0_ = tile_m * 256; n0_ = tile_n * 256; tn_ = tile_n;
     };
@@ -779,14 +800,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
         const int lane = tid & 63, fr = lane & 15, fq = lane >> 4, c16 = tid & 31;
         const int srow = tid >> 3, kc = (tid & 7) ^ (srow & 7);
         unsigned xb[2][2], wb[2][2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const unsigned sw = (unsigned)(((ks * 4 + fq) ^ (fr & 7)) << 4);
-            xb[0][ks] = lds0 + (wm * 64 + fr) * 128 + sw;
-            wb[0][ks] = lds0 + (wn * 32 + fr) * 128 + sw;
-            xb[1][ks] = xb[0][ks] + G2_BUF;
-            wb[1][ks] = wb[0][ks] + G2_BUF;
-        }
+        G2_FRAG_BASES(xb, wb)
         const unsigned voff = ((unsigned)srow * (unsigned)K + (unsigned)kc * 8u) * 2u;     // this lane inside a 64-row piece (bytes)
         const unsigned sX = (unsigned)m0 * (unsigned)K * 2u, sW = (unsigned)n0 * (unsigned)K * 2u;   // tile origins (scalar)
         auto stage = [&](int which, int t) { stage_at(voff, sX, sW, which, t); };
@@ -805,13 +819,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
         }
         auto park_tile_vectors = [&]() {              // first use of the loads above (hipcc waits vmcnt(0) here while a DMA is in flight)
             if (tid < 256) {
-                if (LN_IN) {
-                    const float inv_k = 1.0f / K;
-                    const float sum = (st_a.x + st_a.z) + (st_b.x + st_b.z), sq = (st_a.y + st_a.w) + (st_b.y + st_b.w);
-                    const float mean = sum * inv_k;
-                    const float rstd = rsqrtf(fmaxf(sq * inv_k - mean * mean, 0.f) + 1e-6f);
-                    *reinterpret_cast<float2 *>(smem + G2P_TAIL + tid * 8) = make_float2(rstd, -mean * rstd);
-                }
+                if (LN_IN) *reinterpret_cast<float2 *>(smem + G2P_TAIL + tid * 8) = ln_row_scale(st_a, st_b, 1.0f / K);
             } else {
                 *reinterpret_cast<float *>(smem + G2P_TAIL + 2048 + (tid - 256) * 4) = bias_v;
                 *reinterpret_cast<float *>(smem + G2P_TAIL + 3072 + (tid - 256) * 4) = csum_v;
@@ -840,32 +848,12 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
 
 // KIND -1: run-time end conditions (production); 2: steady state (t + 2 < nk), 3 / 4: the last two K tiles of nk >= 4 (no scalar branch
 // inside those bodies; available for experiments)
-#define G2_TILE_PLAIN(T, B, FIRST, KIND)                                                                 \
+// (the end conditions hoisted into two bools: this kernel's spelling)
+#define G2_TILE_PLAIN(T, B, FIRST, KIND)                                                    \
     {                                                                                       \
         const int t_ = (T);                                                                 \
         const bool c1_ = (KIND) == -1 ? t_ + 1 < nk : (KIND) != 4, c2_ = (KIND) == -1 ? t_ + 2 < nk : (KIND) == 2; \
-        g2_read_w<0>(fw, wb[B][0], wb[B][1]);                                               \
-        g2_read_x<0>(fx, xb[B][0], xb[B][1]);                                               \
-        if (c1_) stage(1, t_ + 1);                                                  \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16, FIRST>(acc[0][0], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        g2_read_w<1>(fw, wb[B][0], wb[B][1]);                                               \
-        if (c1_) stage(2, t_ + 1);                                                  \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16, FIRST>(acc[0][1], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        g2_read_x<1>(fx, xb[B][0], xb[B][1]);                                               \
-        if (c2_) stage(0, t_ + 2);                                                  \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16, FIRST>(acc[1][1], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
-        g2_read_w<0>(fw, wb[B][0], wb[B][1]);                                               \
-        if (c2_) { stage(3, t_ + 2); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); } \
-        else if (c1_) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              \
-        G2_BAR(); G2_LGKM0();                                                               \
-        g2_mma<F16, FIRST>(acc[1][0], fx, fw);                                                     \
-        __builtin_amdgcn_sched_barrier(0); G2_BAR();                                        \
+        G2_PHASES(B, FIRST, c1_, c2_)                                                       \
     }
 // ---- balanced schedule (G2F_BAL).  The plain schedule reads 12 fragments in phase 1 (W0 + X0: 48 KB per wave row against a 256-cycle
 // MFMA slot of the partner row), re-reads W0 in phase 4 (28 reads per K tile) and requests W-lo only 3 phases before its first read.
@@ -942,7 +930,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
             next_issued = true;
         };
         if (vt_tile) {
-            // V third of the qkv projection: transposed image [channel][token] over the whole LDS, as in k_gemm256
+            // V third of the qkv projection: transposed image [channel][token] over the whole LDS
 #pragma unroll
             for (int hm = 0; hm < 2; ++hm)
 #pragma unroll
@@ -955,32 +943,19 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
                             const int nl = hn * 128 + wn * 32 + nb * 16 + fq * 4;
                             f32x4 vv = acc[hm][hn][mb][nb];
                             const float4 b = *reinterpret_cast<const float4 *>(smem + G2P_TAIL + 2048 + nl * 4);
+                            float4 cs;
+                            float2 pr;
                             if constexpr (LN_IN) {
-                                const float4 cs = *reinterpret_cast<const float4 *>(smem + G2P_TAIL + 3072 + nl * 4);
-                                const float2 pr = *reinterpret_cast<const float2 *>(smem + G2P_TAIL + ml * 8);
-                                vv[0] = fmaf(vv[0], pr.x, fmaf(pr.y, cs.x, b.x)); vv[1] = fmaf(vv[1], pr.x, fmaf(pr.y, cs.y, b.y));
-                                vv[2] = fmaf(vv[2], pr.x, fmaf(pr.y, cs.z, b.z)); vv[3] = fmaf(vv[3], pr.x, fmaf(pr.y, cs.w, b.w));
-                            } else {
-                                vv[0] += b.x; vv[1] += b.y; vv[2] += b.z; vv[3] += b.w;
+                                cs = *reinterpret_cast<const float4 *>(smem + G2P_TAIL + 3072 + nl * 4);
+                                pr = *reinterpret_cast<const float2 *>(smem + G2P_TAIL + ml * 8);
                             }
                             // (tail reads above complete before the staging writes below reach the tail: rows < 256)
-                            const unsigned p01 = pack2<F16>(vv[0], vv[1]), p23 = pack2<F16>(vv[2], vv[3]);
-                            *reinterpret_cast<unsigned short *>(smem + (nl + 0) * G2_EPI_LD + ml * 2) = (unsigned short)p01;
-                            *reinterpret_cast<unsigned short *>(smem + (nl + 1) * G2_EPI_LD + ml * 2) = (unsigned short)(p01 >> 16);
-                            *reinterpret_cast<unsigned short *>(smem + (nl + 2) * G2_EPI_LD + ml * 2) = (unsigned short)p23;
-                            *reinterpret_cast<unsigned short *>(smem + (nl + 3) * G2_EPI_LD + ml * 2) = (unsigned short)(p23 >> 16);
+                            G2_EPI_VALUE(vv, pr.x, pr.y, cs, b)
+                            G2_STAGE_VT(vv, nl, ml)
                         }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             G2_BAR();
-            unsigned short *vT = (unsigned short *)g.aux;
-            const size_t s_ = (size_t)(m0 >> 10), t0 = (size_t)(m0 & 1023);
-#pragma unroll 4
-            for (int it = 0; it < 16; ++it) {
-                const int row = it * 16 + (tid >> 5);
-                const int c = n0 - 2048 + row;
-                uint4 vv = *reinterpret_cast<const uint4 *>(smem + row * G2_EPI_LD + c16 * 16);
-                st16<EPI == CPX_EPI_QKV_BF16, EPI == CPX_EPI_QKV_BF16>(vT + ((s_ * 16 + (c >> 6)) * 64 + (c & 63)) * 1024 + t0 + c16 * 8, vv, (g.nt_out & 4) != 0, (g.nt_out & 16) != 0);
-            }
+            G2_STORE_VT_ROWS((st16<EPI == CPX_EPI_QKV_BF16, EPI == CPX_EPI_QKV_BF16>(p_, v_, (g.nt_out & 4) != 0, (g.nt_out & 16) != 0)))
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             G2_BAR();
         } else if constexpr (EPI != CPX_EPI_RESID_BF16 && (FLAGS & G2F_DIRECT) != 0) {
@@ -1021,20 +996,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
 #pragma unroll
                         for (int nb = 0; nb < 2; ++nb) {
                             f32x4 vv = acc[hm][hn][mb][nb];
-                            if constexpr (LN_IN) {
-                                const float nm = ln_nm[mb], rs = ln_rs[mb];
-                                vv[0] = fmaf(vv[0], rs, fmaf(nm, cs[nb].x, b[nb].x)); vv[1] = fmaf(vv[1], rs, fmaf(nm, cs[nb].y, b[nb].y));
-                                vv[2] = fmaf(vv[2], rs, fmaf(nm, cs[nb].z, b[nb].z)); vv[3] = fmaf(vv[3], rs, fmaf(nm, cs[nb].w, b[nb].w));
-                            } else {
-                                vv[0] += b[nb].x; vv[1] += b[nb].y; vv[2] += b[nb].z; vv[3] += b[nb].w;
-                            }
-                            if constexpr (EPI == CPX_EPI_GELU_BF16) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) vv[r] = gelu_erf(vv[r]);
-                            } else if constexpr (EPI == CPX_EPI_RELU_BF16) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) vv[r] = fmaxf(vv[r], 0.f);
-                            }
+                            G2_EPI_VALUE(vv, ln_rs[mb], ln_nm[mb], cs[nb], b[nb])
                             pk[nb][0] = pack2<F16>(vv[0], vv[1]);
                             pk[nb][1] = pack2<F16>(vv[2], vv[3]);
                         }
@@ -1081,20 +1043,7 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
                         for (int mb = 0; mb < 4; ++mb) {
                             const int mlh = wm * 64 + mb * 16 + fr;          // row inside this half
                             f32x4 vv = acc[hm][hn][mb][nb];
-                            if constexpr (LN_IN) {
-                                const float nm = ln_nm[mb], rs = ln_rs[mb];
-                                vv[0] = fmaf(vv[0], rs, fmaf(nm, cs.x, b.x)); vv[1] = fmaf(vv[1], rs, fmaf(nm, cs.y, b.y));
-                                vv[2] = fmaf(vv[2], rs, fmaf(nm, cs.z, b.z)); vv[3] = fmaf(vv[3], rs, fmaf(nm, cs.w, b.w));
-                            } else {
-                                vv[0] += b.x; vv[1] += b.y; vv[2] += b.z; vv[3] += b.w;
-                            }
-                            if constexpr (EPI == CPX_EPI_GELU_BF16) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) vv[r] = gelu_erf(vv[r]);
-                            } else if constexpr (EPI == CPX_EPI_RELU_BF16) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) vv[r] = fmaxf(vv[r], 0.f);
-                            }
+                            G2_EPI_VALUE(vv, ln_rs[mb], ln_nm[mb], cs, b)
                             uint2 o;
                             o.x = pack2<F16>(vv[0], vv[1]);
                             o.y = pack2<F16>(vv[2], vv[3]);
@@ -1109,31 +1058,10 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
                     uint4 vv = *reinterpret_cast<const uint4 *>(stg + mlh * G2_EPI_LD + c16 * 16);
                     const int ml = hm * 128 + mlh;
                     const size_t go = (size_t)(m0 + ml) * g.ld_out + n0 + c16 * 8;
-                    if constexpr (EPI == CPX_EPI_RESID_BF16) {
-                        const uint4 rr = rres[it];
-                        unsigned a[4] = {vv.x, vv.y, vv.z, vv.w}, b[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            float lo = from_half<F16>(a[i] & 0xFFFF) + from_half<F16>(b[i] & 0xFFFF);
-                            float hi = from_half<F16>(a[i] >> 16) + from_half<F16>(b[i] >> 16);
-                            a[i] = pack2<F16>(lo, hi);
-                        }
-                        vv = make_uint4(a[0], a[1], a[2], a[3]);
-                    }
+                    if constexpr (EPI == CPX_EPI_RESID_BF16) G2_ADD_RESID(vv, rres[it])
                     st16<EPI == CPX_EPI_QKV_BF16, EPI == CPX_EPI_RESID_BF16 || EPI == CPX_EPI_QKV_BF16>((unsigned short *)g.out + go, vv, (g.nt_out & (n0 < 1024 ? 1 : 2)) != 0,
                                                                                         (g.nt_out & (EPI == CPX_EPI_QKV_BF16 ? 16 : 8)) != 0);
-                    if constexpr (STATS) {
-                        unsigned a[4] = {vv.x, vv.y, vv.z, vv.w};
-                        float sm = 0.f, sq = 0.f;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const float lo = from_half<F16>(a[i] & 0xFFFF), hi = from_half<F16>(a[i] >> 16);
-                            sm += lo + hi; sq += lo * lo + hi * hi;
-                        }
-                        sm = half_wave_sum(sm); sq = half_wave_sum(sq);
-                        if (c16 == 16)
-                            *reinterpret_cast<float2 *>(g.stats_out + ((size_t)(m0 + ml) * LN_SLOTS + tile_n) * 2) = make_float2(sm, sq);
-                    }
+                    if constexpr (STATS) g2_row_stats<F16>(vv, c16, g.stats_out, (size_t)(m0 + ml), tile_n);
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 G2_BAR();
@@ -1144,6 +1072,13 @@ __global__ void __launch_bounds__(G2_THREADS, 2) k_gemm256p(GemmArgs g) {
         v = vn; m0 = m0n; n0 = n0n; tile_n = tile_nn;
     }
 }
+#undef G2_TILE_OF
+#undef G2_FRAG_BASES
+#undef G2_PHASES
+#undef G2_EPI_VALUE
+#undef G2_STAGE_VT
+#undef G2_STORE_VT_ROWS
+#undef G2_ADD_RESID
 
 CPX_SWITCH(g_gemm_persist, 1);      // 1 = persistent 256^2 kernel (k_gemm256p), 0 = one workgroup per tile (k_gemm256)
 CPX_SWITCH(g_gemm_variant, 1);      // 1 = LDS-DMA staging, 0 = register staging (debug / A-B)
@@ -1176,6 +1111,39 @@ extern "C" void cpx_gemm_set_4w(int on) { g_gemm_4w = on; }
 extern "C" void cpx_gemm_set_nt(int on) { g_gemm_nt = on; }
 #endif
 
+// runs the statement(s) with `F16` a compile-time constant equal to `f16`
+#define CPX_F16_DISPATCH(f16, F16, ...)                               \
+    do {                                                              \
+        if (f16) { constexpr bool F16 = true; __VA_ARGS__; }          \
+        else { constexpr bool F16 = false; __VA_ARGS__; }             \
+    } while (0)
+// lets KERNEL use LDS_BYTES of dynamic LDS: once per (kernel instantiation, device)
+template <auto KERNEL, int LDS_BYTES>
+static void gemm_allow_lds() {
+    static CpxOncePerDevice once;
+    once([] { (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); });
+}
+static int gemm_cu_count() {
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus > 0 ? cus : 256;
+}
+
+// does this shape take the 256^2 kernel (whose RESID epilogue can emit LN statistics)?  The launcher's own rule: launch_gemm256 asks here
+int cpx_gemm_half_uses_big_tile(int M, int N, int K, int epilogue) {
+    if (epilogue == CPX_EPI_F32) return 0;
+    if (!g_gemm_big || M % 256 || N % 256 || K < 128) return 0;
+    // (an odd number of K tiles only on the one-workgroup-per-tile kernel, which is what the positional epilogue takes)
+    if ((K / 64) % 2 && epilogue != CPX_EPI_POS_BF16) return 0;
+    return (M / 256) * (N / 256) >= 256;            // enough tiles for 256 CUs
+}
+
+template <int EPI, bool F16, int FLAGS>
+static void launch_gemm256_tiles(const GemmArgs &a, hipStream_t s) {          // one workgroup per tile
+    gemm_allow_lds<k_gemm256<EPI, F16, FLAGS>, G2_LDS_BYTES>();
+    hipLaunchKernelGGL((k_gemm256<EPI, F16, FLAGS>), dim3(a.n_blocks), dim3(G2_THREADS), G2_LDS_BYTES, s, a);
+}
 template <int EPI, bool F16, int FLAGS>
 static void launch_gemm256_flags(const GemmArgs &a, hipStream_t s) {
     // the qkv projection keeps one workgroup per tile: a third of its tiles (the V^T ones) cannot overlap their
@@ -1184,15 +1152,8 @@ static void launch_gemm256_flags(const GemmArgs &a, hipStream_t s) {
     // (the persistent kernel addresses its operands through 32-bit buffer offsets)
     const bool fits32 = (size_t)a.M * (size_t)a.K * 2 < ((size_t)1 << 31) && (size_t)a.N * (size_t)a.K * 2 < ((size_t)1 << 31);
     if (g_gemm_persist && fits32 && (EPI != CPX_EPI_QKV_BF16 || qkv_balanced)) {
-        static CpxOncePerDevice once_p;
-        static int n_cu = 0;
-        once_p([] {
-            (void)hipFuncSetAttribute((const void *)k_gemm256p<EPI, F16, FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, G2P_LDS_BYTES);
-            int dev = 0, cus = 256;
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            n_cu = cus > 0 ? cus : 256;
-        });
+        gemm_allow_lds<k_gemm256p<EPI, F16, FLAGS>, G2P_LDS_BYTES>();
+        static const int n_cu = gemm_cu_count();
         if (EPI == CPX_EPI_QKV_BF16) {
             if (n_cu == 256) {
                 GemmArgs b = a;
@@ -1206,19 +1167,14 @@ static void launch_gemm256_flags(const GemmArgs &a, hipStream_t s) {
             return;
         }
     }
-    static CpxOncePerDevice once;
-    once([] { (void)hipFuncSetAttribute((const void *)k_gemm256<EPI, F16, FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES); });
-    hipLaunchKernelGGL((k_gemm256<EPI, F16, FLAGS>), dim3(a.n_blocks), dim3(G2_THREADS), G2_LDS_BYTES, s, a);
+    launch_gemm256_tiles<EPI, F16, FLAGS>(a, s);
 }
 
 template <int EPI, bool F16>
 static bool launch_gemm256(const GemmArgs &a0, hipStream_t s) {
     if constexpr (EPI == CPX_EPI_F32) return false;
     else {
-        // (an odd number of K tiles only on the one-workgroup-per-tile kernel, which is what the positional epilogue takes)
-        if (!g_gemm_big || a0.M % 256 || a0.N % 256 || a0.K < 128) return false;
-        if ((a0.K / 64) % 2 && EPI != CPX_EPI_POS_BF16) return false;
-        if ((a0.M / 256) * (a0.N / 256) < 256) return false;          // not enough tiles for 256 CUs
+        if (!cpx_gemm_half_uses_big_tile(a0.M, a0.N, a0.K, EPI)) return false;
         GemmArgs a = a0;
         a.tiles_n = a.N / 256; a.n_blocks = (a.M / 256) * (a.N / 256);
         // one instantiation per (LayerNorm consumer | statistics producer)
@@ -1226,13 +1182,8 @@ static bool launch_gemm256(const GemmArgs &a0, hipStream_t s) {
         constexpr int F1 = PRODUCER ? G2F_STATS : G2F_LN;
         const bool f1 = PRODUCER ? a.stats_out != nullptr : a.ln_stats != nullptr;
         if constexpr (EPI == CPX_EPI_POS_BF16) {       // one workgroup per tile (its epilogue reads the positional table with plain loads)
-            static CpxOncePerDevice once_pos;
-            once_pos([] {
-                (void)hipFuncSetAttribute((const void *)k_gemm256<EPI, F16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
-                (void)hipFuncSetAttribute((const void *)k_gemm256<EPI, F16, G2F_STATS>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
-            });
-            if (f1) hipLaunchKernelGGL((k_gemm256<EPI, F16, G2F_STATS>), dim3(a.n_blocks), dim3(G2_THREADS), G2_LDS_BYTES, s, a);
-            else hipLaunchKernelGGL((k_gemm256<EPI, F16, 0>), dim3(a.n_blocks), dim3(G2_THREADS), G2_LDS_BYTES, s, a);
+            if (!f1) launch_gemm256_tiles<EPI, F16, 0>(a, s);
+            else launch_gemm256_tiles<EPI, F16, G2F_STATS>(a, s);
             return true;
         } else {
             // mlp.lin1 of the bf16 network (folded LayerNorm + bias + erf-GELU) on the one-wave-per-SIMD kernel: bitwise equal to the
@@ -1280,18 +1231,18 @@ static bool launch_gemm256(const GemmArgs &a0, hipStream_t s) {
 
 template <int EPI>
 static void launch_gemm(const GemmArgs &a, hipStream_t s, bool f16) {
-    if (f16 ? launch_gemm256<EPI, true>(a, s) : launch_gemm256<EPI, false>(a, s)) return;
+    bool big;
+    CPX_F16_DISPATCH(f16, F16, big = launch_gemm256<EPI, F16>(a, s));
+    if (big) return;
     dim3 grid(a.n_blocks), block(GEMM_THREADS);
     size_t lds = 2 * STAGE_BYTES;
 #ifdef CPX_DEBUG
     if (!g_gemm_variant) {           // register-staged variant of the 128^2 kernel: A/B reference only
-        if (f16) hipLaunchKernelGGL((k_gemm<EPI, true, false>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_gemm<EPI, false, false>), grid, block, lds, s, a);
+        CPX_F16_DISPATCH(f16, F16, hipLaunchKernelGGL((k_gemm<EPI, F16, false>), grid, block, lds, s, a));
         return;
     }
 #endif
-    if (f16) hipLaunchKernelGGL((k_gemm<EPI, true, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((k_gemm<EPI, false, true>), grid, block, lds, s, a);
+    CPX_F16_DISPATCH(f16, F16, hipLaunchKernelGGL((k_gemm<EPI, F16, true>), grid, block, lds, s, a));
 }
 
 // row statistics (sum, sum of squares) of a half-precision [rows][1024] matrix into slot 0 of
@@ -1316,8 +1267,8 @@ __global__ void __launch_bounds__(256) k_row_stats(const unsigned short *__restr
 }
 int cpx_row_stats_half(int dtype, const void *x, int rows, float *stats, void *stream) {
     CPX_REQUIRE(x && stats && rows > 0 && (dtype == CPX_DT_BF16 || dtype == CPX_DT_F16));
-    if (dtype == CPX_DT_F16) hipLaunchKernelGGL(k_row_stats<true>, dim3(cpx_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short *)x, rows, stats);
-    else hipLaunchKernelGGL(k_row_stats<false>, dim3(cpx_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short *)x, rows, stats);
+    CPX_F16_DISPATCH(dtype == CPX_DT_F16, F16,
+                     hipLaunchKernelGGL(k_row_stats<F16>, dim3(cpx_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short *)x, rows, stats));
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }
@@ -1326,12 +1277,14 @@ extern "C" int cpx_row_stats(const void *x, int rows, float *stats, void *stream
     return cpx_row_stats_half(CPX_DT_BF16, x, rows, stats, stream);
 }
 
-// does this shape take the 256^2 kernel (whose RESID epilogue can emit LN statistics)?
-int cpx_gemm_half_uses_big_tile(int M, int N, int K, int epilogue) {
-    if (epilogue == CPX_EPI_F32) return 0;
-    if (!g_gemm_big || M % 256 || N % 256 || K < 128) return 0;
-    if ((K / 64) % 2 && epilogue != CPX_EPI_POS_BF16) return 0;
-    return (M / 256) * (N / 256) >= 256;
+// the fields every launch fills, 128^2 tile counts included (launch_gemm256 replaces them); everything else off: no LayerNorm fold,
+// no statistics, row-major tile order, ordinary stores, plain GEMM
+static GemmArgs gemm_args(const void *A, const void *Wt, int M, int N, int K, const float *bias, const void *aux, void *out, int ld_out) {
+    GemmArgs a = {};
+    a.A = (const unsigned short *)A; a.W = (const unsigned short *)Wt;
+    a.M = M; a.N = N; a.K = K; a.bias = bias; a.aux = aux; a.out = out; a.ld_out = ld_out;
+    a.tiles_n = N / BN; a.n_blocks = (M / BM) * (N / BN);
+    return a;
 }
 
 int cpx_gemm_half(int dtype, const void *A, const void *Wt, int M, int N, int K, int epilogue,
@@ -1345,13 +1298,9 @@ int cpx_gemm_half(int dtype, const void *A, const void *Wt, int M, int N, int K,
     CPX_REQUIRE(epilogue != CPX_EPI_QKV_BF16 || (N == 3072 && M % 1024 == 0));
     CPX_REQUIRE(!ln_stats || (ln_colsum && epilogue != CPX_EPI_RESID_BF16));
     CPX_REQUIRE(!stats_out || ((epilogue == CPX_EPI_RESID_BF16 || epilogue == CPX_EPI_POS_BF16) && N == 1024 && cpx_gemm_half_uses_big_tile(M, N, K, epilogue)));
-    GemmArgs a;
-    a.A = (const unsigned short *)A; a.W = (const unsigned short *)Wt;
-    a.M = M; a.N = N; a.K = K; a.bias = bias; a.aux = aux; a.out = out; a.ld_out = ld_out;
-    a.tiles_n = N / BN; a.n_blocks = (M / BM) * (N / BN);
+    GemmArgs a = gemm_args(A, Wt, M, N, K, bias, aux, out, ld_out);
     a.ln_stats = ln_stats; a.ln_colsum = ln_colsum; a.stats_out = stats_out; a.l2_block = g_gemm_l2; a.nt_out = g_gemm_nt;
     a.rev_m = (g_gemm_rev && K >= 4096) ? 1 : 0;
-    a.conv_c = 0;
     hipStream_t s = (hipStream_t)stream;
     switch (epilogue) {
         case CPX_EPI_BF16: launch_gemm<CPX_EPI_BF16>(a, s, f16); break;
@@ -1376,23 +1325,14 @@ int cpx_conv3_half(int dtype, const void *x, const void *Wt, int M, int N, int C
     CPX_REQUIRE(x && Wt && out && (dtype == CPX_DT_BF16 || dtype == CPX_DT_F16));
     CPX_REQUIRE(M > 0 && M % 1024 == 0 && N > 0 && N % BN == 0 && C > 0 && C % BK == 0);
     CPX_REQUIRE(ld_out >= N && ld_out % 4 == 0 && (epilogue == CPX_EPI_BF16 || epilogue == CPX_EPI_RELU_BF16));
-    GemmArgs a;
-    a.A = (const unsigned short *)x; a.W = (const unsigned short *)Wt;
-    a.M = M; a.N = N; a.K = 9 * C; a.bias = bias; a.aux = nullptr; a.out = out; a.ld_out = ld_out;
-    a.tiles_n = N / BN; a.n_blocks = (M / BM) * (N / BN);
-    a.ln_stats = nullptr; a.ln_colsum = nullptr; a.stats_out = nullptr; a.l2_block = 0; a.rev_m = 0; a.nt_out = 0;
+    GemmArgs a = gemm_args(x, Wt, M, N, 9 * C, bias, nullptr, out, ld_out);
     a.conv_c = C;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(a.n_blocks), block(GEMM_THREADS);
     const size_t lds = 2 * STAGE_BYTES;
     const bool f16 = dtype == CPX_DT_F16;
-    if (epilogue == CPX_EPI_BF16) {
-        if (f16) hipLaunchKernelGGL((k_gemm<CPX_EPI_BF16, true, true, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_gemm<CPX_EPI_BF16, false, true, true>), grid, block, lds, s, a);
-    } else {
-        if (f16) hipLaunchKernelGGL((k_gemm<CPX_EPI_RELU_BF16, true, true, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_gemm<CPX_EPI_RELU_BF16, false, true, true>), grid, block, lds, s, a);
-    }
+    if (epilogue == CPX_EPI_BF16) CPX_F16_DISPATCH(f16, F16, hipLaunchKernelGGL((k_gemm<CPX_EPI_BF16, F16, true, true>), grid, block, lds, s, a));
+    else CPX_F16_DISPATCH(f16, F16, hipLaunchKernelGGL((k_gemm<CPX_EPI_RELU_BF16, F16, true, true>), grid, block, lds, s, a));
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }

@@ -98,8 +98,7 @@ __global__ void __launch_bounds__(G4_THREADS) __attribute__((amdgpu_waves_per_eu
     const int K = g.K, nk = K / 64, nblk = g.n_blocks, tiles_m = nblk / g.tiles_n;
     // XCD-aware tile order: workgroup ids with equal id % 8 share an XCD and take a contiguous range of tiles, swept 8 x 4 super-tile by super-tile
     auto coords = [&](int v, int &m0_, int &n0_) {
-        const int nxcd = 8, q = nblk / nxcd, r = nblk % nxcd, x = v % nxcd;
-        const int bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + v / nxcd;
+        const int bid = xcd_contiguous_id(v, nblk);
         int tile_m, tile_n;
         if ((tiles_m & 7) == 0 && (g.tiles_n & 3) == 0) {
             const int grp = bid >> 5, w_ = bid & 31, cgn = g.tiles_n >> 2;

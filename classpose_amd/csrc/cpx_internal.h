@@ -77,6 +77,13 @@ int cpx_attention_f32(const float *qkv, const float *rel_h, const float *rel_w, 
 // the neck's im2col: x [n_subtiles * 1024][256] -> out [n_subtiles * 1024][2304], k = tap * 256 + c
 int cpx_im2col3_f32(const float *x, int n_subtiles, float *out, void *stream);
 
+// XCD-aware remap of the GEMM kernels: workgroup ids with equal (id % 8) share an XCD, so id v of nblk gets the position
+// that gives each XCD one contiguous range of tiles (the first nblk % 8 XCDs one tile more)
+__device__ __forceinline__ int xcd_contiguous_id(int v, int nblk) {
+    const int nxcd = 8, q = nblk / nxcd, r = nblk % nxcd, x = v % nxcd;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + v / nxcd;
+}
+
 // returns the first non-zero status of a chain of launches from the enclosing function (or lambda)
 #define CPX_RUN(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 
