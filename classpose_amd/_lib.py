@@ -173,6 +173,11 @@ SIGNATURES = {
     "cpx_blocks_backward_workspace_bytes": (_sz, [_i, _i]),
     "cpx_blocks_backward_slab_crops": (_i, []),
     "cpx_blocks_backward": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _sz, _p, _p, _p, _p, _sz, _p]),
+    "cpx_blocks_backward_workspace_bytes_ex": (_sz, [_i, _i, _i]),
+    "cpx_blocks_backward_ex": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _sz, _p, _i, _p, _p, _p, _sz, _p]),
+    "cpx_gemm_tn_bf16": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p]),
+    "cpx_colsum_workspace_bytes": (_sz, [_i, _i]),
+    "cpx_colsum_add": (_i, [_p, _i, _i, _p, _p, _sz, _p]),
     "cpx_layernorm_backward_bytes": (_sz, [_i, _i]),
     "cpx_attention_backward_workspace_bytes": (_sz, [_i]),
     "cpx_attention_backward": (_i, [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),

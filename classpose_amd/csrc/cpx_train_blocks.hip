@@ -613,6 +613,60 @@ __global__ void __launch_bounds__(256) k_colsum_add(const float *__restrict__ dy
     for (int r = 0; r < rows; ++r) s += (double)dy[(size_t)r * N + c];
     db[c] = (float)((double)db[c] + s);
 }
+// The same sums for the bf16 gradient mode, row-parallel.  grid (N / 64, rows / CS_ROWS), 4 waves: lane = one of 64 columns, wave w one
+// float64 chain over the rows w, w + 4, ... of the workgroup's CS_ROWS rows in order, then (w0 + w1) + w2 + w3 -> part [rows / CS_ROWS][N];
+// k_colsum_finish adds the partials in row order on top of db and rounds once.  A fixed tree per column: no atomics.
+#define CS_ROWS 64
+__global__ void __launch_bounds__(256) k_colsum_part(const float *__restrict__ dy, int N, double *__restrict__ part) {
+    __shared__ double sm[4][64];
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, c = blockIdx.x * 64 + l;
+    const float *p = dy + ((size_t)blockIdx.y * CS_ROWS + w) * N + c;
+    double s = 0;
+#pragma unroll
+    for (int i = 0; i < CS_ROWS / 4; ++i) s += (double)p[(size_t)(4 * i) * N];
+    sm[w][l] = s;
+    __syncthreads();
+    if (w == 0) part[(size_t)blockIdx.y * N + c] = ((sm[0][l] + sm[1][l]) + sm[2][l]) + sm[3][l];
+}
+__global__ void __launch_bounds__(256) k_colsum_finish(const double *__restrict__ part, int nparts, int N, float *__restrict__ db) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N) return;
+    double s = 0;
+    for (int k = 0; k < nparts; ++k) s += part[(size_t)k * N + c];
+    db[c] = (float)((double)db[c] + s);
+}
+extern "C" size_t cpx_colsum_workspace_bytes(int rows, int N) {
+    if (rows <= 0 || N <= 0 || rows % CS_ROWS || N % 64 || rows / CS_ROWS > 65535) return 0;
+    return cpx_align_up((size_t)(rows / CS_ROWS) * N * sizeof(double), 256);
+}
+extern "C" int cpx_colsum_add(const float *dy, int rows, int N, float *db, void *workspace, size_t workspace_bytes, void *stream) {
+    CPX_REQUIRE(dy && db && workspace);
+    const size_t need = cpx_colsum_workspace_bytes(rows, N);
+    CPX_REQUIRE(need > 0 && workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_colsum_part, dim3(N / 64, rows / CS_ROWS), dim3(256), 0, s, dy, N, (double *)workspace);
+    CPX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_colsum_finish, grid1(N), dim3(256), 0, s, (const double *)workspace, rows / CS_ROWS, N, db);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
+// W [Npad][Kpad] of a 2-byte type -> wt [Kp128][Npad] of the same type, rows Kpad .. zero (cpx_wt_run's float32 result, kept in 2 bytes:
+// the operand cpx_gemm_half takes for dX = dY W); 32 x 32 tiles through LDS, Npad and Kp128 multiples of 32
+__global__ void __launch_bounds__(256) k_wt16(const unsigned short *__restrict__ w, int Npad, int Kpad, unsigned short *__restrict__ wt) {
+    __shared__ unsigned short t[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5, k0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[ty + 8 * k][tx] = k0 + tx < Kpad ? w[(size_t)(n0 + ty + 8 * k) * Kpad + k0 + tx] : (unsigned short)0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wt[(size_t)(k0 + ty + 8 * k) * Npad + n0 + tx] = t[tx][ty + 8 * k];
+}
+static int wt16_run(const void *w, int Npad, int Kpad, int Kp128, void *wt, hipStream_t s) {
+    CPX_REQUIRE(Npad % 32 == 0 && Kp128 % 32 == 0 && Kpad <= Kp128 && Npad / 32 <= 65535);
+    hipLaunchKernelGGL(k_wt16, dim3(Kp128 / 32, Npad / 32), dim3(256), 0, s, (const unsigned short *)w, Npad, Kpad, (unsigned short *)wt);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
+}
 // out = a + b (out may be a)
 __global__ void __launch_bounds__(256) k_add_f32(const float *a, const float *b, size_t n4, float *out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -678,23 +732,32 @@ extern "C" long long cpx_block_grad_layout(long long *off) {
 // two transposed GEMM operands [4096][Ms]; a transposed weight and the widened fc1 operand [4096][1024]; the workspaces of
 // cpx_attention_backward and cpx_layernorm_backward; three [1024] vectors.  8 and 32 crops alike: 241 MiB.
 #define BLK_SLAB 2
-struct BlocksBwdLayout { size_t dx, dxl, xn, xh, b1, b2, b3, t1, t2, wt, wop, attn, attn_bytes, ln, ln_bytes, vec, total; };
-static BlocksBwdLayout blocks_bwd_layout() {
+// grad_dtype CPX_DT_BF16 (bf16 operands on the bf16 MFMA): no transposed float32 operands and no widened weights; instead dy, the hidden
+// activations and the LayerNorm output rounded to bf16 ([Ms][4096], [Ms][4096], [Ms][1024]), a transposed 2-byte weight [4096][1024] and the
+// partials of the column sums: 190 MiB.
+struct BlocksBwdLayout { size_t dx, dxl, xn, xh, b1, b2, b3, t1, t2, wt, wop, attn, attn_bytes, ln, ln_bytes, vec, dyb, hb, xb, wt16, cs, cs_bytes, total; };
+static BlocksBwdLayout blocks_bwd_layout(int grad_dtype) {
     BlocksBwdLayout L; CpxArena a; const size_t Ms = (size_t)BLK_SLAB * 1024;
+    const bool g16 = grad_dtype == CPX_DT_BF16;
     L.dx = a.take(Ms * 1024 * 4); L.dxl = a.take(Ms * 1024 * 4); L.xn = a.take(Ms * 1024 * 4); L.xh = a.take(Ms * 1024 * 4);
     L.b1 = a.take(Ms * 4096 * 4); L.b2 = a.take(Ms * 4096 * 4); L.b3 = a.take(Ms * 4096 * 4);
-    L.t1 = a.take(Ms * 4096 * 4); L.t2 = a.take(Ms * 4096 * 4);
-    L.wt = a.take((size_t)4096 * 1024 * 4); L.wop = a.take((size_t)4096 * 1024 * 4);
+    L.t1 = a.take(g16 ? 0 : Ms * 4096 * 4); L.t2 = a.take(g16 ? 0 : Ms * 4096 * 4);
+    L.wt = a.take(g16 ? 0 : (size_t)4096 * 1024 * 4); L.wop = a.take(g16 ? 0 : (size_t)4096 * 1024 * 4);
     L.attn_bytes = cpx_attention_backward_workspace_bytes(BLK_SLAB); L.attn = a.take(L.attn_bytes);
     L.ln_bytes = cpx_layernorm_backward_bytes((int)Ms, 1024); L.ln = a.take(L.ln_bytes);
     L.vec = a.take(3 * 1024 * 4);
+    L.dyb = a.take(g16 ? Ms * 4096 * 2 : 0); L.hb = a.take(g16 ? Ms * 4096 * 2 : 0); L.xb = a.take(g16 ? Ms * 1024 * 2 : 0);
+    L.wt16 = a.take(g16 ? (size_t)4096 * 1024 * 2 : 0);
+    L.cs_bytes = g16 ? cpx_colsum_workspace_bytes((int)Ms, 4096) : 0; L.cs = a.take(L.cs_bytes);
     L.total = a.o;
     return L;
 }
-extern "C" size_t cpx_blocks_backward_workspace_bytes(int nS, int dtype) {
-    if (nS <= 0 || !dtype_ok(dtype)) return 0;
-    return blocks_bwd_layout().total;
+static bool grad_dtype_ok(int dtype, int grad_dtype) { return grad_dtype == CPX_DT_F32 || (grad_dtype == CPX_DT_BF16 && dtype == CPX_DT_BF16); }
+extern "C" size_t cpx_blocks_backward_workspace_bytes_ex(int nS, int dtype, int grad_dtype) {
+    if (nS <= 0 || !dtype_ok(dtype) || !grad_dtype_ok(dtype, grad_dtype)) return 0;
+    return blocks_bwd_layout(grad_dtype).total;
 }
+extern "C" size_t cpx_blocks_backward_workspace_bytes(int nS, int dtype) { return cpx_blocks_backward_workspace_bytes_ex(nS, dtype, CPX_DT_F32); }
 extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
 
 // w: the weights the forward ran with; params: the K blocks' UNFOLDED parameters as the forward reads them (every tensor rounded through
@@ -703,14 +766,21 @@ extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
 // workspace -- the gradient of the last block's output is dy0 W0, formed here.  grads: K records, gradients with respect to the
 // unfolded gamma, beta, W, b and to the operand tables.  dx_all (or NULL): [K + 1][rows][1024] float32, record j < K the gradient of
 // block first_block + j's input, record K that of the last block's output.
-extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
-                                   size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
-                                   size_t workspace_bytes, void *stream) {
+//
+// grad_dtype CPX_DT_BF16 (a bf16 network only): every matrix product takes both operands rounded to bf16 (round to nearest even, each value
+// once), accumulates in float32 on the bf16 MFMA and writes float32 -- dW += bf16(dy)^T bf16(a) on cpx_gemm_tn_bf16, da = bf16(dy) W and the
+// recomputed pre-activation bf16(xhat or xn) W1^T + b1 on cpx_gemm_half with the float32 epilogue, W the forward's own operand (exact in
+// bf16; for da a transposed 2-byte copy) --, and db takes the column sums of the unrounded dy from cpx_colsum_add.  Everything between
+// the products is the float32 / float64 code of the float32 mode, with the same slabs.
+extern "C" int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+                                      size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, float *grads, float *dx_all,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(blocks_weights_ok(w, first_block) && params && fwd_workspace && dy0 && grads && workspace && w->neck0_w);
-    CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block));
+    CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block) && grad_dtype_ok(w->dtype, grad_dtype));
     const int dt = w->dtype, K = w->depth - first_block;
+    const bool g16 = grad_dtype == CPX_DT_BF16;
     const BlocksFwdLayout F = blocks_fwd_layout(nS, dt, K);
-    const BlocksBwdLayout L = blocks_bwd_layout();
+    const BlocksBwdLayout L = blocks_bwd_layout(grad_dtype);
     CPX_REQUIRE(fwd_workspace_bytes >= F.total && workspace_bytes >= L.total);
     CPX_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)fwd_workspace & 255) == 0);
     CPX_REQUIRE((((uintptr_t)params | (uintptr_t)dy0 | (uintptr_t)grads | (uintptr_t)dx_all) & 15) == 0);
@@ -720,6 +790,7 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
     float *dx = (float *)(ws + L.dx), *dxl = (float *)(ws + L.dxl), *xn = (float *)(ws + L.xn), *xh = (float *)(ws + L.xh);
     float *b1 = (float *)(ws + L.b1), *b2 = (float *)(ws + L.b2), *b3 = (float *)(ws + L.b3), *t1 = (float *)(ws + L.t1), *t2 = (float *)(ws + L.t2);
     float *wt = (float *)(ws + L.wt), *wop = (float *)(ws + L.wop), *tg = (float *)(ws + L.vec), *tb = tg + 1024, *ones = tg + 2048;
+    void *dyb = ws + L.dyb, *hb = ws + L.hb, *xb = ws + L.xb, *wt16 = ws + L.wt16;
     long long go[BLK_N];
     const long long gn = cpx_block_grad_layout(go);
     const size_t es = es_of(dt), rows_all = (size_t)nS * 1024;
@@ -747,6 +818,16 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
         CPX_RUN(cpx_gemm_f32(dy, wt, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, stream));
         return CPX_OK;
     };
+    // the same Linear in the bf16 gradient mode: a [Ms][Kin] bf16 (rounded once by the caller, or stored in bf16), Wop [N][Kin] the
+    // forward's bf16 operand
+    auto round16 = [&](const float *src, size_t n, void *dst) -> int { return cpx_round_weights(src, dst, (long long)n, CPX_DT_BF16, 0, stream); };
+    auto linear_bwd16 = [&](const float *dy, const void *a16, const void *Wop, int Ms, int N, int Kin, float *dW, float *db, float *da) -> int {
+        CPX_RUN(round16(dy, (size_t)Ms * N, dyb));
+        CPX_RUN(cpx_gemm_tn_bf16(dyb, a16, Ms, N, Kin, 1, dW, Kin, stream));
+        CPX_RUN(cpx_colsum_add(dy, Ms, N, db, ws + L.cs, L.cs_bytes, stream));
+        CPX_RUN(wt16_run(Wop, N, Kin, Kin, wt16, s));
+        return cpx_gemm_half(CPX_DT_BF16, dyb, wt16, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, nullptr, nullptr, nullptr, stream);
+    };
     // folded: dout is the gradient of xhat (gamma = 1 here; dgamma and dbeta come from k_unfold_grads after the last slab)
     auto ln_bwd = [&](const void *x, const float *g, const float *dout, int Ms, float *dgamma, float *dbeta) -> int {
         CPX_RUN(cpx_layernorm_backward(dt, x, fuse ? ones : g, dout, Ms, 1024, 1e-6f, dxl, tg, tb, ws + L.ln, L.ln_bytes, stream));
@@ -765,8 +846,14 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
         const int nc = std::min(BLK_SLAB, nS - c0), Ms = nc * 1024;
         const size_t r0 = (size_t)c0 * 1024;
         // the gradient of the last block's output: dy0 W0 (the rounded operand [256][1024], widened and transposed)
-        CPX_RUN(cpx_wt_run(dt, w->neck0_w, 256, 1024, 1024, wt, s));
-        CPX_RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, stream));
+        if (g16) {
+            CPX_RUN(round16(dy0 + r0 * 256, (size_t)Ms * 256, dyb));
+            CPX_RUN(wt16_run(w->neck0_w, 256, 1024, 1024, wt16, s));
+            CPX_RUN(cpx_gemm_half(CPX_DT_BF16, dyb, wt16, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, nullptr, nullptr, nullptr, stream));
+        } else {
+            CPX_RUN(cpx_wt_run(dt, w->neck0_w, 256, 1024, 1024, wt, s));
+            CPX_RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, stream));
+        }
         if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)K * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
         for (int j = K - 1; j >= 0; --j) {
             const cpx_block_weights &b = w->blocks[first_block + j];
@@ -778,26 +865,45 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
             // ---- the MLP: x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2 ----
             if (fuse) CPX_RUN(ln_fwd(xmid, nullptr, nullptr, Ms, xh, false));
             else CPX_RUN(ln_fwd(xmid, P + go[8], P + go[9], Ms, xn, half));
-            const float *w1op = (const float *)b.fc1_w;              // the operand the forward multiplied by (folded where it folds)
-            if (half) {
-                CPX_RUN(widen(b.fc1_w, (size_t)4096 * 1024));
-                w1op = wop;
+            if (g16) {
+                CPX_RUN(round16(fuse ? xh : xn, (size_t)Ms * 1024, xb));
+                CPX_RUN(cpx_gemm_half(CPX_DT_BF16, xb, b.fc1_w, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, nullptr, nullptr, nullptr, stream));   // pre
+                hipLaunchKernelGGL(k_gelu_fwd_round<CPX_DT_BF16>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2);                  // h
+                CPX_CHECK_LAUNCH();
+                CPX_RUN(round16(b2, (size_t)Ms * 4096, hb));                                                                   // (exact: h is rounded)
+                CPX_RUN(linear_bwd16(dx, hb, b.fc2_w, Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                          // fc2 -> dh
+                CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                             // dpre
+                CPX_RUN(linear_bwd16(b2, xb, b.fc1_w, Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));                          // fc1 -> d LN2 output
+            } else {
+                const float *w1op = (const float *)b.fc1_w;              // the operand the forward multiplied by (folded where it folds)
+                if (half) {
+                    CPX_RUN(widen(b.fc1_w, (size_t)4096 * 1024));
+                    w1op = wop;
+                }
+                CPX_RUN(cpx_gemm_f32(fuse ? xh : xn, w1op, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, stream));     // pre
+                CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_gelu_fwd_round<DT>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2));   // h
+                CPX_CHECK_LAUNCH();
+                CPX_RUN(linear_bwd(dx, b2, CPX_DT_F32, P + go[12], Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                // fc2 -> dh
+                CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                // dpre
+                CPX_RUN(linear_bwd(b2, fuse ? xh : xn, CPX_DT_F32, fuse ? w1op : P + go[10], Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));   // fc1 -> d LN2 output (folded: d xhat)
             }
-            CPX_RUN(cpx_gemm_f32(fuse ? xh : xn, w1op, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, stream));     // pre
-            CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_gelu_fwd_round<DT>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2));   // h
-            CPX_CHECK_LAUNCH();
-            CPX_RUN(linear_bwd(dx, b2, CPX_DT_F32, P + go[12], Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                // fc2 -> dh
-            CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                // dpre
-            CPX_RUN(linear_bwd(b2, fuse ? xh : xn, CPX_DT_F32, fuse ? w1op : P + go[10], Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));   // fc1 -> d LN2 output (folded: d xhat)
             CPX_RUN(ln_bwd(xmid, P + go[8], b3, Ms, Gd + go[8], Gd + go[9]));                                                 // dx = d x_mid
             // ---- attention: x_mid = x_in + attention(LN1(x_in) Wqkv^T + bqkv) Wp^T + bp ----
-            CPX_RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
+            if (g16) CPX_RUN(linear_bwd16(dx, ao, b.proj_w, Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                       // proj -> dO (ao is stored in bf16)
+            else CPX_RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
             CPX_RUN(cpx_attention_backward_run(dt, qkv, b.rel_h, b.rel_w, nullptr, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
-            if (fuse) {
-                CPX_RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
-                CPX_RUN(widen(b.qkv_w, (size_t)3072 * 1024));
-            } else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, half));
-            CPX_RUN(linear_bwd(b1, fuse ? xh : xn, CPX_DT_F32, fuse ? wop : P + go[2], Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));       // qkv -> d LN1 output (folded: d xhat)
+            if (g16) {
+                if (fuse) CPX_RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
+                else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, true));
+                CPX_RUN(round16(fuse ? xh : xn, (size_t)Ms * 1024, xb));
+                CPX_RUN(linear_bwd16(b1, xb, b.qkv_w, Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));                            // qkv -> d LN1 output
+            } else {
+                if (fuse) {
+                    CPX_RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
+                    CPX_RUN(widen(b.qkv_w, (size_t)3072 * 1024));
+                } else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, half));
+                CPX_RUN(linear_bwd(b1, fuse ? xh : xn, CPX_DT_F32, fuse ? wop : P + go[2], Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));       // qkv -> d LN1 output (folded: d xhat)
+            }
             CPX_RUN(ln_bwd(xin, P + go[0], b3, Ms, Gd + go[0], Gd + go[1]));                                                  // dx = d x_in
             if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)j * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
         }
@@ -812,4 +918,10 @@ extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params
             CPX_CHECK_LAUNCH();
         }
     return CPX_OK;
+}
+extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+                                   size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
+                                   size_t workspace_bytes, void *stream) {
+    return cpx_blocks_backward_ex(w, params, nS, first_block, fwd_workspace, fwd_workspace_bytes, dy0, CPX_DT_F32, grads, dx_all, workspace,
+                                  workspace_bytes, stream);
 }

@@ -4,7 +4,7 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
         --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
-        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K]
+        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K [--grad_precision bf16]]
     python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
         [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
@@ -130,6 +130,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "input rows of block depth - K; turns --train_neck on; not with a UNet class head.  --train_blocks 24 "
                         "--train_flow_head is what the reference trains without --freeze, except for the patch embedding and the "
                         "position table, which stay fixed")
+    p.add_argument("--grad_precision", default="fp32", choices=["fp32", "bf16"],
+                   help="with --train_blocks: bf16 runs the matrix products of the blocks' backward on bf16 operands with float32 "
+                        "accumulation (several times faster; gradients differ from the float32 backward by the operand rounding); "
+                        "needs --precision bf16.  The default fp32 is the exact float32 backward")
     p.add_argument("--freeze", nargs="+", default=None, choices=["none", "backbone", "segmentation_head", "neck"],
                    help="the reference's spelling of the same choice: 'backbone neck' = --train_flow_head, 'backbone "
                         "segmentation_head neck' = the default (class head only); nothing else is built")
@@ -168,6 +172,16 @@ def check_args(args) -> None:
     args.train_blocks = int(getattr(args, "train_blocks", 0) or 0)
     if args.train_blocks < 0:
         raise SystemExit("--train_blocks: a count of blocks, 0 for none")
+    args.grad_precision = getattr(args, "grad_precision", None) or "fp32"
+    if args.grad_precision == "bf16":
+        if not args.train_blocks:
+            raise SystemExit("--grad_precision bf16 goes with --train_blocks K: it is the backward of the trained transformer blocks "
+                             "(the neck's and the heads' gradients stay float32)")
+        precision = getattr(args, "precision", "bf16")
+        if precision == "fp16":
+            raise SystemExit("--grad_precision bf16 needs --precision bf16: fp16 gradients would need loss scaling, which is not built")
+        if precision != "bf16":
+            raise SystemExit(f"--grad_precision bf16 needs --precision bf16: a {precision} network has no half-precision operands")
     if args.train_blocks:
         if getattr(args, "feature_transformation_structure", None) is not None:
             raise SystemExit("--train_blocks: the blocks do not train under a UNet class head (its backward gives the neck output no "
@@ -287,7 +301,8 @@ def _trainer_of(args, make_trainer, nclasses):
         return make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
                             feature_transformation_structure=args.feature_transformation_structure,
                             class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
-                            train_neck=args.train_neck, train_blocks=args.train_blocks)
+                            train_neck=args.train_neck, train_blocks=args.train_blocks,
+                            **({"grad_precision": "bf16"} if getattr(args, "grad_precision", "fp32") == "bf16" else {}))
     except (ValueError, NotImplementedError) as e:
         if args.train_blocks and "train_blocks" in str(e):
             raise SystemExit(f"--train_blocks {args.train_blocks}: {e}")

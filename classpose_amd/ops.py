@@ -986,20 +986,34 @@ def blocks_forward_train(weights, x: torch.Tensor, first_block: int, head: torch
     return o
 
 
-def blocks_backward_workspace(n_subtiles: int, dtype_code: int, device) -> torch.Tensor:
-    n = _lib.lib().cpx_blocks_backward_workspace_bytes(n_subtiles, dtype_code)
+def _grad_dtype_code(grad_dtype, net_dtype_code: int, what: str) -> int:
+    """the ``grad_dtype`` argument of the blocks' backward -> its dtype code; bf16 gradients go with a bf16 network only"""
+    if grad_dtype == torch.float32:
+        return _DT[torch.float32]
+    if grad_dtype != torch.bfloat16:
+        raise ValueError(f"{what}: grad_dtype is torch.float32 or torch.bfloat16, not {grad_dtype}")
+    if net_dtype_code != _DT[torch.bfloat16]:
+        raise ValueError(f"{what}: grad_dtype torch.bfloat16 needs a bf16 network (fp16 gradients would need loss scaling; a float32 "
+                         "network has no half-precision operands)")
+    return _DT[torch.bfloat16]
+
+
+def blocks_backward_workspace(n_subtiles: int, dtype_code: int, device, grad_dtype=torch.float32) -> torch.Tensor:
+    n = _lib.lib().cpx_blocks_backward_workspace_bytes_ex(n_subtiles, dtype_code, _grad_dtype_code(grad_dtype, dtype_code, "blocks_backward_workspace"))
     if n == 0:
         raise ValueError("blocks_backward_workspace: invalid n_subtiles / dtype")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
 def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: torch.Tensor, grads: torch.Tensor | None = None,
-                    workspace: torch.Tensor | None = None, dx_all: torch.Tensor | None = None) -> torch.Tensor:
-    """``cpx_blocks_backward``: the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
+                    workspace: torch.Tensor | None = None, dx_all: torch.Tensor | None = None, grad_dtype=torch.float32) -> torch.Tensor:
+    """``cpx_blocks_backward_ex``: the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
     ``block_grad_layout``), from ``params`` (the K blocks' unfolded parameters as the forward reads them, same layout) and ``dy0``
     (rows, 256) float32, which ``neck_backward`` leaves in its workspace.  ``dx_all`` (K + 1, rows, 1024) float32, when given, receives
-    the gradient of every trained block's input and (last) of the last block's output."""
+    the gradient of every trained block's input and (last) of the last block's output.  ``grad_dtype`` torch.float32: the exact-float32
+    products of ``cpx_blocks_backward``; torch.bfloat16 (a bf16 network only): every product on bf16 operands with float32 accumulation."""
     c, L = weights.c, _lib.lib()
+    gd = _grad_dtype_code(grad_dtype, c.dtype, "blocks_backward")
     K, rows, dev = len(fwd.x), fwd.x_out.shape[0], fwd.x_out.device
     n_g, _off = block_grad_layout()
     if params.dtype != torch.float32 or params.numel() != n_g * K or not params.is_contiguous() or params.device != dev:
@@ -1014,12 +1028,46 @@ def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: t
                                or dx_all.device != dev):
         raise ValueError("blocks_backward: dx_all must be contiguous float32 (K + 1, rows, 1024)")
     if workspace is None:
-        workspace = blocks_backward_workspace(rows // 1024, c.dtype, dev)
+        workspace = blocks_backward_workspace(rows // 1024, c.dtype, dev, grad_dtype)
     if workspace.dtype != torch.uint8 or fwd.workspace.dtype != torch.uint8:
         raise ValueError("blocks_backward: workspaces are uint8 tensors")
-    check(L.cpx_blocks_backward(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
-                                ptr(grads), ptr(dx_all), ptr(workspace), workspace.numel(), _stream(dev)), "blocks_backward")
+    check(L.cpx_blocks_backward_ex(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
+                                   gd, ptr(grads), ptr(dx_all), ptr(workspace), workspace.numel(), _stream(dev)), "blocks_backward")
     return grads
+
+
+def gemm_tn_bf16(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None, add: bool = False) -> torch.Tensor:
+    """``cpx_gemm_tn_bf16``: a^T b for bf16 device matrices a (M, N) and b (M, K), float32 accumulation, into (or, with ``add``, on top
+    of) the float32 ``out`` (N, K) -- which may be a column slice of a wider contiguous matrix."""
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0] \
+            or not a.is_contiguous() or not b.is_contiguous() or not a.is_cuda or b.device != a.device:
+        raise ValueError("gemm_tn_bf16: a (M, N) and b (M, K) must be contiguous bf16 matrices on one device")
+    (M, N), K = a.shape, b.shape[1]
+    if out is None:
+        if add:
+            raise ValueError("gemm_tn_bf16: add needs an out to add to")
+        out = torch.empty((N, K), dtype=torch.float32, device=a.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (N, K) or out.stride(1) != 1 or out.device != a.device:
+        raise ValueError("gemm_tn_bf16: out must be float32 (N, K) with unit column stride on the operands' device")
+    check(_lib.lib().cpx_gemm_tn_bf16(ptr(a), ptr(b), M, N, K, int(bool(add)), ptr(out), out.stride(0), _stream(a.device)), "gemm_tn_bf16")
+    return out
+
+
+def colsum_add(dy: torch.Tensor, db: torch.Tensor, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """``cpx_colsum_add``: db += the column sums of the float32 (rows, N) ``dy``, float64 partial sums in a fixed tree, in place."""
+    if dy.dtype != torch.float32 or dy.dim() != 2 or not dy.is_contiguous() or not dy.is_cuda or db.dtype != torch.float32 \
+            or tuple(db.shape) != (dy.shape[1],) or not db.is_contiguous() or db.device != dy.device:
+        raise ValueError("colsum_add: dy (rows, N) and db (N,) must be contiguous float32 tensors on one device")
+    rows, N = dy.shape
+    n = _lib.lib().cpx_colsum_workspace_bytes(rows, N)
+    if n == 0:
+        raise ValueError("colsum_add: rows and N must be positive multiples of 64")
+    if workspace is None:
+        workspace = torch.empty(n, dtype=torch.uint8, device=dy.device)
+    if workspace.dtype != torch.uint8:
+        raise ValueError("colsum_add: the workspace is a uint8 tensor")
+    check(_lib.lib().cpx_colsum_add(ptr(dy), rows, N, ptr(db), ptr(workspace), workspace.numel(), _stream(dy.device)), "colsum_add")
+    return db
 
 
 # ---- t2: training-time augmentation (csrc/cpx_augment.hip) --------------------------------------------------------

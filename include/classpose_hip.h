@@ -654,6 +654,29 @@ int cpx_blocks_backward_slab_crops(void);
 int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
                         size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
                         size_t workspace_bytes, void *stream);
+/* Mixed-precision gradients for the trained blocks (additive, no ABI bump): grad_dtype CPX_DT_F32 is cpx_blocks_backward (which forwards
+ * here) bit for bit; CPX_DT_BF16 is accepted for a CPX_DT_BF16 network only (fp16 gradients would need loss scaling, a float32 network has
+ * no half operands: both are CPX_EINVAL).  In that mode every matrix product of the backward takes both operands rounded to bf16 (round to
+ * nearest even, each value once), accumulates in float32 on the bf16 MFMA and writes float32:
+ *   dW += bf16(dy)^T bf16(a)   da = bf16(dy) W   pre = bf16(xhat or xn) W1^T + b1   d x_out = bf16(dy0) W0
+ * with W the operand the forward multiplied by (exact in bf16, folded where the forward folds) and db += the column sums of the UNROUNDED
+ * float32 dy in float64.  Activation gradients stay float32 between the products; LayerNorm, GELU and attention backward, the unfolding
+ * of the folded gradients, the slabs and their order are those of the float32 mode; no atomics, bitwise reproducible.  The workspace is
+ * smaller (190 MiB against 241 MiB): it holds no transposed float32 operands.                                                         */
+size_t cpx_blocks_backward_workspace_bytes_ex(int n_subtiles, int dtype, int grad_dtype);
+int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
+                           size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, float *grads, float *dx_all, void *workspace,
+                           size_t workspace_bytes, void *stream);
+/* The weight-gradient product of that mode (csrc/cpx_gemm_tn.hip): out[n][k] (+)= sum_m A[m][n] B[m][k], A [M][N] and B [M][K] bf16 row-major
+ * (both operands are read transposed, by ds_read_b64_tr_b16: no transposing copy), out [N][ld_out] float32; add = 1 adds to what out
+ * holds, add = 0 overwrites.  Each element is one float32 accumulation over m in order.  Requires M % 64 == 0, N % 128 == 0, K % 128 == 0
+ * (all > 0), ld_out >= K, add 0 or 1, and A, B, out 16-byte aligned; anything else returns CPX_EINVAL and launches nothing.          */
+int cpx_gemm_tn_bf16(const void *A, const void *B, int M, int N, int K, int add, float *out, int ld_out, void *stream);
+/* db[c] += sum over rows of dy[row][c], dy [rows][N] float32: float64 partial sums in a fixed tree per column (chains over rows 4 apart,
+ * four chains per 64 rows, the 64-row partials in order), added to db and rounded once.  rows % 64 == 0, N % 64 == 0; workspace of
+ * cpx_colsum_workspace_bytes(rows, N) bytes (0 for an invalid shape), 8-byte aligned.                                                 */
+size_t cpx_colsum_workspace_bytes(int rows, int N);
+int cpx_colsum_add(const float *dy, int rows, int N, float *db, void *workspace, size_t workspace_bytes, void *stream);
 size_t cpx_layernorm_backward_bytes(int rows, int C);
 size_t cpx_attention_backward_workspace_bytes(int n_subtiles);
 int cpx_attention_backward(int dtype, const void *qkv, const void *rel_h, const void *rel_w, const void *O, const float *dO,

@@ -2,7 +2,9 @@
 rounds, medians (the set-up of tools/bench_train_neck.py, whose workload and eager tail this reuses).
 
     python tools/bench_train_blocks.py [--rounds 7] [--crops 32] [--out profiles/train_blocks_bench.txt]
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_train_blocks.py --profile-steps 3      (kernels of the cached K = 1 step only)
+    python tools/bench_train_blocks.py --grad_precision both --skip_eager --out profiles/train_blocks_bf16_bench.txt     
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_train_blocks.py --profile-steps 3 [--grad_precision bf16]
+                                                                                              (kernels of the cached K = 1 step only)
 
 Workload: `--crops` uint8 crops of 256^2 of the synthetic slide, a seeded ViT-L checkpoint with a fresh 7-class 1x1 head, bf16.
   (n)   HeadTrainer(train_neck=True).step from cached backbone rows: the neck-only step of the parent commit
@@ -12,6 +14,8 @@ Workload: `--crops` uint8 crops of 256^2 of the synthetic slide, a seeded ViT-L 
         on bf16 casts of float32 masters (scaled_dot_product_attention with the decomposed rel-pos bias as its mask), float32 losses,
         torch.optim.AdamW on the masters
   (p1)  (b1) from pixels: the frozen 23 blocks first
+  (g1) (g2) (g4)  with --grad_precision both: (bK) with grad_precision="bf16", the blocks' backward on bf16 operands, in the same
+        process and the same rounds; --grad_precision bf16 runs (bK) itself in that mode
 Every round times all of them, the order reversed in odd rounds.
 """
 import argparse
@@ -72,8 +76,12 @@ def main():
     ap.add_argument("--classes", type=int, default=7)
     ap.add_argument("--blocks", type=int, nargs="+", default=[1, 2, 4])
     ap.add_argument("--profile-steps", type=int, default=0, help="run this many cached K = 1 steps and exit (for rocprofv3)")
+    ap.add_argument("--grad_precision", default="fp32", choices=["fp32", "bf16", "both"],
+                    help="the blocks' backward of (bK): float32 products, bf16 operands, or both modes side by side ((bK) float32, (gK) bf16)")
+    ap.add_argument("--skip_eager", action="store_true", help="leave out the eager PyTorch steps (eK) and the step from pixels (p1)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    base_mode = "bf16" if args.grad_precision == "bf16" else "fp32"
     dev = torch.device("cuda:0")
     n, ncls = args.crops, args.classes
     backbone = synth.make_state_dict(1, None, depth=args.depth, seed=0)
@@ -84,7 +92,7 @@ def main():
     lr = 1e-4
     mk = lambda **kw: HeadTrainer(dict(backbone), nclasses=ncls, device=dev, precision="bf16", feature_batch=n, train_flow_head=True, **kw)
     if args.profile_steps:
-        t = mk(train_blocks=1)
+        t = mk(train_blocks=1, grad_precision=base_mode)
         rows = t.backbone_features(ims)
         for _ in range(args.profile_steps):
             t.step(rows, labs, lr, flow_targets=tg)
@@ -95,19 +103,25 @@ def main():
     rows_n = trn.backbone_features(ims)
     fns["n"], what["n"] = (lambda: trn.step(rows_n, labs, lr, flow_targets=tg)["loss"]), "step from cached backbone rows, neck + both heads (the parent commit's step)"
     for K in args.blocks:
-        t = mk(train_blocks=K)
+        t = mk(train_blocks=K, grad_precision=base_mode)
         rows = t.backbone_features(ims)
-        e = EagerBlocks(t, ncls, K)
         first_ev[K] = t.evaluate(rows, labs, flow_targets=tg)["loss"]
         fns[f"b{K}"] = (lambda t=t, rows=rows: t.step(rows, labs, lr, flow_targets=tg)["loss"])
-        what[f"b{K}"] = f"step from cached rows, last {K} block(s) + neck + both heads"
+        what[f"b{K}"] = f"step from cached rows, last {K} block(s) + neck + both heads, {base_mode} gradient products"
+        if args.grad_precision == "both":
+            t16 = mk(train_blocks=K, grad_precision="bf16")
+            fns[f"g{K}"] = (lambda t=t16, rows=rows: t.step(rows, labs, lr, flow_targets=tg)["loss"])
+            what[f"g{K}"] = "the same step with grad_precision bf16: the blocks' backward on bf16 operands"
+        if args.skip_eager:
+            continue
+        e = EagerBlocks(t, ncls, K)
         fns[f"e{K}"] = (lambda e=e, rows=rows: e(rows, labd, tg, lr))
         what[f"e{K}"] = f"eager PyTorch + autograd, last {K} block(s) + neck + both heads, the same cached rows"
         if K == args.blocks[0]:
             fns[f"p{K}"] = (lambda t=t: t.step(ims, labs, lr, flow_targets=tg)["loss"])
             what[f"p{K}"] = f"step from pixels, last {K} block(s) + neck + both heads (the frozen {args.depth - K} blocks first)"
     first = {k: f() for k, f in fns.items()}
-    for K in args.blocks:                                 # (the eager forward rounds where torch's bf16 kernels round: loose agreement only)
+    for K in () if args.skip_eager else args.blocks:      # (the eager forward rounds where torch's bf16 kernels round: loose agreement only)
         assert abs(first[f"e{K}"] - first_ev[K]) <= 5e-2 * abs(first_ev[K]), (K, first, first_ev)
     for f in fns.values():
         f()
@@ -124,7 +138,13 @@ def main():
              f"medians (ms); first losses {({k: round(v, 4) for k, v in first.items()})}"]
     for k in fns:
         lines.append(f"  ({k:2s}) {what[k]:96s} median {med[k]:10.3f}   min {min(times[k]):10.3f} max {max(times[k]):10.3f}   {[round(v, 1) for v in times[k]]}")
-    for K in args.blocks:
+    for K in args.blocks if args.grad_precision == "both" else ():
+        b, g = f"b{K}", f"g{K}"
+        order = "EVERY round of the bf16 mode lies below every round of the float32 mode" if max(times[g]) < min(times[b]) else \
+            "the rounds of the two modes OVERLAP"
+        lines.append(f"  K = {K}: ({b}) / ({g}) = {med[b] / med[g]:.2f}; ({g}) - (n) = {med[g] - med['n']:.1f} ms, {(med[g] - med['n']) / K:.1f} ms per "
+                     f"trained block (float32 mode {(med[b] - med['n']) / K:.1f}); {order}")
+    for K in () if args.skip_eager else args.blocks:
         b, e = f"b{K}", f"e{K}"
         verdict = "the device step is FASTER than eager PyTorch" if max(times[b]) < min(times[e]) else \
             ("the device step LOSES to eager PyTorch" if min(times[b]) > max(times[e]) else "the device step and eager PyTorch overlap: no call")
