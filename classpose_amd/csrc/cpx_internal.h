@@ -175,7 +175,25 @@ __device__ __forceinline__ double wave_sum(double x) {
     return x;               // every lane holds the same bits: a + b and b + a round alike
 }
 
-#define UW_SLAB 512                    // rows per slab of the weight gradients (k_wgrad, k_uwgrad) = longest serial accumulation chain L
+// the attention backward (cpx_train_blocks.hip float32, cpx_attn_bwd16.hip bf16 operands) -- one workspace layout for both:
+// m | 1 / l | delta [crops * 16 * 1024] float32, Bh | Bw | Gh | Gw [crops * 16 * 1024][32] float32, part float64
+struct AttnBwdLayout { size_t off_st[3], off_b[4], off_part, total; };
+static inline AttnBwdLayout cpx_attn_bwd_layout(int nS) {
+    AttnBwdLayout L; CpxArena a; const size_t n = (size_t)nS * 16 * 1024;
+    for (int i = 0; i < 3; ++i) L.off_st[i] = a.take(n * sizeof(float));
+    for (int i = 0; i < 4; ++i) L.off_b[i] = a.take(n * 32 * sizeof(float));
+    L.off_part = a.take((size_t)nS * 4 * 2 * 4096 * sizeof(double));
+    L.total = a.o;
+    return L;
+}
+// the table gradients from the row-group sums Gh, Gw of dS' (k_rel_grad, k_rel_finish); `add_rel`: on top of what drel_h / drel_w hold
+int cpx_attn_rel_grad_run(int dtype, const void *qkv, const float *Gh, const float *Gw, double *part, int nS, int add_rel, float *drel_h,
+                          float *drel_w, void *stream);
+// cpx_attention_backward_bf16 with `add_rel` (the blocks' backward runs a batch in slabs of crops, in order)
+int cpx_attention_backward_bf16_run(const void *qkv, const void *rel_h, const void *rel_w, const float *dO, int nS, float *dqkv, float *drel_h,
+                                    float *drel_w, int add_rel, void *workspace, size_t workspace_bytes, void *stream);
+
+#define UW_SLAB 512                   // rows per slab of the weight gradients (k_wgrad, k_uwgrad) = longest serial accumulation chain L
 
 // kernels of the UNet head's backward (cpx_train_unet.hip) that the neck's backward (cpx_train_neck.hip) runs too
 struct UwArgs {

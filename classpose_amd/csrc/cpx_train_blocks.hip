@@ -379,19 +379,21 @@ __global__ void __launch_bounds__(256) k_rel_finish(const double *__restrict__ p
     *out = (float)sum;
 }
 
-// workspace: m | 1 / l | delta [crops * 16 * 1024] float32, Bh | Bw | Gh | Gw [crops * 16 * 1024][32] float32, part float64
-struct AttnBwdLayout { size_t off_st[3], off_b[4], off_part, total; };
-static AttnBwdLayout attn_bwd_layout(int nS) {
-    AttnBwdLayout L; CpxArena a; const size_t n = (size_t)nS * 16 * 1024;
-    for (int i = 0; i < 3; ++i) L.off_st[i] = a.take(n * sizeof(float));
-    for (int i = 0; i < 4; ++i) L.off_b[i] = a.take(n * 32 * sizeof(float));
-    L.off_part = a.take((size_t)nS * 4 * 2 * 4096 * sizeof(double));
-    L.total = a.o;
-    return L;
+int cpx_attn_rel_grad_run(int dtype, const void *qkv, const float *Gh, const float *Gw, double *part, int nS, int add_rel, float *drel_h,
+                          float *drel_w, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 block(256);
+    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_rel_grad<DT>, dim3(63, 2, nS * 4), block, 0, s, qkv, Gh, Gw, part));
+    CPX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_rel_finish, dim3(32), block, 0, s, part, nS * 4, add_rel, drel_h, drel_w);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
 }
+
+// workspace: cpx_attn_bwd_layout (cpx_internal.h)
 extern "C" size_t cpx_attention_backward_workspace_bytes(int n_subtiles) {
     if (n_subtiles <= 0 || n_subtiles > 16383) return 0;              // blockIdx.z = 4 * crops in k_rel_grad
-    return attn_bwd_layout(n_subtiles).total;
+    return cpx_attn_bwd_layout(n_subtiles).total;
 }
 
 // `add_rel`: drel_h / drel_w receive their sums on top of what they hold (the caller runs a batch in slabs of crops, in order)
@@ -401,7 +403,7 @@ int cpx_attention_backward_run(int dtype, const void *qkv, const void *rel_h, co
     CPX_REQUIRE(qkv && rel_h && rel_w && dO && dqkv && drel_h && drel_w && workspace && dtype_ok(dtype));
     (void)O;                                   // not read: delta comes from the recomputed P (k_attn_bwd_dq, pass 1)
     CPX_REQUIRE(nS > 0 && nS <= 16383);
-    const AttnBwdLayout L = attn_bwd_layout(nS);
+    const AttnBwdLayout L = cpx_attn_bwd_layout(nS);
     CPX_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0);
     CPX_REQUIRE((((uintptr_t)qkv | (uintptr_t)rel_h | (uintptr_t)rel_w | (uintptr_t)O | (uintptr_t)dO | (uintptr_t)dqkv) & 15) == 0);
     char *ws = (char *)workspace;
@@ -414,11 +416,7 @@ int cpx_attention_backward_run(int dtype, const void *qkv, const void *rel_h, co
     CPX_CHECK_LAUNCH();
     CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_attn_bwd_dkv<DT>, grid, block, 0, s, qkv, dO, st_m, st_il, st_dl, Bh, Bw, dqkv));
     CPX_CHECK_LAUNCH();
-    CPX_DT_DISPATCH(dtype, DT, hipLaunchKernelGGL(k_rel_grad<DT>, dim3(63, 2, nS * 4), block, 0, s, qkv, Gh, Gw, part));
-    CPX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_rel_finish, dim3(32), block, 0, s, part, nS * 4, add_rel, drel_h, drel_w);
-    CPX_CHECK_LAUNCH();
-    return CPX_OK;
+    return cpx_attn_rel_grad_run(dtype, qkv, Gh, Gw, part, nS, add_rel, drel_h, drel_w, stream);
 }
 extern "C" int cpx_attention_backward(int dtype, const void *qkv, const void *rel_h, const void *rel_w, const void *O, const float *dO,
                                       int n_subtiles, float *dqkv, float *drel_h, float *drel_w, void *workspace, size_t workspace_bytes,
@@ -753,9 +751,17 @@ static BlocksBwdLayout blocks_bwd_layout(int grad_dtype) {
     return L;
 }
 static bool grad_dtype_ok(int dtype, int grad_dtype) { return grad_dtype == CPX_DT_F32 || (grad_dtype == CPX_DT_BF16 && dtype == CPX_DT_BF16); }
-extern "C" size_t cpx_blocks_backward_workspace_bytes_ex(int nS, int dtype, int grad_dtype) {
-    if (nS <= 0 || !dtype_ok(dtype) || !grad_dtype_ok(dtype, grad_dtype)) return 0;
+// attn_grad_dtype CPX_DT_BF16 (the attention backward on bf16 operands, cpx_attention_backward_bf16) goes with bf16 gradient GEMMs only
+static bool attn_grad_dtype_ok(int grad_dtype, int attn_grad_dtype) {
+    return attn_grad_dtype == CPX_DT_F32 || (attn_grad_dtype == CPX_DT_BF16 && grad_dtype == CPX_DT_BF16);
+}
+// (the two attention backwards share one workspace layout, so attn_grad_dtype does not change the size)
+extern "C" size_t cpx_blocks_backward_workspace_bytes_mp(int nS, int dtype, int grad_dtype, int attn_grad_dtype) {
+    if (nS <= 0 || !dtype_ok(dtype) || !grad_dtype_ok(dtype, grad_dtype) || !attn_grad_dtype_ok(grad_dtype, attn_grad_dtype)) return 0;
     return blocks_bwd_layout(grad_dtype).total;
+}
+extern "C" size_t cpx_blocks_backward_workspace_bytes_ex(int nS, int dtype, int grad_dtype) {
+    return cpx_blocks_backward_workspace_bytes_mp(nS, dtype, grad_dtype, CPX_DT_F32);
 }
 extern "C" size_t cpx_blocks_backward_workspace_bytes(int nS, int dtype) { return cpx_blocks_backward_workspace_bytes_ex(nS, dtype, CPX_DT_F32); }
 extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
@@ -772,13 +778,17 @@ extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
 // recomputed pre-activation bf16(xhat or xn) W1^T + b1 on cpx_gemm_half with the float32 epilogue, W the forward's own operand (exact in
 // bf16; for da a transposed 2-byte copy) --, and db takes the column sums of the unrounded dy from cpx_colsum_add.  Everything between
 // the products is the float32 / float64 code of the float32 mode, with the same slabs.
-extern "C" int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
-                                      size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, float *grads, float *dx_all,
-                                      void *workspace, size_t workspace_bytes, void *stream) {
+//
+// attn_grad_dtype CPX_DT_BF16 (with grad_dtype CPX_DT_BF16 only): the attention backward is cpx_attention_backward_bf16 (cpx_attn_bwd16.hip)
+// in place of the float32 one; CPX_DT_F32 is cpx_blocks_backward_ex, launch for launch.
+extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+                                      size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,
+                                      float *dx_all, void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(blocks_weights_ok(w, first_block) && params && fwd_workspace && dy0 && grads && workspace && w->neck0_w);
     CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block) && grad_dtype_ok(w->dtype, grad_dtype));
+    CPX_REQUIRE(attn_grad_dtype_ok(grad_dtype, attn_grad_dtype));
     const int dt = w->dtype, K = w->depth - first_block;
-    const bool g16 = grad_dtype == CPX_DT_BF16;
+    const bool g16 = grad_dtype == CPX_DT_BF16, a16 = attn_grad_dtype == CPX_DT_BF16;
     const BlocksFwdLayout F = blocks_fwd_layout(nS, dt, K);
     const BlocksBwdLayout L = blocks_bwd_layout(grad_dtype);
     CPX_REQUIRE(fwd_workspace_bytes >= F.total && workspace_bytes >= L.total);
@@ -891,7 +901,8 @@ extern "C" int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *par
             // ---- attention: x_mid = x_in + attention(LN1(x_in) Wqkv^T + bqkv) Wp^T + bp ----
             if (g16) CPX_RUN(linear_bwd16(dx, ao, b.proj_w, Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                       // proj -> dO (ao is stored in bf16)
             else CPX_RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
-            CPX_RUN(cpx_attention_backward_run(dt, qkv, b.rel_h, b.rel_w, nullptr, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
+            if (a16) CPX_RUN(cpx_attention_backward_bf16_run(qkv, b.rel_h, b.rel_w, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
+            else CPX_RUN(cpx_attention_backward_run(dt, qkv, b.rel_h, b.rel_w, nullptr, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
             if (g16) {
                 if (fuse) CPX_RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
                 else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, true));
@@ -918,6 +929,12 @@ extern "C" int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *par
             CPX_CHECK_LAUNCH();
         }
     return CPX_OK;
+}
+extern "C" int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+                                      size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, float *grads, float *dx_all,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    return cpx_blocks_backward_mp(w, params, nS, first_block, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, CPX_DT_F32, grads, dx_all,
+                                  workspace, workspace_bytes, stream);
 }
 extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                    size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,

@@ -4,7 +4,7 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
         --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
-        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K [--grad_precision bf16]]
+        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K [--grad_precision bf16 [--attn_grad_precision bf16]]]
     python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
         [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
@@ -134,6 +134,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --train_blocks: bf16 runs the matrix products of the blocks' backward on bf16 operands with float32 "
                         "accumulation (several times faster; gradients differ from the float32 backward by the operand rounding); "
                         "needs --precision bf16.  The default fp32 is the exact float32 backward")
+    p.add_argument("--attn_grad_precision", default="fp32", choices=["fp32", "bf16"],
+                   help="with --grad_precision bf16: bf16 runs the attention backward of the trained blocks on bf16 operands as well "
+                        "(dO, P and dS' rounded once, float32 accumulation).  The default fp32 keeps it in float32")
     p.add_argument("--freeze", nargs="+", default=None, choices=["none", "backbone", "segmentation_head", "neck"],
                    help="the reference's spelling of the same choice: 'backbone neck' = --train_flow_head, 'backbone "
                         "segmentation_head neck' = the default (class head only); nothing else is built")
@@ -182,6 +185,10 @@ def check_args(args) -> None:
             raise SystemExit("--grad_precision bf16 needs --precision bf16: fp16 gradients would need loss scaling, which is not built")
         if precision != "bf16":
             raise SystemExit(f"--grad_precision bf16 needs --precision bf16: a {precision} network has no half-precision operands")
+    args.attn_grad_precision = getattr(args, "attn_grad_precision", None) or "fp32"
+    if args.attn_grad_precision == "bf16" and args.grad_precision != "bf16":
+        raise SystemExit("--attn_grad_precision bf16 needs --grad_precision bf16: it is the last float32 product of the bf16 backward of "
+                         "the trained blocks, not a mode of the float32 backward")
     if args.train_blocks:
         if getattr(args, "feature_transformation_structure", None) is not None:
             raise SystemExit("--train_blocks: the blocks do not train under a UNet class head (its backward gives the neck output no "
@@ -302,7 +309,8 @@ def _trainer_of(args, make_trainer, nclasses):
                             feature_transformation_structure=args.feature_transformation_structure,
                             class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
                             train_neck=args.train_neck, train_blocks=args.train_blocks,
-                            **({"grad_precision": "bf16"} if getattr(args, "grad_precision", "fp32") == "bf16" else {}))
+                            **({"grad_precision": "bf16"} if getattr(args, "grad_precision", "fp32") == "bf16" else {}),
+                            **({"attn_grad_precision": "bf16"} if getattr(args, "attn_grad_precision", "fp32") == "bf16" else {}))
     except (ValueError, NotImplementedError) as e:
         if args.train_blocks and "train_blocks" in str(e):
             raise SystemExit(f"--train_blocks {args.train_blocks}: {e}")

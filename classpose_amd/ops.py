@@ -883,11 +883,17 @@ def attention_backward_workspace(n_subtiles: int, device) -> torch.Tensor:
 
 
 def attention_backward(qkv: torch.Tensor, rel_h: torch.Tensor, rel_w: torch.Tensor, out: torch.Tensor, dout: torch.Tensor,
-                       workspace: torch.Tensor | None = None):
+                       workspace: torch.Tensor | None = None, grad_dtype=torch.float32):
     """``cpx_attention_backward``: (dqkv (rows, 3072), drel_h (64, 64), drel_w (64, 64)), all float32, of the function
     ``attention(qkv.float(), rel_h.float(), rel_w.float())`` computes, from the stored ``qkv`` (n * 1024, 3072) and attention output
     ``out`` (n * 1024, 1024) in the network dtype, the operand tables (64, 64) of that dtype (rel_pos / scale, zero last row) and
-    ``dout`` (n * 1024, 1024) float32.  The table gradients are with respect to the operand tables, summed over heads and crops."""
+    ``dout`` (n * 1024, 1024) float32.  The table gradients are with respect to the operand tables, summed over heads and crops.
+    ``grad_dtype`` torch.bfloat16 (bf16 tensors only): ``cpx_attention_backward_bf16``, every product on bf16 operands -- ``dout``, P and
+    dS' rounded once -- with float32 accumulation; ``out`` is not read in either mode."""
+    if grad_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"attention_backward: grad_dtype is torch.float32 or torch.bfloat16, not {grad_dtype}")
+    if grad_dtype == torch.bfloat16 and qkv.dtype != torch.bfloat16:
+        raise ValueError("attention_backward: grad_dtype torch.bfloat16 needs bf16 qkv (the operands are the stored values)")
     rows, dev = qkv.shape[0], qkv.device
     if qkv.dim() != 2 or qkv.shape[1] != 3072 or rows == 0 or rows % 1024 or qkv.dtype not in _DT or not qkv.is_contiguous() or not qkv.is_cuda:
         raise ValueError("attention_backward: qkv must be contiguous device rows (n * 1024, 3072) of bf16 / fp16 / fp32")
@@ -902,6 +908,10 @@ def attention_backward(qkv: torch.Tensor, rel_h: torch.Tensor, rel_w: torch.Tens
         raise ValueError("attention_backward: the workspace is a uint8 tensor")
     dqkv = torch.empty((rows, 3072), dtype=torch.float32, device=dev)
     drh, drw = torch.empty((64, 64), dtype=torch.float32, device=dev), torch.empty((64, 64), dtype=torch.float32, device=dev)
+    if grad_dtype == torch.bfloat16:
+        check(_lib.lib().cpx_attention_backward_bf16(ptr(qkv), ptr(rel_h), ptr(rel_w), ptr(dout), rows // 1024, ptr(dqkv), ptr(drh), ptr(drw),
+                                                     ptr(workspace), workspace.numel(), _stream(dev)), "attention_backward")
+        return dqkv, drh, drw
     check(_lib.lib().cpx_attention_backward(_DT[qkv.dtype], ptr(qkv), ptr(rel_h), ptr(rel_w), ptr(out), ptr(dout), rows // 1024, ptr(dqkv),
                                             ptr(drh), ptr(drw), ptr(workspace), workspace.numel(), _stream(dev)), "attention_backward")
     return dqkv, drh, drw
@@ -998,22 +1008,38 @@ def _grad_dtype_code(grad_dtype, net_dtype_code: int, what: str) -> int:
     return _DT[torch.bfloat16]
 
 
-def blocks_backward_workspace(n_subtiles: int, dtype_code: int, device, grad_dtype=torch.float32) -> torch.Tensor:
-    n = _lib.lib().cpx_blocks_backward_workspace_bytes_ex(n_subtiles, dtype_code, _grad_dtype_code(grad_dtype, dtype_code, "blocks_backward_workspace"))
+def _attn_grad_dtype_code(attn_grad_dtype, grad_dtype_code: int, what: str) -> int:
+    """the ``attn_grad_dtype`` argument of the blocks' backward -> its dtype code; a bf16 attention backward goes with bf16 gradient GEMMs only"""
+    if attn_grad_dtype == torch.float32:
+        return _DT[torch.float32]
+    if attn_grad_dtype != torch.bfloat16:
+        raise ValueError(f"{what}: attn_grad_dtype is torch.float32 or torch.bfloat16, not {attn_grad_dtype}")
+    if grad_dtype_code != _DT[torch.bfloat16]:
+        raise ValueError(f"{what}: attn_grad_dtype torch.bfloat16 needs grad_dtype torch.bfloat16")
+    return _DT[torch.bfloat16]
+
+
+def blocks_backward_workspace(n_subtiles: int, dtype_code: int, device, grad_dtype=torch.float32, attn_grad_dtype=torch.float32) -> torch.Tensor:
+    gd = _grad_dtype_code(grad_dtype, dtype_code, "blocks_backward_workspace")
+    n = _lib.lib().cpx_blocks_backward_workspace_bytes_mp(n_subtiles, dtype_code, gd, _attn_grad_dtype_code(attn_grad_dtype, gd, "blocks_backward_workspace"))
     if n == 0:
         raise ValueError("blocks_backward_workspace: invalid n_subtiles / dtype")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
 def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: torch.Tensor, grads: torch.Tensor | None = None,
-                    workspace: torch.Tensor | None = None, dx_all: torch.Tensor | None = None, grad_dtype=torch.float32) -> torch.Tensor:
-    """``cpx_blocks_backward_ex``: the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
+                    workspace: torch.Tensor | None = None, dx_all: torch.Tensor | None = None, grad_dtype=torch.float32,
+                    attn_grad_dtype=torch.float32) -> torch.Tensor:
+    """``cpx_blocks_backward_mp``: the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
     ``block_grad_layout``), from ``params`` (the K blocks' unfolded parameters as the forward reads them, same layout) and ``dy0``
     (rows, 256) float32, which ``neck_backward`` leaves in its workspace.  ``dx_all`` (K + 1, rows, 1024) float32, when given, receives
     the gradient of every trained block's input and (last) of the last block's output.  ``grad_dtype`` torch.float32: the exact-float32
-    products of ``cpx_blocks_backward``; torch.bfloat16 (a bf16 network only): every product on bf16 operands with float32 accumulation."""
+    products of ``cpx_blocks_backward``; torch.bfloat16 (a bf16 network only): every product on bf16 operands with float32 accumulation.
+    ``attn_grad_dtype`` torch.bfloat16 (with ``grad_dtype`` torch.bfloat16 only): the attention backward on bf16 operands too
+    (``cpx_attention_backward_bf16``); torch.float32 leaves it in float32."""
     c, L = weights.c, _lib.lib()
     gd = _grad_dtype_code(grad_dtype, c.dtype, "blocks_backward")
+    ad = _attn_grad_dtype_code(attn_grad_dtype, gd, "blocks_backward")
     K, rows, dev = len(fwd.x), fwd.x_out.shape[0], fwd.x_out.device
     n_g, _off = block_grad_layout()
     if params.dtype != torch.float32 or params.numel() != n_g * K or not params.is_contiguous() or params.device != dev:
@@ -1028,11 +1054,11 @@ def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: t
                                or dx_all.device != dev):
         raise ValueError("blocks_backward: dx_all must be contiguous float32 (K + 1, rows, 1024)")
     if workspace is None:
-        workspace = blocks_backward_workspace(rows // 1024, c.dtype, dev, grad_dtype)
+        workspace = blocks_backward_workspace(rows // 1024, c.dtype, dev, grad_dtype, attn_grad_dtype)
     if workspace.dtype != torch.uint8 or fwd.workspace.dtype != torch.uint8:
         raise ValueError("blocks_backward: workspaces are uint8 tensors")
-    check(L.cpx_blocks_backward_ex(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
-                                   gd, ptr(grads), ptr(dx_all), ptr(workspace), workspace.numel(), _stream(dev)), "blocks_backward")
+    check(L.cpx_blocks_backward_mp(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
+                                   gd, ad, ptr(grads), ptr(dx_all), ptr(workspace), workspace.numel(), _stream(dev)), "blocks_backward")
     return grads
 
 

@@ -349,7 +349,7 @@ class HeadTrainer:
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
                  head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, train_flow_head: bool = False,
-                 train_neck: bool = False, train_blocks: int = 0, grad_precision: str = "fp32"):
+                 train_neck: bool = False, train_blocks: int = 0, grad_precision: str = "fp32", attn_grad_precision: str = "fp32"):
         self.device = torch.device(device)
         self.train_blocks = int(train_blocks)
         if self.train_blocks < 0:
@@ -358,6 +358,9 @@ class HeadTrainer:
         # ``refresh`` and the checkpoint are what they are in "fp32"
         check_grad_precision(grad_precision, self.train_blocks, precision)
         self.grad_precision = grad_precision
+        # ``attn_grad_precision`` = "bf16" (with ``grad_precision`` "bf16"): the attention backward on bf16 operands too
+        check_attn_grad_precision(attn_grad_precision, grad_precision)
+        self.attn_grad_precision = attn_grad_precision
         train_neck = bool(train_neck) or self.train_blocks > 0           # the blocks' gradient comes through the neck
         if self.device.type != "cuda":
             raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
@@ -498,12 +501,14 @@ class HeadTrainer:
         rows, c = fwd.x_out.shape[0], self.weights.c
         key = ("blk_bwd", rows)
         grad_dtype = torch.bfloat16 if self.grad_precision == "bf16" else torch.float32
+        attn_grad_dtype = torch.bfloat16 if self.attn_grad_precision == "bf16" else torch.float32
         if key not in self._buf:
-            self._buf[key] = ops.blocks_backward_workspace(rows // TOKENS, c.dtype, self.device, grad_dtype)
+            self._buf[key] = ops.blocks_backward_workspace(rows // TOKENS, c.dtype, self.device, grad_dtype, attn_grad_dtype)
         nws = self._buf[("neck_bwd", rows)][1]
         off = ops.neck_backward_workspace_offsets(rows // TOKENS, c.dtype, c.ld_head)[3]
         dy0 = nws[off:off + rows * 256 * 4].view(torch.float32).view(rows, 256)
-        ops.blocks_backward(self.weights, self.blocks.rounded, fwd, dy0, self.blocks.grads, self._buf[key], grad_dtype=grad_dtype)
+        ops.blocks_backward(self.weights, self.blocks.rounded, fwd, dy0, self.blocks.grads, self._buf[key], grad_dtype=grad_dtype,
+                            attn_grad_dtype=attn_grad_dtype)
         self.blocks.finish_backward()
 
     def _as_rows(self, X, width: int, what: str) -> torch.Tensor:
@@ -658,6 +663,16 @@ def check_grad_precision(grad_precision: str, train_blocks: int, precision: str)
             raise ValueError("grad_precision bf16 needs precision bf16: fp16 gradients would need loss scaling, which is not built")
         if precision != "bf16":
             raise ValueError(f"grad_precision bf16 needs precision bf16: a {precision} network has no half-precision operands")
+
+
+def check_attn_grad_precision(attn_grad_precision: str, grad_precision: str) -> None:
+    """``attn_grad_precision`` "bf16" (the attention backward on bf16 operands) goes with ``grad_precision`` "bf16" only -- which
+    ``check_grad_precision`` ties to trained blocks of a bf16 network; raises ``ValueError`` with the reason otherwise."""
+    if attn_grad_precision not in ("fp32", "bf16"):
+        raise ValueError(f"attn_grad_precision: 'fp32' or 'bf16', not {attn_grad_precision!r}")
+    if attn_grad_precision == "bf16" and grad_precision != "bf16":
+        raise ValueError("attn_grad_precision bf16 needs grad_precision bf16: it is the last float32 product of the bf16 backward of the "
+                         "trained blocks, not a mode of the float32 backward")
 
 
 def make_trainer(pretrained_model, nclasses: int | None = None, feature_transformation_structure=None, **kw):

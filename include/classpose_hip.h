@@ -683,6 +683,33 @@ int cpx_attention_backward(int dtype, const void *qkv, const void *rel_h, const 
                            int n_subtiles, float *dqkv, float *drel_h, float *drel_w, void *workspace, size_t workspace_bytes,
                            void *stream);
 int cpx_gelu_backward(const float *pre, const float *dh, size_t n, float *dpre, void *stream);
+/* The attention backward of a bf16 network on bf16 operands (csrc/cpx_attn_bwd16.hip; additive, no ABI bump).  qkv [rows][3072], rel_h,
+ * rel_w [64][64] are bf16 (CPX_DT_BF16 is the only element type: there is no dtype argument), dO [rows][1024] float32; outputs float32
+ * dqkv [rows][3072], drel_h, drel_w [64][64].  With q, k, v, Rh, Rw as stored (exact) and r(.) = round to nearest even to bf16, each
+ * value once:
+ *   S'    = q . (k + Rh[qy - ky + 31] + Rw[qx - kx + 31])    bf16 MFMA, float32 accumulation, nothing rounded
+ *   P     = softmax_j(scale S')                              float32, exponent (S' - m) * scale, times 1 / l before any rounding
+ *   dP    = r(dO) v^T                                        r(dO) is the only form in which dO enters anything
+ *   delta = sum_j P dP                                       float32, from the unrounded P and dP (not from the stored O)
+ *   dS'   = scale P (dP - delta)                             float32
+ *   dv    = r(P)^T r(dO)      dk = r(dS')^T q
+ *   dq    = r(dS') k + sum_ky r(G_h) Rh[..] + sum_kx r(G_w) Rw[..],   G_h, G_w = the row-group sums of the unrounded float32 dS'
+ *   dRh, dRw = cpx_attention_backward's table gradients on the float32 G_h, G_w and q (float64 partials, crop order, row 63 zero)
+ * Every product accumulates in float32 on v_mfma_f32_32x32x16_bf16; no floating-point atomics, no workgroup waits for another, every sum
+ * in a fixed order: two runs are bitwise equal.  The workspace has cpx_attention_backward's size.  Null pointers, qkv / rel_h / rel_w /
+ * dO / dqkv not 16-byte aligned, a workspace not 256-byte aligned or too short, n_subtiles outside 1 .. 16383: CPX_EINVAL, nothing is
+ * launched.
+ * cpx_blocks_backward_mp: cpx_blocks_backward_ex with the precision of the attention backward as a third switch.  attn_grad_dtype
+ * CPX_DT_F32 is cpx_blocks_backward_ex (which forwards here): the same launches, the same workspace size.  CPX_DT_BF16 runs
+ * cpx_attention_backward_bf16 in its place and needs grad_dtype CPX_DT_BF16 (hence a bf16 network); every other combination is
+ * CPX_EINVAL (workspace bytes 0) before anything is launched.                                                                       */
+size_t cpx_attention_backward_bf16_workspace_bytes(int n_subtiles);
+int cpx_attention_backward_bf16(const void *qkv, const void *rel_h, const void *rel_w, const float *dO, int n_subtiles, float *dqkv,
+                                float *drel_h, float *drel_w, void *workspace, size_t workspace_bytes, void *stream);
+size_t cpx_blocks_backward_workspace_bytes_mp(int n_subtiles, int dtype, int grad_dtype, int attn_grad_dtype);
+int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
+                           size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads, float *dx_all,
+                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)

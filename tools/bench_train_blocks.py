@@ -3,7 +3,8 @@ rounds, medians (the set-up of tools/bench_train_neck.py, whose workload and eag
 
     python tools/bench_train_blocks.py [--rounds 7] [--crops 32] [--out profiles/train_blocks_bench.txt]
     python tools/bench_train_blocks.py --grad_precision both --skip_eager --out profiles/train_blocks_bf16_bench.txt     
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_train_blocks.py --profile-steps 3 [--grad_precision bf16]
+    python tools/bench_train_blocks.py --grad_precision all --skip_eager --out profiles/train_blocks_attn_bf16_bench.txt  
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_train_blocks.py --profile-steps 3 [--grad_precision bf16 [--attn_grad_precision bf16] | --grad_precision all]
                                                                                               (kernels of the cached K = 1 step only)
 
 Workload: `--crops` uint8 crops of 256^2 of the synthetic slide, a seeded ViT-L checkpoint with a fresh 7-class 1x1 head, bf16.
@@ -16,6 +17,8 @@ Workload: `--crops` uint8 crops of 256^2 of the synthetic slide, a seeded ViT-L 
   (p1)  (b1) from pixels: the frozen 23 blocks first
   (g1) (g2) (g4)  with --grad_precision both: (bK) with grad_precision="bf16", the blocks' backward on bf16 operands, in the same
         process and the same rounds; --grad_precision bf16 runs (bK) itself in that mode
+  (a1) (a2) (a4)  with --grad_precision all: (gK) and, third, the same step with attn_grad_precision="bf16" as well -- the attention
+        backward on bf16 operands; --profile-steps with "all" runs its steps in each of the three modes, one after another
 Every round times all of them, the order reversed in odd rounds.
 """
 import argparse
@@ -76,12 +79,18 @@ def main():
     ap.add_argument("--classes", type=int, default=7)
     ap.add_argument("--blocks", type=int, nargs="+", default=[1, 2, 4])
     ap.add_argument("--profile-steps", type=int, default=0, help="run this many cached K = 1 steps and exit (for rocprofv3)")
-    ap.add_argument("--grad_precision", default="fp32", choices=["fp32", "bf16", "both"],
-                    help="the blocks' backward of (bK): float32 products, bf16 operands, or both modes side by side ((bK) float32, (gK) bf16)")
+    ap.add_argument("--grad_precision", default="fp32", choices=["fp32", "bf16", "both", "all"],
+                    help="the blocks' backward of (bK): float32 products, bf16 operands, both modes side by side ((bK) float32, (gK) bf16), or "
+                         "all three ((aK): bf16 operands in the attention backward as well)")
+    ap.add_argument("--attn_grad_precision", default="fp32", choices=["fp32", "bf16"],
+                    help="with --grad_precision bf16: the attention backward of (bK) and of the --profile-steps run on bf16 operands too")
     ap.add_argument("--skip_eager", action="store_true", help="leave out the eager PyTorch steps (eK) and the step from pixels (p1)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     base_mode = "bf16" if args.grad_precision == "bf16" else "fp32"
+    if args.attn_grad_precision == "bf16" and args.grad_precision != "bf16":
+        ap.error("--attn_grad_precision bf16 goes with --grad_precision bf16 (--grad_precision all times it as (aK))")
+    base_kw = dict(grad_precision=base_mode, attn_grad_precision=args.attn_grad_precision)
     dev = torch.device("cuda:0")
     n, ncls = args.crops, args.classes
     backbone = synth.make_state_dict(1, None, depth=args.depth, seed=0)
@@ -92,26 +101,34 @@ def main():
     lr = 1e-4
     mk = lambda **kw: HeadTrainer(dict(backbone), nclasses=ncls, device=dev, precision="bf16", feature_batch=n, train_flow_head=True, **kw)
     if args.profile_steps:
-        t = mk(train_blocks=1, grad_precision=base_mode)
-        rows = t.backbone_features(ims)
-        for _ in range(args.profile_steps):
-            t.step(rows, labs, lr, flow_targets=tg)
-        torch.cuda.synchronize()
+        modes = [base_kw] if args.grad_precision != "all" else \
+            [dict(grad_precision="fp32"), dict(grad_precision="bf16"), dict(grad_precision="bf16", attn_grad_precision="bf16")]
+        for mode in modes:
+            t = mk(train_blocks=1, **mode)
+            rows = t.backbone_features(ims)
+            for _ in range(args.profile_steps):
+                t.step(rows, labs, lr, flow_targets=tg)
+            torch.cuda.synchronize()
         return
     fns, what, first_ev = {}, {}, {}
     trn = mk(train_neck=True)
     rows_n = trn.backbone_features(ims)
     fns["n"], what["n"] = (lambda: trn.step(rows_n, labs, lr, flow_targets=tg)["loss"]), "step from cached backbone rows, neck + both heads (the parent commit's step)"
     for K in args.blocks:
-        t = mk(train_blocks=K, grad_precision=base_mode)
+        t = mk(train_blocks=K, **base_kw)
         rows = t.backbone_features(ims)
         first_ev[K] = t.evaluate(rows, labs, flow_targets=tg)["loss"]
         fns[f"b{K}"] = (lambda t=t, rows=rows: t.step(rows, labs, lr, flow_targets=tg)["loss"])
-        what[f"b{K}"] = f"step from cached rows, last {K} block(s) + neck + both heads, {base_mode} gradient products"
-        if args.grad_precision == "both":
+        what[f"b{K}"] = f"step from cached rows, last {K} block(s) + neck + both heads, {base_mode} gradient products" + \
+            (", bf16 attention backward" if args.attn_grad_precision == "bf16" else "")
+        if args.grad_precision in ("both", "all"):
             t16 = mk(train_blocks=K, grad_precision="bf16")
             fns[f"g{K}"] = (lambda t=t16, rows=rows: t.step(rows, labs, lr, flow_targets=tg)["loss"])
             what[f"g{K}"] = "the same step with grad_precision bf16: the blocks' backward on bf16 operands"
+        if args.grad_precision == "all":
+            ta = mk(train_blocks=K, grad_precision="bf16", attn_grad_precision="bf16")
+            fns[f"a{K}"] = (lambda t=ta, rows=rows: t.step(rows, labs, lr, flow_targets=tg)["loss"])
+            what[f"a{K}"] = "the same step with attn_grad_precision bf16 as well: the attention backward on bf16 operands"
         if args.skip_eager:
             continue
         e = EagerBlocks(t, ncls, K)
@@ -138,7 +155,13 @@ def main():
              f"medians (ms); first losses {({k: round(v, 4) for k, v in first.items()})}"]
     for k in fns:
         lines.append(f"  ({k:2s}) {what[k]:96s} median {med[k]:10.3f}   min {min(times[k]):10.3f} max {max(times[k]):10.3f}   {[round(v, 1) for v in times[k]]}")
-    for K in args.blocks if args.grad_precision == "both" else ():
+    for K in args.blocks if args.grad_precision == "all" else ():
+        g, a = f"g{K}", f"a{K}"
+        order = "EVERY round of the bf16 attention backward lies below every round of grad_precision bf16 alone" if max(times[a]) < min(times[g]) else \
+            "the rounds of the two modes OVERLAP"
+        lines.append(f"  K = {K}: ({g}) / ({a}) = {med[g] / med[a]:.2f}; ({g}) - ({a}) = {(med[g] - med[a]) / K:.1f} ms per trained block; ({a}) - (n) = "
+                     f"{(med[a] - med['n']) / K:.1f} ms per trained block; {order}")
+    for K in args.blocks if args.grad_precision in ("both", "all") else ():
         b, g = f"b{K}", f"g{K}"
         order = "EVERY round of the bf16 mode lies below every round of the float32 mode" if max(times[g]) < min(times[b]) else \
             "the rounds of the two modes OVERLAP"
