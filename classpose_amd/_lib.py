@@ -185,6 +185,10 @@ SIGNATURES = {
     "cpx_attention_backward_bf16": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "cpx_blocks_backward_workspace_bytes_mp": (_sz, [_i, _i, _i, _i]),
     "cpx_blocks_backward_mp": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _sz, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "cpx_blocks_backward_in": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _sz, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "cpx_embed_grad_layout": (C.c_longlong, [C.POINTER(C.c_longlong)]),
+    "cpx_embed_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cpx_embed_backward": (_i, [_i, _p, _p, _i, _i, _p, _p, _sz, _p]),
     "cpx_gelu_backward": (_i, [_p, _p, _sz, _p, _p]),
     "cpx_neck_grad_layout": (C.c_longlong, [C.POINTER(C.c_longlong)]),
     "cpx_neck_backward_workspace_bytes": (_sz, [_i, _i, _i, C.POINTER(_sz)]),

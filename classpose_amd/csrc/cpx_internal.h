@@ -220,3 +220,5 @@ int cpx_uwgrad_run(int dtype, int kind, const UwArgs &u, int n_valid, int bias_t
 // W [Npad][Kpad] of `dtype` -> float32 [Kp128][Npad], rows Kpad.. zero
 int cpx_wt_run(int dtype, const void *w, int Npad, int Kpad, int Kp128, float *wt, hipStream_t s);
 int cpx_dx_gather_run(int dtype, const DxArgs &g, hipStream_t s);      // col2im, added to g.gx
+// in [R][Cc] of `dtype` -> out [Cc][R] float32, widened exactly (cpx_train_blocks.hip); R and Cc multiples of 32
+int cpx_transpose_f32_run(int dtype, const void *in, int R, int Cc, float *out, hipStream_t s);

@@ -705,6 +705,7 @@ static int transpose_run(int dtype, const void *in, int R, int Cc, float *out, h
     CPX_CHECK_LAUNCH();
     return CPX_OK;
 }
+int cpx_transpose_f32_run(int dtype, const void *in, int R, int Cc, float *out, hipStream_t s) { return transpose_run(dtype, in, R, Cc, out, s); }
 static int add_run(const float *a, const float *b, size_t n, float *out, hipStream_t s) {
     hipLaunchKernelGGL(k_add_f32, grid1(n / 4), dim3(256), 0, s, a, b, n / 4, out);
     CPX_CHECK_LAUNCH();
@@ -781,9 +782,12 @@ extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
 //
 // attn_grad_dtype CPX_DT_BF16 (with grad_dtype CPX_DT_BF16 only): the attention backward is cpx_attention_backward_bf16 (cpx_attn_bwd16.hip)
 // in place of the float32 one; CPX_DT_F32 is cpx_blocks_backward_ex, launch for launch.
-extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+//
+// dx_in (or NULL): [rows][1024] float32, the gradient of block first_block's input alone -- record 0 of dx_all without the other K records,
+// copied per slab from dx where that record is copied.  What the patch embedding's backward (cpx_embed_backward) takes when first_block is 0.
+extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                       size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,
-                                      float *dx_all, void *workspace, size_t workspace_bytes, void *stream) {
+                                      float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(blocks_weights_ok(w, first_block) && params && fwd_workspace && dy0 && grads && workspace && w->neck0_w);
     CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block) && grad_dtype_ok(w->dtype, grad_dtype));
     CPX_REQUIRE(attn_grad_dtype_ok(grad_dtype, attn_grad_dtype));
@@ -793,7 +797,7 @@ extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *par
     const BlocksBwdLayout L = blocks_bwd_layout(grad_dtype);
     CPX_REQUIRE(fwd_workspace_bytes >= F.total && workspace_bytes >= L.total);
     CPX_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)fwd_workspace & 255) == 0);
-    CPX_REQUIRE((((uintptr_t)params | (uintptr_t)dy0 | (uintptr_t)grads | (uintptr_t)dx_all) & 15) == 0);
+    CPX_REQUIRE((((uintptr_t)params | (uintptr_t)dy0 | (uintptr_t)grads | (uintptr_t)dx_all | (uintptr_t)dx_in) & 15) == 0);
     hipStream_t s = (hipStream_t)stream;
     const char *fws = (const char *)fwd_workspace;
     char *ws = (char *)workspace;
@@ -917,6 +921,7 @@ extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *par
             }
             CPX_RUN(ln_bwd(xin, P + go[0], b3, Ms, Gd + go[0], Gd + go[1]));                                                  // dx = d x_in
             if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)j * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
+            if (dx_in && j == 0) CPX_HIP(hipMemcpyAsync(dx_in + r0 * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
         }
     }
     if (fuse)                                                          // the W slots hold dWf, the b slots dbf, summed over the slabs
@@ -929,6 +934,12 @@ extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *par
             CPX_CHECK_LAUNCH();
         }
     return CPX_OK;
+}
+extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+                                      size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,
+                                      float *dx_all, void *workspace, size_t workspace_bytes, void *stream) {
+    return cpx_blocks_backward_in(w, params, nS, first_block, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype, grads, dx_all,
+                                  nullptr, workspace, workspace_bytes, stream);
 }
 extern "C" int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                       size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, float *grads, float *dx_all,

@@ -4,7 +4,7 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
         --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
-        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K [--grad_precision bf16 [--attn_grad_precision bf16]]]
+        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K [--grad_precision bf16 [--attn_grad_precision bf16]] [--train_embed]]
     python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
         [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
@@ -129,7 +129,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="train the last K transformer blocks (encoder.blocks.*) next to the neck and the class head, from the cached "
                         "input rows of block depth - K; turns --train_neck on; not with a UNet class head.  --train_blocks 24 "
                         "--train_flow_head is what the reference trains without --freeze, except for the patch embedding and the "
-                        "position table, which stay fixed")
+                        "position table, which stay fixed unless --train_embed is given")
     p.add_argument("--grad_precision", default="fp32", choices=["fp32", "bf16"],
                    help="with --train_blocks: bf16 runs the matrix products of the blocks' backward on bf16 operands with float32 "
                         "accumulation (several times faster; gradients differ from the float32 backward by the operand rounding); "
@@ -137,6 +137,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--attn_grad_precision", default="fp32", choices=["fp32", "bf16"],
                    help="with --grad_precision bf16: bf16 runs the attention backward of the trained blocks on bf16 operands as well "
                         "(dO, P and dS' rounded once, float32 accumulation).  The default fp32 keeps it in float32")
+    p.add_argument("--train_embed", action="store_true",
+                   help="train the patch embedding (encoder.patch_embed.proj.*) and the position table (encoder.pos_embed) too: full "
+                        "fine-tuning.  Needs --train_blocks equal to the checkpoint's depth (24 for ViT-L), because the gradient reaches "
+                        "the embedding only through every block; not with a UNet class head.  The cache then holds patch rows (384 KB per "
+                        "crop in bf16) and every step runs the whole network.  With --train_flow_head this is what the reference trains "
+                        "without --freeze.  --grad_precision bf16 also runs the embedding's weight gradient on bf16 operands")
     p.add_argument("--freeze", nargs="+", default=None, choices=["none", "backbone", "segmentation_head", "neck"],
                    help="the reference's spelling of the same choice: 'backbone neck' = --train_flow_head, 'backbone "
                         "segmentation_head neck' = the default (class head only); nothing else is built")
@@ -169,6 +175,25 @@ def flow_head_from_freeze(freeze, train_flow_head: bool) -> bool:
     return True
 
 
+def checkpoint_depth(path) -> int | None:
+    """The number of transformer blocks of the checkpoint at ``path`` (its ``encoder.blocks.N.`` keys, read through a memory map), or
+    None when there is no such file or no such key: whatever is wrong with it is then reported where the checkpoint is loaded."""
+    import os
+    import re
+    if path is None or not os.path.isfile(path):
+        return None
+    import warnings
+    import torch
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            sd = torch.load(path, map_location="cpu", weights_only=True, mmap=True)
+    except Exception:
+        return None
+    idx = [int(m.group(1)) for m in (re.match(r"(?:module\.)?encoder\.blocks\.(\d+)\.", k) for k in sd) if m]
+    return max(idx) + 1 if idx else None
+
+
 def check_args(args) -> None:
     """The combinations the parser cannot express; raises ``SystemExit`` with the reason."""
     args.train_neck = bool(getattr(args, "train_neck", False))
@@ -189,6 +214,18 @@ def check_args(args) -> None:
     if args.attn_grad_precision == "bf16" and args.grad_precision != "bf16":
         raise SystemExit("--attn_grad_precision bf16 needs --grad_precision bf16: it is the last float32 product of the bf16 backward of "
                          "the trained blocks, not a mode of the float32 backward")
+    args.train_embed = bool(getattr(args, "train_embed", False))
+    if args.train_embed:
+        if getattr(args, "feature_transformation_structure", None) is not None:
+            raise SystemExit("--train_embed: the patch embedding does not train under a UNet class head (its backward gives the neck "
+                             "output no gradient, so none reaches the blocks or the embedding)")
+        if not args.train_blocks:
+            raise SystemExit("--train_embed needs --train_blocks equal to the checkpoint's depth (24 for ViT-L): the gradient reaches "
+                             "the patch embedding only through every block")
+        depth = checkpoint_depth(getattr(args, "pretrained_model", None))
+        if depth is not None and args.train_blocks != depth:
+            raise SystemExit(f"--train_embed needs --train_blocks {depth}, the checkpoint's depth, not --train_blocks {args.train_blocks}: "
+                             "the gradient reaches the patch embedding only through every block")
     if args.train_blocks:
         if getattr(args, "feature_transformation_structure", None) is not None:
             raise SystemExit("--train_blocks: the blocks do not train under a UNet class head (its backward gives the neck output no "
@@ -310,8 +347,11 @@ def _trainer_of(args, make_trainer, nclasses):
                             class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
                             train_neck=args.train_neck, train_blocks=args.train_blocks,
                             **({"grad_precision": "bf16"} if getattr(args, "grad_precision", "fp32") == "bf16" else {}),
-                            **({"attn_grad_precision": "bf16"} if getattr(args, "attn_grad_precision", "fp32") == "bf16" else {}))
+                            **({"attn_grad_precision": "bf16"} if getattr(args, "attn_grad_precision", "fp32") == "bf16" else {}),
+                            **({"train_embed": True} if getattr(args, "train_embed", False) else {}))
     except (ValueError, NotImplementedError) as e:
+        if getattr(args, "train_embed", False) and "train_embed" in str(e):
+            raise SystemExit(f"--train_embed: {e}")
         if args.train_blocks and "train_blocks" in str(e):
             raise SystemExit(f"--train_blocks {args.train_blocks}: {e}")
         raise

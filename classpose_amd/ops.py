@@ -1029,14 +1029,15 @@ def blocks_backward_workspace(n_subtiles: int, dtype_code: int, device, grad_dty
 
 def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: torch.Tensor, grads: torch.Tensor | None = None,
                     workspace: torch.Tensor | None = None, dx_all: torch.Tensor | None = None, grad_dtype=torch.float32,
-                    attn_grad_dtype=torch.float32) -> torch.Tensor:
-    """``cpx_blocks_backward_mp``: the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
+                    attn_grad_dtype=torch.float32, dx_in: torch.Tensor | None = None) -> torch.Tensor:
+    """``cpx_blocks_backward_in`` (``cpx_blocks_backward_mp`` plus ``dx_in``): the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
     ``block_grad_layout``), from ``params`` (the K blocks' unfolded parameters as the forward reads them, same layout) and ``dy0``
     (rows, 256) float32, which ``neck_backward`` leaves in its workspace.  ``dx_all`` (K + 1, rows, 1024) float32, when given, receives
     the gradient of every trained block's input and (last) of the last block's output.  ``grad_dtype`` torch.float32: the exact-float32
     products of ``cpx_blocks_backward``; torch.bfloat16 (a bf16 network only): every product on bf16 operands with float32 accumulation.
     ``attn_grad_dtype`` torch.bfloat16 (with ``grad_dtype`` torch.bfloat16 only): the attention backward on bf16 operands too
-    (``cpx_attention_backward_bf16``); torch.float32 leaves it in float32."""
+    (``cpx_attention_backward_bf16``); torch.float32 leaves it in float32.  ``dx_in`` (rows, 1024) float32, when given, receives the
+    gradient of the first trained block's input alone (record 0 of ``dx_all`` without the rest): what ``embed_backward`` takes."""
     c, L = weights.c, _lib.lib()
     gd = _grad_dtype_code(grad_dtype, c.dtype, "blocks_backward")
     ad = _attn_grad_dtype_code(attn_grad_dtype, gd, "blocks_backward")
@@ -1053,12 +1054,17 @@ def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: t
     if dx_all is not None and (dx_all.dtype != torch.float32 or tuple(dx_all.shape) != (K + 1, rows, 1024) or not dx_all.is_contiguous()
                                or dx_all.device != dev):
         raise ValueError("blocks_backward: dx_all must be contiguous float32 (K + 1, rows, 1024)")
+    if dx_in is not None and (dx_in.dtype != torch.float32 or tuple(dx_in.shape) != (rows, 1024) or not dx_in.is_contiguous()
+                              or dx_in.device != dev):
+        raise ValueError("blocks_backward: dx_in must be contiguous float32 (rows, 1024)")
     if workspace is None:
         workspace = blocks_backward_workspace(rows // 1024, c.dtype, dev, grad_dtype, attn_grad_dtype)
     if workspace.dtype != torch.uint8 or fwd.workspace.dtype != torch.uint8:
         raise ValueError("blocks_backward: workspaces are uint8 tensors")
-    check(L.cpx_blocks_backward_mp(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
-                                   gd, ad, ptr(grads), ptr(dx_all), ptr(workspace), workspace.numel(), _stream(dev)), "blocks_backward")
+    # (cpx_blocks_backward_mp is this entry with dx_in NULL)
+    check(L.cpx_blocks_backward_in(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
+                                   gd, ad, ptr(grads), ptr(dx_all), ptr(dx_in), ptr(workspace), workspace.numel(), _stream(dev)),
+          "blocks_backward")
     return grads
 
 
@@ -1094,6 +1100,54 @@ def colsum_add(dy: torch.Tensor, db: torch.Tensor, workspace: torch.Tensor | Non
         raise ValueError("colsum_add: the workspace is a uint8 tensor")
     check(_lib.lib().cpx_colsum_add(ptr(dy), rows, N, ptr(db), ptr(workspace), workspace.numel(), _stream(dy.device)), "colsum_add")
     return db
+
+
+EMBED_GRAD_NAMES = ("pe_w", "pe_b", "pos")
+EMBED_GRAD_SHAPES = ((1024, 192), (1024,), (1024, 1024))
+
+
+def embed_grad_layout() -> tuple[int, list[int]]:
+    """(element count, element offsets of the three tensors of ``EMBED_GRAD_NAMES``) of the flat float32 record of ``embed_backward``
+    (``cpx_embed_grad_layout``): W (1024, 192) with k in the order of ``patchify_f32``, b (1024,), pos (1024, 1024)."""
+    off = (C.c_longlong * 3)()
+    n = _lib.lib().cpx_embed_grad_layout(off)
+    return int(n), [int(v) for v in off]
+
+
+def embed_backward_workspace(n_subtiles: int, dtype_code: int, device, grad_dtype=torch.float32) -> torch.Tensor:
+    gd = _grad_dtype_code(grad_dtype, dtype_code, "embed_backward_workspace")
+    n = _lib.lib().cpx_embed_backward_workspace_bytes(n_subtiles, dtype_code, gd)
+    if n == 0:
+        raise ValueError("embed_backward_workspace: invalid n_subtiles / dtype")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def embed_backward(patches: torch.Tensor, dx_in: torch.Tensor, grads: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                   grad_dtype=torch.float32) -> torch.Tensor:
+    """``cpx_embed_backward``: the gradients of the patch embedding ``x = round(p W^T + b + pos)`` into the flat float32 ``grads`` (one
+    record of ``embed_grad_layout``, overwritten), from the patch rows ``patches`` (n * 1024, 192) in the network dtype as the forward
+    read them and ``dx_in`` (n * 1024, 1024) float32, the gradient of block 0's input (``blocks_backward(..., dx_in=)``).  ``grad_dtype``
+    torch.float32: dW on the exact-float32 MFMA; torch.bfloat16 (bf16 patches only): dW = r(dx)^T p on the bf16 MFMA with float32
+    accumulation.  db and dpos are float64 sums of the unrounded ``dx_in`` in both modes."""
+    if patches.dim() != 2 or patches.shape[1] != 192 or patches.shape[0] == 0 or patches.shape[0] % 1024 or patches.dtype not in _DT \
+            or not patches.is_contiguous() or not patches.is_cuda:
+        raise ValueError("embed_backward: patches must be contiguous device rows (n * 1024, 192) in a network dtype")
+    rows, dev, dt = patches.shape[0], patches.device, _DT[patches.dtype]
+    gd = _grad_dtype_code(grad_dtype, dt, "embed_backward")
+    if dx_in.dtype != torch.float32 or tuple(dx_in.shape) != (rows, 1024) or not dx_in.is_contiguous() or dx_in.device != dev:
+        raise ValueError("embed_backward: dx_in must be contiguous float32 (rows, 1024) on the patches' device")
+    n_g, _off = embed_grad_layout()
+    if grads is None:
+        grads = torch.empty(n_g, dtype=torch.float32, device=dev)
+    if grads.dtype != torch.float32 or grads.numel() != n_g or not grads.is_contiguous() or grads.device != dev:
+        raise ValueError("embed_backward: grads must be the flat float32 record of embed_grad_layout")
+    if workspace is None:
+        workspace = embed_backward_workspace(rows // 1024, dt, dev, grad_dtype)
+    if workspace.dtype != torch.uint8:
+        raise ValueError("embed_backward: the workspace is a uint8 tensor")
+    check(_lib.lib().cpx_embed_backward(dt, ptr(patches), ptr(dx_in), rows // 1024, gd, ptr(grads), ptr(workspace), workspace.numel(),
+                                        _stream(dev)), "embed_backward")
+    return grads
 
 
 # ---- t2: training-time augmentation (csrc/cpx_augment.hip) --------------------------------------------------------

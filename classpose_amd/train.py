@@ -21,6 +21,10 @@ Deliberately different from the reference:
 ``train_flow_head`` its ``--freeze backbone``): the cache then holds the backbone's output rows and every step runs the neck's
 training forward and ``cpx_neck_backward``.
 
+``train_blocks=K`` also trains the last K transformer blocks (``BlockParams``) and, with K = depth, ``train_embed=True`` the
+patch embedding and the position table (``EmbedParams``): the cache then holds patch rows and every step runs the whole
+network, which with ``train_flow_head`` is the reference's run without ``--freeze``.
+
 ``train_flow_head=True`` also trains the flow head ``out`` (``FlowHead``): the reference's ``--freeze backbone neck``, seg + CE +
 Tversky with multiplier 1 each (train.py:482-493), the seg loss being cellpose's ``_loss_fn_seg`` restated (``ops.seg_loss``).
 
@@ -331,6 +335,55 @@ class BlockParams:
         return out
 
 
+EMBED_KEYS = ("encoder.patch_embed.proj.weight", "encoder.patch_embed.proj.bias", "encoder.pos_embed")
+
+
+class EmbedParams:
+    """The patch embedding and the position table as a group (what the reference trains on top of every block when ``--freeze`` is not
+    given): float32 masters of ``patch_embed.proj.weight`` as ``W`` [1024, 192] (k in the order of ``ops.patchify_f32``),
+    ``patch_embed.proj.bias`` [1024] and ``pos_embed`` [1024 tokens, 1024] as views of ONE flat buffer in the order of
+    ``ops.embed_grad_layout``, their AdamW moments and the gradient buffer ``cpx_embed_backward`` fills.  Weight decay applies to all
+    three: the reference hands ``net.parameters()`` to AdamW.  The position table is the architecture's own 32 x 32 grid."""
+    keys = EMBED_KEYS
+
+    def __init__(self, sd: dict, weights):
+        shapes = ((1024, 3, 8, 8), (1024,), (1, 32, 32, 1024))
+        for k, shape in zip(EMBED_KEYS, shapes):
+            if k not in sd or tuple(sd[k].shape) != shape:
+                what = "a position table of another grid size is not built" if k == EMBED_KEYS[2] and k in sd else "missing or of another shape"
+                raise ValueError(f"{k} of the checkpoint is not {shape}: {what}")
+        self.weights = weights
+        n, self.off = ops.embed_grad_layout()
+        flat = torch.cat([sd[k].detach().float().reshape(-1) for k in EMBED_KEYS])
+        if flat.numel() != n:
+            raise _lib.CpxError("EmbedParams: the host's parameter layout differs from the library's")
+        self.params = flat.contiguous().to(weights.device)
+        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
+
+    def view(self, i: int, buf: torch.Tensor | None = None) -> torch.Tensor:
+        """Master tensor ``i`` of ``ops.EMBED_GRAD_NAMES`` (a view of ``params``, or of ``buf``: ``grads``)."""
+        shape = ops.EMBED_GRAD_SHAPES[i]
+        return (self.params if buf is None else buf)[self.off[i]:self.off[i] + int(np.prod(shape))].view(shape)
+
+    def update(self, step: int, lr: float, **adam) -> None:
+        """One AdamW step of all three tensors from the flat ``grads``, then ``refresh``."""
+        ops.adamw_step(self.params, self.grads, self.m, self.v, step, lr, **adam)
+        self.refresh()
+
+    def refresh(self) -> None:
+        """Masters -> ``pe_w`` / ``pe_b`` / ``pos`` of ``self.weights`` in place, rounded exactly as at load: the GEMM operand to the
+        network dtype, the two epilogue operands through it and back to float32."""
+        c = self.weights.c
+        half = c.dtype != _lib.DT_F32
+        ops.round_weights(self.view(0), c.pe_w, c.dtype, keep_f32=not half)
+        ops.round_weights(self.view(1), c.pe_b, c.dtype, keep_f32=True)
+        ops.round_weights(self.view(2), c.pos, c.dtype, keep_f32=True)
+
+    def state(self) -> dict:
+        v = [self.view(i).detach().cpu().clone() for i in range(3)]
+        return {EMBED_KEYS[0]: v[0].reshape(1024, 3, 8, 8), EMBED_KEYS[1]: v[1], EMBED_KEYS[2]: v[2].reshape(1, 32, 32, 1024)}
+
+
 def _of_class_group(name: str) -> property:
     return property(lambda self: getattr(self.groups[0], name))
 
@@ -349,8 +402,10 @@ class HeadTrainer:
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
                  head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, train_flow_head: bool = False,
-                 train_neck: bool = False, train_blocks: int = 0, grad_precision: str = "fp32", attn_grad_precision: str = "fp32"):
+                 train_neck: bool = False, train_blocks: int = 0, grad_precision: str = "fp32", attn_grad_precision: str = "fp32",
+                 train_embed: bool = False):
         self.device = torch.device(device)
+        self.train_embed = bool(train_embed)
         self.train_blocks = int(train_blocks)
         if self.train_blocks < 0:
             raise ValueError("train_blocks: a count of blocks, 0 for none")
@@ -387,11 +442,20 @@ class HeadTrainer:
         self.flow = FlowHead(self.sd, self.weights) if train_flow_head else None
         self.neck = NeckParams(self.sd, self.weights) if train_neck else None
         # ``train_blocks`` = K: the last K transformer blocks train too -- with ``train_flow_head`` and K = depth the
-        # reference's run without ``--freeze``, except for the patch embedding and the position table; ``step`` / ``evaluate`` then
+        # reference's run without ``--freeze``, except for the patch embedding and the position table (``train_embed``); ``step`` / ``evaluate`` then
         # start from the input rows of block depth - K (``backbone_features``)
         self.blocks = BlockParams(self.sd, self.weights, self.train_blocks) if self.train_blocks else None
+        # ``train_embed``: the patch embedding and the position table train too -- with ``train_blocks`` = depth and
+        # ``train_flow_head`` the reference's run without ``--freeze``, every parameter; ``step`` / ``evaluate`` then start from patch
+        # rows (``patch_rows``)
+        self.embed = None
+        if self.train_embed:
+            if self.train_blocks != self.weights.depth:
+                raise ValueError(f"train_embed needs train_blocks = {self.weights.depth}, the checkpoint's depth (train_blocks is "
+                                 f"{self.train_blocks}): the gradient reaches the patch embedding only through every block")
+            self.embed = EmbedParams(self.sd, self.weights)
         self.diam_labels = None
-        self.groups = [g for g in (self._class_group(), self.flow, self.neck, self.blocks) if g is not None]
+        self.groups = [g for g in (self._class_group(), self.flow, self.neck, self.blocks, self.embed) if g is not None]
 
     # what ``train_unet.UNetHeadTrainer`` replaces: the checkpoint's preparation, the class group and the forward workspace
     def _prepare(self, pretrained_model, nclasses, head_seed) -> tuple[dict, int]:
@@ -474,18 +538,36 @@ class HeadTrainer:
         if K == 0:
             return self._forward_rows(X, ops.backbone_rows, 1024)
         if K == c.depth:
-            patches = self._patches(X)
-            out = torch.empty((patches.shape[0], 1024), dtype=self.dtype, device=self.device)
-            check(self._L.cpx_gemm(c.dtype, ptr(patches), c.pe_w, patches.shape[0], 1024, 192, ops.EPI["pos"], c.pe_b, c.pos, ptr(out), 1024,
-                                   torch.cuda.current_stream(self.device).cuda_stream), "patch embedding")
-            return out
+            return self._embed(self._patches(X))
         prefix = type(c).from_buffer_copy(c)              # the trainer's own struct is never changed: other users see its full depth
         prefix.depth = c.depth - K
         return self._forward_rows(X, ops.backbone_rows, 1024, prefix)
 
+    def _embed(self, patches: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The patch embedding's launch of ``cpx_net_forward`` on patch rows: block 0's input rows (n * 1024, 1024) in the network dtype."""
+        c = self.weights.c
+        if out is None:
+            out = torch.empty((patches.shape[0], 1024), dtype=self.dtype, device=self.device)
+        check(self._L.cpx_gemm(c.dtype, ptr(patches), c.pe_w, patches.shape[0], 1024, 192, ops.EPI["pos"], c.pe_b, c.pos, ptr(out), 1024,
+                               torch.cuda.current_stream(self.device).cuda_stream), "patch embedding")
+        return out
+
+    def patch_rows(self, X) -> torch.Tensor:
+        """Patch rows (n * 1024, 192) in the network dtype of n crops: the input of the patch embedding, what a trainer built with
+        ``train_embed`` caches (384 KB per crop in bf16, against 2 MB of backbone rows)."""
+        return self._patches(X)
+
     def _blocks_forward(self, X):
-        """The training forward of the last K blocks and the tail on the rows of ``X``: (x_out, the tail's ``ops.NeckForwardOut``)."""
-        x = self._as_rows(X, 1024, "backbone rows")
+        """The training forward of the last K blocks and the tail on the rows of ``X``: (x_out, the tail's ``ops.NeckForwardOut``).
+        With ``train_embed`` it starts from patch rows, which are kept for the embedding's backward."""
+        if self.embed is not None:
+            self._rows = self._as_rows(X, 192, "patch rows")
+            key = ("emb_x", self._rows.shape[0])
+            if key not in self._buf:
+                self._buf[key] = torch.empty((self._rows.shape[0], 1024), dtype=self.dtype, device=self.device)
+            x = self._embed(self._rows, self._buf[key])
+        else:
+            x = self._as_rows(X, 1024, "backbone rows")
         rows, c = x.shape[0], self.weights.c
         key = ("blk_fwd", rows)
         if key not in self._buf:
@@ -507,16 +589,27 @@ class HeadTrainer:
         nws = self._buf[("neck_bwd", rows)][1]
         off = ops.neck_backward_workspace_offsets(rows // TOKENS, c.dtype, c.ld_head)[3]
         dy0 = nws[off:off + rows * 256 * 4].view(torch.float32).view(rows, 256)
+        dx_in = None
+        if self.embed is not None:                        # the gradient of block 0's input, then the embedding's own backward
+            ekey = ("emb_bwd", rows)
+            if ekey not in self._buf:
+                self._buf[ekey] = (torch.empty((rows, 1024), dtype=torch.float32, device=self.device),
+                                   ops.embed_backward_workspace(rows // TOKENS, c.dtype, self.device, grad_dtype))
+            dx_in, ews = self._buf[ekey]
         ops.blocks_backward(self.weights, self.blocks.rounded, fwd, dy0, self.blocks.grads, self._buf[key], grad_dtype=grad_dtype,
-                            attn_grad_dtype=attn_grad_dtype)
+                            attn_grad_dtype=attn_grad_dtype, dx_in=dx_in)
         self.blocks.finish_backward()
+        if self.embed is not None:
+            ops.embed_backward(self._rows, dx_in, self.embed.grads, ews, grad_dtype=grad_dtype)
 
     def _as_rows(self, X, width: int, what: str) -> torch.Tensor:
-        """``X`` itself when it is cached rows of that width, else its crops through the backbone."""
+        """``X`` itself when it is cached rows of that width, else its crops through the backbone (width 192: through ``_patches``)."""
         if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == width and X.dtype == self.dtype and X.is_cuda:
             if X.shape[0] % TOKENS:
                 raise ValueError(f"{what}: 1024 rows per crop")
             return X.contiguous()
+        if width == 192:
+            return self._patches(X)
         return self.features(X) if width == 256 else self.backbone_features(X)
 
     def _neck_forward(self, X):
@@ -875,8 +968,14 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     # a trainer that trains the neck starts from the backbone's output instead of the neck's
     neck = getattr(trainer, "neck", None) is not None
     cache, width = (trainer.backbone_features, 1024) if neck else (trainer.features, 256)
+    # one that trains the patch embedding starts from the patch rows themselves
+    embed = getattr(trainer, "embed", None) is not None
+    if embed:
+        cache, width = trainer.patch_rows, 192
+        train_logger.info(">>> train_embed: the cache holds patch rows (%d KB per crop), every step runs the patch embedding and all "
+                          "%d blocks", TOKENS * 192 * (4 if trainer.precision == "fp32" else 2) // 1024, trainer.train_blocks)
     if cached:
-        train_logger.info(">>> caching %s of %d training crops", "backbone rows" if neck else "neck features", nimg)
+        train_logger.info(">>> caching %s of %d training crops", "patch rows" if embed else "backbone rows" if neck else "neck features", nimg)
         feats = cache(images).view(nimg, TOKENS, width)
         lab_dev = _labels_i16(labels, dev)
     if test_cached:

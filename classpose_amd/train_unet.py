@@ -261,7 +261,10 @@ class UNetHeadTrainer(HeadTrainer):
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
                  head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, feature_transformation_structure=None,
-                 train_flow_head: bool = False, train_neck: bool = False, train_blocks: int = 0):
+                 train_flow_head: bool = False, train_neck: bool = False, train_blocks: int = 0, train_embed: bool = False):
+        if train_embed:
+            raise NotImplementedError("train_embed: the UNet head's backward gives the neck output no gradient, so none reaches the "
+                                      "blocks or the patch embedding; they train under the 1x1 class head only")
         if train_blocks:
             raise NotImplementedError("train_blocks: the UNet head's backward gives the neck output no gradient, so none reaches the "
                                       "blocks; they train under the 1x1 class head only")

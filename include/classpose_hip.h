@@ -710,6 +710,40 @@ size_t cpx_blocks_backward_workspace_bytes_mp(int n_subtiles, int dtype, int gra
 int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
                            size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads, float *dx_all,
                            void *workspace, size_t workspace_bytes, void *stream);
+/* Training the patch embedding and the position table (csrc/cpx_train_embed.hip; additive, no ABI bump): with first_block 0 the last stage
+ * of full fine-tuning.
+ * cpx_blocks_backward_in: cpx_blocks_backward_mp (which forwards here with NULL, bit for bit) with one more output, dx_in: NULL, or
+ * [rows][1024] float32 receiving the gradient of block first_block's input alone -- record 0 of dx_all without the K records after it (128 MB
+ * at 32 crops where dx_all for K = 24 is 3.3 GB), copied per slab from the same buffer.  16-byte aligned like its neighbours; the workspace
+ * sizes are those of cpx_blocks_backward_workspace_bytes_mp.
+ * cpx_embed_grad_layout: the element count of one flat float32 record W [1024][192] | b [1024] | pos [1024][1024] (off: the three element
+ * offsets); k of W in the order of pe_w / cpx_patchify_f32.
+ * cpx_embed_backward: the gradients of x = round(p W^T + b + pos[row % 1024]) (the cpx_gemm(..., CPX_EPI_POS_BF16, ...) launch that opens
+ * cpx_net_forward), rounding passed straight through, from patches [rows][192] in `dtype` as that GEMM read them and dx_in [rows][1024]
+ * float32 (rows = n_subtiles * 1024).  The record is overwritten.
+ *   dpos[t][c] = sum over the crops n, in order, of dx[n * 1024 + t][c]: one float64 chain, rounded once
+ *   db[c]      = sum over the rows of the unrounded float32 dx[row][c] in float64 (the unrounded sums of dpos, tokens in order within groups
+ *                of four, the groups in order), rounded once
+ *   dW[c][k]   = sum over the rows of dx[row][c] p[row][k]:
+ *     grad_dtype CPX_DT_F32   on the exact-float32 MFMA, p widened exactly, in slabs of two crops added in slab order (the float32 route of
+ *                             the blocks' backward)
+ *     grad_dtype CPX_DT_BF16  (a bf16 network only, as in cpx_blocks_backward_ex) r(dx)^T p on v_mfma_f32_32x32x16_bf16: dx rounded to bf16
+ *                             once, nearest even, p exact, float32 accumulation.  The rows are split over S = 8 min(n_subtiles, 4)
+ *                             workgroups per 128-channel tile (128 rows per split up to 4 crops, 32 n_subtiles beyond: 256 workgroups), each
+ *                             split one accumulation chain over its rows in order; the float32 partial tiles are added in split order by a
+ *                             second launch.  Both operands are read transposed from row-major LDS tiles by ds_read_b64_tr_b16.
+ * Takes a stream, allocates nothing, no floating-point atomics, no workgroup waits for another; every sum runs in an order fixed by
+ * n_subtiles alone: two runs are bitwise equal.  Workspace: cpx_embed_backward_workspace_bytes (2 MiB + 768 KiB per split in bf16 mode,
+ * 13 MiB in float32 mode; 0 for invalid arguments).  Null pointers, patches / dx_in / grads not 16-byte aligned, a workspace not 256-byte
+ * aligned or too short, n_subtiles outside the range of cpx_blocks_backward, an unknown dtype, grad_dtype CPX_DT_BF16 with a CPX_DT_F16 or
+ * CPX_DT_F32 network: CPX_EINVAL, nothing is launched.                                                                                  */
+int cpx_blocks_backward_in(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
+                           size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads, float *dx_all,
+                           float *dx_in, void *workspace, size_t workspace_bytes, void *stream);
+long long cpx_embed_grad_layout(long long *off /* [3] or NULL */);
+size_t cpx_embed_backward_workspace_bytes(int n_subtiles, int dtype, int grad_dtype);
+int cpx_embed_backward(int dtype, const void *patches, const float *dx_in, int n_subtiles, int grad_dtype, float *grads, void *workspace,
+                       size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)
