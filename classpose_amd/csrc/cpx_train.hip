@@ -106,13 +106,15 @@ __device__ __forceinline__ int lane_label(const LossArgs &g, int b, int t, int l
     const int tw = g.W >> 3, ph = t / tw, pw = t - ph * tw;
     return g.labels[((size_t)b * g.H + 8 * ph + (lane >> 3)) * g.W + 8 * pw + (lane & 7)];
 }
-// log-sum-exp of the lane's pixel: max, then sum of exp(z - max)
-__device__ __forceinline__ void lane_lse(const float *z, int ncls, float &mx, float &lse) {
+// log-sum-exp of the lane's pixel in two parts, the maximum and ls = log sum exp(z - max).  They are kept apart: the sum max + ls is
+// rounded at the size of the logits (2^-18 at |z| = 80), and that rounding would be a relative error of every p = exp(z - lse) of the
+// pixel, the same for all pixels with the same logits; p = exp((z - max) - ls) and -log p[y] = ls - (z[y] - max) round at their own size
+__device__ __forceinline__ void lane_lse(const float *z, int ncls, float &mx, float &ls) {
     mx = z[0];
     for (int c = 1; c < ncls; ++c) mx = fmaxf(mx, z[c * 64]);
     float s = 0.f;
     for (int c = 0; c < ncls; ++c) s += expf(z[c * 64] - mx);
-    lse = mx + logf(s);
+    ls = logf(s);
 }
 
 __global__ void __launch_bounds__(256) k_loss_sums(LossArgs g) {
@@ -127,16 +129,16 @@ __global__ void __launch_bounds__(256) k_loss_sums(LossArgs g) {
         if (valid && (y < 0 || y >= g.ncls)) bad = 1;
         const bool use = valid && y >= 0 && y < g.ncls;
         const float *z = g.head + ((size_t)b * T + t) * g.ld_head + g.col0 + lane;
-        float mx, lse;
-        lane_lse(z, g.ncls, mx, lse);
+        float mx, ls;
+        lane_lse(z, g.ncls, mx, ls);
         if (use) {
             const float wy = g.cw ? g.cw[y] : 1.f;
-            ce_num += (double)wy * (double)(lse - z[y * 64]);
+            ce_num += (double)wy * (double)(ls - (z[y * 64] - mx));
             ce_den += (double)wy;
             cnt += 1;
         }
         for (int c = 0; c < g.ncls; ++c) {
-            const float p = expf(z[c * 64] - lse);
+            const float p = expf((z[c * 64] - mx) - ls);
             const double s_tp = wave_sum(use && y == c ? (double)p : 0.0);
             const double s_fp = wave_sum(use && y != c ? (double)p : 0.0);
             const double s_fn = wave_sum(use && y == c ? (double)(1.f - p) : 0.0);
@@ -174,16 +176,16 @@ __global__ void __launch_bounds__(256) k_loss_sums_reg(LossArgs g) {
         for (int c = 0; c < NC; ++c) { z[c] = c < g.ncls ? zp[c * 64] : 0.f; if (c < g.ncls) mx = fmaxf(mx, z[c]); }
 #pragma unroll
         for (int c = 0; c < NC; ++c) { if (c < g.ncls) s += expf(z[c] - mx); if (c == y) zy = z[c]; }
-        const float lse = mx + logf(s);
+        const float ls = logf(s);
         if (use) {
             const float wy = g.cw ? g.cw[y] : 1.f;
-            ce_num += (double)wy * (double)(lse - zy);
+            ce_num += (double)wy * (double)(ls - (zy - mx));
             ce_den += (double)wy;
             cnt += 1;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 if (c < g.ncls) {
-                    const float p = expf(z[c] - lse);
+                    const float p = expf((z[c] - mx) - ls);
                     if (c == y) { a_tp[c] += (double)p; a_fn[c] += (double)(1.f - p); }
                     else a_fp[c] += (double)p;
                 }
@@ -295,13 +297,13 @@ __global__ void __launch_bounds__(256) k_loss_grad(LossArgs g) {
             continue;
         }
         const float *z = g.head + row * g.ld_head + g.col0 + lane;
-        float mx, lse;
-        lane_lse(z, g.ncls, mx, lse);
+        float mx, ls;
+        lane_lse(z, g.ncls, mx, ls);
         float S = 0.f;                                      // sum_c p[c] G[c],  G[c] = d loss / d p[c] of this pixel
-        for (int c = 0; c < g.ncls; ++c) S += expf(z[c * 64] - lse) * (c == y ? s_ga[c] : s_gb[c]);
+        for (int c = 0; c < g.ncls; ++c) S += expf((z[c * 64] - mx) - ls) * (c == y ? s_ga[c] : s_gb[c]);
         const float wy = (g.cw ? g.cw[y] : 1.f) * ce_scale;
         for (int c = 0; c < g.ncls; ++c) {
-            const float p = expf(z[c * 64] - lse);
+            const float p = expf((z[c * 64] - mx) - ls);
             const float G = c == y ? s_ga[c] : s_gb[c];
             d[c * 64] = p * (G - S) + wy * (p - (c == y ? 1.f : 0.f));
         }
@@ -332,9 +334,9 @@ __global__ void __launch_bounds__(256) k_loss_grad_reg(LossArgs g) {
         for (int c = 0; c < NC; ++c) { z[c] = c < g.ncls ? zp[c * 64] : 0.f; if (c < g.ncls) mx = fmaxf(mx, z[c]); }
 #pragma unroll
         for (int c = 0; c < NC; ++c) if (c < g.ncls) s += expf(z[c] - mx);
-        const float lse = mx + logf(s);
+        const float ls = logf(s);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) { z[c] = expf(z[c] - lse); if (c < g.ncls) S += z[c] * (c == y ? s_ga[c] : s_gb[c]); }     // z[c] is p[c] from here
+        for (int c = 0; c < NC; ++c) { z[c] = expf((z[c] - mx) - ls); if (c < g.ncls) S += z[c] * (c == y ? s_ga[c] : s_gb[c]); }     // z[c] is p[c] from here
         const float wy = use ? (g.cw ? g.cw[y] : 1.f) * ce_scale : 0.f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {

@@ -159,7 +159,10 @@ def _attn_run(qkv, Rh, Rw, dO, dev):
 
 @pytest.mark.parametrize("prec,qscale,nS", [(p, q, 1) for p in ("bf16", "fp16", "fp32") for q in (1.0, 7.5)] + [("bf16", 1.0, 3)])
 def test_attention_backward_every_output(cuda, prec, qscale, nS):
-    """qscale 7.5: |q . k| reaches about 7.5 * 8 * 8 = 480 before the scale, logits of about +-60.  nS = 3 with dO in every crop: the
+    """A norm test: each of dq, dk, dv, dRel_h, dRel_w enters as ONE relative L2 norm over the whole tensor, so "every output" means each
+    of the five tensors, not each element (dO is scaled by logspace(-2, 0) over the channels: head 0 holds 5e-5 of a tensor's energy,
+    and a fault confined to it passes here).  The elements are checked in tests/test_gpu_attn_bwd_every_element.py.
+    qscale 7.5: |q . k| reaches about 7.5 * 8 * 8 = 480 before the scale, logits of about +-60.  nS = 3 with dO in every crop: the
     table gradients are sums of the partials of three crops"""
     qkv, Rh, Rw, dO = _attn_case(nS, prec, 61, qscale)
     (dqkv, drh, drw), same = _attn_run(qkv, Rh, Rw, dO, cuda)
