@@ -186,6 +186,11 @@ SIGNATURES = {
     "cpx_blocks_backward_workspace_bytes_mp": (_sz, [_i, _i, _i, _i]),
     "cpx_blocks_backward_mp": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _sz, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "cpx_blocks_backward_in": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _sz, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "cpx_gather_crops": (_i, [_i, _p, _i, C.POINTER(_i), _i, _p, _p, _p]),
+    "cpx_scatter_crops": (_i, [_i, _p, _i, C.POINTER(_i), _i, _p, _p]),
+    "cpx_blocks_train_workspace_bytes_drop": (_sz, [_i, _i, _i]),
+    "cpx_blocks_forward_train_drop": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "cpx_blocks_backward_drop": (_i, [C.POINTER(CpxNetWeights), _p, _i, _i, _p, _p, _sz, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "cpx_embed_grad_layout": (C.c_longlong, [C.POINTER(C.c_longlong)]),
     "cpx_embed_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "cpx_embed_backward": (_i, [_i, _p, _p, _i, _i, _p, _p, _sz, _p]),

@@ -1247,13 +1247,10 @@ static void launch_gemm(const GemmArgs &a, hipStream_t s, bool f16) {
 
 // row statistics (sum, sum of squares) of a half-precision [rows][1024] matrix into slot 0 of
 // the [rows][4][2] layout the LN-folded GEMMs read (slots 1..3 zeroed).  One wave per row.
+// (a, b: the lane's 16 elements, columns 16 lane .. 16 lane + 15 of the row; every kernel that writes these statistics goes through here,
+// so they are the same partial sums in the same order)
 template <bool F16>
-__global__ void __launch_bounds__(256) k_row_stats(const unsigned short *__restrict__ x, int rows,
-                                                   float *__restrict__ st) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const unsigned short *xr = x + (size_t)row * 1024 + lane * 16;
-    const uint4 a = *reinterpret_cast<const uint4 *>(xr), b = *reinterpret_cast<const uint4 *>(xr + 8);
+__device__ __forceinline__ void row_stats_emit(const uint4 a, const uint4 b, int lane, size_t row, float *__restrict__ st) {
     const unsigned u[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     float sm = 0.f, sq = 0.f;
 #pragma unroll
@@ -1263,7 +1260,47 @@ __global__ void __launch_bounds__(256) k_row_stats(const unsigned short *__restr
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { sm += __shfl_xor(sm, o); sq += __shfl_xor(sq, o); }
-    if (lane < 4) *reinterpret_cast<float2 *>(st + ((size_t)row * LN_SLOTS + lane) * 2) = lane == 0 ? make_float2(sm, sq) : make_float2(0.f, 0.f);
+    if (lane < 4) *reinterpret_cast<float2 *>(st + (row * LN_SLOTS + lane) * 2) = lane == 0 ? make_float2(sm, sq) : make_float2(0.f, 0.f);
+}
+template <bool F16>
+__global__ void __launch_bounds__(256) k_row_stats(const unsigned short *__restrict__ x, int rows,
+                                                   float *__restrict__ st) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const unsigned short *xr = x + (size_t)row * 1024 + lane * 16;
+    const uint4 a = *reinterpret_cast<const uint4 *>(xr), b = *reinterpret_cast<const uint4 *>(xr + 8);
+    row_stats_emit<F16>(a, b, lane, (size_t)row, st);
+}
+
+// Crop compaction (layer drop, cpx_train_blocks.hip): the 1024 rows of each listed crop move between a full [crops][1024][1024] buffer and
+// a compact one that holds the listed crops alone, in list order.  One wave per row, NV 16-byte chunks per lane (2: a half type, 4:
+// float32), the lane's chunks adjacent so that a half-type lane holds the 16 elements row_stats_emit takes.  scatter 0: full -> compact
+// (STATS 1 bf16 / 2 fp16: the row statistics of the compact rows in the same pass); scatter 1: compact -> full.
+// grid (256 row groups, listed crops), 4 waves: no row index leaves the listed crops, which the host has checked against the crop count
+template <int NV, int STATS>
+__global__ void __launch_bounds__(256) k_move_crop_rows(const uint4 *__restrict__ src, uint4 *__restrict__ dst, CpxCropList list, int scatter,
+                                                        float *__restrict__ st) {
+    const int lane = threadIdx.x & 63, tok = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const size_t crow = (size_t)(list.first + blockIdx.y) * 1024 + tok, frow = (size_t)list.crop[blockIdx.y] * 1024 + tok;
+    const uint4 *s = src + (scatter ? crow : frow) * (64 * NV) + lane * NV;
+    uint4 *d = dst + (scatter ? frow : crow) * (64 * NV) + lane * NV;
+    uint4 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = s[i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) d[i] = v[i];
+    if constexpr (STATS != 0) row_stats_emit<STATS == 2>(v[0], v[1], lane, crow, st);
+}
+int cpx_move_crop_rows_run(int dtype, const void *src, void *dst, const CpxCropList &list, int scatter, float *stats, hipStream_t s) {
+    const dim3 grid(256, list.n), block(256);
+    const uint4 *a = (const uint4 *)src;
+    uint4 *b = (uint4 *)dst;
+    if (dtype == CPX_DT_F32) hipLaunchKernelGGL((k_move_crop_rows<4, 0>), grid, block, 0, s, a, b, list, scatter, stats);
+    else if (!stats || scatter) hipLaunchKernelGGL((k_move_crop_rows<2, 0>), grid, block, 0, s, a, b, list, scatter, stats);
+    else if (dtype == CPX_DT_F16) hipLaunchKernelGGL((k_move_crop_rows<2, 2>), grid, block, 0, s, a, b, list, scatter, stats);
+    else hipLaunchKernelGGL((k_move_crop_rows<2, 1>), grid, block, 0, s, a, b, list, scatter, stats);
+    CPX_CHECK_LAUNCH();
+    return CPX_OK;
 }
 int cpx_row_stats_half(int dtype, const void *x, int rows, float *stats, void *stream) {
     CPX_REQUIRE(x && stats && rows > 0 && (dtype == CPX_DT_BF16 || dtype == CPX_DT_F16));

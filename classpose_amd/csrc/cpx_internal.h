@@ -56,6 +56,13 @@ int cpx_conv3_half(int dtype, const void *x, const void *Wt, int M, int N, int C
                    void *out, int ld_out, void *stream);
 int cpx_row_stats_half(int dtype, const void *x, int rows, float *stats, void *stream);
 int cpx_gemm_half_uses_big_tile(int M, int N, int K, int epilogue);
+// Crop compaction (cpx_gemm.hip, next to the row statistics it shares its sums with): up to CPX_CROP_LIST crops per launch, the list by
+// value in the kernel arguments -- no device table, nothing that outlives the call.  crop[i]: the crop of the full buffer that is crop
+// first + i of the compact one.  scatter 0: full src -> compact dst, with the compact rows' statistics [rows][4][2] where stats is not
+// null (half types); scatter 1: compact src -> full dst.  The caller has checked every crop against the full buffer's crop count
+#define CPX_CROP_LIST 64
+struct CpxCropList { int n, first; int crop[CPX_CROP_LIST]; };
+int cpx_move_crop_rows_run(int dtype, const void *src, void *dst, const CpxCropList &list, int scatter, float *stats, hipStream_t s);
 // one-wave-per-SIMD 256^2 kernel (cpx_gemm4w.hip), bf16 / fp16: gelu(folded-LayerNorm(A) W^T + bias); 1 = launched, 0 = not this kernel's shape
 int cpx_gemm4w_gelu_ln(int f16, const void *A, const void *W, int M, int N, int K, const float *bias, const float *ln_stats, const float *ln_colsum,
                        void *out, int ld_out, hipStream_t s);

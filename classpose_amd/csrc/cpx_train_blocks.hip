@@ -541,6 +541,98 @@ extern "C" int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x,
 }
 
 // ---------------------------------------------------------------------------
+// layer drop (stochastic depth): a block runs on its kept crops alone
+// ---------------------------------------------------------------------------
+// The crops named by `crops` (host, n entries, strictly increasing, each < nS) between a full [nS * 1024][1024] buffer and a compact
+// [n * 1024][1024] one, in list order; the list travels in the kernel arguments, CPX_CROP_LIST crops per launch.
+static bool crop_list_ok(int dtype, int nS, const int *crops, int n) {
+    if (!dtype_ok(dtype) || nS <= 0 || (size_t)nS * 1024 >= 0x7fffffffull || n < 0 || n > nS || (n > 0 && !crops)) return false;
+    for (int i = 0; i < n; ++i)
+        if (crops[i] < 0 || crops[i] >= nS || (i > 0 && crops[i] <= crops[i - 1])) return false;
+    return true;
+}
+static int move_crops(int dtype, const void *src, void *dst, const int *crops, int n, int scatter, float *stats, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += CPX_CROP_LIST) {
+        CpxCropList l = {};
+        l.n = std::min(CPX_CROP_LIST, n - i0); l.first = i0;
+        for (int i = 0; i < l.n; ++i) l.crop[i] = crops[i0 + i];
+        CPX_RUN(cpx_move_crop_rows_run(dtype, src, dst, l, scatter, stats, s));
+    }
+    return CPX_OK;
+}
+extern "C" int cpx_gather_crops(int dtype, const void *src, int nS, const int *crops, int n, void *dst, float *stats, void *stream) {
+    CPX_REQUIRE(crop_list_ok(dtype, nS, crops, n) && (!stats || dtype != CPX_DT_F32));
+    if (n == 0) return CPX_OK;
+    CPX_REQUIRE(src && dst && (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)stats) & 15) == 0);
+    return move_crops(dtype, src, dst, crops, n, 0, stats, (hipStream_t)stream);
+}
+extern "C" int cpx_scatter_crops(int dtype, const void *src, int nS, const int *crops, int n, void *dst, void *stream) {
+    CPX_REQUIRE(crop_list_ok(dtype, nS, crops, n));
+    if (n == 0) return CPX_OK;
+    CPX_REQUIRE(src && dst && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0);
+    return move_crops(dtype, src, dst, crops, n, 1, nullptr, (hipStream_t)stream);
+}
+
+// keep [K][nS], host: keep[j * nS + n] != 0 where block first_block + j runs on crop n.  true: some (block, crop) pair is dropped
+static bool keep_drops(const unsigned char *keep, int K, int nS) {
+    if (keep)
+        for (size_t i = 0; i < (size_t)K * nS; ++i)
+            if (!keep[i]) return true;
+    return false;
+}
+// move_crops for the crops a mask row keeps, the list built launch by launch; *n_keep: how many there are
+static int move_kept(int dtype, const unsigned char *kj, int nS, const void *src, void *dst, int scatter, float *stats, hipStream_t s, int *n_keep) {
+    CpxCropList l = {};
+    int nk = 0;
+    for (int c = 0; c < nS; ++c) {
+        if (kj[c]) l.crop[l.n++] = c;
+        if (l.n == CPX_CROP_LIST || (c + 1 == nS && l.n)) {
+            l.first = nk;
+            CPX_RUN(cpx_move_crop_rows_run(dtype, src, dst, l, scatter, stats, s));
+            nk += l.n; l.n = 0;
+        }
+    }
+    *n_keep = nk;
+    return CPX_OK;
+}
+// the staging rows of a compacted block's output, behind the workspace of cpx_blocks_forward_train
+extern "C" size_t cpx_blocks_train_workspace_bytes_drop(int nS, int dtype, int K) {
+    if (!blocks_args_ok(nS, dtype, K)) return 0;
+    return blocks_fwd_layout(nS, dtype, K).total + cpx_align_up((size_t)nS * 1024 * 1024 * es_of(dtype), 256);
+}
+
+// cpx_blocks_forward_train with x_{j+1}[n] = keep[j][n] ? block_j(x_j[n]) : x_j[n].  No row of one crop meets a row of another inside a
+// block, so block j runs on its kept crops alone: they are gathered, in crop order, out of the running full-batch rows -- the x_out record
+// -- into the block's x_in record (with their row statistics where the weights fold LayerNorm: a compacted block has no GEMM before it
+// to emit them), the block runs on n_keep crops into the staging rows, and those are scattered back.  qkv, ao and x_mid of block j hold
+// n_keep_j * 1024 rows at the front of their records; a block that keeps nothing launches nothing.  The neck runs on all crops.
+extern "C" int cpx_blocks_forward_train_drop(const cpx_net_weights *w, const void *x, int nS, int first_block, const unsigned char *keep,
+                                             float *head, void *workspace, size_t workspace_bytes, void *stream) {
+    CPX_REQUIRE(blocks_weights_ok(w, first_block) && blocks_args_ok(nS, w->dtype, w->depth - first_block));
+    const int dt = w->dtype, K = w->depth - first_block, M = nS * 1024;
+    if (!keep_drops(keep, K, nS)) return cpx_blocks_forward_train(w, x, nS, first_block, head, workspace, workspace_bytes, stream);
+    CPX_REQUIRE(x && head && workspace);
+    const BlocksFwdLayout L = blocks_fwd_layout(nS, dt, K);
+    CPX_REQUIRE(workspace_bytes >= cpx_blocks_train_workspace_bytes_drop(nS, dt, K) && ((uintptr_t)workspace & 255) == 0 && ((uintptr_t)x & 15) == 0);
+    char *ws = (char *)workspace, *state = ws + L.off_out, *stage = ws + L.total;
+    hipStream_t hs = (hipStream_t)stream;
+    float *st = (float *)(ws + L.off_st);
+    CPX_HIP(hipMemcpyAsync(state, x, (size_t)M * 1024 * es_of(dt), hipMemcpyDeviceToDevice, hs));
+    for (int j = 0; j < K; ++j) {
+        const unsigned char *kj = keep + (size_t)j * nS;
+        char *base = ws + L.stride * (size_t)j;
+        int nk = 0;
+        CPX_RUN(move_kept(dt, kj, nS, state, base + L.o_x, 0, w->fuse_ln ? st : nullptr, hs, &nk));
+        if (!nk) continue;
+        const CpxBlockBufs t = {base + L.o_x, base + L.o_mid, stage, ws + L.off_xn, base + L.o_qkv, ws + L.off_vt, base + L.o_ao, ws + L.off_h, st};
+        CPX_RUN(cpx_net_block(w, first_block + j, nk, t, cpx_net_big_stats(w, nk), nullptr, stream));
+        if (dt != CPX_DT_F32) CPX_RUN(vt_to_rows_run(t.vt, t.qkv, nk, hs));
+        CPX_RUN(move_kept(dt, kj, nS, stage, state, 1, nullptr, hs, &nk));
+    }
+    return cpx_neck_forward_train(w, state, nS, head, ws + L.off_neck, L.neck_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------
 // small kernels of the block backward
 // ---------------------------------------------------------------------------
 // LayerNorm over 1024 channels of a stored row, two-pass float32 statistics as k_layernorm_f32 -> float32; gamma == nullptr: xhat alone.
@@ -785,9 +877,14 @@ extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
 //
 // dx_in (or NULL): [rows][1024] float32, the gradient of block first_block's input alone -- record 0 of dx_all without the other K records,
 // copied per slab from dx where that record is copied.  What the patch embedding's backward (cpx_embed_backward) takes when first_block is 0.
-extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
-                                      size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,
-                                      float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream) {
+//
+// keep (or NULL: every pair kept): the mask cpx_blocks_forward_train_drop ran with, [K][nS] on the host.  Per block and slab the body runs on
+// the slab's kept crops: both (adjacent in the compact records, which keep crop order), one (1024 rows, on that crop's half of dx) or
+// none (the body is skipped).  A slab's rows in block j's records start at 1024 times the kept crops of block j before it.  The dx rows
+// of a dropped crop pass down untouched, into dx_all and dx_in too; the gradients are still added in slab order, with no atomics.
+static int blocks_backward_run(const cpx_net_weights *w, const float *params, int nS, int first_block, const unsigned char *keep,
+                               const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype,
+                               float *grads, float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(blocks_weights_ok(w, first_block) && params && fwd_workspace && dy0 && grads && workspace && w->neck0_w);
     CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block) && grad_dtype_ok(w->dtype, grad_dtype));
     CPX_REQUIRE(attn_grad_dtype_ok(grad_dtype, attn_grad_dtype));
@@ -801,7 +898,7 @@ extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *par
     hipStream_t s = (hipStream_t)stream;
     const char *fws = (const char *)fwd_workspace;
     char *ws = (char *)workspace;
-    float *dx = (float *)(ws + L.dx), *dxl = (float *)(ws + L.dxl), *xn = (float *)(ws + L.xn), *xh = (float *)(ws + L.xh);
+    float *dx_slab = (float *)(ws + L.dx), *dxl = (float *)(ws + L.dxl), *xn = (float *)(ws + L.xn), *xh = (float *)(ws + L.xh);
     float *b1 = (float *)(ws + L.b1), *b2 = (float *)(ws + L.b2), *b3 = (float *)(ws + L.b3), *t1 = (float *)(ws + L.t1), *t2 = (float *)(ws + L.t2);
     float *wt = (float *)(ws + L.wt), *wop = (float *)(ws + L.wop), *tg = (float *)(ws + L.vec), *tb = tg + 1024, *ones = tg + 2048;
     void *dyb = ws + L.dyb, *hb = ws + L.hb, *xb = ws + L.xb, *wt16 = ws + L.wt16;
@@ -843,7 +940,7 @@ extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *par
         return cpx_gemm_half(CPX_DT_BF16, dyb, wt16, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, nullptr, nullptr, nullptr, stream);
     };
     // folded: dout is the gradient of xhat (gamma = 1 here; dgamma and dbeta come from k_unfold_grads after the last slab)
-    auto ln_bwd = [&](const void *x, const float *g, const float *dout, int Ms, float *dgamma, float *dbeta) -> int {
+    auto ln_bwd = [&](const void *x, const float *g, const float *dout, int Ms, float *dx, float *dgamma, float *dbeta) -> int {
         CPX_RUN(cpx_layernorm_backward(dt, x, fuse ? ones : g, dout, Ms, 1024, 1e-6f, dxl, tg, tb, ws + L.ln, L.ln_bytes, stream));
         if (!fuse) {
             CPX_RUN(add_run(dgamma, tg, 1024, dgamma, s));
@@ -857,25 +954,48 @@ extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *par
         return CPX_OK;
     };
     for (int c0 = 0; c0 < nS; c0 += BLK_SLAB) {
-        const int nc = std::min(BLK_SLAB, nS - c0), Ms = nc * 1024;
+        const int nc_slab = std::min(BLK_SLAB, nS - c0), Ms_slab = nc_slab * 1024;
         const size_t r0 = (size_t)c0 * 1024;
+        // record j of dx_all (and dx_in) takes the slab's rows as block j leaves them, dropped crops included
+        auto pass_down = [&](int j) -> int {
+            if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)j * rows_all + r0) * 1024, dx_slab, (size_t)Ms_slab * 4096, hipMemcpyDeviceToDevice, s));
+            if (dx_in && j == 0) CPX_HIP(hipMemcpyAsync(dx_in + r0 * 1024, dx_slab, (size_t)Ms_slab * 4096, hipMemcpyDeviceToDevice, s));
+            return CPX_OK;
+        };
         // the gradient of the last block's output: dy0 W0 (the rounded operand [256][1024], widened and transposed)
         if (g16) {
-            CPX_RUN(round16(dy0 + r0 * 256, (size_t)Ms * 256, dyb));
+            CPX_RUN(round16(dy0 + r0 * 256, (size_t)Ms_slab * 256, dyb));
             CPX_RUN(wt16_run(w->neck0_w, 256, 1024, 1024, wt16, s));
-            CPX_RUN(cpx_gemm_half(CPX_DT_BF16, dyb, wt16, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, nullptr, nullptr, nullptr, stream));
+            CPX_RUN(cpx_gemm_half(CPX_DT_BF16, dyb, wt16, Ms_slab, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx_slab, 1024, nullptr, nullptr, nullptr, stream));
         } else {
             CPX_RUN(cpx_wt_run(dt, w->neck0_w, 256, 1024, 1024, wt, s));
-            CPX_RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx, 1024, stream));
+            CPX_RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms_slab, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx_slab, 1024, stream));
         }
-        if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)K * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
+        if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)K * rows_all + r0) * 1024, dx_slab, (size_t)Ms_slab * 4096, hipMemcpyDeviceToDevice, s));
         for (int j = K - 1; j >= 0; --j) {
             const cpx_block_weights &b = w->blocks[first_block + j];
             const float *P = params + (size_t)gn * j;
             float *Gd = grads + (size_t)gn * j;
             const char *base = fws + F.stride * (size_t)j;
-            const void *xin = base + F.o_x + r0 * 1024 * es, *qkv = base + F.o_qkv + r0 * 3072 * es, *ao = base + F.o_ao + r0 * 1024 * es,
-                       *xmid = base + F.o_mid + r0 * 1024 * es;
+            // the slab's crops that this block ran on: nc of them, from row rb of the block's records, their gradient rows at dx
+            float *dx = dx_slab;
+            size_t rb = r0;
+            int nc = nc_slab;
+            if (keep) {
+                const unsigned char *kj = keep + (size_t)j * nS;
+                const int k0 = kj[c0] != 0, k1 = nc_slab > 1 && kj[c0 + 1] != 0;
+                nc = k0 + k1;
+                rb = 0;
+                for (int c = 0; c < c0; ++c) rb += kj[c] ? 1024 : 0;
+                if (!k0) dx += (size_t)1024 * 1024;                    // the second crop's half
+            }
+            if (!nc) {
+                CPX_RUN(pass_down(j));
+                continue;
+            }
+            const int Ms = nc * 1024;
+            const void *xin = base + F.o_x + rb * 1024 * es, *qkv = base + F.o_qkv + rb * 3072 * es, *ao = base + F.o_ao + rb * 1024 * es,
+                       *xmid = base + F.o_mid + rb * 1024 * es;
             // ---- the MLP: x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2 ----
             if (fuse) CPX_RUN(ln_fwd(xmid, nullptr, nullptr, Ms, xh, false));
             else CPX_RUN(ln_fwd(xmid, P + go[8], P + go[9], Ms, xn, half));
@@ -901,7 +1021,7 @@ extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *par
                 CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                // dpre
                 CPX_RUN(linear_bwd(b2, fuse ? xh : xn, CPX_DT_F32, fuse ? w1op : P + go[10], Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));   // fc1 -> d LN2 output (folded: d xhat)
             }
-            CPX_RUN(ln_bwd(xmid, P + go[8], b3, Ms, Gd + go[8], Gd + go[9]));                                                 // dx = d x_mid
+            CPX_RUN(ln_bwd(xmid, P + go[8], b3, Ms, dx, Gd + go[8], Gd + go[9]));                                                 // dx = d x_mid
             // ---- attention: x_mid = x_in + attention(LN1(x_in) Wqkv^T + bqkv) Wp^T + bp ----
             if (g16) CPX_RUN(linear_bwd16(dx, ao, b.proj_w, Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                       // proj -> dO (ao is stored in bf16)
             else CPX_RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
@@ -919,9 +1039,8 @@ extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *par
                 } else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, half));
                 CPX_RUN(linear_bwd(b1, fuse ? xh : xn, CPX_DT_F32, fuse ? wop : P + go[2], Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));       // qkv -> d LN1 output (folded: d xhat)
             }
-            CPX_RUN(ln_bwd(xin, P + go[0], b3, Ms, Gd + go[0], Gd + go[1]));                                                  // dx = d x_in
-            if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)j * rows_all + r0) * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
-            if (dx_in && j == 0) CPX_HIP(hipMemcpyAsync(dx_in + r0 * 1024, dx, (size_t)Ms * 4096, hipMemcpyDeviceToDevice, s));
+            CPX_RUN(ln_bwd(xin, P + go[0], b3, Ms, dx, Gd + go[0], Gd + go[1]));                                              // dx = d x_in
+            CPX_RUN(pass_down(j));
         }
     }
     if (fuse)                                                          // the W slots hold dWf, the b slots dbf, summed over the slabs
@@ -934,6 +1053,22 @@ extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *par
             CPX_CHECK_LAUNCH();
         }
     return CPX_OK;
+}
+extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
+                                      size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,
+                                      float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream) {
+    return blocks_backward_run(w, params, nS, first_block, nullptr, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype, grads,
+                               dx_all, dx_in, workspace, workspace_bytes, stream);
+}
+// cpx_blocks_backward_in for a forward of cpx_blocks_forward_train_drop with the same keep (NULL or all ones: cpx_blocks_backward_in itself)
+extern "C" int cpx_blocks_backward_drop(const cpx_net_weights *w, const float *params, int nS, int first_block, const unsigned char *keep,
+                                        const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dy0, int grad_dtype,
+                                        int attn_grad_dtype, float *grads, float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+    CPX_REQUIRE(blocks_weights_ok(w, first_block) && blocks_args_ok(nS, w->dtype, w->depth - first_block));
+    if (!keep_drops(keep, w->depth - first_block, nS)) keep = nullptr;
+    return blocks_backward_run(w, params, nS, first_block, keep, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype, grads,
+                               dx_all, dx_in, workspace, workspace_bytes, stream);
 }
 extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                       size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,

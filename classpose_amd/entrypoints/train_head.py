@@ -4,7 +4,7 @@ everything else frozen -- the reference's ``--freeze backbone segmentation_head 
 
     python -m classpose_amd.entrypoints.train_head --images X.npy --labels Y.npy --pretrained_model CKPT \\
         --n_epochs 100 --batch_size 8 --save_path DIR --model_name NAME --device cuda:0 [--augment hed_only --scale_range 0.5] \\
-        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K [--grad_precision bf16 [--attn_grad_precision bf16]] [--train_embed]]
+        [--instances I.npy --auto_class_weights --oversampling_method custom --rescale --min_train_masks 1] [--train_neck] [--train_blocks K [--grad_precision bf16 [--attn_grad_precision bf16]] [--train_embed] [--layer_drop 0.4]]
     python -m classpose_amd.entrypoints.train_head --data_path DIR [--test_data_path DIR] [--train_fraction 0.8] \
         [--subsample_fraction F] --pretrained_model CKPT --augment hed_only ... (everything else as above)
 
@@ -143,6 +143,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the embedding only through every block; not with a UNet class head.  The cache then holds patch rows (384 KB per "
                         "crop in bf16) and every step runs the whole network.  With --train_flow_head this is what the reference trains "
                         "without --freeze.  --grad_precision bf16 also runs the embedding's weight gradient on bf16 operands")
+    p.add_argument("--layer_drop", type=float, default=0.0, metavar="RATE",
+                   help="with --train_blocks: stochastic depth.  Every step drops whole trained blocks per crop, block i of the network "
+                        "with probability linspace(0, RATE, depth)[i]; a dropped (block, crop) pair is not computed, forward or "
+                        "backward.  The reference trains with 0.4 (rdrop); the default 0 drops nothing.  Only the trained blocks "
+                        "drop (the frozen ones are cached); validation never drops; the masks are seeded from --random_seed")
     p.add_argument("--freeze", nargs="+", default=None, choices=["none", "backbone", "segmentation_head", "neck"],
                    help="the reference's spelling of the same choice: 'backbone neck' = --train_flow_head, 'backbone "
                         "segmentation_head neck' = the default (class head only); nothing else is built")
@@ -214,6 +219,12 @@ def check_args(args) -> None:
     if args.attn_grad_precision == "bf16" and args.grad_precision != "bf16":
         raise SystemExit("--attn_grad_precision bf16 needs --grad_precision bf16: it is the last float32 product of the bf16 backward of "
                          "the trained blocks, not a mode of the float32 backward")
+    args.layer_drop = float(getattr(args, "layer_drop", 0.0) or 0.0)
+    if not 0.0 <= args.layer_drop < 1.0:
+        raise SystemExit(f"--layer_drop: a rate in [0, 1), not {args.layer_drop} (the reference's rdrop is 0.4)")
+    if args.layer_drop > 0 and not args.train_blocks:
+        raise SystemExit("--layer_drop goes with --train_blocks K: it drops trained transformer blocks per crop (the frozen blocks run "
+                         "once, into the cache, and stay deterministic)")
     args.train_embed = bool(getattr(args, "train_embed", False))
     if args.train_embed:
         if getattr(args, "feature_transformation_structure", None) is not None:
@@ -342,19 +353,28 @@ def _host_maps(instances):
 def _trainer_of(args, make_trainer, nclasses):
     """The trainer the arguments ask for; a block count the checkpoint does not have ends the run with the reason."""
     try:
-        return make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
-                            feature_transformation_structure=args.feature_transformation_structure,
-                            class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
-                            train_neck=args.train_neck, train_blocks=args.train_blocks,
-                            **({"grad_precision": "bf16"} if getattr(args, "grad_precision", "fp32") == "bf16" else {}),
-                            **({"attn_grad_precision": "bf16"} if getattr(args, "attn_grad_precision", "fp32") == "bf16" else {}),
-                            **({"train_embed": True} if getattr(args, "train_embed", False) else {}))
+        trainer = make_trainer(args.pretrained_model, nclasses=nclasses, device=args.device, precision=args.precision,
+                               feature_transformation_structure=args.feature_transformation_structure,
+                               class_weights=args.class_weights, weight_decay=args.weight_decay, train_flow_head=args.train_flow_head,
+                               train_neck=args.train_neck, train_blocks=args.train_blocks,
+                               **({"grad_precision": "bf16"} if getattr(args, "grad_precision", "fp32") == "bf16" else {}),
+                               **({"attn_grad_precision": "bf16"} if getattr(args, "attn_grad_precision", "fp32") == "bf16" else {}),
+                               **({"train_embed": True} if getattr(args, "train_embed", False) else {}),
+                               **({"layer_drop": args.layer_drop, "layer_drop_seed": args.random_seed} if getattr(args, "layer_drop", 0.0) > 0 else {}))
     except (ValueError, NotImplementedError) as e:
         if getattr(args, "train_embed", False) and "train_embed" in str(e):
             raise SystemExit(f"--train_embed: {e}")
         if args.train_blocks and "train_blocks" in str(e):
             raise SystemExit(f"--train_blocks {args.train_blocks}: {e}")
         raise
+    if getattr(args, "layer_drop", 0.0) > 0:
+        from ..train import layer_drop_probs
+        depth, K = trainer.weights.depth, trainer.train_blocks
+        probs = layer_drop_probs(depth, args.layer_drop)[depth - K:]
+        logger.info(f">>> --layer_drop {args.layer_drop:g}: blocks {depth - K} to {depth - 1} of {depth} are dropped per crop with "
+                    f"probabilities {', '.join(f'{v:.4f}' for v in probs)} ({probs.mean():.1%} of the trained (block, crop) pairs on "
+                    f"average), masks seeded with {args.random_seed}" + ("" if K == depth else "; the frozen blocks never drop"))
+    return trainer
 
 
 def main_data_path(args) -> None:

@@ -943,21 +943,79 @@ def block_grad_layout() -> tuple[int, list[int]]:
 class BlocksForwardOut:
     """Results of ``blocks_forward_train``: ``head`` float32 (rows, ld_head); per trained block views ``x[j]``, ``qkv[j]``, ``ao[j]``,
     ``x_mid[j]`` into ``workspace`` (the block's input, qkv rows, attention output, rows after the attention residual); ``x_out``, the
-    last block's output (the neck's input); and ``neck``, the ``NeckForwardOut`` of the tail."""
-    __slots__ = ("head", "x", "qkv", "ao", "x_mid", "x_out", "neck", "workspace", "first_block")
+    last block's output (the neck's input); and ``neck``, the ``NeckForwardOut`` of the tail.  ``keep``: None, or the layer-drop mask
+    (K, n) uint8 numpy the forward ran with, and ``n_keep`` the K counts of kept crops (n everywhere without a mask): the views of block
+    j stay full-size and hold the block's kept crops, compacted in crop order, in their first ``n_keep[j] * 1024`` rows."""
+    __slots__ = ("head", "x", "qkv", "ao", "x_mid", "x_out", "neck", "workspace", "first_block", "keep", "n_keep")
 
 
-def blocks_train_workspace(n_subtiles: int, dtype_code: int, n_blocks: int, device) -> torch.Tensor:
-    n = _lib.lib().cpx_blocks_train_workspace_bytes(n_subtiles, dtype_code, n_blocks)
+def blocks_train_workspace(n_subtiles: int, dtype_code: int, n_blocks: int, device, drop: bool = False) -> torch.Tensor:
+    """The workspace of ``blocks_forward_train``; ``drop``: with the staging rows a ``keep`` mask needs behind it."""
+    L = _lib.lib()
+    n = (L.cpx_blocks_train_workspace_bytes_drop if drop else L.cpx_blocks_train_workspace_bytes)(n_subtiles, dtype_code, n_blocks)
     if n == 0:
         raise ValueError("blocks_train_workspace: invalid n_subtiles / dtype / n_blocks")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+def _crop_list(crops):
+    """a crop list -> (int32 numpy, its ctypes pointer); the array must outlive the call"""
+    a = np.ascontiguousarray(np.asarray(crops, dtype=np.int64).reshape(-1).astype(np.int32))
+    return a, a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _crop_rows(t: torch.Tensor, what: str) -> int:
+    if t.dim() != 2 or t.shape[1] != 1024 or t.shape[0] % 1024 or t.dtype not in _DT or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"{what}: contiguous device rows (n * 1024, 1024) in bf16, fp16 or float32")
+    return t.shape[0] // 1024
+
+
+def gather_crops(src: torch.Tensor, crops, dst: torch.Tensor | None = None, stats: torch.Tensor | None = None) -> torch.Tensor:
+    """``cpx_gather_crops``: the rows of the crops ``crops`` (strictly increasing indices) of the full ``src`` (n * 1024, 1024) into the
+    compact ``dst`` (len(crops) * 1024, 1024), in list order.  ``stats`` (len(crops) * 1024, 4, 2) float32, for a half type: the row
+    statistics of the gathered rows in the same pass, bitwise ``cpx_row_stats`` of them."""
+    nS = _crop_rows(src, "gather_crops: src")
+    a, pa = _crop_list(crops)
+    if dst is None:
+        dst = torch.empty((a.size * 1024, 1024), dtype=src.dtype, device=src.device)
+    if dst.dtype != src.dtype or dst.device != src.device or _crop_rows(dst, "gather_crops: dst") < a.size:
+        raise ValueError("gather_crops: dst holds len(crops) * 1024 rows of src's dtype on its device")
+    if stats is not None and (stats.dtype != torch.float32 or stats.numel() < a.size * 1024 * 8 or not stats.is_contiguous()
+                              or stats.device != src.device):
+        raise ValueError("gather_crops: stats is contiguous float32 (len(crops) * 1024, 4, 2)")
+    check(_lib.lib().cpx_gather_crops(_DT[src.dtype], ptr(src), nS, pa, a.size, ptr(dst), ptr(stats), _stream(src.device)), "gather_crops")
+    return dst
+
+
+def scatter_crops(src: torch.Tensor, crops, dst: torch.Tensor) -> torch.Tensor:
+    """``cpx_scatter_crops``: the compact rows ``src`` (len(crops) * 1024, 1024) back to the crops ``crops`` of the full ``dst``
+    (n * 1024, 1024); the other crops of ``dst`` are untouched."""
+    nS = _crop_rows(dst, "scatter_crops: dst")
+    a, pa = _crop_list(crops)
+    if src.dtype != dst.dtype or src.device != dst.device or _crop_rows(src, "scatter_crops: src") < a.size:
+        raise ValueError("scatter_crops: src holds len(crops) * 1024 rows of dst's dtype on its device")
+    check(_lib.lib().cpx_scatter_crops(_DT[dst.dtype], ptr(src), nS, pa, a.size, ptr(dst), _stream(dst.device)), "scatter_crops")
+    return dst
+
+
+def _keep_mask(keep, K: int, n: int, what: str):
+    """a layer-drop mask -> contiguous uint8 numpy (K, n) of 0 / 1 (None stays None)"""
+    if keep is None:
+        return None
+    if isinstance(keep, torch.Tensor):
+        keep = keep.cpu().numpy()
+    keep = np.asarray(keep)
+    if keep.shape != (K, n) or keep.dtype.kind not in "ub":
+        raise ValueError(f"{what}: keep is a uint8 array ({K}, {n}) = (trained blocks, crops), not {keep.dtype} {keep.shape}")
+    return np.ascontiguousarray(keep != 0, dtype=np.uint8)
+
+
 def blocks_forward_train(weights, x: torch.Tensor, first_block: int, head: torch.Tensor | None = None,
-                         workspace: torch.Tensor | None = None) -> BlocksForwardOut:
+                         workspace: torch.Tensor | None = None, keep=None) -> BlocksForwardOut:
     """``cpx_blocks_forward_train``: blocks ``first_block`` .. depth - 1 of ``weights`` (an ``engine.NetWeights``) and the tail on the rows
-    ``x`` (n * 1024, 1024) in the network dtype -- the input of block ``first_block`` --, keeping what the backward needs."""
+    ``x`` (n * 1024, 1024) in the network dtype -- the input of block ``first_block`` --, keeping what the backward needs.  ``keep``
+    (K, n) uint8, host: layer drop (``cpx_blocks_forward_train_drop``), block j runs on crop i where ``keep[j, i]`` is non-zero and
+    passes the other crops through; the workspace is then ``blocks_train_workspace(..., drop=True)``."""
     c, L = weights.c, _lib.lib()
     if x.dim() != 2 or x.shape[1] != 1024 or x.shape[0] == 0 or x.shape[0] % 1024 or x.dtype not in _DT or _DT[x.dtype] != c.dtype \
             or not x.is_contiguous() or not x.is_cuda:
@@ -967,14 +1025,19 @@ def blocks_forward_train(weights, x: torch.Tensor, first_block: int, head: torch
     if not 0 <= first_block < c.depth:
         raise ValueError(f"blocks_forward_train: first_block {first_block} outside 0 .. {c.depth - 1}")
     rows, nS, dev, K = x.shape[0], x.shape[0] // 1024, x.device, c.depth - first_block
+    keep = _keep_mask(keep, K, nS, "blocks_forward_train")
     if workspace is None:
-        workspace = blocks_train_workspace(nS, c.dtype, K, dev)
+        workspace = blocks_train_workspace(nS, c.dtype, K, dev, drop=keep is not None)
     if head is None:
         head = torch.empty((rows, c.ld_head), dtype=torch.float32, device=dev)
     if head.dtype != torch.float32 or tuple(head.shape) != (rows, c.ld_head) or not head.is_contiguous() or workspace.dtype != torch.uint8:
         raise ValueError("blocks_forward_train: head must be contiguous float32 (rows, ld_head) and workspace uint8")
-    check(L.cpx_blocks_forward_train(C.byref(c), ptr(x), nS, first_block, ptr(head), ptr(workspace), workspace.numel(), _stream(dev)),
-          "blocks_forward_train")
+    if keep is None:
+        check(L.cpx_blocks_forward_train(C.byref(c), ptr(x), nS, first_block, ptr(head), ptr(workspace), workspace.numel(), _stream(dev)),
+              "blocks_forward_train")
+    else:
+        check(L.cpx_blocks_forward_train_drop(C.byref(c), ptr(x), nS, first_block, keep.ctypes.data, ptr(head), ptr(workspace),
+                                              workspace.numel(), _stream(dev)), "blocks_forward_train (keep)")
     off = (C.c_size_t * (4 * K + 2))()
     check(L.cpx_blocks_train_layout(nS, c.dtype, K, off), "blocks_train_layout")
     es = x.element_size()
@@ -983,6 +1046,7 @@ def blocks_forward_train(weights, x: torch.Tensor, first_block: int, head: torch
         return workspace[o:o + rows * width * es].view(x.dtype).view(rows, width)
     o = BlocksForwardOut()
     o.head, o.workspace, o.first_block = head, workspace, first_block
+    o.keep, o.n_keep = keep, [nS] * K if keep is None else [int(v) for v in keep.sum(axis=1)]
     o.x, o.qkv, o.ao, o.x_mid = ([view(off[4 * j + i], wd) for j in range(K)] for i, wd in enumerate((1024, 3072, 1024, 1024)))
     o.x_out = view(off[4 * K], 1024)
     nb = L.cpx_neck_train_workspace_bytes(nS, c.dtype)
@@ -1037,7 +1101,8 @@ def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: t
     products of ``cpx_blocks_backward``; torch.bfloat16 (a bf16 network only): every product on bf16 operands with float32 accumulation.
     ``attn_grad_dtype`` torch.bfloat16 (with ``grad_dtype`` torch.bfloat16 only): the attention backward on bf16 operands too
     (``cpx_attention_backward_bf16``); torch.float32 leaves it in float32.  ``dx_in`` (rows, 1024) float32, when given, receives the
-    gradient of the first trained block's input alone (record 0 of ``dx_all`` without the rest): what ``embed_backward`` takes."""
+    gradient of the first trained block's input alone (record 0 of ``dx_all`` without the rest): what ``embed_backward`` takes.
+    A forward under a layer-drop mask (``fwd.keep``) gets ``cpx_blocks_backward_drop`` with that mask."""
     c, L = weights.c, _lib.lib()
     gd = _grad_dtype_code(grad_dtype, c.dtype, "blocks_backward")
     ad = _attn_grad_dtype_code(attn_grad_dtype, gd, "blocks_backward")
@@ -1062,9 +1127,15 @@ def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: t
     if workspace.dtype != torch.uint8 or fwd.workspace.dtype != torch.uint8:
         raise ValueError("blocks_backward: workspaces are uint8 tensors")
     # (cpx_blocks_backward_mp is this entry with dx_in NULL)
-    check(L.cpx_blocks_backward_in(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
-                                   gd, ad, ptr(grads), ptr(dx_all), ptr(dx_in), ptr(workspace), workspace.numel(), _stream(dev)),
-          "blocks_backward")
+    keep = getattr(fwd, "keep", None)                      # (a BlocksForwardOut put together by hand has no mask)
+    if keep is None:
+        check(L.cpx_blocks_backward_in(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
+                                       gd, ad, ptr(grads), ptr(dx_all), ptr(dx_in), ptr(workspace), workspace.numel(), _stream(dev)),
+              "blocks_backward")
+    else:
+        check(L.cpx_blocks_backward_drop(C.byref(c), ptr(params), rows // 1024, fwd.first_block, keep.ctypes.data, ptr(fwd.workspace),
+                                         fwd.workspace.numel(), ptr(dy0), gd, ad, ptr(grads), ptr(dx_all), ptr(dx_in), ptr(workspace),
+                                         workspace.numel(), _stream(dev)), "blocks_backward (keep)")
     return grads
 
 

@@ -23,7 +23,8 @@ training forward and ``cpx_neck_backward``.
 
 ``train_blocks=K`` also trains the last K transformer blocks (``BlockParams``) and, with K = depth, ``train_embed=True`` the
 patch embedding and the position table (``EmbedParams``): the cache then holds patch rows and every step runs the whole
-network, which with ``train_flow_head`` is the reference's run without ``--freeze``.
+network, which with ``train_flow_head`` is the reference's run without ``--freeze``.  ``layer_drop=rate`` then drops trained blocks
+per crop as the reference's ``net.train()`` does (``layer_drop_probs``, ``draw_keep_mask``, ``step(keep=)``).
 
 ``train_flow_head=True`` also trains the flow head ``out`` (``FlowHead``): the reference's ``--freeze backbone neck``, seg + CE +
 Tversky with multiplier 1 each (train.py:482-493), the seg loss being cellpose's ``_loss_fn_seg`` restated (``ops.seg_loss``).
@@ -384,6 +385,39 @@ class EmbedParams:
         return {EMBED_KEYS[0]: v[0].reshape(1024, 3, 8, 8), EMBED_KEYS[1]: v[1], EMBED_KEYS[2]: v[2].reshape(1, 32, 32, 1024)}
 
 
+def layer_drop_probs(depth: int, rate: float) -> np.ndarray:
+    """The probability with which each of ``depth`` blocks is dropped per crop (vit_sam.py:165, ``torch.linspace(0, rdrop, nlay)``):
+    float64 (depth,), 0 for block 0 up to ``rate`` for the last."""
+    if int(depth) < 1:
+        raise ValueError(f"layer_drop_probs: depth {depth} is not a count of blocks")
+    if not 0.0 <= float(rate) < 1.0:
+        raise ValueError(f"layer_drop: a rate in [0, 1), not {rate!r}")
+    return np.linspace(0.0, float(rate), int(depth), dtype=np.float64)
+
+
+def draw_keep_mask(rng, n: int, depth: int, K: int, rate: float):
+    """One layer-drop mask for ``n`` crops and the last ``K`` of ``depth`` blocks: uint8 (K, n), 1 where the block runs on the crop.
+    Block i is dropped where a uniform draw is strictly below ``layer_drop_probs(depth, rate)[i]``, its ABSOLUTE index -- the
+    reference's ``torch.rand((n, nlay)) < torch.linspace(0, rdrop, nlay)`` restricted to the trained blocks (its own random stream is
+    not reproduced).  One ``rng.random((n, K))`` per mask; rate 0 returns None without drawing."""
+    if not 1 <= int(K) <= int(depth):
+        raise ValueError(f"draw_keep_mask: K = {K} trained blocks of depth {depth}")
+    p = layer_drop_probs(depth, rate)[int(depth) - int(K):]
+    if float(rate) == 0.0:
+        return None
+    u = np.asarray(rng.random((int(n), int(K))), dtype=np.float64)
+    return np.ascontiguousarray(~(u < p[None, :]).T, dtype=np.uint8)
+
+
+def check_layer_drop(layer_drop: float, train_blocks: int) -> None:
+    """``layer_drop`` is a rate in [0, 1) and, above 0, needs trained blocks; raises ``ValueError`` with the reason otherwise."""
+    if not 0.0 <= float(layer_drop) < 1.0:
+        raise ValueError(f"layer_drop: a rate in [0, 1), not {layer_drop!r} (the reference's rdrop is 0.4)")
+    if float(layer_drop) > 0.0 and int(train_blocks) <= 0:
+        raise ValueError("layer_drop drops trained transformer blocks per crop: it needs train_blocks > 0 (the frozen blocks run once, "
+                         "into the cache, and stay deterministic)")
+
+
 def _of_class_group(name: str) -> property:
     return property(lambda self: getattr(self.groups[0], name))
 
@@ -403,7 +437,7 @@ class HeadTrainer:
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
                  head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, train_flow_head: bool = False,
                  train_neck: bool = False, train_blocks: int = 0, grad_precision: str = "fp32", attn_grad_precision: str = "fp32",
-                 train_embed: bool = False):
+                 train_embed: bool = False, layer_drop: float = 0.0, layer_drop_seed: int = 0):
         self.device = torch.device(device)
         self.train_embed = bool(train_embed)
         self.train_blocks = int(train_blocks)
@@ -416,6 +450,9 @@ class HeadTrainer:
         # ``attn_grad_precision`` = "bf16" (with ``grad_precision`` "bf16"): the attention backward on bf16 operands too
         check_attn_grad_precision(attn_grad_precision, grad_precision)
         self.attn_grad_precision = attn_grad_precision
+        # ``layer_drop`` = rate > 0: every ``step`` drops trained blocks per crop (stochastic depth) under a mask drawn from a
+        # generator of the trainer's own; at 0 nothing is ever drawn.  ``evaluate`` never drops
+        self.set_layer_drop(layer_drop, layer_drop_seed)
         train_neck = bool(train_neck) or self.train_blocks > 0           # the blocks' gradient comes through the neck
         if self.device.type != "cuda":
             raise RuntimeError("the head is trained by HIP kernels: pass a cuda device (there is no CPU path)")
@@ -468,6 +505,13 @@ class HeadTrainer:
         return self._L.cpx_net_workspace_bytes(nS, self.weights.c.dtype)
 
     w, b, m_w, v_w, m_b, v_b = (_of_class_group(n) for n in ("w", "b", "m_w", "v_w", "m_b", "v_b"))
+
+    def set_layer_drop(self, layer_drop: float, layer_drop_seed: int = 0) -> None:
+        """The layer-drop rate of the following steps and a fresh ``np.random.default_rng(layer_drop_seed)`` for their masks."""
+        check_layer_drop(layer_drop, self.train_blocks)
+        self.layer_drop = float(layer_drop)
+        self.layer_drop_seed = layer_drop_seed
+        self._drop_rng = np.random.default_rng(layer_drop_seed)
 
     def set_diam_labels(self, diameters) -> None:
         """With the flow head training, ``diam_labels`` of the saved checkpoint becomes the mean diameter of the training set
@@ -557,9 +601,9 @@ class HeadTrainer:
         ``train_embed`` caches (384 KB per crop in bf16, against 2 MB of backbone rows)."""
         return self._patches(X)
 
-    def _blocks_forward(self, X):
+    def _blocks_forward(self, X, keep=None):
         """The training forward of the last K blocks and the tail on the rows of ``X``: (x_out, the tail's ``ops.NeckForwardOut``).
-        With ``train_embed`` it starts from patch rows, which are kept for the embedding's backward."""
+        With ``train_embed`` it starts from patch rows, which are kept for the embedding's backward.  ``keep``: a layer-drop mask."""
         if self.embed is not None:
             self._rows = self._as_rows(X, 192, "patch rows")
             key = ("emb_x", self._rows.shape[0])
@@ -570,11 +614,14 @@ class HeadTrainer:
             x = self._as_rows(X, 1024, "backbone rows")
         rows, c = x.shape[0], self.weights.c
         key = ("blk_fwd", rows)
+        if key in self._buf and keep is not None and not self._buf[key][2]:
+            del self._buf[key]                            # (a mask on a trainer that has run without one: the workspace gains its staging rows)
         if key not in self._buf:
+            drop = keep is not None or self.layer_drop > 0
             self._buf[key] = (torch.empty((rows, c.ld_head), dtype=torch.float32, device=self.device),
-                              ops.blocks_train_workspace(rows // TOKENS, c.dtype, self.train_blocks, self.device))
-        head, ws = self._buf[key]
-        self._bfwd = ops.blocks_forward_train(self.weights, x, c.depth - self.train_blocks, head=head, workspace=ws)
+                              ops.blocks_train_workspace(rows // TOKENS, c.dtype, self.train_blocks, self.device, drop=drop), drop)
+        head, ws, _drop = self._buf[key]
+        self._bfwd = ops.blocks_forward_train(self.weights, x, c.depth - self.train_blocks, head=head, workspace=ws, keep=keep)
         return self._bfwd.x_out, self._bfwd.neck
 
     def _blocks_backward(self) -> None:
@@ -651,10 +698,10 @@ class HeadTrainer:
                                torch.cuda.current_stream(self.device).cuda_stream), "head gemm")
         return out
 
-    def _loss(self, X, labels):
+    def _loss(self, X, labels, keep=None):
         self._fwd = None
         if self.neck is not None:
-            x, fwd = self._blocks_forward(X) if self.blocks is not None else self._neck_forward(X)
+            x, fwd = self._blocks_forward(X, keep) if self.blocks is not None else self._neck_forward(X)
             self._fwd = (x, fwd)
             feat = fwd.feat
         else:
@@ -702,11 +749,27 @@ class HeadTrainer:
             r["head"] = head
         return r
 
-    def step(self, X, labels, lr: float, flow_targets=None) -> dict:
+    def _step_mask(self, labels, keep):
+        """The layer-drop mask of one step: the explicit ``keep`` (K, n), else one draw at the trainer's rate (None at rate 0)."""
+        if keep is None and self.layer_drop == 0.0:
+            return None
+        if self.blocks is None:
+            raise ValueError("keep: the trainer was built without train_blocks, there is no block to drop")
+        n = len(labels)
+        if keep is None:
+            return draw_keep_mask(self._drop_rng, n, self.weights.depth, self.train_blocks, self.layer_drop)
+        shape = tuple(getattr(keep, "shape", ()))
+        if shape != (self.train_blocks, n):
+            raise ValueError(f"keep: a uint8 mask ({self.train_blocks}, {n}) = (trained blocks, crops), not {shape}")
+        return keep
+
+    def step(self, X, labels, lr: float, flow_targets=None, keep=None) -> dict:
         """One optimisation step on a batch of crops (or of cached ``features``) at learning rate ``lr``; returns the losses of the
         batch BEFORE the update, like the reference's loop.  With ``flow_targets`` (see ``evaluate``) the flow head takes the same
-        step from the seg loss: same step counter, betas and weight decay; without them it does not move."""
-        feat, head, o = self._loss(X, labels)             # raises before anything is updated
+        step from the seg loss: same step counter, betas and weight decay; without them it does not move.  ``keep`` (train_blocks, n)
+        uint8: the layer-drop mask of this step (block j runs on crop i where ``keep[j, i]``); without it one is drawn when the
+        trainer's ``layer_drop`` is above 0.  The losses are those of the dropped forward."""
+        feat, head, o = self._loss(X, labels, self._step_mask(labels, keep))             # raises before anything is updated
         seg = self._seg_loss(head, flow_targets)          # (so does this)
         # every gradient from the operands of THIS forward (the neck's backward reads ``head_w``): before any refresh
         if self.neck is not None:
@@ -887,7 +950,7 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
                      save_path=None, model_name: str | None = None, random_seed: int = 42, transform=None,
                      augment: str | None = None, scale_range: float = 0.5, label_fill: int = 0, train_probs=None, diameters=None,
                      diam_mean: float = 30.0, rescale: bool = False, train_flow_head: bool = False, instances=None,
-                     test_instances=None):
+                     test_instances=None, layer_drop: float | None = None, layer_drop_seed: int | None = None):
     """The epoch loop of train.py:606-655 for the frozen-backbone mode: per-epoch learning rate from ``lr_schedule``, seeded sampling
     without replacement (with, when ``nimg_per_epoch`` exceeds the set), sample-weighted running means of CE / Tversky / total,
     validation once per epoch, ``checkpoint_last.pt`` and ``checkpoint_best.pt`` (lowest validation loss; training loss without a
@@ -917,7 +980,11 @@ def train_class_head(trainer: HeadTrainer, images, labels, test_images=None, tes
     with the crops; ``augment.flow_targets_of``, once) or, for an ``ImagePool``, from the pool itself (built with ``instances``);
     an augmented batch warps them with the crop, everything else uses plain windows of the stored planes.  ``transform`` is refused
     (a host callback cannot move the targets).  ``diameters``, when given, also set the checkpoint's ``diam_labels``.
+    ``layer_drop`` / ``layer_drop_seed``, when given, go to ``trainer.set_layer_drop`` (the seed defaults to ``random_seed``) before the
+    first step; left at None the trainer keeps the rate and the generator it was built with.  Validation never drops.
     Returns ``(path of the final model, train_losses, test_losses)``."""
+    if layer_drop is not None:
+        trainer.set_layer_drop(layer_drop, random_seed if layer_drop_seed is None else layer_drop_seed)
     if train_flow_head:
         if trainer.flow is None:
             raise ValueError("train_flow_head=True needs a trainer built with train_flow_head=True")

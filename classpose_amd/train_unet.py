@@ -261,7 +261,8 @@ class UNetHeadTrainer(HeadTrainer):
     def __init__(self, pretrained_model, nclasses: int | None = None, device="cuda:0", precision: str = "bf16", class_weights=None,
                  weight_decay: float = 0.1, alpha: float = 0.3, gamma: float = 1.33, eps: float = 1e-6, feature_batch: int = 8,
                  head_seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, feature_transformation_structure=None,
-                 train_flow_head: bool = False, train_neck: bool = False, train_blocks: int = 0, train_embed: bool = False):
+                 train_flow_head: bool = False, train_neck: bool = False, train_blocks: int = 0, train_embed: bool = False,
+                 layer_drop: float = 0.0, layer_drop_seed: int = 0):
         if train_embed:
             raise NotImplementedError("train_embed: the UNet head's backward gives the neck output no gradient, so none reaches the "
                                       "blocks or the patch embedding; they train under the 1x1 class head only")
@@ -273,7 +274,7 @@ class UNetHeadTrainer(HeadTrainer):
                                       "under the 1x1 class head only")
         self._structure = feature_transformation_structure
         super().__init__(pretrained_model, nclasses, device, precision, class_weights, weight_decay, alpha, gamma, eps, feature_batch,
-                         head_seed, betas, adam_eps, train_flow_head=train_flow_head)
+                         head_seed, betas, adam_eps, train_flow_head=train_flow_head, layer_drop=layer_drop, layer_drop_seed=layer_drop_seed)
 
     def _prepare(self, pretrained_model, nclasses, head_seed) -> tuple[dict, int]:
         sd, ncls, self.fts = prepare_unet_state_dict(pretrained_model, nclasses, head_seed, self._structure)

@@ -744,6 +744,38 @@ long long cpx_embed_grad_layout(long long *off /* [3] or NULL */);
 size_t cpx_embed_backward_workspace_bytes(int n_subtiles, int dtype, int grad_dtype);
 int cpx_embed_backward(int dtype, const void *patches, const float *dx_in, int n_subtiles, int grad_dtype, float *grads, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* Layer drop (stochastic depth, vit_sam.py:165-173) for the trained blocks (csrc/cpx_train_blocks.hip; additive, no ABI bump).  keep
+ * [n_blocks][n_subtiles] uint8 on the HOST, read before the call returns: block first_block + j runs on crop n where keep[j][n] != 0,
+ *   x_{j+1}[n] = keep[j][n] ? block_j(x_j[n]) : x_j[n]     (the second branch bit for bit)
+ * which is the reference's x * mask + blk(x) * (1 - mask) with mask = 1 - keep.  Nothing inside a block crosses a crop, so a block runs on
+ * its kept crops alone, compacted in crop order; a dropped (block, crop) pair costs neither a forward nor a backward.
+ * cpx_gather_crops / cpx_scatter_crops: the 1024 rows of each crop of `crops` (HOST, n entries, strictly increasing, each < n_subtiles)
+ * from a full [n_subtiles * 1024][1024] buffer of `dtype` into a compact [n * 1024][1024] one in list order, and back (the full buffer's
+ * other crops untouched).  One wave per row, 16-byte accesses; the list travels by value in the kernel arguments, 64 crops per launch: no
+ * device table, no allocation, nothing read after the call returns.  stats: NULL, or (half types) [n * 1024][4][2] float32 receiving the
+ * row statistics of the compact rows in the same pass, bitwise cpx_row_stats of them (the same code sums both).  n = 0 launches nothing
+ * and returns CPX_OK; a list that is unordered, repeats a crop or names a crop >= n_subtiles, a null or not 16-byte aligned buffer,
+ * stats with CPX_DT_F32: CPX_EINVAL, nothing is launched.  src and dst are distinct buffers.
+ * cpx_blocks_forward_train_drop: cpx_blocks_forward_train under the mask.  The running full-batch rows live in the x_out record; per
+ * block the kept crops are gathered into the block's x_in record (with their statistics where the weights fold LayerNorm), the block runs
+ * on n_keep crops exactly as cpx_blocks_forward_train runs it on a batch of n_keep, and its output is scattered back.  The x_in, qkv, ao
+ * and x_mid records of block j hold n_keep_j * 1024 valid rows at their front; a block that keeps nothing launches nothing; x_out and
+ * the neck cover all crops.  workspace: cpx_blocks_train_workspace_bytes_drop (the layout of cpx_blocks_train_layout, then one staging
+ * tensor).  keep NULL or all non-zero forwards to cpx_blocks_forward_train: the same launches, and its workspace size suffices.
+ * cpx_blocks_backward_drop: cpx_blocks_backward_in for such a forward, with the same keep.  The slabs of two adjacent crops and their order
+ * stay; per block the body runs on the slab's kept crops -- two (adjacent in the compact records), one (1024 rows, on that crop's half of
+ * the slab's dx) or none (skipped) -- from the compact row offset 1024 * (kept crops of that block before the slab).  A dropped crop's dx
+ * rows pass down untouched, bitwise, into dx_all and dx_in as well; a block with no kept crop has an all-zero gradient record.  Every
+ * precision combination of cpx_blocks_backward_mp; its workspace size; no atomics, two runs are bitwise equal.  keep NULL or all non-zero
+ * is cpx_blocks_backward_in, launch for launch.                                                                                        */
+int cpx_gather_crops(int dtype, const void *src, int n_subtiles, const int *crops, int n, void *dst, float *stats, void *stream);
+int cpx_scatter_crops(int dtype, const void *src, int n_subtiles, const int *crops, int n, void *dst, void *stream);
+size_t cpx_blocks_train_workspace_bytes_drop(int n_subtiles, int dtype, int n_blocks);
+int cpx_blocks_forward_train_drop(const cpx_net_weights *w, const void *x, int n_subtiles, int first_block, const unsigned char *keep,
+                                  float *head, void *workspace, size_t workspace_bytes, void *stream);
+int cpx_blocks_backward_drop(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const unsigned char *keep,
+                             const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype,
+                             float *grads, float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)
