@@ -236,6 +236,9 @@ SIGNATURES = {
     "cpx_dedup_pairs_workspace_bytes": (_sz, [_i, _i, _i]),
     "cpx_dedup_pairs": (_i, [_p, _i, _d, _d, _d, _i, _i, _d, _p, C.c_longlong, _p, _p, _sz, _p]),
     "cpx_write_geojson": (_i, [C.c_char_p, C.c_char_p, _p, C.c_int64, _p, _p, _p, _p, C.c_int64, _p, _i, _d, _d, _i]),
+    "cpx_write_geojson_ex": (_i, [C.c_char_p, C.c_char_p, _p, C.c_int64, _p, _p, _p, _p, C.c_int64, _p, _i, _d, _d, _i, _p, _i, _p]),
+    "cpx_instance_confidence_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "cpx_instance_confidence": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
 }
 # include/classpose_hip_debug.h: process-global A/B and ablation switches -- exported by libclasspose_hip_debug.so only
 _PRIVATE = {
@@ -261,6 +264,7 @@ _PRIVATE = {
     "cpx_gemm_ln_dt": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),
     "cpx_row_stats_dt": (_i, [_i, _p, _i, _p, _p]),
     "cpx_im2col3_f32_debug": (_i, [_p, _i, _p, _p]),
+    "cpx_confidence_set_footprint": (None, [_i]),
     "cpx_unet_head_layout": (_i, [C.POINTER(CpxConvOp), _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
 }
 

@@ -123,6 +123,7 @@ struct Row { double area, perimeter, cx, cy; int64_t n_pts, cls; };      // nump
 struct Job {
     const Row *cells; const double *cen; const double *xy; const int64_t *offs; const int64_t *keep;
     const char *const *class_json; int n_class; double bx, by; bool shift;
+    const char *const *extra_names; int n_extra; const double *extra;     // cpx_write_geojson_ex: [n_cells][n_extra], contours file only
 };
 
 void format_chunk(const Job &j, int64_t lo, int64_t hi, bool first_chunk, Rng &rng, std::string &fc, std::string &fp) {
@@ -138,7 +139,7 @@ void format_chunk(const Job &j, int64_t lo, int64_t hi, bool first_chunk, Rng &r
         meas += "}, {\"name\": \"perimeter\", \"value\": "; put_double(meas, c.perimeter, true);
         meas += "}, {\"name\": \"centroidX\", \"value\": "; put_double(meas, cx, true);
         meas += "}, {\"name\": \"centroidY\", \"value\": "; put_double(meas, cy, true);
-        meas += "}]";
+        meas += "}";                                              // the list is closed per file: the contours file may go on
         const char *sep = (first_chunk && k == lo) ? "" : ", ";
         // polygon
         fc += sep; fc += "{\"type\": \"Feature\", \"id\": \""; put_uuid4(fc, rng);
@@ -153,24 +154,31 @@ void format_chunk(const Job &j, int64_t lo, int64_t hi, bool first_chunk, Rng &r
             put_double(fc, x, true); fc += ", "; put_double(fc, y, true); fc += ']';
         }
         fc += "]]}, \"properties\": {\"objectType\": \"annotation\", \"isLocked\": false, \"classification\": ";
-        fc += cls; fc += ", \"measurements\": "; fc += meas; fc += "}}";
+        fc += cls; fc += ", \"measurements\": "; fc += meas;
+        for (int e = 0; e < j.n_extra; ++e) {
+            fc += ", {\"name\": "; fc += j.extra_names[e]; fc += ", \"value\": ";
+            put_double(fc, j.extra[i * j.n_extra + e], true); fc += '}';
+        }
+        fc += "]}}";
         // centroid
         fp += sep; fp += "{\"type\": \"Feature\", \"id\": \""; put_uuid4(fp, rng);
         fp += "\", \"geometry\": {\"type\": \"Point\", \"coordinates\": [";
         put_double(fp, cx, true); fp += ", "; put_double(fp, cy, true);
         fp += "]}, \"properties\": {\"objectType\": \"annotation\", \"isLocked\": false, \"classification\": ";
-        fp += cls; fp += ", \"measurements\": "; fp += meas; fp += "}}";
+        fp += cls; fp += ", \"measurements\": "; fp += meas; fp += "]}}";
     }
 }
 
 }  // namespace
 
-extern "C" int cpx_write_geojson(const char *contours_path, const char *centroids_path, const void *cells,
-                                 int64_t n_cells, const double *centroids_xy, const double *xy_pool,
-                                 const int64_t *offsets, const int64_t *keep, int64_t n_keep,
-                                 const char *const *class_json, int n_class_json, double bounds_x, double bounds_y,
-                                 int n_threads) {
+extern "C" int cpx_write_geojson_ex(const char *contours_path, const char *centroids_path, const void *cells,
+                                    int64_t n_cells, const double *centroids_xy, const double *xy_pool,
+                                    const int64_t *offsets, const int64_t *keep, int64_t n_keep,
+                                    const char *const *class_json, int n_class_json, double bounds_x, double bounds_y,
+                                    int n_threads, const char *const *extra_names, int n_extra, const double *extra) {
     CPX_REQUIRE(contours_path && centroids_path && n_cells >= 0 && n_keep >= 0 && class_json && n_class_json > 0);
+    CPX_REQUIRE(n_extra >= 0 && (n_extra == 0 || (extra_names && (extra || n_keep == 0))));
+    for (int e = 0; e < n_extra; ++e) CPX_REQUIRE(extra_names[e] != nullptr);
     CPX_REQUIRE(n_keep == 0 || (cells && centroids_xy && xy_pool && offsets && keep));
     for (int64_t k = 0; k < n_keep; ++k) CPX_REQUIRE(keep[k] >= 0 && keep[k] < n_cells);
     FILE *f1 = std::fopen(contours_path, "wb");
@@ -183,7 +191,7 @@ extern "C" int cpx_write_geojson(const char *contours_path, const char *centroid
     bool ok = std::fwrite(head, 1, sizeof head - 1, f1) == sizeof head - 1 &&
               std::fwrite(head, 1, sizeof head - 1, f2) == sizeof head - 1;
     Job job{(const Row *)cells, centroids_xy, xy_pool, offsets, keep, class_json, n_class_json,
-            bounds_x, bounds_y, bounds_x != 0 || bounds_y != 0};
+            bounds_x, bounds_y, bounds_x != 0 || bounds_y != 0, extra_names, n_extra, extra};
     const int64_t CH = 4096;                   // cells per chunk (~4 MB of contour text)
     const int64_t n_chunks = (n_keep + CH - 1) / CH;
     int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
@@ -240,4 +248,13 @@ extern "C" int cpx_write_geojson(const char *contours_path, const char *centroid
     ok = (std::fclose(f2) == 0) & ok;
     CPX_REQUIRE(ok && "short write on a GeoJSON output file");
     return CPX_OK;
+}
+
+extern "C" int cpx_write_geojson(const char *contours_path, const char *centroids_path, const void *cells,
+                                 int64_t n_cells, const double *centroids_xy, const double *xy_pool,
+                                 const int64_t *offsets, const int64_t *keep, int64_t n_keep,
+                                 const char *const *class_json, int n_class_json, double bounds_x, double bounds_y,
+                                 int n_threads) {
+    return cpx_write_geojson_ex(contours_path, centroids_path, cells, n_cells, centroids_xy, xy_pool, offsets, keep, n_keep,
+                                class_json, n_class_json, bounds_x, bounds_y, n_threads, nullptr, 0, nullptr);
 }

@@ -369,6 +369,9 @@ class TileOutputs:
     cells: torch.Tensor | None = None        # uint8 view of cpx_cell[nT][max_rec]   (polygons=...)
     xy_pool: torch.Tensor | None = None      # f64 [max_pts, 2] level-0 vertices
     n_pts_total: torch.Tensor | None = None  # int32 [1]
+    votes: torch.Tensor | None = None        # int32 [nT, max_rec, ncls]   (confidence=True, with a class head)
+    prob_q: torch.Tensor | None = None       # int64 bits of uint64 [nT, max_rec, ncls]
+    cellprob_q: torch.Tensor | None = None   # int64 bits of uint64 [nT, max_rec]   (confidence=True)
 
 
 class _Slot:
@@ -395,6 +398,8 @@ class _Slot:
         self.rec_counts = torch.empty(nT, dtype=torch.int32, device=d)
         self.cells = self.xy_pool = self.n_pts_total = self.poly_ws = self.origins = None   # allocated on first use
         self.has_polygons = False
+        self.votes = self.prob_q = self.cellprob_q = None       # confidence=True: allocated on first use
+        self.has_confidence = False
         if eng.rescaled:
             # eval(diameter=): the tiles at network size, the fields at tile size, and without resample the maps at tile size too
             tH, tW = eng.H, eng.W
@@ -483,12 +488,16 @@ class Engine:
         self.stage_timing: list | None = None
 
     # -- pipeline -------------------------------------------------------
-    def submit(self, tiles_u8: torch.Tensor, inject=None, records: bool = True, polygons=None) -> int:
+    def submit(self, tiles_u8: torch.Tensor, inject=None, records: bool = True, polygons=None, confidence: bool = False) -> int:
         """Enqueue one batch (uint8 [n, H, W, 3] resident on the device, n <= batch_tiles) and
         return its slot id.  ``inject`` = (dP, cellprob, logits) device tensors: flow-injection
         mode (the network still runs; the dynamics consume the injected fields instead).
         ``polygons`` = (scale, origins [n][2] level-0 tile origins): also polygonise the instances
-        on the device (``cpx_polygonize_device``), results via ``fetch_polygons``."""
+        on the device (``cpx_polygonize_device``), results via ``fetch_polygons``.
+        ``confidence``: also the per-cell vote table and quantised probability sums (``cpx_instance_confidence``, one more
+        pass over the fields the class vote read, enqueued right after the chain); ``TileOutputs.votes`` / ``prob_q`` /
+        ``cellprob_q``, rows below ``rec_counts`` (``nlabels`` with ``records=False``: the same number) defined, at the size
+        the dynamics ran at.  Off: nothing is allocated or launched for it."""
         # (ValueError, not assert: these guard raw device pointers handed to the C ABI and must survive `python -O`)
         if tiles_u8.dtype != torch.uint8 or tiles_u8.dim() != 4 or not tiles_u8.is_contiguous():
             raise ValueError(f"Engine.submit: tiles must be a contiguous uint8 [n, H, W, 3] tensor, got {tiles_u8.dtype} {tuple(tiles_u8.shape)}")
@@ -570,6 +579,19 @@ class Engine:
                                                ptr(sl.nlabels), self.max_rec if records else 0,
                                                ptr(sl.records) if records else None, ptr(sl.rec_counts) if records else None,
                                                ptr(sl.pp_ws), sp), "compute_masks")
+        sl.has_confidence = bool(confidence)
+        if confidence:
+            # right behind the chain: before the polygoniser, and before anything reuses the fields
+            if sl.cellprob_q is None:
+                if ncls > 1:
+                    sl.votes = torch.empty((self.nT, self.max_rec, ncls), dtype=torch.int32, device=self.dev)
+                    sl.prob_q = torch.empty((self.nT, self.max_rec, ncls), dtype=torch.int64, device=self.dev)
+                sl.cellprob_q = torch.empty((self.nT, self.max_rec), dtype=torch.int64, device=self.dev)
+                self.s_post.wait_stream(cur)             # (as for the polygon buffers below)
+            check(self.L.cpx_instance_confidence(ptr(sl.masks), ptr(lg) if ncls > 1 else None, ptr(cp),
+                                                 ptr(sl.rec_counts if records else sl.nlabels), n,
+                                                 ncls, self.cH, self.cW, self.max_rec, ptr(sl.votes), ptr(sl.prob_q),
+                                                 ptr(sl.cellprob_q), None, 0, sp), "instance_confidence")
         if self.rescaled and not self.resample:     # ids and classes of the network-size run, cv2.INTER_NEAREST (models.py:804-820)
             check(self.L.cpx_resize_nearest(ptr(sl.masks), 2, n, self.nH, self.nW, ptr(sl.out_masks), self.H, self.W, sp), "resize_nearest")
             check(self.L.cpx_resize_nearest(ptr(sl.class_masks), 1, n, self.nH, self.nW, ptr(sl.out_class_masks), self.H, self.W, sp),
@@ -614,10 +636,22 @@ class Engine:
         dP, cp, lg = (sl.out_dP, sl.out_cellprob, sl.out_logits) if self.rescaled else (sl.dP, sl.cellprob, sl.logits)
         return TileOutputs(masks[:n], cm[:n], sl.nlabels[:n], dP[:n], cp[:n],
                            lg[:n] if self.w.ncls > 1 else None, sl.records, sl.rec_counts,
-                           *((sl.cells, sl.xy_pool, sl.n_pts_total) if sl.has_polygons else (None, None, None)))
+                           *((sl.cells, sl.xy_pool, sl.n_pts_total) if sl.has_polygons else (None, None, None)),
+                           *((sl.votes, sl.prob_q, sl.cellprob_q) if sl.has_confidence else (None, None, None)))
 
-    def run(self, tiles_u8: torch.Tensor, inject=None, records: bool = True, polygons=None) -> "TileOutputs":
-        return self.result(self.submit(tiles_u8, inject, records, polygons))
+    def run(self, tiles_u8: torch.Tensor, inject=None, records: bool = True, polygons=None, confidence: bool = False) -> "TileOutputs":
+        return self.result(self.submit(tiles_u8, inject, records, polygons, confidence))
+
+    def fetch_confidence(self, out: "TileOutputs", tile: np.ndarray, label: np.ndarray):
+        """Confidence rows of the cells (tile in batch, label) of a collected batch -> (votes int64 [m, ncls], prob_q uint64
+        [m, ncls], cellprob_q uint64 [m]); ncls = 0 columns without a class head.  Only the picked rows leave the device."""
+        ti = torch.as_tensor(np.asarray(tile, dtype=np.int64), device=self.dev)
+        ri = torch.as_tensor(np.asarray(label, dtype=np.int64) - 1, device=self.dev)
+        m = len(ti)
+        cq = out.cellprob_q[ti, ri].cpu().numpy().view(np.uint64)
+        if out.votes is None:
+            return np.zeros((m, 0), np.int64), np.zeros((m, 0), np.uint64), cq
+        return out.votes[ti, ri].cpu().numpy().astype(np.int64), out.prob_q[ti, ri].cpu().numpy().view(np.uint64), cq
 
     def fetch_polygons(self, n: int, out: "TileOutputs"):
         """Device polygons of a collected batch -> (cells CELL_DTYPE[m] with a ``tile`` column appended as a

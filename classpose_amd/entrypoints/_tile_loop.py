@@ -29,7 +29,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from .. import engine, geojson, hooks, hostinfo, ops, parallel, postprocess, roi, wsi
+from .. import confidence, engine, geojson, hooks, hostinfo, ops, parallel, postprocess, roi, wsi
 from ..log import get_logger
 from ..model_configs import DEFAULT_MODEL_CONFIGS, ModelConfig
 
@@ -300,6 +300,10 @@ def run_rank(args, rank: int, world: int, device: torch.device):
     pool = ThreadPoolExecutor(max_workers=max(2, min(16, hostinfo.usable_cpus() // max(world, 1))))
     futures = []
     cells_all, xy_all, tile_all, n_invalid = [], [], [], 0
+    # --cell_confidence: one uint64 row per cell (confidence.pack_rows) beside every CELL_ROW, through the same selections
+    want_conf = getattr(args, "cell_confidence", None) is not None
+    conf_all = []
+    conf_width = confidence.row_width(n_classes if n_classes > 1 else 0)
     scale = plan.polygon_scale        # min(train_mpp / mpp_x, train_mpp / mpp_y) from the shared slots, predict_wsi.py:1517-1524
     t0 = time.time()
     n_done = 0
@@ -354,13 +358,20 @@ def run_rank(args, rank: int, world: int, device: torch.device):
                     rows[name] = cells[keep][name]
                 cells_all.append(rows)
                 tile_all.append(np.asarray(chunk, np.int64)[tile_in_batch[keep]])       # global tile index of every cell
+                if want_conf:
+                    # cpx_cell row i of a tile belongs to label i + 1: the kept rows' (tile in batch, label - 1) pick the confidence rows
+                    first = np.concatenate([[0], np.cumsum(np.bincount(tile_in_batch, minlength=n))])[:-1]
+                    label = np.arange(len(cells)) - first[tile_in_batch] + 1
+                    conf_all.append(_fetch_conf_rows(eng, n, out, tile_in_batch[keep], label[keep]))
             else:                                                    # vertex pool overflow: host polygoniser
                 masks = out.masks.cpu().numpy().view(np.uint16)      # D2H: 2 B / pixel
                 recs = eng.fetch_records(n, out)
+                conf = _fetch_conf_rows(eng, n, out, recs["tile"], recs["label"], recs["area"]) if want_conf else None
                 for k, ti in enumerate(chunk):
                     origin = plan.coords[ti][0]
                     futures.append((ti, pool.submit(postprocess.polygonize_tile, masks[k].copy(),
-                                                    recs[recs["tile"] == k], scale, origin)))
+                                                    recs[recs["tile"] == k], scale, origin),
+                                    conf[recs["tile"] == k] if want_conf else None))
             stage["polygons D2H + cell rows"] += time.time() - t_c
             n_done += n
             if rank == 0 and (n_done // nT) % 20 == 0:
@@ -390,7 +401,7 @@ def run_rank(args, rank: int, world: int, device: torch.device):
                     if t_ is not None:
                         t_.record_stream(cur)
             sid = eng.submit(tiles_dev, inject=inject, records=True,
-                             polygons=(scale, [plan.coords[ti][0] for ti in chunk]))
+                             polygons=(scale, [plan.coords[ti][0] for ti in chunk]), confidence=want_conf)
             stage["resize + submit"] += time.time() - t_r
             if in_flight is not None:
                 collect(*in_flight)
@@ -398,9 +409,11 @@ def run_rank(args, rank: int, world: int, device: torch.device):
         if in_flight is not None:
             collect(*in_flight)
         del eng, stream
-    for ti, f in futures:
+    for ti, f, conf in futures:
         cells, xy = f.result()
         keep = cells["valid"] == 1
+        if want_conf:
+            conf_all.append(conf[keep])
         n_invalid += int((~keep).sum())
         xy_all.append(geojson.gather_vertices(xy, cells["offset"][keep], cells["n_pts"][keep]))
         rows = np.zeros(int(keep.sum()), CELL_ROW)
@@ -413,6 +426,7 @@ def run_rank(args, rank: int, world: int, device: torch.device):
     cells = np.concatenate(cells_all) if cells_all else np.zeros(0, CELL_ROW)
     xy = np.concatenate(xy_all) if xy_all else np.zeros((0, 2))
     plan.cell_tiles = np.concatenate(tile_all) if tile_all else np.zeros(0, np.int64)
+    plan.cell_confidence = (np.concatenate(conf_all) if conf_all else np.zeros((0, conf_width), np.uint64)) if want_conf else None
     logger.info(f"[rank {rank}] {len(cells)} cells, {n_invalid} invalid, {len(mine)} tiles in {time.time() - t0:.1f}s")
     # main-thread wall seconds per stage ("device wait" = blocked on the GPU's results, i.e. the engine is the pace-maker; "reader wait" = blocked
     # on decoded tiles [+ the plug-in's fields]; the rest is host work between two batches)
@@ -422,34 +436,57 @@ def run_rank(args, rank: int, world: int, device: torch.device):
     return cells, xy, labels, plan
 
 
-def canonical_cell_order(cells: np.ndarray, xy: np.ndarray, tiles: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+def _fetch_conf_rows(eng, n: int, out, tile_in_batch, label, area=None) -> np.ndarray:
+    """confidence.pack_rows of the cells (tile in batch, label) of a collected batch; ``area`` (the records' pixel counts) is
+    read from the records when the vote table cannot give it (no class head) and the caller has not got it already"""
+    votes, prob_q, cellprob_q = eng.fetch_confidence(out, tile_in_batch, label)
+    if area is None:
+        if votes.shape[1]:
+            area = votes.sum(1)
+        else:
+            recs = eng.fetch_records(n, out)
+            first = np.concatenate([[0], np.cumsum(np.bincount(recs["tile"], minlength=n))])[:-1]
+            area = recs["area"][first[np.asarray(tile_in_batch, np.int64)] + np.asarray(label, np.int64) - 1]
+    return confidence.pack_rows(votes, prob_q, cellprob_q, area)
+
+
+def canonical_cell_order(cells: np.ndarray, xy: np.ndarray, tiles: np.ndarray, extra: np.ndarray | None = None):
     """Cells in the order of their tile's index in the ``_get_coords`` walk (within a tile: label order), whatever rank,
     batch, tile-size group or fallback path produced them.  The reference's order is whatever its worker processes happen
     to deliver (a shared queue); de-duplication depends on it inside clusters of >= 3 cells, so THIS order is what makes the
-    output of an N-GPU run identical to the 1-GPU run (static sharding)."""
+    output of an N-GPU run identical to the 1-GPU run (static sharding).  ``extra`` (optional): further per-cell
+    rows (the confidence rows) that take the same order; then the result is (cells, xy, extra)."""
     if len(cells) == 0 or bool(np.all(tiles[1:] >= tiles[:-1])):
-        return cells, xy
+        return (cells, xy) if extra is None else (cells, xy, extra)
     order = np.argsort(tiles, kind="stable")
     offs = np.concatenate([[0], np.cumsum(cells["n_pts"])])[:-1]
-    return cells[order], geojson.gather_vertices(xy, offs[order], cells["n_pts"][order])
+    xy = geojson.gather_vertices(xy, offs[order], cells["n_pts"][order])
+    return (cells[order], xy) if extra is None else (cells[order], xy, extra[order])
 
 
-def gather_cells(cells: np.ndarray, xy: np.ndarray, device, tiles: np.ndarray | None = None):
+def gather_cells(cells: np.ndarray, xy: np.ndarray, device, tiles: np.ndarray | None = None, extra: np.ndarray | None = None):
     """The path's one exchange (north_star: "RCCL only to all-gather the per-tile centroid / class tensors"):
     the 48-byte cell rows (centroid, class, area, perimeter, vertex count) and the cells' tile indices go to EVERY rank
     (one padded all-gather each); the polygon vertex pools -- ~0.5 KB per cell, needed by the writing rank only -- go to
     rank 0 by point-to-point sends and never leave the device on the other ranks.  Returns (cells, xy, tiles); xy is None
-    on ranks other than 0."""
+    on ranks other than 0.  ``extra`` [n][k] (the confidence rows of --cell_confidence, 8-byte words): one more padded
+    all-gather, made only when given (every rank gives it or none does); the result then ends with the gathered rows."""
     c = torch.from_numpy(cells.view(np.uint8).reshape(len(cells), CELL_ROW.itemsize).copy()).to(device)
     c = parallel.all_gather_records(c).cpu().numpy()
     out_cells = c.reshape(-1).view(CELL_ROW)
     v = torch.from_numpy(np.ascontiguousarray(xy).view(np.uint8).reshape(len(xy), 16).copy()).to(device)
     v = parallel.gather_to_root(v, 0)
     out_xy = None if v is None else v.cpu().numpy().reshape(-1).view(np.float64).reshape(-1, 2)
-    if tiles is None:
-        return out_cells, out_xy
-    t = torch.from_numpy(np.ascontiguousarray(tiles, dtype=np.int64).view(np.uint8).reshape(len(tiles), 8).copy()).to(device)
-    return out_cells, out_xy, parallel.all_gather_records(t).cpu().numpy().reshape(-1).view(np.int64)
+    res = [out_cells, out_xy]
+    if tiles is not None:
+        t = torch.from_numpy(np.ascontiguousarray(tiles, dtype=np.int64).view(np.uint8).reshape(len(tiles), 8).copy()).to(device)
+        res.append(parallel.all_gather_records(t).cpu().numpy().reshape(-1).view(np.int64))
+    if extra is not None:
+        extra = np.ascontiguousarray(extra)
+        width = extra.shape[1] * extra.dtype.itemsize
+        e = torch.from_numpy(extra.view(np.uint8).reshape(len(extra), width).copy()).to(device)
+        res.append(parallel.all_gather_records(e).cpu().numpy().reshape(-1).view(extra.dtype).reshape(-1, extra.shape[1]))
+    return tuple(res)
 
 
 def _detect_artefacts(args, device):
@@ -472,10 +509,12 @@ def _qc_override(kind: str):
     return hooks.qc_provider(kind) if hooks.qc_provider else None
 
 
-def write_outputs(args, cells, xy, labels, plan, device=None):
+def write_outputs(args, cells, xy, labels, plan, device=None, conf_rows=None):
     """De-duplication, ROI / tissue / artefact filters and the output files, on the cell table
     (struct of arrays): same results as the reference's list-of-dict pipeline
-    (predict_wsi.py:1600-1857; ``tests/test_host_polygons_geojson.py`` checks the equivalence)."""
+    (predict_wsi.py:1600-1857; ``tests/test_host_polygons_geojson.py`` checks the equivalence).  ``conf_rows`` (with
+    --cell_confidence): the cells' confidence rows; their measurements follow centroidY in the contours file, picked by the
+    same ``keep`` indices as the cells, repeats of overlapping ROIs included."""
     logger.info(f"Number of detected cells: {len(cells)}")
     if len(cells) == 0:
         logger.warning("No cells detected")
@@ -601,7 +640,11 @@ def write_outputs(args, cells, xy, labels, plan, device=None):
         logger.info(f"Saving cellular densities to {out}/{base}_cell_densities.csv")
     contours = out / get_geojson_output_filename("cell_contours", base)
     centroids = out / get_geojson_output_filename("cell_centroids", base)
-    geojson.write_feature_collections(contours, centroids, cells, xy, keep, labels, (bx, by))
+    extra_names = extra = None
+    if conf_rows is not None:
+        votes, prob_q, cellprob_q, area = confidence.unpack_rows(conf_rows)
+        extra_names, extra = confidence.measurements(votes, prob_q, cellprob_q, cells["cls"], args.cell_confidence, labels, area=area)
+    geojson.write_feature_collections(contours, centroids, cells, xy, keep, labels, (bx, by), extra_names=extra_names, extra=extra)
     logger.info(f"Wrote {contours} and {centroids}")
     return contours, centroids
 
@@ -631,15 +674,22 @@ def run_main(args, spawned: bool = False):
     cells, xy, labels, plan = run_rank(args, rank, world, device)
     t_loop_end = time.time()
     tiles = plan.cell_tiles
+    conf_rows = plan.cell_confidence
     if world > 1:
         n_local = len(cells)
-        cells, xy, tiles = gather_cells(cells, xy, device, tiles)
+        if conf_rows is None:
+            cells, xy, tiles = gather_cells(cells, xy, device, tiles)
+        else:
+            cells, xy, tiles, conf_rows = gather_cells(cells, xy, device, tiles, conf_rows)
         logger.info(f"[rank {rank}] exchange over {torch.distributed.get_backend()}: {n_local} local cells -> {len(cells)} cell rows on "
                     f"every rank; vertex pool {'%d vertices on rank 0' % len(xy) if xy is not None else 'sent to rank 0'}")
     if rank == 0:
         t_gather = time.time()
-        cells, xy = canonical_cell_order(cells, xy, tiles)
-        write_outputs(args, cells, xy, labels, plan, device)
+        if conf_rows is None:
+            cells, xy = canonical_cell_order(cells, xy, tiles)
+        else:
+            cells, xy, conf_rows = canonical_cell_order(cells, xy, tiles, conf_rows)
+        write_outputs(args, cells, xy, labels, plan, device, conf_rows)
         t_end = time.time()
         logger.info(f"wall (s): process start -> main {t_main - t_proc:.1f} (imports"
                     + (f", {os.environ['CLASSPOSE_PARENT_IMPORT_S']} s of them once in the parent the ranks were forked from" if os.environ.get("CLASSPOSE_PARENT_IMPORT_S") else "")

@@ -181,6 +181,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--inference_threads", type=int, default=None,
                    help="accepted for compatibility (the reference runs N Python threads per GPU to hide its "
                         "per-tile host work; here batches overlap on HIP streams and the value has no effect)")
+    # (default=SUPPRESS: the key exists only when the flag is given, so the namespace stays the reference's otherwise)
+    p.add_argument("--cell_confidence", type=str, choices=["summary", "full"], default=argparse.SUPPRESS,
+                   help="not in the reference, which has no such flag: also write per-cell confidence measurements into the contours "
+                        "file -- summary: class_vote_fraction (the share of the cell's pixels that voted for its class), "
+                        "class_probability and detection_probability (mean softmax / sigmoid over its pixels); full: also "
+                        "one 'probability: <label>' per class")
     return p
 
 

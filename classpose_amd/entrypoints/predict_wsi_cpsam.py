@@ -35,6 +35,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--output_type", type=str, nargs="+", default=None, choices=["csv", "spatialdata"])
     p.add_argument("--inference_threads", type=int, default=None,
                    help="accepted for compatibility; the engine overlaps stages with HIP streams instead")
+    # (default=SUPPRESS: the key exists only when the flag is given, so the namespace stays the reference's otherwise)
+    p.add_argument("--cell_confidence", type=str, choices=["summary", "full"], default=argparse.SUPPRESS,
+                   help="not in the reference, which has no such flag: also write the per-cell detection_probability (the mean sigmoid of "
+                        "cellprob over the cell's pixels) into the contours file; this entry has no class head, so both "
+                        "modes write that one measurement")
     return p
 
 

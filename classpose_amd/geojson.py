@@ -32,8 +32,10 @@ def cell_dict(coords: list, cl: int, labels: list[str] | None, area: float, peri
             "label": label, "color": color, "perimeter": float(perimeter), "centroid": centroid}
 
 
-def to_geojson_polygon(curr_cell: dict) -> dict:
-    return {
+def to_geojson_polygon(curr_cell: dict, extra_measurements: list | None = None) -> dict:
+    """``extra_measurements`` (not in the reference): (name, value) pairs appended to the measurements after centroidY,
+    in order -- the per-cell confidence of ``--cell_confidence`` (classpose_amd/confidence.py)."""
+    feature = {
         "type": "Feature",
         "id": curr_cell["id"],
         "geometry": {"type": "Polygon", "coordinates": [curr_cell["coords"]]},
@@ -49,6 +51,9 @@ def to_geojson_polygon(curr_cell: dict) -> dict:
             ],
         },
     }
+    for name, value in extra_measurements or ():
+        feature["properties"]["measurements"].append({"name": str(name), "value": float(value)})
+    return feature
 
 
 def apply_bounds_offset_to_feature(feature: dict, bounds_x: float, bounds_y: float) -> dict:
@@ -283,13 +288,17 @@ def class_json_table(labels: list[str] | None, n_values: int) -> list[str]:
 
 
 def write_feature_collections(contours_path, centroids_path, cells: np.ndarray, xy: np.ndarray, keep,
-                              labels: list[str] | None, bounds=(0.0, 0.0), n_threads: int = 0) -> int:
+                              labels: list[str] | None, bounds=(0.0, 0.0), n_threads: int = 0,
+                              extra_names: list[str] | None = None, extra: np.ndarray | None = None) -> int:
     """Writes ``{"type": "FeatureCollection", "features": [...]}`` for the cells ``keep`` (indices into
     the table, repeats allowed) exactly as ``json.dump`` of ``to_geojson_polygon`` /
     ``polygons_to_centroids`` features (after ``apply_bounds_offset_to_feature``) would.  The text is produced
     by the native streaming writer ``cpx_write_geojson`` (csrc/cpx_host_geojson.cpp): a Python loop over 2 M cells
-    took 28 s at 40k x 40k, longer than the tile loop on 8 GPUs."""
+    took 28 s at 40k x 40k, longer than the tile loop on 8 GPUs.
+    ``extra_names`` / ``extra`` [len(cells)][len(extra_names)] float64: further measurements of the contours file, after
+    centroidY (``to_geojson_polygon(..., extra_measurements=...)``); the centroids file does not carry them."""
     import ctypes as C
+    import json
 
     from . import _lib
     L = _lib.lib()
@@ -305,8 +314,16 @@ def write_feature_collections(contours_path, centroids_path, cells: np.ndarray, 
         raise ValueError("negative class value in the cell table")
     table = [t.encode("ascii") for t in class_json_table(labels, n_cls)]
     arr = (C.c_char_p * len(table))(*table)
-    _lib.check(L.cpx_write_geojson(str(contours_path).encode(), str(centroids_path).encode(),
-                                   cells.ctypes.data, n, cen.ctypes.data, xy.ctypes.data, offs.ctypes.data,
-                                   keep.ctypes.data, len(keep), arr, len(table), float(bounds[0]), float(bounds[1]),
-                                   int(n_threads)), "write_geojson")
+    args = (str(contours_path).encode(), str(centroids_path).encode(),
+            cells.ctypes.data, n, cen.ctypes.data, xy.ctypes.data, offs.ctypes.data,
+            keep.ctypes.data, len(keep), arr, len(table), float(bounds[0]), float(bounds[1]), int(n_threads))
+    if not extra_names:
+        _lib.check(L.cpx_write_geojson(*args), "write_geojson")
+        return len(keep)
+    extra = np.ascontiguousarray(extra, dtype=np.float64)
+    if extra.shape != (n, len(extra_names)):
+        raise ValueError(f"extra measurements: got {extra.shape}, the table has {n} cells and {len(extra_names)} names")
+    names = [json.dumps(str(x)).encode("ascii") for x in extra_names]
+    name_arr = (C.c_char_p * len(names))(*names)
+    _lib.check(L.cpx_write_geojson_ex(*args, C.cast(name_arr, C.c_void_p), len(names), extra.ctypes.data), "write_geojson_ex")
     return len(keep)

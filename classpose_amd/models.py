@@ -155,7 +155,15 @@ class ClassposeModel:
              flow_threshold: float = 0.4, cellprob_threshold: float = 0.0, do_3D: bool = False,
              anisotropy=None, flow3D_smooth=0, stitch_threshold: float = 0.0, min_size: int = 15,
              max_size_fraction: float = 0.4, niter=None, augment: bool = False,
-             tile_overlap: float = 0.1, bsize: int = 256, compute_masks: bool = True, progress=None):
+             tile_overlap: float = 0.1, bsize: int = 256, compute_masks: bool = True, progress=None,
+             cell_confidence: bool = False):
+        """``cell_confidence=True`` (not in the reference): the return gains a fifth element, per image one structured array
+        with a row per id of ``masks`` -- ``label``, ``cls`` (its class-map value), ``area`` (pixels), ``votes[ncls]`` (pixels
+        whose arg-max class is c), ``prob[ncls]`` (the mean softmax probability of class c over the cell's pixels) and
+        ``detection`` (the mean sigmoid of cellprob); classpose_amd/confidence.py has the definitions.  The statistics are
+        computed from the id map and the fields that the class vote read, at the size the vote ran at: with ``diameter=`` and
+        ``resample=False`` that is the NETWORK's size, so ``area`` and ``votes`` count pixels of the resized image there, not
+        of the returned ``masks``.  With the default the four-tuple is what it was."""
         if do_3D or stitch_threshold > 0 or invert or normalize is not True:
             raise NotImplementedError("only the 2-D path of ClassposeModel.eval is built "
                                       "(no do_3D / stitch / invert / custom normalize)")
@@ -183,7 +191,8 @@ class ClassposeModel:
                 chunk = idxs[s:s + nT]
                 tiles = torch.from_numpy(np.stack([np.ascontiguousarray(imgs[i]) for i in chunk])).to(self.device)
                 with self._engine(shape[0], shape[1], augment, tile_overlap, kw, net_hw, resample) as eng:     # held for this batch only
-                    o = eng.run(tiles, records=False)
+                    o = eng.run(tiles, records=False, confidence=bool(cell_confidence))
+                    conf = self._confidence_tables(eng, o, len(chunk)) if cell_confidence else None
                     masks = ops.masks_to_numpy(o.masks) if compute_masks else None
                     cm = o.class_masks.cpu().numpy().astype(np.int64) if compute_masks else None
                     dP, cp = o.dP.cpu().numpy(), o.cellprob.cpu().numpy()
@@ -195,6 +204,32 @@ class ClassposeModel:
                                 (1, *shape) if net_hw is None else (1, *net_hw, shape[2])),      # x.shape: of the resized image
                                cm[k].copy() if compute_masks else np.zeros(0),
                                np.zeros(256, np.float32))          # styles: noise in the reference (vit_sam.py:197)
+                    if cell_confidence:
+                        outs[i] = outs[i] + (conf[k],)
         if is_list:
-            return ([o[0] for o in outs], [o[1] for o in outs], [o[2] for o in outs], [o[3] for o in outs])
+            return tuple([o[j] for o in outs] for j in range(5 if cell_confidence else 4))
         return outs[0]
+
+    @staticmethod
+    def _confidence_tables(eng, o, n: int) -> list:
+        """per image of a collected batch the ``confidence.stats_table`` of its cells (rows 0 .. nlabels-1 of the device tables)"""
+        from . import confidence
+        nlab = o.nlabels[:n].cpu().numpy()
+        mx = int(nlab.max()) if n else 0
+        cq = o.cellprob_q[:n, :mx].cpu().numpy().view(np.uint64)
+        if o.votes is not None:
+            votes, pq = o.votes[:n, :mx].cpu().numpy(), o.prob_q[:n, :mx].cpu().numpy().view(np.uint64)
+        else:
+            # no class head: the pixel counts come from the id map the statistics were taken on
+            ids = eng._last.masks[:n].to(torch.int32) & 0xFFFF
+            area = torch.stack([torch.bincount(ids[t].reshape(-1), minlength=mx + 1)[1:mx + 1] for t in range(n)]).cpu().numpy() if n else None
+        tables = []
+        for t in range(n):
+            k = int(nlab[t])
+            label = np.arange(1, k + 1)
+            if o.votes is not None:
+                v = votes[t, :k].astype(np.int64)
+                tables.append(confidence.stats_table(label, v.argmax(1) if k else np.zeros(0, np.int64), v.sum(1), v, pq[t, :k], cq[t, :k]))
+            else:
+                tables.append(confidence.stats_table(label, np.zeros(k, np.int64), area[t, :k], None, None, cq[t, :k]))
+        return tables

@@ -268,6 +268,40 @@ def compute_masks(dP: torch.Tensor, cellprob: torch.Tensor, logits: torch.Tensor
     return masks, cm, nlab
 
 
+def instance_confidence(masks_u16: torch.Tensor, logits: torch.Tensor | None, cellprob: torch.Tensor | None,
+                        rec_counts: torch.Tensor, max_rec: int, out=None):
+    """Per-cell class confidence of a batch (``cpx_instance_confidence``; include/classpose_hip.h has the definitions):
+    masks_u16 (n,H,W) uint16 ids in an int16 tensor, logits (n,ncls,H,W) float32 or None, cellprob (n,H,W) float32 or None,
+    rec_counts (n,) int32 on the device -> (votes int32 (n,max_rec,ncls), prob_q (n,max_rec,ncls), cellprob_q (n,max_rec)),
+    the two sums as uint64 bits in int64 tensors.  Rows below min(rec_counts, max_rec) are defined, the others are whatever
+    the buffers held (``out`` = the three tensors to write into; fresh ones are uninitialised).  Without a class part
+    (logits None or ncls <= 1) votes and prob_q come back as None, without cellprob cellprob_q does."""
+    nT, H, W = masks_u16.shape
+    dev = masks_u16.device
+    ncls = 0 if logits is None else int(logits.shape[1])
+    cls_part = logits is not None and ncls > 1
+    if masks_u16.dtype not in (torch.int16, torch.uint16) or not masks_u16.is_contiguous():
+        raise ValueError("instance_confidence: masks_u16 must be a contiguous 16-bit (n, H, W) tensor")
+    if rec_counts.dtype != torch.int32 or rec_counts.numel() < nT or rec_counts.device != dev:
+        raise ValueError("instance_confidence: rec_counts must be int32 [n] on the masks' device")
+    for name, t, shape in (("logits", logits, (nT, ncls, H, W)), ("cellprob", cellprob, (nT, H, W))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"instance_confidence: {name} must be a contiguous float32 {shape} tensor on {dev}")
+    max_rec = int(max_rec)
+    if out is None:
+        votes = torch.empty((nT, max_rec, ncls), dtype=torch.int32, device=dev) if cls_part else None
+        prob_q = torch.empty((nT, max_rec, ncls), dtype=torch.int64, device=dev) if cls_part else None
+        cellprob_q = torch.empty((nT, max_rec), dtype=torch.int64, device=dev) if cellprob is not None else None
+    else:
+        votes, prob_q, cellprob_q = out
+    L = _lib.lib()
+    need = L.cpx_instance_confidence_workspace_bytes(nT, ncls, H, W, max_rec)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    check(L.cpx_instance_confidence(ptr(masks_u16), ptr(logits), ptr(cellprob), ptr(rec_counts), nT, ncls, H, W, max_rec,
+                                    ptr(votes), ptr(prob_q), ptr(cellprob_q), ptr(ws), need, _stream(dev)), "instance_confidence")
+    return votes, prob_q, cellprob_q
+
+
 def masks_to_numpy(masks_i16: torch.Tensor) -> np.ndarray:
     """uint16 instance ids (stored in an int16 tensor) -> numpy uint16."""
     return masks_i16.cpu().numpy().view(np.uint16)

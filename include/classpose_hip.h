@@ -418,6 +418,34 @@ int cpx_compute_masks_records(const float *dP, const float *cellprob, const floa
                               uint8_t *class_masks, int32_t *nlabels, int max_rec, cpx_record *records,
                               int32_t *rec_counts, void *workspace, void *stream);
 
+/* Per-cell class confidence (csrc/cpx_confidence.hip): the vote table behind a record's class, the summed softmax of the
+ * class logits and the summed sigmoid of cellprob, per instance.  The reference has nothing like it (its cells carry one
+ * hard class name).  A stand-alone pass that runs AFTER cpx_compute_masks_records on what that call read and wrote: the
+ * final masks_u16 [nT][H][W], logits [nT][ncls][H][W] float32, cellprob [nT][H][W] float32, rec_counts [nT] (device).
+ * For tile t and every label v in 1 .. min(rec_counts[t], max_rec), over the pixels with masks_u16 == v:
+ *   votes[t][v-1][c]   int32   pixels whose arg-max class is c -- the rule of the class vote: the first maximum wins, a NaN
+ *                              beats every number, the first NaN wins;
+ *   prob_q[t][v-1][c]  uint64  sum over pixels of q(p_c), in float64: m = max_c z_c; e_c = exp((double)z_c - m);
+ *                              s = sum_c e_c added in class order; p_c = e_c / s; q(p) = llrint(p * 2^24), round half to even.
+ *                              A pixel with any non-finite logit adds 0 to every prob_q (it still votes; the denominator
+ *                              stays the pixel count);
+ *   cellprob_q[t][v-1] uint64  sum over pixels of q(1 / (1 + exp(-(double)z))); a non-finite z adds 0.
+ * The sums are exact integers (at most 2^20 pixels * 2^24 per instance), integer atomics only: the result does not depend on
+ * arrival order, two runs give the same bits.  Derived per cell on the host in float64, n = sum_c votes[c] (== cpx_record.area):
+ *   class_vote_fraction = votes[cls] / n, class_probability = prob_q[cls] / (n * 2^24), detection_probability =
+ *   cellprob_q / (n * 2^24), cls the record's class-map value (classpose_amd/confidence.py).
+ * votes, prob_q [nT][max_rec][ncls], cellprob_q [nT][max_rec].  Rows < min(rec_counts[t], max_rec) are fully defined: the
+ * entry clears exactly those rows itself on the device; every other row is left untouched.  An id of 0, an id above
+ * rec_counts[t] and an id above max_rec are background: nothing is read or written through them (any uint16 value is safe).
+ * logits == NULL or ncls <= 1: no class part (votes / prob_q untouched, may be NULL); cellprob == NULL: no detection part
+ * (cellprob_q untouched, may be NULL); neither part, ncls outside 0 .. 32 (the vote table's class limit) or a short
+ * workspace: CPX_EINVAL, nothing is launched.  Two launches on `stream`, allocates nothing.                             */
+size_t cpx_instance_confidence_workspace_bytes(int nT, int ncls, int H, int W, int max_rec);
+int cpx_instance_confidence(const uint16_t *masks_u16, const float *logits, const float *cellprob,
+                            const int32_t *rec_counts, int nT, int ncls, int H, int W, int max_rec,
+                            int32_t *votes, uint64_t *prob_q, uint64_t *cellprob_q,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------
  * a10b  eval(diameter=): network-size fields and maps back to the image size
  * replaces transforms.resize_image on dP / cellprob / y_class
@@ -1092,6 +1120,16 @@ int cpx_write_geojson(const char *contours_path, const char *centroids_path, con
                       const int64_t *offsets, const int64_t *keep, int64_t n_keep,
                       const char *const *class_json, int n_class_json, double bounds_x, double bounds_y,
                       int n_threads);
+/* cpx_write_geojson plus n_extra further measurements per cell (the reference has none): after centroidY the contours
+ * file's measurements list gains {"name": extra_names[e], "value": extra[i * n_extra + e]} for e = 0 .. n_extra-1, in order,
+ * i the cell's index in `cells` (extra is [n_cells][n_extra]); extra_names are already JSON-encoded strings (quotes and
+ * escapes included), values are written as float.__repr__.  The centroids file is the one cpx_write_geojson writes.
+ * n_extra == 0 (names / extra may be NULL) is cpx_write_geojson, which forwards here.                                  */
+int cpx_write_geojson_ex(const char *contours_path, const char *centroids_path, const void *cells,
+                         int64_t n_cells, const double *centroids_xy, const double *xy_pool,
+                         const int64_t *offsets, const int64_t *keep, int64_t n_keep,
+                         const char *const *class_json, int n_class_json, double bounds_x, double bounds_y,
+                         int n_threads, const char *const *extra_names, int n_extra, const double *extra);
 
 /* cv2.findContours(mask, RETR_CCOMP, CHAIN_APPROX_SIMPLE) of the GrandQC class maps
  * (/root/reference/src/classpose/grandqc/wsi_tissue_detection.py:209-213,

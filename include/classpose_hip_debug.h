@@ -31,6 +31,7 @@ void cpx_gemm_set_nt(int on);               /* bits 0 / 1 / 2: non-temporal stor
 void cpx_follow_set_early_exit(int on);     /* 1 (default): Euler loop leaves when its orbit closes      */
 void cpx_follow_set_lds_window(int on);     /* 1 (default): 32 x 32-cell foreground segments, the Euler loop's taps from an LDS copy of the segment's neighbourhood; 0: round 4 */
 void cpx_blur_set_tile(int tile);            /* 32 (default): the product's tile of cpx_blur_pool_rects_u8; 64: the same kernel at 64 x 64 (tools/bench_train_quality.py) */
+void cpx_confidence_set_footprint(int foot); /* 0 (default): a workgroup of cpx_instance_confidence covers 256 consecutive pixels; 1: a 16 x 16 block (same bits; tools/bench_cell_confidence.py) */
 /* the product's bf16-only cpx_row_stats, with the half type as its first argument: CPX_DT_BF16 or CPX_DT_F16 */
 int cpx_row_stats_dt(int dtype, const void *x, int rows, float *stats, void *stream);
 /* the product's bf16-only cpx_gemm_ln, with the half type as its first argument: CPX_DT_BF16 or CPX_DT_F16 */
