@@ -119,6 +119,12 @@ void cpx_unet_act_layout(int dtype, const cpx_conv_op *ops, int n_ops, int nS, s
 
 static inline size_t es_of(int dtype) { return dtype == CPX_DT_F32 ? 4 : 2; }
 static inline bool dtype_ok(int dtype) { return dtype == CPX_DT_BF16 || dtype == CPX_DT_F16 || dtype == CPX_DT_F32; }
+// the two predicates of the blocks' backward that the embedding's backward shares: the crop count (rows = nS * 1024 fit an int) and the
+// gradient GEMMs' precision (float32 for every network, bf16 for a bf16 network alone)
+static inline bool cpx_crops_ok(int nS) { return nS > 0 && (size_t)nS * 1024 < 0x7fffffffull; }
+static inline bool cpx_grad_dtype_ok(int dtype, int grad_dtype) {
+    return grad_dtype == CPX_DT_F32 || (grad_dtype == CPX_DT_BF16 && dtype == CPX_DT_BF16);
+}
 static inline int up128(long long x) { return (int)((x + 127) / 128 * 128); }
 static inline int up64(int x) { return (x + 63) / 64 * 64; }
 // GEMM view of a cpx_conv_op, forward and backward: out [rows_pad][Npad] = im2col(X) [rows_pad][Kpad] W^T, W [Npad][Kpad].  rows runs over

@@ -22,6 +22,9 @@
 //   k_rel_grad       per (crop, four heads, table row): float64 sums in query order; k_rel_finish adds the partials in crop order and
 //                    rounds once (row 63, the padding row, is written as zero).
 // No query of one crop sees a key of another: every tile index is taken inside the crop's 1024 rows.
+//
+// The host drivers behind the exported block-training entries, each ONE body: blocks_forward_run (both forwards: one per-block step, with or
+// without a layer-drop mask) and blocks_backward_run (all five backwards: one block walk over one precision-dependent Linear layer).
 #include "cpx_internal.h"
 #include <algorithm>
 
@@ -450,7 +453,7 @@ extern "C" int cpx_gelu_backward(const float *pre, const float *dh, size_t n, fl
 }
 
 // ---------------------------------------------------------------------------
-// the training forward of the last K blocks
+// the workspace of the training forward of the last K blocks
 // ---------------------------------------------------------------------------
 // workspace: per trained block j (block first_block + j) [x_in [M][1024]][qkv [M][3072]][ao [M][1024]][x_mid [M][1024]] in the network
 // dtype -- the block's input, its qkv rows, the attention output and the rows after the attention residual --, then x_out [M][1024],
@@ -474,10 +477,7 @@ static BlocksFwdLayout blocks_fwd_layout(int nS, int dtype, int K) {
     L.total = a.o;
     return L;
 }
-static bool blocks_args_ok(int nS, int dtype, int K) { return nS > 0 && (size_t)nS * 1024 < 0x7fffffffull && dtype_ok(dtype) && K > 0 && K <= 4096; }
-extern "C" size_t cpx_blocks_train_workspace_bytes(int nS, int dtype, int K) {
-    return blocks_args_ok(nS, dtype, K) ? blocks_fwd_layout(nS, dtype, K).total : 0;
-}
+static bool blocks_args_ok(int nS, int dtype, int K) { return cpx_crops_ok(nS) && dtype_ok(dtype) && K > 0 && K <= 4096; }
 // off [4 K + 2]: per trained block x_in, qkv, ao, x_mid; then x_out and the workspace of cpx_neck_forward_train
 extern "C" int cpx_blocks_train_layout(int nS, int dtype, int K, size_t *off) {
     CPX_REQUIRE(blocks_args_ok(nS, dtype, K) && off);
@@ -513,48 +513,21 @@ static bool blocks_weights_ok(const cpx_net_weights *w, int first_block) {
            (w->dtype != CPX_DT_F32 || !w->fuse_ln) && w->n_unet_ops == 0;
 }
 
-// cpx_net_forward's blocks first_block .. depth - 1 (cpx_net_block: its launches in its order, with its MLP row parts), every GEMM writing
-// to a tensor of its own, then cpx_neck_forward_train.  For the half types the V columns of the kept qkv rows are copied from vT after
-// each block: nothing reads them before the backward, and the next block's qkv GEMM overwrites vT.  Where cpx_net_forward takes a
-// block's row statistics from the GEMM before it (the fused half path from 16 crops up), the FIRST trained block takes them from
-// cpx_row_stats, as cpx_net_forward itself does below 16 crops.
-extern "C" int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x, int nS, int first_block, float *head, void *workspace,
-                                        size_t workspace_bytes, void *stream) {
-    CPX_REQUIRE(blocks_weights_ok(w, first_block) && x && head && workspace && blocks_args_ok(nS, w->dtype, w->depth - first_block));
-    const int dt = w->dtype, K = w->depth - first_block, M = nS * 1024;
-    const BlocksFwdLayout L = blocks_fwd_layout(nS, dt, K);
-    CPX_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0 && ((uintptr_t)x & 15) == 0);
-    char *ws = (char *)workspace;
-    hipStream_t hs = (hipStream_t)stream;
-    float *st = (float *)(ws + L.off_st);
-    CPX_HIP(hipMemcpyAsync(ws + L.o_x, x, (size_t)M * 1024 * es_of(dt), hipMemcpyDeviceToDevice, hs));
-    if (w->fuse_ln) CPX_RUN(cpx_row_stats_half(dt, ws + L.o_x, M, st, stream));
-    const bool big_stats = cpx_net_big_stats(w, nS);
-    for (int j = 0; j < K; ++j) {
-        char *base = ws + L.stride * (size_t)j;
-        void *xout = j + 1 < K ? (void *)(base + L.stride + L.o_x) : (void *)(ws + L.off_out);
-        const CpxBlockBufs t = {base + L.o_x, base + L.o_mid, xout, ws + L.off_xn, base + L.o_qkv, ws + L.off_vt, base + L.o_ao, ws + L.off_h, st};
-        CPX_RUN(cpx_net_block(w, first_block + j, nS, t, big_stats, nullptr, stream));
-        if (dt != CPX_DT_F32) CPX_RUN(vt_to_rows_run(t.vt, t.qkv, nS, hs));
-    }
-    return cpx_neck_forward_train(w, ws + L.off_out, nS, head, ws + L.off_neck, L.neck_bytes, stream);
-}
-
 // ---------------------------------------------------------------------------
-// layer drop (stochastic depth): a block runs on its kept crops alone
+// crop lists (layer drop, stochastic depth: a block runs on its kept crops alone)
 // ---------------------------------------------------------------------------
 // The crops named by `crops` (host, n entries, strictly increasing, each < nS) between a full [nS * 1024][1024] buffer and a compact
-// [n * 1024][1024] one, in list order; the list travels in the kernel arguments, CPX_CROP_LIST crops per launch.
+// [n * 1024][1024] one, in list order from compact crop `first`; the list travels in the kernel arguments, CPX_CROP_LIST crops per launch.
 static bool crop_list_ok(int dtype, int nS, const int *crops, int n) {
-    if (!dtype_ok(dtype) || nS <= 0 || (size_t)nS * 1024 >= 0x7fffffffull || n < 0 || n > nS || (n > 0 && !crops)) return false;
+    if (!dtype_ok(dtype) || !cpx_crops_ok(nS) || n < 0 || n > nS || (n > 0 && !crops)) return false;
     for (int i = 0; i < n; ++i)
         if (crops[i] < 0 || crops[i] >= nS || (i > 0 && crops[i] <= crops[i - 1])) return false;
     return true;
 }
-static int move_crops(int dtype, const void *src, void *dst, const int *crops, int n, int scatter, float *stats, hipStream_t s) {
+static int move_crops(int dtype, const void *src, void *dst, const int *crops, int n, int first, int scatter, float *stats, hipStream_t s) {
     for (int i0 = 0; i0 < n; i0 += CPX_CROP_LIST) {
         CpxCropList l = {};
-        l.n = std::min(CPX_CROP_LIST, n - i0); l.first = i0;
+        l.n = std::min(CPX_CROP_LIST, n - i0); l.first = first + i0;
         for (int i = 0; i < l.n; ++i) l.crop[i] = crops[i0 + i];
         CPX_RUN(cpx_move_crop_rows_run(dtype, src, dst, l, scatter, stats, s));
     }
@@ -564,13 +537,13 @@ extern "C" int cpx_gather_crops(int dtype, const void *src, int nS, const int *c
     CPX_REQUIRE(crop_list_ok(dtype, nS, crops, n) && (!stats || dtype != CPX_DT_F32));
     if (n == 0) return CPX_OK;
     CPX_REQUIRE(src && dst && (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)stats) & 15) == 0);
-    return move_crops(dtype, src, dst, crops, n, 0, stats, (hipStream_t)stream);
+    return move_crops(dtype, src, dst, crops, n, 0, 0, stats, (hipStream_t)stream);
 }
 extern "C" int cpx_scatter_crops(int dtype, const void *src, int nS, const int *crops, int n, void *dst, void *stream) {
     CPX_REQUIRE(crop_list_ok(dtype, nS, crops, n));
     if (n == 0) return CPX_OK;
     CPX_REQUIRE(src && dst && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0);
-    return move_crops(dtype, src, dst, crops, n, 1, nullptr, (hipStream_t)stream);
+    return move_crops(dtype, src, dst, crops, n, 0, 1, nullptr, (hipStream_t)stream);
 }
 
 // keep [K][nS], host: keep[j * nS + n] != 0 where block first_block + j runs on crop n.  true: some (block, crop) pair is dropped
@@ -580,56 +553,83 @@ static bool keep_drops(const unsigned char *keep, int K, int nS) {
             if (!keep[i]) return true;
     return false;
 }
-// move_crops for the crops a mask row keeps, the list built launch by launch; *n_keep: how many there are
+// move_crops for the crops a mask row keeps, the list built CPX_CROP_LIST crops at a time (no allocation); *n_keep: how many there are
 static int move_kept(int dtype, const unsigned char *kj, int nS, const void *src, void *dst, int scatter, float *stats, hipStream_t s, int *n_keep) {
-    CpxCropList l = {};
-    int nk = 0;
+    int crops[CPX_CROP_LIST], n = 0;
+    *n_keep = 0;
     for (int c = 0; c < nS; ++c) {
-        if (kj[c]) l.crop[l.n++] = c;
-        if (l.n == CPX_CROP_LIST || (c + 1 == nS && l.n)) {
-            l.first = nk;
-            CPX_RUN(cpx_move_crop_rows_run(dtype, src, dst, l, scatter, stats, s));
-            nk += l.n; l.n = 0;
+        if (kj[c]) crops[n++] = c;
+        if (n == CPX_CROP_LIST || c + 1 == nS) {
+            CPX_RUN(move_crops(dtype, src, dst, crops, n, *n_keep, scatter, stats, s));
+            *n_keep += n; n = 0;
         }
     }
-    *n_keep = nk;
     return CPX_OK;
 }
-// the staging rows of a compacted block's output, behind the workspace of cpx_blocks_forward_train
-extern "C" size_t cpx_blocks_train_workspace_bytes_drop(int nS, int dtype, int K) {
-    if (!blocks_args_ok(nS, dtype, K)) return 0;
-    return blocks_fwd_layout(nS, dtype, K).total + cpx_align_up((size_t)nS * 1024 * 1024 * es_of(dtype), 256);
-}
 
-// cpx_blocks_forward_train with x_{j+1}[n] = keep[j][n] ? block_j(x_j[n]) : x_j[n].  No row of one crop meets a row of another inside a
-// block, so block j runs on its kept crops alone: they are gathered, in crop order, out of the running full-batch rows -- the x_out record
-// -- into the block's x_in record (with their row statistics where the weights fold LayerNorm: a compacted block has no GEMM before it
-// to emit them), the block runs on n_keep crops into the staging rows, and those are scattered back.  qkv, ao and x_mid of block j hold
+// ---------------------------------------------------------------------------
+// the training forward of the last K blocks: one body for both entries
+// ---------------------------------------------------------------------------
+// Trained block j (block first_block + j) on nc crops, from its x_in record into xout: cpx_net_block -- cpx_net_forward's launches in its
+// order, with its MLP row parts --, every GEMM writing to a tensor of its own.  For the half types the V columns of the kept qkv rows are
+// copied from vT afterwards: nothing reads them before the backward, and the next block's qkv GEMM overwrites vT.
+static int block_forward_step(const cpx_net_weights *w, int first_block, int j, int nc, const BlocksFwdLayout &L, char *ws, void *xout, void *stream) {
+    char *base = ws + L.stride * (size_t)j;
+    const CpxBlockBufs t = {base + L.o_x, base + L.o_mid, xout, ws + L.off_xn, base + L.o_qkv, ws + L.off_vt, base + L.o_ao, ws + L.off_h,
+                            (float *)(ws + L.off_st)};
+    CPX_RUN(cpx_net_block(w, first_block + j, nc, t, cpx_net_big_stats(w, nc), nullptr, stream));
+    if (w->dtype != CPX_DT_F32) CPX_RUN(vt_to_rows_run(t.vt, t.qkv, nc, (hipStream_t)stream));
+    return CPX_OK;
+}
+static size_t blocks_fwd_bytes(int nS, int dtype, int K, bool drop) {
+    if (!blocks_args_ok(nS, dtype, K)) return 0;
+    // drop: the staging rows of a compacted block's output, behind the workspace as it is without a mask
+    return blocks_fwd_layout(nS, dtype, K).total + (drop ? cpx_align_up((size_t)nS * 1024 * 1024 * es_of(dtype), 256) : 0);
+}
+// Blocks first_block .. depth - 1, then cpx_neck_forward_train.  keep NULL or all non-zero -- no mask: block j writes straight into block
+// j + 1's x_in record (the last one into x_out).  Where cpx_net_forward takes a block's row statistics from the GEMM before it (the
+// fused half path from 16 crops up), the FIRST trained block takes them from cpx_row_stats, as cpx_net_forward itself does below 16 crops.
+// Under a mask, x_{j+1}[n] = keep[j][n] ? block_j(x_j[n]) : x_j[n].  No row of one crop meets a row of another inside a block, so block j
+// runs on its kept crops alone: they are gathered, in crop order, out of the running full-batch rows -- the x_out record -- into the
+// block's x_in record (with their row statistics where the weights fold LayerNorm: a compacted block has no GEMM before it to emit
+// them), the block runs on n_keep crops into the staging rows, and those are scattered back.  qkv, ao and x_mid of block j hold
 // n_keep_j * 1024 rows at the front of their records; a block that keeps nothing launches nothing.  The neck runs on all crops.
-extern "C" int cpx_blocks_forward_train_drop(const cpx_net_weights *w, const void *x, int nS, int first_block, const unsigned char *keep,
-                                             float *head, void *workspace, size_t workspace_bytes, void *stream) {
-    CPX_REQUIRE(blocks_weights_ok(w, first_block) && blocks_args_ok(nS, w->dtype, w->depth - first_block));
+static int blocks_forward_run(const cpx_net_weights *w, const void *x, int nS, int first_block, const unsigned char *keep, float *head,
+                              void *workspace, size_t workspace_bytes, void *stream) {
+    CPX_REQUIRE(blocks_weights_ok(w, first_block) && x && head && workspace && blocks_args_ok(nS, w->dtype, w->depth - first_block));
     const int dt = w->dtype, K = w->depth - first_block, M = nS * 1024;
-    if (!keep_drops(keep, K, nS)) return cpx_blocks_forward_train(w, x, nS, first_block, head, workspace, workspace_bytes, stream);
-    CPX_REQUIRE(x && head && workspace);
+    if (!keep_drops(keep, K, nS)) keep = nullptr;
     const BlocksFwdLayout L = blocks_fwd_layout(nS, dt, K);
-    CPX_REQUIRE(workspace_bytes >= cpx_blocks_train_workspace_bytes_drop(nS, dt, K) && ((uintptr_t)workspace & 255) == 0 && ((uintptr_t)x & 15) == 0);
+    CPX_REQUIRE(workspace_bytes >= blocks_fwd_bytes(nS, dt, K, keep != nullptr) && ((uintptr_t)workspace & 255) == 0 && ((uintptr_t)x & 15) == 0);
     char *ws = (char *)workspace, *state = ws + L.off_out, *stage = ws + L.total;
     hipStream_t hs = (hipStream_t)stream;
     float *st = (float *)(ws + L.off_st);
-    CPX_HIP(hipMemcpyAsync(state, x, (size_t)M * 1024 * es_of(dt), hipMemcpyDeviceToDevice, hs));
+    CPX_HIP(hipMemcpyAsync(keep ? state : ws + L.o_x, x, (size_t)M * 1024 * es_of(dt), hipMemcpyDeviceToDevice, hs));
+    if (!keep && w->fuse_ln) CPX_RUN(cpx_row_stats_half(dt, ws + L.o_x, M, st, stream));
     for (int j = 0; j < K; ++j) {
+        char *xin = ws + L.stride * (size_t)j + L.o_x;
+        if (!keep) {
+            CPX_RUN(block_forward_step(w, first_block, j, nS, L, ws, j + 1 < K ? xin + L.stride : state, stream));
+            continue;
+        }
         const unsigned char *kj = keep + (size_t)j * nS;
-        char *base = ws + L.stride * (size_t)j;
         int nk = 0;
-        CPX_RUN(move_kept(dt, kj, nS, state, base + L.o_x, 0, w->fuse_ln ? st : nullptr, hs, &nk));
+        CPX_RUN(move_kept(dt, kj, nS, state, xin, 0, w->fuse_ln ? st : nullptr, hs, &nk));
         if (!nk) continue;
-        const CpxBlockBufs t = {base + L.o_x, base + L.o_mid, stage, ws + L.off_xn, base + L.o_qkv, ws + L.off_vt, base + L.o_ao, ws + L.off_h, st};
-        CPX_RUN(cpx_net_block(w, first_block + j, nk, t, cpx_net_big_stats(w, nk), nullptr, stream));
-        if (dt != CPX_DT_F32) CPX_RUN(vt_to_rows_run(t.vt, t.qkv, nk, hs));
+        CPX_RUN(block_forward_step(w, first_block, j, nk, L, ws, stage, stream));
         CPX_RUN(move_kept(dt, kj, nS, stage, state, 1, nullptr, hs, &nk));
     }
     return cpx_neck_forward_train(w, state, nS, head, ws + L.off_neck, L.neck_bytes, stream);
+}
+extern "C" size_t cpx_blocks_train_workspace_bytes(int nS, int dtype, int K) { return blocks_fwd_bytes(nS, dtype, K, false); }
+extern "C" size_t cpx_blocks_train_workspace_bytes_drop(int nS, int dtype, int K) { return blocks_fwd_bytes(nS, dtype, K, true); }
+extern "C" int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x, int nS, int first_block, float *head, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    return blocks_forward_run(w, x, nS, first_block, nullptr, head, workspace, workspace_bytes, stream);
+}
+extern "C" int cpx_blocks_forward_train_drop(const cpx_net_weights *w, const void *x, int nS, int first_block, const unsigned char *keep,
+                                             float *head, void *workspace, size_t workspace_bytes, void *stream) {
+    return blocks_forward_run(w, x, nS, first_block, keep, head, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -843,52 +843,48 @@ static BlocksBwdLayout blocks_bwd_layout(int grad_dtype) {
     L.total = a.o;
     return L;
 }
-static bool grad_dtype_ok(int dtype, int grad_dtype) { return grad_dtype == CPX_DT_F32 || (grad_dtype == CPX_DT_BF16 && dtype == CPX_DT_BF16); }
 // attn_grad_dtype CPX_DT_BF16 (the attention backward on bf16 operands, cpx_attention_backward_bf16) goes with bf16 gradient GEMMs only
 static bool attn_grad_dtype_ok(int grad_dtype, int attn_grad_dtype) {
     return attn_grad_dtype == CPX_DT_F32 || (attn_grad_dtype == CPX_DT_BF16 && grad_dtype == CPX_DT_BF16);
 }
 // (the two attention backwards share one workspace layout, so attn_grad_dtype does not change the size)
-extern "C" size_t cpx_blocks_backward_workspace_bytes_mp(int nS, int dtype, int grad_dtype, int attn_grad_dtype) {
-    if (nS <= 0 || !dtype_ok(dtype) || !grad_dtype_ok(dtype, grad_dtype) || !attn_grad_dtype_ok(grad_dtype, attn_grad_dtype)) return 0;
+static size_t blocks_bwd_bytes(int nS, int dtype, int grad_dtype, int attn_grad_dtype) {
+    if (nS <= 0 || !dtype_ok(dtype) || !cpx_grad_dtype_ok(dtype, grad_dtype) || !attn_grad_dtype_ok(grad_dtype, attn_grad_dtype)) return 0;
     return blocks_bwd_layout(grad_dtype).total;
 }
-extern "C" size_t cpx_blocks_backward_workspace_bytes_ex(int nS, int dtype, int grad_dtype) {
-    return cpx_blocks_backward_workspace_bytes_mp(nS, dtype, grad_dtype, CPX_DT_F32);
-}
-extern "C" size_t cpx_blocks_backward_workspace_bytes(int nS, int dtype) { return cpx_blocks_backward_workspace_bytes_ex(nS, dtype, CPX_DT_F32); }
+extern "C" size_t cpx_blocks_backward_workspace_bytes(int nS, int dtype) { return blocks_bwd_bytes(nS, dtype, CPX_DT_F32, CPX_DT_F32); }
+extern "C" size_t cpx_blocks_backward_workspace_bytes_ex(int nS, int dtype, int grad_dtype) { return blocks_bwd_bytes(nS, dtype, grad_dtype, CPX_DT_F32); }
+extern "C" size_t cpx_blocks_backward_workspace_bytes_mp(int nS, int dtype, int grad_dtype, int ad) { return blocks_bwd_bytes(nS, dtype, grad_dtype, ad); }
 extern "C" int cpx_blocks_backward_slab_crops(void) { return BLK_SLAB; }
 
-// w: the weights the forward ran with; params: the K blocks' UNFOLDED parameters as the forward reads them (every tensor rounded through
-// the network dtype, float32), K records of cpx_block_grad_layout (the rel slots are not read: the tables come from w); fwd_workspace:
-// what cpx_blocks_forward_train filled; dy0 [rows][256] float32: d loss / d (x_out W0^T), what cpx_neck_backward leaves at off[3] of its
-// workspace -- the gradient of the last block's output is dy0 W0, formed here.  grads: K records, gradients with respect to the
-// unfolded gamma, beta, W, b and to the operand tables.  dx_all (or NULL): [K + 1][rows][1024] float32, record j < K the gradient of
-// block first_block + j's input, record K that of the last block's output.
-//
-// grad_dtype CPX_DT_BF16 (a bf16 network only): every matrix product takes both operands rounded to bf16 (round to nearest even, each value
-// once), accumulates in float32 on the bf16 MFMA and writes float32 -- dW += bf16(dy)^T bf16(a) on cpx_gemm_tn_bf16, da = bf16(dy) W and the
-// recomputed pre-activation bf16(xhat or xn) W1^T + b1 on cpx_gemm_half with the float32 epilogue, W the forward's own operand (exact in
-// bf16; for da a transposed 2-byte copy) --, and db takes the column sums of the unrounded dy from cpx_colsum_add.  Everything between
-// the products is the float32 / float64 code of the float32 mode, with the same slabs.
-//
-// attn_grad_dtype CPX_DT_BF16 (with grad_dtype CPX_DT_BF16 only): the attention backward is cpx_attention_backward_bf16 (cpx_attn_bwd16.hip)
-// in place of the float32 one; CPX_DT_F32 is cpx_blocks_backward_ex, launch for launch.
-//
-// dx_in (or NULL): [rows][1024] float32, the gradient of block first_block's input alone -- record 0 of dx_all without the other K records,
-// copied per slab from dx where that record is copied.  What the patch embedding's backward (cpx_embed_backward) takes when first_block is 0.
-//
-// keep (or NULL: every pair kept): the mask cpx_blocks_forward_train_drop ran with, [K][nS] on the host.  Per block and slab the body runs on
-// the slab's kept crops: both (adjacent in the compact records, which keep crop order), one (1024 rows, on that crop's half of dx) or
-// none (the body is skipped).  A slab's rows in block j's records start at 1024 times the kept crops of block j before it.  The dx rows
-// of a dropped crop pass down untouched, into dx_all and dx_in too; the gradients are still added in slab order, with no atomics.
+// The slab's crops (c0 and, where nc_slab is 2, c0 + 1) that a block ran on under its mask row kj (NULL: no mask): nc of them -- both
+// (adjacent in the block's compact records, which keep crop order), one or none --, from row rb of those records (1024 times the block's
+// kept crops before the slab), their gradient rows dx_off floats into the slab's dx (the second crop's half when only that one is kept).
+struct SlabKept { int nc; size_t rb, dx_off; };
+static SlabKept slab_kept(const unsigned char *kj, int c0, int nc_slab) {
+    if (!kj) return {nc_slab, (size_t)c0 * 1024, 0};
+    const int k0 = kj[c0] != 0, k1 = nc_slab > 1 && kj[c0 + 1] != 0;
+    size_t rb = 0;
+    for (int c = 0; c < c0; ++c) rb += kj[c] ? 1024 : 0;
+    return {k0 + k1, rb, k0 ? (size_t)0 : (size_t)1024 * 1024};
+}
+// operands of the backward's products: rows of activations with their element type, and a Linear's weight [N][Kin] -- op, the forward's operand
+// in the network dtype; master, its unfolded float32 record in params (NULL: none); folds: the forward may fold LayerNorm into it
+struct BwdRows { const void *p; int dt; };
+struct BwdWeight { const void *op; const float *master; bool folds; };
+
+// The one body of the five exported backward entries; the contract is at cpx_blocks_backward_drop in include/classpose_hip.h.  w: the
+// weights the forward ran with (the operand tables come from it: the rel slots of params are not read); fwd_workspace: what
+// blocks_forward_run filled under the same keep.  What grad_dtype changes is in the four lambdas of the Linear layer, what attn_grad_dtype
+// changes is the one attention-backward call, what keep changes is slab_kept.  The dx rows of a dropped crop pass down untouched, into dx_all
+// and dx_in too (dx_in: record 0 of dx_all alone, copied where that record is); the gradients are added in slab order, with no atomics.
 static int blocks_backward_run(const cpx_net_weights *w, const float *params, int nS, int first_block, const unsigned char *keep,
                                const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype,
                                float *grads, float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream) {
     CPX_REQUIRE(blocks_weights_ok(w, first_block) && params && fwd_workspace && dy0 && grads && workspace && w->neck0_w);
-    CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block) && grad_dtype_ok(w->dtype, grad_dtype));
-    CPX_REQUIRE(attn_grad_dtype_ok(grad_dtype, attn_grad_dtype));
+    CPX_REQUIRE(blocks_args_ok(nS, w->dtype, w->depth - first_block) && cpx_grad_dtype_ok(w->dtype, grad_dtype) && attn_grad_dtype_ok(grad_dtype, attn_grad_dtype));
     const int dt = w->dtype, K = w->depth - first_block;
+    if (!keep_drops(keep, K, nS)) keep = nullptr;
     const bool g16 = grad_dtype == CPX_DT_BF16, a16 = attn_grad_dtype == CPX_DT_BF16;
     const BlocksFwdLayout F = blocks_fwd_layout(nS, dt, K);
     const BlocksBwdLayout L = blocks_bwd_layout(grad_dtype);
@@ -909,35 +905,72 @@ static int blocks_backward_run(const cpx_net_weights *w, const float *params, in
     CPX_HIP(hipMemsetAsync(grads, 0, (size_t)gn * K * sizeof(float), s));
     hipLaunchKernelGGL(k_fill_f32, dim3(4), dim3(256), 0, s, ones, 1024, 1.0f);
     CPX_CHECK_LAUNCH();
-    // LayerNorm of stored rows -> xn (and xhat where the forward folds LayerNorm into the GEMM)
-    auto ln_fwd = [&](const void *x, const float *g, const float *b, int Ms, float *out, bool round) -> int {
+    // LayerNorm of stored rows, as the forward's GEMM took it -> ln: xhat where the forward folds LayerNorm into the GEMM, else the
+    // LayerNorm output, rounded through the network dtype as the unfused half forward stores it
+    float *ln = fuse ? xh : xn;
+    auto ln_fwd = [&](const void *x, const float *g, const float *b, int Ms) -> int {
         const dim3 grid(cpx_cdiv(Ms, 4)), block(256);
-        if (round) CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL((k_ln_fwd1024<DT, true>), grid, block, 0, s, x, g, b, Ms, 1e-6f, out));
-        else CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL((k_ln_fwd1024<DT, false>), grid, block, 0, s, x, g, b, Ms, 1e-6f, out));
+        if (fuse) { g = nullptr; b = nullptr; }
+        if (half && !fuse) CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL((k_ln_fwd1024<DT, true>), grid, block, 0, s, x, g, b, Ms, 1e-6f, ln));
+        else CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL((k_ln_fwd1024<DT, false>), grid, block, 0, s, x, g, b, Ms, 1e-6f, ln));
         CPX_CHECK_LAUNCH();
         return CPX_OK;
     };
-    // a Linear y = a W^T + b with a [Ms][Kin] float32 (or `a_dt` rows of the network dtype), dy [Ms][N] float32:
-    // dW += dy^T a, db += column sums of dy, da = dy W
-    auto linear_bwd = [&](const float *dy, const void *a, int a_dt, const float *W, int Ms, int N, int Kin, float *dW, float *db, float *da) -> int {
-        CPX_RUN(transpose_run(CPX_DT_F32, dy, Ms, N, t1, s));
-        CPX_RUN(transpose_run(a_dt, a, Ms, Kin, t2, s));
-        CPX_RUN(cpx_gemm_f32(t1, t2, N, Kin, Ms, CPX_EPI_RESID_BF16, nullptr, dW, dW, Kin, stream));
-        hipLaunchKernelGGL(k_colsum_add, grid1(N), dim3(256), 0, s, dy, Ms, N, db);
+    // ---- The Linear layer in either gradient precision: everything that depends on grad_dtype is in the next four lambdas. ----
+    // Which weight a product multiplies by stays with the mode.  float32 mode: the data gradient takes the master record where the weights
+    // are unfolded and the widened folded operand where they are folded (the derivative of what the forward multiplied by); the recomputed
+    // product takes the forward's operand, widened for the half types.  bf16 mode: every product takes the forward's own operand, exact in
+    // bf16 (for da a transposed 2-byte copy).
+    // An activation operand from float32 rows.  float32 mode: the rows as they are; bf16 mode: rounded once into `stage`.  (Stored rows of
+    // the network dtype are BwdRows{rows, dt} in both modes: the bf16 mode runs on a bf16 network alone.)
+    auto operand = [&](const float *rows, size_t n, void *stage, BwdRows *a) -> int {
+        *a = g16 ? BwdRows{stage, CPX_DT_BF16} : BwdRows{rows, CPX_DT_F32};
+        return g16 ? cpx_round_weights(rows, stage, (long long)n, CPX_DT_BF16, 0, stream) : CPX_OK;
+    };
+    // float32 mode: the forward's operand [N][Kin] as float32 -- itself for a float32 network, else widened exactly into wop, once per
+    // block body (the walk clears in_wop at its top): fc1's copy serves the recomputed product and, folded, the data gradient
+    const void *in_wop = nullptr;
+    auto operand_f32 = [&](const void *Wop, int N, int Kin, const float **W32) -> int {
+        *W32 = half ? wop : (const float *)Wop;
+        if (!half || in_wop == Wop) return CPX_OK;
+        const size_t n4 = (size_t)N * Kin / 4;
+        CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_widen_f32<DT>, grid1(n4), dim3(256), 0, s, Wop, n4, wop));
         CPX_CHECK_LAUNCH();
-        CPX_RUN(transpose_run(CPX_DT_F32, W, N, Kin, wt, s));
-        CPX_RUN(cpx_gemm_f32(dy, wt, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, stream));
+        in_wop = Wop;
         return CPX_OK;
     };
-    // the same Linear in the bf16 gradient mode: a [Ms][Kin] bf16 (rounded once by the caller, or stored in bf16), Wop [N][Kin] the
-    // forward's bf16 operand
-    auto round16 = [&](const float *src, size_t n, void *dst) -> int { return cpx_round_weights(src, dst, (long long)n, CPX_DT_BF16, 0, stream); };
-    auto linear_bwd16 = [&](const float *dy, const void *a16, const void *Wop, int Ms, int N, int Kin, float *dW, float *db, float *da) -> int {
-        CPX_RUN(round16(dy, (size_t)Ms * N, dyb));
-        CPX_RUN(cpx_gemm_tn_bf16(dyb, a16, Ms, N, Kin, 1, dW, Kin, stream));
-        CPX_RUN(cpx_colsum_add(dy, Ms, N, db, ws + L.cs, L.cs_bytes, stream));
-        CPX_RUN(wt16_run(Wop, N, Kin, Kin, wt16, s));
-        return cpx_gemm_half(CPX_DT_BF16, dyb, wt16, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, nullptr, nullptr, nullptr, stream);
+    // the recomputed forward product pre = a Wop^T + bias, pre [Ms][N] float32
+    auto linear_fwd = [&](BwdRows a, const void *Wop, const float *bias, int Ms, int N, int Kin, float *pre) -> int {
+        if (g16) return cpx_gemm_half(CPX_DT_BF16, a.p, Wop, Ms, N, Kin, CPX_EPI_F32, bias, nullptr, pre, N, nullptr, nullptr, nullptr, stream);
+        const float *W32;
+        CPX_RUN(operand_f32(Wop, N, Kin, &W32));
+        return cpx_gemm_f32((const float *)a.p, W32, Ms, N, Kin, CPX_EPI_F32, bias, nullptr, pre, N, stream);
+    };
+    // the backward of a Linear y = a W^T + b with a [Ms][Kin], dy [Ms][N] float32: dW += dy^T a and db += the column sums of the unrounded
+    // dy (dW NULL: neither), da = dy W
+    auto linear_bwd = [&](const float *dy, BwdRows a, BwdWeight W, int Ms, int N, int Kin, float *dW, float *db, float *da) -> int {
+        if (g16) {
+            BwdRows d;
+            CPX_RUN(operand(dy, (size_t)Ms * N, dyb, &d));
+            if (dW) {
+                CPX_RUN(cpx_gemm_tn_bf16(d.p, a.p, Ms, N, Kin, 1, dW, Kin, stream));
+                CPX_RUN(cpx_colsum_add(dy, Ms, N, db, ws + L.cs, L.cs_bytes, stream));
+            }
+            CPX_RUN(wt16_run(W.op, N, Kin, Kin, wt16, s));
+            return cpx_gemm_half(CPX_DT_BF16, d.p, wt16, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, nullptr, nullptr, nullptr, stream);
+        }
+        const float *W32 = W.master;
+        if (W.folds && fuse) CPX_RUN(operand_f32(W.op, N, Kin, &W32));
+        if (dW) {
+            CPX_RUN(transpose_run(CPX_DT_F32, dy, Ms, N, t1, s));
+            CPX_RUN(transpose_run(a.dt, a.p, Ms, Kin, t2, s));
+            CPX_RUN(cpx_gemm_f32(t1, t2, N, Kin, Ms, CPX_EPI_RESID_BF16, nullptr, dW, dW, Kin, stream));
+            hipLaunchKernelGGL(k_colsum_add, grid1(N), dim3(256), 0, s, dy, Ms, N, db);
+            CPX_CHECK_LAUNCH();
+        }
+        if (W32) CPX_RUN(transpose_run(CPX_DT_F32, W32, N, Kin, wt, s));
+        else CPX_RUN(cpx_wt_run(dt, W.op, N, Kin, Kin, wt, s));                // (no master: the operand, widened and transposed in one pass)
+        return cpx_gemm_f32(dy, wt, Ms, Kin, N, CPX_EPI_F32, nullptr, nullptr, da, Kin, stream);
     };
     // folded: dout is the gradient of xhat (gamma = 1 here; dgamma and dbeta come from k_unfold_grads after the last slab)
     auto ln_bwd = [&](const void *x, const float *g, const float *dout, int Ms, float *dx, float *dgamma, float *dbeta) -> int {
@@ -947,11 +980,6 @@ static int blocks_backward_run(const cpx_net_weights *w, const float *params, in
             CPX_RUN(add_run(dbeta, tb, 1024, dbeta, s));
         }
         return add_run(dx, dxl, (size_t)Ms * 1024, dx, s);           // the residual: dx is now the gradient of the LayerNorm's input rows
-    };
-    auto widen = [&](const void *src, size_t n) -> int {
-        CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_widen_f32<DT>, grid1(n / 4), dim3(256), 0, s, src, n / 4, wop));
-        CPX_CHECK_LAUNCH();
-        return CPX_OK;
     };
     for (int c0 = 0; c0 < nS; c0 += BLK_SLAB) {
         const int nc_slab = std::min(BLK_SLAB, nS - c0), Ms_slab = nc_slab * 1024;
@@ -963,83 +991,43 @@ static int blocks_backward_run(const cpx_net_weights *w, const float *params, in
             return CPX_OK;
         };
         // the gradient of the last block's output: dy0 W0 (the rounded operand [256][1024], widened and transposed)
-        if (g16) {
-            CPX_RUN(round16(dy0 + r0 * 256, (size_t)Ms_slab * 256, dyb));
-            CPX_RUN(wt16_run(w->neck0_w, 256, 1024, 1024, wt16, s));
-            CPX_RUN(cpx_gemm_half(CPX_DT_BF16, dyb, wt16, Ms_slab, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx_slab, 1024, nullptr, nullptr, nullptr, stream));
-        } else {
-            CPX_RUN(cpx_wt_run(dt, w->neck0_w, 256, 1024, 1024, wt, s));
-            CPX_RUN(cpx_gemm_f32(dy0 + r0 * 256, wt, Ms_slab, 1024, 256, CPX_EPI_F32, nullptr, nullptr, dx_slab, 1024, stream));
-        }
-        if (dx_all) CPX_HIP(hipMemcpyAsync(dx_all + ((size_t)K * rows_all + r0) * 1024, dx_slab, (size_t)Ms_slab * 4096, hipMemcpyDeviceToDevice, s));
+        CPX_RUN(linear_bwd(dy0 + r0 * 256, BwdRows{}, BwdWeight{w->neck0_w, nullptr, false}, Ms_slab, 256, 1024, nullptr, nullptr, dx_slab));
+        CPX_RUN(pass_down(K));                                     // record K of dx_all: the gradient of x_out
         for (int j = K - 1; j >= 0; --j) {
             const cpx_block_weights &b = w->blocks[first_block + j];
             const float *P = params + (size_t)gn * j;
             float *Gd = grads + (size_t)gn * j;
             const char *base = fws + F.stride * (size_t)j;
-            // the slab's crops that this block ran on: nc of them, from row rb of the block's records, their gradient rows at dx
-            float *dx = dx_slab;
-            size_t rb = r0;
-            int nc = nc_slab;
-            if (keep) {
-                const unsigned char *kj = keep + (size_t)j * nS;
-                const int k0 = kj[c0] != 0, k1 = nc_slab > 1 && kj[c0 + 1] != 0;
-                nc = k0 + k1;
-                rb = 0;
-                for (int c = 0; c < c0; ++c) rb += kj[c] ? 1024 : 0;
-                if (!k0) dx += (size_t)1024 * 1024;                    // the second crop's half
-            }
-            if (!nc) {
+            const SlabKept k = slab_kept(keep ? keep + (size_t)j * nS : nullptr, c0, nc_slab);
+            if (!k.nc) {
                 CPX_RUN(pass_down(j));
                 continue;
             }
-            const int Ms = nc * 1024;
-            const void *xin = base + F.o_x + rb * 1024 * es, *qkv = base + F.o_qkv + rb * 3072 * es, *ao = base + F.o_ao + rb * 1024 * es,
-                       *xmid = base + F.o_mid + rb * 1024 * es;
+            const int nc = k.nc, Ms = nc * 1024;
+            in_wop = nullptr;
+            float *dx = dx_slab + k.dx_off;
+            const void *xin = base + F.o_x + k.rb * 1024 * es, *qkv = base + F.o_qkv + k.rb * 3072 * es, *ao = base + F.o_ao + k.rb * 1024 * es,
+                       *xmid = base + F.o_mid + k.rb * 1024 * es;
+            BwdRows a, h;
             // ---- the MLP: x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2 ----
-            if (fuse) CPX_RUN(ln_fwd(xmid, nullptr, nullptr, Ms, xh, false));
-            else CPX_RUN(ln_fwd(xmid, P + go[8], P + go[9], Ms, xn, half));
-            if (g16) {
-                CPX_RUN(round16(fuse ? xh : xn, (size_t)Ms * 1024, xb));
-                CPX_RUN(cpx_gemm_half(CPX_DT_BF16, xb, b.fc1_w, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, nullptr, nullptr, nullptr, stream));   // pre
-                hipLaunchKernelGGL(k_gelu_fwd_round<CPX_DT_BF16>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2);                  // h
-                CPX_CHECK_LAUNCH();
-                CPX_RUN(round16(b2, (size_t)Ms * 4096, hb));                                                                   // (exact: h is rounded)
-                CPX_RUN(linear_bwd16(dx, hb, b.fc2_w, Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                          // fc2 -> dh
-                CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                             // dpre
-                CPX_RUN(linear_bwd16(b2, xb, b.fc1_w, Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));                          // fc1 -> d LN2 output
-            } else {
-                const float *w1op = (const float *)b.fc1_w;              // the operand the forward multiplied by (folded where it folds)
-                if (half) {
-                    CPX_RUN(widen(b.fc1_w, (size_t)4096 * 1024));
-                    w1op = wop;
-                }
-                CPX_RUN(cpx_gemm_f32(fuse ? xh : xn, w1op, Ms, 4096, 1024, CPX_EPI_F32, b.fc1_b, nullptr, b1, 4096, stream));     // pre
-                CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_gelu_fwd_round<DT>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2));   // h
-                CPX_CHECK_LAUNCH();
-                CPX_RUN(linear_bwd(dx, b2, CPX_DT_F32, P + go[12], Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));                // fc2 -> dh
-                CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                // dpre
-                CPX_RUN(linear_bwd(b2, fuse ? xh : xn, CPX_DT_F32, fuse ? w1op : P + go[10], Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));   // fc1 -> d LN2 output (folded: d xhat)
-            }
+            CPX_RUN(ln_fwd(xmid, P + go[8], P + go[9], Ms));
+            CPX_RUN(operand(ln, (size_t)Ms * 1024, xb, &a));
+            CPX_RUN(linear_fwd(a, b.fc1_w, b.fc1_b, Ms, 4096, 1024, b1));                                                         // pre
+            CPX_DT_DISPATCH(dt, DT, hipLaunchKernelGGL(k_gelu_fwd_round<DT>, grid1((size_t)Ms * 4096), dim3(256), 0, s, b1, (size_t)Ms * 4096, b2));   // h
+            CPX_CHECK_LAUNCH();
+            CPX_RUN(operand(b2, (size_t)Ms * 4096, hb, &h));                                                                      // (exact: h is rounded)
+            CPX_RUN(linear_bwd(dx, h, BwdWeight{b.fc2_w, P + go[12], false}, Ms, 1024, 4096, Gd + go[12], Gd + go[13], b3));             // fc2 -> dh
+            CPX_RUN(cpx_gelu_backward(b1, b3, (size_t)Ms * 4096, b2, stream));                                                    // dpre
+            CPX_RUN(linear_bwd(b2, a, BwdWeight{b.fc1_w, P + go[10], true}, Ms, 4096, 1024, Gd + go[10], Gd + go[11], b3));    // fc1 -> d LN2 output (folded: d xhat)
             CPX_RUN(ln_bwd(xmid, P + go[8], b3, Ms, dx, Gd + go[8], Gd + go[9]));                                                 // dx = d x_mid
             // ---- attention: x_mid = x_in + attention(LN1(x_in) Wqkv^T + bqkv) Wp^T + bp ----
-            if (g16) CPX_RUN(linear_bwd16(dx, ao, b.proj_w, Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                       // proj -> dO (ao is stored in bf16)
-            else CPX_RUN(linear_bwd(dx, ao, dt, P + go[6], Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));                           // proj -> dO
+            CPX_RUN(linear_bwd(dx, BwdRows{ao, dt}, BwdWeight{b.proj_w, P + go[6], false}, Ms, 1024, 1024, Gd + go[6], Gd + go[7], b3));  // proj -> dO
             if (a16) CPX_RUN(cpx_attention_backward_bf16_run(qkv, b.rel_h, b.rel_w, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
             else CPX_RUN(cpx_attention_backward_run(dt, qkv, b.rel_h, b.rel_w, nullptr, b3, nc, b1, Gd + go[4], Gd + go[5], 1, ws + L.attn, L.attn_bytes, stream));
-            if (g16) {
-                if (fuse) CPX_RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
-                else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, true));
-                CPX_RUN(round16(fuse ? xh : xn, (size_t)Ms * 1024, xb));
-                CPX_RUN(linear_bwd16(b1, xb, b.qkv_w, Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));                            // qkv -> d LN1 output
-            } else {
-                if (fuse) {
-                    CPX_RUN(ln_fwd(xin, nullptr, nullptr, Ms, xh, false));
-                    CPX_RUN(widen(b.qkv_w, (size_t)3072 * 1024));
-                } else CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms, xn, half));
-                CPX_RUN(linear_bwd(b1, fuse ? xh : xn, CPX_DT_F32, fuse ? wop : P + go[2], Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));       // qkv -> d LN1 output (folded: d xhat)
-            }
-            CPX_RUN(ln_bwd(xin, P + go[0], b3, Ms, dx, Gd + go[0], Gd + go[1]));                                              // dx = d x_in
+            CPX_RUN(ln_fwd(xin, P + go[0], P + go[1], Ms));
+            CPX_RUN(operand(ln, (size_t)Ms * 1024, xb, &a));
+            CPX_RUN(linear_bwd(b1, a, BwdWeight{b.qkv_w, P + go[2], true}, Ms, 3072, 1024, Gd + go[2], Gd + go[3], b3));    // qkv -> d LN1 output (folded: d xhat)
+            CPX_RUN(ln_bwd(xin, P + go[0], b3, Ms, dx, Gd + go[0], Gd + go[1]));                                                  // dx = d x_in
             CPX_RUN(pass_down(j));
         }
     }
@@ -1054,37 +1042,35 @@ static int blocks_backward_run(const cpx_net_weights *w, const float *params, in
         }
     return CPX_OK;
 }
+// the exported entries: cpx_blocks_backward_drop is blocks_backward_run, each older one that with arguments fixed
 extern "C" int cpx_blocks_backward_in(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                       size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,
                                       float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream) {
     return blocks_backward_run(w, params, nS, first_block, nullptr, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype, grads,
                                dx_all, dx_in, workspace, workspace_bytes, stream);
 }
-// cpx_blocks_backward_in for a forward of cpx_blocks_forward_train_drop with the same keep (NULL or all ones: cpx_blocks_backward_in itself)
 extern "C" int cpx_blocks_backward_drop(const cpx_net_weights *w, const float *params, int nS, int first_block, const unsigned char *keep,
                                         const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dy0, int grad_dtype,
                                         int attn_grad_dtype, float *grads, float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes,
                                         void *stream) {
-    CPX_REQUIRE(blocks_weights_ok(w, first_block) && blocks_args_ok(nS, w->dtype, w->depth - first_block));
-    if (!keep_drops(keep, w->depth - first_block, nS)) keep = nullptr;
     return blocks_backward_run(w, params, nS, first_block, keep, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype, grads,
                                dx_all, dx_in, workspace, workspace_bytes, stream);
 }
 extern "C" int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                       size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads,
                                       float *dx_all, void *workspace, size_t workspace_bytes, void *stream) {
-    return cpx_blocks_backward_in(w, params, nS, first_block, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype, grads, dx_all,
-                                  nullptr, workspace, workspace_bytes, stream);
+    return blocks_backward_run(w, params, nS, first_block, nullptr, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype, grads,
+                               dx_all, nullptr, workspace, workspace_bytes, stream);
 }
 extern "C" int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                       size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, float *grads, float *dx_all,
                                       void *workspace, size_t workspace_bytes, void *stream) {
-    return cpx_blocks_backward_mp(w, params, nS, first_block, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, CPX_DT_F32, grads, dx_all,
-                                  workspace, workspace_bytes, stream);
+    return blocks_backward_run(w, params, nS, first_block, nullptr, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, CPX_DT_F32, grads,
+                               dx_all, nullptr, workspace, workspace_bytes, stream);
 }
 extern "C" int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int nS, int first_block, const void *fwd_workspace,
                                    size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
                                    size_t workspace_bytes, void *stream) {
-    return cpx_blocks_backward_ex(w, params, nS, first_block, fwd_workspace, fwd_workspace_bytes, dy0, CPX_DT_F32, grads, dx_all, workspace,
-                                  workspace_bytes, stream);
+    return blocks_backward_run(w, params, nS, first_block, nullptr, fwd_workspace, fwd_workspace_bytes, dy0, CPX_DT_F32, CPX_DT_F32, grads,
+                               dx_all, nullptr, workspace, workspace_bytes, stream);
 }

@@ -206,10 +206,7 @@ static EmbedBwdLayout embed_bwd_layout(int nS, int grad_dtype) {
     L.total = a.o;
     return L;
 }
-static bool embed_args_ok(int nS, int dtype, int grad_dtype) {        // nS: the range of the blocks' backward
-    return nS > 0 && (size_t)nS * 1024 < 0x7fffffffull && dtype_ok(dtype) &&
-           (grad_dtype == CPX_DT_F32 || (grad_dtype == CPX_DT_BF16 && dtype == CPX_DT_BF16));
-}
+static bool embed_args_ok(int nS, int dtype, int grad_dtype) { return cpx_crops_ok(nS) && dtype_ok(dtype) && cpx_grad_dtype_ok(dtype, grad_dtype); }
 extern "C" size_t cpx_embed_backward_workspace_bytes(int nS, int dtype, int grad_dtype) {
     return embed_args_ok(nS, dtype, grad_dtype) ? embed_bwd_layout(nS, grad_dtype).total : 0;
 }

@@ -1046,10 +1046,10 @@ def _keep_mask(keep, K: int, n: int, what: str):
 
 def blocks_forward_train(weights, x: torch.Tensor, first_block: int, head: torch.Tensor | None = None,
                          workspace: torch.Tensor | None = None, keep=None) -> BlocksForwardOut:
-    """``cpx_blocks_forward_train``: blocks ``first_block`` .. depth - 1 of ``weights`` (an ``engine.NetWeights``) and the tail on the rows
-    ``x`` (n * 1024, 1024) in the network dtype -- the input of block ``first_block`` --, keeping what the backward needs.  ``keep``
-    (K, n) uint8, host: layer drop (``cpx_blocks_forward_train_drop``), block j runs on crop i where ``keep[j, i]`` is non-zero and
-    passes the other crops through; the workspace is then ``blocks_train_workspace(..., drop=True)``."""
+    """``cpx_blocks_forward_train_drop``: blocks ``first_block`` .. depth - 1 of ``weights`` (an ``engine.NetWeights``) and the tail on the
+    rows ``x`` (n * 1024, 1024) in the network dtype -- the input of block ``first_block`` --, keeping what the backward needs.  Without
+    ``keep`` the mask pointer is null: ``cpx_blocks_forward_train``.  ``keep`` (K, n) uint8, host: layer drop, block j runs on crop i where
+    ``keep[j, i]`` is non-zero and passes the other crops through; the workspace is then ``blocks_train_workspace(..., drop=True)``."""
     c, L = weights.c, _lib.lib()
     if x.dim() != 2 or x.shape[1] != 1024 or x.shape[0] == 0 or x.shape[0] % 1024 or x.dtype not in _DT or _DT[x.dtype] != c.dtype \
             or not x.is_contiguous() or not x.is_cuda:
@@ -1066,12 +1066,9 @@ def blocks_forward_train(weights, x: torch.Tensor, first_block: int, head: torch
         head = torch.empty((rows, c.ld_head), dtype=torch.float32, device=dev)
     if head.dtype != torch.float32 or tuple(head.shape) != (rows, c.ld_head) or not head.is_contiguous() or workspace.dtype != torch.uint8:
         raise ValueError("blocks_forward_train: head must be contiguous float32 (rows, ld_head) and workspace uint8")
-    if keep is None:
-        check(L.cpx_blocks_forward_train(C.byref(c), ptr(x), nS, first_block, ptr(head), ptr(workspace), workspace.numel(), _stream(dev)),
-              "blocks_forward_train")
-    else:
-        check(L.cpx_blocks_forward_train_drop(C.byref(c), ptr(x), nS, first_block, keep.ctypes.data, ptr(head), ptr(workspace),
-                                              workspace.numel(), _stream(dev)), "blocks_forward_train (keep)")
+    check(L.cpx_blocks_forward_train_drop(C.byref(c), ptr(x), nS, first_block, None if keep is None else keep.ctypes.data, ptr(head),
+                                          ptr(workspace), workspace.numel(), _stream(dev)),
+          "blocks_forward_train" if keep is None else "blocks_forward_train (keep)")
     off = (C.c_size_t * (4 * K + 2))()
     check(L.cpx_blocks_train_layout(nS, c.dtype, K, off), "blocks_train_layout")
     es = x.element_size()
@@ -1128,7 +1125,7 @@ def blocks_backward_workspace(n_subtiles: int, dtype_code: int, device, grad_dty
 def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: torch.Tensor, grads: torch.Tensor | None = None,
                     workspace: torch.Tensor | None = None, dx_all: torch.Tensor | None = None, grad_dtype=torch.float32,
                     attn_grad_dtype=torch.float32, dx_in: torch.Tensor | None = None) -> torch.Tensor:
-    """``cpx_blocks_backward_in`` (``cpx_blocks_backward_mp`` plus ``dx_in``): the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
+    """``cpx_blocks_backward_drop``: the gradients of the K trained blocks of ``fwd`` into the flat float32 ``grads`` (K records of
     ``block_grad_layout``), from ``params`` (the K blocks' unfolded parameters as the forward reads them, same layout) and ``dy0``
     (rows, 256) float32, which ``neck_backward`` leaves in its workspace.  ``dx_all`` (K + 1, rows, 1024) float32, when given, receives
     the gradient of every trained block's input and (last) of the last block's output.  ``grad_dtype`` torch.float32: the exact-float32
@@ -1136,7 +1133,7 @@ def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: t
     ``attn_grad_dtype`` torch.bfloat16 (with ``grad_dtype`` torch.bfloat16 only): the attention backward on bf16 operands too
     (``cpx_attention_backward_bf16``); torch.float32 leaves it in float32.  ``dx_in`` (rows, 1024) float32, when given, receives the
     gradient of the first trained block's input alone (record 0 of ``dx_all`` without the rest): what ``embed_backward`` takes.
-    A forward under a layer-drop mask (``fwd.keep``) gets ``cpx_blocks_backward_drop`` with that mask."""
+    The mask of a forward under layer drop (``fwd.keep``) goes along; without one the mask pointer is null (``cpx_blocks_backward_in``)."""
     c, L = weights.c, _lib.lib()
     gd = _grad_dtype_code(grad_dtype, c.dtype, "blocks_backward")
     ad = _attn_grad_dtype_code(attn_grad_dtype, gd, "blocks_backward")
@@ -1160,16 +1157,10 @@ def blocks_backward(weights, params: torch.Tensor, fwd: BlocksForwardOut, dy0: t
         workspace = blocks_backward_workspace(rows // 1024, c.dtype, dev, grad_dtype, attn_grad_dtype)
     if workspace.dtype != torch.uint8 or fwd.workspace.dtype != torch.uint8:
         raise ValueError("blocks_backward: workspaces are uint8 tensors")
-    # (cpx_blocks_backward_mp is this entry with dx_in NULL)
     keep = getattr(fwd, "keep", None)                      # (a BlocksForwardOut put together by hand has no mask)
-    if keep is None:
-        check(L.cpx_blocks_backward_in(C.byref(c), ptr(params), rows // 1024, fwd.first_block, ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0),
-                                       gd, ad, ptr(grads), ptr(dx_all), ptr(dx_in), ptr(workspace), workspace.numel(), _stream(dev)),
-              "blocks_backward")
-    else:
-        check(L.cpx_blocks_backward_drop(C.byref(c), ptr(params), rows // 1024, fwd.first_block, keep.ctypes.data, ptr(fwd.workspace),
-                                         fwd.workspace.numel(), ptr(dy0), gd, ad, ptr(grads), ptr(dx_all), ptr(dx_in), ptr(workspace),
-                                         workspace.numel(), _stream(dev)), "blocks_backward (keep)")
+    check(L.cpx_blocks_backward_drop(C.byref(c), ptr(params), rows // 1024, fwd.first_block, None if keep is None else keep.ctypes.data,
+                                     ptr(fwd.workspace), fwd.workspace.numel(), ptr(dy0), gd, ad, ptr(grads), ptr(dx_all), ptr(dx_in), ptr(workspace),
+                                     workspace.numel(), _stream(dev)), "blocks_backward" if keep is None else "blocks_backward (keep)")
     return grads
 
 

@@ -648,7 +648,17 @@ int cpx_neck_backward(const cpx_net_weights *w, const void *x, int n_subtiles, c
  *   workspace 256-byte aligned.
  *   cpx_gelu_backward: dpre = dh * (Phi(pre) + pre phi(pre)), the derivative of the erf GELU of the mlp.lin1 epilogue, n float32
  *   elements (a multiple of 4).
- *   cpx_blocks_forward_train: the launches of cpx_net_forward for blocks first_block .. depth - 1 (K = depth - first_block of them), in
+ * The two drivers below (forward, backward) each have ONE body and ONE contract, stated for the widest entry; every older entry is that
+ * entry with some arguments fixed (the tables), bit for bit and launch for launch.  keep, in both: NULL, or [n_blocks][n_subtiles] uint8 on
+ * the HOST, read before the call returns -- layer drop (stochastic depth, vit_sam.py:165-173): block first_block + j runs on crop n where
+ * keep[j][n] != 0,
+ *   x_{j+1}[n] = keep[j][n] ? block_j(x_j[n]) : x_j[n]     (the second branch bit for bit)
+ * which is the reference's x * mask + blk(x) * (1 - mask) with mask = 1 - keep.  Nothing inside a block crosses a crop, so a block runs on
+ * its kept crops alone, compacted in crop order; a dropped (block, crop) pair costs neither a forward nor a backward.  keep NULL or all
+ * non-zero is no mask: the launches of the entries without the argument.
+ *
+ * cpx_blocks_forward_train_drop(w, x, n_subtiles, first_block, keep, head, workspace, workspace_bytes, stream) -- the training forward.
+ *   Without a mask: the launches of cpx_net_forward for blocks first_block .. depth - 1 (K = depth - first_block of them), in
  *   their order and with their MLP row parts (cpx_net_mlp_parts), on x [n_subtiles * 1024][1024] (network dtype), the input of block
  *   first_block -- what cpx_net_forward leaves at cpx_net_backbone_offset when run with a host copy of the weights whose depth is
  *   first_block -- then cpx_neck_forward_train.  Kept per trained block, in the network dtype, at the 4 K + 2 byte offsets of
@@ -659,43 +669,89 @@ int cpx_neck_backward(const cpx_net_weights *w, const void *x, int n_subtiles, c
  *   neck's tensors and x_out are bitwise cpx_net_forward's for the same n_subtiles for float32, for unfused weights, and for the fused
  *   half types below 16 crops; from 16 crops up cpx_net_forward takes a block's row statistics from the GEMM before it, and the first
  *   trained block takes them from cpx_row_stats instead (same sums, another order).  Not with a UNet head.
- *   cpx_blocks_backward: walks the trained blocks in reverse from dy0 [rows][256] float32 = d loss / d (x_out W0^T), which
+ *   Under a mask: the running full-batch rows live in the x_out record; per block the kept crops are gathered into the block's x_in
+ *   record (with their statistics where the weights fold LayerNorm), the block runs on n_keep crops exactly as it runs without a mask on a
+ *   batch of n_keep, and its output is scattered back.  The x_in, qkv, ao and x_mid records of block j hold n_keep_j * 1024 valid rows at
+ *   their front; a block that keeps nothing launches nothing; x_out and the neck cover all crops.
+ *   workspace: cpx_blocks_train_workspace_bytes_drop (the layout of cpx_blocks_train_layout, then one staging tensor of the batch's
+ *   rows); without a mask the size of cpx_blocks_train_workspace_bytes, which ends before the staging tensor, suffices.
+ *     cpx_blocks_forward_train(w, x, n, first_block, head, ...)   = cpx_blocks_forward_train_drop with keep NULL
+ *
+ * cpx_blocks_backward_drop(w, params, n_subtiles, first_block, keep, fwd_workspace, fwd_workspace_bytes, dy0, grad_dtype, attn_grad_dtype,
+ * grads, dx_all, dx_in, workspace, workspace_bytes, stream) -- the backward of that forward.
+ *   Walks the trained blocks in reverse from dy0 [rows][256] float32 = d loss / d (x_out W0^T), which
  *   cpx_neck_backward leaves at off[3] of its workspace (d x_out = dy0 W0 is formed here).  Per block: lin2 (dW, db, dh), GELU backward,
- *   lin1, LayerNorm 2 backward, the residual add; proj, attention backward, qkv, LayerNorm 1 backward, the residual add.  Every
- *   dX = dY W and dW = dY^T X is the exact-float32 GEMM behind a transposing copy.  params: K records of cpx_block_grad_layout holding
+ *   lin1, LayerNorm 2 backward, the residual add; proj, attention backward, qkv, LayerNorm 1 backward, the residual add.
+ *   params: K records of cpx_block_grad_layout holding
  *   the UNFOLDED parameters as the forward reads them (each rounded through the network dtype, float32; the rel slots are not read);
  *   grads: K records of the same layout, ln1 gamma, beta | qkv W, b | rel_h, rel_w [64][64] | proj W, b | ln2 gamma, beta | fc1 W, b |
  *   fc2 W, b: with respect to the unfolded gamma, beta, W, b (not the folded operands of fuse_ln) and to the operand tables.  Where the
  *   forward folds LayerNorm into qkv / lin1, the data gradient and the recomputed pre-activation use the folded operand the forward
  *   multiplied by, and dW, dgamma, dbeta follow from dWf = dpre^T xhat by the chain rule through the fold after the last slab.  Rounding
- *   to the network dtype is the identity (straight-through).  The crops go through all blocks in slabs of
- *   cpx_blocks_backward_slab_crops() = 2 and the slabs' gradients are added in slab order, so the workspace does not grow with the
- *   batch: 241 MiB for 8 and for 32 crops.  dx_all: NULL, or [K + 1][rows][1024] float32 receiving the gradient of every trained
- *   block's input (record j) and of x_out (record K).                                                                              */
+ *   to the network dtype is the identity (straight-through).
+ *   keep: the mask the forward ran with.  The slabs of two adjacent crops and their order stay; per block the body runs on the slab's
+ *   kept crops -- two (adjacent in the compact records), one (1024 rows, on that crop's half of the slab's dx) or none (skipped) -- from
+ *   the compact row offset 1024 * (kept crops of that block before the slab).  A dropped crop's dx rows pass down untouched, bitwise,
+ *   into dx_all and dx_in as well; a block with no kept crop has an all-zero gradient record.
+ *   grad_dtype: CPX_DT_F32 -- every dX = dY W and dW = dY^T X is the exact-float32 GEMM behind a transposing copy.  CPX_DT_BF16 (mixed-
+ *   precision gradients; additive, no ABI bump) is accepted for a CPX_DT_BF16 network only (fp16 gradients would need loss scaling, a float32 network has
+ *   no half operands: both are CPX_EINVAL).  In that mode every matrix product of the backward takes both operands rounded to bf16 (round
+ *   to nearest even, each value once), accumulates in float32 on the bf16 MFMA and writes float32:
+ *     dW += bf16(dy)^T bf16(a)   da = bf16(dy) W   pre = bf16(xhat or xn) W1^T + b1   d x_out = bf16(dy0) W0
+ *   with W the operand the forward multiplied by (exact in bf16, folded where the forward folds) and db += the column sums of the UNROUNDED
+ *   float32 dy in float64.  Activation gradients stay float32 between the products; LayerNorm, GELU and attention backward, the unfolding
+ *   of the folded gradients, the slabs and their order are those of the float32 mode.
+ *   attn_grad_dtype: the precision of the attention backward, a third switch.  CPX_DT_F32 is cpx_attention_backward; CPX_DT_BF16 runs
+ *   cpx_attention_backward_bf16 in its place and needs grad_dtype CPX_DT_BF16 (hence a bf16 network); every other combination is
+ *   CPX_EINVAL (workspace bytes 0) before anything is launched.
+ *   dx_all: NULL, or [K + 1][rows][1024] float32 receiving the gradient of every trained block's input (record j) and of x_out (record K).
+ *   dx_in (additive, no ABI bump): NULL, or [rows][1024] float32 receiving the gradient of block first_block's input alone -- record 0 of dx_all without the K
+ *   records after it (128 MB at 32 crops where dx_all for K = 24 is 3.3 GB), copied per slab from the same buffer.  16-byte aligned like
+ *   its neighbours.  What cpx_embed_backward takes when first_block is 0.
+ *   workspaces: fwd_workspace is what the forward filled; workspace has cpx_blocks_backward_workspace_bytes_mp(n_subtiles, dtype,
+ *   grad_dtype, attn_grad_dtype) bytes, whatever keep and attn_grad_dtype are (the two attention backwards share one layout).  It is
+ *   smaller in the bf16 mode (190 MiB against 241 MiB): it holds no transposed float32 operands.
+ *   slabs: the crops go through all blocks in slabs of cpx_blocks_backward_slab_crops() = 2 and the slabs' gradients are added in slab
+ *   order, so the workspace does not grow with the batch: 241 MiB for 8 and for 32 crops.
+ *   No atomics in any mode or under any mask: two runs are bitwise equal.
+ *   CPX_EINVAL, before anything is launched: a null w, params, fwd_workspace, dy0, grads or workspace; workspace or fwd_workspace too
+ *   short or not 256-byte aligned; params, dy0, grads, dx_all or dx_in not 16-byte aligned; first_block outside 0 .. depth - 1 or more
+ *   than 4096 trained blocks; weights with a UNet head, with a null neck0_w or float32 ones with fuse_ln; n_subtiles * 1024 beyond
+ *   2^31 - 2 rows; the precision combinations named above.
+ *     cpx_blocks_backward_in(.., dy0, grad_dtype, attn_grad_dtype, grads, dx_all, dx_in, ..)  = cpx_blocks_backward_drop with keep NULL
+ *     cpx_blocks_backward_mp(.., dy0, grad_dtype, attn_grad_dtype, grads, dx_all, ..)         = ... and dx_in NULL
+ *     cpx_blocks_backward_ex(.., dy0, grad_dtype, grads, dx_all, ..)                          = ... and attn_grad_dtype CPX_DT_F32
+ *     cpx_blocks_backward(.., dy0, grads, dx_all, ..)                                         = ... and grad_dtype CPX_DT_F32
+ *     cpx_blocks_backward_workspace_bytes_ex(n, dtype, grad_dtype)  = cpx_blocks_backward_workspace_bytes_mp with attn_grad_dtype CPX_DT_F32
+ *     cpx_blocks_backward_workspace_bytes(n, dtype)                 = ... and grad_dtype CPX_DT_F32                                       */
 size_t cpx_blocks_train_workspace_bytes(int n_subtiles, int dtype, int n_blocks);
+size_t cpx_blocks_train_workspace_bytes_drop(int n_subtiles, int dtype, int n_blocks);
 int cpx_blocks_train_layout(int n_subtiles, int dtype, int n_blocks, size_t *off /* [4 * n_blocks + 2] */);
+int cpx_blocks_forward_train_drop(const cpx_net_weights *w, const void *x, int n_subtiles, int first_block, const unsigned char *keep,
+                                  float *head, void *workspace, size_t workspace_bytes, void *stream);
 int cpx_blocks_forward_train(const cpx_net_weights *w, const void *x, int n_subtiles, int first_block, float *head, void *workspace,
                              size_t workspace_bytes, void *stream);
 long long cpx_block_grad_layout(long long *off /* [14] or NULL */);
-size_t cpx_blocks_backward_workspace_bytes(int n_subtiles, int dtype);
 int cpx_blocks_backward_slab_crops(void);
-int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
-                        size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
-                        size_t workspace_bytes, void *stream);
-/* Mixed-precision gradients for the trained blocks (additive, no ABI bump): grad_dtype CPX_DT_F32 is cpx_blocks_backward (which forwards
- * here) bit for bit; CPX_DT_BF16 is accepted for a CPX_DT_BF16 network only (fp16 gradients would need loss scaling, a float32 network has
- * no half operands: both are CPX_EINVAL).  In that mode every matrix product of the backward takes both operands rounded to bf16 (round to
- * nearest even, each value once), accumulates in float32 on the bf16 MFMA and writes float32:
- *   dW += bf16(dy)^T bf16(a)   da = bf16(dy) W   pre = bf16(xhat or xn) W1^T + b1   d x_out = bf16(dy0) W0
- * with W the operand the forward multiplied by (exact in bf16, folded where the forward folds) and db += the column sums of the UNROUNDED
- * float32 dy in float64.  Activation gradients stay float32 between the products; LayerNorm, GELU and attention backward, the unfolding
- * of the folded gradients, the slabs and their order are those of the float32 mode; no atomics, bitwise reproducible.  The workspace is
- * smaller (190 MiB against 241 MiB): it holds no transposed float32 operands.                                                         */
+size_t cpx_blocks_backward_workspace_bytes_mp(int n_subtiles, int dtype, int grad_dtype, int attn_grad_dtype);
 size_t cpx_blocks_backward_workspace_bytes_ex(int n_subtiles, int dtype, int grad_dtype);
+size_t cpx_blocks_backward_workspace_bytes(int n_subtiles, int dtype);
+int cpx_blocks_backward_drop(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const unsigned char *keep,
+                             const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype,
+                             float *grads, float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream);
+int cpx_blocks_backward_in(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
+                           size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads, float *dx_all,
+                           float *dx_in, void *workspace, size_t workspace_bytes, void *stream);
+int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
+                           size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads, float *dx_all,
+                           void *workspace, size_t workspace_bytes, void *stream);
 int cpx_blocks_backward_ex(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
                            size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, float *grads, float *dx_all, void *workspace,
                            size_t workspace_bytes, void *stream);
-/* The weight-gradient product of that mode (csrc/cpx_gemm_tn.hip): out[n][k] (+)= sum_m A[m][n] B[m][k], A [M][N] and B [M][K] bf16 row-major
+int cpx_blocks_backward(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
+                        size_t fwd_workspace_bytes, const float *dy0, float *grads, float *dx_all, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* The weight-gradient product of the bf16 gradient mode (csrc/cpx_gemm_tn.hip): out[n][k] (+)= sum_m A[m][n] B[m][k], A [M][N] and B [M][K] bf16 row-major
  * (both operands are read transposed, by ds_read_b64_tr_b16: no transposing copy), out [N][ld_out] float32; add = 1 adds to what out
  * holds, add = 0 overwrites.  Each element is one float32 accumulation over m in order.  Requires M % 64 == 0, N % 128 == 0, K % 128 == 0
  * (all > 0), ld_out >= K, add 0 or 1, and A, B, out 16-byte aligned; anything else returns CPX_EINVAL and launches nothing.          */
@@ -726,24 +782,12 @@ int cpx_gelu_backward(const float *pre, const float *dh, size_t n, float *dpre, 
  * Every product accumulates in float32 on v_mfma_f32_32x32x16_bf16; no floating-point atomics, no workgroup waits for another, every sum
  * in a fixed order: two runs are bitwise equal.  The workspace has cpx_attention_backward's size.  Null pointers, qkv / rel_h / rel_w /
  * dO / dqkv not 16-byte aligned, a workspace not 256-byte aligned or too short, n_subtiles outside 1 .. 16383: CPX_EINVAL, nothing is
- * launched.
- * cpx_blocks_backward_mp: cpx_blocks_backward_ex with the precision of the attention backward as a third switch.  attn_grad_dtype
- * CPX_DT_F32 is cpx_blocks_backward_ex (which forwards here): the same launches, the same workspace size.  CPX_DT_BF16 runs
- * cpx_attention_backward_bf16 in its place and needs grad_dtype CPX_DT_BF16 (hence a bf16 network); every other combination is
- * CPX_EINVAL (workspace bytes 0) before anything is launched.                                                                       */
+ * launched.  The blocks' backward runs it where attn_grad_dtype is CPX_DT_BF16.                                                       */
 size_t cpx_attention_backward_bf16_workspace_bytes(int n_subtiles);
 int cpx_attention_backward_bf16(const void *qkv, const void *rel_h, const void *rel_w, const float *dO, int n_subtiles, float *dqkv,
                                 float *drel_h, float *drel_w, void *workspace, size_t workspace_bytes, void *stream);
-size_t cpx_blocks_backward_workspace_bytes_mp(int n_subtiles, int dtype, int grad_dtype, int attn_grad_dtype);
-int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
-                           size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads, float *dx_all,
-                           void *workspace, size_t workspace_bytes, void *stream);
 /* Training the patch embedding and the position table (csrc/cpx_train_embed.hip; additive, no ABI bump): with first_block 0 the last stage
- * of full fine-tuning.
- * cpx_blocks_backward_in: cpx_blocks_backward_mp (which forwards here with NULL, bit for bit) with one more output, dx_in: NULL, or
- * [rows][1024] float32 receiving the gradient of block first_block's input alone -- record 0 of dx_all without the K records after it (128 MB
- * at 32 crops where dx_all for K = 24 is 3.3 GB), copied per slab from the same buffer.  16-byte aligned like its neighbours; the workspace
- * sizes are those of cpx_blocks_backward_workspace_bytes_mp.
+ * of full fine-tuning, from the dx_in of the blocks' backward.
  * cpx_embed_grad_layout: the element count of one flat float32 record W [1024][192] | b [1024] | pos [1024][1024] (off: the three element
  * offsets); k of W in the order of pe_w / cpx_patchify_f32.
  * cpx_embed_backward: the gradients of x = round(p W^T + b + pos[row % 1024]) (the cpx_gemm(..., CPX_EPI_POS_BF16, ...) launch that opens
@@ -765,45 +809,20 @@ int cpx_blocks_backward_mp(const cpx_net_weights *w, const float *params, int n_
  * 13 MiB in float32 mode; 0 for invalid arguments).  Null pointers, patches / dx_in / grads not 16-byte aligned, a workspace not 256-byte
  * aligned or too short, n_subtiles outside the range of cpx_blocks_backward, an unknown dtype, grad_dtype CPX_DT_BF16 with a CPX_DT_F16 or
  * CPX_DT_F32 network: CPX_EINVAL, nothing is launched.                                                                                  */
-int cpx_blocks_backward_in(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const void *fwd_workspace,
-                           size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype, float *grads, float *dx_all,
-                           float *dx_in, void *workspace, size_t workspace_bytes, void *stream);
 long long cpx_embed_grad_layout(long long *off /* [3] or NULL */);
 size_t cpx_embed_backward_workspace_bytes(int n_subtiles, int dtype, int grad_dtype);
 int cpx_embed_backward(int dtype, const void *patches, const float *dx_in, int n_subtiles, int grad_dtype, float *grads, void *workspace,
                        size_t workspace_bytes, void *stream);
-/* Layer drop (stochastic depth, vit_sam.py:165-173) for the trained blocks (csrc/cpx_train_blocks.hip; additive, no ABI bump).  keep
- * [n_blocks][n_subtiles] uint8 on the HOST, read before the call returns: block first_block + j runs on crop n where keep[j][n] != 0,
- *   x_{j+1}[n] = keep[j][n] ? block_j(x_j[n]) : x_j[n]     (the second branch bit for bit)
- * which is the reference's x * mask + blk(x) * (1 - mask) with mask = 1 - keep.  Nothing inside a block crosses a crop, so a block runs on
- * its kept crops alone, compacted in crop order; a dropped (block, crop) pair costs neither a forward nor a backward.
+/* The crop moves of layer drop (csrc/cpx_train_blocks.hip; additive, no ABI bump), which the training forward runs under a mask.
  * cpx_gather_crops / cpx_scatter_crops: the 1024 rows of each crop of `crops` (HOST, n entries, strictly increasing, each < n_subtiles)
  * from a full [n_subtiles * 1024][1024] buffer of `dtype` into a compact [n * 1024][1024] one in list order, and back (the full buffer's
  * other crops untouched).  One wave per row, 16-byte accesses; the list travels by value in the kernel arguments, 64 crops per launch: no
  * device table, no allocation, nothing read after the call returns.  stats: NULL, or (half types) [n * 1024][4][2] float32 receiving the
  * row statistics of the compact rows in the same pass, bitwise cpx_row_stats of them (the same code sums both).  n = 0 launches nothing
  * and returns CPX_OK; a list that is unordered, repeats a crop or names a crop >= n_subtiles, a null or not 16-byte aligned buffer,
- * stats with CPX_DT_F32: CPX_EINVAL, nothing is launched.  src and dst are distinct buffers.
- * cpx_blocks_forward_train_drop: cpx_blocks_forward_train under the mask.  The running full-batch rows live in the x_out record; per
- * block the kept crops are gathered into the block's x_in record (with their statistics where the weights fold LayerNorm), the block runs
- * on n_keep crops exactly as cpx_blocks_forward_train runs it on a batch of n_keep, and its output is scattered back.  The x_in, qkv, ao
- * and x_mid records of block j hold n_keep_j * 1024 valid rows at their front; a block that keeps nothing launches nothing; x_out and
- * the neck cover all crops.  workspace: cpx_blocks_train_workspace_bytes_drop (the layout of cpx_blocks_train_layout, then one staging
- * tensor).  keep NULL or all non-zero forwards to cpx_blocks_forward_train: the same launches, and its workspace size suffices.
- * cpx_blocks_backward_drop: cpx_blocks_backward_in for such a forward, with the same keep.  The slabs of two adjacent crops and their order
- * stay; per block the body runs on the slab's kept crops -- two (adjacent in the compact records), one (1024 rows, on that crop's half of
- * the slab's dx) or none (skipped) -- from the compact row offset 1024 * (kept crops of that block before the slab).  A dropped crop's dx
- * rows pass down untouched, bitwise, into dx_all and dx_in as well; a block with no kept crop has an all-zero gradient record.  Every
- * precision combination of cpx_blocks_backward_mp; its workspace size; no atomics, two runs are bitwise equal.  keep NULL or all non-zero
- * is cpx_blocks_backward_in, launch for launch.                                                                                        */
+ * stats with CPX_DT_F32: CPX_EINVAL, nothing is launched.  src and dst are distinct buffers.                                            */
 int cpx_gather_crops(int dtype, const void *src, int n_subtiles, const int *crops, int n, void *dst, float *stats, void *stream);
 int cpx_scatter_crops(int dtype, const void *src, int n_subtiles, const int *crops, int n, void *dst, void *stream);
-size_t cpx_blocks_train_workspace_bytes_drop(int n_subtiles, int dtype, int n_blocks);
-int cpx_blocks_forward_train_drop(const cpx_net_weights *w, const void *x, int n_subtiles, int first_block, const unsigned char *keep,
-                                  float *head, void *workspace, size_t workspace_bytes, void *stream);
-int cpx_blocks_backward_drop(const cpx_net_weights *w, const float *params, int n_subtiles, int first_block, const unsigned char *keep,
-                             const void *fwd_workspace, size_t fwd_workspace_bytes, const float *dy0, int grad_dtype, int attn_grad_dtype,
-                             float *grads, float *dx_all, float *dx_in, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * t2  training-time augmentation of class-head crops (csrc/cpx_augment.hip)
